@@ -9,6 +9,11 @@ structure, 256x256, ONE population of 256 genomes.  Data: seeded synthetic genom
 (the trained weights are external downloads and fix the size to 160x120).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--weak] [--no-cpu-baseline] [--no-roofline] [--no-parity] [--no-supplementary]
+                    [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller -- the fitness
+vector of the population, float64 -- as DIR/fitness.npy.  The workload is seeded, so two builds run with the same arguments
+can be compared output for output.
 
 --gpus N > 1 without a torch.distributed environment re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one rank per GPU, backend
@@ -406,6 +411,15 @@ def supplementary_shape(name, pop, steps, warmup=1, report_memory=False):
     return out
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float64 stays float64, anything else becomes float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -426,7 +440,11 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the untimed parity legs (C-oracle spot check, whole-population classification)")
     ap.add_argument("--no-supplementary", action="store_true", help="skip the untimed supplementary block (ref160, c2, c4, c5 at a device-batch sample)")
     ap.add_argument("--strict-parity", action="store_true", help="exit with status 3 when the parity legs flag a failure (parity_fail)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the population's fitness, float64) as DIR/fitness.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed region is --steps generations)")
     # RCCL / device-tensor sharing across processes needs dmabuf IPC on these hosts; must be in the environment BEFORE the HIP
     # runtime initialises, whoever launched this process (the respawn path below, the driver's own torchrun, a plain shell)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -501,6 +519,8 @@ def main():
             shard_stats.append(dict(fitness.LAST_SHARD_STATS))
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"fitness": fit})
     multi = None
     if use_dist:
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")

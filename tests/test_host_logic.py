@@ -529,6 +529,8 @@ def test_changed_weight_dict_evicts_its_old_engine(monkeypatch):
         def close(self):
             FakeEngine.closed += 1
 
+    # a cache of its own: engines that earlier tests of the session left behind (the stage-level ones have shorter keys) stay out of it
+    monkeypatch.setattr(fitness, "_engines", {})
     fitness._dict_digests.clear()
     d1 = {"w": np.arange(6, dtype=np.float32)}
     d2 = {"w": np.arange(6, dtype=np.float32)}
