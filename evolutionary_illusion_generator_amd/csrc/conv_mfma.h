@@ -114,7 +114,8 @@ struct ConvArgs {
     float* E;           // [B][2C][H/2][W/2]
     // EPI_CONVP
     float* Pout;        // [B][C][H][W]
-    const uint8_t* img; // layer 0 only: next input frame (uint8 [B][C][H][W]) or nullptr = feed the prediction back
+    const uint8_t* img; // layer 0 only: next input frame (uint8, image b at img + b * img_bstride, [C][H][W]) or nullptr = feed the prediction back
+    long long img_bstride;  // elements between two images of img
     float* E0;          // layer 0 only: error units for the NEXT step, or nullptr
     uint8_t* frame;     // layer 0 only: quantised prediction out, or nullptr
     long long frame_bstride;
@@ -986,7 +987,7 @@ conv3x3_mfma(const ConvArgs a)
                     if (a.frame) a.frame[(size_t)eb * a.frame_bstride + (size_t)ch * HW + pix + j] = (uint8_t)(int)(v * 255.0f);
                     if (a.E0) {
                         float x;
-                        if (a.img) x = (float)a.img[base + pix + j] / 255.0f;
+                        if (a.img) x = (float)a.img[(size_t)eb * a.img_bstride + (size_t)ch * HW + pix + j] / 255.0f;
                         else if (a.requant) x = (float)(uint8_t)(int)(v * 255.0f) / 255.0f;
                         else x = v;
                         const size_t e = ((size_t)eb * 2 * a.Cout + ch) * HW + pix + j;
@@ -1046,7 +1047,7 @@ __global__ void __launch_bounds__(P0_TX * P0_TY) convp0_direct_kernel(const floa
         if (a.frame) a.frame[(size_t)b * a.frame_bstride + (size_t)o * HW + pix] = (uint8_t)(int)(v * 255.0f);
         if (a.E0) {
             float x;
-            if (a.img) x = (float)a.img[base + pix] / 255.0f;
+            if (a.img) x = (float)a.img[(size_t)b * a.img_bstride + (size_t)o * HW + pix] / 255.0f;
             else if (a.requant) x = (float)(uint8_t)(int)(v * 255.0f) / 255.0f;
             else x = v;
             const size_t e = ((size_t)b * 2 * C + o) * HW + pix;
@@ -1128,16 +1129,36 @@ __global__ void __launch_bounds__(L0_TX * L0_TY) lstm0_direct_kernel(const float
 }
 
 #ifdef EIG_ENGINE_UNIT   // (non-template kernels: defined in the engine's translation unit only -- this header is included by three)
-// E_0 for the first step: P_0 = 0  ->  E = [relu(x), relu(-x)] = [x, 0]
-__global__ void e0_init_kernel(const uint8_t* img, float* E0, int C, int HW, int B)
+// E_0 for the first step: P_0 = 0  ->  E = [relu(x), relu(-x)] = [x, 0].  Image b at img + b * img_bstride (elements).
+__global__ void e0_init_kernel(const uint8_t* img, long long img_bstride, float* E0, int C, int HW, int B)
 {
     const size_t n = (size_t)B * C * HW;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const size_t b = i / ((size_t)C * HW);
         const size_t r = i - b * (size_t)C * HW;
-        const float x = (float)img[i] / 255.0f;
+        const float x = (float)img[b * img_bstride + r] / 255.0f;
         E0[b * 2 * C * HW + r] = relu_f(x - 0.0f);
         E0[b * 2 * C * HW + (size_t)C * HW + r] = relu_f(0.0f - x);
+    }
+}
+
+// E_0 for the first step of a call that continues from kept state: P_0 is the prediction of the previous call's last step,
+// x the first input (uint8 image b at img + b * img_bstride) or, when img is nullptr, P_0 fed back (requant: through uint8).
+// The operations and their order are those of the ConvP_0 epilogue (EPI_CONVP, convp0_direct_kernel) that computes E_0
+// inside one call, so a sequence split over several calls gives the bits of one call.
+__global__ void e0_resume_kernel(const float* P0, const uint8_t* img, long long img_bstride, int requant, float* E0, int C, int HW, int B)
+{
+    const size_t n = (size_t)B * C * HW;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / ((size_t)C * HW);
+        const size_t r = i - b * (size_t)C * HW;
+        const float v = P0[i];
+        float x;
+        if (img) x = (float)img[b * img_bstride + r] / 255.0f;
+        else if (requant) x = (float)(uint8_t)(int)(v * 255.0f) / 255.0f;
+        else x = v;
+        E0[b * 2 * C * HW + r] = relu_f(x - v);
+        E0[b * 2 * C * HW + (size_t)C * HW + r] = relu_f(v - x);
     }
 }
 

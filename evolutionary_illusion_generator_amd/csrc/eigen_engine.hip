@@ -131,6 +131,7 @@ struct eigen_engine {
     bool profile_convs = false;
     double ms[6] = {0, 0, 0, 0, 0, 0};
     int hflip = 0;  // which h buffer holds the current R
+    int seq_batch = 0;  // batch of the state the last eigen_prednet_sequence left (0: none; eigen_prednet_rollout overwrites it)
     // ConvP_l (l > 0) is read by nobody until ConvA_l of the NEXT step: forked onto a side stream it can fill the CUs the last round of the ConvLSTM below it leaves idle
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join[EIGEN_MAX_LAYERS] = {nullptr};
@@ -1045,31 +1046,42 @@ int eigen_eval_cppn_nodes(eigen_engine* e, const eigen_genome_batch* g, double* 
     return render_cppn_impl(e, g, 1, 3, nullptr, d_nodes, stream);
 }
 
-int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t n_steps, int32_t first_out_step,
-                          uint8_t* d_frames, void* stream)
+}  // extern "C"
+
+// What one roll-out runs (eigen_prednet_rollout, eigen_prednet_sequence).  The input of step t < n_in is the uint8 image
+// in + b * in_bstride + t * in_tstride (elements) of state slot b; every later step is fed the previous prediction (cfg.requant_feedback).
+struct RollPlan {
+    const uint8_t* in;
+    long long in_bstride, in_tstride;
+    int batch, n_in, n_steps, first_out;
+    uint8_t* out;     // [batch][n_steps - first_out][C0][H][W]
+    bool reset;       // start from reset_state(); otherwise from the state the previous roll-out of the same batch left
+    bool keep_state;  // leave a state the next roll-out can continue from: the last step also runs ConvP_l (l > 0), on the caller's stream
+};
+
+static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
 {
-    if (!e || !d_images || !d_frames) return fail(EIGEN_ERR_INVALID, "null argument");
-    if (!e->have_weights) return fail(EIGEN_ERR_STATE, "eigen_set_prednet_weights has not been called");
-    if (batch < 1 || batch > e->B) return fail(EIGEN_ERR_CAPACITY, "batch %d exceeds max_batch %d", batch, e->B);
-    if (n_steps < 1 || n_steps > e->cfg.n_repeat + e->cfg.n_ext) return fail(EIGEN_ERR_INVALID, "n_steps %d out of range", n_steps);
-    if (first_out_step < 0 || first_out_step >= n_steps) return fail(EIGEN_ERR_INVALID, "first_out_step %d out of range", first_out_step);
-    HIPCHK(hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
     const int L = e->L;
     const size_t HW = (size_t)e->H * e->W;
+    const int batch = p.batch, n_steps = p.n_steps, first_out_step = p.first_out;
     const int n_out = n_steps - first_out_step;
-    for (int l = 0; l < L; ++l) {  // reset_state()
-        Layer& y = e->layer[l];
-        const size_t n = (size_t)batch * y.C * y.H * y.W * sizeof(float);
-        HIPCHK(hipMemsetAsync(y.h[0], 0, n, st));
-        HIPCHK(hipMemsetAsync(y.c, 0, n, st));
-        HIPCHK(hipMemsetAsync(y.P, 0, n, st));
+    if (p.reset) {
+        for (int l = 0; l < L; ++l) {  // reset_state()
+            Layer& y = e->layer[l];
+            const size_t n = (size_t)batch * y.C * y.H * y.W * sizeof(float);
+            HIPCHK(hipMemsetAsync(y.h[0], 0, n, st));
+            HIPCHK(hipMemsetAsync(y.c, 0, n, st));
+            HIPCHK(hipMemsetAsync(y.P, 0, n, st));
+        }
     }
-    int cur = 0;  // h[cur] holds the state of the previous step
+    int cur = p.reset ? 0 : e->hflip;  // h[cur] holds the state of the previous step
     // (One stream: the device is busy 99.9 % of a generation and the step's dependency chain is serial.  Round 3 / 4 measured a side stream for the off-chain
     // ConvP_l and two half-populations on two streams -- byte-identical, slower or equal at every shape: profiles/r03_b_ab_w8.txt, r04_b_ab_pipe2.txt; removed in round 5.)
     static const bool skip_zero_sources = !(getenv("EIGEN_NO_T0") && atoi(getenv("EIGEN_NO_T0")));  // A/B measurements only
-    hipLaunchKernelGGL(e0_init_kernel, dim3(1024), dim3(256), 0, st, d_images, e->layer[0].E, e->C0, (int)HW, batch);
+    if (p.reset) hipLaunchKernelGGL(e0_init_kernel, dim3(1024), dim3(256), 0, st, p.in, p.in_bstride, e->layer[0].E, e->C0, (int)HW, batch);
+    else  // E_0 of the first step from the kept P_0 and the first input (the epilogue's arithmetic: e0_resume_kernel)
+        hipLaunchKernelGGL(e0_resume_kernel, dim3(1024), dim3(256), 0, st, (const float*)e->layer[0].P, p.n_in > 0 ? p.in : nullptr, p.in_bstride,
+                           e->cfg.requant_feedback, e->layer[0].E, e->C0, (int)HW, batch);
     HIPCHK(hipGetLastError());
     // ConvP_l (l > 0) on a side stream: pays where the launches are a fraction of a round of the chip -- configs[0] (pop 10 at 64 x 64: 10 to 40 blocks per launch) +7.5 %;
     // neutral at configs[1], -0.7 % at 160 x 120 colour pop 50, -2 % at the headline (profiles/r06_q_side_stream_ab.txt), as in round 3.  Hence: only while the layer-1 maps of
@@ -1080,6 +1092,8 @@ int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batc
     // One PredNet step of genomes [b0, b0 + nb) on stream s; raw4: that range's partial-chain scratch.
     auto run_step = [&](int t, int b0, int nb, hipStream_t s, float* raw4) -> int {
         auto off = [&](float* p, const Layer& y, int mult = 1) { return p + (size_t)b0 * mult * y.C * y.H * y.W; };
+        // the step-0 operators skip the sources that are zero after reset_state(): never on a kept state
+        const bool t0 = (t == 0 && p.reset && skip_zero_sources);
         // bottom-up: E_l from E_{l-1} and the previous prediction P_l
         for (int l = 1; l < L; ++l) {
             Layer& y = e->layer[l];
@@ -1087,8 +1101,9 @@ int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batc
             memset(&a, 0, sizeof(a));
             a.src[0].ptr = off(e->layer[l - 1].E, e->layer[l - 1], 2);
             a.bias = y.biasA; a.P = off(y.P, y); a.E = off(y.E, y, 2);
-            if (side_on && t > 0) HIPCHK(hipStreamWaitEvent(s, e->ev_join[l], 0));   // P_l of the previous step came from the side stream
-            HIPCHK(launch_conv(e, (t == 0 && skip_zero_sources) ? y.convA_t0 : y.convA, a, nb, s));
+            // P_l of the previous step came from the side stream (a call's last step never forks: nothing is pending at its start)
+            if (side_on && t > 0) HIPCHK(hipStreamWaitEvent(s, e->ev_join[l], 0));
+            HIPCHK(launch_conv(e, t0 ? y.convA_t0 : y.convA, a, nb, s));
         }
         // top-down: R_l, then P_l
         for (int l = L - 1; l >= 0; --l) {
@@ -1109,29 +1124,30 @@ int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batc
                     a.acc_init = raw4;
                 }
                 a.src[k++].ptr = off(y.E, y, 2);
-                const bool t0 = (t == 0 && skip_zero_sources);
                 if (!t0) a.src[k++].ptr = off(y.h[cur], y);
                 a.bias = y.bias_lstm; a.c_state = off(y.c, y); a.h_out = off(y.h[cur ^ 1], y); a.peep = y.peep;
                 HIPCHK(launch_conv(e, t0 ? y.lstm_t0 : y.lstm, a, nb, s));
             }
-            // P_l (l > 0) is only read by ConvA_l of the NEXT step: nothing reads it after the last one
-            if (l == 0 || t + 1 < n_steps) {
+            // P_l (l > 0) is only read by ConvA_l of the NEXT step: nothing in this roll-out reads it after the last one
+            const bool last = t + 1 == n_steps;
+            if (l == 0 || !last || p.keep_state) {
                 ConvArgs a;
                 memset(&a, 0, sizeof(a));
                 a.src[0].ptr = off(y.h[cur ^ 1], y);
                 a.bias = y.biasP; a.Pout = off(y.P, y); a.clip = (l == 0) ? 1 : 0;
                 if (l == 0) {
-                    if (t + 1 < n_steps) {  // error units of the next step
+                    if (!last) {  // error units of the next step
                         a.E0 = off(y.E, y, 2);
-                        a.img = (t + 1 < e->cfg.n_repeat) ? d_images + (size_t)b0 * e->C0 * HW : nullptr;
+                        a.img = (t + 1 < p.n_in) ? p.in + (size_t)b0 * p.in_bstride + (size_t)(t + 1) * p.in_tstride : nullptr;
+                        a.img_bstride = p.in_bstride;
                         a.requant = e->cfg.requant_feedback;
                     }
                     if (t >= first_out_step) {
                         a.frame_bstride = (long long)n_out * e->C0 * HW;
-                        a.frame = d_frames + (size_t)b0 * a.frame_bstride + (size_t)(t - first_out_step) * e->C0 * HW;
+                        a.frame = p.out + (size_t)b0 * a.frame_bstride + (size_t)(t - first_out_step) * e->C0 * HW;
                     }
                 }
-                if (side_on && l > 0) {   // fork: behind the ConvLSTM that produced R_l, beside everything that follows on the main stream
+                if (side_on && l > 0 && !last) {   // fork: behind the ConvLSTM that produced R_l, beside everything that follows on the main stream
                     HIPCHK(hipEventRecord(e->ev_fork, s));
                     HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
                     HIPCHK(launch_conv(e, y.convP, a, nb, e->side));
@@ -1148,6 +1164,53 @@ int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batc
         cur ^= 1;
     }
     e->hflip = cur;
+    return EIGEN_OK;
+}
+
+extern "C" {
+
+int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t n_steps, int32_t first_out_step,
+                          uint8_t* d_frames, void* stream)
+{
+    if (!e || !d_images || !d_frames) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (!e->have_weights) return fail(EIGEN_ERR_STATE, "eigen_set_prednet_weights has not been called");
+    if (batch < 1 || batch > e->B) return fail(EIGEN_ERR_CAPACITY, "batch %d exceeds max_batch %d", batch, e->B);
+    if (n_steps < 1 || n_steps > e->cfg.n_repeat + e->cfg.n_ext) return fail(EIGEN_ERR_INVALID, "n_steps %d out of range", n_steps);
+    if (first_out_step < 0 || first_out_step >= n_steps) return fail(EIGEN_ERR_INVALID, "first_out_step %d out of range", first_out_step);
+    HIPCHK(hipSetDevice(e->cfg.device));
+    e->seq_batch = 0;  // the layer state is overwritten: no eigen_prednet_sequence call may continue from it
+    RollPlan p;
+    p.in = d_images; p.in_bstride = (long long)e->C0 * e->H * e->W; p.in_tstride = 0;  // one still image per genome
+    p.batch = batch; p.n_in = std::min(e->cfg.n_repeat, (int)n_steps); p.n_steps = n_steps; p.first_out = first_out_step; p.out = d_frames;
+    p.reset = true; p.keep_state = false;
+    return prednet_run(e, p, (hipStream_t)stream);
+}
+
+int eigen_prednet_sequence(eigen_engine* e, const uint8_t* d_in, int64_t in_bstride, int32_t batch, int32_t n_in, int32_t n_ext,
+                           int32_t reset, int32_t first_out_step, uint8_t* d_out, void* stream)
+{
+    if (!e || !d_out || (n_in > 0 && !d_in)) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (!e->have_weights) return fail(EIGEN_ERR_STATE, "eigen_set_prednet_weights has not been called");
+    if (batch < 1 || batch > e->B) return fail(EIGEN_ERR_CAPACITY, "batch %d exceeds max_batch %d", batch, e->B);
+    if (n_in < 0 || n_ext < 0) return fail(EIGEN_ERR_INVALID, "n_in %d and n_ext %d must be >= 0", n_in, n_ext);
+    if (reset && n_in == 0) return fail(EIGEN_ERR_INVALID, "a call that resets the state needs at least one input frame (n_in = 0)");
+    if (in_bstride < 0) return fail(EIGEN_ERR_INVALID, "in_bstride %lld < 0", (long long)in_bstride);
+    const long long n_steps = (long long)n_in + n_ext;
+    if (n_steps < 1 || n_steps > INT32_MAX) return fail(EIGEN_ERR_INVALID, "n_in + n_ext = %lld steps out of range", n_steps);
+    if (first_out_step < 0 || first_out_step >= n_steps) return fail(EIGEN_ERR_INVALID, "first_out_step %d out of range (0..%lld)", first_out_step, n_steps - 1);
+    if (!reset && e->seq_batch != batch) {
+        if (e->seq_batch == 0) return fail(EIGEN_ERR_STATE, "reset = 0: no state to continue from (none kept yet, or a roll-out / evaluation overwrote it)");
+        return fail(EIGEN_ERR_STATE, "reset = 0: the kept state is of a batch of %d, not %d", e->seq_batch, batch);
+    }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    e->seq_batch = 0;  // valid again only once every step of this call has been enqueued
+    RollPlan p;
+    p.in = d_in; p.in_bstride = in_bstride; p.in_tstride = (long long)e->C0 * e->H * e->W;
+    p.batch = batch; p.n_in = n_in; p.n_steps = (int)n_steps; p.first_out = first_out_step; p.out = d_out;
+    p.reset = reset != 0; p.keep_state = true;
+    const int rc = prednet_run(e, p, (hipStream_t)stream);
+    if (rc) return rc;
+    e->seq_batch = batch;
     return EIGEN_OK;
 }
 

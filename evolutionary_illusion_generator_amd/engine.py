@@ -17,7 +17,7 @@ MAX_LAYERS = 8
 PAIR_POPULATION, PAIR_SINGLE = 0, 1
 
 EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eigen_last_error", "eigen_config_defaults", "eigen_create", "eigen_destroy",
-           "eigen_set_prednet_weights", "eigen_set_grid", "eigen_render_cppn", "eigen_eval_cppn_nodes", "eigen_prednet_rollout", "eigen_flow",
+           "eigen_set_prednet_weights", "eigen_set_grid", "eigen_render_cppn", "eigen_eval_cppn_nodes", "eigen_prednet_rollout", "eigen_prednet_sequence", "eigen_flow",
            "eigen_score", "eigen_eval_population", "eigen_eval_images", "eigen_test_conv", "eigen_time_conv", "eigen_test_det_math",
            "eigen_get_timings", "eigen_conv_profile", "eigen_debug_corners", "eigen_debug_dense_flow", "eigen_prednet_flops_per_step", "eigen_flatten_genomes"]
 
@@ -189,6 +189,35 @@ class Engine:
         self._check_images(d_images, batch)
         _check(self.lib.eigen_prednet_rollout(self._h, _ptr(d_images), ctypes.c_int32(batch), ctypes.c_int32(n_steps),
                                               ctypes.c_int32(first_out_step), _ptr(d_frames), _stream_arg(stream)))
+
+    @staticmethod
+    def _buffer_bytes(buf):
+        """Bytes reachable from the first element of a torch tensor (its storage: a strided view reaches past its own elements) or of a
+        C-contiguous numpy array; None for a raw address."""
+        if isinstance(buf, np.ndarray):
+            return int(buf.nbytes) if buf.flags.c_contiguous else None
+        if hasattr(buf, "untyped_storage"):
+            st = buf.untyped_storage()
+            return int(st.nbytes()) - (int(buf.data_ptr()) - int(st.data_ptr()))
+        return None
+
+    def prednet_sequence(self, d_in, in_bstride, batch, n_in, n_ext, reset, first_out_step, d_out, stream=None):
+        """eigen_prednet_sequence: frame t of sequence b at byte d_in + b * in_bstride + t * C*H*W; predictions of the steps
+        from first_out_step on into d_out [batch][n_in + n_ext - first_out_step][C][H][W].  reset=False continues from the state
+        the previous call with the same batch left."""
+        frame = self.c_dim * self.height * self.width
+        if 1 <= int(batch) <= self.max_batch and int(n_in) >= 0 and int(n_ext) >= 0 and 0 <= int(first_out_step) < int(n_in) + int(n_ext):
+            # the C side reads and writes through raw pointers: refuse buffers smaller than what it touches
+            checks = [(d_out, int(batch) * (int(n_in) + int(n_ext) - int(first_out_step)) * frame, "output")]
+            if int(n_in) > 0 and d_in is not None:
+                checks.append((d_in, (int(batch) - 1) * int(in_bstride) + int(n_in) * frame, "input"))
+            for buf, need, what in checks:
+                have = self._buffer_bytes(buf)
+                if have is not None and have < need:
+                    raise ValueError("%s buffer holds %d bytes, %d are needed" % (what, have, need))
+        _check(self.lib.eigen_prednet_sequence(self._h, _ptr(d_in), ctypes.c_int64(int(in_bstride)), ctypes.c_int32(batch), ctypes.c_int32(n_in),
+                                               ctypes.c_int32(n_ext), ctypes.c_int32(int(reset)), ctypes.c_int32(first_out_step), _ptr(d_out),
+                                               _stream_arg(stream)))
 
     def flow(self, d_img0, stride0, d_img1, stride1, batch, d_vectors, d_counts, stream=None):
         _check(self.lib.eigen_flow(self._h, _ptr(d_img0), ctypes.c_int64(stride0), _ptr(d_img1), ctypes.c_int64(stride1),

@@ -652,3 +652,152 @@ def flow_vectors(img0, img1, method="lk"):
     eng.flow(d0, a.size, d1, b.size, 1, vec, cnt)
     torch.cuda.synchronize()
     return vec.cpu().numpy()[0, :int(cnt.cpu().numpy()[0])]
+
+
+# ----------------------------------------------------------------------------------------------- frame sequences
+# PredNet over sequences of DIFFERENT frames (eigen_prednet_sequence).  What is pinned: every step runs the arithmetic of the
+# constant-image roll-out of oracle/eig_oracle.c -- a sequence whose frames are the oracle's own requantised predictions gives the
+# oracle's frames byte for byte, and a sequence split over several calls gives the bytes of one call (tests/test_gpu_sequence.py).
+# What is NOT pinned: chainer_prednet's own handling of a sequence_list (its reset period, which frame is shown first, how the
+# extension is seeded) -- the reference never runs one, and nothing here has been checked against it.
+def _check_sequence_frames(frames, channels, w, h):
+    shape = tuple(frames.shape)
+    if len(shape) != 5 or shape[2:] != (channels[0], h, w) or shape[1] < 1:
+        raise ValueError("frames must be uint8 [n, T >= 1, %d, %d, %d] (n, T, C, H, W), got %s" % (channels[0], h, w, shape))
+
+
+def prednet_sequence_predictions(frames, model_name, channels, w, h, n_ext=0):
+    """Quantised predictions of PredNet run over frame sequences: frames uint8 [n, T, C, H, W] -> uint8 [n, T + n_ext, C, H, W],
+    where output t is the prediction after step t (input frame t for t < T; the last n_ext steps are fed their own prediction,
+    as the extension frames of test_prednet).  Every sequence starts from a reset state; n is split into batches of the
+    engine's max_batch, each an independent set of sequences."""
+    import torch
+    channels = [int(c) for c in channels]
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    _check_sequence_frames(frames, channels, w, h)
+    if n_ext < 0:
+        raise ValueError("n_ext must be >= 0")
+    n, T = frames.shape[:2]
+    frame = int(np.prod(frames.shape[2:]))
+    eng = get_engine(model_name, w, h, channels)
+    out = np.empty((n, T + n_ext) + frames.shape[2:], dtype=np.uint8)
+    for i in range(0, n, eng.max_batch):
+        chunk = frames[i:i + eng.max_batch]
+        d = torch.from_numpy(chunk).cuda()
+        fr = torch.empty((len(chunk), T + n_ext) + chunk.shape[2:], dtype=torch.uint8, device="cuda")
+        eng.prednet_sequence(d, T * frame, len(chunk), T, n_ext, True, 0, fr)
+        torch.cuda.synchronize()
+        out[i:i + len(chunk)] = fr.cpu().numpy()
+    return out
+
+
+class PredNetStream:
+    """PredNet state carried across calls, for running a long sequence in pieces: ``feed(frames)`` runs one step per frame
+    (uint8 [batch, t, C, H, W], a numpy array or a CUDA tensor) and returns the t predictions, ``extend(n)`` runs n steps fed
+    their own prediction, ``reset()`` makes the next ``feed`` start from a reset state.  Feeding a sequence in pieces gives the
+    bytes of one ``prednet_sequence_predictions`` call over all of it.
+
+    The stream owns a private engine (not one of the cached engines the fitness functions share), so no other call can
+    overwrite its state; ``close()`` frees its device memory.  Results come back as the type of the last ``feed`` input:
+    numpy arrays, or CUDA tensors enqueued on the current stream (no synchronisation)."""
+
+    def __init__(self, model_name, channels, w, h, batch, requant_feedback=False):
+        self.channels = [int(c) for c in channels]
+        self.w, self.h, self.batch = int(w), int(h), int(batch)
+        self._eng = Engine(self.w, self.h, self.channels, self.batch, device=_local_device(), requant_feedback=requant_feedback)
+        self._eng.set_weights(_resolve_weights(model_name, self.channels, self.w, self.h))
+        self._started = False
+        self._tensor_out = False
+
+    def reset(self):
+        self._started = False
+
+    def close(self):
+        if self._eng is not None:
+            self._eng.close()
+            self._eng = None
+
+    def _engine(self):
+        if self._eng is None:
+            raise EngineError("PredNetStream is closed")
+        return self._eng
+
+    def _run(self, d_in, in_bstride, n_in, n_ext):
+        import torch
+        eng = self._engine()
+        out = torch.empty((self.batch, n_in + n_ext, self.channels[0], self.h, self.w), dtype=torch.uint8, device="cuda")
+        stream = torch.cuda.current_stream() if self._tensor_out else None
+        eng.prednet_sequence(d_in, in_bstride, self.batch, n_in, n_ext, not self._started, 0, out, stream=stream)
+        self._started = True
+        if self._tensor_out:
+            return out
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    def feed(self, frames):
+        import torch
+        _check_sequence_frames(frames, self.channels, self.w, self.h)
+        if frames.shape[0] != self.batch:
+            raise ValueError("this stream runs %d sequences, got %d" % (self.batch, frames.shape[0]))
+        if isinstance(frames, torch.Tensor):
+            if frames.dtype != torch.uint8 or not frames.is_cuda:
+                raise ValueError("frames must be a uint8 CUDA tensor or a numpy array")
+            if not frames[0].is_contiguous():   # (the batch stride is free, each sequence must be dense)
+                frames = frames.contiguous()
+            self._tensor_out = True
+            return self._run(frames, frames.stride(0), frames.shape[1], 0)
+        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        self._tensor_out = False
+        return self._run(torch.from_numpy(a).cuda(), int(np.prod(a.shape[1:])), a.shape[1], 0)
+
+    def extend(self, n):
+        if not self._started:
+            raise ValueError("extend() continues a sequence: feed() at least one frame first")
+        if int(n) < 1:
+            raise ValueError("n must be >= 1")
+        return self._run(None, 0, 0, int(n))
+
+
+def _flow_batch_engine(w, h, c_dim, method, n_pairs):
+    """Flow-only engine sized for up to n_pairs pairs per call (a power of two <= DEFAULT_MAX_BATCH, so few sizes are ever built)."""
+    mb = 1
+    while mb < min(n_pairs, DEFAULT_MAX_BATCH):
+        mb *= 2
+    key = ("flow_batch", _local_device(), w, h, c_dim, method, mb)
+    eng = _engines.get(key)
+    if eng is None:
+        eng = Engine(w, h, [c_dim], mb, device=_local_device(), **({} if method == "lk" else {"flow": method}))
+        _engines[key] = eng
+    return eng
+
+
+def sequence_flow(pred_frames, method="lk"):
+    """Flow vectors between consecutive frames of every sequence: pred_frames uint8 [n, T, C, H, W] (e.g. the output of
+    prednet_sequence_predictions) -> a list of n lists of T - 1 float32 arrays [k, 4] ([x, y, dx, dy]; entry t: frame t ->
+    frame t + 1), what flow_vectors gives for each pair.  The n*T frames are one flat list on the device; each engine call
+    takes a batch of consecutive pairs (frame i, frame i + 1) with one stride, and the pairs that cross from one sequence
+    to the next are dropped."""
+    import torch
+    a = np.ascontiguousarray(pred_frames, dtype=np.uint8)
+    if a.ndim != 5:
+        raise ValueError("pred_frames must be uint8 [n, T, C, H, W], got shape %s" % (a.shape,))
+    n, T, c, h, w = a.shape
+    out = [[] for _ in range(n)]
+    n_pairs = n * T - 1
+    if T < 2:
+        return out
+    eng = _flow_batch_engine(w, h, c, method, n_pairs)
+    frame = c * h * w
+    d = torch.from_numpy(a).cuda().reshape(-1)
+    vec = torch.zeros((eng.max_batch, eng.K, 4), dtype=torch.float32, device="cuda")
+    cnt = torch.zeros(eng.max_batch, dtype=torch.int32, device="cuda")
+    for i0 in range(0, n_pairs, eng.max_batch):
+        nb = min(eng.max_batch, n_pairs - i0)
+        eng.flow(d[i0 * frame:], frame, d[(i0 + 1) * frame:], frame, nb, vec, cnt)
+        torch.cuda.synchronize()
+        v, k = vec[:nb].cpu().numpy(), cnt[:nb].cpu().numpy()
+        for j in range(nb):
+            i = i0 + j
+            if (i + 1) % T:   # pair (i, i + 1) inside sequence i // T
+                out[i // T].append(v[j, :int(k[j])].copy())
+    return out

@@ -158,6 +158,19 @@ int eigen_eval_cppn_nodes(eigen_engine* e, const eigen_genome_batch* h_genomes, 
 int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t n_steps,
                           int32_t first_out_step, uint8_t* d_frames, void* stream);
 
+/* PredNet over frame sequences: one step per input frame, then n_ext self-fed steps (cfg.requant_feedback, as in
+ * eigen_prednet_rollout).  The arithmetic of every step is the constant-image roll-out's; the first input is frame 0.
+ *   d_in: uint8 frames, frame t of sequence b at d_in + b * in_bstride + t * C*H*W (bytes); may be NULL when n_in == 0.
+ *   reset = 1: start from reset_state() (needs n_in >= 1).  reset = 0: continue from the state the previous
+ *   eigen_prednet_sequence call on this handle left, which must have had the same batch; a roll-out or evaluation on the
+ *   handle (eigen_prednet_rollout, eigen_eval_images, eigen_eval_population) discards that state (EIGEN_ERR_STATE).
+ *   A sequence run in pieces gives the bytes of one call over the whole sequence.
+ *   The quantised prediction of every step t >= first_out_step of THIS call (t counted from 0 in each call) is written
+ *   to d_out[b][t - first_out_step] (uint8 [batch][n_in + n_ext - first_out_step][C][H][W]).
+ * The number of steps is not bounded by cfg.n_repeat + cfg.n_ext. */
+int eigen_prednet_sequence(eigen_engine* e, const uint8_t* d_in, int64_t in_bstride, int32_t batch, int32_t n_in,
+                           int32_t n_ext, int32_t reset, int32_t first_out_step, uint8_t* d_out, void* stream);
+
 /* Replaces lucas_kanade (generate_illusion.py:549-550, fitness_calculator.py:498) for a batch of pairs.
  * d_img0/d_img1: uint8 planar images, image b at d_imgX + b * strideX (bytes).
  * d_vectors: float [batch][lk_max_corners][4] rows [x, y, dx, dy]; d_counts: int32 [batch]. */
