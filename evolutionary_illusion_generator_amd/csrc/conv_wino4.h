@@ -20,8 +20,8 @@
 // with the 40-float plane rows the sixteen 16-byte patch reads of a lane group fall on sixteen different bank slots) x NI 16-column N-tiles; TWELVE waves (three per
 // SIMD, <= 168 VGPRs), one block per CU.  No transformed-input buffer --
 //   wave (rg, xi), xi = 0..5, multiplies region rg for the six positions (xi, nu = 0..5): 6 NI accumulator tiles; it BUILDS its A operands itself: lane (q, col) holds
-//     channel q of the K-block for tile col, reads the three or four patch rows that row xi of B^T d needs (per row three aligned 16-byte reads out of the
-//     channel's plane: conflict-free, where 4-byte reads of the two end columns were 8-way conflicted and cost the first version 25 %), 12-18 operations for the
+//     channel q of the K-block for tile col, reads the three or four patch rows that row xi of B^T d needs (per row an aligned 8-, 16- and 8-byte read out of the
+//     channel's plane: 4 LDS cycles each, where 4-byte reads of the two end columns were 8-way conflicted and cost the first version 25 %), 12-18 operations for the
 //     row, 12 for the column pass;
 //   K-block = FOUR channels (one MFMA k-step): 6 NI MFMAs per wave in six chunks with the operand read of the next chunk, staging in slices between the chunks;
 //   LDS (156 KB): plane ring 3 x 4 x [18 rows][40 floats] (one DMA instruction per wave and K-block) and U ring 3 x 36 KB ([36 pos][4 ch][16 cols][NI]; the packed
@@ -195,7 +195,9 @@ __global__ void __launch_bounds__((HALF && !NSPLIT) ? W4_THREADS / 2 : W4_THREAD
     constexpr unsigned W4_POSB = 4 * 16 * NI * 4;   // bytes per position of a packed K-block
     // One N-block of the walk, as a lambda called from the loop below.  (Written as the loop's body the same code kept 7 VGPRs in scratch -- K-loop lane invariants reloaded
     // inside the K loop -- and 30 SGPRs in VGPR lanes; as a lambda: 158 VGPRs, nothing in scratch.  Called three times with compile-time indices, i.e. the walk as
-    // straight-line code: 157 VGPRs and 0.6 % SLOWER, profiles/r06_m_walk_clean_ab.txt.)
+    // straight-line code: 157 VGPRs and 0.6 % SLOWER, profiles/r06_m_walk_clean_ab.txt.)  The half blocks and the tall shape left the ConvLSTM instantiation at
+    // 168 VGPRs with 24 bytes of scratch (a K-run-boundary reload and spills in the finishing phase); the 8-byte reads of the end columns of a patch row (read_rows) brought it
+    // back to 166 VGPRs, nothing in scratch, 30 SGPRs in VGPR lanes (tests/test_isa_stats.py holds the headline instantiations to that).
     auto walk_body = [&](const int it) __attribute__((always_inline)) {
     const int nblk = nb0 + it;
     // An opaque zero: the scalars of a phase are derived from the wave index, the K-block counts and the tile coordinates offset by it INSIDE the walk, so that the
@@ -454,9 +456,16 @@ __global__ void __launch_bounds__((HALF && !NSPLIT) ? W4_THREADS / 2 : W4_THREAD
                     const float s0 = pl[0], s1_ = pl[1], s2 = pl[2], s3 = pl[3];
                     pr[j][0] = s0; pr[j][1] = s1_; pr[j][2] = s1_; pr[j][3] = s2; pr[j][4] = s2; pr[j][5] = s3;
                 } else {
-                    const f32x4* const pl = reinterpret_cast<const f32x4*>(pbase_n + rso + w4_rowidx(XI, k) * W4_ROW);
-                    const f32x4 c0 = pl[0], c1 = pl[1], c2 = pl[2];   // three aligned 16-byte reads: floats 0 .. 11 of which 3 .. 8 are the patch row
-                    pr[j][0] = c0[3]; pr[j][1] = c1[0]; pr[j][2] = c1[1]; pr[j][3] = c1[2]; pr[j][4] = c1[3]; pr[j][5] = c2[0];
+                    const float* const pl = pbase_n + rso + w4_rowidx(XI, k) * W4_ROW;
+                    // floats 2, 3 | 4 .. 7 | 8, 9 (aligned 8- / 16- / 8-byte reads) of which 3 .. 8 are the patch row: two VGPRs fewer per end column than a 16-byte
+                    // read -- the VGPRs that took the wide kernel to 0 bytes of scratch.  By the LDS banking of MI355X (not measured apart): an 8-byte read is two
+                    // 32-lane groups on 64 banks, 2-way here (channels q and q + 1 on the same banks), 4 cycles like the 16-byte read it replaces; volatile, because as
+                    // plain loads the compiler pairs the two into one ds_read2_b64, whose 16-lane groups on 32 banks would be 2-way conflicted (16 cycles for the pair, 8 as two reads).
+                    // (volatile also keeps these reads in program order among themselves: an interleave by sched_group_barrier has to take them as they come.)
+                    typedef const volatile __attribute__((address_space(3))) f32x2* lds_f32x2;
+                    const f32x2 c0 = *(lds_f32x2)(pl + 2), c2 = *(lds_f32x2)(pl + 8);
+                    const f32x4 c1 = *reinterpret_cast<const f32x4*>(pl + 4);
+                    pr[j][0] = c0[1]; pr[j][1] = c1[0]; pr[j][2] = c1[1]; pr[j][3] = c1[2]; pr[j][4] = c1[3]; pr[j][5] = c2[0];
                 }
             }
         };

@@ -1075,8 +1075,8 @@ static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
         }
     }
     int cur = p.reset ? 0 : e->hflip;  // h[cur] holds the state of the previous step
-    // (One stream: the device is busy 99.9 % of a generation and the step's dependency chain is serial.  Round 3 / 4 measured a side stream for the off-chain
-    // ConvP_l and two half-populations on two streams -- byte-identical, slower or equal at every shape: profiles/r03_b_ab_w8.txt, r04_b_ab_pipe2.txt; removed in round 5.)
+    // (The step's dependency chain is serial; only ConvP_l (l > 0) may leave it, onto the side stream below, and only for small launches.  Two half-populations on
+    // two streams were byte-identical and slower or equal at every shape: profiles/r04_b_ab_pipe2.txt.)
     static const bool skip_zero_sources = !(getenv("EIGEN_NO_T0") && atoi(getenv("EIGEN_NO_T0")));  // A/B measurements only
     if (p.reset) hipLaunchKernelGGL(e0_init_kernel, dim3(1024), dim3(256), 0, st, p.in, p.in_bstride, e->layer[0].E, e->C0, (int)HW, batch);
     else  // E_0 of the first step from the kept P_0 and the first input (the epilogue's arithmetic: e0_resume_kernel)
