@@ -35,6 +35,12 @@ static int fail(int code, const char* fmt, ...)
     g_err = buf;
     return code;
 }
+// (prednet_train.hip reports its errors through the same thread-local text)
+int eig_set_error(int code, const char* msg)
+{
+    g_err = msg;
+    return code;
+}
 #define HIPCHK(x)                                                                                      \
     do {                                                                                               \
         hipError_t _e = (x);                                                                           \

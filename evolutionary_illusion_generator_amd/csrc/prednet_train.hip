@@ -1,0 +1,488 @@
+// prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
+// layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
+// the kernels of train_kernels.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/eigen_engine.h"
+#include "train_kernels.h"
+
+using namespace eigt;
+
+int eig_set_error(int code, const char* msg);  // eigen_engine.hip: eigen_last_error's text
+
+namespace {
+
+int tfail(int code, const char* fmt, ...)
+{
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return eig_set_error(code, buf);
+}
+
+#define TCHK(x)                                                                                                            \
+    do {                                                                                                                   \
+        hipError_t _e = (x);                                                                                               \
+        if (_e != hipSuccess) return tfail(EIGEN_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(_e)); \
+    } while (0)
+
+constexpr long long SLAB_FLOATS = 16ll << 20;  // split-K slab budget of one wgrad (floats)
+constexpr int WGRAD_WAVES = 2048;              // split-K target: waves of one wgrad launch
+constexpr int LOSS_BLOCKS = 256;
+constexpr int BIAS_SLICES = 64;                // slices of one bias-gradient reduction
+
+// offsets (floats) of one layer's parameters in the flat device table; gate tensors of one source are stacked i, f, c, o
+struct LayerParams {
+    long long aW = -1, ab = -1;   // ConvA (l > 0)
+    long long pW, pb;             // ConvP
+    long long x0, x1 = -1, hW, hb; // ConvLSTM sources (stacked [4C][Cin][3][3]) and h bias [4C]
+    long long peep;               // c_i, c_f, c_o [3][C][H][W]
+};
+
+struct TLayer {
+    int C, H, W, Cb, Ca;          // channels, size, channels of the layer below (Cb) and above (Ca, 0 at the top)
+    long long HW;
+    // tape: [slot][batch][ch][H][W]; E, gates, ZA, dV have max_steps slots, h, c, P have max_steps + 1 (slot 0 = start state)
+    float *E = nullptr, *G = nullptr, *ZA = nullptr, *dV = nullptr, *h = nullptr, *c = nullptr, *P = nullptr;
+    // backward work buffers, one batch each
+    float *dE = nullptr, *dhP = nullptr, *dhc = nullptr, *dc = nullptr, *dPn = nullptr, *dup = nullptr;
+};
+
+}  // namespace
+
+struct eigen_trainer {
+    eigen_trainer_config cfg;
+    int L = 0;
+    TLayer ly[EIGEN_MAX_LAYERS];
+    LayerParams lp[EIGEN_MAX_LAYERS];
+    long long n_params = 0;
+    float *prm = nullptr, *grd = nullptr, *mom = nullptr, *var = nullptr;
+    float* slab = nullptr;
+    long long slab_floats = 0;
+    double *d_part = nullptr, *d_loss = nullptr;
+    long long tape_bytes = 0;
+    bool have_weights = false;
+    int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad call (0: no state kept)
+    int adam_t = 0;
+    std::vector<void*> allocs;
+};
+
+namespace {
+
+// (name -> offset, elements) in the order of weights.tensor_names
+void tensor_table(const eigen_trainer* t, std::vector<std::pair<long long, long long>>& tab)
+{
+    tab.clear();
+    for (int l = 0; l < t->L; ++l) {
+        const TLayer& y = t->ly[l];
+        const LayerParams& p = t->lp[l];
+        const long long C = y.C;
+        if (l > 0) {
+            tab.push_back({p.aW, C * y.Cb * 2 * 9});
+            tab.push_back({p.ab, C});
+        }
+        tab.push_back({p.pW, C * C * 9});
+        tab.push_back({p.pb, C});
+        for (int g = 0; g < 4; ++g) {
+            tab.push_back({p.x0 + g * C * 2 * C * 9, C * 2 * C * 9});
+            if (l < t->L - 1) tab.push_back({p.x1 + g * C * y.Ca * 9, C * y.Ca * 9});
+            tab.push_back({p.hW + g * C * C * 9, C * C * 9});
+            tab.push_back({p.hb + g * C, C});
+        }
+        for (int g = 0; g < 3; ++g) tab.push_back({p.peep + g * C * y.HW, C * y.HW});
+    }
+}
+
+inline unsigned blocks(long long n) { return (unsigned)((n + EW_T - 1) / EW_T); }
+
+TSrc src(const float* p, long long nstride, int cin, int up, const float* w, int wmode)
+{
+    TSrc s;
+    s.p = p; s.w = w; s.nstride = nstride; s.cin = cin; s.up = up; s.wmode = wmode; s.pad_ = 0;
+    return s;
+}
+
+template <int MT>
+void launch_conv_mt(const TConvArgs& a, hipStream_t st)
+{
+    constexpr int NT = 4;
+    const long long P = (long long)a.N * a.H * a.W;
+    dim3 grid((unsigned)((P + 16 * NT - 1) / (16 * NT)), (unsigned)((a.cout + 16 * MT - 1) / (16 * MT)));
+    hipLaunchKernelGGL((tconv3x3_kernel<MT, NT>), grid, dim3(WAVE), 0, st, a);
+}
+
+// 3x3 'same' convolution over up to three summed sources, out [N][cout][H][W] (contiguous samples)
+void conv(hipStream_t st, float* out, int cout, int H, int W, int N, const float* bias, int accumulate, std::initializer_list<TSrc> srcs)
+{
+    TConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nsrc = 0;
+    for (const TSrc& s : srcs) a.s[a.nsrc++] = s;
+    a.out = out; a.out_nstride = (long long)cout * H * W; a.bias = bias;
+    a.cout = cout; a.H = H; a.W = W; a.N = N; a.accumulate = accumulate;
+    if (cout <= 16) launch_conv_mt<1>(a, st);
+    else if (cout <= 32) launch_conv_mt<2>(a, st);
+    else launch_conv_mt<4>(a, st);
+}
+
+template <int MT>
+void launch_wgrad_mt(const TWgradArgs& a, unsigned gx, unsigned gy, hipStream_t st)
+{
+    hipLaunchKernelGGL((twgrad_kernel<MT, 4>), dim3(gx, gy, (unsigned)a.nsplit), dim3(WAVE), 0, st, a);
+}
+
+// dW [cout][cin][3][3] = sum over N samples of dy (x) im2col(x): split-K over fixed pixel ranges, slabs added in order
+void wgrad(eigen_trainer* t, hipStream_t st, float* dW, const float* dy, int cout, int H, int W, int N, const TSrc& x)
+{
+    const long long P = (long long)N * H * W;
+    const long long K = (long long)x.cin * 9;
+    const int MT = cout <= 16 ? 1 : cout <= 32 ? 2 : 4;
+    const unsigned gx = (unsigned)((K + 63) / 64), gy = (unsigned)((cout + 16 * MT - 1) / (16 * MT));
+    long long ns = WGRAD_WAVES / (long long)(gx * gy);
+    ns = std::min<long long>(ns, t->slab_floats / (cout * K));
+    ns = std::min<long long>(ns, (P + 255) / 256);
+    ns = std::max<long long>(ns, 1);
+    long long chunk = (P + ns - 1) / ns;
+    chunk = (chunk + 3) & ~3ll;
+    ns = (P + chunk - 1) / chunk;
+    TWgradArgs a;
+    a.dy = dy; a.dy_nstride = (long long)cout * H * W; a.x = x; a.slab = t->slab;
+    a.cout = cout; a.H = H; a.W = W; a.N = N; a.nsplit = (int)ns; a.chunk = chunk;
+    if (MT == 1) launch_wgrad_mt<1>(a, gx, gy, st);
+    else if (MT == 2) launch_wgrad_mt<2>(a, gx, gy, st);
+    else launch_wgrad_mt<4>(a, gx, gy, st);
+    const long long n = cout * K;
+    hipLaunchKernelGGL(tsum_slabs_kernel, dim3(blocks(n)), dim3(EW_T), 0, st, (const float*)t->slab, (int)ns, n, dW);
+}
+
+// db [C] = sum over N samples and all pixels of dy [N][C][HW]: BIAS_SLICES fixed slices per channel, added in order
+void bias_grad(eigen_trainer* t, hipStream_t st, float* db, const float* dy, int C, long long HW, int N)
+{
+    hipLaunchKernelGGL(tbias_grad_kernel, dim3(C, BIAS_SLICES), dim3(EW_T), 0, st, dy, C, (int)HW, N, t->slab);
+    hipLaunchKernelGGL(tsum_slabs_kernel, dim3(blocks(C)), dim3(EW_T), 0, st, (const float*)t->slab, BIAS_SLICES, (long long)C, db);
+}
+
+}  // namespace
+
+extern "C" {
+
+int eigen_trainer_destroy(eigen_trainer* t)
+{
+    if (!t) return EIGEN_OK;
+    (void)hipSetDevice(t->cfg.device);
+    for (void* p : t->allocs) (void)hipFree(p);
+    delete t;
+    return EIGEN_OK;
+}
+
+int eigen_trainer_create(const eigen_trainer_config* cfg, eigen_trainer** out)
+{
+    if (!cfg || !out) return tfail(EIGEN_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const int L = cfg->n_layers;
+    if (L < 1 || L > EIGEN_MAX_LAYERS) return tfail(EIGEN_ERR_INVALID, "n_layers %d out of range", L);
+    if (cfg->width < 1 || cfg->height < 1 || cfg->width % (1 << (L - 1)) || cfg->height % (1 << (L - 1)))
+        return tfail(EIGEN_ERR_INVALID, "image %dx%d must be divisible by 2^(layers-1)=%d", cfg->width, cfg->height, 1 << (L - 1));
+    if (cfg->channels[0] != 1 && cfg->channels[0] != 3) return tfail(EIGEN_ERR_INVALID, "channels[0] must be 1 or 3");
+    for (int l = 0; l < L; ++l) if (cfg->channels[l] < 1) return tfail(EIGEN_ERR_INVALID, "channels[%d] < 1", l);
+    if (cfg->max_batch < 1 || cfg->max_steps < 2) return tfail(EIGEN_ERR_INVALID, "max_batch >= 1 and max_steps >= 2 required");
+    TCHK(hipSetDevice(cfg->device));
+    hipDeviceProp_t prop;
+    TCHK(hipGetDeviceProperties(&prop, cfg->device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return tfail(EIGEN_ERR_INVALID, "device %d is %s; this library is built for gfx950 (MI355X) only", cfg->device, prop.gcnArchName);
+
+    eigen_trainer* t = new eigen_trainer();
+    t->cfg = *cfg;
+    t->L = L;
+    const long long B = cfg->max_batch, T = cfg->max_steps;
+    long long off = 0, slab = 0;
+    for (int l = 0; l < L; ++l) {
+        TLayer& y = t->ly[l];
+        y.C = cfg->channels[l]; y.H = cfg->height >> l; y.W = cfg->width >> l; y.HW = (long long)y.H * y.W;
+        y.Cb = l > 0 ? cfg->channels[l - 1] : 0;
+        y.Ca = l < L - 1 ? cfg->channels[l + 1] : 0;
+        const long long C = y.C;
+        LayerParams& p = t->lp[l];
+        if (l > 0) { p.aW = off; off += C * 2 * y.Cb * 9; p.ab = off; off += C; slab = std::max(slab, C * 2 * y.Cb * 9); }
+        p.pW = off; off += C * C * 9; p.pb = off; off += C;
+        p.x0 = off; off += 4 * C * 2 * C * 9;
+        if (l < L - 1) { p.x1 = off; off += 4 * C * y.Ca * 9; slab = std::max(slab, 4 * C * y.Ca * 9); }
+        p.hW = off; off += 4 * C * C * 9;
+        p.hb = off; off += 4 * C;
+        p.peep = off; off += 3 * C * y.HW;
+        slab = std::max(slab, std::max(4 * C * 2 * C * 9, BIAS_SLICES * 4 * C));
+    }
+    t->slab_floats = std::max(slab, SLAB_FLOATS);
+    t->n_params = off;
+    std::vector<std::pair<void**, size_t>> want;
+    auto add = [&](void** p, long long bytes) { want.push_back({p, (size_t)bytes}); };
+    auto tape = [&](float** p, long long floats) { add((void**)p, floats * 4); t->tape_bytes += floats * 4; };
+    for (void** p : {(void**)&t->prm, (void**)&t->grd, (void**)&t->mom, (void**)&t->var}) add(p, off * 4);
+    add((void**)&t->slab, t->slab_floats * 4);
+    add((void**)&t->d_part, LOSS_BLOCKS * 8);
+    add((void**)&t->d_loss, 8);
+    for (int l = 0; l < L; ++l) {
+        TLayer& y = t->ly[l];
+        const long long CHW = y.C * y.HW;
+        tape(&y.E, T * B * 2 * CHW);
+        tape(&y.G, T * B * 4 * CHW);
+        tape(&y.dV, T * B * CHW);
+        if (l > 0) tape(&y.ZA, T * B * 4 * CHW);
+        tape(&y.h, (T + 1) * B * CHW);
+        tape(&y.c, (T + 1) * B * CHW);
+        tape(&y.P, (T + 1) * B * CHW);
+        add((void**)&y.dE, B * 2 * CHW * 4);
+        add((void**)&y.dhP, B * CHW * 4);
+        add((void**)&y.dhc, B * CHW * 4);
+        add((void**)&y.dc, B * CHW * 4);
+        add((void**)&y.dPn, B * CHW * 4);
+        if (l > 0) add((void**)&y.dup, B * 4 * CHW * 4);  // [B][C_l][H_{l-1}][W_{l-1}]
+    }
+    for (auto& w : want) {
+        hipError_t e = hipMalloc(w.first, w.second);
+        if (e != hipSuccess) {
+            eigen_trainer_destroy(t);
+            return tfail(EIGEN_ERR_HIP, "hipMalloc(%zu): %s", w.second, hipGetErrorString(e));
+        }
+        t->allocs.push_back(*w.first);
+    }
+    hipError_t e = hipMemset(t->grd, 0, off * 4);
+    if (e == hipSuccess) e = hipMemset(t->prm, 0, off * 4);
+    if (e != hipSuccess) {
+        eigen_trainer_destroy(t);
+        return tfail(EIGEN_ERR_HIP, "hipMemset: %s", hipGetErrorString(e));
+    }
+    *out = t;
+    return EIGEN_OK;
+}
+
+int64_t eigen_trainer_tape_bytes(const eigen_trainer* t) { return t ? t->tape_bytes : 0; }
+
+static int copy_tables(eigen_trainer* t, float* dev, const float* const* h_in, float* const* h_out, int32_t n)
+{
+    if (!t || (!h_in && !h_out)) return tfail(EIGEN_ERR_INVALID, "null argument");
+    std::vector<std::pair<long long, long long>> tab;
+    tensor_table(t, tab);
+    if (n != (int32_t)tab.size()) return tfail(EIGEN_ERR_INVALID, "expected %d weight tensors for %d layers, got %d", (int)tab.size(), t->L, n);
+    TCHK(hipSetDevice(t->cfg.device));
+    TCHK(hipDeviceSynchronize());
+    for (int i = 0; i < n; ++i) {
+        if (h_in ? !h_in[i] : !h_out[i]) return tfail(EIGEN_ERR_INVALID, "tensor %d is NULL", i);
+        if (h_in) TCHK(hipMemcpy(dev + tab[i].first, h_in[i], tab[i].second * 4, hipMemcpyHostToDevice));
+        else TCHK(hipMemcpy(h_out[i], dev + tab[i].first, tab[i].second * 4, hipMemcpyDeviceToHost));
+    }
+    return EIGEN_OK;
+}
+
+int eigen_trainer_set_weights(eigen_trainer* t, const float* const* h_tensors, int32_t n_tensors)
+{
+    if (!t || !h_tensors) return tfail(EIGEN_ERR_INVALID, "null argument");
+    int rc = copy_tables(t, t->prm, h_tensors, nullptr, n_tensors);
+    if (rc) return rc;
+    TCHK(hipMemset(t->mom, 0, t->n_params * 4));
+    TCHK(hipMemset(t->var, 0, t->n_params * 4));
+    TCHK(hipDeviceSynchronize());
+    t->have_weights = true;
+    t->adam_t = 0;
+    t->state_batch = 0;
+    return EIGEN_OK;
+}
+
+int eigen_trainer_get_weights(eigen_trainer* t, float* const* h_tensors, int32_t n_tensors)
+{
+    if (!t || !h_tensors) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    return copy_tables(t, t->prm, nullptr, h_tensors, n_tensors);
+}
+
+int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n_tensors)
+{
+    if (!t || !h_tensors) return tfail(EIGEN_ERR_INVALID, "null argument");
+    return copy_tables(t, t->grd, nullptr, h_tensors, n_tensors);
+}
+
+int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                            int32_t reset, double* h_loss, float* d_pred, void* stream)
+{
+    if (!t || !d_frames) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    if (batch < 1 || n_steps < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 and n_steps >= 1 required");
+    if (batch > t->cfg.max_batch || n_steps > t->cfg.max_steps)
+        return tfail(EIGEN_ERR_CAPACITY, "batch %d / %d steps exceed the trainer's %d / %d", batch, n_steps, t->cfg.max_batch, t->cfg.max_steps);
+    if (reset && n_steps < 2) return tfail(EIGEN_ERR_INVALID, "a reset call needs n_steps >= 2 (one loss term per next frame)");
+    if (!reset && t->state_batch != batch)
+        return tfail(EIGEN_ERR_STATE, t->state_batch ? "reset = 0 needs the previous call's batch (%d, got %d)" : "reset = 0 with no previous call (%d, got %d)",
+                     t->state_batch, batch);
+    const int L = t->L, T = n_steps, B = batch;
+    const long long C0HW = t->ly[0].C * t->ly[0].HW;
+    if (bstride < (long long)T * C0HW && B > 1) return tfail(EIGEN_ERR_INVALID, "bstride %lld is smaller than a sequence (%lld bytes)", (long long)bstride, (long long)T * C0HW);
+    TCHK(hipSetDevice(t->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const float* prm = t->prm;
+    float* grd = t->grd;
+
+    // ---- start state: slot 0 of h, c, P
+    for (int l = 0; l < L; ++l) {
+        TLayer& y = t->ly[l];
+        const long long n = (long long)B * y.C * y.HW;
+        for (float* a : {y.h, y.c, y.P}) {
+            if (reset) TCHK(hipMemsetAsync(a, 0, n * 4, st));
+            else if (t->state_slot != 0) TCHK(hipMemcpyAsync(a, a + t->state_slot * n, n * 4, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    t->state_batch = 0;
+
+    // ---- forward with tape
+    for (int s = 0; s < T; ++s) {
+        const uint8_t* xs = d_frames + (long long)s * C0HW;
+        for (int l = 0; l < L; ++l) {
+            TLayer& y = t->ly[l];
+            const long long CHW = y.C * y.HW;
+            float* E = y.E + (long long)s * B * 2 * CHW;
+            const float* Pp = y.P + (long long)s * B * CHW;
+            if (l == 0) {
+                hipLaunchKernelGGL(terr_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, xs, (long long)bstride, (const float*)nullptr, Pp, E, y.C, y.H, y.W, B);
+            } else {
+                TLayer& yb = t->ly[l - 1];
+                float* ZA = y.ZA + (long long)s * B * 4 * CHW;
+                conv(st, ZA, y.C, yb.H, yb.W, B, prm + t->lp[l].ab, 0,
+                     {src(yb.E + (long long)s * B * 2 * yb.C * yb.HW, 2 * yb.C * yb.HW, 2 * yb.C, 0, prm + t->lp[l].aW, 0)});
+                hipLaunchKernelGGL(terr_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const uint8_t*)nullptr, 0ll, (const float*)ZA, Pp, E, y.C, y.H, y.W, B);
+            }
+        }
+        for (int l = L - 1; l >= 0; --l) {
+            TLayer& y = t->ly[l];
+            const LayerParams& p = t->lp[l];
+            const long long CHW = y.C * y.HW;
+            float* G = y.G + (long long)s * B * 4 * CHW;
+            const TSrc se = src(y.E + (long long)s * B * 2 * CHW, 2 * CHW, 2 * y.C, 0, prm + p.x0, 0);
+            const TSrc sh = src(y.h + (long long)s * B * CHW, CHW, y.C, 0, prm + p.hW, 0);
+            if (l < L - 1) {
+                const TLayer& ya = t->ly[l + 1];
+                const TSrc su = src(ya.h + (long long)(s + 1) * B * ya.C * ya.HW, ya.C * ya.HW, ya.C, 1, prm + p.x1, 0);
+                conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, su, sh});
+            } else {
+                conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, sh});
+            }
+            const float* pk = prm + p.peep;
+            hipLaunchKernelGGL(tlstm_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, G, (const float*)(y.c + (long long)s * B * CHW),
+                               y.c + (long long)(s + 1) * B * CHW, y.h + (long long)(s + 1) * B * CHW, pk, pk + CHW, pk + 2 * CHW, y.C, (int)y.HW, B);
+            float* P = y.P + (long long)(s + 1) * B * CHW;
+            conv(st, P, y.C, y.H, y.W, B, prm + p.pb, 0, {src(y.h + (long long)(s + 1) * B * CHW, CHW, y.C, 0, prm + p.pW, 0)});
+            float* pred = (l == 0 && d_pred) ? d_pred + (long long)s * CHW : nullptr;
+            hipLaunchKernelGGL(tpact_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (long long)B * CHW, l == 0 ? 1 : 0, pred, CHW, (long long)T * CHW);
+        }
+    }
+
+    // ---- loss
+    const long long n_terms = (long long)(T - 1) * B * C0HW;
+    if (T >= 2) {
+        hipLaunchKernelGGL(tloss_partial_kernel, dim3(LOSS_BLOCKS), dim3(EW_T), 0, st, (const float*)t->ly[0].P, d_frames, (long long)bstride, T - 1, B, C0HW, t->d_part);
+        hipLaunchKernelGGL(tloss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)t->d_part, LOSS_BLOCKS, 1.0 / (double)n_terms, t->d_loss);
+    } else {
+        TCHK(hipMemsetAsync(t->d_loss, 0, 8, st));
+    }
+    const float loss_scale = T >= 2 ? (float)(2.0 / (double)n_terms) : 0.f;
+
+    // ---- backward through time
+    for (int l = 0; l < L; ++l) {
+        TLayer& y = t->ly[l];
+        const long long n = (long long)B * y.C * y.HW;
+        TCHK(hipMemsetAsync(y.dPn, 0, n * 4, st));
+        TCHK(hipMemsetAsync(y.dhc, 0, n * 4, st));
+        TCHK(hipMemsetAsync(y.dc, 0, n * 4, st));
+    }
+    for (int s = T - 1; s >= 0; --s) {
+        for (int l = 0; l < L; ++l) {
+            TLayer& y = t->ly[l];
+            const LayerParams& p = t->lp[l];
+            const long long CHW = y.C * y.HW;
+            const float* P = y.P + (long long)(s + 1) * B * CHW;
+            float* dV = y.dV + (long long)s * B * CHW;
+            const uint8_t* xn = (l == 0 && s < T - 1) ? d_frames + (long long)(s + 1) * C0HW : nullptr;
+            hipLaunchKernelGGL(tpact_bwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (const float*)y.dPn, xn, (long long)bstride, CHW, loss_scale,
+                               l == 0 ? 1 : 0, (long long)B * CHW, dV);
+            conv(st, y.dhP, y.C, y.H, y.W, B, nullptr, 0, {src(dV, CHW, y.C, 0, prm + p.pW, 1)});
+            float* G = y.G + (long long)s * B * 4 * CHW;
+            const float* pk = prm + p.peep;
+            hipLaunchKernelGGL(tlstm_bwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, G, (const float*)(y.c + (long long)s * B * CHW),
+                               (const float*)(y.c + (long long)(s + 1) * B * CHW), (const float*)y.dhP, (const float*)(s < T - 1 ? y.dhc : nullptr),
+                               (const float*)(l > 0 ? y.dup : nullptr), y.dc, pk, pk + CHW, pk + 2 * CHW, y.C, y.H, y.W, B);
+            // dZ through the three sources: h of the previous step, E of this step, the upsampled h of the layer above
+            if (s > 0) conv(st, y.dhc, y.C, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.hW, 1)});
+            conv(st, y.dE, 2 * y.C, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x0, 1)});
+            if (l < L - 1) conv(st, t->ly[l + 1].dup, y.Ca, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x1, 1)});
+        }
+        for (int l = L - 1; l >= 0; --l) {
+            TLayer& y = t->ly[l];
+            const long long CHW = y.C * y.HW;
+            const float* E = y.E + (long long)s * B * 2 * CHW;
+            float* ZA = l > 0 ? y.ZA + (long long)s * B * 4 * CHW : nullptr;
+            hipLaunchKernelGGL(terr_bwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const float*)y.dE, E, y.dPn, ZA, y.C, y.H, y.W, B);
+            if (l > 0) {
+                TLayer& yb = t->ly[l - 1];
+                conv(st, yb.dE, 2 * yb.C, yb.H, yb.W, B, nullptr, 1, {src(ZA, 4 * CHW, y.C, 0, prm + t->lp[l].aW, 1)});
+            }
+        }
+    }
+
+    // ---- weight gradients over all T * B samples
+    const int N = T * B;
+    for (int l = 0; l < L; ++l) {
+        TLayer& y = t->ly[l];
+        const LayerParams& p = t->lp[l];
+        const long long CHW = y.C * y.HW;
+        wgrad(t, st, grd + p.pW, y.dV, y.C, y.H, y.W, N, src(y.h + (long long)B * CHW, CHW, y.C, 0, nullptr, 0));
+        bias_grad(t, st, grd + p.pb, y.dV, y.C, y.HW, N);
+        wgrad(t, st, grd + p.x0, y.G, 4 * y.C, y.H, y.W, N, src(y.E, 2 * CHW, 2 * y.C, 0, nullptr, 0));
+        wgrad(t, st, grd + p.hW, y.G, 4 * y.C, y.H, y.W, N, src(y.h, CHW, y.C, 0, nullptr, 0));
+        if (l < L - 1) {
+            const TLayer& ya = t->ly[l + 1];
+            wgrad(t, st, grd + p.x1, y.G, 4 * y.C, y.H, y.W, N, src(ya.h + (long long)B * ya.C * ya.HW, ya.C * ya.HW, ya.C, 1, nullptr, 0));
+        }
+        bias_grad(t, st, grd + p.hb, y.G, 4 * y.C, y.HW, N);
+        hipLaunchKernelGGL(tpeep_grad_kernel, dim3(blocks(CHW)), dim3(EW_T), 0, st, (const float*)y.G, (const float*)y.c, y.C, (int)y.HW, N,
+                           grd + p.peep, grd + p.peep + CHW, grd + p.peep + 2 * CHW);
+        if (l > 0) {
+            const TLayer& yb = t->ly[l - 1];
+            wgrad(t, st, grd + p.aW, y.ZA, y.C, yb.H, yb.W, N, src(yb.E, 2 * yb.C * yb.HW, 2 * yb.C, 0, nullptr, 0));
+            bias_grad(t, st, grd + p.ab, y.ZA, y.C, yb.HW, N);
+        }
+    }
+    TCHK(hipGetLastError());
+    t->state_batch = B;
+    t->state_slot = T;
+    if (h_loss) {
+        TCHK(hipMemcpyAsync(h_loss, t->d_loss, 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+    }
+    return EIGEN_OK;
+}
+
+int eigen_trainer_adam(eigen_trainer* t, double alpha, double beta1, double beta2, double eps, void* stream)
+{
+    if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    if (!(alpha > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
+        return tfail(EIGEN_ERR_INVALID, "Adam needs alpha > 0, 0 <= beta1, beta2 < 1 and eps > 0");
+    TCHK(hipSetDevice(t->cfg.device));
+    const int step = ++t->adam_t;
+    const double lr_t = alpha * std::sqrt(1.0 - std::pow(beta2, step)) / (1.0 - std::pow(beta1, step));
+    hipLaunchKernelGGL(tadam_kernel, dim3(blocks(t->n_params)), dim3(EW_T), 0, (hipStream_t)stream, t->prm, t->mom, t->var, (const float*)t->grd,
+                       t->n_params, (float)lr_t, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+    TCHK(hipGetLastError());
+    return EIGEN_OK;
+}
+
+}  // extern "C"

@@ -70,6 +70,12 @@ def load_chainer_npz(path, channels, w, h):
     return out
 
 
+def save_chainer_npz(weights, path):
+    """Write a weight table as a chainer npz model file: the ``predictor/``-prefixed keys of ``L.Classifier(PredNet)`` that
+    load_chainer_npz (and chainer's serializers.load_npz) read back.  Arrays are stored as float32, unchanged."""
+    np.savez(path, **{"predictor/" + k: np.ascontiguousarray(v, dtype=np.float32) for k, v in weights.items()})
+
+
 def synthetic_prednet_weights(channels, w, h, seed=0, gain=0.6, leak=0.25):
     """Seeded stand-in for trained weights (no network access for the real files).
 

@@ -266,6 +266,51 @@ int eigen_debug_corners(eigen_engine* e, int32_t batch, float* h_corners, int32_
 /* Algorithmic FLOPs (2 x MACs of the 3x3 convolutions) of one PredNet step for one genome. */
 double eigen_prednet_flops_per_step(const eigen_engine* e);
 
+
+/* ---------------------------------------------------------------------------------------------------- training
+ * PredNet training on frame sequences: next-frame MSE, full backprop through time within a call,
+ * Adam as chainer defines it.  A separate handle: no inference handle's state or workspaces are touched.  Gradients and
+ * weights are bit-identical from run to run (fixed-order reductions, no float atomics). */
+typedef struct eigen_trainer eigen_trainer;
+
+typedef struct {
+    int32_t device;                        /* HIP device ordinal */
+    int32_t width, height;                 /* both divisible by 2^(n_layers-1) */
+    int32_t n_layers;
+    int32_t channels[EIGEN_MAX_LAYERS];    /* channels[0] = 1 or 3 */
+    int32_t max_batch;                     /* sequences per call (tape sizing) */
+    int32_t max_steps;                     /* frames per call (tape sizing) */
+} eigen_trainer_config;
+
+int eigen_trainer_create(const eigen_trainer_config* cfg, eigen_trainer** out);
+int eigen_trainer_destroy(eigen_trainer* t);
+
+/* Host float32 tables in the order of eigen_set_prednet_weights.  set_weights also clears the Adam moments and step count
+ * and discards any kept sequence state. */
+int eigen_trainer_set_weights(eigen_trainer* t, const float* const* h_tensors, int32_t n_tensors);
+int eigen_trainer_get_weights(eigen_trainer* t, float* const* h_tensors, int32_t n_tensors);
+
+/* Forward with a tape, loss and backward over one batch of sequences; OVERWRITES the gradients.
+ *   d_frames: uint8 frames, frame s of sequence b at d_frames + b * bstride + s * C*H*W (bytes); n_steps frames each.
+ *   loss = mean over s in [0, n_steps-2], b, c, y, x of (P0_s - x_{s+1})^2, P0_s the float prediction after frame s.
+ *   reset = 1: start from zero state (needs n_steps >= 2).  reset = 0: start from the state (h, c, P) the previous call left,
+ *   which must have had the same batch; that state is a constant (no gradient flows into the previous call).
+ *   h_loss (host, may be NULL) receives the loss; d_pred (may be NULL) float [batch][n_steps][C][H][W] receives P0_s.
+ * Errors: EIGEN_ERR_CAPACITY batch / n_steps above the handle's; EIGEN_ERR_STATE no weights, or reset = 0 without a previous
+ * call of the same batch; EIGEN_ERR_INVALID n_steps < 2 with reset = 1. */
+int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                            int32_t reset, double* h_loss, float* d_pred, void* stream);
+
+/* The gradients of the last eigen_trainer_loss_grad, host tables in eigen_set_prednet_weights order. */
+int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n_tensors);
+
+/* One Adam step on the current gradients (step count kept by the handle, from 1): m += (1-beta1)(g-m),
+ * v += (1-beta2)(g^2-v), p -= lr_t m / (sqrt(v) + eps), lr_t = alpha sqrt(1-beta2^t) / (1-beta1^t). */
+int eigen_trainer_adam(eigen_trainer* t, double alpha, double beta1, double beta2, double eps, void* stream);
+
+/* Device bytes of the handle's tape (activations kept for the backward pass) at max_batch x max_steps. */
+int64_t eigen_trainer_tape_bytes(const eigen_trainer* t);
+
 #ifdef __cplusplus
 }
 #endif

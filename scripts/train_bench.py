@@ -1,0 +1,153 @@
+"""Time PredNet training steps (train.PredNetTrainer: gradient + Adam) at 160x120 colour, channels [3, 48, 96, 192], batch 16,
+10 frames, then -- in a separate process under its own time limit -- torch-ROCm autograd of the same network and loss
+(F.conv2d, float32) on the same GPU.  Prints one JSON line per side and writes profiles/train_bench.json.
+
+    python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+W, H, CH, B, T = 160, 120, [3, 48, 96, 192], 16, 10
+GATES = ("i", "f", "c", "o")
+
+
+def conv_flops_per_sample_step(ch, w, h):
+    """multiply-adds x 2 of the forward 3x3 convolutions of one sample-step; dgrad and wgrad each repeat them"""
+    f, L = 0, len(ch)
+    for l, C in enumerate(ch):
+        hw = (h >> l) * (w >> l)
+        if l > 0:
+            f += 2 * C * 2 * ch[l - 1] * 9 * hw * 4
+        f += 2 * 4 * C * (2 * C + (ch[l + 1] if l < L - 1 else 0) + C) * 9 * hw
+        f += 2 * C * C * 9 * hw
+    return f
+
+
+def frames(seed, n, T, c, h, w):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h + 2 * T, 0:w + 2 * T].astype(np.float64)
+    out = np.zeros((n, T, c, h, w), np.uint8)
+    for i in range(n):
+        tex = sum(np.sin(rng.uniform(0.05, 0.3) * yy + rng.uniform(0.05, 0.3) * xx + rng.uniform(0, 6.3)) for _ in range(3))
+        tex = np.clip(128 + 40 * tex, 0, 255)
+        for t in range(T):
+            out[i, t] = tex[None, T + t:T + t + h, T:T + w].astype(np.uint8).repeat(c, 0)
+    return out
+
+
+def run_trainer(steps, warmup):
+    import torch
+    from evolutionary_illusion_generator_amd import weights
+    from evolutionary_illusion_generator_amd.train import PredNetTrainer
+    d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
+    tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T)
+    for _ in range(warmup):
+        tr.step(d)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        loss = tr.step(d)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / steps
+    res = dict(side="trainer", step_ms=ms, sample_steps_per_s=B * T / ms * 1e3, loss=loss, tape_bytes=tr.tape_bytes,
+               tape_bytes_per_sample_step=tr.tape_bytes / (B * T), conv_flops_per_step=3 * conv_flops_per_sample_step(CH, W, H) * B * T)
+    tr.close()
+    return res
+
+
+def run_torch(steps, warmup):
+    import torch
+    import torch.nn.functional as F
+    from evolutionary_illusion_generator_amd import weights
+    wts = weights.synthetic_prednet_weights(CH, W, H, seed=0)
+    p = {k: torch.tensor(v, device="cuda", requires_grad=True) for k, v in wts.items()}
+    opt = torch.optim.Adam(list(p.values()), lr=1e-3, betas=(0.9, 0.999), eps=1e-8)
+    x = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda().float() / 255.0
+    L = len(CH)
+
+    def loss_fn():
+        z = lambda l: torch.zeros(B, CH[l], H >> l, W >> l, device="cuda")
+        hs, cs, Ps = [z(l) for l in range(L)], [z(l) for l in range(L)], [z(l) for l in range(L)]
+        loss = 0.0
+        for t in range(T):
+            E = [torch.cat((F.relu(x[:, t] - Ps[0]), F.relu(Ps[0] - x[:, t])), 1)]
+            for l in range(1, L):
+                A = F.max_pool2d(F.relu(F.conv2d(E[l - 1], p["ConvA%d/W" % l], p["ConvA%d/b" % l], padding=1)), 2, 2)
+                E.append(torch.cat((F.relu(A - Ps[l]), F.relu(Ps[l] - A)), 1))
+            for l in reversed(range(L)):
+                st = lambda s: torch.cat([p["ConvLSTM%d/%s/W" % (l, s % g)] for g in GATES], 0)
+                zz = F.conv2d(E[l], st("x_%s0"), padding=1) + F.conv2d(hs[l], st("h_%s"), torch.cat([p["ConvLSTM%d/h_%s/b" % (l, g)] for g in GATES]), padding=1)
+                if l < L - 1:
+                    zz = zz + F.conv2d(F.interpolate(hs[l + 1], scale_factor=2, mode="nearest"), st("x_%s1"), padding=1)
+                zi, zf, zc, zo = torch.chunk(zz, 4, 1)
+                c = cs[l]
+                i = torch.sigmoid(zi + p["ConvLSTM%d/c_i/W" % l] * c)
+                f = torch.sigmoid(zf + p["ConvLSTM%d/c_f/W" % l] * c)
+                o = torch.sigmoid(zo + p["ConvLSTM%d/c_o/W" % l] * c)
+                cs[l] = torch.tanh(zc) * i + f * c
+                hs[l] = o * torch.tanh(cs[l])
+                v = F.conv2d(hs[l], p["ConvP%d/W" % l], p["ConvP%d/b" % l], padding=1)
+                Ps[l] = v.clamp(0, 1) if l == 0 else F.relu(v)
+            if t < T - 1:
+                loss = loss + ((Ps[0] - x[:, t + 1]) ** 2).mean()
+        return loss / (T - 1)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = loss_fn()
+        loss.backward()
+        opt.step()
+        return float(loss)
+
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        loss = step()
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / steps
+    return dict(side="torch", step_ms=ms, sample_steps_per_s=B * T / ms * 1e3, loss=loss, max_memory_allocated=torch.cuda.max_memory_allocated())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
+    ap.add_argument("--torch-timeout", type=int, default=600)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
+    a = ap.parse_args()
+    if a.side == "torch":
+        print(json.dumps(run_torch(a.steps, a.warmup)))
+        return
+    res = [run_trainer(a.steps, a.warmup)]
+    print(json.dumps(res[0]), flush=True)
+    if a.side == "both":
+        # torch in a fresh process of its own: its allocator and MIOpen caches do not share the trainer's process
+        cmd = ["timeout", "-k", "10", str(a.torch_timeout), sys.executable, os.path.abspath(__file__), "--side", "torch",
+               "--steps", str(a.steps), "--warmup", str(a.warmup)]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            print(p.stdout[-2000:], p.stderr[-4000:], file=sys.stderr)
+            res.append(dict(side="torch", error=p.returncode))
+        else:
+            res.append(json.loads(p.stdout.strip().splitlines()[-1]))
+        print(json.dumps(res[1]))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(dict(shape=dict(w=W, h=H, channels=CH, batch=B, steps=T), results=res), f, indent=1)
+    sys.exit(0 if all("error" not in r for r in res) else 1)
+
+
+if __name__ == "__main__":
+    main()
