@@ -8,8 +8,8 @@ BASELINE.json configs[2]: neat_configs/circles.txt (num_hidden 20, 3 outputs), c
 structure, 256x256, ONE population of 256 genomes.  Data: seeded synthetic genomes and seeded synthetic PredNet weights
 (the trained weights are external downloads and fix the size to 160x120).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--weak] [--no-cpu-baseline] [--no-roofline] [--no-parity] [--no-supplementary]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--weak] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-roofline] [--no-parity] [--no-supplementary] [--strict-parity]]
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller -- the fitness
 vector of the population, float64 -- as DIR/fitness.npy.  The workload is seeded, so two builds run with the same arguments
@@ -21,13 +21,17 @@ nccl = RCCL); launched that way by the driver it just joins.  Either way it asse
 Scaling: the metric names ONE population of 256, so for N > 1 that population is sharded N ways ("scaling": "strong",
 32 genomes per GPU at N = 8); --weak keeps --pop genomes PER GPU instead (supplementary).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel: the fused
-ConvLSTM 3x3 convolution on the fp32 MFMA pipe, timed live with HIP events on its launch stream), `roofline_hbm` (the two
-HBM-side stages: CPPN render and the flow stencils) and `cpu_baseline` (the CPU oracle's path -- numpy CPPN + torch-CPU fp32
-PredNet + C Lucas-Kanade + numpy scores -- on a bounded sample of >= 8 genomes at the best of a small thread sweep),
-`parity_check` (genome 0 against the bit-exact C oracle; ALL genomes of the population classified against the reference's
-element-wise order, oracle/classify.py) and `supplementary` (the other BASELINE.json configs, a few seconds each, never part
-of `value`).  All of these legs run AFTER the timed region, on rank 0 only.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs: set
+up, warm up, time the --steps generations, write --dump-outputs, print the line (`value`, `ms_per_step`, `config`,
+`stage_ms_last_step`, `multi_gpu` for N > 1).
+
+--full adds the untimed legs, AFTER the timed region and on rank 0 only (each can be left out with its --no-* option):
+`roofline` (dominant kernel: the fused ConvLSTM 3x3 convolution on the fp32 MFMA pipe, timed live with HIP events on its
+launch stream), `roofline_hbm` (the two HBM-side stages: CPPN render and the flow stencils), `cpu_baseline` (the CPU oracle's
+path -- numpy CPPN + torch-CPU fp32 PredNet + C Lucas-Kanade + numpy scores -- on a bounded sample of >= 8 genomes at the
+best of a small thread sweep), `parity_check` (genome 0 against the bit-exact C oracle; ALL genomes of the population
+classified against the reference's element-wise order, oracle/classify.py), `supplementary` (the other BASELINE.json
+configs, a few seconds each, never part of `value`) and, for N > 1, the N = 1 anchor `multi_gpu.n1_same_box_*`.
 """
 import argparse
 import hashlib
@@ -435,16 +439,23 @@ def main():
     ap.add_argument("--flow", default="lk", choices=["lk", "farneback"],
                     help="supplementary: 'farneback' swaps the reference's Lucas-Kanade call for the dense Farneback option (no CPU leg)")
     ap.add_argument("--source", default=None, choices=["rank0", "replicated"], help="multi-rank genome source (fitness.GENOME_SOURCE)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the untimed parity legs (C-oracle spot check, whole-population classification)")
-    ap.add_argument("--no-supplementary", action="store_true", help="skip the untimed supplementary block (ref160, c2, c4, c5 at a device-batch sample)")
-    ap.add_argument("--strict-parity", action="store_true", help="exit with status 3 when the parity legs flag a failure (parity_fail)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the untimed legs: roofline, CPU baseline, parity, supplementary shapes, "
+                         "the N = 1 anchor of a multi-GPU run (a plain run only times the steps and prints the headline line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline legs (one profiled roll-out pass)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the untimed parity legs (C-oracle spot check, whole-population classification)")
+    ap.add_argument("--no-supplementary", action="store_true", help="with --full: skip the untimed supplementary block (ref160, c2, c4, c5 at a device-batch sample)")
+    ap.add_argument("--strict-parity", action="store_true", help="with --full: exit with status 3 when the parity legs flag a failure (parity_fail)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (the population's fitness, float64) as DIR/fitness.npy")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1 (the timed region is --steps generations)")
+    if args.strict_parity and not (args.full and not args.no_parity):
+        ap.error("--strict-parity needs the parity legs: add --full (without --no-parity)")
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_parity = args.no_supplementary = True
     # RCCL / device-tensor sharing across processes needs dmabuf IPC on these hosts; must be in the environment BEFORE the HIP
     # runtime initialises, whoever launched this process (the respawn path below, the driver's own torchrun, a plain shell)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -560,7 +571,7 @@ def main():
         dist.destroy_process_group()
         if rank != 0:
             return
-        if world > 1:
+        if world > 1 and args.full:
             # the SCALE line carries its own N = 1 anchor -- rank 0, now alone, evaluates the WHOLE population on its one GPU (one warm-up
             # + one timed generation, untimed by the driver), so that a mismatch with the N = 1 BENCH record is visible in one record
             fitness.clear_engines()

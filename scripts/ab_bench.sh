@@ -6,7 +6,7 @@ mkdir -p $OUT
 for rep in 1 2; do
   for v in "" "$@"; do
     name=${v:-default}
-    env $v python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/${name%%=*}_$rep.json
+    env $v python $R/bench.py --steps 4 --warmup 1 --full --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/${name%%=*}_$rep.json
     python - <<PY
 import json
 d=json.loads(open("$OUT/${name%%=*}_$rep.json").read())

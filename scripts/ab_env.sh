@@ -9,7 +9,7 @@ for rep in $(seq 1 ${REPS:-2}); do
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs python $R/bench.py $ARGS --warmup 2 --no-cpu-baseline --no-parity --no-supplementary 2>$OUT/err_${i}_$rep.txt | tail -1 > $OUT/ab_${i}_$rep.json
+  env $envs python $R/bench.py $ARGS --warmup 2 --full --no-cpu-baseline --no-parity --no-supplementary 2>$OUT/err_${i}_$rep.txt | tail -1 > $OUT/ab_${i}_$rep.json
   python - <<PY
 import json
 try:

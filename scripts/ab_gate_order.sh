@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$1; mkdir -p $OUT
 for g in 1 0; do
   if [ $g = 0 ]; then export EIGEN_HIP_LIB=$R/evolutionary_illusion_generator_amd/libeigen_hip_gate0.so EIG_ORACLE_LIB=$R/oracle/libeig_oracle_gate0.so; else unset EIGEN_HIP_LIB EIG_ORACLE_LIB; fi
-  python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-supplementary 2>$OUT/gate$g.err | tail -1 > $OUT/gate$g.json
+  python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-supplementary 2>$OUT/gate$g.err | tail -1 > $OUT/gate$g.json
   python - <<PY
 import json
 d=json.loads(open("$OUT/gate$g.json").read())

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for lib in "" "$@"; do
   name=${lib:-default}
   if [ -n "$lib" ]; then export EIGEN_HIP_LIB=$R/evolutionary_illusion_generator_amd/$lib; else unset EIGEN_HIP_LIB; fi
-  env $ABENV python $R/bench.py $ARGS --warmup 2 --no-cpu-baseline --no-parity --no-supplementary 2>/dev/null | tail -1 > $OUT/${name%.so}_$rep.json
+  env $ABENV python $R/bench.py $ARGS --warmup 2 --full --no-cpu-baseline --no-parity --no-supplementary 2>/dev/null | tail -1 > $OUT/${name%.so}_$rep.json
   python - <<PY
 import json
 d=json.loads(open("$OUT/${name%.so}_$rep.json").read())

@@ -7,7 +7,7 @@ for args in "--shape ref160 --steps 10" "--shape c2 --steps 20" "--pop 32 --step
 for lib in "" "$@"; do
   name=${lib:-default}
   if [ -n "$lib" ]; then export EIGEN_HIP_LIB=$R/evolutionary_illusion_generator_amd/$lib; else unset EIGEN_HIP_LIB; fi
-  env $ABENV python $R/bench.py $args --warmup 2 --no-cpu-baseline --no-parity --no-supplementary 2>/dev/null | tail -1 > $OUT/last.json
+  env $ABENV python $R/bench.py $args --warmup 2 --full --no-cpu-baseline --no-parity --no-supplementary 2>/dev/null | tail -1 > $OUT/last.json
   python - <<PY
 import json
 d=json.loads(open("$OUT/last.json").read())

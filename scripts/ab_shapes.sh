@@ -9,7 +9,7 @@ for sh in $SHAPES; do
   args=${sh//@/ }
   for v in "" "$@"; do
     name=${v:-default}
-    env $v python $R/bench.py $args --warmup 2 --no-cpu-baseline --no-parity --no-supplementary 2>/dev/null | tail -1 > $OUT/last.json
+    env $v python $R/bench.py $args --warmup 2 --full --no-cpu-baseline --no-parity --no-supplementary 2>/dev/null | tail -1 > $OUT/last.json
     python - <<PY
 import json
 d=json.loads(open("$OUT/last.json").read())

@@ -6,7 +6,7 @@ TAG=$1; shift
 OUT=$R/gpurun_out/prof_$TAG; mkdir -p $OUT
 cd /tmp
 for sh in "$@"; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$sh -o kt -- python $R/bench.py --shape $sh --steps 3 --warmup 1 --no-roofline > $OUT/bench_$sh.json 2> $OUT/rocprof_$sh.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$sh -o kt -- python $R/bench.py --shape $sh --steps 3 --warmup 1 --full --no-roofline > $OUT/bench_$sh.json 2> $OUT/rocprof_$sh.err
   find $OUT/kt_$sh -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_$sh.csv \;
   rm -rf $OUT/kt_$sh
   echo "== $sh"; head -6 $OUT/kernel_stats_$sh.csv | cut -c1-140

@@ -11,8 +11,8 @@ cd /tmp
 i=0
 for args in "$@"; do
   i=$((i+1))
-  python $R/bench.py $args --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${i}_bench.json 2> $OUT/${i}_bench.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt$i -o kt -- python $R/bench.py $args --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > $OUT/${i}_under_rocprof.json 2> $OUT/${i}_rocprof.err
+  python $R/bench.py $args --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/${i}_bench.json 2> $OUT/${i}_bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt$i -o kt -- python $R/bench.py $args --steps 3 --warmup 1 --full --no-cpu-baseline --no-roofline > $OUT/${i}_under_rocprof.json 2> $OUT/${i}_rocprof.err
   find $OUT/kt$i -name "*kernel_stats.csv" -exec cp {} $OUT/${i}_kernel_stats.csv \;
   find $OUT/kt$i -name "*kernel_trace.csv" -exec cp {} $OUT/${i}_kernel_trace.csv \;
   rm -rf $OUT/kt$i

@@ -408,6 +408,7 @@ def test_bench_gpus_flag_launches_ranks(cuda, tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     small = ["--shape", "c2", "--pop", "8", "--steps", "1", "--warmup", "1", "--no-roofline", "--no-cpu-baseline"]
+    full = small[:-2] + ["--full", "--no-cpu-baseline"]   # with the untimed legs (the roofline block among them)
     bench = os.path.join(ROOT, "bench.py")
     dump = str(tmp_path / "dump")
 
@@ -417,24 +418,25 @@ def test_bench_gpus_flag_launches_ranks(cuda, tmp_path):
     # The launches are independent processes (tiny workloads sharing the one GPU).  At most six processes hold the GPU at once, this
     # one included: the launches run in waves of at most five GPU processes each.
     jobs = {
-        "one": ([sys.executable, bench, "--gpus", "1"] + small[:-2] + ["--no-cpu-baseline", "--dump-outputs", dump], env),   # (WITH the roofline block: the plain single-rank path the driver runs)
+        "one": ([sys.executable, bench, "--gpus", "1"] + small[:-2] + ["--dump-outputs", dump], env),   # the plain single-rank run: headline line only
+        "one_full": ([sys.executable, bench, "--gpus", "1"] + full, env),   # the same with --full: the roofline block after the timed region
         # the multi-rank reporting path (RCCL group, per-rank device times out of the all-gather, leaving the group before rank 0's
         # untimed legs) in a group of ONE rank: what a single-GPU box can run of `--gpus N`
-        "single_rank_group": ([sys.executable, bench, "--gpus", "1"] + small[:-2] + ["--no-cpu-baseline"], dict(env, EIGEN_DIST_SINGLE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")),
+        "single_rank_group": ([sys.executable, bench, "--gpus", "1"] + full, dict(env, EIGEN_DIST_SINGLE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")),
         # TWO ranks for real (sharding, broadcast, all-gather with per-rank times, rank 1 leaving while rank 0 profiles) -- on a 1-GPU
         # box they share the device and gloo carries the collectives (RCCL refuses two ranks on one device): control flow, not a number
-        "two_ranks": (torchrun(2) + small[:-2] + ["--no-cpu-baseline"], env_gloo),
+        "two_ranks": (torchrun(2) + full, env_gloo),
         # joined under a launcher with the wrong world size: refuse (before the GPU is touched)
         "wrong_world_size": ([sys.executable, bench, "--gpus", "2"] + small, dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")),
         # FOUR ranks at the HEADLINE shape: pop 128 -> 32 genomes per rank, engines at max_batch 32 as in the driver's
         # `--gpus 8` run of pop 256, the broadcast of the wire arrays, the all-gather, all ranks leaving the group together -- executed once
         # on a GPU box (the ranks share its one device over gloo: control flow, not a measurement).  Eight ranks on one device would break
         # the bound above; the eight-rank sharding itself is tests/test_host_logic.py::test_population_sharding_gloo_world8
-        "four_ranks": (torchrun(4) + ["--pop", "128", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-parity", "--no-supplementary"], env_gloo),
+        "four_ranks": (torchrun(4) + ["--pop", "128", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-parity", "--no-supplementary"], env_gloo),
         # (three processes at the most: the launcher holds the GPU while its two ranks run, where two GPUs are visible)
         "two_without_launcher": ([sys.executable, bench, "--gpus", "2"] + small, env),
     }
-    waves = [("one", "single_rank_group", "two_ranks", "wrong_world_size"), ("four_ranks",), ("two_without_launcher",)]
+    waves = [("one", "single_rank_group", "two_ranks", "wrong_world_size"), ("four_ranks", "one_full"), ("two_without_launcher",)]
     from concurrent.futures import ThreadPoolExecutor
     res = {}
     for wave in waves:
@@ -448,7 +450,11 @@ def test_bench_gpus_flag_launches_ranks(cuda, tmp_path):
         return json.loads(lines[0])
     line = json_line(res["one"])
     assert line["n_gpus"] == 1 and line["config"]["global_pop"] == 8 and line["scaling"] == "strong" and line["value"] > 0
-    assert line["roofline"]["all_conv_kernels"]["launches"] > 0 and line["roofline"]["winograd_mask"] == "0x0FFFFFFE"
+    assert line["unit"] == "genome evals/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["ms_per_step"] > 0
+    assert not {"roofline", "roofline_hbm", "cpu_baseline", "parity_check", "supplementary"} & set(line), "a plain run has no untimed legs"
+    line_full = json_line(res["one_full"])
+    assert line_full["n_gpus"] == 1 and line_full["config"]["global_pop"] == 8 and line_full["value"] > 0
+    assert line_full["roofline"]["all_conv_kernels"]["launches"] > 0 and line_full["roofline"]["winograd_mask"] == "0x0FFFFFFE"
     # --dump-outputs: the fitness vector the last timed step returned, as its caller received it
     assert os.listdir(dump) == ["fitness.npy"]
     fit = np.load(os.path.join(dump, "fitness.npy"))

@@ -594,3 +594,13 @@ def test_bench_refuses_what_it_cannot_launch():
     import bench as B
     assert len(B.kernel_sources_sha()) == 16 and B.kernel_sources_sha() == B.kernel_sources_sha()
     assert set(B.SHAPES) == {"headline", "ref160", "ref640", "c1", "c2", "c4", "c5"} and B.SHAPES["ref640"][:2] == (640, 480) and B.SHAPES["headline"][:2] == (256, 256) and B.SHAPES["headline"][7] == 256
+
+
+def test_bench_strict_parity_needs_full():
+    """A plain bench.py run has no parity legs (they run with --full), so --strict-parity without them is refused, before the GPU is touched."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    bench = os.path.join(ROOT, "bench.py")
+    for extra in ([], ["--full", "--no-parity"]):
+        r = subprocess.run([sys.executable, bench, "--steps", "1", "--warmup", "0", "--strict-parity"] + extra, env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--strict-parity needs the parity legs" in r.stderr, (extra, r.stderr[-500:])
