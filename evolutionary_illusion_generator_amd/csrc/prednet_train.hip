@@ -39,6 +39,7 @@ int tfail(int code, const char* fmt, ...)
 constexpr long long SLAB_FLOATS = 16ll << 20;  // split-K slab budget of one wgrad (floats)
 constexpr int WGRAD_WAVES = 2048;              // split-K target: waves of one wgrad launch
 constexpr int LOSS_BLOCKS = 256;
+constexpr int STEP_LOSS_BLOCKS = 64;           // blocks of one step's loss reduction
 constexpr int BIAS_SLICES = 64;                // slices of one bias-gradient reduction
 
 // offsets (floats) of one layer's parameters in the flat device table; gate tensors of one source are stacked i, f, c, o
@@ -70,9 +71,10 @@ struct eigen_trainer {
     float* slab = nullptr;
     long long slab_floats = 0;
     double *d_part = nullptr, *d_loss = nullptr;
+    double *d_spart = nullptr, *d_step = nullptr;  // per-step loss: partials [max_steps][STEP_LOSS_BLOCKS], losses [max_steps]
     long long tape_bytes = 0;
     bool have_weights = false;
-    int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad call (0: no state kept)
+    int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
     int adam_t = 0;
     std::vector<void*> allocs;
 };
@@ -232,6 +234,8 @@ int eigen_trainer_create(const eigen_trainer_config* cfg, eigen_trainer** out)
     add((void**)&t->slab, t->slab_floats * 4);
     add((void**)&t->d_part, LOSS_BLOCKS * 8);
     add((void**)&t->d_loss, 8);
+    add((void**)&t->d_spart, T * STEP_LOSS_BLOCKS * 8);
+    add((void**)&t->d_step, T * 8);
     for (int l = 0; l < L; ++l) {
         TLayer& y = t->ly[l];
         const long long CHW = y.C * y.HW;
@@ -312,28 +316,32 @@ int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n
     return copy_tables(t, t->grd, nullptr, h_tensors, n_tensors);
 }
 
-int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
-                            int32_t reset, double* h_loss, float* d_pred, void* stream)
+// argument rules shared by loss_grad_ext and evaluate; max_steps < 0: n_steps is not bounded
+static int check_call(const eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                      int32_t requant, int32_t reset, int max_steps)
 {
     if (!t || !d_frames) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
     if (batch < 1 || n_steps < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 and n_steps >= 1 required");
-    if (batch > t->cfg.max_batch || n_steps > t->cfg.max_steps)
+    if (batch > t->cfg.max_batch || (max_steps >= 0 && n_steps > max_steps))
         return tfail(EIGEN_ERR_CAPACITY, "batch %d / %d steps exceed the trainer's %d / %d", batch, n_steps, t->cfg.max_batch, t->cfg.max_steps);
     if (reset && n_steps < 2) return tfail(EIGEN_ERR_INVALID, "a reset call needs n_steps >= 2 (one loss term per next frame)");
+    if (n_fed < 0 || n_fed > n_steps) return tfail(EIGEN_ERR_INVALID, "n_fed %d outside [0, n_steps = %d]", n_fed, n_steps);
+    if (n_fed == 0 && reset) return tfail(EIGEN_ERR_INVALID, "n_fed = 0 needs reset = 0: a self-fed step continues a kept prediction");
+    if (requant != 0 && requant != 1) return tfail(EIGEN_ERR_INVALID, "requant must be 0 or 1");
     if (!reset && t->state_batch != batch)
         return tfail(EIGEN_ERR_STATE, t->state_batch ? "reset = 0 needs the previous call's batch (%d, got %d)" : "reset = 0 with no previous call (%d, got %d)",
                      t->state_batch, batch);
-    const int L = t->L, T = n_steps, B = batch;
     const long long C0HW = t->ly[0].C * t->ly[0].HW;
-    if (bstride < (long long)T * C0HW && B > 1) return tfail(EIGEN_ERR_INVALID, "bstride %lld is smaller than a sequence (%lld bytes)", (long long)bstride, (long long)T * C0HW);
-    TCHK(hipSetDevice(t->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    const float* prm = t->prm;
-    float* grd = t->grd;
+    if (bstride < (long long)n_steps * C0HW && batch > 1)
+        return tfail(EIGEN_ERR_INVALID, "bstride %lld is smaller than a sequence (%lld bytes)", (long long)bstride, (long long)n_steps * C0HW);
+    return EIGEN_OK;
+}
 
-    // ---- start state: slot 0 of h, c, P
-    for (int l = 0; l < L; ++l) {
+// start state into slot 0 of h, c, P: zeros, or the state the previous call left
+static int start_state(eigen_trainer* t, hipStream_t st, int B, int reset)
+{
+    for (int l = 0; l < t->L; ++l) {
         TLayer& y = t->ly[l];
         const long long n = (long long)B * y.C * y.HW;
         for (float* a : {y.h, y.c, y.P}) {
@@ -342,58 +350,111 @@ int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t b
         }
     }
     t->state_batch = 0;
+    t->state_slot = 0;
+    return EIGEN_OK;
+}
 
-    // ---- forward with tape
-    for (int s = 0; s < T; ++s) {
-        const uint8_t* xs = d_frames + (long long)s * C0HW;
-        for (int l = 0; l < L; ++l) {
-            TLayer& y = t->ly[l];
-            const long long CHW = y.C * y.HW;
-            float* E = y.E + (long long)s * B * 2 * CHW;
-            const float* Pp = y.P + (long long)s * B * CHW;
-            if (l == 0) {
-                hipLaunchKernelGGL(terr_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, xs, (long long)bstride, (const float*)nullptr, Pp, E, y.C, y.H, y.W, B);
-            } else {
-                TLayer& yb = t->ly[l - 1];
-                float* ZA = y.ZA + (long long)s * B * 4 * CHW;
-                conv(st, ZA, y.C, yb.H, yb.W, B, prm + t->lp[l].ab, 0,
-                     {src(yb.E + (long long)s * B * 2 * yb.C * yb.HW, 2 * yb.C * yb.HW, 2 * yb.C, 0, prm + t->lp[l].aW, 0)});
-                hipLaunchKernelGGL(terr_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const uint8_t*)nullptr, 0ll, (const float*)ZA, Pp, E, y.C, y.H, y.W, B);
-            }
-        }
-        for (int l = L - 1; l >= 0; --l) {
-            TLayer& y = t->ly[l];
-            const LayerParams& p = t->lp[l];
-            const long long CHW = y.C * y.HW;
-            float* G = y.G + (long long)s * B * 4 * CHW;
-            const TSrc se = src(y.E + (long long)s * B * 2 * CHW, 2 * CHW, 2 * y.C, 0, prm + p.x0, 0);
-            const TSrc sh = src(y.h + (long long)s * B * CHW, CHW, y.C, 0, prm + p.hW, 0);
-            if (l < L - 1) {
-                const TLayer& ya = t->ly[l + 1];
-                const TSrc su = src(ya.h + (long long)(s + 1) * B * ya.C * ya.HW, ya.C * ya.HW, ya.C, 1, prm + p.x1, 0);
-                conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, su, sh});
-            } else {
-                conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, sh});
-            }
-            const float* pk = prm + p.peep;
-            hipLaunchKernelGGL(tlstm_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, G, (const float*)(y.c + (long long)s * B * CHW),
-                               y.c + (long long)(s + 1) * B * CHW, y.h + (long long)(s + 1) * B * CHW, pk, pk + CHW, pk + 2 * CHW, y.C, (int)y.HW, B);
-            float* P = y.P + (long long)(s + 1) * B * CHW;
-            conv(st, P, y.C, y.H, y.W, B, prm + p.pb, 0, {src(y.h + (long long)(s + 1) * B * CHW, CHW, y.C, 0, prm + p.pW, 0)});
-            float* pred = (l == 0 && d_pred) ? d_pred + (long long)s * CHW : nullptr;
-            hipLaunchKernelGGL(tpact_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (long long)B * CHW, l == 0 ? 1 : 0, pred, CHW, (long long)T * CHW);
+// One forward step: reads (h, c, P) of slot `in`, writes slot `out`, and E, gates and ZA of tape slot `tp`.  xs: this step's
+// frames (frame of sample b at xs + b * bstride), or nullptr for a self-fed step, whose image layer reads P0 of slot `in`
+// (requant: through the byte).  pred (may be null): P0 of this step for sample b at pred + b * pred_bstride.
+static void forward_step(eigen_trainer* t, hipStream_t st, int B, int in, int out, int tp, const uint8_t* xs, long long bstride, int requant,
+                         float* pred, long long pred_bstride)
+{
+    const int L = t->L;
+    const float* prm = t->prm;
+    for (int l = 0; l < L; ++l) {
+        TLayer& y = t->ly[l];
+        const long long CHW = y.C * y.HW;
+        float* E = y.E + (long long)tp * B * 2 * CHW;
+        const float* Pp = y.P + (long long)in * B * CHW;
+        if (l == 0 && xs) {
+            hipLaunchKernelGGL(terr_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, xs, (long long)bstride, (const float*)nullptr, Pp, E, y.C, y.H, y.W, B);
+        } else if (l == 0) {
+            hipLaunchKernelGGL(terr_fed_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, Pp, E, requant, CHW, (long long)B * CHW);
+        } else {
+            TLayer& yb = t->ly[l - 1];
+            float* ZA = y.ZA + (long long)tp * B * 4 * CHW;
+            conv(st, ZA, y.C, yb.H, yb.W, B, prm + t->lp[l].ab, 0,
+                 {src(yb.E + (long long)tp * B * 2 * yb.C * yb.HW, 2 * yb.C * yb.HW, 2 * yb.C, 0, prm + t->lp[l].aW, 0)});
+            hipLaunchKernelGGL(terr_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const uint8_t*)nullptr, 0ll, (const float*)ZA, Pp, E, y.C, y.H, y.W, B);
         }
     }
+    for (int l = L - 1; l >= 0; --l) {
+        TLayer& y = t->ly[l];
+        const LayerParams& p = t->lp[l];
+        const long long CHW = y.C * y.HW;
+        float* G = y.G + (long long)tp * B * 4 * CHW;
+        const TSrc se = src(y.E + (long long)tp * B * 2 * CHW, 2 * CHW, 2 * y.C, 0, prm + p.x0, 0);
+        const TSrc sh = src(y.h + (long long)in * B * CHW, CHW, y.C, 0, prm + p.hW, 0);
+        if (l < L - 1) {
+            const TLayer& ya = t->ly[l + 1];
+            const TSrc su = src(ya.h + (long long)out * B * ya.C * ya.HW, ya.C * ya.HW, ya.C, 1, prm + p.x1, 0);
+            conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, su, sh});
+        } else {
+            conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, sh});
+        }
+        const float* pk = prm + p.peep;
+        hipLaunchKernelGGL(tlstm_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, G, (const float*)(y.c + (long long)in * B * CHW),
+                           y.c + (long long)out * B * CHW, y.h + (long long)out * B * CHW, pk, pk + CHW, pk + 2 * CHW, y.C, (int)y.HW, B);
+        float* P = y.P + (long long)out * B * CHW;
+        conv(st, P, y.C, y.H, y.W, B, prm + p.pb, 0, {src(y.h + (long long)out * B * CHW, CHW, y.C, 0, prm + p.pW, 0)});
+        hipLaunchKernelGGL(tpact_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (long long)B * CHW, l == 0 ? 1 : 0, l == 0 ? pred : (float*)nullptr, CHW,
+                           pred_bstride);
+    }
+}
 
-    // ---- loss
+// mse of n consecutive steps into step_loss[0 .. n): P0 of the first step against the frame x0 it predicts
+static void step_losses(eigen_trainer* t, hipStream_t st, const float* P0, const uint8_t* x0, long long bstride, int n, int B, double* step_loss)
+{
+    const long long C0HW = t->ly[0].C * t->ly[0].HW;
+    hipLaunchKernelGGL(tloss_step_partial_kernel, dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, P0, x0, bstride, B, C0HW, t->d_spart);
+    hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, (double)(B * C0HW), step_loss);
+}
+
+int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                int32_t requant, int32_t reset, const double* h_step_w, double* h_loss, float* d_pred, void* stream)
+{
+    int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, t ? t->cfg.max_steps : 0);
+    if (rc) return rc;
+    const int L = t->L, T = n_steps, B = batch;
+    const long long C0HW = t->ly[0].C * t->ly[0].HW;
+    double sum_w = 0.0;
+    if (h_step_w) {
+        for (int s = 0; s < T - 1; ++s) {
+            if (!(h_step_w[s] >= 0.0) || !std::isfinite(h_step_w[s])) return tfail(EIGEN_ERR_INVALID, "step weight %d is %g: weights must be finite and >= 0", s, h_step_w[s]);
+            sum_w += h_step_w[s];
+        }
+        if (T >= 2 && !(sum_w > 0.0)) return tfail(EIGEN_ERR_INVALID, "all %d step weights are zero", T - 1);
+    }
+    TCHK(hipSetDevice(t->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const float* prm = t->prm;
+    float* grd = t->grd;
+
+    rc = start_state(t, st, B, reset);
+    if (rc) return rc;
+
+    // ---- forward with tape: step s reads slot s of h, c, P and writes slot s + 1
+    for (int s = 0; s < T; ++s)
+        forward_step(t, st, B, s, s + 1, s, s < n_fed ? d_frames + (long long)s * C0HW : nullptr, bstride, requant,
+                     d_pred ? d_pred + (long long)s * C0HW : nullptr, (long long)T * C0HW);
+
+    // ---- loss.  Without weights: one sum over all terms; with weights: one mse per step, combined on the host in step order
     const long long n_terms = (long long)(T - 1) * B * C0HW;
-    if (T >= 2) {
+    if (T >= 2 && !h_step_w) {
         hipLaunchKernelGGL(tloss_partial_kernel, dim3(LOSS_BLOCKS), dim3(EW_T), 0, st, (const float*)t->ly[0].P, d_frames, (long long)bstride, T - 1, B, C0HW, t->d_part);
         hipLaunchKernelGGL(tloss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)t->d_part, LOSS_BLOCKS, 1.0 / (double)n_terms, t->d_loss);
+    } else if (T >= 2) {
+        step_losses(t, st, t->ly[0].P + (long long)B * C0HW, d_frames + C0HW, bstride, T - 1, B, t->d_step);
     } else {
         TCHK(hipMemsetAsync(t->d_loss, 0, 8, st));
     }
-    const float loss_scale = T >= 2 ? (float)(2.0 / (double)n_terms) : 0.f;
+    // d loss / d P0_s = loss_scale(s) * (P0_s - x_{s+1})
+    auto loss_scale = [&](int s) -> float {
+        if (T < 2) return 0.f;
+        if (!h_step_w) return (float)(2.0 / (double)n_terms);
+        return (float)(2.0 * h_step_w[s] / (sum_w * (double)(B * C0HW)));
+    };
 
     // ---- backward through time
     for (int l = 0; l < L; ++l) {
@@ -411,8 +472,8 @@ int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t b
             const float* P = y.P + (long long)(s + 1) * B * CHW;
             float* dV = y.dV + (long long)s * B * CHW;
             const uint8_t* xn = (l == 0 && s < T - 1) ? d_frames + (long long)(s + 1) * C0HW : nullptr;
-            hipLaunchKernelGGL(tpact_bwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (const float*)y.dPn, xn, (long long)bstride, CHW, loss_scale,
-                               l == 0 ? 1 : 0, (long long)B * CHW, dV);
+            hipLaunchKernelGGL(tpact_bwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (const float*)y.dPn, xn, (long long)bstride, CHW,
+                               xn ? loss_scale(s) : 0.f, l == 0 ? 1 : 0, (long long)B * CHW, dV);
             conv(st, y.dhP, y.C, y.H, y.W, B, nullptr, 0, {src(dV, CHW, y.C, 0, prm + p.pW, 1)});
             float* G = y.G + (long long)s * B * 4 * CHW;
             const float* pk = prm + p.peep;
@@ -424,6 +485,8 @@ int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t b
             conv(st, y.dE, 2 * y.C, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x0, 1)});
             if (l < L - 1) conv(st, t->ly[l + 1].dup, y.Ca, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x1, 1)});
         }
+        // the error units, top down; layer 0 sends dE_0 into dP0_{s-1} under the mask E_0 > 0 on every step: on a teacher-forced
+        // step the other path ends in the frame, on a self-fed one in the constant fed-back value
         for (int l = L - 1; l >= 0; --l) {
             TLayer& y = t->ly[l];
             const long long CHW = y.C * y.HW;
@@ -463,10 +526,123 @@ int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t b
     TCHK(hipGetLastError());
     t->state_batch = B;
     t->state_slot = T;
-    if (h_loss) {
+    if (h_loss && h_step_w && T >= 2) {
+        std::vector<double> sl(T - 1);
+        TCHK(hipMemcpyAsync(sl.data(), t->d_step, (T - 1) * 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+        double acc = 0.0;
+        for (int s = 0; s < T - 1; ++s) {
+            const double term = h_step_w[s] * sl[s];
+            acc += term;
+        }
+        *h_loss = acc / sum_w;
+    } else if (h_loss) {
         TCHK(hipMemcpyAsync(h_loss, t->d_loss, 8, hipMemcpyDeviceToHost, st));
         TCHK(hipStreamSynchronize(st));
     }
+    return EIGEN_OK;
+}
+
+int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                            int32_t reset, double* h_loss, float* d_pred, void* stream)
+{
+    return eigen_trainer_loss_grad_ext(t, d_frames, bstride, batch, n_steps, n_steps, 0, reset, nullptr, h_loss, d_pred, stream);
+}
+
+int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                           int32_t requant, int32_t reset, double* h_step_loss, float* d_pred, void* stream)
+{
+    int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, -1);
+    if (rc) return rc;
+    const int T = n_steps, B = batch, M = t->cfg.max_steps;
+    const long long C0HW = t->ly[0].C * t->ly[0].HW;
+    TCHK(hipSetDevice(t->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    rc = start_state(t, st, B, reset);
+    if (rc) return rc;
+    // slots 0 and 1 of h, c, P in turn, slot 0 of E, gates and ZA; the loss of step s goes to d_step[s % max_steps], read back
+    // whenever that table is full
+    for (int s = 0; s < T; ++s) {
+        const int in = s & 1, out = in ^ 1;
+        forward_step(t, st, B, in, out, 0, s < n_fed ? d_frames + (long long)s * C0HW : nullptr, bstride, requant,
+                     d_pred ? d_pred + (long long)s * C0HW : nullptr, (long long)T * C0HW);
+        if (s < T - 1) {
+            step_losses(t, st, t->ly[0].P + (long long)out * B * C0HW, d_frames + (long long)(s + 1) * C0HW, bstride, 1, B, t->d_step + s % M);
+            if (h_step_loss && (s % M == M - 1 || s == T - 2)) {
+                const int first = s - s % M;
+                TCHK(hipMemcpyAsync(h_step_loss + first, t->d_step, (s - first + 1) * 8, hipMemcpyDeviceToHost, st));
+            }
+        }
+    }
+    TCHK(hipGetLastError());
+    t->state_batch = B;
+    t->state_slot = T & 1;
+    if (h_step_loss) TCHK(hipStreamSynchronize(st));
+    return EIGEN_OK;
+}
+
+// Adam moments, step count and the kept sequence state, out.  h_m / h_v: host tables in eigen_set_prednet_weights order (both or
+// neither); h_seq: 3 * n_layers host arrays (h, c, P of layer 0, then of layer 1, ...), each [*seq_batch][C_l][H_l][W_l].
+int eigen_trainer_get_state(eigen_trainer* t, float* const* h_m, float* const* h_v, int32_t n_tensors, int32_t* adam_t, int32_t* seq_batch,
+                            float* const* h_seq, int32_t n_seq)
+{
+    if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    if ((h_m == nullptr) != (h_v == nullptr)) return tfail(EIGEN_ERR_INVALID, "h_m and h_v go together");
+    if (h_seq && n_seq != 3 * t->L) return tfail(EIGEN_ERR_INVALID, "expected %d state arrays for %d layers, got %d", 3 * t->L, t->L, n_seq);
+    if (h_m) {
+        int rc = copy_tables(t, t->mom, nullptr, h_m, n_tensors);
+        if (!rc) rc = copy_tables(t, t->var, nullptr, h_v, n_tensors);
+        if (rc) return rc;
+    }
+    if (adam_t) *adam_t = t->adam_t;
+    if (seq_batch) *seq_batch = t->state_batch;
+    if (h_seq && t->state_batch > 0) {
+        TCHK(hipSetDevice(t->cfg.device));
+        TCHK(hipDeviceSynchronize());
+        for (int l = 0; l < t->L; ++l) {
+            TLayer& y = t->ly[l];
+            const long long n = (long long)t->state_batch * y.C * y.HW;
+            float* a[3] = {y.h, y.c, y.P};
+            for (int k = 0; k < 3; ++k) {
+                if (!h_seq[3 * l + k]) return tfail(EIGEN_ERR_INVALID, "state array %d is NULL", 3 * l + k);
+                TCHK(hipMemcpy(h_seq[3 * l + k], a[k] + t->state_slot * n, n * 4, hipMemcpyDeviceToHost));
+            }
+        }
+    }
+    return EIGEN_OK;
+}
+
+int eigen_trainer_set_state(eigen_trainer* t, const float* const* h_m, const float* const* h_v, int32_t n_tensors, int32_t adam_t, int32_t seq_batch,
+                            const float* const* h_seq, int32_t n_seq)
+{
+    if (!t || !h_m || !h_v) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    if (adam_t < 0) return tfail(EIGEN_ERR_INVALID, "adam_t %d < 0", adam_t);
+    if (seq_batch < 0) return tfail(EIGEN_ERR_INVALID, "seq_batch %d < 0", seq_batch);
+    if (seq_batch > t->cfg.max_batch) return tfail(EIGEN_ERR_CAPACITY, "seq_batch %d exceeds the trainer's %d", seq_batch, t->cfg.max_batch);
+    if (seq_batch > 0) {
+        if (!h_seq) return tfail(EIGEN_ERR_INVALID, "seq_batch %d without state arrays", seq_batch);
+        if (n_seq != 3 * t->L) return tfail(EIGEN_ERR_INVALID, "expected %d state arrays for %d layers, got %d", 3 * t->L, t->L, n_seq);
+        for (int i = 0; i < n_seq; ++i) if (!h_seq[i]) return tfail(EIGEN_ERR_INVALID, "state array %d is NULL", i);
+    }
+    std::vector<std::pair<long long, long long>> tab;
+    tensor_table(t, tab);
+    if (n_tensors != (int32_t)tab.size()) return tfail(EIGEN_ERR_INVALID, "expected %d weight tensors for %d layers, got %d", (int)tab.size(), t->L, n_tensors);
+    for (int i = 0; i < n_tensors; ++i) if (!h_m[i] || !h_v[i]) return tfail(EIGEN_ERR_INVALID, "tensor %d is NULL", i);
+    int rc = copy_tables(t, t->mom, h_m, nullptr, n_tensors);
+    if (!rc) rc = copy_tables(t, t->var, h_v, nullptr, n_tensors);
+    if (rc) return rc;
+    t->adam_t = adam_t;
+    t->state_batch = 0;
+    t->state_slot = 0;
+    for (int l = 0; seq_batch > 0 && l < t->L; ++l) {
+        TLayer& y = t->ly[l];
+        const long long n = (long long)seq_batch * y.C * y.HW;
+        float* a[3] = {y.h, y.c, y.P};
+        for (int k = 0; k < 3; ++k) TCHK(hipMemcpy(a[k], h_seq[3 * l + k], n * 4, hipMemcpyHostToDevice));
+    }
+    t->state_batch = seq_batch;
     return EIGEN_OK;
 }
 

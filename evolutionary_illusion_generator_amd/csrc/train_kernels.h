@@ -266,6 +266,21 @@ __global__ void __launch_bounds__(EW_T) terr_fwd_kernel(const uint8_t* __restric
     e[(long long)C * HW] = fmaxf(p - A, 0.f);
 }
 
+// Image-layer error unit of a self-fed step: the input is the previous prediction P0 itself (requant = 0: E is exactly zero)
+// or the byte the inference engine would emit for it, over 255 (requant = 1; the statement of EPI_CONVP and e0_resume_kernel in
+// conv_mfma.h).  The fed-back value is a constant of the graph; terr_bwd_kernel sends dE into dP under the mask E > 0.
+__global__ void __launch_bounds__(EW_T) terr_fed_fwd_kernel(const float* __restrict__ P, float* __restrict__ E, int requant, long long per_b, long long n)
+{
+    const long long i = (long long)blockIdx.x * EW_T + threadIdx.x;
+    if (i >= n) return;
+    const long long b = i / per_b;
+    const float v = P[i];
+    const float A = requant ? (float)(uint8_t)(int)(v * 255.0f) / 255.0f : v;
+    float* e = E + b * 2 * per_b + (i - b * per_b);
+    e[0] = fmaxf(A - v, 0.f);
+    e[per_b] = fmaxf(v - A, 0.f);
+}
+
 // Backward of E = [relu(A - P), relu(P - A)] (relu'(0) = 0: a unit that is zero passes nothing): dP_prev = -dA.  For l > 0 the
 // max-pool / ReLU backward follows: dA goes to the first maximum of the 2x2 window of relu(ZA) in row-major order, where ZA > 0;
 // ZA is overwritten with dZA (each thread owns its window).
@@ -388,7 +403,8 @@ __global__ void __launch_bounds__(EW_T) tpact_fwd_kernel(float* P, long long n, 
 }
 
 // dV = (dP + dloss) * act'(V).  The activation's derivative is read off P: clamp passes where 0 < v < 1 (0 < P < 1), relu where
-// v > 0 (P > 0).  dloss (layer 0, steps 0..T-2) = 2 (P0_t - x_{t+1}) / n_terms with frame t + 1 of sample b at x + b * xbstride.
+// v > 0 (P > 0).  dloss (layer 0, steps 0..T-2) = loss_scale (P0_t - x_{t+1}) with frame t + 1 of sample b at x + b * xbstride;
+// loss_scale is per launch, i.e. per step: 2 / n_terms without step weights, 2 w_t / (sum w * numel) with them.
 __global__ void __launch_bounds__(EW_T) tpact_bwd_kernel(const float* __restrict__ P, const float* __restrict__ dP, const uint8_t* __restrict__ x,
                                                          long long xbstride, long long per_b, float loss_scale, int clamp01, long long n,
                                                          float* __restrict__ dV)
@@ -435,6 +451,42 @@ __global__ void __launch_bounds__(64) tloss_final_kernel(const double* __restric
     double s = 0.0;
     for (int k = 0; k < n; ++k) s += part[k];
     out[0] = s * scale;
+}
+
+// per-step loss partials: block (k, t) sums (P0_t - x_{t+1})^2 over its fixed strided slice of the (b, element) terms of step t
+// in double, then a fixed LDS tree; part[t][k].  P0 points at the prediction of the first step, x at the frame it is compared
+// with; step t is P0 + t * B * per_b against x + t * per_b.
+__global__ void __launch_bounds__(EW_T) tloss_step_partial_kernel(const float* __restrict__ P0, const uint8_t* __restrict__ x, long long xbstride,
+                                                                  int B, long long per_b, double* __restrict__ part)
+{
+    __shared__ double red[EW_T];
+    const int t = blockIdx.y;
+    const long long n = (long long)B * per_b;
+    const float* p = P0 + (long long)t * n;
+    const uint8_t* xt = x + (long long)t * per_b;
+    double s = 0.0;
+    for (long long i = (long long)blockIdx.x * EW_T + threadIdx.x; i < n; i += (long long)gridDim.x * EW_T) {
+        const long long b = i / per_b;
+        const double d = (double)p[i] - (double)((float)xt[b * xbstride + (i - b * per_b)] / 255.0f);
+        s += d * d;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = EW_T / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[(long long)t * gridDim.x + blockIdx.x] = red[0];
+}
+
+// step_loss[t] = (part[t][0] + part[t][1] + ... in order) / numel, one thread per step
+__global__ void __launch_bounds__(64) tloss_step_final_kernel(const double* __restrict__ part, int nblk, int n_steps, double numel, double* __restrict__ step_loss)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= n_steps) return;
+    double s = 0.0;
+    for (int k = 0; k < nblk; ++k) s += part[(long long)t * nblk + k];
+    step_loss[t] = s / numel;
 }
 
 // Adam as chainer defines it: m += (1 - b1) (g - m); v += (1 - b2) (g^2 - v); p -= lr_t m / (sqrt(v) + eps).  omb1 = 1 - b1 and

@@ -24,10 +24,106 @@ def _bind(lib):
         return
     lib.eigen_trainer_loss_grad.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p]
+    lib.eigen_trainer_loss_grad_ext.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
+                                                ctypes.c_void_p]
+    lib.eigen_trainer_evaluate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int32]
+    lib.eigen_trainer_set_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_int32]
     lib.eigen_trainer_adam.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]
     lib.eigen_trainer_tape_bytes.restype = ctypes.c_int64
     lib.eigen_trainer_tape_bytes.argtypes = [ctypes.c_void_p]
     lib._trainer_bound = True
+
+HYPER = ("alpha", "beta1", "beta2", "eps")
+SEQ_PARTS = ("h", "c", "P")
+
+
+def seq_state_shapes(channels, w, h, batch):
+    """Shapes of the kept sequence state: [(batch, C_l, H_l, W_l) for each layer]."""
+    return [(int(batch), int(c), int(h) >> l, int(w) >> l) for l, c in enumerate(channels)]
+
+
+def check_state(state, channels, w, h, max_batch=None):
+    """Validate a ``PredNetTrainer.state_dict()``-shaped dict against a network; returns it with every array float32 and
+    contiguous.  Raises ValueError on a missing or extra tensor, a wrong shape or a non-float dtype."""
+    shapes = tensor_shapes(channels, w, h)
+    out = {"adam_t": int(state["adam_t"]), "hyper": {k: float(v) for k, v in dict(state.get("hyper") or {}).items()}}
+    if out["adam_t"] < 0:
+        raise ValueError("adam_t must be >= 0, got %d" % out["adam_t"])
+    for key in ("adam_m", "adam_v"):
+        tab = state[key]
+        if sorted(tab) != sorted(shapes):
+            raise ValueError("%s holds %d tensors, expected the %d of %d layers" % (key, len(tab), len(shapes), len(channels)))
+        out[key] = {}
+        for n, shp in shapes.items():
+            a = np.asarray(tab[n])
+            if a.dtype.kind != "f" or a.shape != shp:
+                raise ValueError("%s[%r] is %s %s, expected float32 %s" % (key, n, a.dtype, a.shape, shp))
+            out[key][n] = np.ascontiguousarray(a, dtype=np.float32)
+    seq = state.get("seq")
+    out["seq"] = None
+    if seq is not None:
+        if sorted(seq) != sorted(SEQ_PARTS) or any(len(seq[k]) != len(channels) for k in SEQ_PARTS):
+            raise ValueError("seq must hold h, c and P with one array per layer (%d)" % len(channels))
+        batch = int(np.asarray(seq["h"][0]).shape[0]) if np.asarray(seq["h"][0]).ndim == 4 else -1
+        if batch < 1 or (max_batch is not None and batch > max_batch):
+            raise ValueError("sequence state of batch %d does not fit this trainer (batch %s)" % (batch, max_batch))
+        want = seq_state_shapes(channels, w, h, batch)
+        out["seq"] = {}
+        for k in SEQ_PARTS:
+            out["seq"][k] = []
+            for l, shp in enumerate(want):
+                a = np.asarray(seq[k][l])
+                if a.dtype.kind != "f" or a.shape != shp:
+                    raise ValueError("seq[%r][%d] is %s %s, expected float32 %s" % (k, l, a.dtype, a.shape, shp))
+                out["seq"][k].append(np.ascontiguousarray(a, dtype=np.float32))
+    return out
+
+
+def write_checkpoint(path, weights, state):
+    """ONE npz: the weights under the ``predictor/<name>`` keys of ``weights.save_chainer_npz`` (so ``weights.load_chainer_npz``
+    reads the file), plus ``adam/m/<name>``, ``adam/v/<name>``, ``adam/t``, ``hyper/<alpha|beta1|beta2|eps>`` and, when a sequence
+    state is kept, ``seq/<h|c|P>/<layer>``."""
+    arrs = {"predictor/" + k: np.ascontiguousarray(v, dtype=np.float32) for k, v in weights.items()}
+    for k, v in state["adam_m"].items():
+        arrs["adam/m/" + k] = np.ascontiguousarray(v, dtype=np.float32)
+    for k, v in state["adam_v"].items():
+        arrs["adam/v/" + k] = np.ascontiguousarray(v, dtype=np.float32)
+    arrs["adam/t"] = np.asarray(int(state["adam_t"]), np.int64)
+    for k, v in (state.get("hyper") or {}).items():
+        arrs["hyper/" + k] = np.asarray(float(v), np.float64)
+    if state.get("seq") is not None:
+        for part in SEQ_PARTS:
+            for l, a in enumerate(state["seq"][part]):
+                arrs["seq/%s/%d" % (part, l)] = np.ascontiguousarray(a, dtype=np.float32)
+    with open(path, "wb") as f:   # (a file object: np.savez would append .npz to a bare name)
+        np.savez(f, **arrs)
+
+
+def read_checkpoint(path, channels, w, h):
+    """-> (weights, state) of a ``write_checkpoint`` file, every shape checked against the network (ValueError / KeyError)."""
+    from .weights import load_chainer_npz
+    wts = load_chainer_npz(path, channels, w, h)
+    with np.load(path) as z:
+        files = set(z.files)
+        for n in wts:
+            for mv in "mv":
+                if "adam/%s/%s" % (mv, n) not in files:
+                    raise KeyError("checkpoint %s lacks adam/%s/%s" % (path, mv, n))
+        if "adam/t" not in files:
+            raise KeyError("checkpoint %s lacks adam/t" % path)
+        state = {"adam_m": {n: z["adam/m/" + n] for n in wts}, "adam_v": {n: z["adam/v/" + n] for n in wts}, "adam_t": int(z["adam/t"]),
+                 "hyper": {k: float(z["hyper/" + k]) for k in HYPER if "hyper/" + k in files}, "seq": None}
+        if "seq/h/0" in files:
+            try:
+                state["seq"] = {part: [z["seq/%s/%d" % (part, l)] for l in range(len(channels))] for part in SEQ_PARTS}
+            except KeyError as e:
+                raise KeyError("checkpoint %s: incomplete sequence state (%s)" % (path, e))
+    return wts, check_state(state, channels, w, h)
 
 
 class PredNetTrainer:
@@ -104,20 +200,52 @@ class PredNetTrainer:
         _check_sequence_frames(frames, self.channels, self.w, self.h)
         return torch.from_numpy(np.ascontiguousarray(frames)).cuda(self.device)
 
-    def forward_backward(self, frames, reset=True, pred=False, stream=None):
+    def _fed(self, n_fed, T):
+        return T if n_fed is None else int(n_fed)   # (the range rules are the library's: EngineError -1)
+
+    def forward_backward(self, frames, reset=True, pred=False, stream=None, n_fed=None, requant=False, step_weights=None):
         """Loss of frames uint8 [n, T, C, H, W] (numpy or a device tensor, n <= batch) and the gradients, kept on the device
         (``grads()``).  reset=False continues from the state the previous call left (the same n), as a constant.
-        pred=True also returns the float predictions P0 [n, T, C, H, W] (numpy)."""
+        pred=True also returns the float predictions P0 [n, T, C, H, W] (numpy).
+
+        n_fed: the first n_fed steps read their frame, the rest are fed the previous prediction (None: all T read theirs);
+        requant: feed the prediction back through the byte the inference engine emits, as a constant; step_weights: T - 1
+        weights >= 0 of the loss terms (term s: prediction s against frame s + 1), None: all one."""
         d = self._frames(frames)
         n, T = int(d.shape[0]), int(d.shape[1])
+        n_fed = self._fed(n_fed, T)
+        w_arr = None
+        if step_weights is not None:
+            w_arr = np.ascontiguousarray(step_weights, dtype=np.float64)
+            if w_arr.shape != (T - 1,):
+                raise ValueError("step_weights must have T - 1 = %d entries, got shape %s" % (T - 1, w_arr.shape))
         loss = ctypes.c_double(0.0)
         d_pred = self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
-        _check(self.lib.eigen_trainer_loss_grad(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n),
-                                                ctypes.c_int32(T), ctypes.c_int32(int(bool(reset))), ctypes.byref(loss), _ptr(d_pred),
-                                                _stream_arg(stream)))
+        _check(self.lib.eigen_trainer_loss_grad_ext(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n),
+                                                    ctypes.c_int32(T), ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))),
+                                                    ctypes.c_int32(int(bool(reset))), ctypes.c_void_p(w_arr.ctypes.data if w_arr is not None and w_arr.size else None),
+                                                    ctypes.byref(loss), _ptr(d_pred), _stream_arg(stream)))
         if pred:
             return loss.value, d_pred.cpu().numpy()
         return loss.value
+
+    def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False):
+        """Forward only, no tape: the mean squared error of every step of frames uint8 [n, T, C, H, W], T of any length, as
+        float64 [T - 1] (entry s: prediction s against frame s + 1).  Gradients and Adam state are untouched; the kept sequence
+        state is shared with forward_backward (reset=False of either continues the last call of either).  pred=True also
+        returns the float predictions [n, T, C, H, W]."""
+        d = self._frames(frames)
+        n, T = int(d.shape[0]), int(d.shape[1])
+        n_fed = self._fed(n_fed, T)
+        out = np.zeros(max(T - 1, 1), np.float64)
+        d_pred = self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
+        _check(self.lib.eigen_trainer_evaluate(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n), ctypes.c_int32(T),
+                                               ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))), ctypes.c_int32(int(bool(reset))),
+                                               ctypes.c_void_p(out.ctypes.data), _ptr(d_pred), None))
+        out = out[:T - 1]
+        if pred:
+            return out, d_pred.cpu().numpy()
+        return out
 
     def loss_and_grad(self, frames, reset=True):
         """(loss, {name: gradient}) of frames uint8 [n, T, C, H, W]; overwrites the gradients."""
@@ -128,11 +256,60 @@ class PredNetTrainer:
         """One Adam step on the current gradients."""
         _check(self.lib.eigen_trainer_adam(self._h, self.alpha, self.beta1, self.beta2, self.eps, _stream_arg(stream)))
 
-    def step(self, frames, reset=True):
+    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None):
         """Gradient and one Adam step; returns the loss before the step."""
-        loss = self.forward_backward(frames, reset)
+        loss = self.forward_backward(frames, reset, n_fed=n_fed, requant=requant, step_weights=step_weights)
         self.adam()
         return loss
+
+    # -- state in and out ------------------------------------------------------------------------------
+    def state_dict(self):
+        """Everything a continued run needs besides ``weights()``: {"adam_m", "adam_v": {name: float32 array}, "adam_t": int,
+        "hyper": {alpha, beta1, beta2, eps}, "seq": None or {"h", "c", "P": [one float32 [n, C_l, H_l, W_l] per layer]}}."""
+        nt = len(self._names)
+        m = {n: np.empty(self._shapes[n], np.float32) for n in self._names}
+        v = {n: np.empty(self._shapes[n], np.float32) for n in self._names}
+        tm = (ctypes.c_void_p * nt)(*[m[n].ctypes.data for n in self._names])
+        tv = (ctypes.c_void_p * nt)(*[v[n].ctypes.data for n in self._names])
+        t, nb = ctypes.c_int32(0), ctypes.c_int32(0)
+        _check(self.lib.eigen_trainer_get_state(self._h, tm, tv, ctypes.c_int32(nt), ctypes.byref(t), ctypes.byref(nb), None, ctypes.c_int32(0)))
+        seq = None
+        if nb.value > 0:
+            shp = seq_state_shapes(self.channels, self.w, self.h, nb.value)
+            seq = {k: [np.empty(s, np.float32) for s in shp] for k in SEQ_PARTS}
+            flat = [seq[k][l] for l in range(len(shp)) for k in SEQ_PARTS]
+            ts = (ctypes.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
+            _check(self.lib.eigen_trainer_get_state(self._h, None, None, ctypes.c_int32(0), None, None, ts, ctypes.c_int32(len(flat))))
+        return {"adam_m": m, "adam_v": v, "adam_t": int(t.value), "hyper": {k: float(getattr(self, k)) for k in HYPER}, "seq": seq}
+
+    def load_state_dict(self, state):
+        """Restore a ``state_dict()`` (after ``set_weights``, which clears all of it).  Shapes and dtypes are checked before
+        anything reaches the device (ValueError); the hyper-parameters, when present, replace this trainer's."""
+        st = check_state(state, self.channels, self.w, self.h, self.batch)
+        nt = len(self._names)
+        tm = (ctypes.c_void_p * nt)(*[st["adam_m"][n].ctypes.data for n in self._names])
+        tv = (ctypes.c_void_p * nt)(*[st["adam_v"][n].ctypes.data for n in self._names])
+        ts, ns, nb = None, 0, 0
+        if st["seq"] is not None:
+            flat = [st["seq"][k][l] for l in range(len(self.channels)) for k in SEQ_PARTS]
+            ts, ns, nb = (ctypes.c_void_p * len(flat))(*[a.ctypes.data for a in flat]), len(flat), flat[0].shape[0]
+        _check(self.lib.eigen_trainer_set_state(self._h, tm, tv, ctypes.c_int32(nt), ctypes.c_int32(st["adam_t"]), ctypes.c_int32(nb), ts,
+                                                ctypes.c_int32(ns)))
+        for k, v in st["hyper"].items():
+            if k in HYPER:
+                setattr(self, k, v)
+
+    def save_checkpoint(self, path):
+        """weights(), state_dict() and the hyper-parameters as one npz (``write_checkpoint``)."""
+        write_checkpoint(path, self.weights(), self.state_dict())
+
+    def load_checkpoint(self, path):
+        """Continue the run ``save_checkpoint`` wrote: the following steps give the bits the saved trainer would have given."""
+        wts, state = read_checkpoint(path, self.channels, self.w, self.h)
+        if state["seq"] is not None and state["seq"]["h"][0].shape[0] > self.batch:
+            raise ValueError("checkpoint keeps a sequence state of batch %d, this trainer holds %d" % (state["seq"]["h"][0].shape[0], self.batch))
+        self.set_weights(wts)
+        self.load_state_dict(state)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -152,4 +329,4 @@ class PredNetTrainer:
         self.close()
 
 
-__all__ = ["PredNetTrainer", "EngineError"]
+__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint"]

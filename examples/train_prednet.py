@@ -2,11 +2,16 @@
 """Train PredNet on the MI355X (next-frame MSE, backprop through time, Adam) and use the result in the fitness path.
 
     python examples/train_prednet.py -o trained.npz [-i frames_dir] [--size 160x120] [-c 3] [--steps 200] [--seq 10] [--batch 8]
+                                     [--ext-steps 200 --ext-frames 4 [--requant]] [--checkpoint ckpt.npz [--every 50]] [--resume ckpt.npz]
 
 Input: the PNG files of a folder, in name order, centre-cropped to --size, cut into windows of --seq frames; without -i, seeded
 drifting patterns (rings moving in a different direction per sequence).  The last window (or a held-out seed) is kept out of
-training.  Prints the held-out loss before and after, writes the weights as a chainer npz (-o), then evaluates one synthetic
-population's fitness with them.
+training.  Phase 1 is teacher-forced: every step reads its frame.  --ext-steps adds a second, self-fed fine-tuning phase: the last
+--ext-frames steps of every sequence read the network's own prediction (through the emitted byte with --requant), the regime the
+fitness path scores; its loss weights only the self-fed predictions.  --checkpoint writes weights, Adam state and step counter as
+one npz every --every steps and at the end; --resume continues such a run bit for bit.  Prints the held-out per-step losses
+(tape-free `evaluate`) before and after, writes the weights as a chainer npz (-o), then evaluates one synthetic population's
+fitness with them.
 """
 import argparse
 import os
@@ -53,6 +58,12 @@ def main():
     ap.add_argument("--seq", type=int, default=10, help="frames per sequence")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--alpha", type=float, default=1e-3)
+    ap.add_argument("--ext-steps", type=int, default=0, help="Adam steps of a second phase whose last --ext-frames steps are self-fed")
+    ap.add_argument("--ext-frames", type=int, default=4, help="self-fed steps at the end of every sequence in the second phase")
+    ap.add_argument("--requant", action="store_true", help="feed predictions back through the emitted byte (cfg.requant_feedback)")
+    ap.add_argument("--checkpoint", default=None, help="write weights + Adam state + step counter here (one npz)")
+    ap.add_argument("--every", type=int, default=50, help="checkpoint period in steps")
+    ap.add_argument("--resume", default=None, help="continue the run a --checkpoint file holds")
     args = ap.parse_args()
     w, h = (int(v) for v in args.size.lower().split("x"))
     channels = [int(c) for c in args.channels.split(",")] if args.channels else [args.color_space, 48, 96, 192]
@@ -65,15 +76,38 @@ def main():
         held = drifting(10 ** 6, args.batch, args.seq, c_dim, w, h)
         batch_of = lambda k: drifting(k, args.batch, args.seq, c_dim, w, h)
 
+    n_fed = args.seq - args.ext_frames if args.ext_steps else args.seq
+    if not 1 <= n_fed <= args.seq or (args.ext_steps and args.seq - n_fed < 1):
+        raise SystemExit("--ext-frames must be in [1, --seq - 1]")
+    # the self-fed phase weights the predictions made by self-fed steps only (term s: prediction s against frame s + 1)
+    ext_w = [0.0] * n_fed + [1.0] * (args.seq - 1 - n_fed)
+    total = args.steps + args.ext_steps
+    fmt = lambda v: " ".join("%.5f" % x for x in v)
+
     with PredNetTrainer(args.model, channels, w, h, args.batch, args.seq, alpha=args.alpha) as tr:
-        before = tr.forward_backward(held)
-        for k in range(args.steps):
-            loss = tr.step(batch_of(k))
-            if k % 50 == 0 or k == args.steps - 1:
-                print("step %4d  train loss %.6f" % (k, loss))
-        after = tr.forward_backward(held)
+        first = 0
+        if args.resume:
+            tr.load_checkpoint(args.resume)
+            first = tr.state_dict()["adam_t"]
+            print("resumed %s at step %d" % (args.resume, first))
+        before = tr.evaluate(held, n_fed=n_fed, requant=args.requant)
+        print("held-out loss per step (%d fed, %d self-fed) before: %s" % (n_fed, args.seq - n_fed, fmt(before)))
+        for k in range(first, total):
+            if k < args.steps:
+                loss = tr.step(batch_of(k))
+            else:
+                loss = tr.step(batch_of(k), n_fed=n_fed, requant=args.requant, step_weights=ext_w if any(ext_w) else None)
+            if k % 50 == 0 or k == total - 1 or k == args.steps:
+                print("step %4d  %s train loss %.6f" % (k, "teacher-forced" if k < args.steps else "self-fed      ", loss))
+            if args.checkpoint and ((k + 1) % args.every == 0 or k == total - 1):
+                tr.save_checkpoint(args.checkpoint)
+        after = tr.evaluate(held, n_fed=n_fed, requant=args.requant)
         trained = tr.weights()
-    print("held-out loss: %.6f before, %.6f after (%.1f %% lower)" % (before, after, 100 * (1 - after / before)))
+    print("held-out loss per step after:  %s" % fmt(after))
+    print("held-out loss, mean over the steps: %.6f before, %.6f after (%.1f %% lower)" % (before.mean(), after.mean(), 100 * (1 - after.mean() / before.mean())))
+    if n_fed < args.seq - 1:
+        b, a = before[n_fed:].sum(), after[n_fed:].sum()
+        print("  self-fed steps alone: %.6f before, %.6f after (%.1f %% lower)" % (b, a, 100 * (1 - a / b)))
     weights.save_chainer_npz(trained, args.output)
     print("weights written to %s" % args.output)
 

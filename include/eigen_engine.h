@@ -301,7 +301,50 @@ int eigen_trainer_get_weights(eigen_trainer* t, float* const* h_tensors, int32_t
 int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
                             int32_t reset, double* h_loss, float* d_pred, void* stream);
 
-/* The gradients of the last eigen_trainer_loss_grad, host tables in eigen_set_prednet_weights order. */
+/* eigen_trainer_loss_grad with self-fed steps, requantised feedback and step weights.
+ * eigen_trainer_loss_grad is this call with n_fed = n_steps, requant = 0, h_step_w = NULL.
+ *   n_fed: steps s < n_fed read frame s (teacher-forced); steps s >= n_fed are self-fed: their input is the prediction
+ *     P0_{s-1} (for s = 0: the kept P0).  0 <= n_fed <= n_steps; n_fed = 0 needs reset = 0.  All n_steps frames are still
+ *     passed: on self-fed steps they are targets only.
+ *   requant: how a prediction is fed back, as eigen_config.requant_feedback: 0 the float P0_{s-1} (E_0 is exactly zero);
+ *     1 the byte the inference engine emits for it over 255, (float)(uint8_t)(int)(v * 255.0f) / 255.0f, a constant of the
+ *     graph: E_0 = [relu(q - P0), relu(P0 - q)] is small, non-zero and sends a gradient into P0_{s-1} (relu'(0) = 0).
+ *   h_step_w: host double[n_steps - 1], >= 0, finite, not all zero, or NULL (all ones).  With mse_s the mean over b, c, y, x of
+ *     (P0_s - x_{s+1})^2: loss = sum_s w_s mse_s / sum_s w_s, added in step order.  With NULL the loss and the gradients are
+ *     those of eigen_trainer_loss_grad to the last bit (one sum over all terms times 1 / ((n_steps-1) numel)); with weights the
+ *     mse_s are the numbers eigen_trainer_evaluate returns and the sum above is done in double on the host.
+ *   A call owns its n_steps - 1 loss terms: the term of its last prediction against the next call's first frame is in no call.
+ * Errors: those of eigen_trainer_loss_grad; EIGEN_ERR_INVALID n_fed outside [0, n_steps], n_fed = 0 with reset = 1, requant not
+ * 0 or 1, a negative / non-finite weight or weights that are all zero. */
+int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, double* h_loss,
+                                float* d_pred, void* stream);
+
+/* Forward only, without a tape: the per-step losses of a sequence of ANY length (n_steps is not bounded by max_steps; batch <=
+ * max_batch).  Arguments as eigen_trainer_loss_grad_ext.  Touches neither the gradients (a following eigen_trainer_adam still
+ * applies those of the last loss_grad) nor the Adam state.  It shares the kept sequence state (h, c, P) with loss_grad: there
+ * is one state per handle, every call of either leaves its final state, and a reset = 0 call of either continues it.
+ *   h_step_loss (host, may be NULL): double[n_steps - 1], the unweighted mse_s of every step.
+ *   d_pred (may be NULL): float [batch][n_steps][C][H][W].
+ * Errors: as eigen_trainer_loss_grad_ext, without the bound on n_steps. */
+int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                           int32_t n_fed, int32_t requant, int32_t reset, double* h_step_loss, float* d_pred, void* stream);
+
+/* Everything a continued run depends on besides the weights.
+ *   h_m, h_v: the Adam first and second moments, host tables in eigen_set_prednet_weights order (get: both or neither).
+ *   adam_t: the step count.  seq_batch: the batch of the kept sequence state, 0 when there is none.
+ *   h_seq: 3 * n_layers host arrays, (h, c, P) of layer 0, then of layer 1, ...: each float [seq_batch][C_l][H_l][W_l].
+ * get_state: every output may be NULL; h_seq is written only when *seq_batch > 0 (call once with h_seq = NULL to size it).
+ * set_state: called after eigen_trainer_set_weights (which clears all of this).  seq_batch = 0 discards the sequence state
+ *   (h_seq may be NULL); otherwise the next reset = 0 call of that batch continues from h_seq.
+ * Errors: EIGEN_ERR_STATE no weights; EIGEN_ERR_INVALID a wrong n_tensors / n_seq, a NULL array, adam_t or seq_batch < 0;
+ * EIGEN_ERR_CAPACITY seq_batch above max_batch. */
+int eigen_trainer_get_state(eigen_trainer* t, float* const* h_m, float* const* h_v, int32_t n_tensors, int32_t* adam_t,
+                            int32_t* seq_batch, float* const* h_seq, int32_t n_seq);
+int eigen_trainer_set_state(eigen_trainer* t, const float* const* h_m, const float* const* h_v, int32_t n_tensors,
+                            int32_t adam_t, int32_t seq_batch, const float* const* h_seq, int32_t n_seq);
+
+/* The gradients of the last eigen_trainer_loss_grad / _ext, host tables in eigen_set_prednet_weights order. */
 int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n_tensors);
 
 /* One Adam step on the current gradients (step count kept by the handle, from 1): m += (1-beta1)(g-m),

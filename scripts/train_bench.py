@@ -1,6 +1,7 @@
 """Time PredNet training steps (train.PredNetTrainer: gradient + Adam) at 160x120 colour, channels [3, 48, 96, 192], batch 16,
 10 frames, then -- in a separate process under its own time limit -- torch-ROCm autograd of the same network and loss
-(F.conv2d, float32) on the same GPU.  Prints one JSON line per side and writes profiles/train_bench.json.
+(F.conv2d, float32) on the same GPU.  Between the two: a step whose last 5 steps are self-fed (float and requantised feedback) and
+the tape-free evaluate of that call.  Prints one JSON line per side and writes profiles/train_bench.json.
 
     python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both]
 """
@@ -62,6 +63,29 @@ def run_trainer(steps, warmup):
                tape_bytes_per_sample_step=tr.tape_bytes / (B * T), conv_flops_per_step=3 * conv_flops_per_sample_step(CH, W, H) * B * T)
     tr.close()
     return res
+
+
+def run_ext(steps, warmup, n_self=5):
+    """a step whose last n_self steps are self-fed (float and requantised feedback), and the tape-free evaluate of the same call"""
+    import torch
+    from evolutionary_illusion_generator_amd import weights
+    from evolutionary_illusion_generator_amd.train import PredNetTrainer
+    d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
+    out = []
+    with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
+        calls = [("trainer_self_fed", lambda: tr.step(d, n_fed=T - n_self)), ("trainer_self_fed_requant", lambda: tr.step(d, n_fed=T - n_self, requant=True)),
+                 ("evaluate", lambda: float(tr.evaluate(d, n_fed=T - n_self).mean()))]
+        for side, call in calls:
+            for _ in range(warmup):
+                call()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                loss = call()
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3 / steps
+            out.append(dict(side=side, n_fed=T - n_self, step_ms=ms, sample_steps_per_s=B * T / ms * 1e3, loss=loss))
+    return out
 
 
 def run_torch(steps, warmup):
@@ -132,6 +156,9 @@ def main():
         return
     res = [run_trainer(a.steps, a.warmup)]
     print(json.dumps(res[0]), flush=True)
+    ext = run_ext(a.steps, a.warmup)
+    for r in ext:
+        print(json.dumps(r), flush=True)
     if a.side == "both":
         # torch in a fresh process of its own: its allocator and MIOpen caches do not share the trainer's process
         cmd = ["timeout", "-k", "10", str(a.torch_timeout), sys.executable, os.path.abspath(__file__), "--side", "torch",
@@ -143,6 +170,7 @@ def main():
         else:
             res.append(json.loads(p.stdout.strip().splitlines()[-1]))
         print(json.dumps(res[1]))
+    res += ext
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(dict(shape=dict(w=W, h=H, channels=CH, batch=B, steps=T), results=res), f, indent=1)
