@@ -16,7 +16,9 @@
 #include "../../include/eigen_engine.h"
 #define EIG_ENGINE_UNIT 1   // (conv_mfma.h: the non-template kernels are defined in this unit)
 #include "conv_mfma.h"
-#include "wino_launch.h"   // the Winograd kernels live in wino4_kernels.hip / wino4t_kernels.hip / wino4h_kernels.hip / wino4h_kernels.hip
+#include "wino_launch.h"   // the Winograd kernels live in wino4_kernels.hip / wino4t_kernels.hip / wino4h_kernels.hip / wino4p_kernels.hip
+#include "weight_pack.h"   // host: weight tensors -> the kernels' layouts
+#include "conv_plan.h"     // host: which operators run (plan_prednet) and in which launch shape (plan_launch)
 #include "cppn_kernel.h"
 #include "farneback_kernels.h"
 #include "flow_kernels.h"
@@ -49,43 +51,13 @@ int eig_set_error(int code, const char* msg)
 
 namespace {
 
-struct ConvOp {
-    int tl_seen = 0;  // EIG_TIMING builds: launches seen (timeline dump)
-    int last_grid = 0, last_waves = 4;  // geometry of the last launch (launch_conv), for the EIG_TIMING read-back
-    int epi = 0, NI = 4, TW = 16, layer = 0;
-    int nsrc = 0;
-    int src_C[3] = {0, 0, 0};
-    int src_Ct[3] = {0, 0, 0};  // channels of the source TENSOR when only its first src_C channels are read (0: = src_C)
-    int H = 0, W = 0, Cout = 0, n_nblk = 0, krows = 0;
-    float* d_wpk = nullptr;
-    float* d_wraw = nullptr;  // image-layer ConvP only: the unpacked OIHW weights for convp0_direct_kernel
-    double macs = 0;  // algorithmic multiply-accumulates per image (real channels only)
-    double ms = 0;    // profiling accumulator
-    int launches = 0;
-    // Winograd ConvLSTM below the top layer: its unpooled source R_{l+1} rides inside the same chains (conv_wino4.h: up_fused)
-    bool fused = false;
-    int up_C = 0, up_kb = 0;
-    bool wino = false;  // Winograd F(4x4, 3x3) form (conv_wino4.h); epi stays the operator's epilogue
-};
-
-struct Layer {
-    int C = 0, H = 0, W = 0;
-    float* h[2] = {nullptr, nullptr};
-    float *c = nullptr, *P = nullptr, *E = nullptr;
-    float *bias_lstm = nullptr, *peep = nullptr, *biasA = nullptr, *biasP = nullptr;
-    ConvOp convA, lstm, convP;
-    // Step-0 operators: after reset_state() h_l = 0 and P_l = 0, hence the second half of every E_l (relu(P - A), A >= 0)
-    // is 0 as well.  Their terms fma(0, w, acc) leave the chain untouched, so the first step runs the same chains over the
-    // non-zero sources only: ConvA reads the first half of E_{l-1}, the ConvLSTM the first half of E_l and R_{l+1}.
-    ConvOp convA_t0, lstm_t0;
-    // The unpooled source R_{l+1} of the ConvLSTM in its 2x2 form (conv_mfma.h: EPI_UP4), launched at the resolution of
-    // layer l+1 ahead of the ConvLSTM launch, which adds the result to its own chain (eigen_engine::d_raw4).
-    ConvOp up4;
-};
-
-template <typename T> struct DevBuf {
+template <typename T> struct DevBuf {   // an owned device allocation that only grows
     T* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t n)
     {
         if (n <= cap) return 0;
@@ -97,6 +69,32 @@ template <typename T> struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+
+static int upload(DevBuf<float>& dst, const float* src, size_t n)
+{
+    if (dst.ensure(n)) return -1;
+    return hipMemcpy(dst.p, src, n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+
+// An operator of the plan (conv_plan.h: OpDesc is its geometry) with its device weights and its counters
+struct ConvOp : OpDesc {
+    DevBuf<float> wpk;   // the packed weights of the form the operator runs
+    DevBuf<float> wraw;  // image layer only (OpDesc::raw): the unpacked table of convp0_direct_kernel / lstm0_direct_kernel
+    double ms = 0;       // profiling accumulator
+    int launches = 0;
+    int tl_seen = 0;     // EIG_TIMING builds: launches seen (timeline dump)
+    int last_grid = 0, last_waves = 4;  // timeline records of the last launch (launch_conv), for the EIG_TIMING read-back
+    void replan(const OpDesc& d) { OpDesc::operator=(d); ms = 0; launches = 0; tl_seen = 0; }   // the allocations stay
+};
+
+struct Layer {
+    int C = 0, H = 0, W = 0;
+    float* h[2] = {nullptr, nullptr};
+    float *c = nullptr, *P = nullptr, *E = nullptr;
+    DevBuf<float> bias_lstm, peep, biasA, biasP;
+    ConvOp convA, lstm, convP, convA_t0, lstm_t0, up4;   // conv_plan.h: LayerPlan
+};
+
 
 }  // namespace
 
@@ -128,8 +126,7 @@ struct eigen_engine {
     float* d_zeros = nullptr;  // DMA source for zero fill (conv_mfma.h)
     // Farneback dense flow (cfg.flow_method == EIGEN_FLOW_FARNEBACK): allocated on first use
     float *fb_I = nullptr, *fb_R0 = nullptr, *fb_R1 = nullptr, *fb_M = nullptr, *fb_V = nullptr, *fb_flow[2] = {nullptr, nullptr};
-    float* d_raw4 = nullptr;   // partial chains of the unpooled source, [B][4 classes][n_nblk*NB][H/2][W/2], reused by all layers
-    size_t raw4_floats = 0;
+    DevBuf<float> raw4;   // partial chains of the unpooled source, [B][4 classes][n_nblk*NB][H/2][W/2], reused by all layers
     // timing
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t pev0 = nullptr, pev1 = nullptr;
@@ -144,7 +141,6 @@ struct eigen_engine {
 };
 
 // ------------------------------------------------------------------------------------------------ helpers
-static int pad4(int c) { return (c + 3) & ~3; }
 
 // ---- Farneback constants (host; the same double-precision recipe as oracle/farneback.c, checked by tests/test_gpu_parity.py) ----
 static int fb_levels_used(int H, int W, int levels)  // calcOpticalFlowFarneback: no level below 32 pixels
@@ -226,142 +222,7 @@ static FbConst fb_poly_constants(int n, double sigma)  // FarnebackPrepareGaussi
     return c;
 }
 
-static void choose_ni(int Cout, bool lstm, int* NI, int* n_nblk)
-{
-    if (lstm) { *NI = 4; *n_nblk = (Cout + 15) / 16; return; }
-    int best = 1; double beste = -1;
-    for (int ni = 1; ni <= 4; ++ni) {
-        const int nb = (Cout + 16 * ni - 1) / (16 * ni);
-        const double eff = (double)Cout / (nb * 16.0 * ni) + 1e-3 * ni;  // ties -> larger tile
-        if (eff > beste) { beste = eff; best = ni; }
-    }
-    *NI = best; *n_nblk = (Cout + 16 * best - 1) / (16 * best);
-}
-
-// Tile shape of an operator: 16 x 16, or 8 x 8 where that covers the map at least 15 % better.
-static int choose_tw(int H, int W)
-{
-    auto util = [&](int tw) {
-        const int th = (tw == 8) ? 8 : 16;
-        const int ty = (H + th - 1) / th, tx = (W + tw - 1) / tw;
-        return (double)H * W / ((double)ty * th * tx * tw);
-    };
-    // 16 x 16 tiles unless 8 x 8 tiles cover the map at least 15 % better: the 8-wide instantiations have no branch-free staging path
-    // and a conflicted LDS row stride (conv_mfma.h) -- measured at 160 x 120 maps (640x480 colour, layer 2: profiles/r04_c_perop_shapes.txt):
-    // 8 x 8 tiles at 100 % cover ran at 0.78 of peak, 16 x 16 tiles at 93.75 % cover at 0.86.  EIGEN_TW8_FACTOR for A/Bs.
-    static const double tw8_factor = getenv("EIGEN_TW8_FACTOR") ? atof(getenv("EIGEN_TW8_FACTOR")) : 1.15;
-    const int sq = (util(16) * tw8_factor + 1e-9 >= util(8)) ? 16 : 8;
-    return sq;
-}
-
-// Pack OIHW weights of one fused conv into [n_nblk][krows][NB]; row = (source, channel (padded to 4), tap).
-// srcw[s][g] points at [Cout][Cin_s][3][3]; g = 0 for plain convs, 0..3 (i,f,c,o) for the LSTM.
-// lstm: 0 plain conv, 1 gates as four 16-channel tiles (column = gate*16 + channel), 2 packed for C <= 4
-// (ONE 16-column tile, column = gate*4 + channel).
-static std::vector<float> pack_weights(const ConvOp& op, const float* const srcw[3][4], int lstm)
-{
-    const int NB = op.NI * 16;
-    std::vector<float> out((size_t)op.n_nblk * op.krows * NB, 0.0f);
-    for (int nb = 0; nb < op.n_nblk; ++nb) {
-        size_t row = 0;
-        for (int s = 0; s < op.nsrc; ++s) {
-            const int Cin = op.src_C[s], Cp = pad4(Cin);
-            const int Cw = op.src_Ct[s] ? op.src_Ct[s] : Cin;  // input channels of the weight tensor
-            for (int c = 0; c < Cp; ++c)
-                for (int tap = 0; tap < 9; ++tap, ++row) {
-                    if (c >= Cin) continue;
-                    float* dst = &out[((size_t)nb * op.krows + row) * NB];
-                    for (int n = 0; n < NB; ++n) {
-                        int g = 0, o;
-                        if (lstm == 1) { g = n / 16; o = nb * 16 + (n % 16); }
-                        else if (lstm == 2) { g = n / 4; o = n % 4; }
-                        else o = nb * NB + n;
-                        if (o >= op.Cout) continue;
-                        // LDS/slab column order: [16 lanes (n % 16)][NI tiles (n / 16)] so that a lane reads its NI values
-                        // of a row with one ds_read_b128 (conv_mfma.h: boff)
-                        dst[(n % 16) * op.NI + (n / 16)] = srcw[s][g][((size_t)o * Cw + c) * 9 + tap];
-                    }
-                }
-        }
-    }
-    return out;
-}
-
-// Weights of the 2x2 form of `unpool x2 -> conv3x3` for parity class (py, px) of the output pixel (oracle/eig_oracle.c:
-// presum_up_weights states the same rule).  Output row 2Y+py reads source rows Y-1, Y, Y (py = 0) or Y, Y, Y+1 (py = 1): tap a
-// stands for source row Y+a-1+py and collects ky in {0} / {1,2} (py = 0) or {0,1} / {2} (py = 1); columns likewise.  The
-// collected weights are added in fp32 in (ky, kx) row-major order starting from the first one.
-static float presum_up_weight(const float* w9, int py, int px, int a, int b)
-{
-    const int ky0 = py ? (a ? 2 : 0) : (a ? 1 : 0), ky1 = py ? (a ? 2 : 1) : (a ? 2 : 0);
-    const int kx0 = px ? (b ? 2 : 0) : (b ? 1 : 0), kx1 = px ? (b ? 2 : 1) : (b ? 2 : 0);
-    volatile float s = 0.0f;  // volatile: one fp32 rounding per addition whatever the host compiler's flags
-    bool first = true;
-    for (int ky = ky0; ky <= ky1; ++ky)
-        for (int kx = kx0; kx <= kx1; ++kx) {
-            if (first) { s = w9[ky * 3 + kx]; first = false; }
-            else s = s + w9[ky * 3 + kx];
-        }
-    return s;
-}
-
-// Pack the 2x2-form weights of ONE unpooled source into [4 classes][n_nblk][krows = Cpad*4][NB]; row = (channel, a, b);
-// column order as pack_weights (lstm: 0 plain, 1 four 16-channel gate tiles, 2 packed gates for C <= 4).
-static std::vector<float> pack_weights_up4(const ConvOp& op, const float* const srcw[4], int lstm)
-{
-    const int NB = op.NI * 16;
-    const int Cin = op.src_C[0], Cp = pad4(Cin);
-    std::vector<float> out((size_t)4 * op.n_nblk * op.krows * NB, 0.0f);
-    for (int cls = 0; cls < 4; ++cls)
-        for (int nb = 0; nb < op.n_nblk; ++nb)
-            for (int c = 0; c < Cin; ++c)
-                for (int tap = 0; tap < 4; ++tap) {
-                    float* dst = &out[(((size_t)cls * op.n_nblk + nb) * op.krows + (size_t)c * 4 + tap) * NB];
-                    for (int n = 0; n < NB; ++n) {
-                        int g = 0, o;
-                        if (lstm == 1) { g = n / 16; o = nb * 16 + (n % 16); }
-                        else if (lstm == 2) { g = n / 4; o = n % 4; }
-                        else o = nb * NB + n;
-                        if (o >= op.Cout) continue;
-                        dst[(n % 16) * op.NI + (n / 16)] = presum_up_weight(srcw[g] + ((size_t)o * Cin + c) * 9, cls >> 1, cls & 1, tap >> 1, tap & 1);
-                    }
-                }
-    (void)Cp;
-    return out;
-}
-
-// EPI_UP4C (conv_mfma.h): the four classes are the four N-tiles of ONE block: [n_nblk][krows][16 columns][4 classes]
-static std::vector<float> pack_weights_up4c(const ConvOp& op, const float* const srcw[4], int lstm)
-{
-    const int Cin = op.src_C[0];
-    std::vector<float> out((size_t)op.n_nblk * op.krows * 64, 0.0f);
-    for (int nb = 0; nb < op.n_nblk; ++nb)
-        for (int c = 0; c < Cin; ++c)
-            for (int tap = 0; tap < 4; ++tap)
-                for (int n = 0; n < 16; ++n) {
-                    int g = 0, o;
-                    if (lstm == 2) { g = n / 4; o = n % 4; }
-                    else o = nb * 16 + n;
-                    if (o >= op.Cout) continue;
-                    for (int cls = 0; cls < 4; ++cls)
-                        out[(((size_t)nb * op.krows + (size_t)c * 4 + tap) * 16 + n) * 4 + cls] =
-                            presum_up_weight(srcw[g] + ((size_t)o * Cin + c) * 9, cls >> 1, cls & 1, tap >> 1, tap & 1);
-                }
-    return out;
-}
-
-// ---- Winograd F(4x4, 3x3) form of the 3x3 convolutions of layers >= 1 (conv_wino4.h; oracle/eig_oracle.c: wino4_* state the same rule)
-// EIGEN_WINOGRAD: bit l = ConvLSTM_l, bit 8 + l = ConvA_l, bit 16 + l = ConvP_l may take the Winograd form (if eligible) AND bit 25 / 26 / 27 enables it for the
-// ConvLSTMs / ConvAs / ConvPs as a class (rounds 4-5 had an F(2x2, 3x3) kernel behind the per-operator bits and F(4x4) behind the class bits; round 6 removed the
-// F(2x2) kernel -- nothing ran it -- and an operator whose class bit is clear now runs direct).  Default: all of them -- measured faster at every shape tried,
-// 256^2 / 512^2 / 640x480 / 160x120, colour and gray.  Eligibility (the same rule in oracle/eig_oracle.c: eig_wino_op) is a property
-// of the operator's shape only, never of the batch: results must not depend on the device batch a genome lands in.
-//   kind 0 ConvLSTM_l, 1 ConvA_l, 2 ConvP_l; Cin = channels of the full-resolution sources (multiples of 8 each), Cout per gate;
-//   H x W = the resolution the convolution runs at; odd H only for an operator of the TOP layer (nothing is pooled / unpooled from it)
-#ifndef EIGEN_WINO_DEFAULT
-#define EIGEN_WINO_DEFAULT 0x0FFFFFFE   // every eligible operator in Winograd form, the unpooled source inside the ConvLSTM chains (bit 24), F(4x4, 3x3) tiles (bits 25-27)
-#endif
-// the effective mask of this process: EIGEN_WINOGRAD (default EIGEN_WINO_DEFAULT), bit 24 cleared by EIGEN_WINO_FUSEUP=0 (eigen_winograd_mask; oracle.wino_mask_default)
+// the effective mask of this process: EIGEN_WINOGRAD (default EIGEN_WINO_DEFAULT, conv_plan.h), bit 24 cleared by EIGEN_WINO_FUSEUP=0 (eigen_winograd_mask; oracle.wino_mask_default)
 static int wino_mask_env()
 {
     static const int mask = [] {
@@ -371,60 +232,39 @@ static int wino_mask_env()
     }();
     return mask;
 }
-static bool wino_op(int mask, int kind, int l, int Cin, int Cout, int H, int W, bool top)
+// The A/B switches of this process (conv_plan.h: Switches says what each is for): read from the environment once, before the first use
+static const Switches& switches()
 {
-    if (!((mask >> (8 * kind + l)) & 1) || !((mask >> (25 + kind)) & 1) || l < 1) return false;
-    if ((Cin % 8) || (Cout % 16) || (W % 4)) return false;
-    if ((H % 2) && !(top && kind != 1)) return false;
-    if (kind != 0 && (Cout % 48) && (Cout % 64)) return false;  // plain convolutions: N-blocks of 48 or 64 columns without padding
-    return true;
+    static const Switches sw = [] {
+        Switches s;
+        auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+        s.tile_map = num("EIGEN_TILE_MAP", 1);
+        s.w8 = num("EIGEN_W8", -1);
+        s.w4_tall = num("EIGEN_W4_TALL", -1); s.w4_half = num("EIGEN_W4_HALF", -1); s.w4_pack = num("EIGEN_W4_PACK", -1);
+        s.w4_parts = num("EIGEN_W4_PARTS", 0);
+        if (getenv("EIGEN_TW8_FACTOR")) s.tw8_factor = atof(getenv("EIGEN_TW8_FACTOR"));
+        s.convp0_direct = !num("EIGEN_CONVP0_MFMA", 0); s.lstm0_direct = !num("EIGEN_LSTM0_MFMA", 0);
+        s.onekb = !num("EIGEN_NO_ONEKB", 0); s.up4c = !num("EIGEN_NO_UP4C", 0); s.skip_zero_sources = !num("EIGEN_NO_T0", 0);
+        s.side_stream = num("EIGEN_SIDE_STREAM", -1);
+        return s;
+    }();
+    return sw;
 }
-// F(4x4, 3x3): U = G g G^T, 6 x 6 (oracle/eig_oracle.c: wino4_w1d / wino4_weights state the same operations in the same order; fmaf = one rounding, this file
-// is compiled with -ffp-contract=off)
-static void wino4_w1d(float g0, float g1, float g2, float* W)
+
+// The packed weights of the form an operator runs; wt[WT_*][gate]: the layer's weight tensors (conv_plan.h)
+static std::vector<float> pack_op(const OpDesc& d, const float* const wt[5][4])
 {
-    const float c6 = -1.0f / 6.0f, c24 = 1.0f / 24.0f;
-    W[0] = 0.25f * g0;
-    const float a = g0 + g2;
-    W[1] = (a + g1) * c6; W[2] = (a - g1) * c6;
-    const float b = fmaf(4.0f, g2, g0);
-    W[3] = fmaf(2.0f, g1, b) * c24; W[4] = fmaf(-2.0f, g1, b) * c24;
-    W[5] = g2;
-}
-static void wino4_weight(const float* g, float* U)
-{
-    float s[6][3], W[6];
-    for (int j = 0; j < 3; ++j) { wino4_w1d(g[j], g[3 + j], g[6 + j], W); for (int i = 0; i < 6; ++i) s[i][j] = W[i]; }
-    for (int i = 0; i < 6; ++i) wino4_w1d(s[i][0], s[i][1], s[i][2], U + i * 6);
-}
-// [n_nblk][K-blocks: 4 channels of one source, sources in order][36 positions][4 channels][16 columns][NI N-tiles]
-// lstm: N-tile = gate, output channel = 16 nb + column (srcw[s][gate]); plain convolution: output channel = 16 (NI nb + N-tile) + column (srcw[s][0])
-static std::vector<float> pack_weights_wino(int C, int NI, int n_nblk, bool lstm, int nsrc, const int* src_C, const int* src_Cw, const float* const srcw[3][4])
-{
-    const int kc = W4_KC;   // channels of a packed K-block (conv_wino4.h streams them with a running offset, and one K-block past the end: padding)
-    int nkb = 0;
-    for (int s = 0; s < nsrc; ++s) nkb += src_C[s] / kc;
-    const int npos = W4_NPOS;
-    const int uf = wino4_u_floats(NI);
-    std::vector<float> out((size_t)n_nblk * nkb * uf + uf, 0.0f);
-    float U[36];
-    for (int nb = 0; nb < n_nblk; ++nb) {
-        int kb0 = 0;
-        for (int s = 0; s < nsrc; ++s) {
-            for (int c = 0; c < src_C[s]; ++c)
-                for (int ni = 0; ni < NI; ++ni)
-                    for (int n = 0; n < 16; ++n) {
-                        const int o = lstm ? nb * 16 + n : (nb * NI + ni) * 16 + n;
-                        if (o >= C) continue;
-                        wino4_weight(srcw[s][lstm ? ni : 0] + ((size_t)o * src_Cw[s] + c) * 9, U);
-                        float* dst = &out[((size_t)nb * nkb + kb0 + c / kc) * uf];
-                        for (int pos = 0; pos < npos; ++pos) dst[((pos * kc + (c % kc)) * 16 + n) * NI + ni] = U[pos];
-                    }
-            kb0 += src_C[s] / kc;
-        }
+    const float* sw[3][4] = {{nullptr}, {nullptr}, {nullptr}};
+    for (int s = 0; s < d.npk; ++s)
+        for (int g = 0; g < 4; ++g) sw[s][g] = wt[d.pk_w[s]][g];
+    switch (d.pack) {
+        case PACK_WINO: return pack_weights_wino(d.Cout, d.NI, d.n_nblk, d.lstm_mode != 0, d.npk, d.pk_C, d.pk_Ct, sw);
+        case PACK_UP4: return pack_weights_up4(d, sw[0], d.lstm_mode);
+        case PACK_UP4C: return pack_weights_up4c(d, sw[0], d.lstm_mode);
+        default: return pack_weights(d, sw, d.lstm_mode);
     }
-    return out;
 }
+
 
 template <int NI, int TW, int EPI, bool VEC, bool ONEKB = false, int SPLIT = 0> static hipError_t launch_inst2(const ConvArgs& a, int grid, hipStream_t st)
 {
@@ -467,148 +307,92 @@ template <int EPI> static hipError_t launch_epi(int NI, int TW, const ConvArgs& 
     }
 }
 
+// Timeline of one launch (measurement builds, -DEIG_TIMING=1, with EIGEN_TIMELINE=<dir>): the record buffer of a steady-state launch of every ConvLSTM op and
+// 2x2-form pass (EIGEN_TIMELINE_ALL: every Winograd operator), sized from the plan; read back and written to <dir> after the launch.
+#if EIG_TIMING
+static unsigned long long* timeline_begin(ConvOp& op, ConvArgs& a, const LaunchPlan& p)
+{
+    if (!(getenv("EIGEN_TIMELINE") && (op.epi == EPI_LSTM || (op.epi == EPI_UP4 && op.NI == 4) || (op.wino && getenv("EIGEN_TIMELINE_ALL"))) && ++op.tl_seen == 6)) return nullptr;
+    unsigned long long* d = nullptr;
+    const size_t bytes = (size_t)p.last_grid * p.last_waves * 64;
+    if (hipMalloc((void**)&d, bytes) != hipSuccess) return nullptr;
+    (void)hipMemset(d, 0, bytes);
+    a.dbg = d;
+    return d;
+}
+static void timeline_end(const ConvOp& op, ConvArgs& a, const LaunchPlan& p, unsigned long long* d, hipStream_t st)
+{
+    if (!d) return;
+    (void)hipStreamSynchronize(st);
+    std::vector<unsigned long long> h((size_t)p.last_grid * p.last_waves * 8);
+    (void)hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost);
+    char name[256];
+    snprintf(name, sizeof(name), "%s/timeline_H%d_C%d%s.bin", getenv("EIGEN_TIMELINE"), op.H, op.Cout, op.epi == EPI_UP4 ? "_up4" : op.epi == EPI_CONVA ? "_convA" : op.epi == EPI_CONVP ? "_convP" : "");
+    if (FILE* f = fopen(name, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+    (void)hipFree(d);
+    a.dbg = nullptr;
+}
+#else
+static inline unsigned long long* timeline_begin(ConvOp&, ConvArgs&, const LaunchPlan&) { return nullptr; }
+static inline void timeline_end(const ConvOp&, ConvArgs&, const LaunchPlan&, unsigned long long*, hipStream_t) {}
+#endif
+
+// The launch the plan names (conv_plan.h: LaunchPlan)
+static hipError_t dispatch_conv(const ConvOp& op, const LaunchPlan& p, const ConvArgs& a, int batch, hipStream_t st)
+{
+    const int grid = p.grid;
+    const bool vec = p.vec;
+    switch (p.kernel) {
+        case K_WINO: return launch_wino4(op.NI, op.epi, p.shape, a, grid, st);
+        case K_CONVP0: {
+            const dim3 g(p.gx, p.gy, batch);
+            if (op.Cout == 3) hipLaunchKernelGGL(convp0_direct_kernel<3>, g, dim3(p.threads), 0, st, a.src[0].ptr, op.wraw.p, a);
+            else hipLaunchKernelGGL(convp0_direct_kernel<1>, g, dim3(p.threads), 0, st, a.src[0].ptr, op.wraw.p, a);
+            return hipGetLastError();
+        }
+        case K_LSTM0: {   // the step-0 operator has one source
+            const dim3 g(p.gx, p.gy, batch), blk(p.threads);
+            const float *sE = a.src[0].ptr, *sH = a.src[1].ptr;
+            if (op.nsrc == 1) {
+                if (op.Cout == 3) hipLaunchKernelGGL((lstm0_direct_kernel<3, true>), g, blk, 0, st, sE, sH, op.wraw.p, a);
+                else hipLaunchKernelGGL((lstm0_direct_kernel<1, true>), g, blk, 0, st, sE, sH, op.wraw.p, a);
+            } else {
+                if (op.Cout == 3) hipLaunchKernelGGL((lstm0_direct_kernel<3, false>), g, blk, 0, st, sE, sH, op.wraw.p, a);
+                else hipLaunchKernelGGL((lstm0_direct_kernel<1, false>), g, blk, 0, st, sE, sH, op.wraw.p, a);
+            }
+            return hipGetLastError();
+        }
+        default: break;
+    }
+    switch (op.epi) {
+        case EPI_LSTM: return (op.TW == 16) ? launch_inst<4, 16, EPI_LSTM>(a, grid, st, vec) : launch_inst<4, 8, EPI_LSTM>(a, grid, st, vec);
+        case EPI_LSTM_PACKED: return (op.TW == 16) ? launch_inst<1, 16, EPI_LSTM_PACKED>(a, grid, st, vec) : launch_inst<1, 8, EPI_LSTM_PACKED>(a, grid, st, vec);
+        case EPI_CONVA:
+            if (p.onekb) return launch_inst2<3, 16, EPI_CONVA, true, true>(a, grid, st);
+            return launch_epi<EPI_CONVA>(op.NI, op.TW, a, grid, st, vec, p.w8);
+        case EPI_CONVP: return launch_epi<EPI_CONVP>(op.NI, op.TW, a, grid, st, vec, p.w8);
+        case EPI_UP4: return launch_epi<EPI_UP4>(op.NI, op.TW, a, grid, st, vec, p.w8);
+        case EPI_UP4C: return launch_inst2<4, 16, EPI_UP4C, true>(a, grid, st);  // chosen only for 16-wide tiles and 16-byte staging
+        default: return launch_epi<EPI_RAW>(op.NI, op.TW, a, grid, st, vec, p.w8);  // (eigen_test_conv)
+    }
+}
+
+// Plan the launch (conv_plan.h), fill the geometry half of ConvArgs, launch, profile.  The caller has filled the pointers.
 static hipError_t launch_conv(eigen_engine* e, ConvOp& op, ConvArgs& a, int batch, hipStream_t st)
 {
-    const int TH = (op.TW == 8) ? 8 : 16;
-    const int NIMG = 256 / (TH * op.TW);
+    const LaunchPlan p = plan_launch(op, batch, e->n_cu, a.up_src != nullptr, a.acc_init != nullptr, switches());
+    if (!p.ok) return hipErrorInvalidConfiguration;
+    op.last_grid = p.last_grid; op.last_waves = p.last_waves;
     a.H = op.H; a.W = op.W; a.B = batch;
-    a.tilesX = (op.W + op.TW - 1) / op.TW;
-    a.tilesY = (op.H + TH - 1) / TH;
-    a.n_nblk = op.n_nblk; a.krows = op.krows; a.wpk = op.d_wpk; a.Cout = op.Cout; a.zeros = e->d_zeros;
+    a.tilesX = p.tilesX; a.tilesY = p.tilesY; a.tile_map = p.tile_map;
+    a.n_nblk = op.n_nblk; a.krows = op.krows; a.wpk = op.wpk.p; a.Cout = op.Cout; a.zeros = e->d_zeros;
     a.nsrc = op.nsrc;
     for (int s = 0; s < op.nsrc; ++s) { a.src[s].C = op.src_C[s]; a.src[s].Cpad = pad4(op.src_C[s]); a.src[s]._reserved = 0; a.src[s].Ct = op.src_Ct[s] ? op.src_Ct[s] : op.src_C[s]; }
-    int ntile = ((batch + NIMG - 1) / NIMG) * a.tilesX * a.tilesY;
-    const int per_tile = op.n_nblk * (op.epi == EPI_UP4 ? 4 : 1);
-    int grid = per_tile * ((ntile + 7) / 8) * 8;  // XCD-aware tile map (conv_mfma.h): tiles padded to a multiple of 8
-    // 16-byte DMA staging needs chunk-aligned rows: W % 4 == 0
-    const bool vec = (op.W % 4) == 0;
-#if EIG_TIMING
-    unsigned long long* tl_dbg = nullptr;
-    if (getenv("EIGEN_TIMELINE") && (op.epi == EPI_LSTM || (op.epi == EPI_UP4 && op.NI == 4) || (op.wino && getenv("EIGEN_TIMELINE_ALL"))) && ++op.tl_seen == 6) {  // a steady-state launch of every ConvLSTM op and 2x2-form pass
-        (void)hipMalloc((void**)&tl_dbg, (size_t)grid * 2 * 64 * 8);  // half blocks double the grid, W8 blocks have 8 waves
-        (void)hipMemset(tl_dbg, 0, (size_t)grid * 2 * 64 * 8);
-        a.dbg = tl_dbg;
-    }
-#endif
-    {
-        // 0 only for A/B measurements: tiles interleaved over the XCDs instead of a contiguous tile range per XCD
-        static const int tile_map = getenv("EIGEN_TILE_MAP") ? atoi(getenv("EIGEN_TILE_MAP")) : 1;
-        a.tile_map = tile_map != 0;
-    }
-    // Eight-wave instantiation of the direct ConvA (conv_mfma.h: W8): launches of at most four rounds of the device's block slots gain 4-5 % from twice as many waves out
-    // of the same few blocks (profiles/r03_b_ab_w8.txt); EIGEN_W8 = 0 / 1 forces it off / on (A/B measurements and the parity tests).
-    static const int w8_env = getenv("EIGEN_W8") ? atoi(getenv("EIGEN_W8")) : -1;
-    const int w8 = (vec && op.epi == EPI_CONVA && op.TW == 16 && op.NI < 4 && (w8_env >= 0 ? w8_env != 0 : grid <= 8 * e->n_cu)) ? 1 : 0;
-    op.last_grid = grid; op.last_waves = (w8 == 1) ? 8 : 4;
+    if (p.kernel == K_WINO) { a.nparts = p.nparts; a.nwalk = p.nwalk; for (int i = 0; i < 3; ++i) a.mg[i] = p.mg[i]; }
+    unsigned long long* tl = timeline_begin(op, a, p);
     if (e->profile_convs) (void)hipEventRecord(e->pev0, st);
-    hipError_t r;
-    if (op.wino) {  // Winograd form: F(4x4, 3x3), conv_wino4.h
-        if (op.epi == EPI_LSTM && a.acc_init != nullptr) return hipErrorInvalidConfiguration;   // (set_weights never pairs F(4x4) with a separate unpooled chain)
-        // Block shape (conv_wino4.h): 16 rows x 32 columns, or 32 x 16 ("tall") where that covers the MAP with fewer blocks -- 80 x 60: 10 instead of 12, 40 x 30: 3
-        // instead of 4 (the reference's 160 x 120); a function of the operator's map size alone, and the chains do not depend on it.  EIGEN_W4_TALL = 0 / 1 forces it (A/B, tests).
-        static const int tall_env = getenv("EIGEN_W4_TALL") ? atoi(getenv("EIGEN_W4_TALL")) : -1;
-        const bool tall = tall_env >= 0 ? tall_env != 0 : ((op.W + 15) / 16) * ((op.H + 31) / 32) < ((op.W + 31) / 32) * ((op.H + 15) / 16);
-        a.tilesX = tall ? (op.W + 15) / 16 : (op.W + 31) / 32; a.tilesY = tall ? (op.H + 31) / 32 : (op.H + 15) / 16;
-        // Half blocks (conv_wino4.h: HALF, 8 x 32 pixels, six or twelve waves) while even THEY are at most one block per CU: the launch's time is then ONE block's time, and a half
-        // block has the CU's matrix pipe to itself for half the multiply-adds (c1: +15 %; with more half blocks than CUs the second round costs more than the halving gains --
-        // c2's 20 x 15 top layer, 200 full blocks: -7 %).  A choice by launch size, like the walk.  EIGEN_W4_HALF = 0 / 1 forces it (A/B, tests).
-        static const int half_env = getenv("EIGEN_W4_HALF") ? atoi(getenv("EIGEN_W4_HALF")) : -1;
-        const bool half = !tall && (half_env >= 0 ? half_env != 0 : (long long)op.n_nblk * batch * a.tilesX * ((op.H + 7) / 8) <= e->n_cu);
-        if (half) a.tilesY = (op.H + 7) / 8;
-        // Packed tiles (conv_wino4.h: PACK): maps of 4 x 4 or 5 x 4 tiles -- the 20 x 15 top layer of the reference's 160 x 120 fills 62 % of a wide block -- on half blocks
-        // whose sixteen MFMA rows are all real tiles: tile columns 0-3 of one image, or tile column 4 of four images (five blocks per four images).  For ConvLSTMs without
-        // an unpooled source and ConvPs.  Taken when its rounds of half blocks (a half block takes about two thirds of a full one's time) cost less than the rounds of
-        // full blocks: ref160's ConvLSTM_3, 600 blocks = 3 rounds -> 756 half blocks = 3 rounds of two thirds; configs[1]'s, 200 blocks -> 252 half blocks, one round each.  A choice
-        // by map and launch size; the chains do not depend on it.  EIGEN_W4_PACK = 0 / 1 forbids / forces it for every operator it can run.
-        static const int pack_env = getenv("EIGEN_W4_PACK") ? atoi(getenv("EIGEN_W4_PACK")) : -1;
-        const int ptx = (op.W + 3) / 4, pty = (op.H + 3) / 4;
-        const bool pack_can = op.epi != EPI_CONVA && a.up_src == nullptr && (ptx == 4 || ptx == 5) && pty == 4 && tall_env < 0 && half_env < 0;
-        bool pack = false;
-        if (pack_can) {
-            const long long nhalf = (long long)op.n_nblk * (batch + (ptx == 5 ? (batch + 3) / 4 : 0)), nfull = (long long)op.n_nblk * batch;
-            pack = pack_env >= 0 ? pack_env != 0 : 2 * ((nhalf + e->n_cu - 1) / e->n_cu) < 3 * ((nfull + e->n_cu - 1) / e->n_cu);
-        }
-        if (pack) { a.tilesX = ptx; a.tilesY = pty; }
-        const int ntile4 = pack ? batch + (ptx == 5 ? (batch + 3) / 4 : 0) : batch * a.tilesX * a.tilesY;
-        // WALK (conv_wino4.h): nparts blocks per tile, each computing nwalk = n_nblk / nparts consecutive N-blocks of it: walks of three N-blocks where n_nblk allows, of
-        // two otherwise (the blocks of a tile share its planes through the XCD's L2), no walk while the launch would not give every CU four blocks.  A property of the
-        // launch only -- the bits do not depend on it.  EIGEN_W4_PARTS = n forces min(n, n_nblk) rounded down to a divisor (n >= n_nblk: one N-block per block), for A/B
-        // measurements and the parity tests.
-        static const int parts_env = getenv("EIGEN_W4_PARTS") ? atoi(getenv("EIGEN_W4_PARTS")) : 0;
-        int nparts;
-        if (parts_env > 0) { nparts = std::min(parts_env, op.n_nblk); while (op.n_nblk % nparts) --nparts; }
-        else {   // walks of three N-blocks where n_nblk allows (two otherwise), shorter while the launch would not give every CU four blocks
-            int nwalk = (op.n_nblk % 3 == 0) ? 3 : ((op.n_nblk % 2 == 0) ? 2 : 1);
-            if ((long long)(op.n_nblk / nwalk) * ntile4 < 4ll * e->n_cu) nwalk = 1;
-            nparts = op.n_nblk / nwalk;
-        }
-        if (tall || half || pack) nparts = op.n_nblk;   // (tall and half blocks do not walk)
-        a.nparts = nparts; a.nwalk = op.n_nblk / nparts;
-        const int g4 = nparts * ((ntile4 + 7) / 8) * 8;
-        {   // q = umulhi(x, ceil(2^32 / d)) = x / d for every x with x * d < 2^32 (x < number of blocks here)
-            auto magic = [&](long long d) -> unsigned { return (d > 1 && (long long)g4 * 16 * d < (1ll << 32)) ? (unsigned)(((1ll << 32) + d - 1) / d) : 0u; };   // (x 16: a packed block divides its first TILE's index)
-            a.mg[0] = magic(nparts); a.mg[1] = magic((long long)a.tilesX * a.tilesY); a.mg[2] = magic(a.tilesX);
-        }
-        op.last_grid = g4 * a.nwalk; op.last_waves = ((half || pack) && !(op.NI == 4 && op.epi != EPI_CONVA)) ? W4_WAVES / 2 : W4_WAVES;   // (64-column ConvLSTM / ConvP half blocks: twelve waves, conv_wino4.h: NSPLIT)   // (timeline records: one per block and N-block of its walk)
-#if EIG_TIMING
-        if (tl_dbg) {   // sized from THIS launch's records (the buffer above was sized for the four-wave grid)
-            (void)hipFree(tl_dbg);
-            (void)hipMalloc((void**)&tl_dbg, (size_t)op.last_grid * op.last_waves * 64);
-            (void)hipMemset(tl_dbg, 0, (size_t)op.last_grid * op.last_waves * 64);
-            a.dbg = tl_dbg;
-        }
-#endif
-        r = launch_wino4(op.NI, op.epi, pack ? W4_PACK : (tall ? W4_TALL : (half ? W4_HALF : W4_WIDE)), a, g4, st);
-    } else {
-    static const bool direct_p0 = !(getenv("EIGEN_CONVP0_MFMA") && atoi(getenv("EIGEN_CONVP0_MFMA")));  // A/B measurements only
-    if (op.epi == EPI_CONVP && op.d_wraw && direct_p0) {  // image layer: HBM-bound, one thread per pixel (conv_mfma.h)
-        const dim3 g((op.W + P0_TX - 1) / P0_TX, (op.H + P0_TY - 1) / P0_TY, batch);
-        if (op.Cout == 3) hipLaunchKernelGGL(convp0_direct_kernel<3>, g, dim3(P0_TX * P0_TY), 0, st, a.src[0].ptr, op.d_wraw, a);
-        else hipLaunchKernelGGL(convp0_direct_kernel<1>, g, dim3(P0_TX * P0_TY), 0, st, a.src[0].ptr, op.d_wraw, a);
-        r = hipGetLastError();
-    } else if (static const bool direct_l0 = !(getenv("EIGEN_LSTM0_MFMA") && atoi(getenv("EIGEN_LSTM0_MFMA")));  // A/B measurements only
-               op.epi == EPI_LSTM_PACKED && op.d_wraw && direct_l0 && (op.Cout == 1 || op.Cout == 3)) {
-        // image layer: one thread per pixel (conv_mfma.h: lstm0_direct_kernel); the step-0 operator has one source
-        const dim3 g((op.W + L0_TX - 1) / L0_TX, (op.H + L0_TY - 1) / L0_TY, batch);
-        const dim3 blk(L0_TX * L0_TY);
-        const float *sE = a.src[0].ptr, *sH = a.src[1].ptr;
-        if (op.nsrc == 1) {
-            if (op.Cout == 3) hipLaunchKernelGGL((lstm0_direct_kernel<3, true>), g, blk, 0, st, sE, sH, op.d_wraw, a);
-            else hipLaunchKernelGGL((lstm0_direct_kernel<1, true>), g, blk, 0, st, sE, sH, op.d_wraw, a);
-        } else {
-            if (op.Cout == 3) hipLaunchKernelGGL((lstm0_direct_kernel<3, false>), g, blk, 0, st, sE, sH, op.d_wraw, a);
-            else hipLaunchKernelGGL((lstm0_direct_kernel<1, false>), g, blk, 0, st, sE, sH, op.d_wraw, a);
-        }
-        r = hipGetLastError();
-    } else
-    switch (op.epi) {
-        case EPI_LSTM: r = (op.TW == 16) ? launch_inst<4, 16, EPI_LSTM>(a, grid, st, vec) : launch_inst<4, 8, EPI_LSTM>(a, grid, st, vec); break;
-        case EPI_LSTM_PACKED: r = (op.TW == 16) ? launch_inst<1, 16, EPI_LSTM_PACKED>(a, grid, st, vec) : launch_inst<1, 8, EPI_LSTM_PACKED>(a, grid, st, vec); break;
-        case EPI_CONVA: {
-            // the image layer's ConvA (K = 9 x 6 channels): one K-block, its own instantiation (conv_mfma.h: ONEKB)
-            static const bool onekb = !(getenv("EIGEN_NO_ONEKB") && atoi(getenv("EIGEN_NO_ONEKB")));  // A/B measurements only
-            if (onekb && op.NI == 3 && op.TW == 16 && vec && op.nsrc == 1 && pad4(op.src_C[0]) <= KC) r = launch_inst2<3, 16, EPI_CONVA, true, true>(a, grid, st);
-            else r = launch_epi<EPI_CONVA>(op.NI, op.TW, a, grid, st, vec, w8);
-            break;
-        }
-        case EPI_CONVP: r = launch_epi<EPI_CONVP>(op.NI, op.TW, a, grid, st, vec, w8); break;
-        case EPI_UP4: r = launch_epi<EPI_UP4>(op.NI, op.TW, a, grid, st, vec, w8); break;
-        case EPI_UP4C: r = launch_inst2<4, 16, EPI_UP4C, true>(a, grid, st); break;  // chosen only for 16-wide tiles and 16-byte staging
-        default: r = launch_epi<EPI_RAW>(op.NI, op.TW, a, grid, st, vec, w8); break;  // (eigen_test_conv)
-    }
-    }
-#if EIG_TIMING
-    if (tl_dbg) {
-        (void)hipStreamSynchronize(st);
-        std::vector<unsigned long long> h((size_t)op.last_grid * op.last_waves * 8);
-        (void)hipMemcpy(h.data(), tl_dbg, h.size() * 8, hipMemcpyDeviceToHost);
-        char name[256];
-        snprintf(name, sizeof(name), "%s/timeline_H%d_C%d%s.bin", getenv("EIGEN_TIMELINE"), op.H, op.Cout, op.epi == EPI_UP4 ? "_up4" : op.epi == EPI_CONVA ? "_convA" : op.epi == EPI_CONVP ? "_convP" : "");
-        if (FILE* f = fopen(name, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-        (void)hipFree(tl_dbg);
-        a.dbg = nullptr;
-    }
-#endif
+    const hipError_t r = dispatch_conv(op, p, a, batch, st);
+    timeline_end(op, a, p, tl, st);
     if (e->profile_convs && r == hipSuccess) {
         (void)hipEventRecord(e->pev1, st);
         (void)hipEventSynchronize(e->pev1);
@@ -618,6 +402,7 @@ static hipError_t launch_conv(eigen_engine* e, ConvOp& op, ConvArgs& a, int batc
     }
     return r;
 }
+
 
 
 // ------------------------------------------------------------------------------------------------ ABI
@@ -643,14 +428,14 @@ int eigen_destroy(eigen_engine* e)
     (void)hipSetDevice(e->cfg.device);
     for (int l = 0; l < e->L; ++l) {
         Layer& y = e->layer[l];
-        float* ptrs[] = {y.h[0], y.h[1], y.c, y.P, y.E, y.bias_lstm, y.peep, y.biasA, y.biasP, y.convA.d_wpk, y.lstm.d_wpk, y.convP.d_wpk, y.convP.d_wraw, y.lstm.d_wraw, y.convA_t0.d_wpk, y.lstm_t0.d_wpk, y.up4.d_wpk};
+        float* ptrs[] = {y.h[0], y.h[1], y.c, y.P, y.E};   // (the weights are owned buffers: ~DevBuf)
         for (float* p : ptrs) if (p) (void)hipFree(p);
     }
     if (e->d_planes) (void)hipFree(e->d_planes);
     e->g_node_off.release(); e->g_edge_off.release(); e->g_edge_src.release(); e->g_out_node.release();
     e->g_node_act.release(); e->g_node_bias.release(); e->g_node_resp.release(); e->g_edge_w.release();
     void* misc[] = {e->d_images, e->d_frames, e->d_eig, e->d_cand, e->d_corners, e->d_next, e->d_vectors, e->d_status,
-                    e->d_ncorners, e->d_counts, e->d_fitness, e->d_zeros, e->d_raw4,
+                    e->d_ncorners, e->d_counts, e->d_fitness, e->d_zeros,
                     e->fb_I, e->fb_R0, e->fb_R1, e->fb_M, e->fb_V, e->fb_flow[0], e->fb_flow[1]};
     for (void* p : misc) if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
@@ -750,194 +535,61 @@ int eigen_create(const eigen_config* cfg, eigen_engine** out)
     *out = e;
     return EIGEN_OK;
 }
-
 int eigen_set_prednet_weights(eigen_engine* e, const float* const* t, int32_t n_tensors)
 {
     if (!e || !t) return fail(EIGEN_ERR_INVALID, "null argument");
     HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipDeviceSynchronize());   // a second call overwrites the weights in place: no roll-out still running on any stream may be reading them
     const int L = e->L;
     int expect = 0;
     for (int l = 0; l < L; ++l) expect += (l > 0 ? 2 : 0) + 2 + 4 * (l < L - 1 ? 4 : 3) + 3;
     if (n_tensors != expect) return fail(EIGEN_ERR_INVALID, "expected %d weight tensors for %d layers, got %d", expect, L, n_tensors);
+    int Cs[EIGEN_MAX_LAYERS], Hs[EIGEN_MAX_LAYERS], Ws[EIGEN_MAX_LAYERS];
+    for (int l = 0; l < L; ++l) { Cs[l] = e->layer[l].C; Hs[l] = e->layer[l].H; Ws[l] = e->layer[l].W; }
+    std::vector<LayerPlan> plan(L);
+    plan_prednet(L, Cs, Hs, Ws, wino_mask_env(), switches(), plan.data());
     int k = 0;
-    const int wino_env = wino_mask_env();
-    auto upload = [&](float** dst, const float* src, size_t n) -> int {
-        if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-        if (hipMalloc((void**)dst, n * sizeof(float)) != hipSuccess) return -1;
-        return hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-    };
     for (int l = 0; l < L; ++l) {
         Layer& y = e->layer[l];
         const int C = y.C;
-        const float *convA_w = nullptr, *convA_b = nullptr;
-        if (l > 0) { convA_w = t[k++]; convA_b = t[k++]; }
-        const float* convP_w = t[k++];
+        // the layer's weight tensors, [WT_*][gate] (conv_plan.h)
+        const float* wt[5][4] = {{nullptr}, {nullptr}, {nullptr}, {nullptr}, {nullptr}};
+        const float *convA_b = nullptr, *bh[4];
+        if (l > 0) { wt[WT_CONVA][0] = t[k++]; convA_b = t[k++]; }
+        wt[WT_CONVP][0] = t[k++];
         const float* convP_b = t[k++];
-        const float *wx0[4], *wx1[4] = {nullptr, nullptr, nullptr, nullptr}, *wh[4], *bh[4];
         for (int g = 0; g < 4; ++g) {
-            wx0[g] = t[k++];
-            if (l < L - 1) wx1[g] = t[k++];
-            wh[g] = t[k++];
+            wt[WT_X0][g] = t[k++];
+            if (l < L - 1) wt[WT_X1][g] = t[k++];
+            wt[WT_H][g] = t[k++];
             bh[g] = t[k++];
         }
         const float* peep[3] = {t[k], t[k + 1], t[k + 2]};
         k += 3;
         for (int i = 0; i < k; ++i) if (!t[i]) return fail(EIGEN_ERR_INVALID, "weight tensor %d is NULL", i);
 
-        // ---- ConvA_l: E_{l-1} (2 C_{l-1} ch at the finer resolution) -> C_l, fused relu / 2x2 max-pool / error unit
-        if (l > 0) {
-            ConvOp& op = y.convA;
-            { float *k0 = op.d_wpk, *k1 = op.d_wraw; op = ConvOp(); op.d_wpk = k0; op.d_wraw = k1; }  // keep the allocations: upload() frees them
-            op.epi = EPI_CONVA; op.layer = l; op.nsrc = 1; op.src_C[0] = 2 * e->layer[l - 1].C;
-            op.H = e->layer[l - 1].H; op.W = e->layer[l - 1].W; op.Cout = C;
-            choose_ni(C, false, &op.NI, &op.n_nblk);
-            op.TW = choose_tw(op.H, op.W);
-            op.krows = pad4(op.src_C[0]) * 9;
-            op.macs = (double)op.H * op.W * C * op.src_C[0] * 9;
-            const float* sw[3][4] = {{convA_w, nullptr, nullptr, nullptr}, {nullptr}, {nullptr}};
-            std::vector<float> pk = pack_weights(op, sw, 0);
-            if (upload(&op.d_wpk, pk.data(), pk.size()) || upload(&y.biasA, convA_b, C)) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvA%d)", l);
-            ConvOp& t0 = y.convA_t0;  // step 0: first half of E_{l-1} only (Layer::convA_t0)
-            { float* k0 = t0.d_wpk; t0 = op; t0.d_wpk = k0; t0.d_wraw = nullptr; }
-            t0.src_C[0] = e->layer[l - 1].C; t0.src_Ct[0] = 2 * e->layer[l - 1].C;
-            t0.krows = pad4(t0.src_C[0]) * 9;
-            t0.macs = (double)op.H * op.W * C * t0.src_C[0] * 9;
-            std::vector<float> pk0 = pack_weights(t0, sw, 0);
-            if (upload(&t0.d_wpk, pk0.data(), pk0.size())) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvA%d, step 0)", l);
-            if (wino_op(wino_env, 1, l, e->layer[l - 1].C, C, op.H, op.W, false)) {  // (the step-0 operator reads C_{l-1} channels: multiples of 8 too)
-                const int ni = (C % 64) ? 3 : 4, nb = C / (16 * ni);
-                const int sc[1] = {2 * e->layer[l - 1].C}, scw[1] = {2 * e->layer[l - 1].C}, sc0[1] = {e->layer[l - 1].C};
-                const int wt = 4;   // F(4x4, 3x3) tiles
-                std::vector<float> pw = pack_weights_wino(C, ni, nb, false, 1, sc, scw, sw);
-                std::vector<float> pw0 = pack_weights_wino(C, ni, nb, false, 1, sc0, scw, sw);
-                if (upload(&op.d_wpk, pw.data(), pw.size()) || upload(&t0.d_wpk, pw0.data(), pw0.size())) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvA%d, Winograd form)", l);
-                for (ConvOp* f : {&op, &t0}) { f->wino = true; f->TW = 16; f->NI = ni; f->n_nblk = nb; }
-                const double tl = (double)((op.H + wt - 1) / wt) * ((op.W + wt - 1) / wt) * (wt + 2) * (wt + 2);   // tiles x positions
-                op.macs = tl * C * sc[0];
-                t0.macs = tl * C * sc0[0];
-            }
+        // every operator: the form it will run, packed once and uploaded
+        const LayerPlan& pl = plan[l];
+        const std::vector<float> raw0 = pl.lstm.raw ? lstm0_raw_table(C, wt[WT_X0], wt[WT_H]) : std::vector<float>();
+        const struct { ConvOp* op; const OpDesc* d; const char* name; } ops[6] = {{&y.convA, &pl.convA, "ConvA"}, {&y.convA_t0, &pl.convA_t0, "ConvA, step 0"}, {&y.lstm, &pl.lstm, "ConvLSTM"},
+                                                                                   {&y.lstm_t0, &pl.lstm_t0, "ConvLSTM, step 0"}, {&y.up4, &pl.up4, "ConvLSTM, unpooled source"}, {&y.convP, &pl.convP, "ConvP"}};
+        for (const auto& o : ops) {
+            o.op->replan(*o.d);
+            if (!o.d->present) continue;
+            const std::vector<float> pk = pack_op(*o.d, wt);
+            bool bad = upload(o.op->wpk, pk.data(), pk.size()) != 0;
+            if (o.d->raw && !bad)   // image layer: ConvP's OIHW tensor itself; the ConvLSTM's table -- the step-0 operator reads the table's second part from a copy of its OWN (a few KB: every operator owns what it reads)
+                bad = o.d->epi == EPI_CONVP ? upload(o.op->wraw, wt[WT_CONVP][0], (size_t)C * C * 9) : upload(o.op->wraw, raw0.data(), raw0.size());
+            if (bad) return fail(EIGEN_ERR_HIP, "weight upload failed (%s, layer %d%s)", o.name, l, o.d->wino ? ", Winograd form" : "");
         }
-        // ---- ConvLSTM_l: 4 gates fused on N.  Chain over E_l, h_l + chain of the unpooled R_{l+1} in its 2x2 form (own launch, Layer::up4)
-        {
-            ConvOp& op = y.lstm;
-            { float *k0 = op.d_wpk, *k1 = op.d_wraw; op = ConvOp(); op.d_wpk = k0; op.d_wraw = k1; }  // keep the allocations: upload() frees them
-            op.epi = EPI_LSTM; op.layer = l; op.H = y.H; op.W = y.W; op.Cout = C;
-            op.nsrc = 2;
-            op.src_C[0] = 2 * C; op.src_C[1] = C;
-            choose_ni(C, true, &op.NI, &op.n_nblk);
-            if (C <= 4) { op.epi = EPI_LSTM_PACKED; op.NI = 1; op.n_nblk = 1; }  // 4 gates x <=4 channels in one MFMA tile
-            const int lstm_mode = (op.epi == EPI_LSTM_PACKED) ? 2 : 1;
-            op.TW = choose_tw(op.H, op.W);
-            op.krows = 0; op.macs = 0;
-            for (int s = 0; s < op.nsrc; ++s) { op.krows += pad4(op.src_C[s]) * 9; op.macs += (double)y.H * y.W * 4 * C * op.src_C[s] * 9; }
-            const float* sw[3][4];
-            for (int g = 0; g < 4; ++g) { sw[0][g] = wx0[g]; sw[1][g] = wh[g]; sw[2][g] = nullptr; }
-            std::vector<float> pk = pack_weights(op, sw, lstm_mode);
-            std::vector<float> bias(4 * (size_t)C);
-            for (int g = 0; g < 4; ++g) memcpy(&bias[(size_t)g * C], bh[g], sizeof(float) * C);
-            const size_t chw = (size_t)C * y.H * y.W;
-            std::vector<float> pp(3 * chw);
-            for (int g = 0; g < 3; ++g) memcpy(&pp[g * chw], peep[g], sizeof(float) * chw);
-            if (upload(&op.d_wpk, pk.data(), pk.size()) || upload(&y.bias_lstm, bias.data(), bias.size()) || upload(&y.peep, pp.data(), pp.size()))
-                return fail(EIGEN_ERR_HIP, "weight upload failed (ConvLSTM%d)", l);
-            if (op.epi == EPI_LSTM_PACKED && (C == 1 || C == 3)) {  // image layer, lstm0_direct_kernel: [C outputs][K taps = (channel, ky, kx) over E_0 then h_0][4 gates], then the step-0 table (first half of E_0 only)
-                const int K = 3 * C * 9, K0 = C * 9;
-                std::vector<float> raw((size_t)C * K * 4 + (size_t)C * K0 * 4);
-                for (int o = 0; o < C; ++o)
-                    for (int g = 0; g < 4; ++g) {
-                        for (int c = 0; c < 2 * C; ++c)
-                            for (int t9 = 0; t9 < 9; ++t9) {
-                                const float wv = wx0[g][((size_t)o * 2 * C + c) * 9 + t9];
-                                raw[((size_t)o * K + c * 9 + t9) * 4 + g] = wv;
-                                if (c < C) raw[(size_t)C * K * 4 + ((size_t)o * K0 + c * 9 + t9) * 4 + g] = wv;
-                            }
-                        for (int c = 0; c < C; ++c)
-                            for (int t9 = 0; t9 < 9; ++t9) raw[((size_t)o * K + (2 * C + c) * 9 + t9) * 4 + g] = wh[g][((size_t)o * C + c) * 9 + t9];
-                    }
-                if (upload(&op.d_wraw, raw.data(), raw.size())) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvLSTM%d direct)", l);
-            }
-            ConvOp& t0 = y.lstm_t0;  // step 0: first half of E_l only; h_l = 0 is not read (Layer::lstm_t0)
-            { float* k0 = t0.d_wpk; t0 = op; t0.d_wpk = k0; }  // (d_wraw is shared with the full operator, which owns it)
-            t0.nsrc = 1;
-            t0.src_C[0] = C; t0.src_Ct[0] = 2 * C; t0.src_C[1] = 0;
-            t0.krows = pad4(C) * 9; t0.macs = (double)y.H * y.W * 4 * C * C * 9;
-            std::vector<float> pk0 = pack_weights(t0, sw, lstm_mode);
-            if (upload(&t0.d_wpk, pk0.data(), pk0.size())) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvLSTM%d, step 0)", l);
-            // The chain of the unpooled source R_{l+1}.  Direct ConvLSTM (the image layer, ineligible shapes, EIGEN_WINOGRAD=0): a pass of its own at the source resolution
-            // in 2x2 form (EPI_UP4 / EPI_UP4C), added to the ConvLSTM's chain with one fp32 addition.  Winograd ConvLSTM: INSIDE the same chains, between E_l and h_l
-            // (conv_wino4.h: up_fused; oracle/eig_oracle.c: eig_wino_lstm) -- below the top layer the Winograd form exists only that way (16-byte rows at the
-            // source resolution: W % 8 == 0, 8-channel K-blocks: C_{l+1} % 8 == 0, bit 24 of the mask); an operator that cannot is a direct one.
-            // EIGEN_WINOGRAD = bit mask of the operators that run in Winograd form (bit l ConvLSTM_l, 8 + l ConvA_l, 16 + l ConvP_l; bit 24: see above; bits 25-27: F(4x4, 3x3)
-            // tiles) -- ANOTHER canonical summation order per setting, which the oracle follows through the same variable.  DEFAULT ON for every eligible operator
-            // (EIGEN_WINO_DEFAULT); EIGEN_WINOGRAD=0 = the direct chains of rounds 1-3.  Every rank of a multi-GPU run must use the same value (eigen_winograd_mask).
-            const bool wino_fuse = ((wino_env >> 24) & 1) && l < L - 1 && (y.W % 8) == 0 && (e->layer[l + 1].C % 8) == 0;
-            const bool wino = op.epi == EPI_LSTM && wino_op(wino_env, 0, l, 3 * C, C, y.H, y.W, l == L - 1) && (l == L - 1 || wino_fuse);
-            if (wino) {
-                const int Cu = wino_fuse ? e->layer[l + 1].C : 0;
-                const float* w3[3][4];
-                for (int g = 0; g < 4; ++g) { w3[0][g] = wx0[g]; w3[1][g] = wino_fuse ? wx1[g] : wh[g]; w3[2][g] = wino_fuse ? wh[g] : nullptr; }
-                const int sc[3] = {2 * C, wino_fuse ? Cu : C, C}, sw[3] = {2 * C, wino_fuse ? Cu : C, C};
-                const int sc0[2] = {C, Cu}, sw0[2] = {2 * C, Cu};
-                const int wt = 4;   // F(4x4, 3x3) tiles
-                std::vector<float> pw = pack_weights_wino(C, 4, op.n_nblk, true, wino_fuse ? 3 : 2, sc, sw, w3);
-                std::vector<float> pw0 = pack_weights_wino(C, 4, op.n_nblk, true, wino_fuse ? 2 : 1, sc0, sw0, w3);
-                if (upload(&op.d_wpk, pw.data(), pw.size()) || upload(&t0.d_wpk, pw0.data(), pw0.size())) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvLSTM%d, Winograd form)", l);
-                op.wino = t0.wino = true; op.TW = t0.TW = 16;
-                const double tiles = (double)((y.H + wt - 1) / wt) * ((y.W + wt - 1) / wt);
-                const double pf = 36, pu = 25;   // positions of a tile: full-resolution sources, the unpooled one
-                op.macs = tiles * pf * 4 * C * (3.0 * C) + tiles * pu * 4 * C * Cu;   // executed: 16 / 36 (unpooled source: 9 / 25) multiply-adds per channel and tile
-                t0.macs = tiles * pf * 4 * C * (1.0 * C) + tiles * pu * 4 * C * Cu;
-                if (wino_fuse)
-                    for (ConvOp* f : {&op, &t0}) { f->fused = true; f->up_C = Cu; f->up_kb = Cu / KC; }
-            }
-            ConvOp& u = y.up4;
-            { float* k0 = u.d_wpk; u = ConvOp(); u.d_wpk = k0; }
-            if (l < L - 1 && !wino) {  // R_{l+1}, at ITS resolution; columns = the ConvLSTM's
-                const Layer& yu = e->layer[l + 1];
-                u.epi = EPI_UP4; u.layer = l; u.nsrc = 1; u.src_C[0] = e->layer[l + 1].C; u.H = yu.H; u.W = yu.W; u.Cout = C;
-                u.NI = op.NI; u.n_nblk = op.n_nblk; u.TW = choose_tw(u.H, u.W);
-                u.krows = pad4(u.src_C[0]) * 4;
-                u.macs = (double)y.H * y.W * 4 * C * u.src_C[0] * 4;  // 4 taps per output pixel and channel instead of 9
-                const size_t need = (size_t)e->B * 4 * u.n_nblk * u.NI * 16 * u.H * u.W;
-                // <= 16 columns (the packed image-layer ConvLSTM): all four classes in one block (EPI_UP4C) where the wide staging path exists
-                static const bool up4c = !(getenv("EIGEN_NO_UP4C") && atoi(getenv("EIGEN_NO_UP4C")));  // A/B measurements only
-                std::vector<float> pku;
-                if (up4c && op.NI == 1 && lstm_mode == 2 && u.TW == 16 && (u.W % 4) == 0) {
-                    u.epi = EPI_UP4C; u.NI = 4;
-                    pku = pack_weights_up4c(u, wx1, lstm_mode);
-                } else pku = pack_weights_up4(u, wx1, lstm_mode);
-                if (upload(&u.d_wpk, pku.data(), pku.size())) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvLSTM%d, unpooled source)", l);
-                if (need > e->raw4_floats) {
-                    if (e->d_raw4) { (void)hipFree(e->d_raw4); e->d_raw4 = nullptr; e->raw4_floats = 0; }
-                    if (hipMalloc((void**)&e->d_raw4, need * sizeof(float)) != hipSuccess) return fail(EIGEN_ERR_HIP, "hipMalloc(%zu) for the unpooled-source partial chains", need * sizeof(float));
-                    e->raw4_floats = need;
-                }
-            }
-        }
-        // ---- ConvP_l
-        {
-            ConvOp& op = y.convP;
-            { float *k0 = op.d_wpk, *k1 = op.d_wraw; op = ConvOp(); op.d_wpk = k0; op.d_wraw = k1; }  // keep the allocations: upload() frees them
-            op.epi = EPI_CONVP; op.layer = l; op.nsrc = 1; op.src_C[0] = C;
-            op.H = y.H; op.W = y.W; op.Cout = C;
-            choose_ni(C, false, &op.NI, &op.n_nblk);
-            op.TW = choose_tw(op.H, op.W);
-            op.krows = pad4(C) * 9;
-            op.macs = (double)y.H * y.W * C * C * 9;
-            const float* sw[3][4] = {{convP_w, nullptr, nullptr, nullptr}, {nullptr}, {nullptr}};
-            std::vector<float> pk = pack_weights(op, sw, 0);
-            if (upload(&op.d_wpk, pk.data(), pk.size()) || upload(&y.biasP, convP_b, C)) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvP%d)", l);
-            if (l == 0 && (C == 1 || C == 3) && upload(&op.d_wraw, convP_w, (size_t)C * C * 9)) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvP0 direct)");
-            if (wino_op(wino_env, 2, l, C, C, y.H, y.W, l == L - 1)) {
-                const int ni = (C % 64) ? 3 : 4, nb = C / (16 * ni);
-                const int sc[1] = {C};
-                const int wt = 4;
-                std::vector<float> pw = pack_weights_wino(C, ni, nb, false, 1, sc, sc, sw);
-                if (upload(&op.d_wpk, pw.data(), pw.size())) return fail(EIGEN_ERR_HIP, "weight upload failed (ConvP%d, Winograd form)", l);
-                op.wino = true; op.TW = 16; op.NI = ni; op.n_nblk = nb;
-                op.macs = (double)((y.H + wt - 1) / wt) * ((y.W + wt - 1) / wt) * (wt + 2) * (wt + 2) * C * C;
-            }
-        }
+        if (e->raw4.ensure((size_t)e->B * pl.up4.scratch_floats)) return fail(EIGEN_ERR_HIP, "hipMalloc(%zu) for the unpooled-source partial chains", (size_t)e->B * pl.up4.scratch_floats * sizeof(float));
+        std::vector<float> bias(4 * (size_t)C);
+        for (int g = 0; g < 4; ++g) memcpy(&bias[(size_t)g * C], bh[g], sizeof(float) * C);
+        const size_t chw = (size_t)C * y.H * y.W;
+        std::vector<float> pp(3 * chw);
+        for (int g = 0; g < 3; ++g) memcpy(&pp[g * chw], peep[g], sizeof(float) * chw);
+        if ((l > 0 && upload(y.biasA, convA_b, C)) || upload(y.biasP, convP_b, C) || upload(y.bias_lstm, bias.data(), bias.size()) || upload(y.peep, pp.data(), pp.size()))
+            return fail(EIGEN_ERR_HIP, "weight upload failed (biases and peepholes, layer %d)", l);
     }
     e->have_weights = true;
     return EIGEN_OK;
@@ -1083,7 +735,7 @@ static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
     int cur = p.reset ? 0 : e->hflip;  // h[cur] holds the state of the previous step
     // (The step's dependency chain is serial; only ConvP_l (l > 0) may leave it, onto the side stream below, and only for small launches.  Two half-populations on
     // two streams were byte-identical and slower or equal at every shape: profiles/r04_b_ab_pipe2.txt.)
-    static const bool skip_zero_sources = !(getenv("EIGEN_NO_T0") && atoi(getenv("EIGEN_NO_T0")));  // A/B measurements only
+    const Switches& sw = switches();
     if (p.reset) hipLaunchKernelGGL(e0_init_kernel, dim3(1024), dim3(256), 0, st, p.in, p.in_bstride, e->layer[0].E, e->C0, (int)HW, batch);
     else  // E_0 of the first step from the kept P_0 and the first input (the epilogue's arithmetic: e0_resume_kernel)
         hipLaunchKernelGGL(e0_resume_kernel, dim3(1024), dim3(256), 0, st, (const float*)e->layer[0].P, p.n_in > 0 ? p.in : nullptr, p.in_bstride,
@@ -1092,21 +744,20 @@ static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
     // ConvP_l (l > 0) on a side stream: pays where the launches are a fraction of a round of the chip -- configs[0] (pop 10 at 64 x 64: 10 to 40 blocks per launch) +7.5 %;
     // neutral at configs[1], -0.7 % at 160 x 120 colour pop 50, -2 % at the headline (profiles/r06_q_side_stream_ab.txt), as in round 3.  Hence: only while the layer-1 maps of
     // the batch are less than one block per CU.  A scheduling choice of the launch, not of the arithmetic.  EIGEN_SIDE_STREAM = 0 / 1 forces it (A/B, tests).
-    static const int side_env = getenv("EIGEN_SIDE_STREAM") ? atoi(getenv("EIGEN_SIDE_STREAM")) : -1;
     const bool side_auto = L > 1 && (long long)batch * e->layer[1].H * e->layer[1].W < 512ll * e->n_cu;
-    const bool side_on = (side_env >= 0 ? side_env != 0 : side_auto) && !e->profile_convs;
+    const bool side_on = (sw.side_stream >= 0 ? sw.side_stream != 0 : side_auto) && !e->profile_convs;
     // One PredNet step of genomes [b0, b0 + nb) on stream s; raw4: that range's partial-chain scratch.
     auto run_step = [&](int t, int b0, int nb, hipStream_t s, float* raw4) -> int {
         auto off = [&](float* p, const Layer& y, int mult = 1) { return p + (size_t)b0 * mult * y.C * y.H * y.W; };
         // the step-0 operators skip the sources that are zero after reset_state(): never on a kept state
-        const bool t0 = (t == 0 && p.reset && skip_zero_sources);
+        const bool t0 = (t == 0 && p.reset && sw.skip_zero_sources);
         // bottom-up: E_l from E_{l-1} and the previous prediction P_l
         for (int l = 1; l < L; ++l) {
             Layer& y = e->layer[l];
             ConvArgs a;
             memset(&a, 0, sizeof(a));
             a.src[0].ptr = off(e->layer[l - 1].E, e->layer[l - 1], 2);
-            a.bias = y.biasA; a.P = off(y.P, y); a.E = off(y.E, y, 2);
+            a.bias = y.biasA.p; a.P = off(y.P, y); a.E = off(y.E, y, 2);
             // P_l of the previous step came from the side stream (a call's last step never forks: nothing is pending at its start)
             if (side_on && t > 0) HIPCHK(hipStreamWaitEvent(s, e->ev_join[l], 0));
             HIPCHK(launch_conv(e, t0 ? y.convA_t0 : y.convA, a, nb, s));
@@ -1131,7 +782,7 @@ static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
                 }
                 a.src[k++].ptr = off(y.E, y, 2);
                 if (!t0) a.src[k++].ptr = off(y.h[cur], y);
-                a.bias = y.bias_lstm; a.c_state = off(y.c, y); a.h_out = off(y.h[cur ^ 1], y); a.peep = y.peep;
+                a.bias = y.bias_lstm.p; a.c_state = off(y.c, y); a.h_out = off(y.h[cur ^ 1], y); a.peep = y.peep.p;
                 HIPCHK(launch_conv(e, t0 ? y.lstm_t0 : y.lstm, a, nb, s));
             }
             // P_l (l > 0) is only read by ConvA_l of the NEXT step: nothing in this roll-out reads it after the last one
@@ -1140,7 +791,7 @@ static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
                 ConvArgs a;
                 memset(&a, 0, sizeof(a));
                 a.src[0].ptr = off(y.h[cur ^ 1], y);
-                a.bias = y.biasP; a.Pout = off(y.P, y); a.clip = (l == 0) ? 1 : 0;
+                a.bias = y.biasP.p; a.Pout = off(y.P, y); a.clip = (l == 0) ? 1 : 0;
                 if (l == 0) {
                     if (!last) {  // error units of the next step
                         a.E0 = off(y.E, y, 2);
@@ -1165,7 +816,7 @@ static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
         return EIGEN_OK;
     };
     for (int t = 0; t < n_steps; ++t) {
-        const int rc = run_step(t, 0, batch, st, e->d_raw4);
+        const int rc = run_step(t, 0, batch, st, e->raw4.p);
         if (rc) return rc;
         cur ^= 1;
     }
@@ -1437,39 +1088,32 @@ static int test_conv_impl(eigen_engine* e, int32_t n_src, const float* const* d_
     for (int s = 0; s < n_src; ++s) { if (up[s]) { ++n_up; i_up = s; } else ++n_full; }
     if (n_up > 1 || n_full < 1) return fail(EIGEN_ERR_INVALID, "at most one unpooled source and at least one full-resolution source");
     if (n_up && ((H | W) & 1)) return fail(EIGEN_ERR_INVALID, "an unpooled source needs even H and W");
-    ConvOp op;
-    op.epi = EPI_RAW; op.nsrc = 0; op.H = H; op.W = W; op.Cout = cout;
-    choose_ni(cout, false, &op.NI, &op.n_nblk);
-    op.TW = choose_tw(H, W);
-    op.krows = 0;
+    // the operator and its 2x2-form companion as the planner describes them (conv_plan.h); one weight tensor per source
     const float* sw[3][4] = {{nullptr}, {nullptr}, {nullptr}};
+    int cfull[3] = {0, 0, 0};
     ConvArgs a;
     memset(&a, 0, sizeof(a));
-    for (int s = 0; s < n_src; ++s) {
+    for (int s = 0, k = 0; s < n_src; ++s) {
         if (up[s]) continue;
-        op.src_C[op.nsrc] = cin[s]; op.krows += pad4(cin[s]) * 9; sw[op.nsrc][0] = h_w[s]; a.src[op.nsrc].ptr = d_src[s];
-        op.nsrc++;
+        cfull[k] = cin[s]; sw[k][0] = h_w[s]; a.src[k].ptr = d_src[s];
+        ++k;
     }
-    std::vector<float> pk = pack_weights(op, sw, 0);
-    HIPCHK(hipMalloc((void**)&op.d_wpk, pk.size() * sizeof(float)));
-    HIPCHK(hipMemcpy(op.d_wpk, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+    ConvOp op, u;
+    op.replan(plain_conv_desc(EPI_RAW, 0, cout, H, W, n_full, cfull, 0, switches()));
+    const std::vector<float> pk = pack_weights(op, sw, 0);
+    if (upload(op.wpk, pk.data(), pk.size())) return fail(EIGEN_ERR_HIP, "weight upload failed");
     a.raw = d_out;
-    ConvOp u;
     ConvArgs ua;
     memset(&ua, 0, sizeof(ua));
-    float* d_raw4 = nullptr;
+    DevBuf<float> raw4;
     if (n_up) {
-        u.epi = EPI_UP4; u.nsrc = 1; u.src_C[0] = cin[i_up]; u.H = H / 2; u.W = W / 2; u.Cout = cout;
-        u.NI = op.NI; u.n_nblk = op.n_nblk; u.TW = choose_tw(u.H, u.W);
-        u.krows = pad4(cin[i_up]) * 4;
+        u.replan(up4_desc(op, cin[i_up], H / 2, W / 2, switches()));
         const float* uw[4] = {h_w[i_up], nullptr, nullptr, nullptr};
-        std::vector<float> pku = pack_weights_up4(u, uw, 0);
-        HIPCHK(hipMalloc((void**)&u.d_wpk, pku.size() * sizeof(float)));
-        HIPCHK(hipMemcpy(u.d_wpk, pku.data(), pku.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc((void**)&d_raw4, (size_t)batch * 4 * u.n_nblk * u.NI * 16 * u.H * u.W * sizeof(float)));
+        const std::vector<float> pku = pack_weights_up4(u, uw, 0);
+        if (upload(u.wpk, pku.data(), pku.size()) || raw4.ensure((size_t)batch * u.scratch_floats)) return fail(EIGEN_ERR_HIP, "weight upload failed (unpooled source)");
         ua.src[0].ptr = d_src[i_up];
-        ua.raw = d_raw4;
-        a.acc_init = d_raw4;
+        ua.raw = raw4.p;
+        a.acc_init = raw4.p;
     }
     auto launch_both = [&]() -> hipError_t {
         if (n_up) { hipError_t ru = launch_conv(e, u, ua, batch, (hipStream_t)stream); if (ru != hipSuccess) return ru; }
@@ -1510,9 +1154,6 @@ static int test_conv_impl(eigen_engine* e, int32_t n_src, const float* const* d_
     }
     e->profile_convs = prof;
     hipError_t r2 = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(op.d_wpk);
-    if (u.d_wpk) (void)hipFree(u.d_wpk);
-    if (d_raw4) (void)hipFree(d_raw4);
     if (r != hipSuccess) return fail(EIGEN_ERR_HIP, "conv launch: %s", hipGetErrorString(r));
     if (r2 != hipSuccess) return fail(EIGEN_ERR_HIP, "conv sync: %s", hipGetErrorString(r2));
     return EIGEN_OK;
@@ -1746,6 +1387,42 @@ int eigen_flatten_genomes(int32_t G, int32_t n_in, const int32_t* in_keys, int32
         o_node_off[g + 1] = nn;
     }
     return EIGEN_OK;
+}
+
+// Host-only: the launches of one PredNet step as prednet_run issues them, planned by the same two functions (conv_plan.h) with every switch at its default.
+int eigen_plan_text(int32_t n_layers, const int32_t* channels, int32_t width, int32_t height, int32_t batch, int32_t n_cu, int32_t wino_mask, int32_t step0,
+                    char* out, int32_t cap)
+{
+    const int L = n_layers;
+    if (!channels || !out || cap < 1) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (L < 1 || L > EIGEN_MAX_LAYERS) return fail(EIGEN_ERR_INVALID, "n_layers %d out of range", L);
+    if (width <= 0 || height <= 0 || (width % (1 << (L - 1))) || (height % (1 << (L - 1)))) return fail(EIGEN_ERR_INVALID, "image %dx%d must be divisible by 2^(layers-1)", width, height);
+    if (batch < 1 || n_cu < 1) return fail(EIGEN_ERR_INVALID, "batch and n_cu must be >= 1");
+    int C[EIGEN_MAX_LAYERS], H[EIGEN_MAX_LAYERS], W[EIGEN_MAX_LAYERS];
+    for (int l = 0; l < L; ++l) { C[l] = channels[l]; H[l] = height >> l; W[l] = width >> l; if (C[l] < 1) return fail(EIGEN_ERR_INVALID, "channels[%d] < 1", l); }
+    const Switches sw;   // the default path: the environment is not read
+    LayerPlan plan[EIGEN_MAX_LAYERS];
+    plan_prednet(L, C, H, W, wino_mask < 0 ? EIGEN_WINO_DEFAULT : wino_mask, sw, plan);
+    std::string text;
+    auto line = [&](const char* name, const OpDesc& op, bool up_src, bool acc_init) {
+        const LaunchPlan p = plan_launch(op, batch, n_cu, up_src, acc_init, sw);
+        static const char* const shapes[4] = {"wide", "tall", "half", "pack"};
+        const char* kernel = p.kernel == K_WINO ? "wino" : p.kernel == K_CONVP0 ? "convp0" : p.kernel == K_LSTM0 ? "lstm0" : p.onekb ? "mfma_onekb" : p.w8 ? "mfma_w8" : "mfma";
+        char buf[320];
+        snprintf(buf, sizeof(buf), "%s layer=%d kernel=%s shape=%s epi=%d wino=%d fused=%d vec=%d NI=%d n_nblk=%d tilesX=%d tilesY=%d nparts=%d nwalk=%d grid=%d threads=%d\n", name, op.layer, kernel,
+                 p.kernel == K_WINO ? shapes[p.shape] : p.kernel == K_MFMA ? (op.TW == 8 ? "tw8" : "tw16") : "pixel", op.epi, (int)op.wino, (int)op.fused, (int)p.vec, op.NI, op.n_nblk,
+                 p.tilesX, p.tilesY, p.nparts, p.nwalk, p.grid, p.threads);
+        text += buf;
+    };
+    for (int l = 1; l < L; ++l) line("convA", step0 ? plan[l].convA_t0 : plan[l].convA, false, false);
+    for (int l = L - 1; l >= 0; --l) {
+        const bool fused = l < L - 1 && plan[l].lstm.fused;
+        if (l < L - 1 && !fused) line("up4", plan[l].up4, false, false);
+        line("lstm", step0 ? plan[l].lstm_t0 : plan[l].lstm, fused, l < L - 1 && !fused);
+        line("convP", plan[l].convP, false, false);
+    }
+    snprintf(out, (size_t)cap, "%s", text.c_str());
+    return (int)text.size();
 }
 
 int eigen_test_det_math(eigen_engine* e, const float* d_x, int32_t n, float* d_exp, float* d_sig, float* d_tanh, void* stream)

@@ -19,7 +19,7 @@ PAIR_POPULATION, PAIR_SINGLE = 0, 1
 EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eigen_last_error", "eigen_config_defaults", "eigen_create", "eigen_destroy",
            "eigen_set_prednet_weights", "eigen_set_grid", "eigen_render_cppn", "eigen_eval_cppn_nodes", "eigen_prednet_rollout", "eigen_prednet_sequence", "eigen_flow",
            "eigen_score", "eigen_eval_population", "eigen_eval_images", "eigen_test_conv", "eigen_time_conv", "eigen_test_det_math",
-           "eigen_get_timings", "eigen_conv_profile", "eigen_debug_corners", "eigen_debug_dense_flow", "eigen_prednet_flops_per_step", "eigen_flatten_genomes",
+           "eigen_get_timings", "eigen_conv_profile", "eigen_debug_corners", "eigen_debug_dense_flow", "eigen_prednet_flops_per_step", "eigen_flatten_genomes", "eigen_plan_text",
            "eigen_trainer_create", "eigen_trainer_destroy", "eigen_trainer_set_weights", "eigen_trainer_get_weights", "eigen_trainer_loss_grad",
            "eigen_trainer_get_grads", "eigen_trainer_adam", "eigen_trainer_tape_bytes", "eigen_trainer_loss_grad_ext", "eigen_trainer_evaluate",
            "eigen_trainer_get_state", "eigen_trainer_set_state"]
@@ -101,6 +101,28 @@ def _stream_arg(stream):
     if stream is None:
         return None
     return ctypes.c_void_p(int(getattr(stream, "cuda_stream", stream)))
+
+
+def plan_text(channels, width, height, batch, n_cu=256, wino_mask=-1, step0=False):
+    """The launches of one PredNet step as the library plans them (eigen_plan_text: host-only, default switches; wino_mask < 0: the built-in default):
+    one dict per launch, in launch order -- op, kernel, shape as strings, every other field an int."""
+    lib = load_library()
+    ch = (ctypes.c_int32 * len(channels))(*channels)
+    buf = ctypes.create_string_buffer(1 << 16)
+    n = lib.eigen_plan_text(ctypes.c_int32(len(channels)), ch, ctypes.c_int32(width), ctypes.c_int32(height), ctypes.c_int32(batch), ctypes.c_int32(n_cu),
+                            ctypes.c_int32(wino_mask), ctypes.c_int32(int(step0)), buf, ctypes.c_int32(len(buf)))
+    _check(min(n, 0))
+    if n >= len(buf):
+        raise EngineError("eigen_plan_text: the plan has %d characters, the buffer %d" % (n, len(buf)))
+    rows = []
+    for ln in buf.value.decode().splitlines():
+        op, *fields = ln.split()
+        row = {"op": op}
+        for f in fields:
+            k, v = f.split("=")
+            row[k] = v if k in ("kernel", "shape") else int(v)
+        rows.append(row)
+    return rows
 
 
 class Engine:

@@ -234,6 +234,15 @@ int eigen_flatten_genomes(int32_t n_genomes, int32_t n_inputs, const int32_t* in
  * cell update), 0 = rounds 1-3.  The CPU oracle (oracle/eig_oracle.c: eig_oracle_gate_order) must report the same value. */
 int eigen_gate_order(void);
 
+/* Host-only, like eigen_flatten_genomes (no engine, no device): the launches of ONE PredNet step -- step0 != 0: the first step after reset_state(), otherwise a
+ * steady-state step that is not the roll-out's last -- as csrc/conv_plan.h plans them for `batch` images on a device of n_cu compute units, with every EIGEN_* A/B
+ * switch at its default (the environment is not read).  wino_mask: as eigen_winograd_mask reports it; < 0: the built-in default.  One text line per launch, in
+ * launch order: "<convA|up4|lstm|convP> layer=.. kernel=<mfma|mfma_onekb|mfma_w8|convp0|lstm0|wino> shape=<tw16|tw8|pixel|wide|tall|half|pack> epi=.. wino=..
+ * fused=.. vec=.. NI=.. n_nblk=.. tilesX=.. tilesY=.. nparts=.. nwalk=.. grid=.. threads=..".  Returns the length of the text (it was truncated to cap - 1
+ * characters if that is >= cap) or a negative eigen_status. */
+int eigen_plan_text(int32_t n_layers, const int32_t* channels, int32_t width, int32_t height, int32_t batch, int32_t n_cu,
+                    int32_t wino_mask, int32_t step0, char* out, int32_t cap);
+
 /* The EFFECTIVE operator-form mask of this process (csrc/eigen_engine.hip: EIGEN_WINOGRAD with EIGEN_WINO_FUSEUP=0 folded in as a cleared bit 24): which 3x3
  * convolutions run in which canonical summation order.  Every rank of a multi-GPU run must report the same value -- a population scored
  * under two orders still looks valid (bench.py gathers it).  The CPU oracle's oracle.wino_mask_default() states the same rule. */

@@ -72,6 +72,7 @@ def lib():
         _LIB.eig_oracle_conv_chain.restype = ctypes.c_int
         _LIB.eig_oracle_wino_chain.restype = ctypes.c_int
         _LIB.eig_oracle_wino_chain_m.restype = ctypes.c_int
+        _LIB.eig_oracle_wino_form.restype = ctypes.c_int
         for f in ("eig_oracle_farneback", "eig_oracle_fb_vectors", "eig_oracle_fb_levels", "eig_oracle_fb_grid_step"):
             getattr(_LIB, f).restype = ctypes.c_int
     return _LIB
@@ -120,6 +121,13 @@ def tensor_names(n_layers):
 # engine's default is the same mask); bit 24: the unpooled source inside the Winograd ConvLSTM's chains (eig_wino_fuse_up); bits 25 / 26 / 27:
 # the class bits of the ConvLSTMs / ConvAs / ConvPs -- an operator is a Winograd F(4x4, 3x3) one only with its own bit AND its class bit set (eig_wino_op)
 WINO_AUTO = 0x0FFFFFFE
+
+
+def wino_form(wino_mask, kind, l, channels, w, h):
+    """(winograd, fused) of operator `kind` (0 ConvLSTM_l, 1 ConvA_l, 2 ConvP_l) as the roll-out decides it (eig_oracle.c: eig_oracle_wino_form)."""
+    ch = (ctypes.c_int * len(channels))(*channels)
+    r = lib().eig_oracle_wino_form(ctypes.c_int(int(wino_mask)), ctypes.c_int(kind), ctypes.c_int(l), ctypes.c_int(len(channels)), ch, ctypes.c_int(w), ctypes.c_int(h))
+    return bool(r & 1), bool(r & 2)
 
 
 def wino_mask_default():

@@ -486,7 +486,7 @@ static void wino_finish(float* out, const float* M, int Cout, int H, int W, int 
 static size_t wino_m_floats(int Cout, int H, int W, int m) { return (size_t)WINO_NPOS(m) * Cout * wino_th(H, m) * wino_tw(W, m); }
 #define EIG_WINO_M 4   /* tile size of every Winograd operator of the roll-out: F(4x4, 3x3) (csrc/conv_wino4.h) */
 
-/* Which operators take the Winograd form (the HIP engine applies the same rule, eigen_engine.hip: wino_op).  wino_mask: bit l =
+/* Which operators take the Winograd form (the HIP engine applies the same rule, csrc/conv_plan.h: wino_op).  wino_mask: bit l =
  * ConvLSTM_l, bit 8 + l = ConvA_l, bit 16 + l = ConvP_l, AND the class bit 25 / 26 / 27 of the ConvLSTMs / ConvAs / ConvPs (rounds 4-5: the class bit chose F(4x4) over
  * F(2x2); with the F(2x2) kernel gone an operator whose class bit is clear is a direct one).  kind 0 ConvLSTM_l, 1 ConvA_l, 2 ConvP_l; Cin: every full-resolution source
  * has a multiple of 8 channels; Cout (per gate): 16-channel groups, and for the plain convolutions N-blocks of 48 or 64 columns
@@ -514,6 +514,16 @@ static int eig_wino_fuse_up(int wino_mask, int l, int L, int W, int Cup) { retur
 static int eig_wino_lstm(int wino_mask, int l, int L, int C, int H, int W, int Cup)
 {
     return eig_wino_op(wino_mask, 0, l, C, C, H, W, l == L - 1) && (l == L - 1 || eig_wino_fuse_up(wino_mask, l, L, W, Cup));
+}
+
+/* exported for tests/test_launch_plan.py: the form the roll-out below gives operator `kind` (0 ConvLSTM_l, 1 ConvA_l, 2 ConvP_l) of an L-layer net with ch[] channels on
+ * W x H images -- bit 0: Winograd form, bit 1: the unpooled source inside the ConvLSTM's chains.  The engine's planner (csrc/conv_plan.h) must decide alike. */
+int eig_oracle_wino_form(int wino_mask, int kind, int l, int L, const int* ch, int W, int H)
+{
+    const int C = ch[l], h = H >> l, w = W >> l;
+    if (kind == 1) return l > 0 && eig_wino_op(wino_mask, 1, l, ch[l - 1], C, H >> (l - 1), W >> (l - 1), 0);
+    if (kind == 2) return eig_wino_op(wino_mask, 2, l, C, C, h, w, l == L - 1);
+    return eig_wino_lstm(wino_mask, l, L, C, h, w, l < L - 1 ? ch[l + 1] : 0) ? (l < L - 1 ? 3 : 1) : 0;
 }
 
 /* exported for kernel-level tests: out[Cout][H][W] = Winograd chain over the listed full-resolution sources (canonical order) */

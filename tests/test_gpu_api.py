@@ -253,3 +253,33 @@ def test_specialised_operators_equal_the_general_mfma_path(cuda):
     with ThreadPoolExecutor(max_workers=4) as pool:   # (fresh processes sharing the one GPU: the runs are tiny)
         for env, got in zip(envs, pool.map(run, envs)):
             assert got == base, env
+
+
+def test_weights_can_be_set_again_on_the_same_engine(cuda):
+    """eigen_set_prednet_weights twice on one engine (the operators keep their device buffers and overwrite them): the roll-out after the second call is
+    byte-identical to that of a fresh engine given the second weight set, and differs from the first set's."""
+    import torch
+    from evolutionary_illusion_generator_amd.engine import Engine
+    w, h, ch, B = 64, 64, [3, 48, 96], 3   # Winograd operators and the image layer's direct ones
+    rng = np.random.default_rng(11)
+    img = torch.from_numpy(rng.integers(0, 256, (B, ch[0], h, w), dtype=np.uint8)).cuda()
+    wts = [weights.synthetic_prednet_weights(ch, w, h, seed=s) for s in (3, 4)]
+
+    def frames(eng):
+        fr = torch.zeros((B, 6, ch[0], h, w), dtype=torch.uint8, device="cuda")
+        eng.prednet_rollout(img, B, 6, 0, fr)
+        torch.cuda.synchronize()
+        return fr.cpu().numpy()
+
+    e = Engine(w, h, ch, B, n_repeat=4, n_ext=2)
+    e.set_weights(wts[0])
+    first = frames(e)
+    e.set_weights(wts[1])
+    again = frames(e)
+    e.close()
+    fresh_engine = Engine(w, h, ch, B, n_repeat=4, n_ext=2)
+    fresh_engine.set_weights(wts[1])
+    fresh = frames(fresh_engine)
+    fresh_engine.close()
+    assert (again == fresh).all()
+    assert (again != first).any()
