@@ -72,6 +72,7 @@ struct eigen_trainer {
     long long slab_floats = 0;
     double *d_part = nullptr, *d_loss = nullptr;
     double *d_spart = nullptr, *d_step = nullptr;  // per-step loss: partials [max_steps][STEP_LOSS_BLOCKS], losses [max_steps]
+    double* d_err = nullptr;                       // error-unit means err[s][l]: [max_steps][n_layers]
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -236,6 +237,7 @@ int eigen_trainer_create(const eigen_trainer_config* cfg, eigen_trainer** out)
     add((void**)&t->d_loss, 8);
     add((void**)&t->d_spart, T * STEP_LOSS_BLOCKS * 8);
     add((void**)&t->d_step, T * 8);
+    add((void**)&t->d_err, T * L * 8);
     for (int l = 0; l < L; ++l) {
         TLayer& y = t->ly[l];
         const long long CHW = y.C * y.HW;
@@ -407,15 +409,58 @@ static void forward_step(eigen_trainer* t, hipStream_t st, int B, int in, int ou
 static void step_losses(eigen_trainer* t, hipStream_t st, const float* P0, const uint8_t* x0, long long bstride, int n, int B, double* step_loss)
 {
     const long long C0HW = t->ly[0].C * t->ly[0].HW;
-    hipLaunchKernelGGL(tloss_step_partial_kernel, dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, P0, x0, bstride, B, C0HW, t->d_spart);
-    hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, (double)(B * C0HW), step_loss);
+    hipLaunchKernelGGL(tloss_step_partial_kernel<TERM_SQ>, dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, P0, x0, bstride, B, C0HW, t->d_spart);
+    hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, (double)(B * C0HW), step_loss, 1);
 }
 
-int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
-                                int32_t requant, int32_t reset, const double* h_step_w, double* h_loss, float* d_pred, void* stream)
+// image-layer column of n consecutive rows of the error table: row r is P0 of step r against the TRUE frame it predicts,
+// mean of [relu(x - P0), relu(P0 - x)] over b and the 2 C_0 error channels; err points at the first row's entry (row stride L)
+static void image_errors(eigen_trainer* t, hipStream_t st, const float* P0, const uint8_t* x0, long long bstride, int n, int B, double* err)
+{
+    const long long C0HW = t->ly[0].C * t->ly[0].HW;
+    hipLaunchKernelGGL(tloss_step_partial_kernel<TERM_ABS>, dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, P0, x0, bstride, B, C0HW, t->d_spart);
+    hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, (double)(B * 2 * C0HW), err, t->L);
+}
+
+// columns l > 0 of n consecutive rows of the error table: the mean of E_l over n consecutive tape slots from `slot` on; err
+// points at the first row (entry of layer 0)
+static void upper_errors(eigen_trainer* t, hipStream_t st, int slot, int n, int B, double* err)
+{
+    for (int l = 1; l < t->L; ++l) {
+        const TLayer& y = t->ly[l];
+        const long long ECHW = 2 * y.C * y.HW;
+        hipLaunchKernelGGL(tloss_step_partial_kernel<TERM_SUM>, dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, (const float*)(y.E + (long long)slot * B * ECHW),
+                           (const uint8_t*)nullptr, 0ll, B, ECHW, t->d_spart);
+        hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, (double)(B * ECHW), err + l, t->L);
+    }
+}
+
+// layer weights of the error-unit objective into lam[L]: NULL is L_0, [1, 0, ...]
+static int layer_weights(const eigen_trainer* t, const double* h_layer_w, double* lam)
+{
+    double sum = 0.0;
+    for (int l = 0; l < t->L; ++l) {
+        lam[l] = h_layer_w ? h_layer_w[l] : (l == 0 ? 1.0 : 0.0);
+        if (!(lam[l] >= 0.0) || !std::isfinite(lam[l])) return tfail(EIGEN_ERR_INVALID, "layer weight %d is %g: weights must be finite and >= 0", l, lam[l]);
+        sum += lam[l];
+    }
+    if (!(sum > 0.0)) return tfail(EIGEN_ERR_INVALID, "all %d layer weights are zero", t->L);
+    return EIGEN_OK;
+}
+
+int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                double* h_layer_err, float* d_pred, void* stream)
 {
     int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, t ? t->cfg.max_steps : 0);
     if (rc) return rc;
+    if (objective != EIGEN_OBJ_MSE && objective != EIGEN_OBJ_ERROR) return tfail(EIGEN_ERR_INVALID, "objective %d is neither EIGEN_OBJ_MSE nor EIGEN_OBJ_ERROR", objective);
+    double lam[EIGEN_MAX_LAYERS];
+    if (h_layer_w || objective == EIGEN_OBJ_ERROR) {
+        rc = layer_weights(t, h_layer_w, lam);
+        if (rc) return rc;
+    }
+    const bool by_error = objective == EIGEN_OBJ_ERROR;
     const int L = t->L, T = n_steps, B = batch;
     const long long C0HW = t->ly[0].C * t->ly[0].HW;
     double sum_w = 0.0;
@@ -441,7 +486,15 @@ int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64
 
     // ---- loss.  Without weights: one sum over all terms; with weights: one mse per step, combined on the host in step order
     const long long n_terms = (long long)(T - 1) * B * C0HW;
-    if (T >= 2 && !h_step_w) {
+    const bool want_table = T >= 2 && (h_layer_err || (by_error && h_loss));
+    if (want_table) {
+        // row s: P0 of step s (slot s + 1) against frame s + 1, and E_l of step s + 1 (tape slot s + 1)
+        image_errors(t, st, t->ly[0].P + (long long)B * C0HW, d_frames + C0HW, bstride, T - 1, B, t->d_err);
+        upper_errors(t, st, 1, T - 1, B, t->d_err);
+    }
+    if (by_error) {
+        if (T < 2) TCHK(hipMemsetAsync(t->d_loss, 0, 8, st));
+    } else if (T >= 2 && !h_step_w) {
         hipLaunchKernelGGL(tloss_partial_kernel, dim3(LOSS_BLOCKS), dim3(EW_T), 0, st, (const float*)t->ly[0].P, d_frames, (long long)bstride, T - 1, B, C0HW, t->d_part);
         hipLaunchKernelGGL(tloss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)t->d_part, LOSS_BLOCKS, 1.0 / (double)n_terms, t->d_loss);
     } else if (T >= 2) {
@@ -454,6 +507,12 @@ int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64
         if (T < 2) return 0.f;
         if (!h_step_w) return (float)(2.0 / (double)n_terms);
         return (float)(2.0 * h_step_w[s] / (sum_w * (double)(B * C0HW)));
+    };
+    // error-unit objective: d loss / d (one element of E_l of term s) = w_s lambda_l / (sum w * numel(E_l)), formed in double
+    auto err_scale = [&](int s, int l) -> float {
+        const double numel = (double)B * 2.0 * (double)(t->ly[l].C * t->ly[l].HW);
+        if (!h_step_w) return (float)(lam[l] / ((double)(T - 1) * numel));
+        return (float)(h_step_w[s] * lam[l] / (sum_w * numel));
     };
 
     // ---- backward through time
@@ -472,8 +531,15 @@ int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64
             const float* P = y.P + (long long)(s + 1) * B * CHW;
             float* dV = y.dV + (long long)s * B * CHW;
             const uint8_t* xn = (l == 0 && s < T - 1) ? d_frames + (long long)(s + 1) * C0HW : nullptr;
-            hipLaunchKernelGGL(tpact_bwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (const float*)y.dPn, xn, (long long)bstride, CHW,
-                               xn ? loss_scale(s) : 0.f, l == 0 ? 1 : 0, (long long)B * CHW, dV);
+            const float scale = !xn ? 0.f : by_error ? err_scale(s, 0) : loss_scale(s);
+            // an error-unit term whose seed is zero is left out, not added as +0.0f (which would turn a -0 gradient into +0)
+            if (by_error && scale == 0.f) xn = nullptr;
+            if (by_error && xn)
+                hipLaunchKernelGGL(tpact_bwd_kernel<1>, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (const float*)y.dPn, xn, (long long)bstride, CHW, scale, 1,
+                                   (long long)B * CHW, dV);
+            else
+                hipLaunchKernelGGL(tpact_bwd_kernel<0>, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (const float*)y.dPn, xn, (long long)bstride, CHW, scale,
+                                   l == 0 ? 1 : 0, (long long)B * CHW, dV);
             conv(st, y.dhP, y.C, y.H, y.W, B, nullptr, 0, {src(dV, CHW, y.C, 0, prm + p.pW, 1)});
             float* G = y.G + (long long)s * B * 4 * CHW;
             const float* pk = prm + p.peep;
@@ -492,7 +558,12 @@ int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64
             const long long CHW = y.C * y.HW;
             const float* E = y.E + (long long)s * B * 2 * CHW;
             float* ZA = l > 0 ? y.ZA + (long long)s * B * 4 * CHW : nullptr;
-            hipLaunchKernelGGL(terr_bwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const float*)y.dE, E, y.dPn, ZA, y.C, y.H, y.W, B);
+            // E_l of step s belongs to term s - 1 (the errors of a call's first step belong to no call)
+            const float seed = by_error && l > 0 && s >= 1 ? err_scale(s - 1, l) : 0.f;
+            if (seed != 0.f)
+                hipLaunchKernelGGL(terr_bwd_kernel<1>, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const float*)y.dE, E, y.dPn, ZA, y.C, y.H, y.W, B, seed);
+            else
+                hipLaunchKernelGGL(terr_bwd_kernel<0>, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const float*)y.dE, E, y.dPn, ZA, y.C, y.H, y.W, B, 0.f);
             if (l > 0) {
                 TLayer& yb = t->ly[l - 1];
                 conv(st, yb.dE, 2 * yb.C, yb.H, yb.W, B, nullptr, 1, {src(ZA, 4 * CHW, y.C, 0, prm + t->lp[l].aW, 1)});
@@ -526,7 +597,25 @@ int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64
     TCHK(hipGetLastError());
     t->state_batch = B;
     t->state_slot = T;
-    if (h_loss && h_step_w && T >= 2) {
+    std::vector<double> tab;
+    if (want_table) {
+        tab.resize((size_t)(T - 1) * L);
+        TCHK(hipMemcpyAsync(tab.data(), t->d_err, tab.size() * 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+        if (h_layer_err) memcpy(h_layer_err, tab.data(), tab.size() * 8);
+    }
+    if (h_loss && by_error && T >= 2) {
+        // sum_s w_s sum_l lambda_l err[s][l] / sum_s w_s, in (step, layer) order (train.combine_terms states the same sums)
+        double acc = 0.0, tot = 0.0;
+        for (int s = 0; s < T - 1; ++s) {
+            double row = 0.0;
+            for (int l = 0; l < L; ++l) row += lam[l] * tab[(size_t)s * L + l];
+            const double w = h_step_w ? h_step_w[s] : 1.0;
+            acc += w * row;
+            tot += w;
+        }
+        *h_loss = acc / tot;
+    } else if (h_loss && h_step_w && T >= 2) {
         std::vector<double> sl(T - 1);
         TCHK(hipMemcpyAsync(sl.data(), t->d_step, (T - 1) * 8, hipMemcpyDeviceToHost, st));
         TCHK(hipStreamSynchronize(st));
@@ -543,29 +632,47 @@ int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64
     return EIGEN_OK;
 }
 
+int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                int32_t requant, int32_t reset, const double* h_step_w, double* h_loss, float* d_pred, void* stream)
+{
+    return eigen_trainer_loss_grad_obj(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_w, EIGEN_OBJ_MSE, nullptr, h_loss, nullptr, d_pred, stream);
+}
+
 int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
                             int32_t reset, double* h_loss, float* d_pred, void* stream)
 {
     return eigen_trainer_loss_grad_ext(t, d_frames, bstride, batch, n_steps, n_steps, 0, reset, nullptr, h_loss, d_pred, stream);
 }
 
-int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
-                           int32_t requant, int32_t reset, double* h_step_loss, float* d_pred, void* stream)
+int eigen_trainer_evaluate_err(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                               int32_t requant, int32_t reset, double* h_step_loss, double* h_layer_err, float* d_pred, void* stream)
 {
     int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, -1);
     if (rc) return rc;
-    const int T = n_steps, B = batch, M = t->cfg.max_steps;
+    const int T = n_steps, B = batch, M = t->cfg.max_steps, L = t->L;
     const long long C0HW = t->ly[0].C * t->ly[0].HW;
     TCHK(hipSetDevice(t->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     rc = start_state(t, st, B, reset);
     if (rc) return rc;
     // slots 0 and 1 of h, c, P in turn, slot 0 of E, gates and ZA; the loss of step s goes to d_step[s % max_steps], read back
-    // whenever that table is full
+    // whenever that table is full.  Row r of the error table lives at d_err[r % max_steps]: its image-layer entry is reduced after
+    // step r, its upper entries (E_l of step r + 1) after step r + 1, and the rows are read back once the table's last row, or the
+    // call's, is complete -- ahead of the image-layer entry that reuses row 0.
     for (int s = 0; s < T; ++s) {
         const int in = s & 1, out = in ^ 1;
         forward_step(t, st, B, in, out, 0, s < n_fed ? d_frames + (long long)s * C0HW : nullptr, bstride, requant,
                      d_pred ? d_pred + (long long)s * C0HW : nullptr, (long long)T * C0HW);
+        if (h_layer_err && s >= 1) {
+            const int r = s - 1;
+            upper_errors(t, st, 0, 1, B, t->d_err + (long long)(r % M) * L);
+            if (r % M == M - 1 || r == T - 2) {
+                const int first = r - r % M;
+                TCHK(hipMemcpyAsync(h_layer_err + (long long)first * L, t->d_err, (long long)(r - first + 1) * L * 8, hipMemcpyDeviceToHost, st));
+            }
+        }
+        if (h_layer_err && s < T - 1)
+            image_errors(t, st, t->ly[0].P + (long long)out * B * C0HW, d_frames + (long long)(s + 1) * C0HW, bstride, 1, B, t->d_err + (long long)(s % M) * L);
         if (s < T - 1) {
             step_losses(t, st, t->ly[0].P + (long long)out * B * C0HW, d_frames + (long long)(s + 1) * C0HW, bstride, 1, B, t->d_step + s % M);
             if (h_step_loss && (s % M == M - 1 || s == T - 2)) {
@@ -577,8 +684,14 @@ int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bs
     TCHK(hipGetLastError());
     t->state_batch = B;
     t->state_slot = T & 1;
-    if (h_step_loss) TCHK(hipStreamSynchronize(st));
+    if (h_step_loss || h_layer_err) TCHK(hipStreamSynchronize(st));
     return EIGEN_OK;
+}
+
+int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                           int32_t requant, int32_t reset, double* h_step_loss, float* d_pred, void* stream)
+{
+    return eigen_trainer_evaluate_err(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_loss, nullptr, d_pred, stream);
 }
 
 // Adam moments, step count and the kept sequence state, out.  h_m / h_v: host tables in eigen_set_prednet_weights order (both or

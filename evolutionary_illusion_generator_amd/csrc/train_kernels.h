@@ -283,9 +283,11 @@ __global__ void __launch_bounds__(EW_T) terr_fed_fwd_kernel(const float* __restr
 
 // Backward of E = [relu(A - P), relu(P - A)] (relu'(0) = 0: a unit that is zero passes nothing): dP_prev = -dA.  For l > 0 the
 // max-pool / ReLU backward follows: dA goes to the first maximum of the 2x2 window of relu(ZA) in row-major order, where ZA > 0;
-// ZA is overwritten with dZA (each thread owns its window).
+// ZA is overwritten with dZA (each thread owns its window).  SEED = 1 (the error-unit objective, layers l > 0): `seed`, the
+// derivative of the loss by every element of this E, is added to dE ahead of the mask; SEED = 0 is the arithmetic without it.
+template <int SEED>
 __global__ void __launch_bounds__(EW_T) terr_bwd_kernel(const float* __restrict__ dE, const float* __restrict__ E, float* __restrict__ dP,
-                                                        float* za, int C, int H, int W, int B)
+                                                        float* za, int C, int H, int W, int B, float seed)
 {
     const int HW = H * W;
     const long long i = (long long)blockIdx.x * EW_T + threadIdx.x;
@@ -294,7 +296,9 @@ __global__ void __launch_bounds__(EW_T) terr_bwd_kernel(const float* __restrict_
     const int r = (int)(i - (long long)b * C * HW);
     const int c = r / HW, j = r - c * HW;
     const long long e0 = (long long)b * 2 * C * HW + (long long)c * HW + j, e1 = e0 + (long long)C * HW;
-    const float dA = (E[e0] > 0.f ? dE[e0] : 0.f) - (E[e1] > 0.f ? dE[e1] : 0.f);
+    float d0 = dE[e0], d1 = dE[e1];
+    if constexpr (SEED) { d0 += seed; d1 += seed; }
+    const float dA = (E[e0] > 0.f ? d0 : 0.f) - (E[e1] > 0.f ? d1 : 0.f);
     dP[i] = -dA;
     if (za) {
         const int y = j / W, xx = j - y * W;
@@ -404,7 +408,10 @@ __global__ void __launch_bounds__(EW_T) tpact_fwd_kernel(float* P, long long n, 
 
 // dV = (dP + dloss) * act'(V).  The activation's derivative is read off P: clamp passes where 0 < v < 1 (0 < P < 1), relu where
 // v > 0 (P > 0).  dloss (layer 0, steps 0..T-2) = loss_scale (P0_t - x_{t+1}) with frame t + 1 of sample b at x + b * xbstride;
-// loss_scale is per launch, i.e. per step: 2 / n_terms without step weights, 2 w_t / (sum w * numel) with them.
+// loss_scale is per launch, i.e. per step: 2 / n_terms without step weights, 2 w_t / (sum w * numel) with them.  OBJ = 1 (the
+// error-unit objective): dloss = loss_scale sign(P0_t - x_{t+1}), sign(0) = 0, the derivative of the image layer's error units
+// against the true frame; loss_scale = w_t lambda_0 / (sum w * 2 numel).
+template <int OBJ>
 __global__ void __launch_bounds__(EW_T) tpact_bwd_kernel(const float* __restrict__ P, const float* __restrict__ dP, const uint8_t* __restrict__ x,
                                                          long long xbstride, long long per_b, float loss_scale, int clamp01, long long n,
                                                          float* __restrict__ dV)
@@ -415,7 +422,13 @@ __global__ void __launch_bounds__(EW_T) tpact_bwd_kernel(const float* __restrict
     float g = dP[i];
     if (x) {
         const long long b = i / per_b;
-        g += loss_scale * (p - (float)x[b * xbstride + (i - b * per_b)] / 255.0f);
+        const float d = p - (float)x[b * xbstride + (i - b * per_b)] / 255.0f;
+        if constexpr (OBJ == 0) {
+            g += loss_scale * d;
+        } else {
+            if (d > 0.f) g += loss_scale;
+            else if (d < 0.f) g -= loss_scale;
+        }
     }
     const bool pass = clamp01 ? (p > 0.f && p < 1.f) : p > 0.f;
     dV[i] = pass ? g : 0.f;
@@ -456,6 +469,11 @@ __global__ void __launch_bounds__(64) tloss_final_kernel(const double* __restric
 // per-step loss partials: block (k, t) sums (P0_t - x_{t+1})^2 over its fixed strided slice of the (b, element) terms of step t
 // in double, then a fixed LDS tree; part[t][k].  P0 points at the prediction of the first step, x at the frame it is compared
 // with; step t is P0 + t * B * per_b against x + t * per_b.
+// TERM_ABS sums the image layer's error units against that frame instead, relu(x - P0) + relu(P0 - x), each formed in float as
+// terr_fwd_kernel forms them.  TERM_SUM sums the floats themselves (x unused): P0 is then one layer's E tape, [B][2C][H][W] per
+// step, per_b = 2 C H W.
+enum { TERM_SQ = 0, TERM_ABS = 1, TERM_SUM = 2 };
+template <int TERM>
 __global__ void __launch_bounds__(EW_T) tloss_step_partial_kernel(const float* __restrict__ P0, const uint8_t* __restrict__ x, long long xbstride,
                                                                   int B, long long per_b, double* __restrict__ part)
 {
@@ -466,9 +484,18 @@ __global__ void __launch_bounds__(EW_T) tloss_step_partial_kernel(const float* _
     const uint8_t* xt = x + (long long)t * per_b;
     double s = 0.0;
     for (long long i = (long long)blockIdx.x * EW_T + threadIdx.x; i < n; i += (long long)gridDim.x * EW_T) {
-        const long long b = i / per_b;
-        const double d = (double)p[i] - (double)((float)xt[b * xbstride + (i - b * per_b)] / 255.0f);
-        s += d * d;
+        if constexpr (TERM == TERM_SUM) {
+            s += (double)p[i];
+        } else {
+            const long long b = i / per_b;
+            const float xv = (float)xt[b * xbstride + (i - b * per_b)] / 255.0f;
+            if constexpr (TERM == TERM_SQ) {
+                const double d = (double)p[i] - (double)xv;
+                s += d * d;
+            } else {
+                s += (double)fmaxf(xv - p[i], 0.f) + (double)fmaxf(p[i] - xv, 0.f);
+            }
+        }
     }
     red[threadIdx.x] = s;
     __syncthreads();
@@ -479,14 +506,16 @@ __global__ void __launch_bounds__(EW_T) tloss_step_partial_kernel(const float* _
     if (threadIdx.x == 0) part[(long long)t * gridDim.x + blockIdx.x] = red[0];
 }
 
-// step_loss[t] = (part[t][0] + part[t][1] + ... in order) / numel, one thread per step
-__global__ void __launch_bounds__(64) tloss_step_final_kernel(const double* __restrict__ part, int nblk, int n_steps, double numel, double* __restrict__ step_loss)
+// step_loss[t * stride] = (part[t][0] + part[t][1] + ... in order) / numel, one thread per step (stride > 1: one column of the
+// [step][layer] table of error-unit means)
+__global__ void __launch_bounds__(64) tloss_step_final_kernel(const double* __restrict__ part, int nblk, int n_steps, double numel, double* __restrict__ step_loss,
+                                                              int stride)
 {
     const int t = blockIdx.x * 64 + threadIdx.x;
     if (t >= n_steps) return;
     double s = 0.0;
     for (int k = 0; k < nblk; ++k) s += part[(long long)t * nblk + k];
-    step_loss[t] = s / numel;
+    step_loss[(long long)t * stride] = s / numel;
 }
 
 // Adam as chainer defines it: m += (1 - b1) (g - m); v += (1 - b2) (g^2 - v); p -= lr_t m / (sqrt(v) + eps).  omb1 = 1 - b1 and

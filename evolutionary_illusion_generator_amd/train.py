@@ -1,6 +1,7 @@
 """PredNet training on frame sequences (include/eigen_engine.h eigen_trainer_*).
 
-Next-frame MSE of the float prediction, full backprop through time within a call, Adam as chainer defines it; every kernel is
+Next-frame MSE of the float prediction or, per call, PredNet's own objective on the error units (``objective="error"``: L_0 by
+default, L_all with ``layer_weights=[1, 0.1, ...]``), full backprop through time within a call, Adam as chainer defines it; every kernel is
 HIP for gfx950 (csrc/prednet_train.hip), there is no CPU or PyTorch fallback.  The trained weights are a plain
 ``{name: float32 array}`` table, usable as ``model_name`` anywhere the fitness path takes one, and
 ``weights.save_chainer_npz`` writes them as a chainer npz file.
@@ -29,6 +30,11 @@ def _bind(lib):
                                                 ctypes.c_void_p]
     lib.eigen_trainer_evaluate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.eigen_trainer_loss_grad_obj.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.eigen_trainer_evaluate_err.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int32]
     lib.eigen_trainer_set_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -40,6 +46,49 @@ def _bind(lib):
 
 HYPER = ("alpha", "beta1", "beta2", "eps")
 SEQ_PARTS = ("h", "c", "P")
+OBJECTIVES = {"mse": 0, "error": 1}  # eigen_objective
+
+
+def check_layer_weights(layer_weights, n_layers):
+    """layer_weights as a contiguous float64 [n_layers] array, or None (L_0: [1, 0, ...]).  ValueError on another length; the
+    value rules (>= 0, finite, not all zero) are the library's."""
+    if layer_weights is None:
+        return None
+    lam = np.ascontiguousarray(layer_weights, dtype=np.float64)
+    if lam.shape != (n_layers,):
+        raise ValueError("layer_weights must have one entry per layer (%d), got shape %s" % (n_layers, lam.shape))
+    return lam
+
+
+def combine_terms(table, layer_weights=None, step_weights=None):
+    """The loss of the error-unit objective from the table err[s][l] (float64 [T - 1, L]), as the library forms it: in double,
+    sum_s w_s (sum_l lambda_l err[s][l]) / sum_s w_s, added in (step, layer) order.  layer_weights None: L_0, [1, 0, ...];
+    step_weights None: all one.  An empty table (T = 1) gives 0."""
+    table = np.asarray(table, np.float64)
+    if table.ndim != 2:
+        raise ValueError("table must be [T - 1, L], got shape %s" % (table.shape,))
+    n, L = table.shape
+    lam = check_layer_weights(layer_weights, L)
+    lam = [1.0] + [0.0] * (L - 1) if lam is None else [float(v) for v in lam]
+    if step_weights is None:
+        w = [1.0] * n
+    else:
+        w = [float(v) for v in np.asarray(step_weights, np.float64).ravel()]
+        if len(w) != n:
+            raise ValueError("step_weights must have T - 1 = %d entries, got %d" % (n, len(w)))
+    bad = [v for v in lam + w if not (v >= 0.0 and np.isfinite(v))]
+    if bad or not sum(lam) > 0.0 or (n and not sum(w) > 0.0):
+        raise ValueError("weights must be finite, >= 0 and not all zero")
+    if n == 0:
+        return 0.0
+    acc, tot = 0.0, 0.0
+    for s in range(n):
+        row = 0.0
+        for l in range(L):
+            row += lam[l] * float(table[s, l])
+        acc += w[s] * row
+        tot += w[s]
+    return acc / tot
 
 
 def seq_state_shapes(channels, w, h, batch):
@@ -203,49 +252,64 @@ class PredNetTrainer:
     def _fed(self, n_fed, T):
         return T if n_fed is None else int(n_fed)   # (the range rules are the library's: EngineError -1)
 
-    def forward_backward(self, frames, reset=True, pred=False, stream=None, n_fed=None, requant=False, step_weights=None):
+    def forward_backward(self, frames, reset=True, pred=False, stream=None, n_fed=None, requant=False, step_weights=None, objective="mse",
+                         layer_weights=None, layer_errors=False):
         """Loss of frames uint8 [n, T, C, H, W] (numpy or a device tensor, n <= batch) and the gradients, kept on the device
         (``grads()``).  reset=False continues from the state the previous call left (the same n), as a constant.
         pred=True also returns the float predictions P0 [n, T, C, H, W] (numpy).
 
         n_fed: the first n_fed steps read their frame, the rest are fed the previous prediction (None: all T read theirs);
         requant: feed the prediction back through the byte the inference engine emits, as a constant; step_weights: T - 1
-        weights >= 0 of the loss terms (term s: prediction s against frame s + 1), None: all one."""
+        weights >= 0 of the loss terms (term s: prediction s against frame s + 1), None: all one.
+
+        objective: "mse", the squared error of the image-layer prediction, or "error", PredNet's own objective: the means of
+        the error units err[s][l] (layer 0 against the true next frame, half the mean absolute error; layers above as the
+        network computed them at step s + 1) weighted by layer_weights, one weight >= 0 per layer: None is L_0, [1, 0, ...];
+        L_all is [1, 0.1, ...].  The loss is ``combine_terms`` of the table.  layer_errors=True appends the float64 [T - 1, L]
+        table to the return value, under either objective."""
         d = self._frames(frames)
         n, T = int(d.shape[0]), int(d.shape[1])
         n_fed = self._fed(n_fed, T)
+        if objective not in OBJECTIVES:
+            raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
+        lam = check_layer_weights(layer_weights, len(self.channels))
         w_arr = None
         if step_weights is not None:
             w_arr = np.ascontiguousarray(step_weights, dtype=np.float64)
             if w_arr.shape != (T - 1,):
                 raise ValueError("step_weights must have T - 1 = %d entries, got shape %s" % (T - 1, w_arr.shape))
         loss = ctypes.c_double(0.0)
+        by_error = objective == "error"
+        table = np.zeros((max(T - 1, 1), len(self.channels)), np.float64) if (layer_errors or by_error) else None
         d_pred = self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
-        _check(self.lib.eigen_trainer_loss_grad_ext(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n),
+        _check(self.lib.eigen_trainer_loss_grad_obj(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n),
                                                     ctypes.c_int32(T), ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))),
                                                     ctypes.c_int32(int(bool(reset))), ctypes.c_void_p(w_arr.ctypes.data if w_arr is not None and w_arr.size else None),
-                                                    ctypes.byref(loss), _ptr(d_pred), _stream_arg(stream)))
-        if pred:
-            return loss.value, d_pred.cpu().numpy()
-        return loss.value
+                                                    ctypes.c_int32(OBJECTIVES[objective]), _ptr(lam), ctypes.byref(loss), _ptr(table), _ptr(d_pred),
+                                                    _stream_arg(stream)))
+        if table is not None:
+            table = table[:T - 1]
+        value = combine_terms(table, lam, w_arr if w_arr is not None and w_arr.size else None) if by_error else loss.value
+        out = (value,) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table,) if layer_errors else ())
+        return out[0] if len(out) == 1 else out
 
-    def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False):
+    def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False, layer_errors=False):
         """Forward only, no tape: the mean squared error of every step of frames uint8 [n, T, C, H, W], T of any length, as
         float64 [T - 1] (entry s: prediction s against frame s + 1).  Gradients and Adam state are untouched; the kept sequence
         state is shared with forward_backward (reset=False of either continues the last call of either).  pred=True also
-        returns the float predictions [n, T, C, H, W]."""
+        returns the float predictions [n, T, C, H, W]; layer_errors=True appends the float64 [T - 1, L] table of error-unit
+        means, the one forward_backward returns."""
         d = self._frames(frames)
         n, T = int(d.shape[0]), int(d.shape[1])
         n_fed = self._fed(n_fed, T)
         out = np.zeros(max(T - 1, 1), np.float64)
+        table = np.zeros((max(T - 1, 1), len(self.channels)), np.float64) if layer_errors else None
         d_pred = self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
-        _check(self.lib.eigen_trainer_evaluate(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n), ctypes.c_int32(T),
-                                               ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))), ctypes.c_int32(int(bool(reset))),
-                                               ctypes.c_void_p(out.ctypes.data), _ptr(d_pred), None))
-        out = out[:T - 1]
-        if pred:
-            return out, d_pred.cpu().numpy()
-        return out
+        _check(self.lib.eigen_trainer_evaluate_err(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n), ctypes.c_int32(T),
+                                                   ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))), ctypes.c_int32(int(bool(reset))),
+                                                   ctypes.c_void_p(out.ctypes.data), _ptr(table), _ptr(d_pred), None))
+        res = (out[:T - 1],) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table[:T - 1],) if layer_errors else ())
+        return res[0] if len(res) == 1 else res
 
     def loss_and_grad(self, frames, reset=True):
         """(loss, {name: gradient}) of frames uint8 [n, T, C, H, W]; overwrites the gradients."""
@@ -256,9 +320,10 @@ class PredNetTrainer:
         """One Adam step on the current gradients."""
         _check(self.lib.eigen_trainer_adam(self._h, self.alpha, self.beta1, self.beta2, self.eps, _stream_arg(stream)))
 
-    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None):
+    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None, objective="mse", layer_weights=None):
         """Gradient and one Adam step; returns the loss before the step."""
-        loss = self.forward_backward(frames, reset, n_fed=n_fed, requant=requant, step_weights=step_weights)
+        loss = self.forward_backward(frames, reset, n_fed=n_fed, requant=requant, step_weights=step_weights, objective=objective,
+                                     layer_weights=layer_weights)
         self.adam()
         return loss
 
@@ -329,4 +394,4 @@ class PredNetTrainer:
         self.close()
 
 
-__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint"]
+__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms"]

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Train PredNet on the MI355X (next-frame MSE, backprop through time, Adam) and use the result in the fitness path.
+"""Train PredNet on the MI355X (next-frame MSE or PredNet's own error-unit objective, backprop through time, Adam) and use the
+result in the fitness path.
 
     python examples/train_prednet.py -o trained.npz [-i frames_dir] [--size 160x120] [-c 3] [--steps 200] [--seq 10] [--batch 8]
+                                     [--loss mse|l0|lall]
                                      [--ext-steps 200 --ext-frames 4 [--requant]] [--checkpoint ckpt.npz [--every 50]] [--resume ckpt.npz]
 
 Input: the PNG files of a folder, in name order, centre-cropped to --size, cut into windows of --seq frames; without -i, seeded
@@ -9,8 +11,10 @@ drifting patterns (rings moving in a different direction per sequence).  The las
 training.  Phase 1 is teacher-forced: every step reads its frame.  --ext-steps adds a second, self-fed fine-tuning phase: the last
 --ext-frames steps of every sequence read the network's own prediction (through the emitted byte with --requant), the regime the
 fitness path scores; its loss weights only the self-fed predictions.  --checkpoint writes weights, Adam state and step counter as
-one npz every --every steps and at the end; --resume continues such a run bit for bit.  Prints the held-out per-step losses
-(tape-free `evaluate`) before and after, writes the weights as a chainer npz (-o), then evaluates one synthetic population's
+one npz every --every steps and at the end; --resume continues such a run bit for bit.  --loss picks the objective of both phases:
+mse, the squared error of the prediction; l0, the mean of the image layer's error units (Lotter's L_0, an L1 next-frame error);
+lall, L_0 plus the error units of the upper layers at weight 0.1 (L_all).  Prints the held-out per-step squared errors and the
+mean error units of every layer (tape-free `evaluate`) before and after, writes the weights as a chainer npz (-o), then evaluates one synthetic population's
 fitness with them.
 """
 import argparse
@@ -58,6 +62,7 @@ def main():
     ap.add_argument("--seq", type=int, default=10, help="frames per sequence")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--alpha", type=float, default=1e-3)
+    ap.add_argument("--loss", default="mse", choices=["mse", "l0", "lall"], help="objective: squared error, or the error units (L_0 / L_all)")
     ap.add_argument("--ext-steps", type=int, default=0, help="Adam steps of a second phase whose last --ext-frames steps are self-fed")
     ap.add_argument("--ext-frames", type=int, default=4, help="self-fed steps at the end of every sequence in the second phase")
     ap.add_argument("--requant", action="store_true", help="feed predictions back through the emitted byte (cfg.requant_feedback)")
@@ -83,6 +88,7 @@ def main():
     ext_w = [0.0] * n_fed + [1.0] * (args.seq - 1 - n_fed)
     total = args.steps + args.ext_steps
     fmt = lambda v: " ".join("%.5f" % x for x in v)
+    obj = {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(channels) - 1))}[args.loss]
 
     with PredNetTrainer(args.model, channels, w, h, args.batch, args.seq, alpha=args.alpha) as tr:
         first = 0
@@ -90,20 +96,22 @@ def main():
             tr.load_checkpoint(args.resume)
             first = tr.state_dict()["adam_t"]
             print("resumed %s at step %d" % (args.resume, first))
-        before = tr.evaluate(held, n_fed=n_fed, requant=args.requant)
+        before, err_before = tr.evaluate(held, n_fed=n_fed, requant=args.requant, layer_errors=True)
         print("held-out loss per step (%d fed, %d self-fed) before: %s" % (n_fed, args.seq - n_fed, fmt(before)))
+        print("held-out error units per layer (mean over the steps; layer 0 is the L_0 error) before: %s" % fmt(err_before.mean(0)))
         for k in range(first, total):
             if k < args.steps:
-                loss = tr.step(batch_of(k))
+                loss = tr.step(batch_of(k), **obj)
             else:
-                loss = tr.step(batch_of(k), n_fed=n_fed, requant=args.requant, step_weights=ext_w if any(ext_w) else None)
+                loss = tr.step(batch_of(k), n_fed=n_fed, requant=args.requant, step_weights=ext_w if any(ext_w) else None, **obj)
             if k % 50 == 0 or k == total - 1 or k == args.steps:
-                print("step %4d  %s train loss %.6f" % (k, "teacher-forced" if k < args.steps else "self-fed      ", loss))
+                print("step %4d  %s train loss (%s) %.6f" % (k, "teacher-forced" if k < args.steps else "self-fed      ", args.loss, loss))
             if args.checkpoint and ((k + 1) % args.every == 0 or k == total - 1):
                 tr.save_checkpoint(args.checkpoint)
-        after = tr.evaluate(held, n_fed=n_fed, requant=args.requant)
+        after, err_after = tr.evaluate(held, n_fed=n_fed, requant=args.requant, layer_errors=True)
         trained = tr.weights()
     print("held-out loss per step after:  %s" % fmt(after))
+    print("held-out error units per layer after:  %s" % fmt(err_after.mean(0)))
     print("held-out loss, mean over the steps: %.6f before, %.6f after (%.1f %% lower)" % (before.mean(), after.mean(), 100 * (1 - after.mean() / before.mean())))
     if n_fed < args.seq - 1:
         b, a = before[n_fed:].sum(), after[n_fed:].sum()

@@ -277,8 +277,8 @@ double eigen_prednet_flops_per_step(const eigen_engine* e);
 
 
 /* ---------------------------------------------------------------------------------------------------- training
- * PredNet training on frame sequences: next-frame MSE, full backprop through time within a call,
- * Adam as chainer defines it.  A separate handle: no inference handle's state or workspaces are touched.  Gradients and
+ * PredNet training on frame sequences: next-frame MSE or, per call, the error-unit objective L_0 / L_all
+ * (eigen_trainer_loss_grad_obj), full backprop through time within a call, Adam as chainer defines it.  A separate handle: no inference handle's state or workspaces are touched.  Gradients and
  * weights are bit-identical from run to run (fixed-order reductions, no float atomics). */
 typedef struct eigen_trainer eigen_trainer;
 
@@ -338,6 +338,39 @@ int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64
  * Errors: as eigen_trainer_loss_grad_ext, without the bound on n_steps. */
 int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
                            int32_t n_fed, int32_t requant, int32_t reset, double* h_step_loss, float* d_pred, void* stream);
+
+/* The training objective of one call (a per-call argument: the handle keeps nothing of it).
+ *   EIGEN_OBJ_MSE: the squared error of eigen_trainer_loss_grad_ext.
+ *   EIGEN_OBJ_ERROR: PredNet's own objective (Lotter et al.), the mean of the error units, weighted per layer. */
+typedef enum { EIGEN_OBJ_MSE = 0, EIGEN_OBJ_ERROR = 1 } eigen_objective;
+
+/* eigen_trainer_loss_grad_ext with a choice of objective and the table of error-unit means.
+ * eigen_trainer_loss_grad_ext is this call with objective = EIGEN_OBJ_MSE, h_layer_w = NULL, h_layer_err = NULL.
+ *   err[s][l], s in [0, n_steps-2] (term s belongs to step s + 1, as mse_s does):
+ *     l = 0: the mean over b, the 2 C_0 error channels, y, x of [relu(x_{s+1} - P0_s), relu(P0_s - x_{s+1})], always against the
+ *       TRUE frame x_{s+1} = (float)byte / 255.0f, on self-fed steps as well; it equals mean |P0_s - x_{s+1}| / 2.
+ *     l > 0: the mean over b, 2 C_l, y, x of E_l of step s + 1, the errors the network itself computed there.
+ *     The errors of the call's first step (the kept P against the first frame) belong to no call.
+ *   objective = EIGEN_OBJ_ERROR: loss = sum_s w_s sum_l lambda_l err[s][l] / sum_s w_s, formed on the host in double in (step,
+ *     layer) order; w = h_step_w (NULL: all one), lambda = h_layer_w.  The gradients are those of this loss (relu'(0) = 0,
+ *     sign(0) = 0).
+ *   objective = EIGEN_OBJ_MSE: the loss and gradients of eigen_trainer_loss_grad_ext to the last bit.
+ *   h_layer_w: host double[n_layers], >= 0, finite, not all zero, or NULL: L_0, [1, 0, ...] (Lotter's L_all is [1, 0.1, ...]).
+ *     Checked whenever it is given; used by EIGEN_OBJ_ERROR only.
+ *   h_layer_err (host, may be NULL): double[(n_steps-1) * n_layers], err[s][l] at s * n_layers + l, under either objective.
+ *     Every entry is reduced in double over fixed slices in a fixed order: the same frames give the same bits from
+ *     eigen_trainer_evaluate_err.
+ * Errors: those of eigen_trainer_loss_grad_ext; EIGEN_ERR_INVALID an unknown objective, a negative / non-finite layer weight or
+ * layer weights that are all zero. */
+int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, void* stream);
+
+/* eigen_trainer_evaluate plus the table err[s][l] of eigen_trainer_loss_grad_obj (h_layer_err, host double[(n_steps-1) *
+ * n_layers], may be NULL), for a sequence of any length.  eigen_trainer_evaluate is this call with h_layer_err = NULL. */
+int eigen_trainer_evaluate_err(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                               int32_t n_fed, int32_t requant, int32_t reset, double* h_step_loss, double* h_layer_err,
+                               float* d_pred, void* stream);
 
 /* Everything a continued run depends on besides the weights.
  *   h_m, h_v: the Adam first and second moments, host tables in eigen_set_prednet_weights order (get: both or neither).

@@ -3,7 +3,10 @@
 (F.conv2d, float32) on the same GPU.  Between the two: a step whose last 5 steps are self-fed (float and requantised feedback) and
 the tape-free evaluate of that call.  Prints one JSON line per side and writes profiles/train_bench.json.
 
-    python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both]
+    python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both] [--objective mse|l0|lall]
+
+--objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
+side is always the squared error.
 """
 import argparse
 import json
@@ -45,21 +48,26 @@ def frames(seed, n, T, c, h, w):
     return out
 
 
-def run_trainer(steps, warmup):
+def objective_args(name):
+    return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
+
+
+def run_trainer(steps, warmup, objective="mse"):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
     d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
     tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T)
+    kw = objective_args(objective)
     for _ in range(warmup):
-        tr.step(d)
+        tr.step(d, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss = tr.step(d)
+        loss = tr.step(d, **kw)
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / steps
-    res = dict(side="trainer", step_ms=ms, sample_steps_per_s=B * T / ms * 1e3, loss=loss, tape_bytes=tr.tape_bytes,
+    res = dict(side="trainer", objective=objective, step_ms=ms, sample_steps_per_s=B * T / ms * 1e3, loss=loss, tape_bytes=tr.tape_bytes,
                tape_bytes_per_sample_step=tr.tape_bytes / (B * T), conv_flops_per_step=3 * conv_flops_per_sample_step(CH, W, H) * B * T)
     tr.close()
     return res
@@ -148,13 +156,14 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
+    ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall"], help="the trainer side's objective")
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
     a = ap.parse_args()
     if a.side == "torch":
         print(json.dumps(run_torch(a.steps, a.warmup)))
         return
-    res = [run_trainer(a.steps, a.warmup)]
+    res = [run_trainer(a.steps, a.warmup, a.objective)]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
