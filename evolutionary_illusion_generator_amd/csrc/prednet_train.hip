@@ -8,7 +8,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "../../include/eigen_engine.h"
@@ -53,10 +52,23 @@ struct LayerParams {
 struct TLayer {
     int C, H, W, Cb, Ca;          // channels, size, channels of the layer below (Cb) and above (Ca, 0 at the top)
     long long HW;
-    // tape: [slot][batch][ch][H][W]; E, gates, ZA, dV have max_steps slots, h, c, P have max_steps + 1 (slot 0 = start state)
+    // tape: [slot][batch][ch][H][W], addressed through the accessors below and nowhere else.  Two slot conventions:
+    //   tape slot s of E [2C], G (gates) [4C], ZA [C at the size of the layer below = 4 C HW; l > 0] and dV [C]: what step s
+    //     wrote; max_steps slots;
+    //   state slot s of h, c and P [C]: slot 0 is the start state, step s reads slot s and writes slot s + 1; max_steps + 1 slots.
     float *E = nullptr, *G = nullptr, *ZA = nullptr, *dV = nullptr, *h = nullptr, *c = nullptr, *P = nullptr;
     // backward work buffers, one batch each
     float *dE = nullptr, *dhP = nullptr, *dhc = nullptr, *dc = nullptr, *dPn = nullptr, *dup = nullptr;
+
+    long long CHW() const { return C * HW; }
+    float* E_at(int slot, int B) const { return E + (long long)slot * B * 2 * CHW(); }
+    float* G_at(int slot, int B) const { return G + (long long)slot * B * 4 * CHW(); }
+    float* ZA_at(int slot, int B) const { return ZA ? ZA + (long long)slot * B * 4 * CHW() : nullptr; }
+    float* dV_at(int slot, int B) const { return dV + (long long)slot * B * CHW(); }
+    float* state_at(int part, int slot, int B) const { return (part == 0 ? h : part == 1 ? c : P) + (long long)slot * B * CHW(); }
+    float* h_at(int slot, int B) const { return state_at(0, slot, B); }
+    float* c_at(int slot, int B) const { return state_at(1, slot, B); }
+    float* P_at(int slot, int B) const { return state_at(2, slot, B); }
 };
 
 }  // namespace
@@ -82,10 +94,12 @@ struct eigen_trainer {
 
 namespace {
 
-// (name -> offset, elements) in the order of weights.tensor_names
-void tensor_table(const eigen_trainer* t, std::vector<std::pair<long long, long long>>& tab)
+using Table = std::vector<std::pair<long long, long long>>;
+
+// (offset, elements) of every tensor in the order of weights.tensor_names
+Table tensor_table(const eigen_trainer* t)
 {
-    tab.clear();
+    Table tab;
     for (int l = 0; l < t->L; ++l) {
         const TLayer& y = t->ly[l];
         const LayerParams& p = t->lp[l];
@@ -104,9 +118,14 @@ void tensor_table(const eigen_trainer* t, std::vector<std::pair<long long, long 
         }
         for (int g = 0; g < 3; ++g) tab.push_back({p.peep + g * C * y.HW, C * y.HW});
     }
+    return tab;
 }
 
 inline unsigned blocks(long long n) { return (unsigned)((n + EW_T - 1) / EW_T); }
+
+// launch of an element-wise kernel over n elements
+template <typename K, typename... A>
+void ew(hipStream_t st, K kernel, long long n, A... a) { hipLaunchKernelGGL(kernel, dim3(blocks(n)), dim3(EW_T), 0, st, a...); }
 
 TSrc src(const float* p, long long nstride, int cin, int up, const float* w, int wmode)
 {
@@ -165,14 +184,376 @@ void wgrad(eigen_trainer* t, hipStream_t st, float* dW, const float* dy, int cou
     else if (MT == 2) launch_wgrad_mt<2>(a, gx, gy, st);
     else launch_wgrad_mt<4>(a, gx, gy, st);
     const long long n = cout * K;
-    hipLaunchKernelGGL(tsum_slabs_kernel, dim3(blocks(n)), dim3(EW_T), 0, st, (const float*)t->slab, (int)ns, n, dW);
+    ew(st, tsum_slabs_kernel, n, (const float*)t->slab, (int)ns, n, dW);
 }
 
 // db [C] = sum over N samples and all pixels of dy [N][C][HW]: BIAS_SLICES fixed slices per channel, added in order
 void bias_grad(eigen_trainer* t, hipStream_t st, float* db, const float* dy, int C, long long HW, int N)
 {
     hipLaunchKernelGGL(tbias_grad_kernel, dim3(C, BIAS_SLICES), dim3(EW_T), 0, st, dy, C, (int)HW, N, t->slab);
-    hipLaunchKernelGGL(tsum_slabs_kernel, dim3(blocks(C)), dim3(EW_T), 0, st, (const float*)t->slab, BIAS_SLICES, (long long)C, db);
+    ew(st, tsum_slabs_kernel, C, (const float*)t->slab, BIAS_SLICES, (long long)C, db);
+}
+
+// shapes of every layer, offsets of its parameters in the flat table, and the split-K slab that holds the largest wgrad
+void plan_layout(eigen_trainer* t)
+{
+    const eigen_trainer_config& cfg = t->cfg;
+    const int L = t->L;
+    long long off = 0, slab = 0;
+    for (int l = 0; l < L; ++l) {
+        TLayer& y = t->ly[l];
+        y.C = cfg.channels[l]; y.H = cfg.height >> l; y.W = cfg.width >> l; y.HW = (long long)y.H * y.W;
+        y.Cb = l > 0 ? cfg.channels[l - 1] : 0;
+        y.Ca = l < L - 1 ? cfg.channels[l + 1] : 0;
+        const long long C = y.C;
+        LayerParams& p = t->lp[l];
+        if (l > 0) { p.aW = off; off += C * 2 * y.Cb * 9; p.ab = off; off += C; slab = std::max(slab, C * 2 * y.Cb * 9); }
+        p.pW = off; off += C * C * 9; p.pb = off; off += C;
+        p.x0 = off; off += 4 * C * 2 * C * 9;
+        if (l < L - 1) { p.x1 = off; off += 4 * C * y.Ca * 9; slab = std::max(slab, 4 * C * y.Ca * 9); }
+        p.hW = off; off += 4 * C * C * 9; p.hb = off; off += 4 * C;
+        p.peep = off; off += 3 * C * y.HW;
+        slab = std::max(slab, std::max(4 * C * 2 * C * 9, BIAS_SLICES * 4 * C));
+    }
+    t->slab_floats = std::max(slab, SLAB_FLOATS);
+    t->n_params = off;
+}
+
+// every device buffer of the handle, parameters and gradients zeroed; after a failure the caller destroys t, which frees what was made
+int allocate(eigen_trainer* t)
+{
+    const long long B = t->cfg.max_batch, T = t->cfg.max_steps, L = t->L, np = t->n_params;
+    std::vector<std::pair<void**, size_t>> want;
+    auto add = [&](void** p, long long bytes) { want.push_back({p, (size_t)bytes}); };
+    auto tape = [&](float** p, long long floats) { add((void**)p, floats * 4); t->tape_bytes += floats * 4; };
+    for (void** p : {(void**)&t->prm, (void**)&t->grd, (void**)&t->mom, (void**)&t->var}) add(p, np * 4);
+    add((void**)&t->slab, t->slab_floats * 4);
+    add((void**)&t->d_part, LOSS_BLOCKS * 8); add((void**)&t->d_loss, 8);
+    add((void**)&t->d_spart, T * STEP_LOSS_BLOCKS * 8); add((void**)&t->d_step, T * 8); add((void**)&t->d_err, T * L * 8);
+    for (int l = 0; l < L; ++l) {
+        TLayer& y = t->ly[l];
+        const long long CHW = y.CHW();
+        tape(&y.E, T * B * 2 * CHW);
+        tape(&y.G, T * B * 4 * CHW);
+        tape(&y.dV, T * B * CHW);
+        if (l > 0) tape(&y.ZA, T * B * 4 * CHW);
+        for (float** p : {&y.h, &y.c, &y.P}) tape(p, (T + 1) * B * CHW);
+        add((void**)&y.dE, B * 2 * CHW * 4);
+        for (float** p : {&y.dhP, &y.dhc, &y.dc, &y.dPn}) add((void**)p, B * CHW * 4);
+        if (l > 0) add((void**)&y.dup, B * 4 * CHW * 4);  // [B][C_l][H_{l-1}][W_{l-1}]
+    }
+    for (auto& w : want) {
+        const hipError_t e = hipMalloc(w.first, w.second);
+        if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%zu): %s", w.second, hipGetErrorString(e));
+        t->allocs.push_back(*w.first);
+    }
+    hipError_t e = hipMemset(t->grd, 0, np * 4);
+    if (e == hipSuccess) e = hipMemset(t->prm, 0, np * 4);
+    return e == hipSuccess ? EIGEN_OK : tfail(EIGEN_ERR_HIP, "hipMemset: %s", hipGetErrorString(e));
+}
+
+// Up to two host tables (eigen_set_prednet_weights order) to or from the flat device arrays d0, d1: h1 / d1 may be null.  The count and every
+// pointer are checked before anything reaches the device.
+int copy_tables(eigen_trainer* t, int32_t n, bool to_device, float* d0, const float* const* h0, float* d1 = nullptr, const float* const* h1 = nullptr)
+{
+    if (!t || !h0) return tfail(EIGEN_ERR_INVALID, "null argument");
+    const Table tab = tensor_table(t);
+    if (n != (int32_t)tab.size()) return tfail(EIGEN_ERR_INVALID, "expected %d weight tensors for %d layers, got %d", (int)tab.size(), t->L, n);
+    for (int i = 0; i < n; ++i) if (!h0[i] || (h1 && !h1[i])) return tfail(EIGEN_ERR_INVALID, "tensor %d is NULL", i);
+    TCHK(hipSetDevice(t->cfg.device));
+    TCHK(hipDeviceSynchronize());
+    for (int k = 0; k < (h1 ? 2 : 1); ++k)
+        for (int i = 0; i < n; ++i) {
+            float *dev = (k ? d1 : d0) + tab[i].first, *host = const_cast<float*>((k ? h1 : h0)[i]);
+            TCHK(to_device ? hipMemcpy(dev, host, tab[i].second * 4, hipMemcpyHostToDevice) : hipMemcpy(host, dev, tab[i].second * 4, hipMemcpyDeviceToHost));
+        }
+    return EIGEN_OK;
+}
+
+// argument rules shared by loss_grad_obj and evaluate_err; max_steps < 0: n_steps is not bounded
+int check_call(const eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant, int32_t reset, int max_steps)
+{
+    if (!t || !d_frames) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    if (batch < 1 || n_steps < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 and n_steps >= 1 required");
+    if (batch > t->cfg.max_batch || (max_steps >= 0 && n_steps > max_steps))
+        return tfail(EIGEN_ERR_CAPACITY, "batch %d / %d steps exceed the trainer's %d / %d", batch, n_steps, t->cfg.max_batch, t->cfg.max_steps);
+    if (reset && n_steps < 2) return tfail(EIGEN_ERR_INVALID, "a reset call needs n_steps >= 2 (one loss term per next frame)");
+    if (n_fed < 0 || n_fed > n_steps) return tfail(EIGEN_ERR_INVALID, "n_fed %d outside [0, n_steps = %d]", n_fed, n_steps);
+    if (n_fed == 0 && reset) return tfail(EIGEN_ERR_INVALID, "n_fed = 0 needs reset = 0: a self-fed step continues a kept prediction");
+    if (requant != 0 && requant != 1) return tfail(EIGEN_ERR_INVALID, "requant must be 0 or 1");
+    if (!reset && t->state_batch != batch)
+        return tfail(EIGEN_ERR_STATE, t->state_batch ? "reset = 0 needs the previous call's batch (%d, got %d)" : "reset = 0 with no previous call (%d, got %d)",
+                     t->state_batch, batch);
+    const long long C0HW = t->ly[0].CHW();
+    if (bstride < (long long)n_steps * C0HW && batch > 1)
+        return tfail(EIGEN_ERR_INVALID, "bstride %lld is smaller than a sequence (%lld bytes)", (long long)bstride, (long long)n_steps * C0HW);
+    return EIGEN_OK;
+}
+
+// the handle's device made current, and the start state into state slot 0: zeros, or the state the previous call left
+int start_state(eigen_trainer* t, hipStream_t st, int B, int reset)
+{
+    TCHK(hipSetDevice(t->cfg.device));
+    for (int l = 0; l < t->L; ++l) {
+        const TLayer& y = t->ly[l];
+        const long long bytes = (long long)B * y.CHW() * 4;
+        for (int part = 0; part < 3; ++part) {
+            if (reset) TCHK(hipMemsetAsync(y.state_at(part, 0, B), 0, bytes, st));
+            else if (t->state_slot != 0) TCHK(hipMemcpyAsync(y.state_at(part, 0, B), y.state_at(part, t->state_slot, B), bytes, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    t->state_batch = t->state_slot = 0;
+    return EIGEN_OK;
+}
+
+// One forward step: reads state slot `in`, writes state slot `out` and tape slot `tp`.  xs: this step's frames (frame of sample b
+// at xs + b * bstride), or nullptr for a self-fed step, whose image layer reads P0 of slot `in` (requant: through the byte).
+// pred (may be null): P0 of this step for sample b at pred + b * pred_bstride.
+void forward_step(eigen_trainer* t, hipStream_t st, int B, int in, int out, int tp, const uint8_t* xs, long long bstride, int requant, float* pred, long long pred_bstride)
+{
+    const int L = t->L;
+    const float* prm = t->prm;
+    for (int l = 0; l < L; ++l) {
+        const TLayer& y = t->ly[l];
+        const long long CHW = y.CHW();
+        float* E = y.E_at(tp, B);
+        const float* Pp = y.P_at(in, B);
+        if (l == 0 && xs) {
+            ew(st, terr_fwd_kernel, B * CHW, xs, (long long)bstride, (const float*)nullptr, Pp, E, y.C, y.H, y.W, B);
+        } else if (l == 0) {
+            ew(st, terr_fed_fwd_kernel, B * CHW, Pp, E, requant, CHW, (long long)B * CHW);
+        } else {
+            const TLayer& yb = t->ly[l - 1];
+            float* ZA = y.ZA_at(tp, B);
+            conv(st, ZA, y.C, yb.H, yb.W, B, prm + t->lp[l].ab, 0, {src(yb.E_at(tp, B), 2 * yb.CHW(), 2 * yb.C, 0, prm + t->lp[l].aW, 0)});
+            ew(st, terr_fwd_kernel, B * CHW, (const uint8_t*)nullptr, 0ll, (const float*)ZA, Pp, E, y.C, y.H, y.W, B);
+        }
+    }
+    for (int l = L - 1; l >= 0; --l) {
+        const TLayer& y = t->ly[l];
+        const LayerParams& p = t->lp[l];
+        const long long CHW = y.CHW();
+        float* G = y.G_at(tp, B);
+        const TSrc se = src(y.E_at(tp, B), 2 * CHW, 2 * y.C, 0, prm + p.x0, 0);
+        const TSrc sh = src(y.h_at(in, B), CHW, y.C, 0, prm + p.hW, 0);
+        if (l < L - 1) {
+            const TLayer& ya = t->ly[l + 1];
+            conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, src(ya.h_at(out, B), ya.CHW(), ya.C, 1, prm + p.x1, 0), sh});
+        } else {
+            conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, sh});
+        }
+        const float* pk = prm + p.peep;
+        ew(st, tlstm_fwd_kernel, B * CHW, G, (const float*)y.c_at(in, B), y.c_at(out, B), y.h_at(out, B), pk, pk + CHW, pk + 2 * CHW, y.C, (int)y.HW, B);
+        float* P = y.P_at(out, B);
+        conv(st, P, y.C, y.H, y.W, B, prm + p.pb, 0, {src(y.h_at(out, B), CHW, y.C, 0, prm + p.pW, 0)});
+        ew(st, tpact_fwd_kernel, B * CHW, P, (long long)B * CHW, l == 0 ? 1 : 0, l == 0 ? pred : (float*)nullptr, CHW, pred_bstride);
+    }
+}
+
+// n per-step means into dst[0], dst[stride], ...  Row r: the sum of `term` over the B samples of `per` floats at p + r * B * per, against the frames at
+// x + r * per (sample b at + b * bstride), over div; STEP_LOSS_BLOCKS fixed slices per row, added in order.  Its three uses, with C0HW = C_0 H W:
+//   TERM_SQ, div B C0HW: the mse of P0 of n consecutive steps against the frames they predict, the numbers eigen_trainer_evaluate returns;
+//   TERM_ABS, div 2 B C0HW, stride L: the image-layer column of the error table err[s][l], the mean of [relu(x - P0), relu(P0 - x)] against the TRUE frame;
+//   TERM_SUM, per 2 C_l H_l W_l, no frames, stride L: a column l > 0 of the table, the mean of E_l over n consecutive tape slots (upper_errors).
+void reduce_steps(decltype(TERM_SQ) term, eigen_trainer* t, hipStream_t st, const float* p, const uint8_t* x, long long bstride, long long per, int n, int B, double div,
+                  double* dst, int stride)
+{
+    static constexpr decltype(&tloss_step_partial_kernel<TERM_SQ>) partial[] = {tloss_step_partial_kernel<TERM_SQ>, tloss_step_partial_kernel<TERM_ABS>,
+                                                                                 tloss_step_partial_kernel<TERM_SUM>};  // [term], in the enum's order
+    hipLaunchKernelGGL(partial[term], dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, p, x, bstride, B, per, t->d_spart);
+    hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, div, dst, stride);
+}
+
+// columns l > 0 of n consecutive rows of the error table, from tape slot `slot` and the row at err on
+void upper_errors(eigen_trainer* t, hipStream_t st, int slot, int n, int B, double* err)
+{
+    for (int l = 1; l < t->L; ++l)
+        reduce_steps(TERM_SUM, t, st, t->ly[l].E_at(slot, B), nullptr, 0ll, 2 * t->ly[l].CHW(), n, B, (double)(B * 2 * t->ly[l].CHW()), err + l, t->L);
+}
+
+// The loss of one loss_grad call: the weights of its terms and the seeds they put into the backward pass.
+struct Objective {
+    bool by_error = false;
+    const double* step_w = nullptr;     // host, T - 1 weights; NULL: all one
+    double sum_w = 0.0;                 // of step_w
+    double lam[EIGEN_MAX_LAYERS] = {};  // layer weights of the error-unit objective
+    int T = 0, B = 0;
+    const TLayer* ly = nullptr;
+    long long n_terms() const { return (long long)(T - 1) * B * ly[0].CHW(); }
+    // squared error: d loss / d P0_s = loss_scale(s) * (P0_s - x_{s+1})
+    float loss_scale(int s) const
+    {
+        if (T < 2) return 0.f;
+        return step_w ? (float)(2.0 * step_w[s] / (sum_w * (double)(B * ly[0].CHW()))) : (float)(2.0 / (double)n_terms());
+    }
+    // error units: d loss / d (one element of E_l of term s) = w_s lambda_l / (sum w * numel(E_l)), formed in double
+    float err_scale(int s, int l) const
+    {
+        const double numel = (double)B * 2.0 * (double)ly[l].CHW();
+        return step_w ? (float)(step_w[s] * lam[l] / (sum_w * numel)) : (float)(lam[l] / ((double)(T - 1) * numel));
+    }
+};
+
+// o from the call's arguments: the objective, the layer weights (NULL is L_0, [1, 0, ...]; checked whenever given), the step weights
+int make_objective(const eigen_trainer* t, int32_t objective, const double* h_layer_w, const double* h_step_w, int T, int B, Objective& o)
+{
+    if (objective != EIGEN_OBJ_MSE && objective != EIGEN_OBJ_ERROR) return tfail(EIGEN_ERR_INVALID, "objective %d is neither EIGEN_OBJ_MSE nor EIGEN_OBJ_ERROR", objective);
+    o.by_error = objective == EIGEN_OBJ_ERROR; o.step_w = h_step_w; o.T = T; o.B = B; o.ly = t->ly;
+    if (h_layer_w || o.by_error) {
+        double sum = 0.0;
+        for (int l = 0; l < t->L; ++l) {
+            o.lam[l] = h_layer_w ? h_layer_w[l] : (l == 0 ? 1.0 : 0.0);
+            if (!(o.lam[l] >= 0.0) || !std::isfinite(o.lam[l])) return tfail(EIGEN_ERR_INVALID, "layer weight %d is %g: weights must be finite and >= 0", l, o.lam[l]);
+            sum += o.lam[l];
+        }
+        if (!(sum > 0.0)) return tfail(EIGEN_ERR_INVALID, "all %d layer weights are zero", t->L);
+    }
+    if (h_step_w) {
+        for (int s = 0; s < T - 1; ++s) {
+            if (!(h_step_w[s] >= 0.0) || !std::isfinite(h_step_w[s])) return tfail(EIGEN_ERR_INVALID, "step weight %d is %g: weights must be finite and >= 0", s, h_step_w[s]);
+            o.sum_w += h_step_w[s];
+        }
+        if (T >= 2 && !(o.sum_w > 0.0)) return tfail(EIGEN_ERR_INVALID, "all %d step weights are zero", T - 1);
+    }
+    return EIGEN_OK;
+}
+
+// The error table (when wanted) into d_err and the squared-error loss into d_loss or d_step.  There are two squared-error reductions on
+// purpose.  Without step weights the loss is ONE sum over all terms in LOSS_BLOCKS slices, scaled on the device: eigen_trainer_loss_grad's
+// arithmetic, kept to the bit.  With step weights it is the per-step means eigen_trainer_evaluate returns, combined on the host in step order
+// (read_loss).  One in place of the other would change the low bits of the returned loss.
+int reduce_losses(eigen_trainer* t, hipStream_t st, const Objective& o, const uint8_t* d_frames, long long bstride, bool want_table)
+{
+    const int T = o.T, B = o.B;
+    const long long C0HW = t->ly[0].CHW();
+    const float* P0 = t->ly[0].P_at(1, B);  // of step 0: term s is P0 of step s against frame s + 1, and E_l of step s + 1
+    if (T < 2) TCHK(hipMemsetAsync(t->d_loss, 0, 8, st));
+    if (want_table) {
+        reduce_steps(TERM_ABS, t, st, P0, d_frames + C0HW, bstride, C0HW, T - 1, B, (double)(B * 2 * C0HW), t->d_err, t->L);
+        upper_errors(t, st, 1, T - 1, B, t->d_err);
+    }
+    if (T < 2 || o.by_error) return EIGEN_OK;  // the error objective's loss is formed from the table, on the host
+    if (o.step_w) {
+        reduce_steps(TERM_SQ, t, st, P0, d_frames + C0HW, bstride, C0HW, T - 1, B, (double)(B * C0HW), t->d_step, 1);
+    } else {
+        hipLaunchKernelGGL(tloss_partial_kernel, dim3(LOSS_BLOCKS), dim3(EW_T), 0, st, (const float*)t->ly[0].P_at(0, B), d_frames, bstride, T - 1, B, C0HW, t->d_part);
+        hipLaunchKernelGGL(tloss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)t->d_part, LOSS_BLOCKS, 1.0 / (double)o.n_terms(), t->d_loss);
+    }
+    return EIGEN_OK;
+}
+
+// One step of backprop through time: the cells bottom up (dP, dh, dc and dZ of step s), then the error units top down.
+void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, const uint8_t* d_frames, long long bstride)
+{
+    const int L = t->L, T = o.T, B = o.B;
+    const float* prm = t->prm;
+    for (int l = 0; l < L; ++l) {
+        const TLayer& y = t->ly[l];
+        const LayerParams& p = t->lp[l];
+        const long long CHW = y.CHW();
+        const float* P = y.P_at(s + 1, B);
+        float* dV = y.dV_at(s, B);
+        const uint8_t* xn = (l == 0 && s < T - 1) ? d_frames + (long long)(s + 1) * CHW : nullptr;
+        const float scale = !xn ? 0.f : o.by_error ? o.err_scale(s, 0) : o.loss_scale(s);
+        // an error-unit term whose seed is zero is left out, not added as +0.0f (which would turn a -0 gradient into +0)
+        if (o.by_error && scale == 0.f) xn = nullptr;
+        if (o.by_error && xn)
+            ew(st, tpact_bwd_kernel<1>, B * CHW, P, (const float*)y.dPn, xn, (long long)bstride, CHW, scale, 1, (long long)B * CHW, dV);
+        else
+            ew(st, tpact_bwd_kernel<0>, B * CHW, P, (const float*)y.dPn, xn, (long long)bstride, CHW, scale, l == 0 ? 1 : 0, (long long)B * CHW, dV);
+        conv(st, y.dhP, y.C, y.H, y.W, B, nullptr, 0, {src(dV, CHW, y.C, 0, prm + p.pW, 1)});
+        float* G = y.G_at(s, B);
+        const float* pk = prm + p.peep;
+        ew(st, tlstm_bwd_kernel, B * CHW, G, (const float*)y.c_at(s, B), (const float*)y.c_at(s + 1, B), (const float*)y.dhP, (const float*)(s < T - 1 ? y.dhc : nullptr),
+           (const float*)(l > 0 ? y.dup : nullptr), y.dc, pk, pk + CHW, pk + 2 * CHW, y.C, y.H, y.W, B);
+        // dZ through the three sources: h of the previous step, E of this step, the upsampled h of the layer above
+        if (s > 0) conv(st, y.dhc, y.C, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.hW, 1)});
+        conv(st, y.dE, 2 * y.C, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x0, 1)});
+        if (l < L - 1) conv(st, t->ly[l + 1].dup, y.Ca, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x1, 1)});
+    }
+    // the error units, top down; layer 0 sends dE_0 into dP0_{s-1} under the mask E_0 > 0 on every step: on a teacher-forced
+    // step the other path ends in the frame, on a self-fed one in the constant fed-back value
+    for (int l = L - 1; l >= 0; --l) {
+        const TLayer& y = t->ly[l];
+        const long long CHW = y.CHW();
+        const float* E = y.E_at(s, B);
+        float* ZA = y.ZA_at(s, B);
+        // E_l of step s belongs to term s - 1 (the errors of a call's first step belong to no call)
+        const float seed = o.by_error && l > 0 && s >= 1 ? o.err_scale(s - 1, l) : 0.f;
+        if (seed != 0.f)
+            ew(st, terr_bwd_kernel<1>, B * CHW, (const float*)y.dE, E, y.dPn, ZA, y.C, y.H, y.W, B, seed);
+        else
+            ew(st, terr_bwd_kernel<0>, B * CHW, (const float*)y.dE, E, y.dPn, ZA, y.C, y.H, y.W, B, 0.f);
+        if (l > 0) {
+            const TLayer& yb = t->ly[l - 1];
+            conv(st, yb.dE, 2 * yb.C, yb.H, yb.W, B, nullptr, 1, {src(ZA, 4 * CHW, y.C, 0, prm + t->lp[l].aW, 1)});
+        }
+    }
+}
+
+// every weight gradient over the tape's T * B samples: dV, the gates and ZA hold the deltas the backward steps left there
+void weight_gradients(eigen_trainer* t, hipStream_t st, int T, int B)
+{
+    const int L = t->L, N = T * B;
+    float* grd = t->grd;
+    for (int l = 0; l < L; ++l) {
+        const TLayer& y = t->ly[l];
+        const LayerParams& p = t->lp[l];
+        const long long CHW = y.CHW();
+        const float *dV = y.dV_at(0, B), *G = y.G_at(0, B);
+        wgrad(t, st, grd + p.pW, dV, y.C, y.H, y.W, N, src(y.h_at(1, B), CHW, y.C, 0, nullptr, 0));
+        bias_grad(t, st, grd + p.pb, dV, y.C, y.HW, N);
+        wgrad(t, st, grd + p.x0, G, 4 * y.C, y.H, y.W, N, src(y.E_at(0, B), 2 * CHW, 2 * y.C, 0, nullptr, 0));
+        wgrad(t, st, grd + p.hW, G, 4 * y.C, y.H, y.W, N, src(y.h_at(0, B), CHW, y.C, 0, nullptr, 0));
+        if (l < L - 1) {
+            const TLayer& ya = t->ly[l + 1];
+            wgrad(t, st, grd + p.x1, G, 4 * y.C, y.H, y.W, N, src(ya.h_at(1, B), ya.CHW(), ya.C, 1, nullptr, 0));
+        }
+        bias_grad(t, st, grd + p.hb, G, 4 * y.C, y.HW, N);
+        ew(st, tpeep_grad_kernel, CHW, G, (const float*)y.c_at(0, B), y.C, (int)y.HW, N, grd + p.peep, grd + p.peep + CHW, grd + p.peep + 2 * CHW);
+        if (l > 0) {
+            const TLayer& yb = t->ly[l - 1];
+            wgrad(t, st, grd + p.aW, y.ZA_at(0, B), y.C, yb.H, yb.W, N, src(yb.E_at(0, B), 2 * yb.CHW(), 2 * yb.C, 0, nullptr, 0));
+            bias_grad(t, st, grd + p.ab, y.ZA_at(0, B), y.C, yb.HW, N);
+        }
+    }
+}
+
+// the table to h_layer_err and the loss to h_loss (either may be NULL); everything combined here is added in double, in order
+int read_loss(eigen_trainer* t, hipStream_t st, const Objective& o, bool want_table, double* h_loss, double* h_layer_err)
+{
+    const int T = o.T, L = t->L;
+    std::vector<double> tab(want_table ? (size_t)(T - 1) * L : 0);
+    if (want_table) {
+        TCHK(hipMemcpyAsync(tab.data(), t->d_err, tab.size() * 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+        if (h_layer_err) memcpy(h_layer_err, tab.data(), tab.size() * 8);
+    }
+    if (!h_loss) return EIGEN_OK;
+    if (o.by_error && T >= 2) {
+        // sum_s w_s sum_l lambda_l err[s][l] / sum_s w_s, in (step, layer) order (train.combine_terms states the same sums)
+        double acc = 0.0, tot = 0.0;
+        for (int s = 0; s < T - 1; ++s) {
+            double row = 0.0;
+            for (int l = 0; l < L; ++l) row += o.lam[l] * tab[(size_t)s * L + l];
+            const double w = o.step_w ? o.step_w[s] : 1.0;
+            acc += w * row;
+            tot += w;
+        }
+        *h_loss = acc / tot;
+    } else if (o.step_w && T >= 2) {
+        std::vector<double> sl(T - 1);
+        TCHK(hipMemcpyAsync(sl.data(), t->d_step, (T - 1) * 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+        double acc = 0.0;
+        for (int s = 0; s < T - 1; ++s) acc += o.step_w[s] * sl[s];
+        *h_loss = acc / o.sum_w;
+    } else {
+        TCHK(hipMemcpyAsync(h_loss, t->d_loss, 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+    }
+    return EIGEN_OK;
 }
 
 }  // namespace
@@ -204,97 +585,22 @@ int eigen_trainer_create(const eigen_trainer_config* cfg, eigen_trainer** out)
     TCHK(hipGetDeviceProperties(&prop, cfg->device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return tfail(EIGEN_ERR_INVALID, "device %d is %s; this library is built for gfx950 (MI355X) only", cfg->device, prop.gcnArchName);
-
     eigen_trainer* t = new eigen_trainer();
     t->cfg = *cfg;
     t->L = L;
-    const long long B = cfg->max_batch, T = cfg->max_steps;
-    long long off = 0, slab = 0;
-    for (int l = 0; l < L; ++l) {
-        TLayer& y = t->ly[l];
-        y.C = cfg->channels[l]; y.H = cfg->height >> l; y.W = cfg->width >> l; y.HW = (long long)y.H * y.W;
-        y.Cb = l > 0 ? cfg->channels[l - 1] : 0;
-        y.Ca = l < L - 1 ? cfg->channels[l + 1] : 0;
-        const long long C = y.C;
-        LayerParams& p = t->lp[l];
-        if (l > 0) { p.aW = off; off += C * 2 * y.Cb * 9; p.ab = off; off += C; slab = std::max(slab, C * 2 * y.Cb * 9); }
-        p.pW = off; off += C * C * 9; p.pb = off; off += C;
-        p.x0 = off; off += 4 * C * 2 * C * 9;
-        if (l < L - 1) { p.x1 = off; off += 4 * C * y.Ca * 9; slab = std::max(slab, 4 * C * y.Ca * 9); }
-        p.hW = off; off += 4 * C * C * 9;
-        p.hb = off; off += 4 * C;
-        p.peep = off; off += 3 * C * y.HW;
-        slab = std::max(slab, std::max(4 * C * 2 * C * 9, BIAS_SLICES * 4 * C));
-    }
-    t->slab_floats = std::max(slab, SLAB_FLOATS);
-    t->n_params = off;
-    std::vector<std::pair<void**, size_t>> want;
-    auto add = [&](void** p, long long bytes) { want.push_back({p, (size_t)bytes}); };
-    auto tape = [&](float** p, long long floats) { add((void**)p, floats * 4); t->tape_bytes += floats * 4; };
-    for (void** p : {(void**)&t->prm, (void**)&t->grd, (void**)&t->mom, (void**)&t->var}) add(p, off * 4);
-    add((void**)&t->slab, t->slab_floats * 4);
-    add((void**)&t->d_part, LOSS_BLOCKS * 8);
-    add((void**)&t->d_loss, 8);
-    add((void**)&t->d_spart, T * STEP_LOSS_BLOCKS * 8);
-    add((void**)&t->d_step, T * 8);
-    add((void**)&t->d_err, T * L * 8);
-    for (int l = 0; l < L; ++l) {
-        TLayer& y = t->ly[l];
-        const long long CHW = y.C * y.HW;
-        tape(&y.E, T * B * 2 * CHW);
-        tape(&y.G, T * B * 4 * CHW);
-        tape(&y.dV, T * B * CHW);
-        if (l > 0) tape(&y.ZA, T * B * 4 * CHW);
-        tape(&y.h, (T + 1) * B * CHW);
-        tape(&y.c, (T + 1) * B * CHW);
-        tape(&y.P, (T + 1) * B * CHW);
-        add((void**)&y.dE, B * 2 * CHW * 4);
-        add((void**)&y.dhP, B * CHW * 4);
-        add((void**)&y.dhc, B * CHW * 4);
-        add((void**)&y.dc, B * CHW * 4);
-        add((void**)&y.dPn, B * CHW * 4);
-        if (l > 0) add((void**)&y.dup, B * 4 * CHW * 4);  // [B][C_l][H_{l-1}][W_{l-1}]
-    }
-    for (auto& w : want) {
-        hipError_t e = hipMalloc(w.first, w.second);
-        if (e != hipSuccess) {
-            eigen_trainer_destroy(t);
-            return tfail(EIGEN_ERR_HIP, "hipMalloc(%zu): %s", w.second, hipGetErrorString(e));
-        }
-        t->allocs.push_back(*w.first);
-    }
-    hipError_t e = hipMemset(t->grd, 0, off * 4);
-    if (e == hipSuccess) e = hipMemset(t->prm, 0, off * 4);
-    if (e != hipSuccess) {
-        eigen_trainer_destroy(t);
-        return tfail(EIGEN_ERR_HIP, "hipMemset: %s", hipGetErrorString(e));
-    }
-    *out = t;
-    return EIGEN_OK;
+    plan_layout(t);
+    const int rc = allocate(t);
+    if (rc) eigen_trainer_destroy(t);
+    else *out = t;
+    return rc;
 }
 
 int64_t eigen_trainer_tape_bytes(const eigen_trainer* t) { return t ? t->tape_bytes : 0; }
 
-static int copy_tables(eigen_trainer* t, float* dev, const float* const* h_in, float* const* h_out, int32_t n)
-{
-    if (!t || (!h_in && !h_out)) return tfail(EIGEN_ERR_INVALID, "null argument");
-    std::vector<std::pair<long long, long long>> tab;
-    tensor_table(t, tab);
-    if (n != (int32_t)tab.size()) return tfail(EIGEN_ERR_INVALID, "expected %d weight tensors for %d layers, got %d", (int)tab.size(), t->L, n);
-    TCHK(hipSetDevice(t->cfg.device));
-    TCHK(hipDeviceSynchronize());
-    for (int i = 0; i < n; ++i) {
-        if (h_in ? !h_in[i] : !h_out[i]) return tfail(EIGEN_ERR_INVALID, "tensor %d is NULL", i);
-        if (h_in) TCHK(hipMemcpy(dev + tab[i].first, h_in[i], tab[i].second * 4, hipMemcpyHostToDevice));
-        else TCHK(hipMemcpy(h_out[i], dev + tab[i].first, tab[i].second * 4, hipMemcpyDeviceToHost));
-    }
-    return EIGEN_OK;
-}
-
 int eigen_trainer_set_weights(eigen_trainer* t, const float* const* h_tensors, int32_t n_tensors)
 {
     if (!t || !h_tensors) return tfail(EIGEN_ERR_INVALID, "null argument");
-    int rc = copy_tables(t, t->prm, h_tensors, nullptr, n_tensors);
+    int rc = copy_tables(t, n_tensors, true, t->prm, h_tensors);
     if (rc) return rc;
     TCHK(hipMemset(t->mom, 0, t->n_params * 4));
     TCHK(hipMemset(t->var, 0, t->n_params * 4));
@@ -309,143 +615,12 @@ int eigen_trainer_get_weights(eigen_trainer* t, float* const* h_tensors, int32_t
 {
     if (!t || !h_tensors) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
-    return copy_tables(t, t->prm, nullptr, h_tensors, n_tensors);
+    return copy_tables(t, n_tensors, false, t->prm, h_tensors);
 }
 
 int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n_tensors)
 {
-    if (!t || !h_tensors) return tfail(EIGEN_ERR_INVALID, "null argument");
-    return copy_tables(t, t->grd, nullptr, h_tensors, n_tensors);
-}
-
-// argument rules shared by loss_grad_ext and evaluate; max_steps < 0: n_steps is not bounded
-static int check_call(const eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
-                      int32_t requant, int32_t reset, int max_steps)
-{
-    if (!t || !d_frames) return tfail(EIGEN_ERR_INVALID, "null argument");
-    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
-    if (batch < 1 || n_steps < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 and n_steps >= 1 required");
-    if (batch > t->cfg.max_batch || (max_steps >= 0 && n_steps > max_steps))
-        return tfail(EIGEN_ERR_CAPACITY, "batch %d / %d steps exceed the trainer's %d / %d", batch, n_steps, t->cfg.max_batch, t->cfg.max_steps);
-    if (reset && n_steps < 2) return tfail(EIGEN_ERR_INVALID, "a reset call needs n_steps >= 2 (one loss term per next frame)");
-    if (n_fed < 0 || n_fed > n_steps) return tfail(EIGEN_ERR_INVALID, "n_fed %d outside [0, n_steps = %d]", n_fed, n_steps);
-    if (n_fed == 0 && reset) return tfail(EIGEN_ERR_INVALID, "n_fed = 0 needs reset = 0: a self-fed step continues a kept prediction");
-    if (requant != 0 && requant != 1) return tfail(EIGEN_ERR_INVALID, "requant must be 0 or 1");
-    if (!reset && t->state_batch != batch)
-        return tfail(EIGEN_ERR_STATE, t->state_batch ? "reset = 0 needs the previous call's batch (%d, got %d)" : "reset = 0 with no previous call (%d, got %d)",
-                     t->state_batch, batch);
-    const long long C0HW = t->ly[0].C * t->ly[0].HW;
-    if (bstride < (long long)n_steps * C0HW && batch > 1)
-        return tfail(EIGEN_ERR_INVALID, "bstride %lld is smaller than a sequence (%lld bytes)", (long long)bstride, (long long)n_steps * C0HW);
-    return EIGEN_OK;
-}
-
-// start state into slot 0 of h, c, P: zeros, or the state the previous call left
-static int start_state(eigen_trainer* t, hipStream_t st, int B, int reset)
-{
-    for (int l = 0; l < t->L; ++l) {
-        TLayer& y = t->ly[l];
-        const long long n = (long long)B * y.C * y.HW;
-        for (float* a : {y.h, y.c, y.P}) {
-            if (reset) TCHK(hipMemsetAsync(a, 0, n * 4, st));
-            else if (t->state_slot != 0) TCHK(hipMemcpyAsync(a, a + t->state_slot * n, n * 4, hipMemcpyDeviceToDevice, st));
-        }
-    }
-    t->state_batch = 0;
-    t->state_slot = 0;
-    return EIGEN_OK;
-}
-
-// One forward step: reads (h, c, P) of slot `in`, writes slot `out`, and E, gates and ZA of tape slot `tp`.  xs: this step's
-// frames (frame of sample b at xs + b * bstride), or nullptr for a self-fed step, whose image layer reads P0 of slot `in`
-// (requant: through the byte).  pred (may be null): P0 of this step for sample b at pred + b * pred_bstride.
-static void forward_step(eigen_trainer* t, hipStream_t st, int B, int in, int out, int tp, const uint8_t* xs, long long bstride, int requant,
-                         float* pred, long long pred_bstride)
-{
-    const int L = t->L;
-    const float* prm = t->prm;
-    for (int l = 0; l < L; ++l) {
-        TLayer& y = t->ly[l];
-        const long long CHW = y.C * y.HW;
-        float* E = y.E + (long long)tp * B * 2 * CHW;
-        const float* Pp = y.P + (long long)in * B * CHW;
-        if (l == 0 && xs) {
-            hipLaunchKernelGGL(terr_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, xs, (long long)bstride, (const float*)nullptr, Pp, E, y.C, y.H, y.W, B);
-        } else if (l == 0) {
-            hipLaunchKernelGGL(terr_fed_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, Pp, E, requant, CHW, (long long)B * CHW);
-        } else {
-            TLayer& yb = t->ly[l - 1];
-            float* ZA = y.ZA + (long long)tp * B * 4 * CHW;
-            conv(st, ZA, y.C, yb.H, yb.W, B, prm + t->lp[l].ab, 0,
-                 {src(yb.E + (long long)tp * B * 2 * yb.C * yb.HW, 2 * yb.C * yb.HW, 2 * yb.C, 0, prm + t->lp[l].aW, 0)});
-            hipLaunchKernelGGL(terr_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const uint8_t*)nullptr, 0ll, (const float*)ZA, Pp, E, y.C, y.H, y.W, B);
-        }
-    }
-    for (int l = L - 1; l >= 0; --l) {
-        TLayer& y = t->ly[l];
-        const LayerParams& p = t->lp[l];
-        const long long CHW = y.C * y.HW;
-        float* G = y.G + (long long)tp * B * 4 * CHW;
-        const TSrc se = src(y.E + (long long)tp * B * 2 * CHW, 2 * CHW, 2 * y.C, 0, prm + p.x0, 0);
-        const TSrc sh = src(y.h + (long long)in * B * CHW, CHW, y.C, 0, prm + p.hW, 0);
-        if (l < L - 1) {
-            const TLayer& ya = t->ly[l + 1];
-            const TSrc su = src(ya.h + (long long)out * B * ya.C * ya.HW, ya.C * ya.HW, ya.C, 1, prm + p.x1, 0);
-            conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, su, sh});
-        } else {
-            conv(st, G, 4 * y.C, y.H, y.W, B, prm + p.hb, 0, {se, sh});
-        }
-        const float* pk = prm + p.peep;
-        hipLaunchKernelGGL(tlstm_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, G, (const float*)(y.c + (long long)in * B * CHW),
-                           y.c + (long long)out * B * CHW, y.h + (long long)out * B * CHW, pk, pk + CHW, pk + 2 * CHW, y.C, (int)y.HW, B);
-        float* P = y.P + (long long)out * B * CHW;
-        conv(st, P, y.C, y.H, y.W, B, prm + p.pb, 0, {src(y.h + (long long)out * B * CHW, CHW, y.C, 0, prm + p.pW, 0)});
-        hipLaunchKernelGGL(tpact_fwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (long long)B * CHW, l == 0 ? 1 : 0, l == 0 ? pred : (float*)nullptr, CHW,
-                           pred_bstride);
-    }
-}
-
-// mse of n consecutive steps into step_loss[0 .. n): P0 of the first step against the frame x0 it predicts
-static void step_losses(eigen_trainer* t, hipStream_t st, const float* P0, const uint8_t* x0, long long bstride, int n, int B, double* step_loss)
-{
-    const long long C0HW = t->ly[0].C * t->ly[0].HW;
-    hipLaunchKernelGGL(tloss_step_partial_kernel<TERM_SQ>, dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, P0, x0, bstride, B, C0HW, t->d_spart);
-    hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, (double)(B * C0HW), step_loss, 1);
-}
-
-// image-layer column of n consecutive rows of the error table: row r is P0 of step r against the TRUE frame it predicts,
-// mean of [relu(x - P0), relu(P0 - x)] over b and the 2 C_0 error channels; err points at the first row's entry (row stride L)
-static void image_errors(eigen_trainer* t, hipStream_t st, const float* P0, const uint8_t* x0, long long bstride, int n, int B, double* err)
-{
-    const long long C0HW = t->ly[0].C * t->ly[0].HW;
-    hipLaunchKernelGGL(tloss_step_partial_kernel<TERM_ABS>, dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, P0, x0, bstride, B, C0HW, t->d_spart);
-    hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, (double)(B * 2 * C0HW), err, t->L);
-}
-
-// columns l > 0 of n consecutive rows of the error table: the mean of E_l over n consecutive tape slots from `slot` on; err
-// points at the first row (entry of layer 0)
-static void upper_errors(eigen_trainer* t, hipStream_t st, int slot, int n, int B, double* err)
-{
-    for (int l = 1; l < t->L; ++l) {
-        const TLayer& y = t->ly[l];
-        const long long ECHW = 2 * y.C * y.HW;
-        hipLaunchKernelGGL(tloss_step_partial_kernel<TERM_SUM>, dim3(STEP_LOSS_BLOCKS, n), dim3(EW_T), 0, st, (const float*)(y.E + (long long)slot * B * ECHW),
-                           (const uint8_t*)nullptr, 0ll, B, ECHW, t->d_spart);
-        hipLaunchKernelGGL(tloss_step_final_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const double*)t->d_spart, STEP_LOSS_BLOCKS, n, (double)(B * ECHW), err + l, t->L);
-    }
-}
-
-// layer weights of the error-unit objective into lam[L]: NULL is L_0, [1, 0, ...]
-static int layer_weights(const eigen_trainer* t, const double* h_layer_w, double* lam)
-{
-    double sum = 0.0;
-    for (int l = 0; l < t->L; ++l) {
-        lam[l] = h_layer_w ? h_layer_w[l] : (l == 0 ? 1.0 : 0.0);
-        if (!(lam[l] >= 0.0) || !std::isfinite(lam[l])) return tfail(EIGEN_ERR_INVALID, "layer weight %d is %g: weights must be finite and >= 0", l, lam[l]);
-        sum += lam[l];
-    }
-    if (!(sum > 0.0)) return tfail(EIGEN_ERR_INVALID, "all %d layer weights are zero", t->L);
-    return EIGEN_OK;
+    return copy_tables(t, n_tensors, false, t->grd, h_tensors);
 }
 
 int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
@@ -454,182 +629,29 @@ int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64
 {
     int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, t ? t->cfg.max_steps : 0);
     if (rc) return rc;
-    if (objective != EIGEN_OBJ_MSE && objective != EIGEN_OBJ_ERROR) return tfail(EIGEN_ERR_INVALID, "objective %d is neither EIGEN_OBJ_MSE nor EIGEN_OBJ_ERROR", objective);
-    double lam[EIGEN_MAX_LAYERS];
-    if (h_layer_w || objective == EIGEN_OBJ_ERROR) {
-        rc = layer_weights(t, h_layer_w, lam);
-        if (rc) return rc;
-    }
-    const bool by_error = objective == EIGEN_OBJ_ERROR;
-    const int L = t->L, T = n_steps, B = batch;
-    const long long C0HW = t->ly[0].C * t->ly[0].HW;
-    double sum_w = 0.0;
-    if (h_step_w) {
-        for (int s = 0; s < T - 1; ++s) {
-            if (!(h_step_w[s] >= 0.0) || !std::isfinite(h_step_w[s])) return tfail(EIGEN_ERR_INVALID, "step weight %d is %g: weights must be finite and >= 0", s, h_step_w[s]);
-            sum_w += h_step_w[s];
-        }
-        if (T >= 2 && !(sum_w > 0.0)) return tfail(EIGEN_ERR_INVALID, "all %d step weights are zero", T - 1);
-    }
-    TCHK(hipSetDevice(t->cfg.device));
+    const int T = n_steps, B = batch;
+    const long long C0HW = t->ly[0].CHW();
+    Objective o;
+    rc = make_objective(t, objective, h_layer_w, h_step_w, T, B, o);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const float* prm = t->prm;
-    float* grd = t->grd;
-
     rc = start_state(t, st, B, reset);
     if (rc) return rc;
-
-    // ---- forward with tape: step s reads slot s of h, c, P and writes slot s + 1
+    // forward with tape: step s reads state slot s, writes state slot s + 1 and tape slot s
     for (int s = 0; s < T; ++s)
-        forward_step(t, st, B, s, s + 1, s, s < n_fed ? d_frames + (long long)s * C0HW : nullptr, bstride, requant,
-                     d_pred ? d_pred + (long long)s * C0HW : nullptr, (long long)T * C0HW);
-
-    // ---- loss.  Without weights: one sum over all terms; with weights: one mse per step, combined on the host in step order
-    const long long n_terms = (long long)(T - 1) * B * C0HW;
-    const bool want_table = T >= 2 && (h_layer_err || (by_error && h_loss));
-    if (want_table) {
-        // row s: P0 of step s (slot s + 1) against frame s + 1, and E_l of step s + 1 (tape slot s + 1)
-        image_errors(t, st, t->ly[0].P + (long long)B * C0HW, d_frames + C0HW, bstride, T - 1, B, t->d_err);
-        upper_errors(t, st, 1, T - 1, B, t->d_err);
-    }
-    if (by_error) {
-        if (T < 2) TCHK(hipMemsetAsync(t->d_loss, 0, 8, st));
-    } else if (T >= 2 && !h_step_w) {
-        hipLaunchKernelGGL(tloss_partial_kernel, dim3(LOSS_BLOCKS), dim3(EW_T), 0, st, (const float*)t->ly[0].P, d_frames, (long long)bstride, T - 1, B, C0HW, t->d_part);
-        hipLaunchKernelGGL(tloss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)t->d_part, LOSS_BLOCKS, 1.0 / (double)n_terms, t->d_loss);
-    } else if (T >= 2) {
-        step_losses(t, st, t->ly[0].P + (long long)B * C0HW, d_frames + C0HW, bstride, T - 1, B, t->d_step);
-    } else {
-        TCHK(hipMemsetAsync(t->d_loss, 0, 8, st));
-    }
-    // d loss / d P0_s = loss_scale(s) * (P0_s - x_{s+1})
-    auto loss_scale = [&](int s) -> float {
-        if (T < 2) return 0.f;
-        if (!h_step_w) return (float)(2.0 / (double)n_terms);
-        return (float)(2.0 * h_step_w[s] / (sum_w * (double)(B * C0HW)));
-    };
-    // error-unit objective: d loss / d (one element of E_l of term s) = w_s lambda_l / (sum w * numel(E_l)), formed in double
-    auto err_scale = [&](int s, int l) -> float {
-        const double numel = (double)B * 2.0 * (double)(t->ly[l].C * t->ly[l].HW);
-        if (!h_step_w) return (float)(lam[l] / ((double)(T - 1) * numel));
-        return (float)(h_step_w[s] * lam[l] / (sum_w * numel));
-    };
-
-    // ---- backward through time
-    for (int l = 0; l < L; ++l) {
-        TLayer& y = t->ly[l];
-        const long long n = (long long)B * y.C * y.HW;
-        TCHK(hipMemsetAsync(y.dPn, 0, n * 4, st));
-        TCHK(hipMemsetAsync(y.dhc, 0, n * 4, st));
-        TCHK(hipMemsetAsync(y.dc, 0, n * 4, st));
-    }
-    for (int s = T - 1; s >= 0; --s) {
-        for (int l = 0; l < L; ++l) {
-            TLayer& y = t->ly[l];
-            const LayerParams& p = t->lp[l];
-            const long long CHW = y.C * y.HW;
-            const float* P = y.P + (long long)(s + 1) * B * CHW;
-            float* dV = y.dV + (long long)s * B * CHW;
-            const uint8_t* xn = (l == 0 && s < T - 1) ? d_frames + (long long)(s + 1) * C0HW : nullptr;
-            const float scale = !xn ? 0.f : by_error ? err_scale(s, 0) : loss_scale(s);
-            // an error-unit term whose seed is zero is left out, not added as +0.0f (which would turn a -0 gradient into +0)
-            if (by_error && scale == 0.f) xn = nullptr;
-            if (by_error && xn)
-                hipLaunchKernelGGL(tpact_bwd_kernel<1>, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (const float*)y.dPn, xn, (long long)bstride, CHW, scale, 1,
-                                   (long long)B * CHW, dV);
-            else
-                hipLaunchKernelGGL(tpact_bwd_kernel<0>, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, P, (const float*)y.dPn, xn, (long long)bstride, CHW, scale,
-                                   l == 0 ? 1 : 0, (long long)B * CHW, dV);
-            conv(st, y.dhP, y.C, y.H, y.W, B, nullptr, 0, {src(dV, CHW, y.C, 0, prm + p.pW, 1)});
-            float* G = y.G + (long long)s * B * 4 * CHW;
-            const float* pk = prm + p.peep;
-            hipLaunchKernelGGL(tlstm_bwd_kernel, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, G, (const float*)(y.c + (long long)s * B * CHW),
-                               (const float*)(y.c + (long long)(s + 1) * B * CHW), (const float*)y.dhP, (const float*)(s < T - 1 ? y.dhc : nullptr),
-                               (const float*)(l > 0 ? y.dup : nullptr), y.dc, pk, pk + CHW, pk + 2 * CHW, y.C, y.H, y.W, B);
-            // dZ through the three sources: h of the previous step, E of this step, the upsampled h of the layer above
-            if (s > 0) conv(st, y.dhc, y.C, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.hW, 1)});
-            conv(st, y.dE, 2 * y.C, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x0, 1)});
-            if (l < L - 1) conv(st, t->ly[l + 1].dup, y.Ca, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x1, 1)});
-        }
-        // the error units, top down; layer 0 sends dE_0 into dP0_{s-1} under the mask E_0 > 0 on every step: on a teacher-forced
-        // step the other path ends in the frame, on a self-fed one in the constant fed-back value
-        for (int l = L - 1; l >= 0; --l) {
-            TLayer& y = t->ly[l];
-            const long long CHW = y.C * y.HW;
-            const float* E = y.E + (long long)s * B * 2 * CHW;
-            float* ZA = l > 0 ? y.ZA + (long long)s * B * 4 * CHW : nullptr;
-            // E_l of step s belongs to term s - 1 (the errors of a call's first step belong to no call)
-            const float seed = by_error && l > 0 && s >= 1 ? err_scale(s - 1, l) : 0.f;
-            if (seed != 0.f)
-                hipLaunchKernelGGL(terr_bwd_kernel<1>, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const float*)y.dE, E, y.dPn, ZA, y.C, y.H, y.W, B, seed);
-            else
-                hipLaunchKernelGGL(terr_bwd_kernel<0>, dim3(blocks(B * CHW)), dim3(EW_T), 0, st, (const float*)y.dE, E, y.dPn, ZA, y.C, y.H, y.W, B, 0.f);
-            if (l > 0) {
-                TLayer& yb = t->ly[l - 1];
-                conv(st, yb.dE, 2 * yb.C, yb.H, yb.W, B, nullptr, 1, {src(ZA, 4 * CHW, y.C, 0, prm + t->lp[l].aW, 1)});
-            }
-        }
-    }
-
-    // ---- weight gradients over all T * B samples
-    const int N = T * B;
-    for (int l = 0; l < L; ++l) {
-        TLayer& y = t->ly[l];
-        const LayerParams& p = t->lp[l];
-        const long long CHW = y.C * y.HW;
-        wgrad(t, st, grd + p.pW, y.dV, y.C, y.H, y.W, N, src(y.h + (long long)B * CHW, CHW, y.C, 0, nullptr, 0));
-        bias_grad(t, st, grd + p.pb, y.dV, y.C, y.HW, N);
-        wgrad(t, st, grd + p.x0, y.G, 4 * y.C, y.H, y.W, N, src(y.E, 2 * CHW, 2 * y.C, 0, nullptr, 0));
-        wgrad(t, st, grd + p.hW, y.G, 4 * y.C, y.H, y.W, N, src(y.h, CHW, y.C, 0, nullptr, 0));
-        if (l < L - 1) {
-            const TLayer& ya = t->ly[l + 1];
-            wgrad(t, st, grd + p.x1, y.G, 4 * y.C, y.H, y.W, N, src(ya.h + (long long)B * ya.C * ya.HW, ya.C * ya.HW, ya.C, 1, nullptr, 0));
-        }
-        bias_grad(t, st, grd + p.hb, y.G, 4 * y.C, y.HW, N);
-        hipLaunchKernelGGL(tpeep_grad_kernel, dim3(blocks(CHW)), dim3(EW_T), 0, st, (const float*)y.G, (const float*)y.c, y.C, (int)y.HW, N,
-                           grd + p.peep, grd + p.peep + CHW, grd + p.peep + 2 * CHW);
-        if (l > 0) {
-            const TLayer& yb = t->ly[l - 1];
-            wgrad(t, st, grd + p.aW, y.ZA, y.C, yb.H, yb.W, N, src(yb.E, 2 * yb.C * yb.HW, 2 * yb.C, 0, nullptr, 0));
-            bias_grad(t, st, grd + p.ab, y.ZA, y.C, yb.HW, N);
-        }
-    }
+        forward_step(t, st, B, s, s + 1, s, s < n_fed ? d_frames + s * C0HW : nullptr, bstride, requant, d_pred ? d_pred + s * C0HW : nullptr, T * C0HW);
+    const bool want_table = T >= 2 && (h_layer_err || (o.by_error && h_loss));
+    rc = reduce_losses(t, st, o, d_frames, bstride, want_table);
+    if (rc) return rc;
+    // backward through time, from zero carries
+    for (int l = 0; l < t->L; ++l)
+        for (float* a : {t->ly[l].dPn, t->ly[l].dhc, t->ly[l].dc}) TCHK(hipMemsetAsync(a, 0, B * t->ly[l].CHW() * 4, st));
+    for (int s = T - 1; s >= 0; --s) backward_step(t, st, o, s, d_frames, bstride);
+    weight_gradients(t, st, T, B);
     TCHK(hipGetLastError());
     t->state_batch = B;
     t->state_slot = T;
-    std::vector<double> tab;
-    if (want_table) {
-        tab.resize((size_t)(T - 1) * L);
-        TCHK(hipMemcpyAsync(tab.data(), t->d_err, tab.size() * 8, hipMemcpyDeviceToHost, st));
-        TCHK(hipStreamSynchronize(st));
-        if (h_layer_err) memcpy(h_layer_err, tab.data(), tab.size() * 8);
-    }
-    if (h_loss && by_error && T >= 2) {
-        // sum_s w_s sum_l lambda_l err[s][l] / sum_s w_s, in (step, layer) order (train.combine_terms states the same sums)
-        double acc = 0.0, tot = 0.0;
-        for (int s = 0; s < T - 1; ++s) {
-            double row = 0.0;
-            for (int l = 0; l < L; ++l) row += lam[l] * tab[(size_t)s * L + l];
-            const double w = h_step_w ? h_step_w[s] : 1.0;
-            acc += w * row;
-            tot += w;
-        }
-        *h_loss = acc / tot;
-    } else if (h_loss && h_step_w && T >= 2) {
-        std::vector<double> sl(T - 1);
-        TCHK(hipMemcpyAsync(sl.data(), t->d_step, (T - 1) * 8, hipMemcpyDeviceToHost, st));
-        TCHK(hipStreamSynchronize(st));
-        double acc = 0.0;
-        for (int s = 0; s < T - 1; ++s) {
-            const double term = h_step_w[s] * sl[s];
-            acc += term;
-        }
-        *h_loss = acc / sum_w;
-    } else if (h_loss) {
-        TCHK(hipMemcpyAsync(h_loss, t->d_loss, 8, hipMemcpyDeviceToHost, st));
-        TCHK(hipStreamSynchronize(st));
-    }
-    return EIGEN_OK;
+    return read_loss(t, st, o, want_table, h_loss, h_layer_err);
 }
 
 int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
@@ -650,36 +672,30 @@ int eigen_trainer_evaluate_err(eigen_trainer* t, const uint8_t* d_frames, int64_
     int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, -1);
     if (rc) return rc;
     const int T = n_steps, B = batch, M = t->cfg.max_steps, L = t->L;
-    const long long C0HW = t->ly[0].C * t->ly[0].HW;
-    TCHK(hipSetDevice(t->cfg.device));
+    const long long C0HW = t->ly[0].CHW();
     hipStream_t st = (hipStream_t)stream;
     rc = start_state(t, st, B, reset);
     if (rc) return rc;
-    // slots 0 and 1 of h, c, P in turn, slot 0 of E, gates and ZA; the loss of step s goes to d_step[s % max_steps], read back
-    // whenever that table is full.  Row r of the error table lives at d_err[r % max_steps]: its image-layer entry is reduced after
-    // step r, its upper entries (E_l of step r + 1) after step r + 1, and the rows are read back once the table's last row, or the
-    // call's, is complete -- ahead of the image-layer entry that reuses row 0.
+    // state slots 0 and 1 in turn, tape slot 0; the loss of step s goes to d_step[s % max_steps], read back whenever that table is
+    // full.  Row r of the error table lives at d_err[r % max_steps]: its image-layer entry is reduced after step r, its upper entries
+    // (E_l of step r + 1) after step r + 1, and the rows are read back once the table's last row, or the call's, is complete --
+    // ahead of the image-layer entry that reuses row 0.
+    auto flush = [&](double* host, const double* dev, int r, int width) {  // rows r - r % M .. r, once r is the table's last row or the call's
+        if (r % M != M - 1 && r != T - 2) return hipSuccess;
+        return hipMemcpyAsync(host + (long long)(r - r % M) * width, dev, (long long)(r % M + 1) * width * 8, hipMemcpyDeviceToHost, st);
+    };
     for (int s = 0; s < T; ++s) {
         const int in = s & 1, out = in ^ 1;
-        forward_step(t, st, B, in, out, 0, s < n_fed ? d_frames + (long long)s * C0HW : nullptr, bstride, requant,
-                     d_pred ? d_pred + (long long)s * C0HW : nullptr, (long long)T * C0HW);
+        forward_step(t, st, B, in, out, 0, s < n_fed ? d_frames + s * C0HW : nullptr, bstride, requant, d_pred ? d_pred + s * C0HW : nullptr, T * C0HW);
+        const float* P0 = t->ly[0].P_at(out, B);
+        const uint8_t* next = d_frames + (s + 1) * C0HW;  // the frame P0 predicts (read only while s < T - 1)
         if (h_layer_err && s >= 1) {
-            const int r = s - 1;
-            upper_errors(t, st, 0, 1, B, t->d_err + (long long)(r % M) * L);
-            if (r % M == M - 1 || r == T - 2) {
-                const int first = r - r % M;
-                TCHK(hipMemcpyAsync(h_layer_err + (long long)first * L, t->d_err, (long long)(r - first + 1) * L * 8, hipMemcpyDeviceToHost, st));
-            }
+            upper_errors(t, st, 0, 1, B, t->d_err + (long long)((s - 1) % M) * L);
+            TCHK(flush(h_layer_err, t->d_err, s - 1, L));
         }
-        if (h_layer_err && s < T - 1)
-            image_errors(t, st, t->ly[0].P + (long long)out * B * C0HW, d_frames + (long long)(s + 1) * C0HW, bstride, 1, B, t->d_err + (long long)(s % M) * L);
-        if (s < T - 1) {
-            step_losses(t, st, t->ly[0].P + (long long)out * B * C0HW, d_frames + (long long)(s + 1) * C0HW, bstride, 1, B, t->d_step + s % M);
-            if (h_step_loss && (s % M == M - 1 || s == T - 2)) {
-                const int first = s - s % M;
-                TCHK(hipMemcpyAsync(h_step_loss + first, t->d_step, (s - first + 1) * 8, hipMemcpyDeviceToHost, st));
-            }
-        }
+        if (h_layer_err && s < T - 1) reduce_steps(TERM_ABS, t, st, P0, next, bstride, C0HW, 1, B, (double)(B * 2 * C0HW), t->d_err + (long long)(s % M) * L, L);
+        if (s < T - 1) reduce_steps(TERM_SQ, t, st, P0, next, bstride, C0HW, 1, B, (double)(B * C0HW), t->d_step + s % M, 1);
+        if (s < T - 1 && h_step_loss) TCHK(flush(h_step_loss, t->d_step, s, 1));
     }
     TCHK(hipGetLastError());
     t->state_batch = B;
@@ -696,31 +712,23 @@ int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bs
 
 // Adam moments, step count and the kept sequence state, out.  h_m / h_v: host tables in eigen_set_prednet_weights order (both or
 // neither); h_seq: 3 * n_layers host arrays (h, c, P of layer 0, then of layer 1, ...), each [*seq_batch][C_l][H_l][W_l].
-int eigen_trainer_get_state(eigen_trainer* t, float* const* h_m, float* const* h_v, int32_t n_tensors, int32_t* adam_t, int32_t* seq_batch,
-                            float* const* h_seq, int32_t n_seq)
+int eigen_trainer_get_state(eigen_trainer* t, float* const* h_m, float* const* h_v, int32_t n_tensors, int32_t* adam_t, int32_t* seq_batch, float* const* h_seq, int32_t n_seq)
 {
     if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
     if ((h_m == nullptr) != (h_v == nullptr)) return tfail(EIGEN_ERR_INVALID, "h_m and h_v go together");
     if (h_seq && n_seq != 3 * t->L) return tfail(EIGEN_ERR_INVALID, "expected %d state arrays for %d layers, got %d", 3 * t->L, t->L, n_seq);
-    if (h_m) {
-        int rc = copy_tables(t, t->mom, nullptr, h_m, n_tensors);
-        if (!rc) rc = copy_tables(t, t->var, nullptr, h_v, n_tensors);
-        if (rc) return rc;
-    }
+    const int rc = h_m ? copy_tables(t, n_tensors, false, t->mom, h_m, t->var, h_v) : EIGEN_OK;
+    if (rc) return rc;
     if (adam_t) *adam_t = t->adam_t;
     if (seq_batch) *seq_batch = t->state_batch;
     if (h_seq && t->state_batch > 0) {
         TCHK(hipSetDevice(t->cfg.device));
         TCHK(hipDeviceSynchronize());
-        for (int l = 0; l < t->L; ++l) {
-            TLayer& y = t->ly[l];
-            const long long n = (long long)t->state_batch * y.C * y.HW;
-            float* a[3] = {y.h, y.c, y.P};
-            for (int k = 0; k < 3; ++k) {
-                if (!h_seq[3 * l + k]) return tfail(EIGEN_ERR_INVALID, "state array %d is NULL", 3 * l + k);
-                TCHK(hipMemcpy(h_seq[3 * l + k], a[k] + t->state_slot * n, n * 4, hipMemcpyDeviceToHost));
-            }
+        for (int i = 0; i < 3 * t->L; ++i) {
+            const TLayer& y = t->ly[i / 3];
+            if (!h_seq[i]) return tfail(EIGEN_ERR_INVALID, "state array %d is NULL", i);
+            TCHK(hipMemcpy(h_seq[i], y.state_at(i % 3, t->state_slot, t->state_batch), (long long)t->state_batch * y.CHW() * 4, hipMemcpyDeviceToHost));
         }
     }
     return EIGEN_OK;
@@ -739,21 +747,13 @@ int eigen_trainer_set_state(eigen_trainer* t, const float* const* h_m, const flo
         if (n_seq != 3 * t->L) return tfail(EIGEN_ERR_INVALID, "expected %d state arrays for %d layers, got %d", 3 * t->L, t->L, n_seq);
         for (int i = 0; i < n_seq; ++i) if (!h_seq[i]) return tfail(EIGEN_ERR_INVALID, "state array %d is NULL", i);
     }
-    std::vector<std::pair<long long, long long>> tab;
-    tensor_table(t, tab);
-    if (n_tensors != (int32_t)tab.size()) return tfail(EIGEN_ERR_INVALID, "expected %d weight tensors for %d layers, got %d", (int)tab.size(), t->L, n_tensors);
-    for (int i = 0; i < n_tensors; ++i) if (!h_m[i] || !h_v[i]) return tfail(EIGEN_ERR_INVALID, "tensor %d is NULL", i);
-    int rc = copy_tables(t, t->mom, h_m, nullptr, n_tensors);
-    if (!rc) rc = copy_tables(t, t->var, h_v, nullptr, n_tensors);
+    const int rc = copy_tables(t, n_tensors, true, t->mom, h_m, t->var, h_v);
     if (rc) return rc;
     t->adam_t = adam_t;
-    t->state_batch = 0;
-    t->state_slot = 0;
-    for (int l = 0; seq_batch > 0 && l < t->L; ++l) {
-        TLayer& y = t->ly[l];
-        const long long n = (long long)seq_batch * y.C * y.HW;
-        float* a[3] = {y.h, y.c, y.P};
-        for (int k = 0; k < 3; ++k) TCHK(hipMemcpy(a[k], h_seq[3 * l + k], n * 4, hipMemcpyHostToDevice));
+    t->state_batch = t->state_slot = 0;
+    for (int i = 0; seq_batch > 0 && i < 3 * t->L; ++i) {
+        const TLayer& y = t->ly[i / 3];
+        TCHK(hipMemcpy(y.state_at(i % 3, 0, seq_batch), h_seq[i], (long long)seq_batch * y.CHW() * 4, hipMemcpyHostToDevice));
     }
     t->state_batch = seq_batch;
     return EIGEN_OK;
@@ -768,8 +768,8 @@ int eigen_trainer_adam(eigen_trainer* t, double alpha, double beta1, double beta
     TCHK(hipSetDevice(t->cfg.device));
     const int step = ++t->adam_t;
     const double lr_t = alpha * std::sqrt(1.0 - std::pow(beta2, step)) / (1.0 - std::pow(beta1, step));
-    hipLaunchKernelGGL(tadam_kernel, dim3(blocks(t->n_params)), dim3(EW_T), 0, (hipStream_t)stream, t->prm, t->mom, t->var, (const float*)t->grd,
-                       t->n_params, (float)lr_t, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+    ew((hipStream_t)stream, tadam_kernel, t->n_params, t->prm, t->mom, t->var, (const float*)t->grd, t->n_params, (float)lr_t, (float)(1.0 - beta1),
+       (float)(1.0 - beta2), (float)eps);
     TCHK(hipGetLastError());
     return EIGEN_OK;
 }

@@ -213,13 +213,19 @@ class PredNetTrainer:
             if a.shape != self._shapes[n]:
                 raise ValueError("tensor %r has shape %s, expected %s" % (n, a.shape, self._shapes[n]))
             arrs.append(a)
-        tab = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        _check(self.lib.eigen_trainer_set_weights(self._h, tab, ctypes.c_int32(len(arrs))))
+        _check(self.lib.eigen_trainer_set_weights(self._h, self._table(arrs), ctypes.c_int32(len(arrs))))
+
+    @staticmethod
+    def _table(arrays):
+        """the ctypes table of the data pointers of a list of arrays (which the caller keeps alive)"""
+        return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+    def _empty(self):
+        return {n: np.empty(self._shapes[n], np.float32) for n in self._names}
 
     def _read(self, fn):
-        out = {n: np.empty(self._shapes[n], np.float32) for n in self._names}
-        tab = (ctypes.c_void_p * len(self._names))(*[out[n].ctypes.data for n in self._names])
-        _check(fn(self._h, tab, ctypes.c_int32(len(self._names))))
+        out = self._empty()
+        _check(fn(self._h, self._table([out[n] for n in self._names]), ctypes.c_int32(len(self._names))))
         return out
 
     def weights(self):
@@ -249,8 +255,18 @@ class PredNetTrainer:
         _check_sequence_frames(frames, self.channels, self.w, self.h)
         return torch.from_numpy(np.ascontiguousarray(frames)).cuda(self.device)
 
-    def _fed(self, n_fed, T):
-        return T if n_fed is None else int(n_fed)   # (the range rules are the library's: EngineError -1)
+    def _call_args(self, frames, n_fed):
+        """What forward_backward and evaluate pass alike: the frames on the device, (n, T), n_fed (None: T; the range rules are the
+        library's: EngineError -1) and the byte stride between sequences."""
+        d = self._frames(frames)
+        n, T = int(d.shape[0]), int(d.shape[1])
+        return d, n, T, T if n_fed is None else int(n_fed), ctypes.c_int64(T * int(np.prod(d.shape[2:])))
+
+    def _outputs(self, d, table, pred):
+        """The outputs a call asked for, None where not wanted: the float64 [max(T - 1, 1), L] table of error-unit means and the
+        device tensor of predictions.  Made once every argument has passed its checks."""
+        tab = np.zeros((max(int(d.shape[1]) - 1, 1), len(self.channels)), np.float64) if table else None
+        return tab, self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
 
     def forward_backward(self, frames, reset=True, pred=False, stream=None, n_fed=None, requant=False, step_weights=None, objective="mse",
                          layer_weights=None, layer_errors=False):
@@ -267,9 +283,7 @@ class PredNetTrainer:
         network computed them at step s + 1) weighted by layer_weights, one weight >= 0 per layer: None is L_0, [1, 0, ...];
         L_all is [1, 0.1, ...].  The loss is ``combine_terms`` of the table.  layer_errors=True appends the float64 [T - 1, L]
         table to the return value, under either objective."""
-        d = self._frames(frames)
-        n, T = int(d.shape[0]), int(d.shape[1])
-        n_fed = self._fed(n_fed, T)
+        d, n, T, n_fed, bstride = self._call_args(frames, n_fed)
         if objective not in OBJECTIVES:
             raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
         lam = check_layer_weights(layer_weights, len(self.channels))
@@ -280,11 +294,10 @@ class PredNetTrainer:
                 raise ValueError("step_weights must have T - 1 = %d entries, got shape %s" % (T - 1, w_arr.shape))
         loss = ctypes.c_double(0.0)
         by_error = objective == "error"
-        table = np.zeros((max(T - 1, 1), len(self.channels)), np.float64) if (layer_errors or by_error) else None
-        d_pred = self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
-        _check(self.lib.eigen_trainer_loss_grad_obj(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n),
-                                                    ctypes.c_int32(T), ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))),
-                                                    ctypes.c_int32(int(bool(reset))), ctypes.c_void_p(w_arr.ctypes.data if w_arr is not None and w_arr.size else None),
+        table, d_pred = self._outputs(d, layer_errors or by_error, pred)
+        _check(self.lib.eigen_trainer_loss_grad_obj(self._h, _ptr(d), bstride, ctypes.c_int32(n), ctypes.c_int32(T), ctypes.c_int32(n_fed),
+                                                    ctypes.c_int32(int(bool(requant))), ctypes.c_int32(int(bool(reset))),
+                                                    ctypes.c_void_p(w_arr.ctypes.data if w_arr is not None and w_arr.size else None),
                                                     ctypes.c_int32(OBJECTIVES[objective]), _ptr(lam), ctypes.byref(loss), _ptr(table), _ptr(d_pred),
                                                     _stream_arg(stream)))
         if table is not None:
@@ -299,14 +312,11 @@ class PredNetTrainer:
         state is shared with forward_backward (reset=False of either continues the last call of either).  pred=True also
         returns the float predictions [n, T, C, H, W]; layer_errors=True appends the float64 [T - 1, L] table of error-unit
         means, the one forward_backward returns."""
-        d = self._frames(frames)
-        n, T = int(d.shape[0]), int(d.shape[1])
-        n_fed = self._fed(n_fed, T)
+        d, n, T, n_fed, bstride = self._call_args(frames, n_fed)
         out = np.zeros(max(T - 1, 1), np.float64)
-        table = np.zeros((max(T - 1, 1), len(self.channels)), np.float64) if layer_errors else None
-        d_pred = self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
-        _check(self.lib.eigen_trainer_evaluate_err(self._h, _ptr(d), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), ctypes.c_int32(n), ctypes.c_int32(T),
-                                                   ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))), ctypes.c_int32(int(bool(reset))),
+        table, d_pred = self._outputs(d, layer_errors, pred)
+        _check(self.lib.eigen_trainer_evaluate_err(self._h, _ptr(d), bstride, ctypes.c_int32(n), ctypes.c_int32(T), ctypes.c_int32(n_fed),
+                                                   ctypes.c_int32(int(bool(requant))), ctypes.c_int32(int(bool(reset))),
                                                    ctypes.c_void_p(out.ctypes.data), _ptr(table), _ptr(d_pred), None))
         res = (out[:T - 1],) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table[:T - 1],) if layer_errors else ())
         return res[0] if len(res) == 1 else res
@@ -331,35 +341,26 @@ class PredNetTrainer:
     def state_dict(self):
         """Everything a continued run needs besides ``weights()``: {"adam_m", "adam_v": {name: float32 array}, "adam_t": int,
         "hyper": {alpha, beta1, beta2, eps}, "seq": None or {"h", "c", "P": [one float32 [n, C_l, H_l, W_l] per layer]}}."""
-        nt = len(self._names)
-        m = {n: np.empty(self._shapes[n], np.float32) for n in self._names}
-        v = {n: np.empty(self._shapes[n], np.float32) for n in self._names}
-        tm = (ctypes.c_void_p * nt)(*[m[n].ctypes.data for n in self._names])
-        tv = (ctypes.c_void_p * nt)(*[v[n].ctypes.data for n in self._names])
+        m, v = self._empty(), self._empty()
         t, nb = ctypes.c_int32(0), ctypes.c_int32(0)
-        _check(self.lib.eigen_trainer_get_state(self._h, tm, tv, ctypes.c_int32(nt), ctypes.byref(t), ctypes.byref(nb), None, ctypes.c_int32(0)))
+        _check(self.lib.eigen_trainer_get_state(self._h, self._table([m[n] for n in self._names]), self._table([v[n] for n in self._names]),
+                                                ctypes.c_int32(len(self._names)), ctypes.byref(t), ctypes.byref(nb), None, ctypes.c_int32(0)))
         seq = None
         if nb.value > 0:
             shp = seq_state_shapes(self.channels, self.w, self.h, nb.value)
             seq = {k: [np.empty(s, np.float32) for s in shp] for k in SEQ_PARTS}
             flat = [seq[k][l] for l in range(len(shp)) for k in SEQ_PARTS]
-            ts = (ctypes.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
-            _check(self.lib.eigen_trainer_get_state(self._h, None, None, ctypes.c_int32(0), None, None, ts, ctypes.c_int32(len(flat))))
+            _check(self.lib.eigen_trainer_get_state(self._h, None, None, ctypes.c_int32(0), None, None, self._table(flat), ctypes.c_int32(len(flat))))
         return {"adam_m": m, "adam_v": v, "adam_t": int(t.value), "hyper": {k: float(getattr(self, k)) for k in HYPER}, "seq": seq}
 
     def load_state_dict(self, state):
         """Restore a ``state_dict()`` (after ``set_weights``, which clears all of it).  Shapes and dtypes are checked before
         anything reaches the device (ValueError); the hyper-parameters, when present, replace this trainer's."""
         st = check_state(state, self.channels, self.w, self.h, self.batch)
-        nt = len(self._names)
-        tm = (ctypes.c_void_p * nt)(*[st["adam_m"][n].ctypes.data for n in self._names])
-        tv = (ctypes.c_void_p * nt)(*[st["adam_v"][n].ctypes.data for n in self._names])
-        ts, ns, nb = None, 0, 0
-        if st["seq"] is not None:
-            flat = [st["seq"][k][l] for l in range(len(self.channels)) for k in SEQ_PARTS]
-            ts, ns, nb = (ctypes.c_void_p * len(flat))(*[a.ctypes.data for a in flat]), len(flat), flat[0].shape[0]
-        _check(self.lib.eigen_trainer_set_state(self._h, tm, tv, ctypes.c_int32(nt), ctypes.c_int32(st["adam_t"]), ctypes.c_int32(nb), ts,
-                                                ctypes.c_int32(ns)))
+        tm, tv = (self._table([st[key][n] for n in self._names]) for key in ("adam_m", "adam_v"))
+        flat = [] if st["seq"] is None else [st["seq"][k][l] for l in range(len(self.channels)) for k in SEQ_PARTS]
+        _check(self.lib.eigen_trainer_set_state(self._h, tm, tv, ctypes.c_int32(len(self._names)), ctypes.c_int32(st["adam_t"]),
+                                                ctypes.c_int32(flat[0].shape[0] if flat else 0), self._table(flat) if flat else None, ctypes.c_int32(len(flat))))
         for k, v in st["hyper"].items():
             if k in HYPER:
                 setattr(self, k, v)

@@ -299,78 +299,72 @@ int eigen_trainer_destroy(eigen_trainer* t);
 int eigen_trainer_set_weights(eigen_trainer* t, const float* const* h_tensors, int32_t n_tensors);
 int eigen_trainer_get_weights(eigen_trainer* t, float* const* h_tensors, int32_t n_tensors);
 
-/* Forward with a tape, loss and backward over one batch of sequences; OVERWRITES the gradients.
- *   d_frames: uint8 frames, frame s of sequence b at d_frames + b * bstride + s * C*H*W (bytes); n_steps frames each.
- *   loss = mean over s in [0, n_steps-2], b, c, y, x of (P0_s - x_{s+1})^2, P0_s the float prediction after frame s.
- *   reset = 1: start from zero state (needs n_steps >= 2).  reset = 0: start from the state (h, c, P) the previous call left,
- *   which must have had the same batch; that state is a constant (no gradient flows into the previous call).
- *   h_loss (host, may be NULL) receives the loss; d_pred (may be NULL) float [batch][n_steps][C][H][W] receives P0_s.
- * Errors: EIGEN_ERR_CAPACITY batch / n_steps above the handle's; EIGEN_ERR_STATE no weights, or reset = 0 without a previous
- * call of the same batch; EIGEN_ERR_INVALID n_steps < 2 with reset = 1. */
-int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
-                            int32_t reset, double* h_loss, float* d_pred, void* stream);
+/* The training objective of one call (a per-call argument: the handle keeps nothing of it).
+ *   EIGEN_OBJ_MSE: the squared error of the image-layer prediction against the next frame.
+ *   EIGEN_OBJ_ERROR: PredNet's own objective (Lotter et al.), the mean of the error units, weighted per layer. */
+typedef enum { EIGEN_OBJ_MSE = 0, EIGEN_OBJ_ERROR = 1 } eigen_objective;
 
-/* eigen_trainer_loss_grad with self-fed steps, requantised feedback and step weights.
- * eigen_trainer_loss_grad is this call with n_fed = n_steps, requant = 0, h_step_w = NULL.
+/* Forward with a tape, loss and backward over one batch of sequences; OVERWRITES the gradients (DESIGN.md section 13).
+ *   d_frames: uint8 frames, frame s of sequence b at d_frames + b * bstride + s * C*H*W (bytes); n_steps frames each.
+ *   reset = 1: start from zero state (needs n_steps >= 2).  reset = 0: start from the state (h, c, P) the previous call left,
+ *     which must have had the same batch; that state is a constant (no gradient flows into the previous call).
  *   n_fed: steps s < n_fed read frame s (teacher-forced); steps s >= n_fed are self-fed: their input is the prediction
  *     P0_{s-1} (for s = 0: the kept P0).  0 <= n_fed <= n_steps; n_fed = 0 needs reset = 0.  All n_steps frames are still
  *     passed: on self-fed steps they are targets only.
  *   requant: how a prediction is fed back, as eigen_config.requant_feedback: 0 the float P0_{s-1} (E_0 is exactly zero);
  *     1 the byte the inference engine emits for it over 255, (float)(uint8_t)(int)(v * 255.0f) / 255.0f, a constant of the
  *     graph: E_0 = [relu(q - P0), relu(P0 - q)] is small, non-zero and sends a gradient into P0_{s-1} (relu'(0) = 0).
- *   h_step_w: host double[n_steps - 1], >= 0, finite, not all zero, or NULL (all ones).  With mse_s the mean over b, c, y, x of
- *     (P0_s - x_{s+1})^2: loss = sum_s w_s mse_s / sum_s w_s, added in step order.  With NULL the loss and the gradients are
- *     those of eigen_trainer_loss_grad to the last bit (one sum over all terms times 1 / ((n_steps-1) numel)); with weights the
- *     mse_s are the numbers eigen_trainer_evaluate returns and the sum above is done in double on the host.
- *   A call owns its n_steps - 1 loss terms: the term of its last prediction against the next call's first frame is in no call.
- * Errors: those of eigen_trainer_loss_grad; EIGEN_ERR_INVALID n_fed outside [0, n_steps], n_fed = 0 with reset = 1, requant not
- * 0 or 1, a negative / non-finite weight or weights that are all zero. */
-int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
-                                int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, double* h_loss,
-                                float* d_pred, void* stream);
-
-/* Forward only, without a tape: the per-step losses of a sequence of ANY length (n_steps is not bounded by max_steps; batch <=
- * max_batch).  Arguments as eigen_trainer_loss_grad_ext.  Touches neither the gradients (a following eigen_trainer_adam still
- * applies those of the last loss_grad) nor the Adam state.  It shares the kept sequence state (h, c, P) with loss_grad: there
- * is one state per handle, every call of either leaves its final state, and a reset = 0 call of either continues it.
- *   h_step_loss (host, may be NULL): double[n_steps - 1], the unweighted mse_s of every step.
- *   d_pred (may be NULL): float [batch][n_steps][C][H][W].
- * Errors: as eigen_trainer_loss_grad_ext, without the bound on n_steps. */
-int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
-                           int32_t n_fed, int32_t requant, int32_t reset, double* h_step_loss, float* d_pred, void* stream);
-
-/* The training objective of one call (a per-call argument: the handle keeps nothing of it).
- *   EIGEN_OBJ_MSE: the squared error of eigen_trainer_loss_grad_ext.
- *   EIGEN_OBJ_ERROR: PredNet's own objective (Lotter et al.), the mean of the error units, weighted per layer. */
-typedef enum { EIGEN_OBJ_MSE = 0, EIGEN_OBJ_ERROR = 1 } eigen_objective;
-
-/* eigen_trainer_loss_grad_ext with a choice of objective and the table of error-unit means.
- * eigen_trainer_loss_grad_ext is this call with objective = EIGEN_OBJ_MSE, h_layer_w = NULL, h_layer_err = NULL.
- *   err[s][l], s in [0, n_steps-2] (term s belongs to step s + 1, as mse_s does):
+ *   h_step_w: host double[n_steps - 1], >= 0, finite, not all zero, or NULL (all ones): the weight w_s of term s.  A call owns
+ *     its n_steps - 1 terms; term s belongs to step s + 1: the prediction P0_s after frame s against frame s + 1.  The term of
+ *     the last prediction against the next call's first frame is in no call.
+ *   objective = EIGEN_OBJ_MSE: with mse_s the mean over b, c, y, x of (P0_s - x_{s+1})^2, loss = sum_s w_s mse_s / sum_s w_s.
+ *     With h_step_w = NULL it is one sum over all terms times 1 / ((n_steps-1) numel), formed on the device; with weights the mse_s
+ *     are the numbers eigen_trainer_evaluate returns and the sum is done in double on the host, in step order.
+ *   objective = EIGEN_OBJ_ERROR: loss = sum_s w_s sum_l lambda_l err[s][l] / sum_s w_s, formed on the host in double in (step,
+ *     layer) order; lambda = h_layer_w.  The gradients are those of this loss (relu'(0) = 0, sign(0) = 0).
+ *   err[s][l], s in [0, n_steps-2]:
  *     l = 0: the mean over b, the 2 C_0 error channels, y, x of [relu(x_{s+1} - P0_s), relu(P0_s - x_{s+1})], always against the
  *       TRUE frame x_{s+1} = (float)byte / 255.0f, on self-fed steps as well; it equals mean |P0_s - x_{s+1}| / 2.
  *     l > 0: the mean over b, 2 C_l, y, x of E_l of step s + 1, the errors the network itself computed there.
  *     The errors of the call's first step (the kept P against the first frame) belong to no call.
- *   objective = EIGEN_OBJ_ERROR: loss = sum_s w_s sum_l lambda_l err[s][l] / sum_s w_s, formed on the host in double in (step,
- *     layer) order; w = h_step_w (NULL: all one), lambda = h_layer_w.  The gradients are those of this loss (relu'(0) = 0,
- *     sign(0) = 0).
- *   objective = EIGEN_OBJ_MSE: the loss and gradients of eigen_trainer_loss_grad_ext to the last bit.
  *   h_layer_w: host double[n_layers], >= 0, finite, not all zero, or NULL: L_0, [1, 0, ...] (Lotter's L_all is [1, 0.1, ...]).
  *     Checked whenever it is given; used by EIGEN_OBJ_ERROR only.
+ *   h_loss (host, may be NULL) receives the loss; d_pred (may be NULL) float [batch][n_steps][C][H][W] receives P0_s.
  *   h_layer_err (host, may be NULL): double[(n_steps-1) * n_layers], err[s][l] at s * n_layers + l, under either objective.
  *     Every entry is reduced in double over fixed slices in a fixed order: the same frames give the same bits from
  *     eigen_trainer_evaluate_err.
- * Errors: those of eigen_trainer_loss_grad_ext; EIGEN_ERR_INVALID an unknown objective, a negative / non-finite layer weight or
- * layer weights that are all zero. */
+ * Errors: EIGEN_ERR_CAPACITY batch / n_steps above the handle's; EIGEN_ERR_STATE no weights, or reset = 0 without a previous
+ * call of the same batch; EIGEN_ERR_INVALID n_steps < 2 with reset = 1, n_fed outside [0, n_steps], n_fed = 0 with reset = 1,
+ * requant not 0 or 1, an unknown objective, a negative / non-finite step or layer weight, or weights that are all zero. */
 int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
                                 int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
                                 const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, void* stream);
 
-/* eigen_trainer_evaluate plus the table err[s][l] of eigen_trainer_loss_grad_obj (h_layer_err, host double[(n_steps-1) *
- * n_layers], may be NULL), for a sequence of any length.  eigen_trainer_evaluate is this call with h_layer_err = NULL. */
+/* eigen_trainer_loss_grad_obj with objective = EIGEN_OBJ_MSE, h_layer_w = NULL, h_layer_err = NULL. */
+int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, double* h_loss,
+                                float* d_pred, void* stream);
+
+/* eigen_trainer_loss_grad_ext with n_fed = n_steps, requant = 0, h_step_w = NULL. */
+int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                            int32_t reset, double* h_loss, float* d_pred, void* stream);
+
+/* Forward only, without a tape: the per-step losses of a sequence of ANY length (n_steps is not bounded by max_steps; batch <=
+ * max_batch).  d_frames, bstride, batch, n_fed, requant and reset as eigen_trainer_loss_grad_obj.  Touches neither the gradients
+ * (a following eigen_trainer_adam still applies those of the last loss_grad) nor the Adam state.  It shares the kept sequence
+ * state (h, c, P) with loss_grad: there is one state per handle, every call of either leaves its final state, and a reset = 0
+ * call of either continues it.
+ *   h_step_loss (host, may be NULL): double[n_steps - 1], the unweighted mse_s of every step.
+ *   h_layer_err (host, may be NULL): double[(n_steps-1) * n_layers], the table err[s][l] of eigen_trainer_loss_grad_obj.
+ *   d_pred (may be NULL): float [batch][n_steps][C][H][W].
+ * Errors: as eigen_trainer_loss_grad_obj, without the bound on n_steps. */
 int eigen_trainer_evaluate_err(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
                                int32_t n_fed, int32_t requant, int32_t reset, double* h_step_loss, double* h_layer_err,
                                float* d_pred, void* stream);
+
+/* eigen_trainer_evaluate_err with h_layer_err = NULL. */
+int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                           int32_t n_fed, int32_t requant, int32_t reset, double* h_step_loss, float* d_pred, void* stream);
 
 /* Everything a continued run depends on besides the weights.
  *   h_m, h_v: the Adam first and second moments, host tables in eigen_set_prednet_weights order (get: both or neither).
@@ -386,7 +380,7 @@ int eigen_trainer_get_state(eigen_trainer* t, float* const* h_m, float* const* h
 int eigen_trainer_set_state(eigen_trainer* t, const float* const* h_m, const float* const* h_v, int32_t n_tensors,
                             int32_t adam_t, int32_t seq_batch, const float* const* h_seq, int32_t n_seq);
 
-/* The gradients of the last eigen_trainer_loss_grad / _ext, host tables in eigen_set_prednet_weights order. */
+/* The gradients of the last eigen_trainer_loss_grad / _ext / _obj, host tables in eigen_set_prednet_weights order. */
 int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n_tensors);
 
 /* One Adam step on the current gradients (step count kept by the handle, from 1): m += (1-beta1)(g-m),

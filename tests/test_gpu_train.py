@@ -1,113 +1,18 @@
-"""PredNet training on the GPU (eigen_trainer_*, train.PredNetTrainer) against a float64 torch-CPU autograd restatement of the
-network and loss written here (DESIGN.md section 13 states the semantics both follow)."""
+"""PredNet training on the GPU (eigen_trainer_*, train.PredNetTrainer) against the float64 torch-CPU autograd restatement of the
+network and loss in oracle/prednet_train_ref.py (DESIGN.md section 13 states the semantics both follow)."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from evolutionary_illusion_generator_amd import engine, fitness, weights
 from evolutionary_illusion_generator_amd.engine import EngineError
 from evolutionary_illusion_generator_amd.train import PredNetTrainer, TrainerConfig
+from oracle import prednet_train_ref as ref
+from tests.train_support import SHAPES, _check_grads, _drifting, _weight_sets
 
 pytestmark = pytest.mark.gpu
-
-GATES = ("i", "f", "c", "o")
-# (w, h, channels): 2, 3 and 4 layers, gray and colour, none square
-SHAPES = [(12, 8, [1, 4]), (16, 12, [3, 4, 6]), (24, 16, [1, 3, 4, 5])]
-
-
-def _drifting(seed, n, T, c, h, w, speed=1):
-    """n sequences of T frames: a smooth texture shifted by `speed` pixels per frame, each sequence in its own direction."""
-    rng = np.random.default_rng(seed)
-    H, W = h + 2 * speed * T, w + 2 * speed * T
-    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
-    out = np.zeros((n, T, c, h, w), np.uint8)
-    for i in range(n):
-        tex = np.zeros((c, H, W))
-        for ch in range(c):
-            for _ in range(3):
-                fy, fx, ph = rng.uniform(0.1, 0.6), rng.uniform(0.1, 0.6), rng.uniform(0, 2 * np.pi)
-                tex[ch] += np.sin(fy * yy + fx * xx + ph)
-        tex = np.clip(128 + 40 * tex, 0, 255)
-        dy, dx = [(1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1)][rng.integers(6)]
-        for t in range(T):
-            y0, x0 = speed * T + dy * speed * t, speed * T + dx * speed * t
-            out[i, t] = tex[:, y0:y0 + h, x0:x0 + w].astype(np.uint8)
-    return out
-
-
-def _random_weights(ch, w, h, seed):
-    rng = np.random.default_rng(seed)
-    out = {}
-    for k, shp in weights.tensor_shapes(ch, w, h).items():
-        fan = shp[1] * 9 if len(shp) == 4 and "/c_" not in k else 1
-        out[k] = (rng.normal(0, 0.8 / np.sqrt(fan), shp) if fan > 1 else rng.normal(0, 0.3, shp)).astype(np.float32)
-    return out
-
-
-def _clamp01(v):
-    """clamp(v, 0, 1) whose gradient passes only where 0 < v < 1 (chainer's clipped_relu)"""
-    inside = (v > 0) & (v < 1)
-    return torch.where(inside, v, v.detach().clamp(0.0, 1.0))
-
-
-def _ref(wts, ch, frames, state=None):
-    """float64 autograd PredNet over frames uint8 [B, T, C, H, W] from `state` (detached (h, c, P), or zeros).
-    -> (loss, {name: grad}, P0 [B, T, C, H, W], final state)"""
-    L = len(ch)
-    p = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in wts.items()}
-    x = torch.from_numpy(frames.astype(np.float32) / np.float32(255.0)).double()
-    B, T = frames.shape[:2]
-    H, W = frames.shape[3:]
-    if state is None:
-        z = lambda l: torch.zeros(B, ch[l], H >> l, W >> l, dtype=torch.float64)
-        hs, cs, Ps = [z(l) for l in range(L)], [z(l) for l in range(L)], [z(l) for l in range(L)]
-    else:
-        hs, cs, Ps = [list(s) for s in state]
-    conv = lambda a, wt, b=None: F.conv2d(a, wt, b, padding=1)
-    preds, loss = [], 0.0
-    for t in range(T):
-        E = [None] * L
-        E[0] = torch.cat((F.relu(x[:, t] - Ps[0]), F.relu(Ps[0] - x[:, t])), 1)
-        for l in range(1, L):
-            A = F.max_pool2d(F.relu(conv(E[l - 1], p["ConvA%d/W" % l], p["ConvA%d/b" % l])), 2, 2)
-            E[l] = torch.cat((F.relu(A - Ps[l]), F.relu(Ps[l] - A)), 1)
-        for l in reversed(range(L)):
-            stack = lambda s: torch.cat([p["ConvLSTM%d/%s/W" % (l, s % g)] for g in GATES], 0)
-            zz = conv(E[l], stack("x_%s0")) + conv(hs[l], stack("h_%s"), torch.cat([p["ConvLSTM%d/h_%s/b" % (l, g)] for g in GATES]))
-            if l < L - 1:
-                zz = zz + conv(F.interpolate(hs[l + 1], scale_factor=2, mode="nearest"), stack("x_%s1"))
-            zi, zf, zc, zo = torch.chunk(zz, 4, 1)
-            c = cs[l]
-            i = torch.sigmoid(zi + p["ConvLSTM%d/c_i/W" % l] * c)
-            f = torch.sigmoid(zf + p["ConvLSTM%d/c_f/W" % l] * c)
-            o = torch.sigmoid(zo + p["ConvLSTM%d/c_o/W" % l] * c)
-            cs[l] = torch.tanh(zc) * i + f * c
-            hs[l] = o * torch.tanh(cs[l])
-            v = conv(hs[l], p["ConvP%d/W" % l], p["ConvP%d/b" % l])
-            Ps[l] = _clamp01(v) if l == 0 else F.relu(v)
-        preds.append(Ps[0])
-        if t < T - 1:
-            loss = loss + ((Ps[0] - x[:, t + 1]) ** 2).sum()
-    loss = loss / ((T - 1) * Ps[0].numel())
-    names = list(p)
-    g = torch.autograd.grad(loss, [p[n] for n in names], allow_unused=True)
-    grads = {n: (gg.numpy() if gg is not None else np.zeros(p[n].shape)) for n, gg in zip(names, g)}
-    state = tuple([s.detach() for s in ss] for ss in (hs, cs, Ps))
-    return float(loss.detach()), grads, torch.stack(preds, 1).detach().numpy(), state
-
-
-def _check_grads(got, ref):
-    G = np.sqrt(sum(float((r ** 2).sum()) for r in ref.values()))
-    for k, r in ref.items():
-        err = np.linalg.norm((got[k].astype(np.float64) - r).ravel())
-        assert err <= 1e-3 * np.linalg.norm(r.ravel()) + 1e-6 * G, (k, err, np.linalg.norm(r.ravel()), G)
-
-
-def _weight_sets(ch, w, h):
-    return [("synthetic", weights.synthetic_prednet_weights(ch, w, h, seed=1)), ("random", _random_weights(ch, w, h, seed=2))]
 
 
 @pytest.mark.parametrize("w,h,ch", SHAPES)
@@ -118,7 +23,8 @@ def test_forward_loss_and_every_gradient_match_float64_autograd(cuda, w, h, ch):
         with PredNetTrainer(wts, ch, w, h, B, T) as tr:
             loss, pred = tr.forward_backward(frames, pred=True)
             got = tr.grads()
-        ref_loss, ref_g, ref_pred, _ = _ref(wts, ch, frames)
+        r = ref.run(wts, ch, frames)
+        ref_loss, ref_g, ref_pred = r.loss, r.grads, r.pred
         assert np.abs(pred - ref_pred).max() <= 1e-5, (label, np.abs(pred - ref_pred).max())
         assert abs(loss - ref_loss) <= 1e-5 * ref_loss, (label, loss, ref_loss)
         _check_grads(got, ref_g)
@@ -133,8 +39,9 @@ def test_truncated_bptt_matches_the_reference_detached_at_the_split(cuda, w, h, 
         l1, g1 = tr.loss_and_grad(frames[:, :k], reset=True)
         l2, pred2 = tr.forward_backward(frames[:, k:], reset=False, pred=True)
         g2 = tr.grads()
-    r1, rg1, _, state = _ref(wts, ch, frames[:, :k])
-    r2, rg2, rpred2, _ = _ref(wts, ch, frames[:, k:], state)
+    first = ref.run(wts, ch, frames[:, :k])
+    second = ref.run(wts, ch, frames[:, k:], state=first.state)
+    r1, rg1, r2, rg2, rpred2 = first.loss, first.grads, second.loss, second.grads, second.pred
     assert abs(l1 - r1) <= 1e-5 * r1 and abs(l2 - r2) <= 1e-5 * r2, (l1, r1, l2, r2)
     assert np.abs(pred2 - rpred2).max() <= 1e-5
     _check_grads(g1, rg1)

@@ -1,103 +1,20 @@
 """Self-fed training steps, step weights, tape-free evaluation and trainer state in and out (eigen_trainer_loss_grad_ext,
-eigen_trainer_evaluate, eigen_trainer_get_state / set_state) against a float64 torch-CPU autograd
-restatement written here: `_ref_ext` restates tests/test_gpu_train.py's `_ref` with n_fed, a detached requantisation and step
-weights.  Shapes, weight sets and tolerances are those of tests/test_gpu_train.py."""
+eigen_trainer_evaluate, eigen_trainer_get_state / set_state) against the float64 torch-CPU autograd
+restatement in oracle/prednet_train_ref.py, run with n_fed, a detached requantisation and step weights.  Shapes, weight sets and
+tolerances are those of tests/test_gpu_train.py."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from evolutionary_illusion_generator_amd import engine, fitness, weights
 from evolutionary_illusion_generator_amd.engine import EngineError
 from evolutionary_illusion_generator_amd.train import PredNetTrainer
-from tests.test_gpu_train import GATES, SHAPES, _check_grads, _clamp01, _drifting, _weight_sets
+from oracle import prednet_train_ref as ref
+from tests.train_support import SHAPES, _check_grads, _drifting, _fed_from, _grads_differ, _same_weights, _weight_sets
 
 pytestmark = pytest.mark.gpu
-
-
-def _q(v):
-    """The byte the inference engine emits for a float32 prediction, over 255: the statement of EPI_CONVP / e0_resume_kernel
-    (csrc/conv_mfma.h) and of terr_fed_fwd_kernel, `(float)(uint8_t)(int)(v * 255.0f) / 255.0f`, in float32."""
-    v = np.asarray(v, np.float32)
-    return (v * np.float32(255.0)).astype(np.int32).astype(np.uint8).astype(np.float32) / np.float32(255.0)
-
-
-def _ref_ext(wts, ch, frames, n_fed=None, requant=False, step_w=None, state=None, fed=None):
-    """float64 autograd PredNet over frames uint8 [B, T, C, H, W]: steps t < n_fed read frame t, steps t >= n_fed are fed the
-    previous prediction -- itself (requant False: part of the graph, E_0 = relu(0)) or the constant fed[:, t] (requant True:
-    float32 [B, T, C, H, W], the requantised prediction of step t - 1).  loss = sum_t w_t mse_t / sum_t w_t against the true
-    frames.  -> (loss, {name: grad}, P0 [B, T, C, H, W], per-step mse [T - 1], final state)"""
-    L = len(ch)
-    p = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in wts.items()}
-    x = torch.from_numpy(frames.astype(np.float32) / np.float32(255.0)).double()
-    B, T = frames.shape[:2]
-    H, W = frames.shape[3:]
-    n_fed = T if n_fed is None else n_fed
-    w_t = torch.ones(T - 1, dtype=torch.float64) if step_w is None else torch.tensor(np.asarray(step_w, np.float64))
-    if state is None:
-        z = lambda l: torch.zeros(B, ch[l], H >> l, W >> l, dtype=torch.float64)
-        hs, cs, Ps = [z(l) for l in range(L)], [z(l) for l in range(L)], [z(l) for l in range(L)]
-    else:
-        hs, cs, Ps = [list(s) for s in state]
-    conv = lambda a, wt, b=None: F.conv2d(a, wt, b, padding=1)
-    preds, mses = [], []
-    for t in range(T):
-        if t < n_fed:
-            xin = x[:, t]
-        elif requant:
-            xin = torch.from_numpy(np.asarray(fed[:, t], np.float32)).double()   # a constant: quantisation passes no gradient
-        else:
-            xin = Ps[0]                                                           # the float prediction itself
-        E = [None] * L
-        E[0] = torch.cat((F.relu(xin - Ps[0]), F.relu(Ps[0] - xin)), 1)
-        for l in range(1, L):
-            A = F.max_pool2d(F.relu(conv(E[l - 1], p["ConvA%d/W" % l], p["ConvA%d/b" % l])), 2, 2)
-            E[l] = torch.cat((F.relu(A - Ps[l]), F.relu(Ps[l] - A)), 1)
-        for l in reversed(range(L)):
-            stack = lambda s: torch.cat([p["ConvLSTM%d/%s/W" % (l, s % g)] for g in GATES], 0)
-            zz = conv(E[l], stack("x_%s0")) + conv(hs[l], stack("h_%s"), torch.cat([p["ConvLSTM%d/h_%s/b" % (l, g)] for g in GATES]))
-            if l < L - 1:
-                zz = zz + conv(F.interpolate(hs[l + 1], scale_factor=2, mode="nearest"), stack("x_%s1"))
-            zi, zf, zc, zo = torch.chunk(zz, 4, 1)
-            c = cs[l]
-            i = torch.sigmoid(zi + p["ConvLSTM%d/c_i/W" % l] * c)
-            f = torch.sigmoid(zf + p["ConvLSTM%d/c_f/W" % l] * c)
-            o = torch.sigmoid(zo + p["ConvLSTM%d/c_o/W" % l] * c)
-            cs[l] = torch.tanh(zc) * i + f * c
-            hs[l] = o * torch.tanh(cs[l])
-            v = conv(hs[l], p["ConvP%d/W" % l], p["ConvP%d/b" % l])
-            Ps[l] = _clamp01(v) if l == 0 else F.relu(v)
-        preds.append(Ps[0])
-        if t < T - 1:
-            mses.append(((Ps[0] - x[:, t + 1]) ** 2).mean())
-    names = list(p)
-    if T >= 2:
-        loss = sum(w_t[t] * mses[t] for t in range(T - 1)) / w_t.sum()
-        g = torch.autograd.grad(loss, [p[n] for n in names], allow_unused=True)
-        loss = float(loss.detach())
-    else:
-        loss, g = 0.0, [None] * len(names)
-    grads = {n: (gg.numpy() if gg is not None else np.zeros(p[n].shape)) for n, gg in zip(names, g)}
-    state = tuple([s.detach() for s in ss] for ss in (hs, cs, Ps))
-    return loss, grads, torch.stack(preds, 1).detach().numpy(), np.array([float(m.detach()) for m in mses]), state
-
-
-def _fed_from(pred):
-    """fed[:, t] = q(pred[:, t - 1]): the constants a requantised self-fed step t reads, from float32 predictions"""
-    fed = np.zeros_like(pred, dtype=np.float32)
-    fed[:, 1:] = _q(pred[:, :-1])
-    return fed
-
-
-def _grads_differ(a, b):
-    """True when b misses a by more than _check_grads allows on at least one tensor"""
-    try:
-        _check_grads(b, a)
-    except AssertionError:
-        return True
-    return False
 
 
 T_EXT, N_FED = 6, 3
@@ -121,7 +38,8 @@ def test_self_fed_loss_predictions_and_every_gradient_match_float64_autograd(cud
             got = tr.grads()
             loss2, pred2 = tr.forward_backward(frames, pred=True, n_fed=N_FED, requant=requant, step_weights=sw)
             got2 = tr.grads()
-        ref_loss, ref_g, ref_pred, _, _ = _ref_ext(wts, ch, frames, N_FED, requant, sw, fed=_fed_from(pred) if requant else None)
+        r = ref.run(wts, ch, frames, n_fed=N_FED, requant=requant, step_weights=sw, fed=_fed_from(pred) if requant else None)
+        ref_loss, ref_g, ref_pred = r.loss, r.grads, r.pred
         print("%s requant=%d %s: loss %.8f ref %.8f, max |pred diff| %.2e" % (label, requant, wkey, loss, ref_loss, np.abs(pred - ref_pred).max()))
         assert np.abs(pred - ref_pred).max() <= 1e-5, (label, np.abs(pred - ref_pred).max())
         assert abs(loss - ref_loss) <= 1e-5 * ref_loss, (label, loss, ref_loss)
@@ -134,7 +52,7 @@ def test_self_fed_loss_predictions_and_every_gradient_match_float64_autograd(cud
             # (the random set at the two gray shapes drives P0 into the clamp everywhere: every gradient is exactly zero with
             # either feedback, so the comparison is made wherever the float-feedback gradient is not zero; the synthetic set
             # has one at every shape)
-            _, g0, _, _, _ = _ref_ext(wts, ch, frames, N_FED, False, sw)
+            g0 = ref.run(wts, ch, frames, n_fed=N_FED, requant=False, step_weights=sw).grads
             assert label == "random" or any(np.any(g) for g in g0.values())
             if any(np.any(g) for g in g0.values()):
                 assert _grads_differ(ref_g, g0), label
@@ -212,8 +130,8 @@ def test_evaluate_runs_past_max_steps_and_leaves_the_gradients_alone(cuda):
             assert tr.tape_bytes == tape
         for k in before:
             assert np.array_equal(before[k], after[k]), k
-        _, _, ref_pred, ref_l, _ = _ref_ext(wts, ch, frames, n_fed)
-        _, _, _, ref_tf, _ = _ref_ext(wts, ch, frames)
+        r = ref.run(wts, ch, frames, n_fed=n_fed)
+        ref_pred, ref_l, ref_tf = r.pred, r.step_mse, ref.run(wts, ch, frames).step_mse
         print(label, "evaluate, 11 frames on a 4-step tape: max rel err", np.abs(got / ref_l - 1).max(), np.abs(got_tf / ref_tf - 1).max())
         assert got.shape == (T - 1,) and got_tf.shape == (T - 1,)
         assert np.abs(pred - ref_pred).max() <= 1e-5
@@ -248,11 +166,6 @@ def test_step_losses_are_the_numbers_loss_grad_reduces(cuda, requant):
     assert ones == acc / (T - 1)
     print("NULL weights against the mean of the step losses: %.3e relative" % abs(plain / ones - 1))
     assert abs(plain - ones) <= 64 * np.finfo(np.float64).eps * ones, (plain, ones)
-
-
-def _same_weights(a, b):
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
 
 
 def test_resume_from_a_checkpoint_is_bit_exact(cuda, tmp_path):

@@ -1,83 +1,25 @@
 """Training on the error units, Lotter's L_0 / L_all (eigen_trainer_loss_grad_obj, eigen_trainer_evaluate_err,
-train.PredNetTrainer(objective="error")), against a float64 torch-CPU autograd restatement written here:
-`_ref_obj` restates tests/test_gpu_train.py's `_ref` with n_fed, a detached requantisation, the image layer's error units taken
-against the true frame, and the table err[s][l].  Shapes, weight sets and tolerances are those of tests/test_gpu_train.py."""
+train.PredNetTrainer(objective="error")), against the float64 torch-CPU autograd restatement in
+oracle/prednet_train_ref.py, run with objective="error": the image layer's error units taken against the true frame, and the
+table err[s][l].  Shapes, weight sets and tolerances are those of tests/test_gpu_train.py."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from evolutionary_illusion_generator_amd import weights
 from evolutionary_illusion_generator_amd.engine import EngineError
 from evolutionary_illusion_generator_amd.train import PredNetTrainer, combine_terms
-from tests.test_gpu_train import GATES, SHAPES, _check_grads, _clamp01, _drifting, _random_weights
-from tests.test_gpu_train_ext import _fed_from, _grads_differ
+from oracle import prednet_train_ref as ref
+from tests.train_support import (SHAPES, _check_grads, _drifting, _fed_from, _grads_differ, _loss_grad_ext, _loss_grad_obj_loss, _random_weights,
+                                 _same_weights)
 
 pytestmark = pytest.mark.gpu
 
 
 def _lam(name, L):
     return {"l0": [1.0] + [0.0] * (L - 1), "lall": [1.0] + [0.1] * (L - 1)}[name]
-
-
-def _ref_obj(wts, ch, frames, lam, n_fed=None, requant=False, step_w=None, fed=None):
-    """float64 autograd PredNet over frames uint8 [B, T, C, H, W], as tests/test_gpu_train_ext.py's `_ref_ext` runs it (steps
-    t >= n_fed are fed the previous prediction: itself, or with requant the constant fed[:, t]).
-    err[s][0] = mean of [relu(x_{s+1} - P0_s), relu(P0_s - x_{s+1})] against the TRUE frame; err[s][l > 0] = mean of E_l of step
-    s + 1.  loss = sum_s w_s sum_l lam_l err[s][l] / sum_s w_s.
-    -> (loss, {name: grad}, P0 [B, T, C, H, W], table [T - 1, L], per-step mse [T - 1])"""
-    L = len(ch)
-    p = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in wts.items()}
-    x = torch.from_numpy(frames.astype(np.float32) / np.float32(255.0)).double()
-    B, T = frames.shape[:2]
-    H, W = frames.shape[3:]
-    n_fed = T if n_fed is None else n_fed
-    w_t = [1.0] * (T - 1) if step_w is None else [float(v) for v in step_w]
-    z = lambda l: torch.zeros(B, ch[l], H >> l, W >> l, dtype=torch.float64)
-    hs, cs, Ps = [z(l) for l in range(L)], [z(l) for l in range(L)], [z(l) for l in range(L)]
-    conv = lambda a, wt, b=None: F.conv2d(a, wt, b, padding=1)
-    preds, mses = [], []
-    err = [[None] * L for _ in range(T - 1)]
-    for t in range(T):
-        if t < n_fed:
-            xin = x[:, t]
-        elif requant:
-            xin = torch.from_numpy(np.asarray(fed[:, t], np.float32)).double()   # a constant: quantisation passes no gradient
-        else:
-            xin = Ps[0]
-        E = [None] * L
-        E[0] = torch.cat((F.relu(xin - Ps[0]), F.relu(Ps[0] - xin)), 1)
-        for l in range(1, L):
-            A = F.max_pool2d(F.relu(conv(E[l - 1], p["ConvA%d/W" % l], p["ConvA%d/b" % l])), 2, 2)
-            E[l] = torch.cat((F.relu(A - Ps[l]), F.relu(Ps[l] - A)), 1)
-            if t >= 1:
-                err[t - 1][l] = E[l].mean()
-        for l in reversed(range(L)):
-            stack = lambda s: torch.cat([p["ConvLSTM%d/%s/W" % (l, s % g)] for g in GATES], 0)
-            zz = conv(E[l], stack("x_%s0")) + conv(hs[l], stack("h_%s"), torch.cat([p["ConvLSTM%d/h_%s/b" % (l, g)] for g in GATES]))
-            if l < L - 1:
-                zz = zz + conv(F.interpolate(hs[l + 1], scale_factor=2, mode="nearest"), stack("x_%s1"))
-            zi, zf, zc, zo = torch.chunk(zz, 4, 1)
-            c = cs[l]
-            i = torch.sigmoid(zi + p["ConvLSTM%d/c_i/W" % l] * c)
-            f = torch.sigmoid(zf + p["ConvLSTM%d/c_f/W" % l] * c)
-            o = torch.sigmoid(zo + p["ConvLSTM%d/c_o/W" % l] * c)
-            cs[l] = torch.tanh(zc) * i + f * c
-            hs[l] = o * torch.tanh(cs[l])
-            v = conv(hs[l], p["ConvP%d/W" % l], p["ConvP%d/b" % l])
-            Ps[l] = _clamp01(v) if l == 0 else F.relu(v)
-        preds.append(Ps[0])
-        if t < T - 1:
-            err[t][0] = torch.cat((F.relu(x[:, t + 1] - Ps[0]), F.relu(Ps[0] - x[:, t + 1])), 1).mean()
-            mses.append(((Ps[0] - x[:, t + 1]) ** 2).mean())
-    loss = sum(w_t[s] * sum(lam[l] * err[s][l] for l in range(L)) for s in range(T - 1)) / sum(w_t)
-    names = list(p)
-    g = torch.autograd.grad(loss, [p[n] for n in names], allow_unused=True)
-    grads = {n: (gg.numpy() if gg is not None else np.zeros(p[n].shape)) for n, gg in zip(names, g)}
-    table = np.array([[float(e.detach()) for e in row] for row in err])
-    return float(loss.detach()), grads, torch.stack(preds, 1).detach().numpy(), table, np.array([float(m.detach()) for m in mses])
 
 
 def _rel_close(got, ref, tol=1e-5):
@@ -92,20 +34,6 @@ CASES = {"teacher_forced": (None, False, None), "self_fed": (N_FED, False, None)
          "self_fed_requant_weighted": (N_FED, True, [0.0, 1.0, 0.5, 2.0, 1.5])}
 
 
-def _loss_grad_obj_loss(tr, frames, n_fed, requant, sw, lam):
-    """the loss eigen_trainer_loss_grad_obj itself returns under EIGEN_OBJ_ERROR (train.py forms its own from the table)"""
-    d = torch.from_numpy(frames).cuda()
-    B, T = frames.shape[:2]
-    loss = ctypes.c_double()
-    w_arr = None if sw is None else np.ascontiguousarray(sw, np.float64)
-    l_arr = np.ascontiguousarray(lam, np.float64)
-    rc = tr.lib.eigen_trainer_loss_grad_obj(tr._h, ctypes.c_void_p(d.data_ptr()), ctypes.c_int64(T * frames[0, 0].size), B, T, T if n_fed is None else n_fed,
-                                            int(requant), 1, ctypes.c_void_p(None if w_arr is None else w_arr.ctypes.data), 1,
-                                            ctypes.c_void_p(l_arr.ctypes.data), ctypes.byref(loss), None, None, None)
-    assert rc == 0
-    return loss.value
-
-
 def _run_case(wts, ch, w, h, frames, lam, case):
     n_fed, requant, sw = CASES[case]
     with PredNetTrainer(wts, ch, w, h, frames.shape[0], frames.shape[1]) as tr:
@@ -114,8 +42,9 @@ def _run_case(wts, ch, w, h, frames, lam, case):
         got = tr.grads()
         c_loss = _loss_grad_obj_loss(tr, frames, n_fed, requant, sw, lam)
     # with requant both sides read the bytes of the GPU's own float32 predictions (tests/test_gpu_train_ext.py says why)
-    ref = _ref_obj(wts, ch, frames, lam, n_fed, requant, sw, fed=_fed_from(pred) if requant else None)
-    return (loss, pred, table, got, c_loss), ref
+    r = ref.run(wts, ch, frames, objective="error", layer_weights=lam, n_fed=n_fed, requant=requant, step_weights=sw,
+                fed=_fed_from(pred) if requant else None)
+    return (loss, pred, table, got, c_loss), (r.loss, r.grads, r.pred, r.table)
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -128,7 +57,7 @@ def test_error_objective_loss_table_predictions_and_every_gradient_match_float64
     lam = _lam(objective, len(ch))
     frames = _drifting(w + len(ch), 2, T_OBJ, ch[0], h, w)
     wts = weights.synthetic_prednet_weights(ch, w, h, seed=1)
-    (loss, pred, table, got, c_loss), (ref_loss, ref_g, ref_pred, ref_table, _) = _run_case(wts, ch, w, h, frames, lam, case)
+    (loss, pred, table, got, c_loss), (ref_loss, ref_g, ref_pred, ref_table) = _run_case(wts, ch, w, h, frames, lam, case)
     zero = [k for k, g in ref_g.items() if not np.any(g)]
     assert not zero, ("the reference gradient of these tensors is zero: the case checks nothing there", zero)
     print("%s %s: loss %.8f ref %.8f, max |pred diff| %.2e, table max rel err %.2e"
@@ -143,7 +72,8 @@ def test_error_objective_loss_table_predictions_and_every_gradient_match_float64
     if objective == "lall":
         # the upper-layer term cannot vanish unnoticed: against the L_0 reference this gradient is far outside the bound
         n_fed, requant, sw = CASES[case]
-        _, g0, _, _, _ = _ref_obj(wts, ch, frames, _lam("l0", len(ch)), n_fed, requant, sw, fed=_fed_from(pred) if requant else None)
+        g0 = ref.run(wts, ch, frames, objective="error", layer_weights=_lam("l0", len(ch)), n_fed=n_fed, requant=requant, step_weights=sw,
+                     fed=_fed_from(pred) if requant else None).grads
         assert _grads_differ(g0, got)
 
 
@@ -155,24 +85,13 @@ def test_random_weights_at_the_colour_shape_where_their_gradients_are_not_zero(c
     wts = _random_weights(ch, w, h, seed=2)
     for objective in ("l0", "lall"):
         lam = _lam(objective, len(ch))
-        (loss, pred, table, got, c_loss), (ref_loss, ref_g, ref_pred, ref_table, _) = _run_case(wts, ch, w, h, frames, lam, "self_fed_requant")
+        (loss, pred, table, got, c_loss), (ref_loss, ref_g, ref_pred, ref_table) = _run_case(wts, ch, w, h, frames, lam, "self_fed_requant")
         nonzero = sum(1 for g in ref_g.values() if np.any(g))
         assert nonzero == len(ref_g), (objective, nonzero, len(ref_g))
         assert np.abs(pred - ref_pred).max() <= 1e-5
         assert abs(loss - ref_loss) <= 1e-5 * ref_loss, (loss, ref_loss)
         assert _rel_close(table, ref_table), (table, ref_table)
         _check_grads(got, ref_g)
-
-
-def _loss_grad_ext(tr, d, n_fed, requant, sw):
-    """eigen_trainer_loss_grad_ext called directly: (loss, {name: grad})"""
-    B, T = int(d.shape[0]), int(d.shape[1])
-    loss = ctypes.c_double()
-    w_arr = None if sw is None else np.ascontiguousarray(sw, np.float64)
-    rc = tr.lib.eigen_trainer_loss_grad_ext(tr._h, ctypes.c_void_p(d.data_ptr()), ctypes.c_int64(T * int(np.prod(d.shape[2:]))), B, T, n_fed, int(requant), 1,
-                                            ctypes.c_void_p(None if w_arr is None else w_arr.ctypes.data), ctypes.byref(loss), None, None)
-    assert rc == 0
-    return loss.value, tr.grads()
 
 
 @pytest.mark.parametrize("sw", [None, [0.0, 1.0, 0.5, 2.0, 1.5]])
@@ -250,11 +169,6 @@ def test_one_table_from_evaluate_forward_backward_and_from_pieces(cuda, requant)
     with PredNetTrainer("synthetic:4", ch, w, h, B, 4) as tr:
         mse_small, ev_small = tr.evaluate(frames, n_fed=n_fed, requant=requant, layer_errors=True)
     assert np.array_equal(ev_small, one) and np.array_equal(mse_small, mse)
-
-
-def _same_weights(a, b):
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
 
 
 def test_training_under_l_all_is_reproducible_and_the_objective_is_not_trainer_state(cuda, tmp_path):

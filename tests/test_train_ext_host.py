@@ -1,59 +1,26 @@
-"""CPU: the host side of self-fed training, tape-free evaluation and trainer state -- the new C ABI
-entry points, the register metadata of the new training kernels (read from the built library as tests/test_train_host.py does)
-and the checkpoint npz layout."""
+"""CPU: the host side of self-fed training, tape-free evaluation and trainer state -- the register metadata
+of their kernels, the kernel list of tests/train_support.py against the header, and the checkpoint npz layout."""
 import os
 import re
 
 import numpy as np
 import pytest
 
-from tests import test_isa_stats as isa
+from tests.train_support import GRADIENT_KERNELS, STEP_KERNELS, TEMPLATED, TRAIN_KERNELS, check_no_scratch_and_no_spills
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_API = ["eigen_trainer_loss_grad_ext", "eigen_trainer_evaluate", "eigen_trainer_get_state", "eigen_trainer_set_state"]
-# every __global__ this change adds to csrc/train_kernels.h
-NEW_KERNELS = ["terr_fed_fwd_kernel", "tloss_step_partial_kernel", "tloss_step_final_kernel"]
-
-
-def test_new_entry_points_are_declared_exported_and_listed():
-    from evolutionary_illusion_generator_amd import engine
-    header = open(os.path.join(ROOT, "include", "eigen_engine.h")).read()
-    declared = set(re.findall(r"\b(eigen_[a-z_0-9]+)\s*\(", header))
-    assert "#define EIGEN_ABI_VERSION 4" in header
-    for name in NEW_API:
-        assert name in declared, name
-        assert name in engine.EXPORTS, name
-    if os.path.exists(engine.LIB_PATH):
-        lib = engine.load_library()
-        for name in NEW_API:
-            assert hasattr(lib, name), name
 
 
 def test_the_kernel_lists_name_every_global_of_the_header():
-    from tests.test_train_host import TRAIN_KERNELS
     src = open(os.path.join(ROOT, "evolutionary_illusion_generator_amd", "csrc", "train_kernels.h")).read()
     found = set(re.findall(r"__global__\s+void\s+(?:__launch_bounds__\(\w+\)\s+)?(\w+)\s*\(", src))
-    assert found == set(TRAIN_KERNELS) | set(NEW_KERNELS), found ^ (set(TRAIN_KERNELS) | set(NEW_KERNELS))
+    assert found == set(TRAIN_KERNELS), found ^ set(TRAIN_KERNELS)
+    assert len(TRAIN_KERNELS) == len(found) and not set(GRADIENT_KERNELS) & set(STEP_KERNELS) and set(TEMPLATED) <= found
 
 
-@pytest.fixture(scope="module")
-def stats():
-    if not os.path.exists(isa.LIB):
-        pytest.skip("libeigen_hip.so not built")
-    if not os.path.exists(isa.READELF):
-        pytest.skip("llvm-readelf not found")
-    return isa._kernel_stats()
-
-
-@pytest.mark.parametrize("kernel", NEW_KERNELS)
-def test_new_training_kernels_have_no_scratch_and_no_spills(stats, kernel):
-    names = [n for n in stats if re.match(r"_ZN4eigt\d+%s" % kernel, n)]
-    assert names, "%s not in the library" % kernel
-    for n in names:
-        for s in stats[n]:
-            assert s["private_segment_fixed_size"] == 0, (n, s)
-            assert s["vgpr_spill_count"] == 0, (n, s)
-            assert s["sgpr_spill_count"] == 0, (n, s)
+@pytest.mark.parametrize("kernel", STEP_KERNELS)
+def test_new_training_kernels_have_no_scratch_and_no_spills(kernel):
+    check_no_scratch_and_no_spills(kernel)
 
 
 def _state(ch, w, h, seed, batch=None):
