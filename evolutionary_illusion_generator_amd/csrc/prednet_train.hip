@@ -1,6 +1,6 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
-// the kernels of train_kernels.h.
+// the kernels of train_kernels.h and, for the frame gradient and the refinement of stills, frame_grad_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +12,7 @@
 
 #include "../../include/eigen_engine.h"
 #include "train_kernels.h"
+#include "frame_grad_kernels.h"
 
 using namespace eigt;
 
@@ -85,6 +86,7 @@ struct eigen_trainer {
     double *d_part = nullptr, *d_loss = nullptr;
     double *d_spart = nullptr, *d_step = nullptr;  // per-step loss: partials [max_steps][STEP_LOSS_BLOCKS], losses [max_steps]
     double* d_err = nullptr;                       // error-unit means err[s][l]: [max_steps][n_layers]
+    float* d_absmax = nullptr;                     // eigen_trainer_still_step: max |g| of every image, [max_batch]
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -230,6 +232,7 @@ int allocate(eigen_trainer* t)
     add((void**)&t->slab, t->slab_floats * 4);
     add((void**)&t->d_part, LOSS_BLOCKS * 8); add((void**)&t->d_loss, 8);
     add((void**)&t->d_spart, T * STEP_LOSS_BLOCKS * 8); add((void**)&t->d_step, T * 8); add((void**)&t->d_err, T * L * 8);
+    add((void**)&t->d_absmax, B * 4);
     for (int l = 0; l < L; ++l) {
         TLayer& y = t->ly[l];
         const long long CHW = y.CHW();
@@ -270,7 +273,7 @@ int copy_tables(eigen_trainer* t, int32_t n, bool to_device, float* d0, const fl
     return EIGEN_OK;
 }
 
-// argument rules shared by loss_grad_obj and evaluate_err; max_steps < 0: n_steps is not bounded
+// argument rules shared by loss_grad_frames and evaluate_err; max_steps < 0: n_steps is not bounded
 int check_call(const eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant, int32_t reset, int max_steps)
 {
     if (!t || !d_frames) return tfail(EIGEN_ERR_INVALID, "null argument");
@@ -473,7 +476,8 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
         if (l < L - 1) conv(st, t->ly[l + 1].dup, y.Ca, y.H, y.W, B, nullptr, 0, {src(G, 4 * CHW, 4 * y.C, 0, prm + p.x1, 1)});
     }
     // the error units, top down; layer 0 sends dE_0 into dP0_{s-1} under the mask E_0 > 0 on every step: on a teacher-forced
-    // step the other path ends in the frame, on a self-fed one in the constant fed-back value
+    // step the other path ends in the frame (frame_grad_step takes it from there when the call wants d loss / d frames), on a
+    // self-fed one in the constant fed-back value
     for (int l = L - 1; l >= 0; --l) {
         const TLayer& y = t->ly[l];
         const long long CHW = y.CHW();
@@ -490,6 +494,32 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
             conv(st, yb.dE, 2 * yb.C, yb.H, yb.W, B, nullptr, 1, {src(ZA, 4 * CHW, y.C, 0, prm + t->lp[l].aW, 1)});
         }
     }
+}
+
+// Where a call wants d loss / d frames: sample b, step s at p + b * bstride + s * tstride (floats); tstride == 0 is the tied mode,
+// one image per sample into which every step is added.  p == nullptr: not wanted.
+struct FrameGrad {
+    float* p = nullptr;
+    long long bstride = 0, tstride = 0;
+};
+
+// g_s of backward step s, after layer 0's terr_bwd of that step (dE_0 and E_0 of step s are what that kernel read): the input path on
+// a teacher-forced step, and the target path of term s - 1, whose prediction P0_{s-1} is state slot s
+void frame_grad_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, int n_fed, const uint8_t* d_frames, long long bstride, const FrameGrad& fg)
+{
+    const TLayer& y = t->ly[0];
+    const int B = o.B;
+    const long long CHW = y.CHW();
+    const float scale = s < 1 ? 0.f : o.by_error ? o.err_scale(s - 1, 0) : o.loss_scale(s - 1);
+    const int has_input = s < n_fed, has_target = s >= 1 && scale != 0.f;
+    float* out = fg.p + (long long)s * fg.tstride;
+    const int acc = fg.tstride == 0;
+    if (o.by_error)
+        ew(st, tframe_grad_kernel<1>, B * CHW, (const float*)y.dE, (const float*)y.E_at(s, B), (const float*)y.P_at(s, B), d_frames + (long long)s * CHW, bstride, scale,
+           has_input, has_target, CHW, (long long)B * CHW, out, fg.bstride, acc);
+    else
+        ew(st, tframe_grad_kernel<0>, B * CHW, (const float*)y.dE, (const float*)y.E_at(s, B), (const float*)y.P_at(s, B), d_frames + (long long)s * CHW, bstride, scale,
+           has_input, has_target, CHW, (long long)B * CHW, out, fg.bstride, acc);
 }
 
 // every weight gradient over the tape's T * B samples: dV, the gates and ZA hold the deltas the backward steps left there
@@ -623,14 +653,22 @@ int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n
     return copy_tables(t, n_tensors, false, t->grd, h_tensors);
 }
 
-int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
-                                int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
-                                double* h_layer_err, float* d_pred, void* stream)
+int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                   int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                   double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, void* stream)
 {
     int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, t ? t->cfg.max_steps : 0);
     if (rc) return rc;
     const int T = n_steps, B = batch;
     const long long C0HW = t->ly[0].CHW();
+    FrameGrad fg;
+    if (d_frame_grad) {
+        fg.p = d_frame_grad; fg.bstride = g_bstride; fg.tstride = g_tstride;
+        if (g_tstride != 0 && g_tstride < C0HW)
+            return tfail(EIGEN_ERR_INVALID, "g_tstride %lld is neither 0 (tied) nor at least a frame (%lld floats)", (long long)g_tstride, C0HW);
+        const long long extent = g_tstride == 0 ? C0HW : (long long)(T - 1) * g_tstride + C0HW;
+        if (g_bstride < extent) return tfail(EIGEN_ERR_INVALID, "g_bstride %lld is smaller than one sample's gradient (%lld floats)", (long long)g_bstride, extent);
+    }
     Objective o;
     rc = make_objective(t, objective, h_layer_w, h_step_w, T, B, o);
     if (rc) return rc;
@@ -646,12 +684,44 @@ int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64
     // backward through time, from zero carries
     for (int l = 0; l < t->L; ++l)
         for (float* a : {t->ly[l].dPn, t->ly[l].dhc, t->ly[l].dc}) TCHK(hipMemsetAsync(a, 0, B * t->ly[l].CHW() * 4, st));
-    for (int s = T - 1; s >= 0; --s) backward_step(t, st, o, s, d_frames, bstride);
+    // the tied frame gradient starts from zero; only the C0 H W floats of every sample are touched, whatever g_bstride is
+    for (int b = 0; fg.p && fg.tstride == 0 && b < B; ++b) TCHK(hipMemsetAsync(fg.p + b * fg.bstride, 0, C0HW * 4, st));
+    for (int s = T - 1; s >= 0; --s) {
+        backward_step(t, st, o, s, d_frames, bstride);
+        if (fg.p) frame_grad_step(t, st, o, s, n_fed, d_frames, bstride, fg);
+    }
     weight_gradients(t, st, T, B);
     TCHK(hipGetLastError());
     t->state_batch = B;
     t->state_slot = T;
     return read_loss(t, st, o, want_table, h_loss, h_layer_err);
+}
+
+int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                double* h_layer_err, float* d_pred, void* stream)
+{
+    return eigen_trainer_loss_grad_frames(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_w, objective, h_layer_w, h_loss, h_layer_err, d_pred,
+                                          nullptr, 0, 0, stream);
+}
+
+int eigen_trainer_still_step(eigen_trainer* t, uint8_t* d_images, const float* d_grad, int64_t g_bstride, const uint8_t* d_mask, double step_bytes,
+                             int32_t batch, void* stream)
+{
+    if (!t || !d_images || !d_grad) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!std::isfinite(step_bytes) || !(step_bytes > 0.0)) return tfail(EIGEN_ERR_INVALID, "step_bytes %g: the step must be finite and > 0", step_bytes);
+    if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
+    if (batch > t->cfg.max_batch) return tfail(EIGEN_ERR_CAPACITY, "batch %d exceeds the trainer's %d", batch, t->cfg.max_batch);
+    const TLayer& y = t->ly[0];
+    const long long C0HW = y.CHW();
+    if (g_bstride < C0HW) return tfail(EIGEN_ERR_INVALID, "g_bstride %lld is smaller than one image (%lld floats)", (long long)g_bstride, C0HW);
+    TCHK(hipSetDevice(t->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const float k = (float)(step_bytes / 255.0);
+    hipLaunchKernelGGL(tstill_absmax_kernel, dim3(batch), dim3(EW_T), 0, st, d_grad, (long long)g_bstride, d_mask, (int)y.HW, C0HW, t->d_absmax);
+    ew(st, tstill_step_kernel, batch * C0HW, d_images, d_grad, (long long)g_bstride, d_mask, (const float*)t->d_absmax, k, (int)y.HW, C0HW, (long long)batch * C0HW);
+    TCHK(hipGetLastError());
+    return EIGEN_OK;
 }
 
 int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,

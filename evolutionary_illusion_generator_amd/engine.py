@@ -22,7 +22,8 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_get_timings", "eigen_conv_profile", "eigen_debug_corners", "eigen_debug_dense_flow", "eigen_prednet_flops_per_step", "eigen_flatten_genomes", "eigen_plan_text",
            "eigen_trainer_create", "eigen_trainer_destroy", "eigen_trainer_set_weights", "eigen_trainer_get_weights", "eigen_trainer_loss_grad",
            "eigen_trainer_get_grads", "eigen_trainer_adam", "eigen_trainer_tape_bytes", "eigen_trainer_loss_grad_ext", "eigen_trainer_evaluate",
-           "eigen_trainer_get_state", "eigen_trainer_set_state", "eigen_trainer_loss_grad_obj", "eigen_trainer_evaluate_err"]
+           "eigen_trainer_get_state", "eigen_trainer_set_state", "eigen_trainer_loss_grad_obj", "eigen_trainer_evaluate_err",
+           "eigen_trainer_loss_grad_frames", "eigen_trainer_still_step"]
 
 
 class EigenConfig(ctypes.Structure):

@@ -33,6 +33,9 @@ def _bind(lib):
     lib.eigen_trainer_loss_grad_obj.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.eigen_trainer_loss_grad_frames.argtypes = lib.eigen_trainer_loss_grad_obj.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
+    lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
+                                             ctypes.c_void_p]
     lib.eigen_trainer_evaluate_err.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
@@ -47,6 +50,7 @@ def _bind(lib):
 HYPER = ("alpha", "beta1", "beta2", "eps")
 SEQ_PARTS = ("h", "c", "P")
 OBJECTIVES = {"mse": 0, "error": 1}  # eigen_objective
+FRAME_GRADS = (None, "frames", "tied")
 
 
 def check_layer_weights(layer_weights, n_layers):
@@ -268,8 +272,40 @@ class PredNetTrainer:
         tab = np.zeros((max(int(d.shape[1]) - 1, 1), len(self.channels)), np.float64) if table else None
         return tab, self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
 
+    def _loss_grad(self, d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights, layer_errors, frame_grads):
+        """The call behind forward_backward, on frames already on the device: (loss, table or None, d_pred or None, d_grad or None), the
+        last two device tensors.  Every argument is checked before anything is launched."""
+        torch = self._torch
+        if objective not in OBJECTIVES:
+            raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
+        lam = check_layer_weights(layer_weights, len(self.channels))
+        w_arr = None
+        if step_weights is not None:
+            w_arr = np.ascontiguousarray(step_weights, dtype=np.float64)
+            if w_arr.shape != (T - 1,):
+                raise ValueError("step_weights must have T - 1 = %d entries, got shape %s" % (T - 1, w_arr.shape))
+        loss = ctypes.c_double(0.0)
+        by_error = objective == "error"
+        table, d_pred = self._outputs(d, layer_errors or by_error, pred)
+        args = [self._h, _ptr(d), bstride, ctypes.c_int32(n), ctypes.c_int32(T), ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))),
+                ctypes.c_int32(int(bool(reset))), ctypes.c_void_p(w_arr.ctypes.data if w_arr is not None and w_arr.size else None),
+                ctypes.c_int32(OBJECTIVES[objective]), _ptr(lam), ctypes.byref(loss), _ptr(table), _ptr(d_pred)]
+        d_grad = None
+        if frame_grads is None:
+            _check(self.lib.eigen_trainer_loss_grad_obj(*args, _stream_arg(stream)))
+        else:
+            img = tuple(d.shape[2:])
+            d_grad = torch.empty((n,) + (() if frame_grads == "tied" else (T,)) + img, dtype=torch.float32, device=d.device)
+            per = int(np.prod(img))
+            g_b, g_t = (per, 0) if frame_grads == "tied" else (T * per, per)
+            _check(self.lib.eigen_trainer_loss_grad_frames(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), _stream_arg(stream)))
+        if table is not None:
+            table = table[:T - 1]
+        value = combine_terms(table, lam, w_arr if w_arr is not None and w_arr.size else None) if by_error else loss.value
+        return value, table, d_pred, d_grad
+
     def forward_backward(self, frames, reset=True, pred=False, stream=None, n_fed=None, requant=False, step_weights=None, objective="mse",
-                         layer_weights=None, layer_errors=False):
+                         layer_weights=None, layer_errors=False, frame_grads=None):
         """Loss of frames uint8 [n, T, C, H, W] (numpy or a device tensor, n <= batch) and the gradients, kept on the device
         (``grads()``).  reset=False continues from the state the previous call left (the same n), as a constant.
         pred=True also returns the float predictions P0 [n, T, C, H, W] (numpy).
@@ -282,28 +318,18 @@ class PredNetTrainer:
         the error units err[s][l] (layer 0 against the true next frame, half the mean absolute error; layers above as the
         network computed them at step s + 1) weighted by layer_weights, one weight >= 0 per layer: None is L_0, [1, 0, ...];
         L_all is [1, 0.1, ...].  The loss is ``combine_terms`` of the table.  layer_errors=True appends the float64 [T - 1, L]
-        table to the return value, under either objective."""
+        table to the return value, under either objective.
+
+        frame_grads: None, or the gradient of the loss by the frames (as floats, byte / 255), appended last as a float32 numpy
+        array: "frames" gives d loss / d frame t, [n, T, C, H, W] (the input path of every step that read its frame plus the
+        target path of every frame but the first); "tied" gives their sum over t, [n, C, H, W], the gradient by a still that
+        is repeated T times.  Nothing else the call returns or leaves on the device changes."""
+        if frame_grads not in FRAME_GRADS:
+            raise ValueError("frame_grads must be None, 'frames' or 'tied', got %r" % (frame_grads,))
         d, n, T, n_fed, bstride = self._call_args(frames, n_fed)
-        if objective not in OBJECTIVES:
-            raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
-        lam = check_layer_weights(layer_weights, len(self.channels))
-        w_arr = None
-        if step_weights is not None:
-            w_arr = np.ascontiguousarray(step_weights, dtype=np.float64)
-            if w_arr.shape != (T - 1,):
-                raise ValueError("step_weights must have T - 1 = %d entries, got shape %s" % (T - 1, w_arr.shape))
-        loss = ctypes.c_double(0.0)
-        by_error = objective == "error"
-        table, d_pred = self._outputs(d, layer_errors or by_error, pred)
-        _check(self.lib.eigen_trainer_loss_grad_obj(self._h, _ptr(d), bstride, ctypes.c_int32(n), ctypes.c_int32(T), ctypes.c_int32(n_fed),
-                                                    ctypes.c_int32(int(bool(requant))), ctypes.c_int32(int(bool(reset))),
-                                                    ctypes.c_void_p(w_arr.ctypes.data if w_arr is not None and w_arr.size else None),
-                                                    ctypes.c_int32(OBJECTIVES[objective]), _ptr(lam), ctypes.byref(loss), _ptr(table), _ptr(d_pred),
-                                                    _stream_arg(stream)))
-        if table is not None:
-            table = table[:T - 1]
-        value = combine_terms(table, lam, w_arr if w_arr is not None and w_arr.size else None) if by_error else loss.value
-        out = (value,) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table,) if layer_errors else ())
+        value, table, d_pred, d_grad = self._loss_grad(d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights,
+                                                       layer_errors, frame_grads)
+        out = (value,) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table,) if layer_errors else ()) + ((d_grad.cpu().numpy(),) if frame_grads else ())
         return out[0] if len(out) == 1 else out
 
     def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False, layer_errors=False):
@@ -395,4 +421,59 @@ class PredNetTrainer:
         self.close()
 
 
-__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms"]
+def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, requant=True, objective="mse", layer_weights=None, step_weights=None,
+                  mask=None):
+    """Gradient ascent on stills: raise how far PredNet's extended prediction leaves a still, the differentiable stand-in for the
+    fitness (which scores the flow between the still and that prediction).  -> (uint8 [n, C, H, W] numpy, float64 [iters + 1]).
+
+    images: uint8 [n, C, H, W] (numpy or a device tensor, n <= the trainer's batch); they are not modified.  Per iteration the
+    frames are the image repeated T = n_repeat + n_ext times, the first n_repeat steps read it and the last n_ext are self-fed
+    (requant: through the byte, as the fitness path feeds them), the targets are the still on every step, and the loss is
+    `objective` under step_weights (None: 0 for the terms s < n_repeat - 1, 1 for the n_ext terms of the extension).  One call
+    with reset=True gives the loss and its tied frame gradient; ``eigen_trainer_still_step`` then moves every free pixel by at
+    most `step` bytes along the gradient, normalised by the image's largest |g| over the free pixels.  mask: [H, W], zero keeps
+    a pixel as it is (None: every pixel is free).  Everything stays on the device between iterations.
+
+    history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images.  The calls
+    OVERWRITE the trainer's weight gradients and its kept sequence state."""
+    T = int(n_repeat) + int(n_ext)
+    if n_repeat < 1 or n_ext < 1 or iters < 0:
+        raise ValueError("n_repeat >= 1, n_ext >= 1 and iters >= 0 required")
+    if T > trainer.max_steps:
+        raise ValueError("n_repeat + n_ext = %d frames exceed the trainer's max_steps %d" % (T, trainer.max_steps))
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError("step must be finite and > 0, got %r" % (step,))
+    if step_weights is None:
+        step_weights = [0.0] * (n_repeat - 1) + [1.0] * n_ext
+    torch = trainer._torch
+    if isinstance(images, torch.Tensor):
+        img = images.detach().to("cuda:%d" % trainer.device).clone()
+    else:
+        img = torch.from_numpy(np.ascontiguousarray(images)).cuda(trainer.device)
+    if img.dtype != torch.uint8 or img.dim() != 4 or tuple(img.shape[1:]) != (trainer.channels[0], trainer.h, trainer.w):
+        raise ValueError("images must be uint8 [n, %d, %d, %d], got %s %s" % (trainer.channels[0], trainer.h, trainer.w, img.dtype, tuple(img.shape)))
+    img = img.contiguous()
+    n, per = int(img.shape[0]), int(np.prod(img.shape[1:]))
+    d_mask = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != (trainer.h, trainer.w):
+            raise ValueError("mask must be [%d, %d], got %s" % (trainer.h, trainer.w, m.shape))
+        d_mask = torch.from_numpy(m).cuda(trainer.device)
+
+    def loss_of(frame_grads):
+        d = img[:, None].expand(n, T, *img.shape[1:]).contiguous()
+        value, _, _, d_grad = trainer._loss_grad(d, n, T, n_repeat, ctypes.c_int64(T * per), True, False, None, requant, step_weights, objective,
+                                                 layer_weights, False, frame_grads)
+        return value, d_grad
+
+    history = np.zeros(iters + 1, np.float64)
+    for i in range(iters):
+        history[i], d_grad = loss_of("tied")
+        _check(trainer.lib.eigen_trainer_still_step(trainer._h, _ptr(img), _ptr(d_grad), ctypes.c_int64(per), _ptr(d_mask), ctypes.c_double(float(step)),
+                                                    ctypes.c_int32(n), None))
+    history[iters], _ = loss_of(None)
+    return img.cpu().numpy(), history
+
+
+__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills"]

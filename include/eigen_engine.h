@@ -340,6 +340,32 @@ int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64
                                 int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
                                 const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, void* stream);
 
+/* eigen_trainer_loss_grad_obj plus d loss / d frames ("Frame gradients").  d_frame_grad NULL: exactly
+ * eigen_trainer_loss_grad_obj, which is this call with NULL, 0, 0: the same launches, the same bits.
+ *   d_frame_grad: device float; g_t = d loss / d x_t of sample b, step t at d_frame_grad + b * g_bstride + t * g_tstride as [C][H][W],
+ *     strides in floats, x_t = (float)byte / 255.0f.  g_t is the sum of the input path (steps t < n_fed: dA of the image layer's
+ *     error unit, relu'(0) = 0) and the target path (t >= 1: frame t is the target of term t - 1 under either objective, on
+ *     self-fed steps too; sign(0) = 0; a term whose weight is zero adds nothing).  Frame 0 of a call has no target path.
+ *   g_tstride == 0: tied, for a still repeated n_steps times: one image per sample, cleared by the call, then g_t added in
+ *     float in the order t = n_steps - 1 .. 0.  Otherwise g_tstride >= C*H*W.  g_bstride >= the extent of one sample (C*H*W tied,
+ *     (n_steps - 1) * g_tstride + C*H*W otherwise).  Floats between the images are never written.
+ * Everything else the call returns (loss, table, predictions, weight gradients, kept state) is what it returns without d_frame_grad.
+ * Errors: as eigen_trainer_loss_grad_obj; EIGEN_ERR_INVALID for a g_tstride in [1, C*H*W - 1] or < 0, or too small a g_bstride. */
+int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                   int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                   const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                   int64_t g_bstride, int64_t g_tstride, void* stream);
+
+/* One normalised ascent step on uint8 stills d_images [batch][C][H][W], in place, from a tied gradient (image b at d_grad + b *
+ * g_bstride floats): per image m_b = max |g| over the pixels the mask keeps free, then x = byte / 255.0f,
+ * x' = min(max(x + k * (g / m_b), 0), 1) with k = (float)(step_bytes / 255.0), byte' = (uint8_t)(int)(x' * 255.0f + 0.5f), each one
+ * float operation.  d_mask: uint8 [H][W] shared by the channels, 0 = keep the pixel's byte, or NULL: every pixel moves.  An image
+ * with m_b == 0 is left as it is.  No byte moves by more than ceil(step_bytes).
+ * Errors: EIGEN_ERR_INVALID a NULL image or gradient, step_bytes not finite or <= 0, batch < 1, g_bstride < C*H*W;
+ * EIGEN_ERR_CAPACITY batch above max_batch. */
+int eigen_trainer_still_step(eigen_trainer* t, uint8_t* d_images, const float* d_grad, int64_t g_bstride, const uint8_t* d_mask,
+                             double step_bytes, int32_t batch, void* stream);
+
 /* eigen_trainer_loss_grad_obj with objective = EIGEN_OBJ_MSE, h_layer_w = NULL, h_layer_err = NULL. */
 int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
                                 int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, double* h_loss,

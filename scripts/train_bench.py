@@ -4,9 +4,11 @@
 the tape-free evaluate of that call.  Prints one JSON line per side and writes profiles/train_bench.json.
 
     python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both] [--objective mse|l0|lall]
+    python scripts/train_bench.py --frame-grads [--steps 5] [--warmup 2]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
-side is always the squared error.
+side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
+per-frame and with tied ones, every output left on the device; one JSON line each.
 """
 import argparse
 import json
@@ -96,6 +98,38 @@ def run_ext(steps, warmup, n_self=5):
     return out
 
 
+def run_frame_grads(steps, warmup):
+    """ms per eigen_trainer_loss_grad_frames call with d_frame_grad NULL (the call eigen_trainer_loss_grad_obj is), with a per-frame
+    buffer and with a tied one"""
+    import ctypes
+    import torch
+    from evolutionary_illusion_generator_amd import weights
+    from evolutionary_illusion_generator_amd.train import PredNetTrainer
+    d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
+    per = CH[0] * H * W
+    out = []
+    with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
+        for side, shape, g_b, g_t in (("loss_grad", None, 0, 0), ("loss_grad_frames", (B, T, per), T * per, per), ("loss_grad_tied", (B, per), per, 0)):
+            buf = None if shape is None else torch.zeros(shape, dtype=torch.float32, device="cuda")
+            loss = ctypes.c_double()
+
+            def call():
+                rc = tr.lib.eigen_trainer_loss_grad_frames(tr._h, ctypes.c_void_p(d.data_ptr()), T * per, B, T, T, 0, 1, None, 0, None, ctypes.byref(loss), None, None,
+                                                           None if buf is None else ctypes.c_void_p(buf.data_ptr()), g_b, g_t, None)
+                assert rc == 0, rc
+
+            for _ in range(warmup):
+                call()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                call()
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3 / steps
+            out.append(dict(side=side, call_ms=ms, loss=loss.value, grad_norm=None if buf is None else float(buf.double().norm())))
+    return out
+
+
 def run_torch(steps, warmup):
     import torch
     import torch.nn.functional as F
@@ -157,11 +191,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
     ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall"], help="the trainer side's objective")
+    ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
     a = ap.parse_args()
     if a.side == "torch":
         print(json.dumps(run_torch(a.steps, a.warmup)))
+        return
+    if a.frame_grads:
+        for r in run_frame_grads(a.steps, a.warmup):
+            print(json.dumps(r), flush=True)
         return
     res = [run_trainer(a.steps, a.warmup, a.objective)]
     print(json.dumps(res[0]), flush=True)
