@@ -25,7 +25,7 @@ def _error_pair(a, p):
 
 
 def run(weights, channels, frames, *, objective="mse", layer_weights=None, n_fed=None, requant=False, step_weights=None, state=None,
-        fed=None):
+        fed=None, dtype=torch.float64):
     """float64 autograd PredNet over frames uint8 [B, T, C, H, W] from `state` (detached (h, c, P), or zeros).
 
     Steps t < n_fed read frame t (None: all do); steps t >= n_fed are fed the previous prediction -- itself (requant False: part
@@ -35,22 +35,24 @@ def run(weights, channels, frames, *, objective="mse", layer_weights=None, n_fed
     TRUE frame on every step; table[s][l > 0] = mean of E_l of step s + 1.
     objective "mse": loss = sum_s w_s step_mse[s] / sum_s w_s; "error": loss = sum_s w_s sum_l lam_l table[s][l] / sum_s w_s,
     with w = step_weights (None: all one) and lam = layer_weights (None: L_0, [1, 0, ...]).  T = 1 has no term: loss 0, zero
-    gradients."""
+    gradients.
+    dtype=torch.float32 runs the same statement in float32 (results are still returned as float64 arrays): the yardstick of what
+    float32 arithmetic alone costs, which tests/train_support.py `_check_grads` takes its element-wise bound from."""
     if objective not in ("mse", "error"):
         raise ValueError("objective must be 'mse' or 'error', got %r" % (objective,))
     ch, L = list(channels), len(channels)
-    p = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in weights.items()}
-    x = torch.from_numpy(frames.astype(np.float32) / np.float32(255.0)).double()
+    p = {k: torch.tensor(np.asarray(v, np.float64), dtype=dtype, requires_grad=True) for k, v in weights.items()}
+    x = torch.from_numpy(frames.astype(np.float32) / np.float32(255.0)).to(dtype)
     B, T = frames.shape[:2]
     H, W = frames.shape[3:]
     n_fed = T if n_fed is None else n_fed
     w_s = [1.0] * (T - 1) if step_weights is None else [float(v) for v in step_weights]
     lam = [1.0] + [0.0] * (L - 1) if layer_weights is None else [float(v) for v in layer_weights]
     if state is None:
-        z = lambda l: torch.zeros(B, ch[l], H >> l, W >> l, dtype=torch.float64)
+        z = lambda l: torch.zeros(B, ch[l], H >> l, W >> l, dtype=dtype)
         hs, cs, Ps = [z(l) for l in range(L)], [z(l) for l in range(L)], [z(l) for l in range(L)]
     else:
-        hs, cs, Ps = [list(s) for s in state]
+        hs, cs, Ps = [[v.to(dtype) for v in s] for s in state]
     conv = lambda a, wt, b=None: F.conv2d(a, wt, b, padding=1)
     preds, mses = [], []
     err = [[None] * L for _ in range(T - 1)]
@@ -58,7 +60,7 @@ def run(weights, channels, frames, *, objective="mse", layer_weights=None, n_fed
         if t < n_fed:
             xin = x[:, t]
         elif requant:
-            xin = torch.from_numpy(np.asarray(fed[:, t], np.float32)).double()
+            xin = torch.from_numpy(np.asarray(fed[:, t], np.float32)).to(dtype)
         else:
             xin = Ps[0]
         E = [None] * L
@@ -94,8 +96,8 @@ def run(weights, channels, frames, *, objective="mse", layer_weights=None, n_fed
         loss = float(loss.detach())
     else:
         loss, g = 0.0, [None] * len(names)
-    grads = {n: (gg.numpy() if gg is not None else np.zeros(p[n].shape)) for n, gg in zip(names, g)}
+    grads = {n: (gg.double().numpy() if gg is not None else np.zeros(p[n].shape)) for n, gg in zip(names, g)}
     table = np.array([[float(e.detach()) for e in row] for row in err]).reshape(T - 1, L)
     step_mse = np.array([float(m.detach()) for m in mses])
     state = tuple([s.detach() for s in ss] for ss in (hs, cs, Ps))
-    return Result(loss, grads, torch.stack(preds, 1).detach().numpy(), step_mse, table, state)
+    return Result(loss, grads, torch.stack(preds, 1).detach().double().numpy(), step_mse, table, state)

@@ -10,24 +10,57 @@ from evolutionary_illusion_generator_amd import engine, fitness, weights
 from evolutionary_illusion_generator_amd.engine import EngineError
 from evolutionary_illusion_generator_amd.train import PredNetTrainer, TrainerConfig
 from oracle import prednet_train_ref as ref
-from tests.train_support import SHAPES, _check_grads, _drifting, _weight_sets
+from tests.train_support import (SHAPES, WSETS, _check_grads, _drifting, case_frames, case_id, case_reference, case_weights, cases, is_all_zero,
+                                 select)
 
 pytestmark = pytest.mark.gpu
 
 
+def _teacher_forced(c):
+    """one teacher-forced squared-error call of the trainer against the reference: predictions, loss and every gradient"""
+    wts, frames = case_weights(c.w, c.h, c.ch, c.wset), case_frames(c)
+    with PredNetTrainer(wts, list(c.ch), c.w, c.h, c.B + c.room[0], c.T + c.room[1]) as tr:
+        loss, pred = tr.forward_backward(frames, pred=True)
+        got = tr.grads()
+    r = case_reference(c)
+    assert np.abs(pred - r.pred).max() <= 1e-5, (case_id(c), np.abs(pred - r.pred).max())
+    assert abs(loss - r.loss) <= 1e-5 * r.loss, (case_id(c), loss, r.loss)
+    if is_all_zero(c):
+        # P0 sits at the clamp everywhere: the reference gradient of every tensor is exactly zero, and so is the trainer's
+        assert all(not g.any() for g in r.grads.values()) and all(not g.any() for g in got.values()), case_id(c)
+    worst = _check_grads(got, r.grads, zero_allowed=is_all_zero(c), what=case_id(c))
+    print("%s: error / bound %.4f in norm, %.4f element-wise" % (case_id(c), worst[0], worst[1]))
+
+
 @pytest.mark.parametrize("w,h,ch", SHAPES)
 def test_forward_loss_and_every_gradient_match_float64_autograd(cuda, w, h, ch):
-    B, T = 2, 5
-    frames = _drifting(w + len(ch), B, T, ch[0], h, w)
-    for label, wts in _weight_sets(ch, w, h):
-        with PredNetTrainer(wts, ch, w, h, B, T) as tr:
-            loss, pred = tr.forward_backward(frames, pred=True)
+    todo = select("teacher_forced", w, h, ch)
+    assert [c.wset for c in todo] == WSETS and all((c.B, c.T) == (2, 5) for c in todo)
+    for c in todo:
+        _teacher_forced(c)
+
+
+@pytest.mark.parametrize("c", cases("teacher_forced", wide=True), ids=case_id)
+def test_every_gradient_matches_at_the_wide_shapes(cuda, c):
+    """The MT = 4 tiles, gridDim.y > 1, partial M tiles, pixel counts off a multiple of 4 and a handle larger than the call
+    (tests/train_support.py TILE_PROPERTIES)."""
+    _teacher_forced(c)
+
+
+@pytest.mark.parametrize("w,h,ch", [s for s in SHAPES if s[2][0] == 1])
+def test_weights_that_saturate_every_prediction_give_exactly_zero_gradients(cuda, w, h, ch):
+    """The random set at the gray shapes: every pixel of P0 at the clamp on every step, so no gradient reaches a weight under the
+    squared error, teacher-forced or self-fed.  Exact zeros, not small numbers: whatever the kernels add up is a sum of zeros."""
+    todo = [c for c in select("teacher_forced", w, h, ch, wset="random") + select("self_fed", w, h, ch, wset="random", requant=False, sw=None)]
+    assert len(todo) == 2 and all(is_all_zero(c) for c in todo)
+    for c in todo:
+        wts, frames = case_weights(c.w, c.h, c.ch, c.wset), case_frames(c)
+        with PredNetTrainer(wts, list(c.ch), c.w, c.h, c.B, c.T) as tr:
+            loss, pred = tr.forward_backward(frames, pred=True, n_fed=c.n_fed)
             got = tr.grads()
-        r = ref.run(wts, ch, frames)
-        ref_loss, ref_g, ref_pred = r.loss, r.grads, r.pred
-        assert np.abs(pred - ref_pred).max() <= 1e-5, (label, np.abs(pred - ref_pred).max())
-        assert abs(loss - ref_loss) <= 1e-5 * ref_loss, (label, loss, ref_loss)
-        _check_grads(got, ref_g)
+        assert loss > 0 and ((pred == 0) | (pred == 1)).all()
+        for k, g in got.items():
+            assert not g.any(), (case_id(c), k)
 
 
 @pytest.mark.parametrize("w,h,ch", SHAPES[1:])

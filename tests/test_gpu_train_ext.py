@@ -12,14 +12,34 @@ from evolutionary_illusion_generator_amd import engine, fitness, weights
 from evolutionary_illusion_generator_amd.engine import EngineError
 from evolutionary_illusion_generator_amd.train import PredNetTrainer
 from oracle import prednet_train_ref as ref
-from tests.train_support import SHAPES, _check_grads, _drifting, _fed_from, _grads_differ, _same_weights, _weight_sets
+from tests.train_support import (N_FED, SHAPES, STEP_WEIGHTS, T_SELF as T_EXT, WSETS, _check_grads, _drifting, _grads_differ, _same_weights, _weight_sets,
+                                 case_frames, case_id, case_reference, case_weights, cases, is_all_zero, select)
 
 pytestmark = pytest.mark.gpu
 
 
-T_EXT, N_FED = 6, 3
 # term s is prediction s against frame s + 1; steps 3, 4, 5 are self-fed
-STEP_WEIGHTS = {"ones": None, "leading_zero": [0.0, 1.0, 0.5, 2.0, 1.5], "self_fed_only": [0.0, 0.0, 0.0, 1.0, 1.0]}
+
+
+def _self_fed(c):
+    """One self-fed squared-error call against the reference.  Returns what the caller's own checks need."""
+    wts, frames = case_weights(c.w, c.h, c.ch, c.wset), case_frames(c)
+    sw = None if c.sw is None else list(c.sw)
+    with PredNetTrainer(wts, list(c.ch), c.w, c.h, c.B + c.room[0], c.T + c.room[1]) as tr:
+        loss, pred = tr.forward_backward(frames, pred=True, n_fed=c.n_fed, requant=c.requant, step_weights=sw)
+        got = tr.grads()
+        loss2, pred2 = tr.forward_backward(frames, pred=True, n_fed=c.n_fed, requant=c.requant, step_weights=sw)
+        got2 = tr.grads()
+    r = case_reference(c, pred=pred)
+    print("%s: loss %.8f ref %.8f, max |pred diff| %.2e" % (case_id(c), loss, r.loss, np.abs(pred - r.pred).max()))
+    assert np.abs(pred - r.pred).max() <= 1e-5, (case_id(c), np.abs(pred - r.pred).max())
+    assert abs(loss - r.loss) <= 1e-5 * r.loss, (case_id(c), loss, r.loss)
+    worst = _check_grads(got, r.grads, zero_allowed=is_all_zero(c), what=case_id(c))
+    print("  error / bound %.4f in norm, %.4f element-wise" % worst)
+    # the same call twice gives the same bits
+    assert loss2 == loss and np.array_equal(pred, pred2)
+    assert all(np.array_equal(got[k], got2[k]) for k in got)
+    return wts, frames, sw, pred, r
 
 
 @pytest.mark.parametrize("wkey", list(STEP_WEIGHTS))
@@ -29,40 +49,30 @@ def test_self_fed_loss_predictions_and_every_gradient_match_float64_autograd(cud
     """A prediction on a byte boundary can quantise differently in float32 and in the float64 restatement, so with requant the
     restatement is fed the bytes of the GPU's own float32 predictions of the previous step: both sides read the same constants,
     and the comparison is of the network and its gradient, not of one rounding."""
-    B = 2
-    sw = STEP_WEIGHTS[wkey]
-    frames = _drifting(w + len(ch), B, T_EXT, ch[0], h, w)
-    for label, wts in _weight_sets(ch, w, h):
-        with PredNetTrainer(wts, ch, w, h, B, T_EXT) as tr:
-            loss, pred = tr.forward_backward(frames, pred=True, n_fed=N_FED, requant=requant, step_weights=sw)
-            got = tr.grads()
-            loss2, pred2 = tr.forward_backward(frames, pred=True, n_fed=N_FED, requant=requant, step_weights=sw)
-            got2 = tr.grads()
-        r = ref.run(wts, ch, frames, n_fed=N_FED, requant=requant, step_weights=sw, fed=_fed_from(pred) if requant else None)
-        ref_loss, ref_g, ref_pred = r.loss, r.grads, r.pred
-        print("%s requant=%d %s: loss %.8f ref %.8f, max |pred diff| %.2e" % (label, requant, wkey, loss, ref_loss, np.abs(pred - ref_pred).max()))
-        assert np.abs(pred - ref_pred).max() <= 1e-5, (label, np.abs(pred - ref_pred).max())
-        assert abs(loss - ref_loss) <= 1e-5 * ref_loss, (label, loss, ref_loss)
-        _check_grads(got, ref_g)
-        # the same call twice gives the same bits
-        assert loss2 == loss and np.array_equal(pred, pred2)
-        assert all(np.array_equal(got[k], got2[k]) for k in got)
+    todo = select("self_fed", w, h, ch, requant=requant, sw=STEP_WEIGHTS[wkey])
+    assert [c.wset for c in todo] == WSETS and all((c.B, c.T, c.n_fed) == (2, T_EXT, N_FED) for c in todo)
+    for c in todo:
+        wts, frames, sw, pred, r = _self_fed(c)
         if requant:
             # the error-unit term counts: without it (requant = 0 semantics) the restatement's own gradient is another one
-            # (the random set at the two gray shapes drives P0 into the clamp everywhere: every gradient is exactly zero with
-            # either feedback, so the comparison is made wherever the float-feedback gradient is not zero; the synthetic set
-            # has one at every shape)
+            # (the dead cases aside, where every gradient is exactly zero with either feedback)
             g0 = ref.run(wts, ch, frames, n_fed=N_FED, requant=False, step_weights=sw).grads
-            assert label == "random" or any(np.any(g) for g in g0.values())
-            if any(np.any(g) for g in g0.values()):
-                assert _grads_differ(ref_g, g0), label
+            assert is_all_zero(c) == (not any(np.any(g) for g in g0.values()))
+            if not is_all_zero(c):
+                assert _grads_differ(r.grads, g0), case_id(c)
         else:
             # float feedback: E_0 of a self-fed step is exactly zero, so the prediction of a self-fed step does not depend on its frame
             other = frames.copy()
             other[:, N_FED:] = 255 - other[:, N_FED:]
-            with PredNetTrainer(wts, ch, w, h, B, T_EXT) as tr:
+            with PredNetTrainer(wts, ch, w, h, c.B, T_EXT) as tr:
                 _, pred3 = tr.forward_backward(other, pred=True, n_fed=N_FED)
             assert np.array_equal(pred, pred3)
+
+
+@pytest.mark.parametrize("c", cases("self_fed", wide=True), ids=case_id)
+def test_self_fed_gradients_match_at_the_wide_shapes(cuda, c):
+    """tests/train_support.py TILE_PROPERTIES: the tiles real channel counts use, under self-fed steps"""
+    _self_fed(c)
 
 
 @pytest.mark.parametrize("w,h,ch", SHAPES)

@@ -12,14 +12,13 @@ from evolutionary_illusion_generator_amd import weights
 from evolutionary_illusion_generator_amd.engine import EngineError
 from evolutionary_illusion_generator_amd.train import PredNetTrainer, combine_terms
 from oracle import prednet_train_ref as ref
-from tests.train_support import (SHAPES, _check_grads, _drifting, _fed_from, _grads_differ, _loss_grad_ext, _loss_grad_obj_loss, _random_weights,
-                                 _same_weights)
+from tests.train_support import (N_FED, OBJ_CALLS as CASES, SHAPES, T_SELF as T_OBJ, _check_grads, _drifting, _grads_differ, _loss_grad_ext, _loss_grad_obj_loss,
+                                 _same_weights, case_frames, case_id, case_reference, case_weights, cases, lam_of, select)
 
 pytestmark = pytest.mark.gpu
 
 
-def _lam(name, L):
-    return {"l0": [1.0] + [0.0] * (L - 1), "lall": [1.0] + [0.1] * (L - 1)}[name]
+_lam = lam_of
 
 
 def _rel_close(got, ref, tol=1e-5):
@@ -27,71 +26,64 @@ def _rel_close(got, ref, tol=1e-5):
     return bool((np.abs(got - ref) <= tol * np.abs(ref)).all())
 
 
-T_OBJ, N_FED = 6, 3
-# (n_fed, requant, step weights): teacher-forced; three self-fed steps, float and requantised; and the latter with step weights
-# (term s is prediction s against frame s + 1; the zero exercises a term whose seed is left out)
-CASES = {"teacher_forced": (None, False, None), "self_fed": (N_FED, False, None), "self_fed_requant": (N_FED, True, None),
-         "self_fed_requant_weighted": (N_FED, True, [0.0, 1.0, 0.5, 2.0, 1.5])}
-
-
-def _run_case(wts, ch, w, h, frames, lam, case):
-    n_fed, requant, sw = CASES[case]
-    with PredNetTrainer(wts, ch, w, h, frames.shape[0], frames.shape[1]) as tr:
-        loss, pred, table = tr.forward_backward(frames, pred=True, n_fed=n_fed, requant=requant, step_weights=sw, objective="error",
+def _run_case(c):
+    """One error-objective call of the trainer and the reference of the same case.  Bounds: `_check_grads` per tensor, 1e-5 relative
+    for the loss and every table entry, 1e-5 absolute for the predictions (values in [0, 1], the bound tests/test_gpu_train.py
+    puts on them).  A case counts only if the reference gradient of every tensor is non-zero, which `_check_grads` asserts."""
+    wts, frames = case_weights(c.w, c.h, c.ch, c.wset), case_frames(c)
+    lam, sw = list(c.lam), None if c.sw is None else list(c.sw)
+    with PredNetTrainer(wts, list(c.ch), c.w, c.h, c.B + c.room[0], c.T + c.room[1]) as tr:
+        loss, pred, table = tr.forward_backward(frames, pred=True, n_fed=c.n_fed, requant=c.requant, step_weights=sw, objective="error",
                                                 layer_weights=lam, layer_errors=True)
         got = tr.grads()
-        c_loss = _loss_grad_obj_loss(tr, frames, n_fed, requant, sw, lam)
+        c_loss = _loss_grad_obj_loss(tr, frames, c.n_fed, c.requant, sw, lam)
     # with requant both sides read the bytes of the GPU's own float32 predictions (tests/test_gpu_train_ext.py says why)
-    r = ref.run(wts, ch, frames, objective="error", layer_weights=lam, n_fed=n_fed, requant=requant, step_weights=sw,
-                fed=_fed_from(pred) if requant else None)
-    return (loss, pred, table, got, c_loss), (r.loss, r.grads, r.pred, r.table)
+    r = case_reference(c, pred=pred)
+    print("%s: loss %.8f ref %.8f, max |pred diff| %.2e, table max rel err %.2e" % (case_id(c), loss, r.loss, np.abs(pred - r.pred).max(), np.abs(table / r.table - 1).max()))
+    assert table.shape == (c.T - 1, len(c.ch)) and table.dtype == np.float64
+    assert np.abs(pred - r.pred).max() <= 1e-5, np.abs(pred - r.pred).max()
+    assert abs(loss - r.loss) <= 1e-5 * r.loss, (loss, r.loss)
+    assert _rel_close(table, r.table), (table, r.table)
+    worst = _check_grads(got, r.grads, what=case_id(c))
+    print("  error / bound %.4f in norm, %.4f element-wise" % worst)
+    # the library's own loss is the documented host formula over the returned table, to the bit
+    assert c_loss == loss == combine_terms(table, lam, sw), (c_loss, loss)
+    return pred, got
+
+
+def _l0_differs(c, pred, got):
+    """the upper-layer term cannot vanish unnoticed: against the L_0 reference this gradient is far outside the bound"""
+    g0 = case_reference(c._replace(lam=tuple(lam_of("l0", len(c.ch)))), pred=pred).grads
+    assert _grads_differ(g0, got)
 
 
 @pytest.mark.parametrize("case", list(CASES))
 @pytest.mark.parametrize("objective", ["l0", "lall"])
 @pytest.mark.parametrize("w,h,ch", SHAPES)
 def test_error_objective_loss_table_predictions_and_every_gradient_match_float64_autograd(cuda, w, h, ch, objective, case):
-    """Bounds: `_check_grads` per tensor, 1e-5 relative for the loss and every table entry, 1e-5 absolute for the predictions
-    (values in [0, 1], the bound tests/test_gpu_train.py puts on them).  A case counts only if the reference gradient of every
-    tensor is non-zero, which is asserted first."""
-    lam = _lam(objective, len(ch))
-    frames = _drifting(w + len(ch), 2, T_OBJ, ch[0], h, w)
-    wts = weights.synthetic_prednet_weights(ch, w, h, seed=1)
-    (loss, pred, table, got, c_loss), (ref_loss, ref_g, ref_pred, ref_table) = _run_case(wts, ch, w, h, frames, lam, case)
-    zero = [k for k, g in ref_g.items() if not np.any(g)]
-    assert not zero, ("the reference gradient of these tensors is zero: the case checks nothing there", zero)
-    print("%s %s: loss %.8f ref %.8f, max |pred diff| %.2e, table max rel err %.2e"
-          % (objective, case, loss, ref_loss, np.abs(pred - ref_pred).max(), np.abs(table / ref_table - 1).max()))
-    assert table.shape == (T_OBJ - 1, len(ch)) and table.dtype == np.float64
-    assert np.abs(pred - ref_pred).max() <= 1e-5, np.abs(pred - ref_pred).max()
-    assert abs(loss - ref_loss) <= 1e-5 * ref_loss, (loss, ref_loss)
-    assert _rel_close(table, ref_table), (table, ref_table)
-    _check_grads(got, ref_g)
-    # the library's own loss is the documented host formula over the returned table, to the bit
-    assert c_loss == loss == combine_terms(table, lam, CASES[case][2]), (c_loss, loss)
+    n_fed, requant, sw = CASES[case]
+    (c,) = select("error_objective", w, h, ch, wset="synthetic", lam=lam_of(objective, len(ch)), n_fed=n_fed, requant=requant, sw=sw)
+    assert (c.B, c.T) == (2, T_OBJ)
+    pred, got = _run_case(c)
     if objective == "lall":
-        # the upper-layer term cannot vanish unnoticed: against the L_0 reference this gradient is far outside the bound
-        n_fed, requant, sw = CASES[case]
-        g0 = ref.run(wts, ch, frames, objective="error", layer_weights=_lam("l0", len(ch)), n_fed=n_fed, requant=requant, step_weights=sw,
-                     fed=_fed_from(pred) if requant else None).grads
-        assert _grads_differ(g0, got)
+        _l0_differs(c, pred, got)
+
+
+@pytest.mark.parametrize("c", cases("error_objective", wide=True), ids=case_id)
+def test_l_all_gradients_match_at_the_wide_shapes(cuda, c):
+    """tests/train_support.py TILE_PROPERTIES: the tiles real channel counts use, under L_all"""
+    pred, got = _run_case(c)
+    _l0_differs(c, pred, got)
 
 
 def test_random_weights_at_the_colour_shape_where_their_gradients_are_not_zero(cuda):
-    """The `random` set of tests/test_gpu_train.py saturates P0 at the two gray shapes (every L_0 gradient is exactly zero there),
-    so it is used at the colour shape only, and the count of non-zero reference tensors is asserted before anything is compared."""
-    w, h, ch = SHAPES[1]
-    frames = _drifting(w + len(ch), 2, T_OBJ, ch[0], h, w)
-    wts = _random_weights(ch, w, h, seed=2)
-    for objective in ("l0", "lall"):
-        lam = _lam(objective, len(ch))
-        (loss, pred, table, got, c_loss), (ref_loss, ref_g, ref_pred, ref_table) = _run_case(wts, ch, w, h, frames, lam, "self_fed_requant")
-        nonzero = sum(1 for g in ref_g.values() if np.any(g))
-        assert nonzero == len(ref_g), (objective, nonzero, len(ref_g))
-        assert np.abs(pred - ref_pred).max() <= 1e-5
-        assert abs(loss - ref_loss) <= 1e-5 * ref_loss, (loss, ref_loss)
-        assert _rel_close(table, ref_table), (table, ref_table)
-        _check_grads(got, ref_g)
+    """The `random` set saturates P0 at the two gray shapes (every L_0 gradient is exactly zero there), so under this objective it is
+    used at the colour shape only, where two thirds of P0 sit at the clamp and every tensor still has a gradient
+    (tests/train_support.py `is_clamped`): `_check_grads` fails on a tensor whose reference is zero."""
+    todo = cases("error_objective_random")
+    assert len(todo) == 2 and all((c.w, c.h, list(c.ch)) == SHAPES[1] for c in todo)
+    for c in todo:
+        _run_case(c)
 
 
 @pytest.mark.parametrize("sw", [None, [0.0, 1.0, 0.5, 2.0, 1.5]])
