@@ -1448,6 +1448,25 @@ int eigen_debug_dense_flow(eigen_engine* e, int32_t batch, float* h_flow, void* 
     return EIGEN_OK;
 }
 
+// Stage-level access for the parity tests: one tensor of the layer state the last eigen_prednet_sequence call left (that call's last step runs ConvP_l for
+// l > 0 too -- RollPlan::keep_state -- and forks nothing onto the side stream, so the state is complete behind the caller's stream).
+// which: EIGEN_STATE_R (h[hflip]) / _C / _P, float [batch][C_l][H_l][W_l]; EIGEN_STATE_E, float [batch][2 C_l][H_l][W_l].
+int eigen_debug_state(eigen_engine* e, int32_t batch, int32_t layer, int32_t which, float* h_out, void* stream)
+{
+    if (!e || !h_out) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (layer < 0 || layer >= e->L) return fail(EIGEN_ERR_INVALID, "layer %d out of range (0..%d)", layer, e->L - 1);
+    if (which < EIGEN_STATE_R || which > EIGEN_STATE_E) return fail(EIGEN_ERR_INVALID, "which %d is none of EIGEN_STATE_R / _C / _P / _E", which);
+    if (e->seq_batch == 0) return fail(EIGEN_ERR_STATE, "no kept state (no eigen_prednet_sequence call yet, or a roll-out / evaluation overwrote it)");
+    if (e->seq_batch != batch) return fail(EIGEN_ERR_STATE, "the kept state is of a batch of %d, not %d", e->seq_batch, batch);
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    const Layer& y = e->layer[layer];
+    const float* src = which == EIGEN_STATE_R ? y.h[e->hflip] : which == EIGEN_STATE_C ? y.c : which == EIGEN_STATE_P ? y.P : y.E;
+    const size_t n = (size_t)batch * (which == EIGEN_STATE_E ? 2 : 1) * y.C * y.H * y.W;
+    HIPCHK(hipMemcpy(h_out, src, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return EIGEN_OK;
+}
+
 // Stage-level access for the parity tests: corner list of the last eigen_flow call.
 int eigen_debug_corners(eigen_engine* e, int32_t batch, float* h_corners, int32_t* h_ncorners, float* h_next, uint8_t* h_status, void* stream)
 {

@@ -19,7 +19,7 @@ PAIR_POPULATION, PAIR_SINGLE = 0, 1
 EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eigen_last_error", "eigen_config_defaults", "eigen_create", "eigen_destroy",
            "eigen_set_prednet_weights", "eigen_set_grid", "eigen_render_cppn", "eigen_eval_cppn_nodes", "eigen_prednet_rollout", "eigen_prednet_sequence", "eigen_flow",
            "eigen_score", "eigen_eval_population", "eigen_eval_images", "eigen_test_conv", "eigen_time_conv", "eigen_test_det_math",
-           "eigen_get_timings", "eigen_conv_profile", "eigen_debug_corners", "eigen_debug_dense_flow", "eigen_prednet_flops_per_step", "eigen_flatten_genomes", "eigen_plan_text",
+           "eigen_get_timings", "eigen_conv_profile", "eigen_debug_corners", "eigen_debug_dense_flow", "eigen_debug_state", "eigen_prednet_flops_per_step", "eigen_flatten_genomes", "eigen_plan_text",
            "eigen_trainer_create", "eigen_trainer_destroy", "eigen_trainer_set_weights", "eigen_trainer_get_weights", "eigen_trainer_loss_grad",
            "eigen_trainer_get_grads", "eigen_trainer_adam", "eigen_trainer_tape_bytes", "eigen_trainer_loss_grad_ext", "eigen_trainer_evaluate",
            "eigen_trainer_get_state", "eigen_trainer_set_state", "eigen_trainer_loss_grad_obj", "eigen_trainer_evaluate_err",
@@ -319,6 +319,18 @@ class Engine:
         f = np.zeros((batch, 2, self.height, self.width), np.float32)
         _check(self.lib.eigen_debug_dense_flow(self._h, ctypes.c_int32(batch), _ptr(f), _stream_arg(stream)))
         return f
+
+    def debug_state(self, batch, stream=None):
+        """The float32 layer state the last prednet_sequence call left (eigen_debug_state): one dict per layer, "R", "c", "P" of
+        [batch, C_l, H_l, W_l] and "E" of [batch, 2 C_l, H_l, W_l] (E_0: the error units the last executed step consumed)."""
+        out = []
+        for l, C in enumerate(self.channels):
+            d = {}
+            for which, k in enumerate(("R", "c", "P", "E")):
+                d[k] = np.zeros((batch, (2 if k == "E" else 1) * C, self.height >> l, self.width >> l), np.float32)
+                _check(self.lib.eigen_debug_state(self._h, ctypes.c_int32(batch), ctypes.c_int32(l), ctypes.c_int32(which), _ptr(d[k]), _stream_arg(stream)))
+            out.append(d)
+        return out
 
     def debug_corners(self, batch, stream=None):
         c = np.zeros((batch, self.K, 2), np.float32); n = np.zeros(batch, np.int32)

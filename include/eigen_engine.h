@@ -268,6 +268,19 @@ int eigen_conv_profile(eigen_engine* e, int32_t enable, int32_t reset, double* h
  * flow_method = EIGEN_FLOW_FARNEBACK, float [batch][2][H][W] (dx plane, dy plane). */
 int eigen_debug_dense_flow(eigen_engine* e, int32_t batch, float* h_flow, void* stream);
 
+/* Stage-level read-back for the parity tests: one float32 tensor of the layer state that the last eigen_prednet_sequence call left
+ * on the handle (its last step also runs ConvP_l for l > 0, so every tensor is of the same step).
+ *   which = EIGEN_STATE_R: R_l (the ConvLSTM output h), EIGEN_STATE_C: the cell state c_l, EIGEN_STATE_P: the prediction P_l, each
+ *   float [batch][C_l][H_l][W_l]; EIGEN_STATE_E: the error units E_l, float [batch][2 C_l][H_l][W_l] (relu(A - P), then relu(P - A)).
+ *   E_l for l >= 1 belongs to the last executed step.  E_0 is the tensor that step CONSUMED -- err(its input frame, P_0 of the step
+ *   before): the last step of a call does not write the next one, whose frame it has not seen (the next call forms it from the kept
+ *   P_0 and its first input).  The CPU oracle's prednet_step leaves exactly that in E[0] (error_unit(x, P[0]) on entry).
+ * Synchronises the stream and copies; no kernel is launched and the state is not changed.
+ * Errors: EIGEN_ERR_STATE where a reset = 0 call of this batch would be refused (no call yet, a roll-out or evaluation since, another
+ * batch); EIGEN_ERR_INVALID for a layer outside 0 .. n_layers - 1, an unknown `which` or a NULL pointer. */
+enum eigen_state_tensor { EIGEN_STATE_R = 0, EIGEN_STATE_C = 1, EIGEN_STATE_P = 2, EIGEN_STATE_E = 3 };
+int eigen_debug_state(eigen_engine* e, int32_t batch, int32_t layer, int32_t which, float* h_out, void* stream);
+
 /* Stage-level read-back for the parity tests: corners / tracked points / status of the last eigen_flow call. */
 int eigen_debug_corners(eigen_engine* e, int32_t batch, float* h_corners, int32_t* h_ncorners, float* h_next,
                         uint8_t* h_status, void* stream);

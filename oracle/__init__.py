@@ -67,6 +67,7 @@ def lib():
         _LIB.eig_oracle_prednet_rollout.restype = ctypes.c_int
         _LIB.eig_oracle_prednet_rollout_order.restype = ctypes.c_int
         _LIB.eig_oracle_prednet_rollout_wino.restype = ctypes.c_int
+        _LIB.eig_oracle_prednet_rollout_state.restype = ctypes.c_int
         _LIB.eig_oracle_lucas_kanade.restype = ctypes.c_int
         _LIB.eig_oracle_good_features.restype = ctypes.c_int
         _LIB.eig_oracle_conv_chain.restype = ctypes.c_int
@@ -140,11 +141,16 @@ def wino_mask_default():
     return m
 
 
-def prednet_rollout(weights, channels, w, h, img, n_repeat=20, n_ext=2, requant=False, return_float=False, order="canonical", wino_mask=None):
+STATE_TENSORS = ("R", "c", "P", "E")   # eig_oracle.c: eig_oracle_prednet_rollout_state, `which` 0..3 (the engine's eigen_debug_state numbers them alike)
+
+
+def prednet_rollout(weights, channels, w, h, img, n_repeat=20, n_ext=2, requant=False, return_float=False, order="canonical", wino_mask=None, state_steps=None):
     """Roll ``img`` (uint8 [C0,H,W]) through PredNet; returns uint8 frames [n_repeat+n_ext, C0, H, W].
     order: "canonical" = the build's arithmetic (what the HIP kernels reproduce bit for bit); "chainer" = the reference's
     element-wise order (eig_oracle.c: lstm_reference_order) -- separate convolution tensors added left to right, plain unpool ->
-    9-tap, un-fused gate products, sigmoid = tanh(x/2)/2 + 1/2 on libm."""
+    9-tap, un-fused gate products, sigmoid = tanh(x/2)/2 + 1/2 on libm.
+    state_steps: a list of step counts (1 .. n_repeat + n_ext); the float32 state after that many steps is returned LAST, as
+    {count: [per layer {"R": [C_l,H_l,W_l], "c", "P", "E": [2 C_l,H_l,W_l]}]} (E_0: the error units the last executed step consumed)."""
     L = len(channels)
     names = tensor_names(L)
     arrs = [np.ascontiguousarray(weights[n], dtype=np.float32) for n in names]
@@ -155,14 +161,24 @@ def prednet_rollout(weights, channels, w, h, img, n_repeat=20, n_ext=2, requant=
     T = n_repeat + n_ext
     out = np.zeros((T, channels[0], h, w), dtype=np.uint8)
     p0 = np.zeros((T, channels[0], h, w), dtype=np.float32) if return_float else None
-    rc = lib().eig_oracle_prednet_rollout_wino(
+    steps = [] if state_steps is None else [int(s) for s in state_steps]
+    if any(s < 1 or s > T for s in steps):
+        raise ValueError("state_steps are step counts in 1 .. %d, got %s" % (T, steps))
+    states = {s: [{k: np.zeros(((2 if k == "E" else 1) * channels[l], h >> l, w >> l), np.float32) for k in STATE_TENSORS} for l in range(L)] for s in steps}
+    st_arr = np.asarray(steps, dtype=np.int32)
+    st_tab = (ctypes.POINTER(ctypes.c_float) * max(len(steps) * L * 4, 1))(*[_p(states[s][l][k], ctypes.c_float) for s in steps for l in range(L) for k in STATE_TENSORS])
+    rc = lib().eig_oracle_prednet_rollout_state(
         ctypes.c_int(L), _p(ch, ctypes.c_int), ctypes.c_int(w), ctypes.c_int(h), tab, _p(img, ctypes.c_uint8),
         ctypes.c_int(n_repeat), ctypes.c_int(n_ext), ctypes.c_int(int(requant)), _p(out, ctypes.c_uint8),
         _p(p0, ctypes.c_float) if return_float else None, ctypes.c_int({"canonical": 0, "chainer": 1}[order]),
-        ctypes.c_int((wino_mask_default() if wino_mask is None else int(wino_mask)) if order == "canonical" else 0))
+        ctypes.c_int((wino_mask_default() if wino_mask is None else int(wino_mask)) if order == "canonical" else 0),
+        ctypes.c_int(len(steps)), _p(st_arr, ctypes.c_int) if steps else None, st_tab if steps else None)
     if rc != 0:
         raise ValueError("eig_oracle_prednet_rollout failed (size must be divisible by 2^(L-1))")
-    return (out, p0) if return_float else out
+    res = (out, p0) if return_float else (out,)
+    if state_steps is not None:
+        res += (states,)
+    return res if len(res) > 1 else out
 
 
 class PredNetC:

@@ -831,12 +831,32 @@ int eig_oracle_prednet_rollout_order(int L, const int* channels, int W, int H, c
 }
 
 /* wino_mask (canonical order only): which operators run in their Winograd form -- eig_wino_op; bit 24: eig_wino_fuse_up */
+int eig_oracle_prednet_rollout_state(int L, const int* channels, int W, int H, const float* const* tensors,
+                                     const uint8_t* img, int n_repeat, int n_ext, int requant,
+                                     uint8_t* out_frames, float* out_p0, int order, int wino_mask,
+                                     int n_state, const int* state_steps, float* const* state_out);
 int eig_oracle_prednet_rollout_wino(int L, const int* channels, int W, int H, const float* const* tensors,
                                     const uint8_t* img, int n_repeat, int n_ext, int requant,
                                     uint8_t* out_frames, float* out_p0, int order, int wino_mask)
 {
+    return eig_oracle_prednet_rollout_state(L, channels, W, H, tensors, img, n_repeat, n_ext, requant, out_frames, out_p0, order, wino_mask, 0, NULL, NULL);
+}
+
+/* The same roll-out, with the float state read out on the way (test hook of the state-parity tests; the arithmetic is not touched).
+ *   state_steps : n_state step COUNTS, each in 1 .. n_repeat + n_ext: entry k asks for the state after state_steps[k] executed steps
+ *   state_out   : [n_state][L][4] caller buffers, ((k * L + l) * 4 + which): which 0 = R_l (n.h[l]) [C_l][H_l][W_l], 1 = c_l, 2 = P_l,
+ *                 3 = E_l [2 C_l][H_l][W_l]
+ * After prednet_step, E[0] is error_unit(x, P_0 of the step before): the error units the step just executed CONSUMED (P_0 of that
+ * step itself has met no frame yet) -- the tensor the engine's eigen_debug_state returns as E_0. */
+int eig_oracle_prednet_rollout_state(int L, const int* channels, int W, int H, const float* const* tensors,
+                                     const uint8_t* img, int n_repeat, int n_ext, int requant,
+                                     uint8_t* out_frames, float* out_p0, int order, int wino_mask,
+                                     int n_state, const int* state_steps, float* const* state_out)
+{
     if (L < 1 || L > EIG_MAX_LAYERS || order < 0 || order > 1) return -1;
     if ((W % (1 << (L - 1))) || (H % (1 << (L - 1)))) return -1;
+    if (n_state < 0 || (n_state > 0 && (!state_steps || !state_out))) return -1;
+    for (int k = 0; k < n_state; k++) if (state_steps[k] < 1 || state_steps[k] > n_repeat + n_ext) return -1;
     prednet_t n;
     memset(&n, 0, sizeof(n));
     n.L = L;
@@ -859,6 +879,17 @@ int eig_oracle_prednet_rollout_wino(int L, const int* channels, int W, int H, co
         prednet_step(&n, x);
         for (size_t i = 0; i < fsz; i++) out_frames[(size_t)t * fsz + i] = (uint8_t)(int)(n.P[0][i] * 255.0f);
         if (out_p0) memcpy(out_p0 + (size_t)t * fsz, n.P[0], sizeof(float) * fsz);
+        for (int k = 0; k < n_state; k++) {
+            if (state_steps[k] != t + 1) continue;
+            for (int l = 0; l < L; l++) {
+                const size_t chw = sizeof(float) * (size_t)n.ch[l] * n.H[l] * n.W[l];
+                float* const* o = state_out + ((size_t)k * L + l) * 4;
+                memcpy(o[0], n.h[l], chw);
+                memcpy(o[1], n.c[l], chw);
+                memcpy(o[2], n.P[l], chw);
+                memcpy(o[3], n.E[l], 2 * chw);
+            }
+        }
     }
     free(x);
     prednet_free(&n);
