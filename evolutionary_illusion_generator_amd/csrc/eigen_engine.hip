@@ -20,6 +20,7 @@
 #include "weight_pack.h"   // host: weight tensors -> the kernels' layouts
 #include "conv_plan.h"     // host: which operators run (plan_prednet) and in which launch shape (plan_launch)
 #include "cppn_kernel.h"
+#include "cppn_grad_kernel.h"
 #include "farneback_kernels.h"
 #include "flow_kernels.h"
 #include "score_kernels.h"
@@ -109,6 +110,7 @@ struct eigen_engine {
     DevBuf<int32_t> g_node_off, g_edge_off, g_edge_src, g_out_node;
     DevBuf<uint8_t> g_node_act;
     DevBuf<double> g_node_bias, g_node_resp, g_edge_w;
+    DevBuf<double> g_grad_slabs, g_grad_sum;   // eigen_cppn_param_grads: one slab per pixel block, and their sum
     // images / frames
     uint8_t* d_images = nullptr;  // [B][C0][H][W]
     uint8_t* d_frames = nullptr;  // [B][3][C0][H][W]
@@ -434,6 +436,7 @@ int eigen_destroy(eigen_engine* e)
     if (e->d_planes) (void)hipFree(e->d_planes);
     e->g_node_off.release(); e->g_edge_off.release(); e->g_edge_src.release(); e->g_out_node.release();
     e->g_node_act.release(); e->g_node_bias.release(); e->g_node_resp.release(); e->g_edge_w.release();
+    e->g_grad_slabs.release(); e->g_grad_sum.release();
     void* misc[] = {e->d_images, e->d_frames, e->d_eig, e->d_cand, e->d_corners, e->d_next, e->d_vectors, e->d_status,
                     e->d_ncorners, e->d_counts, e->d_fitness, e->d_zeros,
                     e->fb_I, e->fb_R0, e->fb_R1, e->fb_M, e->fb_V, e->fb_flow[0], e->fb_flow[1]};
@@ -625,14 +628,16 @@ int eigen_set_grid(eigen_engine* e, const double* h_planes, int32_t n_planes)
     return EIGEN_OK;
 }
 
-static int render_cppn_impl(eigen_engine* e, const eigen_genome_batch* g, int32_t bg, int mode, uint8_t* d_images, double* d_nodes, void* stream)
+// What both CPPN entry points do before they launch: the call-order and genome checks, then the batch on the device.
+// lds_of(max_nodes, max_edges): the caller's LDS need; above 160 KiB the batch is refused before anything is uploaded.
+struct GenomeExtent { int total_nodes = 0, total_edges = 0, max_nodes = 0, max_edges = 0; size_t lds = 0; };
+
+static int stage_genomes(eigen_engine* e, const eigen_genome_batch* g, int need_out, size_t (*lds_of)(int, int), hipStream_t st, GenomeExtent& x, CppnArgs& a)
 {
     if (!e->have_grid) return fail(EIGEN_ERR_STATE, "eigen_set_grid has not been called");
     HIPCHK(hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
     const int G = g->n_genomes;
     if (G < 1) return fail(EIGEN_ERR_INVALID, "n_genomes < 1");
-    const int need_out = (mode == 0) ? e->C0 : (mode == 4 ? 3 : 1);
     if (g->c_out < need_out) return fail(EIGEN_ERR_INVALID, "genome batch provides %d outputs per genome, %d needed", g->c_out, need_out);
     const int total_nodes = g->node_off[G];
     const int total_edges = g->edge_off[total_nodes];
@@ -659,7 +664,7 @@ static int render_cppn_impl(eigen_engine* e, const eigen_genome_batch* g, int32_
             if (o < 0 || o >= n1 - n0) return fail(EIGEN_ERR_INVALID, "genome %d: output %d names node %d of %d", gi, c, o, n1 - n0);
         }
     }
-    const size_t lds = (size_t)max_nodes * CPPN_THREADS * 8 + (size_t)max_nodes * 16 + (size_t)max_edges * 8 + (size_t)(max_nodes + 1) * 4 + (size_t)max_edges * 4 + max_nodes + 64;
+    const size_t lds = lds_of(max_nodes, max_edges);
     if (lds > 160 * 1024) return fail(EIGEN_ERR_CAPACITY, "genome with %d nodes / %d edges needs %zu B of LDS (> 160 KiB)", max_nodes, max_edges, lds);
     if (e->g_node_off.ensure(G + 1) || e->g_edge_off.ensure(total_nodes + 1) || e->g_node_act.ensure(total_nodes) ||
         e->g_node_bias.ensure(total_nodes) || e->g_node_resp.ensure(total_nodes) || e->g_edge_src.ensure(std::max(total_edges, 1)) ||
@@ -675,13 +680,32 @@ static int render_cppn_impl(eigen_engine* e, const eigen_genome_batch* g, int32_
         HIPCHK(hipMemcpyAsync(e->g_edge_w.p, g->edge_w, sizeof(double) * total_edges, hipMemcpyHostToDevice, st));
     }
     HIPCHK(hipMemcpyAsync(e->g_out_node.p, g->out_node, sizeof(int32_t) * G * g->c_out, hipMemcpyHostToDevice, st));
-    CppnArgs a;
     a.node_off = e->g_node_off.p; a.edge_off = e->g_edge_off.p; a.node_act = e->g_node_act.p;
     a.node_bias = e->g_node_bias.p; a.node_resp = e->g_node_resp.p; a.edge_src = e->g_edge_src.p; a.edge_w = e->g_edge_w.p;
     a.out_node = e->g_out_node.p; a.planes = e->d_planes; a.n_planes = e->n_planes; a.N = e->H * e->W;
-    a.c_out = g->c_out; a.c_dim = e->C0; a.bg = bg; a.mode = mode; a.max_nodes = max_nodes; a.out = d_images; a.out_f64 = d_nodes;
-    (void)hipFuncSetAttribute((const void*)cppn_render_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(cppn_render_kernel, dim3((a.N + CPPN_THREADS - 1) / CPPN_THREADS, G), dim3(CPPN_THREADS), lds, st, a);
+    a.c_out = g->c_out; a.c_dim = e->C0; a.max_nodes = max_nodes;
+    x.total_nodes = total_nodes; x.total_edges = total_edges; x.max_nodes = max_nodes; x.max_edges = max_edges; x.lds = lds;
+    return EIGEN_OK;
+}
+
+// the genome program (bias, resp, weights, offsets, sources, activations) beside `columns` float64 [node][thread] columns
+static size_t cppn_lds(size_t columns, int max_nodes, int max_edges)
+{
+    return columns + (size_t)max_nodes * 16 + (size_t)max_edges * 8 + (size_t)(max_nodes + 1) * 4 + (size_t)max_edges * 4 + max_nodes + 64;
+}
+static size_t render_lds(int max_nodes, int max_edges) { return cppn_lds((size_t)max_nodes * CPPN_THREADS * 8, max_nodes, max_edges); }
+static size_t grad_lds(int max_nodes, int max_edges) { return cppn_lds((size_t)2 * max_nodes * CPPN_GRAD_THREADS * 8, max_nodes, max_edges); }
+
+static int render_cppn_impl(eigen_engine* e, const eigen_genome_batch* g, int32_t bg, int mode, uint8_t* d_images, double* d_nodes, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    GenomeExtent x;
+    CppnArgs a;
+    const int rc = stage_genomes(e, g, (mode == 0) ? e->C0 : (mode == 4 ? 3 : 1), render_lds, st, x, a);
+    if (rc != EIGEN_OK) return rc;
+    a.bg = bg; a.mode = mode; a.out = d_images; a.out_f64 = d_nodes;
+    (void)hipFuncSetAttribute((const void*)cppn_render_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds);
+    hipLaunchKernelGGL(cppn_render_kernel, dim3((a.N + CPPN_THREADS - 1) / CPPN_THREADS, g->n_genomes), dim3(CPPN_THREADS), x.lds, st, a);
     HIPCHK(hipGetLastError());
     return EIGEN_OK;
 }
@@ -702,6 +726,38 @@ int eigen_eval_cppn_nodes(eigen_engine* e, const eigen_genome_batch* g, double* 
 {
     if (!e || !g || !d_nodes) return fail(EIGEN_ERR_INVALID, "null argument");
     return render_cppn_impl(e, g, 1, 3, nullptr, d_nodes, stream);
+}
+
+int eigen_cppn_param_grads(eigen_engine* e, const eigen_genome_batch* g, int32_t bg, int32_t gradient, const float* d_image_grad, int64_t g_bstride,
+                           double* h_grad_bias, double* h_grad_resp, double* h_grad_w, void* stream)
+{
+    if (!e || !g || !d_image_grad || !h_grad_bias || !h_grad_resp || !h_grad_w) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (!e->have_grid) return fail(EIGEN_ERR_STATE, "eigen_set_grid has not been called");
+    if (gradient != 1) return fail(EIGEN_ERR_INVALID, "gradient %d: only the gradient = 1 render is differentiable (not the palette, the rounded gray or the h,s,v renderer)", gradient);
+    const long long per = (long long)e->C0 * e->H * e->W;
+    if (g_bstride < per) return fail(EIGEN_ERR_INVALID, "g_bstride %lld < C*H*W = %lld", (long long)g_bstride, per);
+    hipStream_t st = (hipStream_t)stream;
+    GenomeExtent x;
+    CppnGradArgs ga;
+    const int rc = stage_genomes(e, g, e->C0, grad_lds, st, x, ga.c);
+    if (rc != EIGEN_OK) return rc;
+    ga.c.bg = bg; ga.c.mode = 0;   // (the fill itself never reaches a gradient: background pixels get no seed)
+    ga.c.out = nullptr; ga.c.out_f64 = nullptr;
+    const int n_blocks = (ga.c.N + CPPN_GRAD_THREADS - 1) / CPPN_GRAD_THREADS;
+    const size_t n_params = 2 * (size_t)x.total_nodes + x.total_edges;
+    if (e->g_grad_slabs.ensure((size_t)n_blocks * n_params) || e->g_grad_sum.ensure(n_params))
+        return fail(EIGEN_ERR_HIP, "hipMalloc(%zu) for the gradient slabs failed", (size_t)n_blocks * n_params * sizeof(double));
+    ga.image_grad = d_image_grad; ga.g_bstride = g_bstride; ga.total_nodes = x.total_nodes; ga.total_edges = x.total_edges; ga.slabs = e->g_grad_slabs.p;
+    (void)hipFuncSetAttribute((const void*)cppn_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds);
+    hipLaunchKernelGGL(cppn_grad_kernel, dim3(n_blocks, g->n_genomes), dim3(CPPN_GRAD_THREADS), x.lds, st, ga);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(cppn_grad_sum_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, st, e->g_grad_slabs.p, e->g_grad_sum.p, (int)n_params, n_blocks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_grad_bias, e->g_grad_sum.p, sizeof(double) * x.total_nodes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_grad_resp, e->g_grad_sum.p + x.total_nodes, sizeof(double) * x.total_nodes, hipMemcpyDeviceToHost, st));
+    if (x.total_edges) HIPCHK(hipMemcpyAsync(h_grad_w, e->g_grad_sum.p + 2 * (size_t)x.total_nodes, sizeof(double) * x.total_edges, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return EIGEN_OK;
 }
 
 }  // extern "C"

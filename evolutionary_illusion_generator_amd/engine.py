@@ -23,7 +23,7 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_trainer_create", "eigen_trainer_destroy", "eigen_trainer_set_weights", "eigen_trainer_get_weights", "eigen_trainer_loss_grad",
            "eigen_trainer_get_grads", "eigen_trainer_adam", "eigen_trainer_tape_bytes", "eigen_trainer_loss_grad_ext", "eigen_trainer_evaluate",
            "eigen_trainer_get_state", "eigen_trainer_set_state", "eigen_trainer_loss_grad_obj", "eigen_trainer_evaluate_err",
-           "eigen_trainer_loss_grad_frames", "eigen_trainer_still_step"]
+           "eigen_trainer_loss_grad_frames", "eigen_trainer_still_step", "eigen_cppn_param_grads"]
 
 
 class EigenConfig(ctypes.Structure):
@@ -199,6 +199,26 @@ class Engine:
         """float64 [n, c_out, H*W] raw output-node values (create_cppn node calls, generate_illusion.py:395)."""
         s = self._genome_struct(gb)
         _check(self.lib.eigen_eval_cppn_nodes(self._h, ctypes.byref(s), _ptr(d_nodes), _stream_arg(stream)))
+
+    def cppn_param_grads(self, gb, d_image_grad, bg=1, gradient=1, stream=None):
+        """The gradient of a loss by the parameters of the genomes of `gb`, from its gradient by their gradient = 1 renders (DESIGN.md
+        section 13, "CPPN parameter gradients").  d_image_grad: a float32 device tensor [n, C, H, W], d loss / d (byte / 255), as
+        ``PredNetTrainer`` returns its tied frame gradient; a stride between the images above C*H*W is taken from the tensor.
+        -> (g_bias [total_nodes], g_resp [total_nodes], g_w [total_edges]) float64 numpy arrays in the batch's own layout."""
+        per = self.c_dim * self.height * self.width
+        shape, dtype = tuple(getattr(d_image_grad, "shape", ())), str(getattr(d_image_grad, "dtype", ""))
+        if "float32" not in dtype or len(shape) != 4 or shape[0] < gb.n_genomes or int(np.prod(shape[1:])) != per:
+            raise ValueError("d_image_grad must be float32 [>= %d, %d, %d, %d], got %s %s" % (gb.n_genomes, self.c_dim, self.height, self.width, dtype, shape))
+        stride = getattr(d_image_grad, "stride", None)
+        bstride = int(stride(0)) if callable(stride) and shape[0] > 1 else per
+        if callable(stride) and tuple(stride()[1:]) != (shape[2] * shape[3], shape[3], 1):
+            raise ValueError("every image of d_image_grad must be contiguous")
+        n_nodes = int(gb.node_off[gb.n_genomes])
+        g_bias, g_resp, g_w = np.zeros(n_nodes, np.float64), np.zeros(n_nodes, np.float64), np.zeros(max(int(gb.edge_off[n_nodes]), 1), np.float64)
+        s = self._genome_struct(gb)
+        _check(self.lib.eigen_cppn_param_grads(self._h, ctypes.byref(s), ctypes.c_int32(bg), ctypes.c_int32(gradient), _ptr(d_image_grad), ctypes.c_int64(bstride),
+                                               _ptr(g_bias), _ptr(g_resp), _ptr(g_w), _stream_arg(stream)))
+        return g_bias, g_resp, g_w[:int(gb.edge_off[n_nodes])]
 
     def _check_images(self, d_images, batch):
         """The C side reads batch * C0 * H * W bytes from the raw pointer: refuse anything smaller."""

@@ -77,8 +77,29 @@ def flatten_genome(genome, config, n_leaves=2):
                 edge_w=np.asarray(edge_w, np.float64), out_node=np.asarray(out_node, np.int32))
 
 
+def flatten_genome_map(genome, config, n_leaves=2):
+    """flatten_genome's dict plus which gene every flat parameter is: ``node_key[n]``, the key in ``genome.nodes`` of flat node n
+    (its bias and response), and ``edge_key[k]``, the key (i, o) in ``genome.connections`` of flat edge k (its weight); both lists.
+
+    ``None`` marks what stands for no single gene: the identity node synthesised for a constant output, and an edge that carries
+    folded float32 constants (a leading run of constant sources, or a source that is a constant node).  Those entries, and every
+    gene inside a folded sub-graph (which has no flat parameter at all), are FROZEN: ``train.refine_genomes`` does not update them in
+    this version.  The native flattener is element for element ``_flatten_lists``, so the map holds for a GenomeBatch of either."""
+    act, bias, resp, edge_off, edge_src, edge_w, out_node, node_key, edge_key = _flatten_lists_keys(genome, config, n_leaves)
+    out = dict(act=np.asarray(act, np.uint8), bias=np.asarray(bias, np.float64), resp=np.asarray(resp, np.float64),
+               edge_off=np.asarray(edge_off, np.int32), edge_src=np.asarray(edge_src, np.int32),
+               edge_w=np.asarray(edge_w, np.float64), out_node=np.asarray(out_node, np.int32))
+    out["node_key"], out["edge_key"] = node_key, edge_key
+    return out
+
+
 def _flatten_lists(genome, config, n_leaves=2):
     """flatten_genome's work on plain Python lists (GenomeBatch concatenates these and converts once per batch)."""
+    return _flatten_lists_keys(genome, config, n_leaves)[:7]
+
+
+def _flatten_lists_keys(genome, config, n_leaves=2):
+    """_flatten_lists' seven lists, then node_key and edge_key (flatten_genome_map): which gene every flat parameter is."""
     gc = config.genome_config
     in_keys, out_keys = list(gc.input_keys), list(gc.output_keys)
     if len(in_keys) != n_leaves:
@@ -128,6 +149,7 @@ def _flatten_lists(genome, config, n_leaves=2):
     const32 = {}   # node -> np.float32 constant
     index = {}
     act, bias, resp, edge_off, edge_src, edge_w = [], [], [], [0], [], []
+    node_key, edge_key = [], []
     ONE = -(n_leaves + 1)
     for n in order:
         node = genome.nodes[n]
@@ -150,6 +172,7 @@ def _flatten_lists(genome, config, n_leaves=2):
             continue
         index[n] = len(act)
         act.append(ACT_IDS[node.activation]); bias.append(float(node.bias)); resp.append(float(node.response))
+        node_key.append(n)
         # Python's sum() adds left to right: a LEADING run of float32 constants is accumulated in float32 before the
         # first float64 term promotes the running sum; later float32 terms are promoted one by one.
         lead = 0
@@ -162,16 +185,16 @@ def _flatten_lists(genome, config, n_leaves=2):
                 for i, w in conns[:lead]:
                     t = np.float32(w) * const32[i]
                     pre = t if pre is None else np.float32(pre + t)
-            edge_src.append(ONE); edge_w.append(float(pre))
+            edge_src.append(ONE); edge_w.append(float(pre)); edge_key.append(None)
         for i, w in (conns[lead:] if lead else conns):
             li = leaf_of.get(i)
             if li is not None:
-                edge_src.append(-(li + 1)); edge_w.append(float(w))
+                edge_src.append(-(li + 1)); edge_w.append(float(w)); edge_key.append((i, n))
             elif i in const32:
                 with np.errstate(all="ignore"):
-                    edge_src.append(ONE); edge_w.append(float(np.float32(w) * const32[i]))
+                    edge_src.append(ONE); edge_w.append(float(np.float32(w) * const32[i])); edge_key.append(None)
             else:
-                edge_src.append(index[i]); edge_w.append(float(w))
+                edge_src.append(index[i]); edge_w.append(float(w)); edge_key.append((i, n))
         edge_off.append(len(edge_src))
     out_node = []
     for o in out_keys:
@@ -179,8 +202,9 @@ def _flatten_lists(genome, config, n_leaves=2):
             index[o] = len(act)
             act.append(ACT_IDS["identity"]); bias.append(0.0); resp.append(1.0)
             edge_src.append(ONE); edge_w.append(float(const32[o])); edge_off.append(len(edge_src))
+            node_key.append(None); edge_key.append(None)
         out_node.append(index[o])
-    return act, bias, resp, edge_off, edge_src, edge_w, out_node
+    return act, bias, resp, edge_off, edge_src, edge_w, out_node, node_key, edge_key
 
 
 def _marshal_python(genomes):

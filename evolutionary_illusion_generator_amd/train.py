@@ -476,4 +476,140 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
     return img.cpu().numpy(), history
 
 
-__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills"]
+PARAM_KINDS = ("weight", "bias", "response")
+
+
+def _genome_bounds(config, bounds):
+    """{kind: (lo, hi)} of refine_genomes: `bounds` as given, else the <kind>_min_value / <kind>_max_value the genome config carries; a
+    kind without both is not clipped."""
+    if bounds is not None:
+        out = {}
+        for k, v in dict(bounds).items():
+            if k not in PARAM_KINDS or len(v) != 2 or not float(v[0]) <= float(v[1]):
+                raise ValueError("bounds must map %s to (lo, hi) with lo <= hi, got %r: %r" % (", ".join(PARAM_KINDS), k, v))
+            out[k] = (float(v[0]), float(v[1]))
+        return out
+    gc = getattr(config, "genome_config", None)
+    out = {}
+    for k in PARAM_KINDS:
+        lo, hi = getattr(gc, k + "_min_value", None), getattr(gc, k + "_max_value", None)
+        if lo is not None and hi is not None:
+            out[k] = (float(lo), float(hi))
+    return out
+
+
+def genome_update(genome, gmap, g_bias, g_resp, g_w, lr, params=PARAM_KINDS, bounds=None):
+    """One normalised ascent step of refine_genomes on ONE genome, in place, in float64.  gmap: ``genome.flatten_genome_map`` of it;
+    g_bias, g_resp, g_w: the gradients of its flat parameters.  The trainable parameters are those of the selected kinds whose map
+    entry is a gene (not None); m = max |g| over them; m zero or not finite leaves the genome as it is, otherwise every one moves
+    by lr * g / m and is then clipped to bounds[kind] where that is given.  Returns whether the genome moved."""
+    todo = []   # (gene, attribute, kind, gradient)
+    if "bias" in params or "response" in params:
+        for n, key in enumerate(gmap["node_key"]):
+            if key is None:
+                continue
+            if "bias" in params:
+                todo.append((genome.nodes[key], "bias", "bias", float(g_bias[n])))
+            if "response" in params:
+                todo.append((genome.nodes[key], "response", "response", float(g_resp[n])))
+    if "weight" in params:
+        for k, key in enumerate(gmap["edge_key"]):
+            if key is not None:
+                todo.append((genome.connections[key], "weight", "weight", float(g_w[k])))
+    if not todo:
+        return False
+    m = float(np.max(np.abs(np.asarray([t[3] for t in todo], np.float64))))
+    if not (np.isfinite(m) and m > 0):
+        return False
+    bounds = bounds or {}
+    for gene, attr, kind, g in todo:
+        v = float(getattr(gene, attr)) + float(lr) * (g / m)
+        if kind in bounds:
+            v = min(max(v, bounds[kind][0]), bounds[kind][1])
+        setattr(gene, attr, v)
+    return True
+
+
+def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, iters=10, lr=0.02, requant=True, objective="mse", layer_weights=None,
+                   step_weights=None, bg=1, params=PARAM_KINDS, bounds=None):
+    """Gradient ascent on the genomes' own parameters: ``refine_stills``' loss (how far PredNet's extended prediction leaves the still),
+    climbed through the CPPN render instead of in pixel space, so that what comes back can be mutated, crossed and rendered at any
+    size.  -> (genomes', float64 [iters + 1] history, uint8 [n, C, H, W] images).
+
+    genomes: a list of n <= the trainer's batch NEAT genomes of `config`; they are never modified: genomes' are deep copies that
+    keep keys, structure, `enabled` flags and `fitness`.  structure: the grid (``fitness.leaf_planes``) at the trainer's w, h.
+    Per iteration the copies are rendered on the device (gradient = 1 render, background `bg`), one trainer call exactly as
+    ``refine_stills`` makes it gives the loss and its tied frame gradient, ``Engine.cppn_param_grads`` turns that into the gradient by
+    every flat parameter (straight through the uint8 quantisation; DESIGN.md section 13, "CPPN parameter gradients"), and the host
+    updates every genome in float64 (``genome_update``): theta += lr * g / max |g| over its trainable parameters of the kinds in
+    `params`, then clipped to `bounds` ({kind: (lo, hi)}; None: the <kind>_min_value / _max_value of the genome config, where it has
+    them).  FROZEN, i.e. never updated: folded float32 constants (``genome.flatten_genome_map``'s None entries and everything inside a
+    folded sub-graph), disabled connections and whatever the outputs do not depend on.
+
+    history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images, which are the
+    render of genomes'.  The calls OVERWRITE the trainer's weight gradients and its kept sequence state."""
+    import copy
+    from . import fitness
+    from .genome import GenomeBatch, flatten_genome_map
+    T = int(n_repeat) + int(n_ext)
+    if n_repeat < 1 or n_ext < 1 or iters < 0:
+        raise ValueError("n_repeat >= 1, n_ext >= 1 and iters >= 0 required")
+    if T > trainer.max_steps:
+        raise ValueError("n_repeat + n_ext = %d frames exceed the trainer's max_steps %d" % (T, trainer.max_steps))
+    genomes = list(genomes)
+    n = len(genomes)
+    if not 1 <= n <= trainer.batch:
+        raise ValueError("%d genomes: 1 .. the trainer's batch %d required" % (n, trainer.batch))
+    if not (np.isfinite(lr) and lr > 0):
+        raise ValueError("lr must be finite and > 0, got %r" % (lr,))
+    params = (params,) if isinstance(params, str) else tuple(params)
+    if not params or any(k not in PARAM_KINDS for k in params):
+        raise ValueError("params must be a non-empty selection of %s, got %r" % (", ".join(PARAM_KINDS), params))
+    limits = _genome_bounds(config, bounds)
+    if step_weights is None:
+        step_weights = [0.0] * (n_repeat - 1) + [1.0] * n_ext
+    torch = trainer._torch
+    C0, h, w = trainer.channels[0], trainer.h, trainer.w
+    n_in = len(config.genome_config.input_keys)
+    out = [copy.deepcopy(g) for g in genomes]
+    maps = [flatten_genome_map(g, config, n_in) for g in out]   # values change below, the structure (and so the map) does not
+    per = C0 * h * w
+    with torch.cuda.device(trainer.device):
+        eng = engine.Engine(w, h, [C0], n, device=trainer.device)   # weight-free: it renders and differentiates the render
+        try:
+            eng.set_grid(fitness.leaf_planes(structure, w, h, n_in))
+            img = torch.empty((n, C0, h, w), dtype=torch.uint8, device="cuda:%d" % trainer.device)
+
+            def render():
+                gb = GenomeBatch(out, config, C0, n_leaves=n_in)
+                eng.render_cppn(gb, img, bg=bg, gradient=1)
+                return gb
+
+            def loss_of(frame_grads):
+                d = img[:, None].expand(n, T, C0, h, w).contiguous()
+                value, _, _, d_grad = trainer._loss_grad(d, n, T, n_repeat, ctypes.c_int64(T * per), True, False, None, requant, step_weights, objective,
+                                                         layer_weights, False, frame_grads)
+                return value, d_grad
+
+            history = np.zeros(iters + 1, np.float64)
+            for i in range(iters):
+                gb = render()
+                history[i], d_grad = loss_of("tied")
+                g_bias, g_resp, g_w = eng.cppn_param_grads(gb, d_grad, bg=bg, gradient=1)
+                for j, (g, m) in enumerate(zip(out, maps)):
+                    n0, n1 = int(gb.node_off[j]), int(gb.node_off[j + 1])
+                    e0, e1 = int(gb.edge_off[n0]), int(gb.edge_off[n1])
+                    if n1 - n0 != len(m["node_key"]) or e1 - e0 != len(m["edge_key"]):
+                        raise RuntimeError("genome %r: the batch holds %d nodes / %d edges, its map %d / %d" % (getattr(g, "key", None), n1 - n0, e1 - e0,
+                                                                                                              len(m["node_key"]), len(m["edge_key"])))
+                    genome_update(g, m, g_bias[n0:n1], g_resp[n0:n1], g_w[e0:e1], lr, params, limits)
+            render()
+            history[iters], _ = loss_of(None)
+            torch.cuda.synchronize(trainer.device)
+            images = img.cpu().numpy()
+        finally:
+            eng.close()
+    return out, history, images
+
+
+__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update"]

@@ -4,6 +4,8 @@
 
     python examples/evolve_illusion.py -o results -g 5 [-m model.npz] [--size small|big|256] [-s 1] [-c 3]
     python -m torch.distributed.run --nproc-per-node 8 examples/evolve_illusion.py ...   (population sharded over GPUs)
+    python examples/evolve_illusion.py -g 5 --refine 4 --refine_iters 5    (Lamarckian step: after every generation the parameters of
+        the 4 best genomes are replaced by those `train.refine_genomes` climbs to, before reproduction; gradient = 1 renders only)
 """
 import argparse
 import os
@@ -28,6 +30,8 @@ def main():
     ap.add_argument("--gradient", "-g1", type=int, default=1)
     ap.add_argument("--generations", "-g", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--refine", type=int, default=0, help="refine the parameters of this many of the best genomes after every generation (0: off)")
+    ap.add_argument("--refine_iters", type=int, default=5, help="ascent steps of train.refine_genomes per generation")
     a = ap.parse_args()
     w, h = {"small": (160, 120), "big": (640, 480)}.get(a.size) or (int(a.size), int(a.size))
     channels = [int(c) for c in a.channels.split(",")]
@@ -39,6 +43,27 @@ def main():
     def eval_genomes(genomes, config):
         fitness.get_fitnesses_neat(a.structure, genomes, a.model, config, w, h, channels, c_dim=a.color_space,
                                    best_dir=a.output_dir, gradient=a.gradient)
+        if a.refine > 0 and a.refine_iters > 0:
+            refine_best(genomes, config)
+
+    trainer = []
+
+    def refine_best(genomes, config):
+        """The Lamarckian step: the a.refine best of the generation keep key, structure and fitness and take the refined parameters.
+        Every rank refines the same genomes with the same deterministic calls, so the populations stay identical."""
+        from evolutionary_illusion_generator_amd import train
+        if a.gradient != 1:
+            raise SystemExit("--refine needs the gradient = 1 render (the palette and the rounded gray are not differentiable)")
+        best = sorted((g for _, g in genomes), key=lambda g: -g.fitness)[:a.refine]
+        if not trainer:
+            trainer.append(train.PredNetTrainer(a.model, channels, w, h, a.refine, 22))
+        refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters)
+        for g, r in zip(best, refined):
+            for k, n in r.nodes.items():
+                g.nodes[k].bias, g.nodes[k].response = n.bias, n.response
+            for k, c in r.connections.items():
+                g.connections[k].weight = c.weight
+        print("refined %d genomes: stand-in loss %.6e -> %.6e" % (len(best), history[0], history[-1]))
 
     p = neat.Population(config, seed=a.seed)  # identical on every rank: same seed, same all-gathered fitness
     p.add_reporter(neat.StdOutReporter(True))

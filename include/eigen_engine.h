@@ -151,6 +151,24 @@ int eigen_render_cppn(eigen_engine* e, const eigen_genome_batch* h_genomes, int3
  * d_nodes: float64 [n_genomes][c_out][H*W].  Used by the import shim pytorch_neat.pytorch_neat.cppn. */
 int eigen_eval_cppn_nodes(eigen_engine* e, const eigen_genome_batch* h_genomes, double* d_nodes, void* stream);
 
+/* The backward pass through eigen_render_cppn's gradient = 1 render ("CPPN parameter gradients"): the gradient
+ * of a loss by every bias, response and connection weight of the batch, from its gradient by the images.
+ *   d_image_grad: device float, d loss / d (byte / 255) of image g at d_image_grad + g * g_bstride as [c_dim][H][W] (what
+ *     eigen_trainer_loss_grad_frames returns); g_bstride in floats, >= C*H*W; floats between the images are never read.
+ *   The forward is the render's arithmetic, so the node values are the render's bits.  The gradient passes straight through the
+ *   uint8 quantisation where the byte follows the node: the pixel is not background (plane 0 != -1) and t = trunc(255 v) lies in
+ *   [0, 255].  Elsewhere (the fill, the low-byte wrap, NaN) the seed is zero.  bg does not enter the result.
+ *   h_grad_bias [total_nodes], h_grad_resp [total_nodes], h_grad_w [total_edges]: host float64, in the batch's own layout, valid on
+ *   return (the call synchronises the stream).  An edge from the constant-1 leaf gets its gradient like any other.
+ *   The pixels are summed in a fixed order without atomics: two calls give the same bits, and the bits of a genome do not depend on
+ *   the batch it is in or on its place in it.
+ * Errors: EIGEN_ERR_STATE no grid; EIGEN_ERR_INVALID gradient != 1 (the palette, the rounded gray and the h,s,v renderer are not
+ * differentiable here), a NULL pointer, g_bstride < C*H*W, and the genome checks of eigen_render_cppn; EIGEN_ERR_CAPACITY a genome
+ * whose node values and adjoints need more than 160 KiB of LDS. */
+int eigen_cppn_param_grads(eigen_engine* e, const eigen_genome_batch* h_genomes, int32_t bg, int32_t gradient,
+                           const float* d_image_grad, int64_t g_bstride,
+                           double* h_grad_bias, double* h_grad_resp, double* h_grad_w, void* stream);
+
 /* Replaces test_prednet (generate_illusion.py:533-537, fitness_calculator.py:487-491) for a batch: state
  * reset, n_repeat steps on the constant frame, then extension steps feeding the prediction back; runs
  * n_steps <= n_repeat + n_ext steps in total.  The quantised prediction of every step t >= first_out_step
