@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 from evolutionary_illusion_generator_amd import genome as genome_mod
 from evolutionary_illusion_generator_amd import synth, weights
 from evolutionary_illusion_generator_amd.engine import PAIR_POPULATION, PAIR_SINGLE, Engine
+from tests.flow_config_support import blocky_pairs as _blocky_pairs, textured_pairs as _textured_pairs
 
 
 def _eng(w, h, ch, B, **kw):
@@ -177,20 +178,6 @@ def test_prednet_rollout_frames_bit_exact(cuda, oracle_lib, w, h, ch, requant, m
     e.prednet_rollout(d_img, len(pop), 21, 19, d2)
     torch.cuda.synchronize()
     assert np.array_equal(d2.cpu().numpy(), got[:, 19:21])
-
-
-def _textured_pairs(rng, B, c, h, w):
-    """Smooth random textures and a sub-pixel-shifted, slightly perturbed copy (uint8 planar)."""
-    from numpy.fft import irfft2, rfft2
-    a = rng.normal(0, 1, (B, c, h, w))
-    fy, fx = np.meshgrid(np.fft.fftfreq(h), np.fft.rfftfreq(w), indexing="ij")
-    filt = np.exp(-(fy ** 2 + fx ** 2) * 60.0)
-    base = irfft2(rfft2(a) * filt, s=(h, w))
-    sh = irfft2(rfft2(a) * filt * np.exp(-2j * np.pi * (fy * 0.12 + fx * -0.17)), s=(h, w))
-    def q(v):
-        v = (v - v.min()) / (v.max() - v.min())
-        return (v * 255).astype(np.uint8)
-    return q(base), q(sh)
 
 
 @pytest.mark.parametrize("w,h,c", [(64, 64, 1), (160, 120, 3), (96, 40, 3)])
@@ -522,18 +509,7 @@ def test_flow_rare_branches_bit_exact(cuda, oracle_lib):
     rng = np.random.default_rng(77)
     lost_total = 0
     for (w, h, c, B) in [(96, 72, 1, 24), (40, 36, 3, 8), (160, 120, 3, 8)]:
-        i0 = np.zeros((B, c, h, w), np.uint8)
-        i1 = np.zeros((B, c, h, w), np.uint8)
-        for b in range(B):
-            base = rng.integers(0, 256, (c, h // 4 + 12, w // 4 + 12)).astype(np.float64)
-            big = np.kron(base, np.ones((1, 4, 4)))[:, :h + 40, :w + 40]                    # blocky texture: strong corners
-            big = (big + np.roll(big, 1, 1) + np.roll(big, 1, 2)) / 3.0
-            sy, sx = rng.integers(0, 6, 2) if b % 4 else rng.integers(0, 3, 2) * 13                # 0..5 px, sometimes 13/26 px
-            a = big[:, 30:30 + h, 30:30 + w]
-            bimg = big[:, 30 - sy:30 - sy + h, 30 - sx:30 - sx + w]
-            noise = rng.normal(0, [0, 3, 12][b % 3], a.shape)
-            i0[b] = np.clip(a, 0, 255)
-            i1[b] = np.clip(bimg + noise, 0, 255)
+        i0, i1 = _blocky_pairs(rng, B, c, h, w)
         e = _eng(w if w % 2 == 0 else w + 1, h if h % 2 == 0 else h + 1, [c, 4], B)
         d0, d1 = torch.from_numpy(i0).to(cuda), torch.from_numpy(i1).to(cuda)
         dv = torch.zeros((B, e.K, 4), dtype=torch.float32, device=cuda)
