@@ -1,6 +1,7 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
-// the kernels of train_kernels.h and, for the frame gradient and the refinement of stills, frame_grad_kernels.h.
+// the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for the flow objective
+// flow_obj_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include "../../include/eigen_engine.h"
 #include "train_kernels.h"
 #include "frame_grad_kernels.h"
+#include "flow_obj_kernels.h"
 
 using namespace eigt;
 
@@ -87,6 +89,8 @@ struct eigen_trainer {
     double *d_spart = nullptr, *d_step = nullptr;  // per-step loss: partials [max_steps][STEP_LOSS_BLOCKS], losses [max_steps]
     double* d_err = nullptr;                       // error-unit means err[s][l]: [max_steps][n_layers]
     float* d_absmax = nullptr;                     // eigen_trainer_still_step: max |g| of every image, [max_batch]
+    // the flow objective's float64 planes, one batch each: Ix, Iy, It [3][B H W]; q [2][B H W]; the masked value [B H W]
+    double *f_planes = nullptr, *f_q = nullptr, *f_mv = nullptr;
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -233,6 +237,7 @@ int allocate(eigen_trainer* t)
     add((void**)&t->d_part, LOSS_BLOCKS * 8); add((void**)&t->d_loss, 8);
     add((void**)&t->d_spart, T * STEP_LOSS_BLOCKS * 8); add((void**)&t->d_step, T * 8); add((void**)&t->d_err, T * L * 8);
     add((void**)&t->d_absmax, B * 4);
+    add((void**)&t->f_planes, 3 * B * t->ly[0].HW * 8); add((void**)&t->f_q, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_mv, B * t->ly[0].HW * 8);
     for (int l = 0; l < L; ++l) {
         TLayer& y = t->ly[l];
         const long long CHW = y.CHW();
@@ -375,9 +380,67 @@ void upper_errors(eigen_trainer* t, hipStream_t st, int slot, int n, int B, doub
         reduce_steps(TERM_SUM, t, st, t->ly[l].E_at(slot, B), nullptr, 0ll, 2 * t->ly[l].CHW(), n, B, (double)(B * 2 * t->ly[l].CHW()), err + l, t->L);
 }
 
+// The flow objective's settings once checked: the window, the direction field and the mask (device, may be null) and the mask's count
+struct FlowSpec {
+    int r = 0;
+    double eps = 0.0;
+    const float* dir = nullptr;
+    const uint8_t* mask = nullptr;
+    long long n_mask = 0;
+};
+
+// The settings of a flow call against the handle's image, before anything is launched.  The direction field and the mask are read back
+// to the host: every d must be finite, and kappa needs the mask's count.
+int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, FlowSpec& f)
+{
+    if (!flow) return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs its settings");
+    if (flow->radius < 1 || flow->radius > FLOW_MAX_R) return tfail(EIGEN_ERR_INVALID, "flow radius %d outside 1 .. %d", flow->radius, FLOW_MAX_R);
+    if (!std::isfinite(flow->eps) || !(flow->eps > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow eps %g: must be finite and > 0", flow->eps);
+    const long long HW = t->ly[0].HW;
+    f.r = flow->radius; f.eps = flow->eps; f.dir = d_dir; f.mask = d_mask; f.n_mask = HW;
+    TCHK(hipSetDevice(t->cfg.device));
+    if (d_dir) {
+        std::vector<float> d(2 * HW);
+        TCHK(hipMemcpy(d.data(), d_dir, 2 * HW * 4, hipMemcpyDeviceToHost));
+        for (long long i = 0; i < 2 * HW; ++i) if (!std::isfinite(d[i])) return tfail(EIGEN_ERR_INVALID, "flow direction element %lld is not finite", i);
+    }
+    if (d_mask) {
+        std::vector<uint8_t> m(HW);
+        TCHK(hipMemcpy(m.data(), d_mask, HW, hipMemcpyDeviceToHost));
+        f.n_mask = 0;
+        for (long long i = 0; i < HW; ++i) f.n_mask += m[i] != 0;
+        if (f.n_mask == 0) return tfail(EIGEN_ERR_INVALID, "the flow mask counts no pixel");
+    }
+    return EIGEN_OK;
+}
+
+// The flow stage of one prediction / reference pair per sample (eigen_trainer_flow_term states the arithmetic): the planes, the tiled
+// solve, then what is wanted of the value (d_value, through the STEP_LOSS_BLOCKS partials at part), the flow and the seed.
+void flow_stage(eigen_trainer* t, hipStream_t st, int B, const float* pred, long long p_bstride, const uint8_t* ref, long long r_bstride, const FlowSpec& f,
+                double kappa, double* part, double* d_value, double* d_flow, float* d_seed, long long s_bstride, int accumulate)
+{
+    const TLayer& y = t->ly[0];
+    const long long n = (long long)B * y.HW;
+    ew(st, tflow_prep_kernel, n, pred, p_bstride, ref, r_bstride, y.C, y.H, y.W, n, t->f_planes);
+    const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
+    hipLaunchKernelGGL(tflow_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, n, y.H, y.W, f.r, f.eps, f.dir, f.mask, t->f_q, t->f_mv, d_flow);
+    if (d_value) {
+        hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, part);
+        hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), d_value, 1);
+    }
+    if (d_seed)
+        hipLaunchKernelGGL(tflow_seed_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, n, y.H, y.W, y.C, f.r, kappa, d_seed,
+                           s_bstride, accumulate);
+}
+
 // The loss of one loss_grad call: the weights of its terms and the seeds they put into the backward pass.
 struct Objective {
     bool by_error = false;
+    bool by_flow = false;
+    FlowSpec flow;                      // by_flow
+    double* h_terms = nullptr;          // by_flow: host, T - 1 terms, may be null
+    double weight(int s) const { return step_w ? step_w[s] : 1.0; }
+    double total_weight() const { return step_w ? sum_w : (double)(T - 1); }
     const double* step_w = nullptr;     // host, T - 1 weights; NULL: all one
     double sum_w = 0.0;                 // of step_w
     double lam[EIGEN_MAX_LAYERS] = {};  // layer weights of the error-unit objective
@@ -401,6 +464,7 @@ struct Objective {
 // o from the call's arguments: the objective, the layer weights (NULL is L_0, [1, 0, ...]; checked whenever given), the step weights
 int make_objective(const eigen_trainer* t, int32_t objective, const double* h_layer_w, const double* h_step_w, int T, int B, Objective& o)
 {
+    if (objective == EIGEN_OBJ_FLOW) return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs the settings eigen_trainer_loss_grad_flow takes");
     if (objective != EIGEN_OBJ_MSE && objective != EIGEN_OBJ_ERROR) return tfail(EIGEN_ERR_INVALID, "objective %d is neither EIGEN_OBJ_MSE nor EIGEN_OBJ_ERROR", objective);
     o.by_error = objective == EIGEN_OBJ_ERROR; o.step_w = h_step_w; o.T = T; o.B = B; o.ly = t->ly;
     if (h_layer_w || o.by_error) {
@@ -436,7 +500,7 @@ int reduce_losses(eigen_trainer* t, hipStream_t st, const Objective& o, const ui
         reduce_steps(TERM_ABS, t, st, P0, d_frames + C0HW, bstride, C0HW, T - 1, B, (double)(B * 2 * C0HW), t->d_err, t->L);
         upper_errors(t, st, 1, T - 1, B, t->d_err);
     }
-    if (T < 2 || o.by_error) return EIGEN_OK;  // the error objective's loss is formed from the table, on the host
+    if (T < 2 || o.by_error || o.by_flow) return EIGEN_OK;  // the error objective's loss is formed from the table, the flow objective's from the terms the backward steps leave, on the host
     if (o.step_w) {
         reduce_steps(TERM_SQ, t, st, P0, d_frames + C0HW, bstride, C0HW, T - 1, B, (double)(B * C0HW), t->d_step, 1);
     } else {
@@ -458,6 +522,14 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
         const float* P = y.P_at(s + 1, B);
         float* dV = y.dV_at(s, B);
         const uint8_t* xn = (l == 0 && s < T - 1) ? d_frames + (long long)(s + 1) * CHW : nullptr;
+        if (o.by_flow && xn) {
+            // term s: its value into d_step[s] and its seed added to dP0_s, which tpact_bwd then masks; a term of weight zero is not computed
+            const double w = o.weight(s);
+            if (w != 0.0)
+                flow_stage(t, st, B, P, CHW, xn, bstride, o.flow, (w / o.total_weight()) / (double)(B * o.flow.n_mask), t->d_spart + (long long)s * STEP_LOSS_BLOCKS,
+                           t->d_step + s, nullptr, y.dPn, CHW, 1);
+            xn = nullptr;
+        }
         const float scale = !xn ? 0.f : o.by_error ? o.err_scale(s, 0) : o.loss_scale(s);
         // an error-unit term whose seed is zero is left out, not added as +0.0f (which would turn a -0 gradient into +0)
         if (o.by_error && scale == 0.f) xn = nullptr;
@@ -510,7 +582,8 @@ void frame_grad_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s
     const TLayer& y = t->ly[0];
     const int B = o.B;
     const long long CHW = y.CHW();
-    const float scale = s < 1 ? 0.f : o.by_error ? o.err_scale(s - 1, 0) : o.loss_scale(s - 1);
+    // under the flow objective the frames are constants of every term: no target path
+    const float scale = s < 1 || o.by_flow ? 0.f : o.by_error ? o.err_scale(s - 1, 0) : o.loss_scale(s - 1);
     const int has_input = s < n_fed, has_target = s >= 1 && scale != 0.f;
     float* out = fg.p + (long long)s * fg.tstride;
     const int acc = fg.tstride == 0;
@@ -559,6 +632,20 @@ int read_loss(eigen_trainer* t, hipStream_t st, const Objective& o, bool want_ta
         TCHK(hipMemcpyAsync(tab.data(), t->d_err, tab.size() * 8, hipMemcpyDeviceToHost, st));
         TCHK(hipStreamSynchronize(st));
         if (h_layer_err) memcpy(h_layer_err, tab.data(), tab.size() * 8);
+    }
+    if (o.by_flow && T >= 2) {
+        // sum_s w_s f_s / sum_s w_s in step order; a term of weight zero was not computed and is 0.0
+        std::vector<double> f(T - 1);
+        TCHK(hipMemcpyAsync(f.data(), t->d_step, (T - 1) * 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+        double acc = 0.0;
+        for (int s = 0; s < T - 1; ++s) {
+            if (o.weight(s) == 0.0) f[s] = 0.0;
+            acc += o.weight(s) * f[s];
+        }
+        if (o.h_terms) memcpy(o.h_terms, f.data(), (T - 1) * 8);
+        if (h_loss) *h_loss = acc / o.total_weight();
+        return EIGEN_OK;
     }
     if (!h_loss) return EIGEN_OK;
     if (o.by_error && T >= 2) {
@@ -653,9 +740,10 @@ int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n
     return copy_tables(t, n_tensors, false, t->grd, h_tensors);
 }
 
-int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
-                                   int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
-                                   double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, void* stream)
+int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                 int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                 double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow,
+                                 const float* d_dir, const uint8_t* d_mask, double* h_terms, void* stream)
 {
     int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, t ? t->cfg.max_steps : 0);
     if (rc) return rc;
@@ -670,8 +758,17 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
         if (g_bstride < extent) return tfail(EIGEN_ERR_INVALID, "g_bstride %lld is smaller than one sample's gradient (%lld floats)", (long long)g_bstride, extent);
     }
     Objective o;
-    rc = make_objective(t, objective, h_layer_w, h_step_w, T, B, o);
+    const bool by_flow = objective == EIGEN_OBJ_FLOW;
+    if (!by_flow && (flow || d_dir || d_mask)) return tfail(EIGEN_ERR_INVALID, "flow settings, direction and mask go with EIGEN_OBJ_FLOW only");
+    // the step and layer weights follow the same rules under every objective
+    rc = make_objective(t, by_flow ? (int32_t)EIGEN_OBJ_MSE : objective, h_layer_w, h_step_w, T, B, o);
     if (rc) return rc;
+    if (by_flow) {
+        rc = check_flow(t, flow, d_dir, d_mask, o.flow);
+        if (rc) return rc;
+        o.by_flow = true;
+        o.h_terms = h_terms;
+    }
     hipStream_t st = (hipStream_t)stream;
     rc = start_state(t, st, B, reset);
     if (rc) return rc;
@@ -695,6 +792,41 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
     t->state_batch = B;
     t->state_slot = T;
     return read_loss(t, st, o, want_table, h_loss, h_layer_err);
+}
+
+int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                   int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                   double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, void* stream)
+{
+    // it has nowhere to take the flow settings from: the objective is refused here, ahead of every other check of the call
+    if (objective == EIGEN_OBJ_FLOW) return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs the settings eigen_trainer_loss_grad_flow takes");
+    return eigen_trainer_loss_grad_flow(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_w, objective, h_layer_w, h_loss, h_layer_err, d_pred,
+                                        d_frame_grad, g_bstride, g_tstride, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int eigen_trainer_flow_term(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
+                            const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow,
+                            float* d_seed, int64_t s_bstride, void* stream)
+{
+    if (!t || !d_pred || !d_ref || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
+    if (batch > t->cfg.max_batch) return tfail(EIGEN_ERR_CAPACITY, "batch %d exceeds the trainer's %d", batch, t->cfg.max_batch);
+    const long long C0HW = t->ly[0].CHW();
+    if (p_bstride < C0HW || r_bstride < C0HW || (d_seed && s_bstride < C0HW))
+        return tfail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", C0HW);
+    if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale %g is not finite", scale);
+    FlowSpec f;
+    const int rc = check_flow(t, flow, d_dir, d_mask, f);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    flow_stage(t, st, batch, d_pred, p_bstride, d_ref, r_bstride, f, scale / (double)(batch * f.n_mask), t->d_spart, h_value ? t->d_step : nullptr, d_flow, d_seed,
+               s_bstride, 0);
+    TCHK(hipGetLastError());
+    if (h_value) {
+        TCHK(hipMemcpyAsync(h_value, t->d_step, 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+    }
+    return EIGEN_OK;
 }
 
 int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,

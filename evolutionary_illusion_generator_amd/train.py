@@ -1,7 +1,8 @@
 """PredNet training on frame sequences (include/eigen_engine.h eigen_trainer_*).
 
 Next-frame MSE of the float prediction or, per call, PredNet's own objective on the error units (``objective="error"``: L_0 by
-default, L_all with ``layer_weights=[1, 0.1, ...]``), full backprop through time within a call, Adam as chainer defines it; every kernel is
+default, L_all with ``layer_weights=[1, 0.1, ...]``) or the displacement a dense Lucas-Kanade solve finds between the next frame and
+the prediction (``objective="flow"`` with a ``FlowObjective``), full backprop through time within a call, Adam as chainer defines it; every kernel is
 HIP for gfx950 (csrc/prednet_train.hip), there is no CPU or PyTorch fallback.  The trained weights are a plain
 ``{name: float32 array}`` table, usable as ``model_name`` anywhere the fitness path takes one, and
 ``weights.save_chainer_npz`` writes them as a chainer npz file.
@@ -13,6 +14,11 @@ import numpy as np
 from . import engine
 from .engine import EngineError, _check, _ptr, _stream_arg
 from .weights import tensor_names, tensor_shapes
+
+
+class FlowSettings(ctypes.Structure):
+    """eigen_flow_settings"""
+    _fields_ = [("radius", ctypes.c_int32), ("reserved", ctypes.c_int32), ("eps", ctypes.c_double)]
 
 
 class TrainerConfig(ctypes.Structure):
@@ -34,6 +40,10 @@ def _bind(lib):
                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.eigen_trainer_loss_grad_frames.argtypes = lib.eigen_trainer_loss_grad_obj.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
+    lib.eigen_trainer_loss_grad_flow.argtypes = lib.eigen_trainer_loss_grad_frames.argtypes[:-1] + [ctypes.c_void_p] * 5
+    lib.eigen_trainer_flow_term.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                            ctypes.c_void_p]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_evaluate_err.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -49,8 +59,93 @@ def _bind(lib):
 
 HYPER = ("alpha", "beta1", "beta2", "eps")
 SEQ_PARTS = ("h", "c", "P")
-OBJECTIVES = {"mse": 0, "error": 1}  # eigen_objective
+OBJECTIVES = {"mse": 0, "error": 1, "flow": 2}  # eigen_objective
 FRAME_GRADS = (None, "frames", "tied")
+FLOW_MAX_RADIUS = 16
+FLOW_DIRECTIONS = ("tangent", "radial", "horizontal", "vertical")
+
+
+def flow_direction(kind, w, h):
+    """A direction field for ``FlowObjective``: float32 [2, h, w], the x then the y component of a unit vector per pixel.
+    "horizontal" is (1, 0) and "vertical" (0, 1) everywhere.  "radial" points away from the image centre ((w - 1) / 2, (h - 1) / 2):
+    (dx, dy) / |(dx, dy)| with (dx, dy) the pixel's offset from it; "tangent" is that turned counter-clockwise in image coordinates,
+    (-dy, dx) / |(dx, dy)|.  Both are zero at the centre pixel, where an odd-sized image has one."""
+    if kind not in FLOW_DIRECTIONS:
+        raise ValueError("kind must be one of %s, got %r" % (", ".join(FLOW_DIRECTIONS), kind))
+    w, h = int(w), int(h)
+    if w < 1 or h < 1:
+        raise ValueError("w and h must be >= 1")
+    out = np.zeros((2, h, w), np.float64)
+    if kind == "horizontal":
+        out[0] = 1.0
+    elif kind == "vertical":
+        out[1] = 1.0
+    else:
+        dy, dx = np.mgrid[0:h, 0:w].astype(np.float64)
+        dx -= (w - 1) / 2.0
+        dy -= (h - 1) / 2.0
+        norm = np.sqrt(dx * dx + dy * dy)
+        norm[norm == 0] = 1.0
+        out[0], out[1] = (dx / norm, dy / norm) if kind == "radial" else (-dy / norm, dx / norm)
+    return out.astype(np.float32)
+
+
+class FlowObjective:
+    """The settings of ``objective="flow"`` ("The flow objective"): a dense, regularised Lucas-Kanade solve from
+    the reference frame to the prediction over windows of Chebyshev radius `radius`, truncated at the border, with `eps` added to the
+    diagonal of every 2x2 system.  direction None: the term is the mean squared displacement; direction float32 [2, H, W] (x then y
+    component, ``flow_direction``): the mean displacement along it.  mask: [H, W], zero = the pixel is not counted (None: all are).
+
+    The defaults are a design choice: radius 7 is a 15-pixel window, the fitness path's ``lk_win``; eps 1e-2 is in units of summed
+    squared gradients of images in [0, 1] (a 15 x 15 window over an edge of contrast 0.1 sums to about 0.1), so it damps flat windows
+    and leaves textured ones alone.  ValueError: radius outside 1 .. 16, eps not finite or <= 0, a direction that is not
+    [2, H, W] or not finite, a mask that is not [H, W] or counts no pixel."""
+
+    def __init__(self, radius=7, eps=1e-2, direction=None, mask=None):
+        if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= FLOW_MAX_RADIUS:
+            raise ValueError("radius must be an integer in 1 .. %d, got %r" % (FLOW_MAX_RADIUS, radius))
+        eps = float(eps)
+        if not (np.isfinite(eps) and eps > 0):
+            raise ValueError("eps must be finite and > 0, got %r" % (eps,))
+        self.radius, self.eps = int(radius), eps
+        self.direction = self.mask = None
+        if direction is not None:
+            d = np.ascontiguousarray(direction, dtype=np.float32)
+            if d.ndim != 3 or d.shape[0] != 2:
+                raise ValueError("direction must be [2, H, W], got shape %s" % (d.shape,))
+            if not np.isfinite(d).all():
+                raise ValueError("direction must be finite")
+            self.direction = d
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if m.ndim != 2:
+                raise ValueError("mask must be [H, W], got shape %s" % (m.shape,))
+            if not m.any():
+                raise ValueError("the mask counts no pixel")
+            self.mask = m
+        self._dev = {}
+
+    def settings(self):
+        return FlowSettings(self.radius, 0, self.eps)
+
+    def on_device(self, torch, device, h, w):
+        """(direction, mask) as device tensors (None where not set), uploaded once per device; ValueError if they are not [.., h, w]"""
+        for name, a in (("direction", self.direction), ("mask", self.mask)):
+            if a is not None and tuple(a.shape[-2:]) != (h, w):
+                raise ValueError("%s is %s, the trainer's image is [%d, %d]" % (name, a.shape, h, w))
+        if device not in self._dev:
+            up = lambda a: None if a is None else torch.from_numpy(a).cuda(device)
+            self._dev[device] = (up(self.direction), up(self.mask))
+        return self._dev[device]
+
+
+def _check_flow(objective, flow):
+    """`flow` goes with objective="flow" and with nothing else"""
+    if objective == "flow":
+        if not isinstance(flow, FlowObjective):
+            raise ValueError("objective='flow' needs flow=FlowObjective(...), got %r" % (flow,))
+    elif flow is not None:
+        raise ValueError("flow is given but the objective is %r" % (objective,))
 
 
 def check_layer_weights(layer_weights, n_layers):
@@ -272,12 +367,16 @@ class PredNetTrainer:
         tab = np.zeros((max(int(d.shape[1]) - 1, 1), len(self.channels)), np.float64) if table else None
         return tab, self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
 
-    def _loss_grad(self, d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights, layer_errors, frame_grads):
+    def _loss_grad(self, d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights, layer_errors, frame_grads, flow=None):
         """The call behind forward_backward, on frames already on the device: (loss, table or None, d_pred or None, d_grad or None), the
-        last two device tensors.  Every argument is checked before anything is launched."""
+        last two device tensors.  Every argument is checked before anything is launched.  Under objective="flow" the float64 [T - 1]
+        terms of the call are left in ``self.last_flow_terms``."""
         torch = self._torch
         if objective not in OBJECTIVES:
             raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
+        _check_flow(objective, flow)
+        by_flow = objective == "flow"
+        d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w) if by_flow else (None, None)
         lam = check_layer_weights(layer_weights, len(self.channels))
         w_arr = None
         if step_weights is not None:
@@ -290,14 +389,21 @@ class PredNetTrainer:
         args = [self._h, _ptr(d), bstride, ctypes.c_int32(n), ctypes.c_int32(T), ctypes.c_int32(n_fed), ctypes.c_int32(int(bool(requant))),
                 ctypes.c_int32(int(bool(reset))), ctypes.c_void_p(w_arr.ctypes.data if w_arr is not None and w_arr.size else None),
                 ctypes.c_int32(OBJECTIVES[objective]), _ptr(lam), ctypes.byref(loss), _ptr(table), _ptr(d_pred)]
-        d_grad = None
-        if frame_grads is None:
-            _check(self.lib.eigen_trainer_loss_grad_obj(*args, _stream_arg(stream)))
-        else:
+        d_grad, g_b, g_t = None, 0, 0
+        if frame_grads is not None:
             img = tuple(d.shape[2:])
             d_grad = torch.empty((n,) + (() if frame_grads == "tied" else (T,)) + img, dtype=torch.float32, device=d.device)
             per = int(np.prod(img))
             g_b, g_t = (per, 0) if frame_grads == "tied" else (T * per, per)
+        if by_flow:
+            terms = np.zeros(max(T - 1, 1), np.float64)
+            cfg = flow.settings()
+            _check(self.lib.eigen_trainer_loss_grad_flow(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask),
+                                                         _ptr(terms), _stream_arg(stream)))
+            self.last_flow_terms = terms[:T - 1]
+        elif frame_grads is None:
+            _check(self.lib.eigen_trainer_loss_grad_obj(*args, _stream_arg(stream)))
+        else:
             _check(self.lib.eigen_trainer_loss_grad_frames(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), _stream_arg(stream)))
         if table is not None:
             table = table[:T - 1]
@@ -305,7 +411,7 @@ class PredNetTrainer:
         return value, table, d_pred, d_grad
 
     def forward_backward(self, frames, reset=True, pred=False, stream=None, n_fed=None, requant=False, step_weights=None, objective="mse",
-                         layer_weights=None, layer_errors=False, frame_grads=None):
+                         layer_weights=None, layer_errors=False, frame_grads=None, flow_terms=False, flow=None):
         """Loss of frames uint8 [n, T, C, H, W] (numpy or a device tensor, n <= batch) and the gradients, kept on the device
         (``grads()``).  reset=False continues from the state the previous call left (the same n), as a constant.
         pred=True also returns the float predictions P0 [n, T, C, H, W] (numpy).
@@ -323,14 +429,48 @@ class PredNetTrainer:
         frame_grads: None, or the gradient of the loss by the frames (as floats, byte / 255), appended last as a float32 numpy
         array: "frames" gives d loss / d frame t, [n, T, C, H, W] (the input path of every step that read its frame plus the
         target path of every frame but the first); "tied" gives their sum over t, [n, C, H, W], the gradient by a still that
-        is repeated T times.  Nothing else the call returns or leaves on the device changes."""
+        is repeated T times.  Nothing else the call returns or leaves on the device changes.
+
+        objective "flow" with flow=FlowObjective(...) (required then, refused otherwise): term s is the displacement a dense
+        Lucas-Kanade solve finds from frame s + 1, a constant of the graph, to prediction s: its mean square, or its mean along the
+        direction field ("The flow objective").  The frame gradient is then the input path alone.
+        flow_terms=True (flow only) appends the float64 [T - 1] terms last; a term of weight zero is not computed and reads 0."""
         if frame_grads not in FRAME_GRADS:
             raise ValueError("frame_grads must be None, 'frames' or 'tied', got %r" % (frame_grads,))
+        if flow_terms and objective != "flow":
+            raise ValueError("flow_terms goes with objective='flow'")
+        _check_flow(objective, flow)
         d, n, T, n_fed, bstride = self._call_args(frames, n_fed)
         value, table, d_pred, d_grad = self._loss_grad(d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights,
-                                                       layer_errors, frame_grads)
+                                                       layer_errors, frame_grads, flow=flow)
         out = (value,) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table,) if layer_errors else ()) + ((d_grad.cpu().numpy(),) if frame_grads else ())
+        out += (self.last_flow_terms,) if flow_terms else ()
         return out[0] if len(out) == 1 else out
+
+    def flow_term(self, pred, ref, flow, scale=1.0):
+        """The flow stage alone (eigen_trainer_flow_term), with the kernels a training call runs: pred float32 [n, C, H, W], the
+        prediction; ref uint8 [n, C, H, W], the reference frame; n <= batch.  -> (value, u, seed): the term, the flow float64
+        [n, 2, H, W] in pixels per frame (x then y) and scale * d value / d pred as float32 [n, C, H, W]."""
+        torch = self._torch
+        if not isinstance(flow, FlowObjective):
+            raise ValueError("flow must be a FlowObjective, got %r" % (flow,))
+        if not np.isfinite(scale):
+            raise ValueError("scale must be finite, got %r" % (scale,))
+        shp = (self.channels[0], self.h, self.w)
+        dev = "cuda:%d" % self.device
+        p = (pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32))).to(dev).contiguous()
+        r = (ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref))).to(dev).contiguous()
+        if p.dtype != torch.float32 or r.dtype != torch.uint8 or p.dim() != 4 or tuple(p.shape[1:]) != shp or tuple(r.shape) != tuple(p.shape):
+            raise ValueError("pred must be float32 and ref uint8, both [n, %d, %d, %d]; got %s %s and %s %s" % (shp + (p.dtype, tuple(p.shape), r.dtype, tuple(r.shape))))
+        n, per = int(p.shape[0]), int(np.prod(shp))
+        d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w)
+        value = ctypes.c_double(0.0)
+        u = torch.empty((n, 2, self.h, self.w), dtype=torch.float64, device=dev)
+        seed = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
+        cfg = flow.settings()
+        _check(self.lib.eigen_trainer_flow_term(self._h, _ptr(p), ctypes.c_int64(per), _ptr(r), ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_dir),
+                                                _ptr(d_mask), ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(u), _ptr(seed), ctypes.c_int64(per), None))
+        return value.value, u.cpu().numpy(), seed.cpu().numpy()
 
     def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False, layer_errors=False):
         """Forward only, no tape: the mean squared error of every step of frames uint8 [n, T, C, H, W], T of any length, as
@@ -356,10 +496,10 @@ class PredNetTrainer:
         """One Adam step on the current gradients."""
         _check(self.lib.eigen_trainer_adam(self._h, self.alpha, self.beta1, self.beta2, self.eps, _stream_arg(stream)))
 
-    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None, objective="mse", layer_weights=None):
+    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None, objective="mse", layer_weights=None, flow=None):
         """Gradient and one Adam step; returns the loss before the step."""
         loss = self.forward_backward(frames, reset, n_fed=n_fed, requant=requant, step_weights=step_weights, objective=objective,
-                                     layer_weights=layer_weights)
+                                     layer_weights=layer_weights, flow=flow)
         self.adam()
         return loss
 
@@ -422,7 +562,7 @@ class PredNetTrainer:
 
 
 def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, requant=True, objective="mse", layer_weights=None, step_weights=None,
-                  mask=None):
+                  mask=None, flow=None):
     """Gradient ascent on stills: raise how far PredNet's extended prediction leaves a still, the differentiable stand-in for the
     fitness (which scores the flow between the still and that prediction).  -> (uint8 [n, C, H, W] numpy, float64 [iters + 1]).
 
@@ -432,11 +572,14 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
     `objective` under step_weights (None: 0 for the terms s < n_repeat - 1, 1 for the n_ext terms of the extension).  One call
     with reset=True gives the loss and its tied frame gradient; ``eigen_trainer_still_step`` then moves every free pixel by at
     most `step` bytes along the gradient, normalised by the image's largest |g| over the free pixels.  mask: [H, W], zero keeps
-    a pixel as it is (None: every pixel is free).  Everything stays on the device between iterations.
+    a pixel as it is (None: every pixel is free).  Everything stays on the device between iterations.  objective "flow" with
+    flow=FlowObjective(...) climbs the displacement between the still and the extended prediction itself, which is what the fitness
+    scores; the FlowObjective's own mask selects the pixels that are counted, `mask` the pixels that move.
 
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images.  The calls
     OVERWRITE the trainer's weight gradients and its kept sequence state."""
     T = int(n_repeat) + int(n_ext)
+    _check_flow(objective, flow)
     if n_repeat < 1 or n_ext < 1 or iters < 0:
         raise ValueError("n_repeat >= 1, n_ext >= 1 and iters >= 0 required")
     if T > trainer.max_steps:
@@ -464,7 +607,7 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
     def loss_of(frame_grads):
         d = img[:, None].expand(n, T, *img.shape[1:]).contiguous()
         value, _, _, d_grad = trainer._loss_grad(d, n, T, n_repeat, ctypes.c_int64(T * per), True, False, None, requant, step_weights, objective,
-                                                 layer_weights, False, frame_grads)
+                                                 layer_weights, False, frame_grads, flow=flow)
         return value, d_grad
 
     history = np.zeros(iters + 1, np.float64)
@@ -531,7 +674,7 @@ def genome_update(genome, gmap, g_bias, g_resp, g_w, lr, params=PARAM_KINDS, bou
 
 
 def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, iters=10, lr=0.02, requant=True, objective="mse", layer_weights=None,
-                   step_weights=None, bg=1, params=PARAM_KINDS, bounds=None):
+                   step_weights=None, bg=1, params=PARAM_KINDS, bounds=None, flow=None):
     """Gradient ascent on the genomes' own parameters: ``refine_stills``' loss (how far PredNet's extended prediction leaves the still),
     climbed through the CPPN render instead of in pixel space, so that what comes back can be mutated, crossed and rendered at any
     size.  -> (genomes', float64 [iters + 1] history, uint8 [n, C, H, W] images).
@@ -546,12 +689,15 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     them).  FROZEN, i.e. never updated: folded float32 constants (``genome.flatten_genome_map``'s None entries and everything inside a
     folded sub-graph), disabled connections and whatever the outputs do not depend on.
 
+    objective "flow" takes flow=FlowObjective(...) as ``refine_stills`` does.
+
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images, which are the
     render of genomes'.  The calls OVERWRITE the trainer's weight gradients and its kept sequence state."""
     import copy
     from . import fitness
     from .genome import GenomeBatch, flatten_genome_map
     T = int(n_repeat) + int(n_ext)
+    _check_flow(objective, flow)
     if n_repeat < 1 or n_ext < 1 or iters < 0:
         raise ValueError("n_repeat >= 1, n_ext >= 1 and iters >= 0 required")
     if T > trainer.max_steps:
@@ -588,7 +734,7 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
             def loss_of(frame_grads):
                 d = img[:, None].expand(n, T, C0, h, w).contiguous()
                 value, _, _, d_grad = trainer._loss_grad(d, n, T, n_repeat, ctypes.c_int64(T * per), True, False, None, requant, step_weights, objective,
-                                                         layer_weights, False, frame_grads)
+                                                         layer_weights, False, frame_grads, flow=flow)
                 return value, d_grad
 
             history = np.zeros(iters + 1, np.float64)
@@ -612,4 +758,5 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     return out, history, images
 
 
-__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update"]
+__all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update", "FlowObjective",
+           "flow_direction"]

@@ -5,7 +5,8 @@
     python examples/evolve_illusion.py -o results -g 5 [-m model.npz] [--size small|big|256] [-s 1] [-c 3]
     python -m torch.distributed.run --nproc-per-node 8 examples/evolve_illusion.py ...   (population sharded over GPUs)
     python examples/evolve_illusion.py -g 5 --refine 4 --refine_iters 5    (Lamarckian step: after every generation the parameters of
-        the 4 best genomes are replaced by those `train.refine_genomes` climbs to, before reproduction; gradient = 1 renders only)
+        the 4 best genomes are replaced by those `train.refine_genomes` climbs to, before reproduction; gradient = 1 renders only;
+        --objective flow --flow-direction tangent climbs the flow objective instead of the squared error)
 """
 import argparse
 import os
@@ -32,6 +33,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--refine", type=int, default=0, help="refine the parameters of this many of the best genomes after every generation (0: off)")
     ap.add_argument("--refine_iters", type=int, default=5, help="ascent steps of train.refine_genomes per generation")
+    ap.add_argument("--objective", default="mse", choices=["mse", "error", "flow"], help="what --refine climbs")
+    ap.add_argument("--flow-direction", default=None, choices=["tangent", "radial", "horizontal", "vertical"], help="objective flow: the field (default: the mean square)")
+    ap.add_argument("--flow-radius", type=int, default=7)
+    ap.add_argument("--flow-eps", type=float, default=1e-2)
     a = ap.parse_args()
     w, h = {"small": (160, 120), "big": (640, 480)}.get(a.size) or (int(a.size), int(a.size))
     channels = [int(c) for c in a.channels.split(",")]
@@ -57,7 +62,11 @@ def main():
         best = sorted((g for _, g in genomes), key=lambda g: -g.fitness)[:a.refine]
         if not trainer:
             trainer.append(train.PredNetTrainer(a.model, channels, w, h, a.refine, 22))
-        refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters)
+        flow = None
+        if a.objective == "flow":
+            inside = (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype("uint8")
+            flow = train.FlowObjective(a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), inside)
+        refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters, objective=a.objective, flow=flow)
         for g, r in zip(best, refined):
             for k, n in r.nodes.items():
                 g.nodes[k].bias, g.nodes[k].response = n.bias, n.response

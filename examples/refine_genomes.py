@@ -8,6 +8,7 @@ rendered at any size.  This script takes a seeded CPPN population, refines the b
 fitness of each before and after.  Whether the fitness follows the stand-in is an observation to make, not a property.
 
     python examples/refine_genomes.py [-m model.npz] [--size small|N] [-s 1] [-c 3] [--pop 16] [-k 4] [--iters 10] [--lr 0.02]
+    python examples/refine_genomes.py --objective flow --flow-direction tangent [--flow-radius 7] [--flow-eps 1e-2]
     python examples/refine_genomes.py -o refined      (PNGs, and best.png / enhanced.png ... of the best refined genome)
 """
 import argparse
@@ -30,6 +31,13 @@ def score(images, model, structure, w, h, channels):
     return fit, np.array([len(v) for v in vecs])
 
 
+def flow_of(a, w, h, mask=None):
+    """the FlowObjective of the command line (None under another objective); the term counts the pixels of `mask`"""
+    if a.objective != "flow":
+        return None
+    return train.FlowObjective(a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", "-m", default="synthetic", help="chainer npz weights, or synthetic[:seed]")
@@ -43,7 +51,10 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--lr", type=float, default=0.02, help="largest move of a parameter per iteration")
     ap.add_argument("--params", default="weight,bias,response", help="which kinds of parameters move")
-    ap.add_argument("--objective", default="mse", choices=["mse", "error"])
+    ap.add_argument("--objective", default="mse", choices=["mse", "error", "flow"])
+    ap.add_argument("--flow-direction", default=None, choices=list(train.FLOW_DIRECTIONS), help="objective flow: climb the displacement along this field (default: its mean square)")
+    ap.add_argument("--flow-radius", type=int, default=7, help="objective flow: the window is 2 R + 1 pixels wide")
+    ap.add_argument("--flow-eps", type=float, default=1e-2, help="objective flow: the regulariser of the 2x2 systems")
     ap.add_argument("--n_repeat", type=int, default=20)
     ap.add_argument("--n_ext", type=int, default=2)
     ap.add_argument("--output_dir", "-o", default=None, help="write before_<i>.png / after_<i>.png and the artefacts of the best refined genome here")
@@ -59,7 +70,8 @@ def main():
     chosen, stills = [genomes[b] for b in best], np.ascontiguousarray(images[best])
     with train.PredNetTrainer(a.model, channels, w, h, len(chosen), a.n_repeat + a.n_ext) as tr:
         refined, history, after = train.refine_genomes(tr, chosen, config, a.structure, n_repeat=a.n_repeat, n_ext=a.n_ext, iters=a.iters, lr=a.lr,
-                                                       objective=a.objective, params=tuple(a.params.split(",")))
+                                                       objective=a.objective, params=tuple(a.params.split(",")),
+                                                       flow=flow_of(a, w, h, (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype(np.uint8)))
     fit0, n0 = score(stills, a.model, a.structure, w, h, channels)
     fit1, n1 = score(after, a.model, a.structure, w, h, channels)
     print("stand-in loss (mean over the %d genomes) per iteration: %s" % (len(chosen), " ".join("%.6e" % v for v in history)))

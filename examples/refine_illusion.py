@@ -9,6 +9,8 @@ every image before and after.  Whether the fitness follows the stand-in is an ob
 
     python examples/refine_illusion.py [-m model.npz] [--size small|N] [-s 1] [-c 3] [--pop 16] [-k 4] [--iters 10] [--step 2]
     python examples/refine_illusion.py --png image.png -o refined
+    python examples/refine_illusion.py --objective flow --flow-direction tangent [--flow-radius 7] [--flow-eps 1e-2]
+        (climb the displacement a dense Lucas-Kanade solve finds between the still and the prediction, inside the structure)
 """
 import argparse
 import os
@@ -30,6 +32,13 @@ def score(images, model, structure, w, h, channels):
     return fit, np.array([len(v) for v in vecs])
 
 
+def flow_of(a, w, h, mask=None):
+    """the FlowObjective of the command line (None under another objective); the term counts the pixels of `mask`"""
+    if a.objective != "flow":
+        return None
+    return train.FlowObjective(a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", "-m", default="synthetic", help="chainer npz weights, or synthetic[:seed]")
@@ -43,7 +52,10 @@ def main():
     ap.add_argument("--png", default=None, help="refine this image instead of a population")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--step", type=float, default=2.0, help="largest move of a byte per iteration")
-    ap.add_argument("--objective", default="mse", choices=["mse", "error"])
+    ap.add_argument("--objective", default="mse", choices=["mse", "error", "flow"])
+    ap.add_argument("--flow-direction", default=None, choices=list(train.FLOW_DIRECTIONS), help="objective flow: climb the displacement along this field (default: its mean square)")
+    ap.add_argument("--flow-radius", type=int, default=7, help="objective flow: the window is 2 R + 1 pixels wide")
+    ap.add_argument("--flow-eps", type=float, default=1e-2, help="objective flow: the regulariser of the 2x2 systems")
     ap.add_argument("--n_repeat", type=int, default=20)
     ap.add_argument("--n_ext", type=int, default=2)
     ap.add_argument("--output_dir", "-o", default=None, help="write before_<i>.png / after_<i>.png here")
@@ -62,7 +74,8 @@ def main():
     stills = np.ascontiguousarray(images[best])
     mask = (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype(np.uint8)   # 0 on the structure's background
     with train.PredNetTrainer(a.model, channels, w, h, len(stills), a.n_repeat + a.n_ext) as tr:
-        refined, history = train.refine_stills(tr, stills, n_repeat=a.n_repeat, n_ext=a.n_ext, iters=a.iters, step=a.step, objective=a.objective, mask=mask)
+        refined, history = train.refine_stills(tr, stills, n_repeat=a.n_repeat, n_ext=a.n_ext, iters=a.iters, step=a.step, objective=a.objective, mask=mask,
+                                                flow=flow_of(a, w, h, mask))
     fit0, n0 = score(stills, a.model, a.structure, w, h, channels)
     fit1, n1 = score(refined, a.model, a.structure, w, h, channels)
     print("stand-in loss (mean over the %d images) per iteration: %s" % (len(stills), " ".join("%.6e" % v for v in history)))

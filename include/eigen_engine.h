@@ -332,8 +332,10 @@ int eigen_trainer_get_weights(eigen_trainer* t, float* const* h_tensors, int32_t
 
 /* The training objective of one call (a per-call argument: the handle keeps nothing of it).
  *   EIGEN_OBJ_MSE: the squared error of the image-layer prediction against the next frame.
- *   EIGEN_OBJ_ERROR: PredNet's own objective (Lotter et al.), the mean of the error units, weighted per layer. */
-typedef enum { EIGEN_OBJ_MSE = 0, EIGEN_OBJ_ERROR = 1 } eigen_objective;
+ *   EIGEN_OBJ_ERROR: PredNet's own objective (Lotter et al.), the mean of the error units, weighted per layer.
+ *   EIGEN_OBJ_FLOW: the displacement a dense Lucas-Kanade solve finds from the next frame to the prediction; it needs settings,
+ *     which only eigen_trainer_loss_grad_flow takes: every other entry refuses it. */
+typedef enum { EIGEN_OBJ_MSE = 0, EIGEN_OBJ_ERROR = 1, EIGEN_OBJ_FLOW = 2 } eigen_objective;
 
 /* Forward with a tape, loss and backward over one batch of sequences; OVERWRITES the gradients.
  *   d_frames: uint8 frames, frame s of sequence b at d_frames + b * bstride + s * C*H*W (bytes); n_steps frames each.
@@ -386,6 +388,55 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
                                    int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
                                    const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
                                    int64_t g_bstride, int64_t g_tstride, void* stream);
+
+/* Settings of EIGEN_OBJ_FLOW ("The flow objective"): the window is the pixels within Chebyshev radius
+ * `radius` (1 .. 16) that lie inside the image; eps (finite, > 0) is added to the diagonal of the 2x2 system, in units of summed
+ * squared gradients of images in [0, 1]. */
+typedef struct {
+    int32_t radius;
+    int32_t reserved;   /* 0 */
+    double eps;
+} eigen_flow_settings;
+
+/* The flow stage alone, on one prediction / reference pair per sample; it runs the kernels a training call runs.  All arithmetic is
+ * float64 on the device, one IEEE operation per operation written:
+ *   gray: C = 1: I = v; C = 3: I = (0.299 v0 + 0.587 v1) + 0.114 v2; I0 from the reference ((float)byte / 255.0f), I1 from the
+ *     prediction, It = I1 - I0.  Ix, Iy: the normalised Scharr derivative of I0 alone, indices clamped to the image.
+ *   window sums Gxx, Gxy, Gyy, bx, by of Ix Ix, Ix Iy, Iy Iy, Ix It, Iy It over the truncated window: rows first, then columns,
+ *     offsets ascending, each sum started from its first term.
+ *   a = Gxx + eps, c = Gyy + eps, b = Gxy, det = a c - b b, ux = -((c bx - b by) / det), uy = -((a by - b bx) / det), pixels per frame.
+ *   v = ux ux + uy uy, or dx ux + dy uy with a direction field; value = sum_b sum_p m(p) v / (batch N_m), N_m the count of the mask,
+ *     reduced in double over fixed slices in a fixed order.
+ *   seed = scale * d value / d prediction, exact because I0 is a constant: g = (2 ux, 2 uy) or d, q = m ((c gx - b gy) / det,
+ *     (a gy - b gx) / det), Q = the window sums of q, t = Ix Qx + Iy Qy, s = -(t kappa), kappa = scale / (batch N_m) formed in double on
+ *     the host, seed[c] = (float)(k_c s), k = (0.299, 0.587, 0.114) or (1).
+ *   d_pred: float, sample b at d_pred + b * p_bstride (floats) as [C][H][W]; d_ref: uint8, sample b at d_ref + b * r_bstride (bytes).
+ *   d_dir: float [2][H][W] (x then y component), shared by the batch, or NULL: the energy mode.  d_mask: uint8 [H][W], 0 = not counted,
+ *     or NULL: all ones.
+ *   Outputs, each may be NULL: h_value (host double); d_flow double [batch][2][H][W]; d_seed float, sample b at d_seed + b * s_bstride
+ *     (floats) as [C][H][W]; floats between the samples are never written.
+ * It needs no weights and touches neither gradients nor the kept state.
+ * Errors: EIGEN_ERR_INVALID a NULL handle, prediction, reference or settings, batch < 1, a stride below C*H*W, radius outside 1 .. 16,
+ * eps not finite or <= 0, scale not finite, a direction that is not finite, a mask without a non-zero pixel; EIGEN_ERR_CAPACITY batch
+ * above max_batch.  A refused call launches and writes nothing. */
+int eigen_trainer_flow_term(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride,
+                            int32_t batch, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale,
+                            double* h_value, double* d_flow, float* d_seed, int64_t s_bstride, void* stream);
+
+/* eigen_trainer_loss_grad_frames plus the flow objective.  objective = EIGEN_OBJ_FLOW: term s is the value of
+ * eigen_trainer_flow_term for the prediction P0_s against frame s + 1 (the pairing of the other objectives), loss = sum_s w_s f_s /
+ * sum_s w_s formed on the host in double in step order; a term with w_s = 0 is not computed and reports 0.0.  Its seed, with scale =
+ * w_s / sum w, is added in float to d loss / d P0_s ahead of the clamp's mask, where the squared-error seed enters under
+ * EIGEN_OBJ_MSE.  The frames are constants of the flow term: d_frame_grad holds the input path alone.
+ *   flow: the settings, required under EIGEN_OBJ_FLOW; d_dir, d_mask as eigen_trainer_flow_term.  Under another objective flow, d_dir
+ *     and d_mask must be NULL and the call is eigen_trainer_loss_grad_frames.
+ *   h_terms (host, may be NULL): double[n_steps - 1], the terms f_s; written under EIGEN_OBJ_FLOW only.
+ * Errors: as eigen_trainer_loss_grad_frames and eigen_trainer_flow_term. */
+int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                 int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                 const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                 int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                 const uint8_t* d_mask, double* h_terms, void* stream);
 
 /* One normalised ascent step on uint8 stills d_images [batch][C][H][W], in place, from a tied gradient (image b at d_grad + b *
  * g_bstride floats): per image m_b = max |g| over the pixels the mask keeps free, then x = byte / 255.0f,

@@ -5,10 +5,13 @@ the tape-free evaluate of that call.  Prints one JSON line per side and writes p
 
     python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both] [--objective mse|l0|lall]
     python scripts/train_bench.py --frame-grads [--steps 5] [--warmup 2]
+    python scripts/train_bench.py --flow-cost [--steps 5] [--warmup 2]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
 side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
-per-frame and with tied ones, every output left on the device; one JSON line each.
+per-frame and with tied ones, every output left on the device; one JSON line each.  --objective flow is the flow objective (r = 7,
+energy, the last two terms weighted); --flow-cost times one loss_grad call (no Adam) under "mse" and under "flow" with the same step
+weights, alternated round by round in one process, and prints the ms per call of each with the spread over the rounds.
 """
 import argparse
 import json
@@ -50,8 +53,38 @@ def frames(seed, n, T, c, h, w):
     return out
 
 
+FLOW_WEIGHTS = [0.0] * (T - 3) + [1.0, 1.0]   # two weighted terms, as a refinement call has them
+
+
 def objective_args(name):
+    if name == "flow":
+        from evolutionary_illusion_generator_amd.train import FlowObjective
+        return dict(objective="flow", flow=FlowObjective(radius=7, eps=1e-2), step_weights=FLOW_WEIGHTS)
     return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
+
+
+def run_flow_cost(steps, warmup, rounds=6):
+    """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round"""
+    import torch
+    from evolutionary_illusion_generator_amd import weights
+    from evolutionary_illusion_generator_amd.train import PredNetTrainer
+    d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
+    calls = {"mse": dict(step_weights=FLOW_WEIGHTS), "flow": objective_args("flow")}
+    ms = {k: [] for k in calls}
+    loss = {}
+    with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
+        for k, kw in calls.items():
+            for _ in range(warmup):
+                tr.forward_backward(d, **kw)
+        for _ in range(rounds):
+            for k, kw in calls.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    loss[k] = tr.forward_backward(d, **kw)
+                torch.cuda.synchronize()
+                ms[k].append((time.perf_counter() - t0) * 1e3 / steps)
+    return [dict(side="loss_grad_" + k, call_ms=float(np.median(v)), call_ms_min=min(v), call_ms_max=max(v), rounds=rounds, loss=loss[k]) for k, v in ms.items()]
 
 
 def run_trainer(steps, warmup, objective="mse"):
@@ -190,7 +223,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
-    ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall"], help="the trainer side's objective")
+    ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall", "flow"], help="the trainer side's objective")
+    ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
@@ -200,6 +234,10 @@ def main():
         return
     if a.frame_grads:
         for r in run_frame_grads(a.steps, a.warmup):
+            print(json.dumps(r), flush=True)
+        return
+    if a.flow_cost:
+        for r in run_flow_cost(a.steps, a.warmup):
             print(json.dumps(r), flush=True)
         return
     res = [run_trainer(a.steps, a.warmup, a.objective)]
