@@ -15,6 +15,7 @@
 #include "train_kernels.h"
 #include "frame_grad_kernels.h"
 #include "flow_obj_kernels.h"
+#include "flow_ref_kernels.h"
 
 using namespace eigt;
 
@@ -91,6 +92,8 @@ struct eigen_trainer {
     float* d_absmax = nullptr;                     // eigen_trainer_still_step: max |g| of every image, [max_batch]
     // the flow objective's float64 planes, one batch each: Ix, Iy, It [3][B H W]; q [2][B H W]; the masked value [B H W]
     double *f_planes = nullptr, *f_q = nullptr, *f_mv = nullptr;
+    // the moving reference's: the flow u [B][2][H W], which the solve writes there when that mode asks, and rx, ry, e [3][B H W]
+    double *f_u = nullptr, *f_r = nullptr;
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -238,6 +241,7 @@ int allocate(eigen_trainer* t)
     add((void**)&t->d_spart, T * STEP_LOSS_BLOCKS * 8); add((void**)&t->d_step, T * 8); add((void**)&t->d_err, T * L * 8);
     add((void**)&t->d_absmax, B * 4);
     add((void**)&t->f_planes, 3 * B * t->ly[0].HW * 8); add((void**)&t->f_q, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_mv, B * t->ly[0].HW * 8);
+    add((void**)&t->f_u, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_r, 3 * B * t->ly[0].HW * 8);
     for (int l = 0; l < L; ++l) {
         TLayer& y = t->ly[l];
         const long long CHW = y.CHW();
@@ -387,15 +391,18 @@ struct FlowSpec {
     const float* dir = nullptr;
     const uint8_t* mask = nullptr;
     long long n_mask = 0;
+    bool moving = false;  // EIGEN_FLOW_MOVING_REFERENCE: a training call adds every term's reference path to the frame gradient
 };
 
 // The settings of a flow call against the handle's image, before anything is launched.  The direction field and the mask are read back
 // to the host: every d must be finite, and kappa needs the mask's count.
-int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, FlowSpec& f)
+int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, int32_t allowed_flags, FlowSpec& f)
 {
     if (!flow) return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs its settings");
     if (flow->radius < 1 || flow->radius > FLOW_MAX_R) return tfail(EIGEN_ERR_INVALID, "flow radius %d outside 1 .. %d", flow->radius, FLOW_MAX_R);
     if (!std::isfinite(flow->eps) || !(flow->eps > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow eps %g: must be finite and > 0", flow->eps);
+    if (flow->flags & ~allowed_flags) return tfail(EIGEN_ERR_INVALID, "flow flags 0x%x: this entry takes 0x%x at most", (unsigned)flow->flags, (unsigned)allowed_flags);
+    f.moving = (flow->flags & EIGEN_FLOW_MOVING_REFERENCE) != 0;
     const long long HW = t->ly[0].HW;
     f.r = flow->radius; f.eps = flow->eps; f.dir = d_dir; f.mask = d_mask; f.n_mask = HW;
     TCHK(hipSetDevice(t->cfg.device));
@@ -415,10 +422,14 @@ int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const fl
 }
 
 // The flow stage of one prediction / reference pair per sample (eigen_trainer_flow_term states the arithmetic): the planes, the tiled
-// solve, then what is wanted of the value (d_value, through the STEP_LOSS_BLOCKS partials at part), the flow and the seed.
+// solve, then what is wanted of the value (d_value, through the STEP_LOSS_BLOCKS partials at part), the flow and the seed.  d_refg
+// (may be null): the term's gradient by its reference frame (flow_ref_kernels.h), from the planes, q and u this stage leaves; u is then
+// written to the handle's workspace unless the caller wants it anyway.
 void flow_stage(eigen_trainer* t, hipStream_t st, int B, const float* pred, long long p_bstride, const uint8_t* ref, long long r_bstride, const FlowSpec& f,
-                double kappa, double* part, double* d_value, double* d_flow, float* d_seed, long long s_bstride, int accumulate)
+                double kappa, double* part, double* d_value, double* d_flow, float* d_seed, long long s_bstride, int accumulate, float* d_refg = nullptr,
+                long long rg_bstride = 0, int rg_accumulate = 0)
 {
+    if (d_refg && !d_flow) d_flow = t->f_u;
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
     ew(st, tflow_prep_kernel, n, pred, p_bstride, ref, r_bstride, y.C, y.H, y.W, n, t->f_planes);
@@ -431,6 +442,11 @@ void flow_stage(eigen_trainer* t, hipStream_t st, int B, const float* pred, long
     if (d_seed)
         hipLaunchKernelGGL(tflow_seed_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, n, y.H, y.W, y.C, f.r, kappa, d_seed,
                            s_bstride, accumulate);
+    if (d_refg) {
+        hipLaunchKernelGGL(tflow_ref_sums_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, (const double*)d_flow, n, y.H, y.W, f.r,
+                           kappa, t->f_r);
+        ew(st, tflow_ref_fold_kernel, n, (const double*)t->f_r, n, y.H, y.W, y.C, d_refg, rg_bstride, rg_accumulate);
+    }
 }
 
 // The loss of one loss_grad call: the weights of its terms and the seeds they put into the backward pass.
@@ -510,8 +526,16 @@ int reduce_losses(eigen_trainer* t, hipStream_t st, const Objective& o, const ui
     return EIGEN_OK;
 }
 
-// One step of backprop through time: the cells bottom up (dP, dh, dc and dZ of step s), then the error units top down.
-void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, const uint8_t* d_frames, long long bstride)
+// Where a call wants d loss / d frames: sample b, step s at p + b * bstride + s * tstride (floats); tstride == 0 is the tied mode,
+// one image per sample into which every step is added.  p == nullptr: not wanted.
+struct FrameGrad {
+    float* p = nullptr;
+    long long bstride = 0, tstride = 0;
+};
+
+// One step of backprop through time: the cells bottom up (dP, dh, dc and dZ of step s), then the error units top down.  fg: under
+// the flow objective's moving reference, where term s adds its reference path, which belongs to frame s + 1.
+void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, const uint8_t* d_frames, long long bstride, const FrameGrad& fg)
 {
     const int L = t->L, T = o.T, B = o.B;
     const float* prm = t->prm;
@@ -524,10 +548,12 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
         const uint8_t* xn = (l == 0 && s < T - 1) ? d_frames + (long long)(s + 1) * CHW : nullptr;
         if (o.by_flow && xn) {
             // term s: its value into d_step[s] and its seed added to dP0_s, which tpact_bwd then masks; a term of weight zero is not computed
+            // with the moving reference and a frame gradient wanted, the term's reference path is added in float to g_{s+1}, which
+            // frame_grad_step(s + 1) stored earlier (per frame), or to the one image of the tied mode ahead of this step's input path
             const double w = o.weight(s);
             if (w != 0.0)
                 flow_stage(t, st, B, P, CHW, xn, bstride, o.flow, (w / o.total_weight()) / (double)(B * o.flow.n_mask), t->d_spart + (long long)s * STEP_LOSS_BLOCKS,
-                           t->d_step + s, nullptr, y.dPn, CHW, 1);
+                           t->d_step + s, nullptr, y.dPn, CHW, 1, o.flow.moving && fg.p ? fg.p + (long long)(s + 1) * fg.tstride : nullptr, fg.bstride, 1);
             xn = nullptr;
         }
         const float scale = !xn ? 0.f : o.by_error ? o.err_scale(s, 0) : o.loss_scale(s);
@@ -568,13 +594,6 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
     }
 }
 
-// Where a call wants d loss / d frames: sample b, step s at p + b * bstride + s * tstride (floats); tstride == 0 is the tied mode,
-// one image per sample into which every step is added.  p == nullptr: not wanted.
-struct FrameGrad {
-    float* p = nullptr;
-    long long bstride = 0, tstride = 0;
-};
-
 // g_s of backward step s, after layer 0's terr_bwd of that step (dE_0 and E_0 of step s are what that kernel read): the input path on
 // a teacher-forced step, and the target path of term s - 1, whose prediction P0_{s-1} is state slot s
 void frame_grad_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, int n_fed, const uint8_t* d_frames, long long bstride, const FrameGrad& fg)
@@ -582,7 +601,8 @@ void frame_grad_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s
     const TLayer& y = t->ly[0];
     const int B = o.B;
     const long long CHW = y.CHW();
-    // under the flow objective the frames are constants of every term: no target path
+    // under the flow objective this kernel adds no target path: the frames are constants of every term, or, with the moving reference,
+    // backward_step(s - 1) adds term s - 1's reference path to what is stored here
     const float scale = s < 1 || o.by_flow ? 0.f : o.by_error ? o.err_scale(s - 1, 0) : o.loss_scale(s - 1);
     const int has_input = s < n_fed, has_target = s >= 1 && scale != 0.f;
     float* out = fg.p + (long long)s * fg.tstride;
@@ -764,7 +784,7 @@ int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int6
     rc = make_objective(t, by_flow ? (int32_t)EIGEN_OBJ_MSE : objective, h_layer_w, h_step_w, T, B, o);
     if (rc) return rc;
     if (by_flow) {
-        rc = check_flow(t, flow, d_dir, d_mask, o.flow);
+        rc = check_flow(t, flow, d_dir, d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
         if (rc) return rc;
         o.by_flow = true;
         o.h_terms = h_terms;
@@ -784,7 +804,7 @@ int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int6
     // the tied frame gradient starts from zero; only the C0 H W floats of every sample are touched, whatever g_bstride is
     for (int b = 0; fg.p && fg.tstride == 0 && b < B; ++b) TCHK(hipMemsetAsync(fg.p + b * fg.bstride, 0, C0HW * 4, st));
     for (int s = T - 1; s >= 0; --s) {
-        backward_step(t, st, o, s, d_frames, bstride);
+        backward_step(t, st, o, s, d_frames, bstride, fg);
         if (fg.p) frame_grad_step(t, st, o, s, n_fed, d_frames, bstride, fg);
     }
     weight_gradients(t, st, T, B);
@@ -804,29 +824,45 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
                                         d_frame_grad, g_bstride, g_tstride, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
-int eigen_trainer_flow_term(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
-                            const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow,
-                            float* d_seed, int64_t s_bstride, void* stream)
+// the two stage-alone entries: d_refg == nullptr is eigen_trainer_flow_term
+static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
+                          const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
+                          int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream)
 {
     if (!t || !d_pred || !d_ref || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
     if (batch > t->cfg.max_batch) return tfail(EIGEN_ERR_CAPACITY, "batch %d exceeds the trainer's %d", batch, t->cfg.max_batch);
     const long long C0HW = t->ly[0].CHW();
-    if (p_bstride < C0HW || r_bstride < C0HW || (d_seed && s_bstride < C0HW))
+    if (p_bstride < C0HW || r_bstride < C0HW || (d_seed && s_bstride < C0HW) || (d_refg && rg_bstride < C0HW))
         return tfail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", C0HW);
     if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale %g is not finite", scale);
     FlowSpec f;
-    const int rc = check_flow(t, flow, d_dir, d_mask, f);
+    const int rc = check_flow(t, flow, d_dir, d_mask, 0, f);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     flow_stage(t, st, batch, d_pred, p_bstride, d_ref, r_bstride, f, scale / (double)(batch * f.n_mask), t->d_spart, h_value ? t->d_step : nullptr, d_flow, d_seed,
-               s_bstride, 0);
+               s_bstride, 0, d_refg, rg_bstride, 0);
     TCHK(hipGetLastError());
     if (h_value) {
         TCHK(hipMemcpyAsync(h_value, t->d_step, 8, hipMemcpyDeviceToHost, st));
         TCHK(hipStreamSynchronize(st));
     }
     return EIGEN_OK;
+}
+
+int eigen_trainer_flow_term(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
+                            const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow,
+                            float* d_seed, int64_t s_bstride, void* stream)
+{
+    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, nullptr, 0, stream);
+}
+
+int eigen_trainer_flow_term_ref(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
+                                const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow,
+                                float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream)
+{
+    if (!d_ref_grad) return tfail(EIGEN_ERR_INVALID, "null argument");
+    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream);
 }
 
 int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,

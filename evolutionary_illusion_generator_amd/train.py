@@ -18,7 +18,7 @@ from .weights import tensor_names, tensor_shapes
 
 class FlowSettings(ctypes.Structure):
     """eigen_flow_settings"""
-    _fields_ = [("radius", ctypes.c_int32), ("reserved", ctypes.c_int32), ("eps", ctypes.c_double)]
+    _fields_ = [("radius", ctypes.c_int32), ("flags", ctypes.c_int32), ("eps", ctypes.c_double)]
 
 
 class TrainerConfig(ctypes.Structure):
@@ -44,6 +44,7 @@ def _bind(lib):
     lib.eigen_trainer_flow_term.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                             ctypes.c_void_p]
+    lib.eigen_trainer_flow_term_ref.argtypes = lib.eigen_trainer_flow_term.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_evaluate_err.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -63,6 +64,8 @@ OBJECTIVES = {"mse": 0, "error": 1, "flow": 2}  # eigen_objective
 FRAME_GRADS = (None, "frames", "tied")
 FLOW_MAX_RADIUS = 16
 FLOW_DIRECTIONS = ("tangent", "radial", "horizontal", "vertical")
+FLOW_REFERENCES = ("constant", "moving")
+FLOW_MOVING_REFERENCE = 1  # EIGEN_FLOW_MOVING_REFERENCE
 
 
 def flow_direction(kind, w, h):
@@ -95,13 +98,20 @@ class FlowObjective:
     the reference frame to the prediction over windows of Chebyshev radius `radius`, truncated at the border, with `eps` added to the
     diagonal of every 2x2 system.  direction None: the term is the mean squared displacement; direction float32 [2, H, W] (x then y
     component, ``flow_direction``): the mean displacement along it.  mask: [H, W], zero = the pixel is not counted (None: all are).
+    reference: "constant", the reference frame of every term is a constant of the graph and a frame gradient is the input path alone;
+    "moving", frame s + 1 is in the graph as the reference of term s, and the frame gradient of a training call (``forward_backward``,
+    ``refine_stills``, ``refine_genomes``) also holds how every term moves with its reference ("The moving
+    reference").  Loss, terms, weight gradients, predictions and state do not depend on it.
 
     The defaults are a design choice: radius 7 is a 15-pixel window, the fitness path's ``lk_win``; eps 1e-2 is in units of summed
     squared gradients of images in [0, 1] (a 15 x 15 window over an edge of contrast 0.1 sums to about 0.1), so it damps flat windows
     and leaves textured ones alone.  ValueError: radius outside 1 .. 16, eps not finite or <= 0, a direction that is not
-    [2, H, W] or not finite, a mask that is not [H, W] or counts no pixel."""
+    [2, H, W] or not finite, a mask that is not [H, W] or counts no pixel, a reference that is neither "constant" nor "moving"."""
 
-    def __init__(self, radius=7, eps=1e-2, direction=None, mask=None):
+    def __init__(self, radius=7, eps=1e-2, direction=None, mask=None, reference="constant"):
+        if reference not in FLOW_REFERENCES:
+            raise ValueError("reference must be one of %s, got %r" % (", ".join(FLOW_REFERENCES), reference))
+        self.reference = reference
         if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= FLOW_MAX_RADIUS:
             raise ValueError("radius must be an integer in 1 .. %d, got %r" % (FLOW_MAX_RADIUS, radius))
         eps = float(eps)
@@ -125,8 +135,9 @@ class FlowObjective:
             self.mask = m
         self._dev = {}
 
-    def settings(self):
-        return FlowSettings(self.radius, 0, self.eps)
+    def settings(self, stage_alone=False):
+        """eigen_flow_settings; the stage-alone entries take no flags (the reference gradient is asked for by the entry called)"""
+        return FlowSettings(self.radius, FLOW_MOVING_REFERENCE if self.reference == "moving" and not stage_alone else 0, self.eps)
 
     def on_device(self, torch, device, h, w):
         """(direction, mask) as device tensors (None where not set), uploaded once per device; ValueError if they are not [.., h, w]"""
@@ -433,7 +444,10 @@ class PredNetTrainer:
 
         objective "flow" with flow=FlowObjective(...) (required then, refused otherwise): term s is the displacement a dense
         Lucas-Kanade solve finds from frame s + 1, a constant of the graph, to prediction s: its mean square, or its mean along the
-        direction field ("The flow objective").  The frame gradient is then the input path alone.
+        direction field ("The flow objective").  The frame gradient is then the input path alone, unless the
+        FlowObjective has reference="moving": frame s + 1 is then in the graph as the reference of term s, and g_t = fl(input path of
+        step t + reference path of term t - 1); "tied" starts from zero and for s = T - 1 .. 0 adds the reference path of term s, then
+        the input path of step s.  Nothing else the call returns depends on that setting.
         flow_terms=True (flow only) appends the float64 [T - 1] terms last; a term of weight zero is not computed and reads 0."""
         if frame_grads not in FRAME_GRADS:
             raise ValueError("frame_grads must be None, 'frames' or 'tied', got %r" % (frame_grads,))
@@ -447,10 +461,13 @@ class PredNetTrainer:
         out += (self.last_flow_terms,) if flow_terms else ()
         return out[0] if len(out) == 1 else out
 
-    def flow_term(self, pred, ref, flow, scale=1.0):
+    def flow_term(self, pred, ref, flow, scale=1.0, reference_grad=False):
         """The flow stage alone (eigen_trainer_flow_term), with the kernels a training call runs: pred float32 [n, C, H, W], the
         prediction; ref uint8 [n, C, H, W], the reference frame; n <= batch.  -> (value, u, seed): the term, the flow float64
-        [n, 2, H, W] in pixels per frame (x then y) and scale * d value / d pred as float32 [n, C, H, W]."""
+        [n, 2, H, W] in pixels per frame (x then y) and scale * d value / d pred as float32 [n, C, H, W].  reference_grad=True
+        (eigen_trainer_flow_term_ref) appends scale * d value / d ref, by the reference as floats (byte / 255), float32
+        [n, C, H, W]: what a training call adds to the frame gradient under reference="moving".  The FlowObjective's own `reference`
+        plays no part here."""
         torch = self._torch
         if not isinstance(flow, FlowObjective):
             raise ValueError("flow must be a FlowObjective, got %r" % (flow,))
@@ -467,10 +484,15 @@ class PredNetTrainer:
         value = ctypes.c_double(0.0)
         u = torch.empty((n, 2, self.h, self.w), dtype=torch.float64, device=dev)
         seed = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
-        cfg = flow.settings()
-        _check(self.lib.eigen_trainer_flow_term(self._h, _ptr(p), ctypes.c_int64(per), _ptr(r), ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_dir),
-                                                _ptr(d_mask), ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(u), _ptr(seed), ctypes.c_int64(per), None))
-        return value.value, u.cpu().numpy(), seed.cpu().numpy()
+        cfg = flow.settings(stage_alone=True)
+        args = [self._h, _ptr(p), ctypes.c_int64(per), _ptr(r), ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask),
+                ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(u), _ptr(seed), ctypes.c_int64(per)]
+        if not reference_grad:
+            _check(self.lib.eigen_trainer_flow_term(*args, None))
+            return value.value, u.cpu().numpy(), seed.cpu().numpy()
+        rg = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
+        _check(self.lib.eigen_trainer_flow_term_ref(*args, _ptr(rg), ctypes.c_int64(per), None))
+        return value.value, u.cpu().numpy(), seed.cpu().numpy(), rg.cpu().numpy()
 
     def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False, layer_errors=False):
         """Forward only, no tape: the mean squared error of every step of frames uint8 [n, T, C, H, W], T of any length, as
@@ -574,7 +596,9 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
     most `step` bytes along the gradient, normalised by the image's largest |g| over the free pixels.  mask: [H, W], zero keeps
     a pixel as it is (None: every pixel is free).  Everything stays on the device between iterations.  objective "flow" with
     flow=FlowObjective(...) climbs the displacement between the still and the extended prediction itself, which is what the fitness
-    scores; the FlowObjective's own mask selects the pixels that are counted, `mask` the pixels that move.
+    scores; the FlowObjective's own mask selects the pixels that are counted, `mask` the pixels that move.  The still is also the
+    reference frame of every flow term: with FlowObjective(reference="constant") the step follows the input path alone and ignores how the
+    term moves with its reference, with reference="moving" it follows the whole gradient.
 
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images.  The calls
     OVERWRITE the trainer's weight gradients and its kept sequence state."""
@@ -689,7 +713,7 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     them).  FROZEN, i.e. never updated: folded float32 constants (``genome.flatten_genome_map``'s None entries and everything inside a
     folded sub-graph), disabled connections and whatever the outputs do not depend on.
 
-    objective "flow" takes flow=FlowObjective(...) as ``refine_stills`` does.
+    objective "flow" takes flow=FlowObjective(...) as ``refine_stills`` does, its `reference` setting included.
 
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images, which are the
     render of genomes'.  The calls OVERWRITE the trainer's weight gradients and its kept sequence state."""

@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--flow-direction", default=None, choices=["tangent", "radial", "horizontal", "vertical"], help="objective flow: the field (default: the mean square)")
     ap.add_argument("--flow-radius", type=int, default=7)
     ap.add_argument("--flow-eps", type=float, default=1e-2)
+    ap.add_argument("--flow-reference", default="constant", choices=["constant", "moving"], help="objective flow: moving also follows how the term moves with the still as its reference frame")
     a = ap.parse_args()
     w, h = {"small": (160, 120), "big": (640, 480)}.get(a.size) or (int(a.size), int(a.size))
     channels = [int(c) for c in a.channels.split(",")]
@@ -65,7 +66,7 @@ def main():
         flow = None
         if a.objective == "flow":
             inside = (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype("uint8")
-            flow = train.FlowObjective(a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), inside)
+            flow = train.FlowObjective(a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), inside, reference=a.flow_reference)
         refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters, objective=a.objective, flow=flow)
         for g, r in zip(best, refined):
             for k, n in r.nodes.items():

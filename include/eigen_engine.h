@@ -391,10 +391,13 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
 
 /* Settings of EIGEN_OBJ_FLOW ("The flow objective"): the window is the pixels within Chebyshev radius
  * `radius` (1 .. 16) that lie inside the image; eps (finite, > 0) is added to the diagonal of the 2x2 system, in units of summed
- * squared gradients of images in [0, 1]. */
+ * squared gradients of images in [0, 1].
+ * flags, bit 0, EIGEN_FLOW_MOVING_REFERENCE (eigen_trainer_loss_grad_flow only): the reference frame of every term is part of the
+ * graph, not a constant of it.  Default (0): every call launches what it launched before the flag existed. */
+#define EIGEN_FLOW_MOVING_REFERENCE 1
 typedef struct {
     int32_t radius;
-    int32_t reserved;   /* 0 */
+    int32_t flags;      /* 0, or EIGEN_FLOW_MOVING_REFERENCE where an entry takes it; any other bit is refused */
     double eps;
 } eigen_flow_settings;
 
@@ -417,8 +420,8 @@ typedef struct {
  *     (floats) as [C][H][W]; floats between the samples are never written.
  * It needs no weights and touches neither gradients nor the kept state.
  * Errors: EIGEN_ERR_INVALID a NULL handle, prediction, reference or settings, batch < 1, a stride below C*H*W, radius outside 1 .. 16,
- * eps not finite or <= 0, scale not finite, a direction that is not finite, a mask without a non-zero pixel; EIGEN_ERR_CAPACITY batch
- * above max_batch.  A refused call launches and writes nothing. */
+ * eps not finite or <= 0, non-zero flags, scale not finite, a direction that is not finite, a mask without a non-zero pixel;
+ * EIGEN_ERR_CAPACITY batch above max_batch.  A refused call launches and writes nothing. */
 int eigen_trainer_flow_term(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride,
                             int32_t batch, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale,
                             double* h_value, double* d_flow, float* d_seed, int64_t s_bstride, void* stream);
@@ -427,7 +430,13 @@ int eigen_trainer_flow_term(eigen_trainer* t, const float* d_pred, int64_t p_bst
  * eigen_trainer_flow_term for the prediction P0_s against frame s + 1 (the pairing of the other objectives), loss = sum_s w_s f_s /
  * sum_s w_s formed on the host in double in step order; a term with w_s = 0 is not computed and reports 0.0.  Its seed, with scale =
  * w_s / sum w, is added in float to d loss / d P0_s ahead of the clamp's mask, where the squared-error seed enters under
- * EIGEN_OBJ_MSE.  The frames are constants of the flow term: d_frame_grad holds the input path alone.
+ * EIGEN_OBJ_MSE.  By default the frames are constants of the flow term: d_frame_grad holds the input path alone.
+ *   flow->flags & EIGEN_FLOW_MOVING_REFERENCE: frame s + 1, the reference of term s, is in the graph.  Every computed term (w_s != 0)
+ *     then adds the gradient eigen_trainer_flow_term_ref states, with scale = w_s / sum w, in float to d_frame_grad: per frame
+ *     (g_tstride != 0) g_t = fl(input path of step t + reference path of term t - 1); tied (g_tstride == 0) the image starts from zero
+ *     and for s = n_steps - 1 .. 0 first the reference path of term s is added, then the input path of step s.  Self-fed steps have
+ *     a reference path too: targets stay the true frames.  Without d_frame_grad the bit changes nothing, and loss, terms, weight
+ *     gradients, predictions and the kept state are the same bits with it and without.  Any other bit: EIGEN_ERR_INVALID.
  *   flow: the settings, required under EIGEN_OBJ_FLOW; d_dir, d_mask as eigen_trainer_flow_term.  Under another objective flow, d_dir
  *     and d_mask must be NULL and the call is eigen_trainer_loss_grad_frames.
  *   h_terms (host, may be NULL): double[n_steps - 1], the terms f_s; written under EIGEN_OBJ_FLOW only.
@@ -437,6 +446,22 @@ int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int6
                                  const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
                                  int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
                                  const uint8_t* d_mask, double* h_terms, void* stream);
+
+/* eigen_trainer_flow_term plus the gradient of the term by its REFERENCE frame, scale * d value / d x with x = (float)byte / 255.0f
+ * the reference's floats: the kernels a training call runs under EIGEN_FLOW_MOVING_REFERENCE.  Float64, one IEEE operation per
+ * operation written.  With u, q, Q, Ix, Iy, It and kappa of eigen_trainer_flow_term:
+ *   window sums (the same order) Mxx = sum 2 (qx ux), Mxy = sum (qx uy + qy ux), Myy = sum 2 (qy uy);
+ *   rx = -(((Qx It + Mxx Ix) + Mxy Iy) kappa), ry = -(((Qy It + Mxy Ix) + Myy Iy) kappa), e = (Ix Qx + Iy Qy) kappa;
+ *   d = e + S^T(rx, ry), S^T the adjoint of the normalised Scharr pair with clamped indices: a tap the forward pass clamps onto a
+ *     border pixel sends its share back to that pixel (csrc/flow_ref_kernels.h fixes the order of the additions);
+ *   d_ref_grad[c] = (float)(k_c d), k = (0.299, 0.587, 0.114) or (1): sample b at d_ref_grad + b * rg_bstride (floats) as [C][H][W],
+ *     a plain store; floats between the samples are never written.
+ * Errors: as eigen_trainer_flow_term (non-zero flags among them: the entry is the request); EIGEN_ERR_INVALID a NULL d_ref_grad or an
+ * rg_bstride below C*H*W. */
+int eigen_trainer_flow_term_ref(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride,
+                                int32_t batch, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale,
+                                double* h_value, double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride,
+                                void* stream);
 
 /* One normalised ascent step on uint8 stills d_images [batch][C][H][W], in place, from a tied gradient (image b at d_grad + b *
  * g_bstride floats): per image m_b = max |g| over the pixels the mask keeps free, then x = byte / 255.0f,

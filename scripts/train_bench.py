@@ -5,13 +5,15 @@ the tape-free evaluate of that call.  Prints one JSON line per side and writes p
 
     python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both] [--objective mse|l0|lall]
     python scripts/train_bench.py --frame-grads [--steps 5] [--warmup 2]
-    python scripts/train_bench.py --flow-cost [--steps 5] [--warmup 2]
+    python scripts/train_bench.py --flow-cost [--steps 5] [--warmup 2] [--flow-reference constant|moving]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
 side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
 per-frame and with tied ones, every output left on the device; one JSON line each.  --objective flow is the flow objective (r = 7,
 energy, the last two terms weighted); --flow-cost times one loss_grad call (no Adam) under "mse" and under "flow" with the same step
 weights, alternated round by round in one process, and prints the ms per call of each with the spread over the rounds.
+--flow-reference moving gives the FlowObjective the moving reference; --flow-cost then adds two legs, the "flow" call with tied frame
+gradients (left on the device) under the constant and under the moving reference: their difference is what the mode costs.
 """
 import argparse
 import json
@@ -56,44 +58,57 @@ def frames(seed, n, T, c, h, w):
 FLOW_WEIGHTS = [0.0] * (T - 3) + [1.0, 1.0]   # two weighted terms, as a refinement call has them
 
 
-def objective_args(name):
+def objective_args(name, reference="constant"):
     if name == "flow":
         from evolutionary_illusion_generator_amd.train import FlowObjective
-        return dict(objective="flow", flow=FlowObjective(radius=7, eps=1e-2), step_weights=FLOW_WEIGHTS)
+        return dict(objective="flow", flow=FlowObjective(radius=7, eps=1e-2, reference=reference), step_weights=FLOW_WEIGHTS)
     return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
 
 
-def run_flow_cost(steps, warmup, rounds=6):
-    """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round"""
+def run_flow_cost(steps, warmup, rounds=6, reference="constant"):
+    """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round; with
+    the moving reference also per "flow" call with tied frame gradients, under either reference"""
+    import ctypes
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
     d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
-    calls = {"mse": dict(step_weights=FLOW_WEIGHTS), "flow": objective_args("flow")}
+    calls = {"mse": dict(step_weights=FLOW_WEIGHTS), "flow": objective_args("flow", reference)}
+    if reference == "moving":
+        calls["flow_tied_constant"] = dict(objective_args("flow"), frame_grads="tied")
+        calls["flow_tied_moving"] = dict(objective_args("flow", "moving"), frame_grads="tied")
     ms = {k: [] for k in calls}
     loss = {}
     with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
+        def run(kw):
+            if "frame_grads" not in kw:
+                return tr.forward_backward(d, **kw)
+            # the tied gradient stays on the device, as refine_stills leaves it
+            kw = dict(kw)
+            return tr._loss_grad(d, B, T, T, ctypes.c_int64(T * CH[0] * H * W), True, False, None, False, kw.pop("step_weights"), kw.pop("objective", "mse"), None,
+                                 False, kw.pop("frame_grads", None), flow=kw.pop("flow", None))[0]
+
         for k, kw in calls.items():
             for _ in range(warmup):
-                tr.forward_backward(d, **kw)
+                run(kw)
         for _ in range(rounds):
             for k, kw in calls.items():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(steps):
-                    loss[k] = tr.forward_backward(d, **kw)
+                    loss[k] = run(kw)
                 torch.cuda.synchronize()
                 ms[k].append((time.perf_counter() - t0) * 1e3 / steps)
     return [dict(side="loss_grad_" + k, call_ms=float(np.median(v)), call_ms_min=min(v), call_ms_max=max(v), rounds=rounds, loss=loss[k]) for k, v in ms.items()]
 
 
-def run_trainer(steps, warmup, objective="mse"):
+def run_trainer(steps, warmup, objective="mse", reference="constant"):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
     d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
     tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T)
-    kw = objective_args(objective)
+    kw = objective_args(objective, reference)
     for _ in range(warmup):
         tr.step(d, **kw)
     torch.cuda.synchronize()
@@ -225,6 +240,7 @@ def main():
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
     ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall", "flow"], help="the trainer side's objective")
     ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
+    ap.add_argument("--flow-reference", default="constant", choices=["constant", "moving"], help="the flow objective's reference frame: a constant of the graph, or part of it")
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
@@ -237,10 +253,10 @@ def main():
             print(json.dumps(r), flush=True)
         return
     if a.flow_cost:
-        for r in run_flow_cost(a.steps, a.warmup):
+        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference):
             print(json.dumps(r), flush=True)
         return
-    res = [run_trainer(a.steps, a.warmup, a.objective)]
+    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference)]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
