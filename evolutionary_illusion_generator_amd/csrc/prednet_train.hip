@@ -1,7 +1,7 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
 // the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for the flow objective
-// flow_obj_kernels.h.
+// flow_obj_kernels.h, flow_ref_kernels.h and flow_pair_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +16,7 @@
 #include "frame_grad_kernels.h"
 #include "flow_obj_kernels.h"
 #include "flow_ref_kernels.h"
+#include "flow_pair_kernels.h"
 
 using namespace eigt;
 
@@ -392,6 +393,7 @@ struct FlowSpec {
     const uint8_t* mask = nullptr;
     long long n_mask = 0;
     bool moving = false;  // EIGEN_FLOW_MOVING_REFERENCE: a training call adds every term's reference path to the frame gradient
+    bool pair_pred = false;  // EIGEN_FLOW_PAIR_PREDICTION: the reference of term s is the float P0_{s-1}, in the graph
 };
 
 // The settings of a flow call against the handle's image, before anything is launched.  The direction field and the mask are read back
@@ -421,18 +423,33 @@ int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const fl
     return EIGEN_OK;
 }
 
+// The gradient of the term by its reference, from the planes and q the flow stage of the same term left in the workspace and its flow
+// at d_flow: into d_refg (sample b at + b * rg_bstride), added in float or stored.  A training call under the prediction pairing runs
+// this apart from the stage, once layer 0's terr_bwd of the step has written dP0_{s-1}.
+void flow_ref_path(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, double kappa, const double* d_flow, float* d_refg, long long rg_bstride,
+                   int rg_accumulate)
+{
+    const TLayer& y = t->ly[0];
+    const long long n = (long long)B * y.HW;
+    const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
+    hipLaunchKernelGGL(tflow_ref_sums_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, d_flow, n, y.H, y.W, f.r, kappa, t->f_r);
+    ew(st, tflow_ref_fold_kernel, n, (const double*)t->f_r, n, y.H, y.W, y.C, d_refg, rg_bstride, rg_accumulate);
+}
+
 // The flow stage of one prediction / reference pair per sample (eigen_trainer_flow_term states the arithmetic): the planes, the tiled
 // solve, then what is wanted of the value (d_value, through the STEP_LOSS_BLOCKS partials at part), the flow and the seed.  d_refg
 // (may be null): the term's gradient by its reference frame (flow_ref_kernels.h), from the planes, q and u this stage leaves; u is then
-// written to the handle's workspace unless the caller wants it anyway.
+// written to the handle's workspace unless the caller wants it anyway.  fref: the reference as a float image (the prediction pairing,
+// flow_pair_kernels.h), in place of the bytes at ref.
 void flow_stage(eigen_trainer* t, hipStream_t st, int B, const float* pred, long long p_bstride, const uint8_t* ref, long long r_bstride, const FlowSpec& f,
                 double kappa, double* part, double* d_value, double* d_flow, float* d_seed, long long s_bstride, int accumulate, float* d_refg = nullptr,
-                long long rg_bstride = 0, int rg_accumulate = 0)
+                long long rg_bstride = 0, int rg_accumulate = 0, const float* fref = nullptr)
 {
     if (d_refg && !d_flow) d_flow = t->f_u;
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
-    ew(st, tflow_prep_kernel, n, pred, p_bstride, ref, r_bstride, y.C, y.H, y.W, n, t->f_planes);
+    if (fref) ew(st, tflow_pair_prep_kernel, n, pred, p_bstride, fref, r_bstride, y.C, y.H, y.W, n, t->f_planes);
+    else ew(st, tflow_prep_kernel, n, pred, p_bstride, ref, r_bstride, y.C, y.H, y.W, n, t->f_planes);
     const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
     hipLaunchKernelGGL(tflow_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, n, y.H, y.W, f.r, f.eps, f.dir, f.mask, t->f_q, t->f_mv, d_flow);
     if (d_value) {
@@ -442,11 +459,7 @@ void flow_stage(eigen_trainer* t, hipStream_t st, int B, const float* pred, long
     if (d_seed)
         hipLaunchKernelGGL(tflow_seed_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, n, y.H, y.W, y.C, f.r, kappa, d_seed,
                            s_bstride, accumulate);
-    if (d_refg) {
-        hipLaunchKernelGGL(tflow_ref_sums_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, (const double*)d_flow, n, y.H, y.W, f.r,
-                           kappa, t->f_r);
-        ew(st, tflow_ref_fold_kernel, n, (const double*)t->f_r, n, y.H, y.W, y.C, d_refg, rg_bstride, rg_accumulate);
-    }
+    if (d_refg) flow_ref_path(t, st, B, f, kappa, d_flow, d_refg, rg_bstride, rg_accumulate);
 }
 
 // The loss of one loss_grad call: the weights of its terms and the seeds they put into the backward pass.
@@ -463,6 +476,8 @@ struct Objective {
     int T = 0, B = 0;
     const TLayer* ly = nullptr;
     long long n_terms() const { return (long long)(T - 1) * B * ly[0].CHW(); }
+    // the flow objective: kappa of term s, (w_s / sum w) / (B N_m)
+    double flow_kappa(int s) const { return (weight(s) / total_weight()) / (double)(B * flow.n_mask); }
     // squared error: d loss / d P0_s = loss_scale(s) * (P0_s - x_{s+1})
     float loss_scale(int s) const
     {
@@ -550,9 +565,14 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
             // term s: its value into d_step[s] and its seed added to dP0_s, which tpact_bwd then masks; a term of weight zero is not computed
             // with the moving reference and a frame gradient wanted, the term's reference path is added in float to g_{s+1}, which
             // frame_grad_step(s + 1) stored earlier (per frame), or to the one image of the tied mode ahead of this step's input path
+            // under the prediction pairing the reference is P0_{s-1}, state slot s (for s = 0 the call's start state, a constant); the
+            // flow is kept in the workspace for the reference path, which follows this step's terr_bwd
             const double w = o.weight(s);
-            if (w != 0.0)
-                flow_stage(t, st, B, P, CHW, xn, bstride, o.flow, (w / o.total_weight()) / (double)(B * o.flow.n_mask), t->d_spart + (long long)s * STEP_LOSS_BLOCKS,
+            if (w != 0.0 && o.flow.pair_pred)
+                flow_stage(t, st, B, P, CHW, nullptr, CHW, o.flow, o.flow_kappa(s), t->d_spart + (long long)s * STEP_LOSS_BLOCKS, t->d_step + s,
+                           s >= 1 ? t->f_u : nullptr, y.dPn, CHW, 1, nullptr, 0, 0, y.P_at(s, B));
+            else if (w != 0.0)
+                flow_stage(t, st, B, P, CHW, xn, bstride, o.flow, o.flow_kappa(s), t->d_spart + (long long)s * STEP_LOSS_BLOCKS,
                            t->d_step + s, nullptr, y.dPn, CHW, 1, o.flow.moving && fg.p ? fg.p + (long long)(s + 1) * fg.tstride : nullptr, fg.bstride, 1);
             xn = nullptr;
         }
@@ -592,6 +612,10 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
             conv(st, yb.dE, 2 * yb.C, yb.H, yb.W, B, nullptr, 1, {src(ZA, 4 * CHW, y.C, 0, prm + t->lp[l].aW, 1)});
         }
     }
+    // the prediction pairing: dP0_{s-1} holds what layer 0's terr_bwd of this step left; term s adds its gradient by its reference
+    // P0_{s-1} now, and the seed of term s - 1 follows in backward_step(s - 1), ahead of that step's clamp mask
+    if (o.by_flow && o.flow.pair_pred && s >= 1 && s < T - 1 && o.weight(s) != 0.0)
+        flow_ref_path(t, st, B, o.flow, o.flow_kappa(s), t->f_u, t->ly[0].dPn, t->ly[0].CHW(), 1);
 }
 
 // g_s of backward step s, after layer 0's terr_bwd of that step (dE_0 and E_0 of step s are what that kernel read): the input path on
@@ -760,13 +784,16 @@ int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n
     return copy_tables(t, n_tensors, false, t->grd, h_tensors);
 }
 
-int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
-                                 int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
-                                 double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow,
-                                 const float* d_dir, const uint8_t* d_mask, double* h_terms, void* stream)
+int eigen_trainer_loss_grad_flow_pair(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                      int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                      double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride,
+                                      const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double* h_terms, int32_t pairing, void* stream)
 {
     int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, t ? t->cfg.max_steps : 0);
     if (rc) return rc;
+    if (pairing != EIGEN_FLOW_PAIR_FRAME && pairing != EIGEN_FLOW_PAIR_PREDICTION)
+        return tfail(EIGEN_ERR_INVALID, "pairing %d is neither EIGEN_FLOW_PAIR_FRAME nor EIGEN_FLOW_PAIR_PREDICTION", pairing);
+    if (pairing != EIGEN_FLOW_PAIR_FRAME && objective != EIGEN_OBJ_FLOW) return tfail(EIGEN_ERR_INVALID, "EIGEN_FLOW_PAIR_PREDICTION goes with EIGEN_OBJ_FLOW only");
     const int T = n_steps, B = batch;
     const long long C0HW = t->ly[0].CHW();
     FrameGrad fg;
@@ -786,6 +813,9 @@ int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int6
     if (by_flow) {
         rc = check_flow(t, flow, d_dir, d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
         if (rc) return rc;
+        o.flow.pair_pred = pairing == EIGEN_FLOW_PAIR_PREDICTION;
+        // a frame is no reference under the prediction pairing: there is nothing the flag could move
+        if (o.flow.pair_pred && o.flow.moving) return tfail(EIGEN_ERR_INVALID, "EIGEN_FLOW_PAIR_PREDICTION does not take EIGEN_FLOW_MOVING_REFERENCE");
         o.by_flow = true;
         o.h_terms = h_terms;
     }
@@ -814,6 +844,15 @@ int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int6
     return read_loss(t, st, o, want_table, h_loss, h_layer_err);
 }
 
+int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                 int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                 double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow,
+                                 const float* d_dir, const uint8_t* d_mask, double* h_terms, void* stream)
+{
+    return eigen_trainer_loss_grad_flow_pair(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_w, objective, h_layer_w, h_loss, h_layer_err, d_pred,
+                                             d_frame_grad, g_bstride, g_tstride, flow, d_dir, d_mask, h_terms, EIGEN_FLOW_PAIR_FRAME, stream);
+}
+
 int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
                                    int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
                                    double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, void* stream)
@@ -824,12 +863,13 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
                                         d_frame_grad, g_bstride, g_tstride, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
-// the two stage-alone entries: d_refg == nullptr is eigen_trainer_flow_term
+// the three stage-alone entries: d_refg == nullptr is eigen_trainer_flow_term; d_fref, a float reference in place of d_ref, is
+// eigen_trainer_flow_term_pair
 static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
-                          int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream)
+                          int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr)
 {
-    if (!t || !d_pred || !d_ref || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!t || !d_pred || (!d_ref && !d_fref) || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
     if (batch > t->cfg.max_batch) return tfail(EIGEN_ERR_CAPACITY, "batch %d exceeds the trainer's %d", batch, t->cfg.max_batch);
     const long long C0HW = t->ly[0].CHW();
@@ -841,7 +881,7 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     flow_stage(t, st, batch, d_pred, p_bstride, d_ref, r_bstride, f, scale / (double)(batch * f.n_mask), t->d_spart, h_value ? t->d_step : nullptr, d_flow, d_seed,
-               s_bstride, 0, d_refg, rg_bstride, 0);
+               s_bstride, 0, d_refg, rg_bstride, 0, d_fref);
     TCHK(hipGetLastError());
     if (h_value) {
         TCHK(hipMemcpyAsync(h_value, t->d_step, 8, hipMemcpyDeviceToHost, st));
@@ -863,6 +903,15 @@ int eigen_trainer_flow_term_ref(eigen_trainer* t, const float* d_pred, int64_t p
 {
     if (!d_ref_grad) return tfail(EIGEN_ERR_INVALID, "null argument");
     return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream);
+}
+
+int eigen_trainer_flow_term_pair(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const float* d_prev, int64_t r_bstride, int32_t batch,
+                                 const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow,
+                                 float* d_seed, int64_t s_bstride, float* d_prev_grad, int64_t pg_bstride, void* stream)
+{
+    if (!d_prev) return tfail(EIGEN_ERR_INVALID, "null argument");
+    return flow_term_call(t, d_pred, p_bstride, nullptr, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_prev_grad, pg_bstride, stream,
+                          d_prev);
 }
 
 int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,

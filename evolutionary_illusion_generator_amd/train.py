@@ -45,6 +45,8 @@ def _bind(lib):
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                             ctypes.c_void_p]
     lib.eigen_trainer_flow_term_ref.argtypes = lib.eigen_trainer_flow_term.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    lib.eigen_trainer_loss_grad_flow_pair.argtypes = lib.eigen_trainer_loss_grad_flow.argtypes[:-1] + [ctypes.c_int32, ctypes.c_void_p]
+    lib.eigen_trainer_flow_term_pair.argtypes = list(lib.eigen_trainer_flow_term_ref.argtypes)
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_evaluate_err.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -66,6 +68,7 @@ FLOW_MAX_RADIUS = 16
 FLOW_DIRECTIONS = ("tangent", "radial", "horizontal", "vertical")
 FLOW_REFERENCES = ("constant", "moving")
 FLOW_MOVING_REFERENCE = 1  # EIGEN_FLOW_MOVING_REFERENCE
+FLOW_PAIRINGS = {"frame": 0, "prediction": 1}  # EIGEN_FLOW_PAIR_FRAME, EIGEN_FLOW_PAIR_PREDICTION
 
 
 def flow_direction(kind, w, h):
@@ -106,7 +109,12 @@ class FlowObjective:
     The defaults are a design choice: radius 7 is a 15-pixel window, the fitness path's ``lk_win``; eps 1e-2 is in units of summed
     squared gradients of images in [0, 1] (a 15 x 15 window over an edge of contrast 0.1 sums to about 0.1), so it damps flat windows
     and leaves textured ones alone.  ValueError: radius outside 1 .. 16, eps not finite or <= 0, a direction that is not
-    [2, H, W] or not finite, a mask that is not [H, W] or counts no pixel, a reference that is neither "constant" nor "moving"."""
+    [2, H, W] or not finite, a mask that is not [H, W] or counts no pixel, a reference that is neither "constant" nor "moving".
+
+    ``pairing`` is "frame": the reference of term s is frame s + 1.  For a repeated still that is "still -> extended prediction", what
+    the single-image fitness path (``get_vectors``, ``PAIR_SINGLE``) scores.  ``PredictionFlow`` is the other pairing."""
+
+    pairing = "frame"
 
     def __init__(self, radius=7, eps=1e-2, direction=None, mask=None, reference="constant"):
         if reference not in FLOW_REFERENCES:
@@ -148,6 +156,34 @@ class FlowObjective:
             up = lambda a: None if a is None else torch.from_numpy(a).cuda(device)
             self._dev[device] = (up(self.direction), up(self.mask))
         return self._dev[device]
+
+
+class PredictionFlow(FlowObjective):
+    """``objective="flow"`` with the pairing of the population fitness ("The prediction pairing"): the reference of
+    term s is the previous PREDICTION P0_{s-1}, a float image that is itself part of the graph, in place of frame s + 1; for s = 0 it
+    is the start state's P of layer 0 (zeros after a reset, the kept P of a continued call), a constant.  Term s is then the flow from
+    P0_{s-1} to P0_s, and its gradient enters the backward pass twice: by P0_s as before, and by P0_{s-1} one step earlier.  With the
+    weight on the term "prediction after the last fed frame -> first extended prediction" alone (``refine_stills``' default under this
+    class) the loss is the dense stand-in for what ``get_fitnesses_neat`` / ``eval_images(pairing=PAIR_POPULATION)`` score.  Frames are no
+    references here: a frame gradient is the input path alone, which is the whole gradient, and there is no `reference` argument.
+    radius, eps, direction, mask: as ``FlowObjective``."""
+
+    pairing = "prediction"
+
+    def __init__(self, radius=7, eps=1e-2, direction=None, mask=None):
+        super().__init__(radius, eps, direction, mask)
+
+
+def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, reference="constant"):
+    """The flow objective of a command line: a ``FlowObjective`` (pairing "frame", with its `reference`) or a ``PredictionFlow``
+    (pairing "prediction"; it has no frame as a reference, so reference="moving" is a ValueError)."""
+    if pairing not in FLOW_PAIRINGS:
+        raise ValueError("pairing must be one of %s, got %r" % (", ".join(FLOW_PAIRINGS), pairing))
+    if pairing == "frame":
+        return FlowObjective(radius, eps, direction, mask, reference=reference)
+    if reference != "constant":
+        raise ValueError("the prediction pairing has no frame as a reference: reference=%r does not go with it" % (reference,))
+    return PredictionFlow(radius, eps, direction, mask)
 
 
 def _check_flow(objective, flow):
@@ -409,8 +445,12 @@ class PredNetTrainer:
         if by_flow:
             terms = np.zeros(max(T - 1, 1), np.float64)
             cfg = flow.settings()
-            _check(self.lib.eigen_trainer_loss_grad_flow(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask),
-                                                         _ptr(terms), _stream_arg(stream)))
+            if flow.pairing == "frame":
+                _check(self.lib.eigen_trainer_loss_grad_flow(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask),
+                                                             _ptr(terms), _stream_arg(stream)))
+            else:
+                _check(self.lib.eigen_trainer_loss_grad_flow_pair(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), ctypes.byref(cfg), _ptr(d_dir),
+                                                                  _ptr(d_mask), _ptr(terms), ctypes.c_int32(FLOW_PAIRINGS[flow.pairing]), _stream_arg(stream)))
             self.last_flow_terms = terms[:T - 1]
         elif frame_grads is None:
             _check(self.lib.eigen_trainer_loss_grad_obj(*args, _stream_arg(stream)))
@@ -448,6 +488,9 @@ class PredNetTrainer:
         FlowObjective has reference="moving": frame s + 1 is then in the graph as the reference of term s, and g_t = fl(input path of
         step t + reference path of term t - 1); "tied" starts from zero and for s = T - 1 .. 0 adds the reference path of term s, then
         the input path of step s.  Nothing else the call returns depends on that setting.
+        With flow=PredictionFlow(...) term s runs from the previous prediction P0_{s-1} (for s = 0 the start state's P0: zeros after a
+        reset) to prediction s, both in the graph ("The prediction pairing"); loss and terms are those of that
+        pairing and the frame gradient is the input path alone.
         flow_terms=True (flow only) appends the float64 [T - 1] terms last; a term of weight zero is not computed and reads 0."""
         if frame_grads not in FRAME_GRADS:
             raise ValueError("frame_grads must be None, 'frames' or 'tied', got %r" % (frame_grads,))
@@ -493,6 +536,36 @@ class PredNetTrainer:
         rg = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
         _check(self.lib.eigen_trainer_flow_term_ref(*args, _ptr(rg), ctypes.c_int64(per), None))
         return value.value, u.cpu().numpy(), seed.cpu().numpy(), rg.cpu().numpy()
+
+    def flow_term_pair(self, pred, prev, flow, scale=1.0, reference_grad=False):
+        """The flow stage alone on a pair of float images (eigen_trainer_flow_term_pair), with the kernels a training call runs under a
+        ``PredictionFlow``: pred float32 [n, C, H, W], the prediction; prev float32 [n, C, H, W], the reference (the previous
+        prediction); n <= batch.  -> (value, u, seed) as ``flow_term``; reference_grad=True appends scale * d value / d prev, float32
+        [n, C, H, W]: what a training call adds to d loss / d P0_{s-1}.  The radius, eps, direction and mask of `flow` are used; its
+        pairing and `reference` play no part here."""
+        torch = self._torch
+        if not isinstance(flow, FlowObjective):
+            raise ValueError("flow must be a FlowObjective, got %r" % (flow,))
+        if not np.isfinite(scale):
+            raise ValueError("scale must be finite, got %r" % (scale,))
+        shp = (self.channels[0], self.h, self.w)
+        dev = "cuda:%d" % self.device
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))).to(dev).contiguous()
+        p, r = up(pred), up(prev)
+        if p.dtype != torch.float32 or r.dtype != torch.float32 or p.dim() != 4 or tuple(p.shape[1:]) != shp or tuple(r.shape) != tuple(p.shape):
+            raise ValueError("pred and prev must be float32, both [n, %d, %d, %d]; got %s %s and %s %s" % (shp + (p.dtype, tuple(p.shape), r.dtype, tuple(r.shape))))
+        n, per = int(p.shape[0]), int(np.prod(shp))
+        d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w)
+        value = ctypes.c_double(0.0)
+        u = torch.empty((n, 2, self.h, self.w), dtype=torch.float64, device=dev)
+        seed = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
+        rg = torch.empty((n,) + shp, dtype=torch.float32, device=dev) if reference_grad else None
+        cfg = flow.settings(stage_alone=True)
+        _check(self.lib.eigen_trainer_flow_term_pair(self._h, _ptr(p), ctypes.c_int64(per), _ptr(r), ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg),
+                                                     _ptr(d_dir), _ptr(d_mask), ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(u), _ptr(seed),
+                                                     ctypes.c_int64(per), _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None))
+        out = (value.value, u.cpu().numpy(), seed.cpu().numpy())
+        return out + (rg.cpu().numpy(),) if reference_grad else out
 
     def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False, layer_errors=False):
         """Forward only, no tape: the mean squared error of every step of frames uint8 [n, T, C, H, W], T of any length, as
@@ -600,6 +673,15 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
     reference frame of every flow term: with FlowObjective(reference="constant") the step follows the input path alone and ignores how the
     term moves with its reference, with reference="moving" it follows the whole gradient.
 
+    Which fitness path the loss stands in for: a ``FlowObjective`` pairs the still with the extended predictions, the pairing of the
+    single-image path (``get_vectors``, ``PAIR_SINGLE``).  flow=PredictionFlow(...) pairs consecutive predictions, as the population path
+    does (``get_fitnesses_neat``, ``eval_images(pairing=PAIR_POPULATION)``): the default step_weights are then 0 for the terms s < n_repeat
+    and 1 for the n_ext - 1 terms between extended predictions and their predecessors, at n_ext = 2 exactly the term "prediction after
+    the last fed frame -> first extended prediction" that fitness scores; n_ext < 2 leaves no such term and is a ValueError.
+    With requant=True the byte a self-fed step reads is a constant of the graph, so the gradient does not hold how that byte follows the
+    prediction; under a PredictionFlow every weighted term passes through such a step, and at 160 x 120 that gradient was measured
+    not to predict the change of the loss, while with requant=False it does ("The prediction pairing").
+
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images.  The calls
     OVERWRITE the trainer's weight gradients and its kept sequence state."""
     T = int(n_repeat) + int(n_ext)
@@ -610,8 +692,7 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
         raise ValueError("n_repeat + n_ext = %d frames exceed the trainer's max_steps %d" % (T, trainer.max_steps))
     if not (np.isfinite(step) and step > 0):
         raise ValueError("step must be finite and > 0, got %r" % (step,))
-    if step_weights is None:
-        step_weights = [0.0] * (n_repeat - 1) + [1.0] * n_ext
+    step_weights = _still_weights(step_weights, n_repeat, n_ext, flow)
     torch = trainer._torch
     if isinstance(images, torch.Tensor):
         img = images.detach().to("cuda:%d" % trainer.device).clone()
@@ -641,6 +722,17 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
                                                     ctypes.c_int32(n), None))
     history[iters], _ = loss_of(None)
     return img.cpu().numpy(), history
+
+
+def _still_weights(step_weights, n_repeat, n_ext, flow):
+    """the step weights of refine_stills / refine_genomes: as given, else the extension's terms under the pairing of `flow`.  Under a
+    PredictionFlow the first of them, P0_{n_repeat - 1} -> P0_{n_repeat}, is term n_repeat; n_ext < 2 has none (ValueError)."""
+    by_pred = flow is not None and flow.pairing == "prediction"
+    if by_pred and n_ext < 2:
+        raise ValueError("a PredictionFlow needs n_ext >= 2: its first term between two predictions of the extension is term n_repeat, got n_ext = %d" % n_ext)
+    if step_weights is not None:
+        return step_weights
+    return [0.0] * n_repeat + [1.0] * (n_ext - 1) if by_pred else [0.0] * (n_repeat - 1) + [1.0] * n_ext
 
 
 PARAM_KINDS = ("weight", "bias", "response")
@@ -713,7 +805,10 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     them).  FROZEN, i.e. never updated: folded float32 constants (``genome.flatten_genome_map``'s None entries and everything inside a
     folded sub-graph), disabled connections and whatever the outputs do not depend on.
 
-    objective "flow" takes flow=FlowObjective(...) as ``refine_stills`` does, its `reference` setting included.
+    objective "flow" takes flow=FlowObjective(...) as ``refine_stills`` does, its `reference` setting included: that loss pairs the
+    still with the extended predictions and stands in for the single-image fitness path (``get_vectors``, ``PAIR_SINGLE``).
+    flow=PredictionFlow(...) pairs consecutive predictions and stands in for the population path (``get_fitnesses_neat``,
+    ``eval_images(pairing=PAIR_POPULATION)``); the default step_weights and the n_ext >= 2 rule are ``refine_stills``'.
 
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images, which are the
     render of genomes'.  The calls OVERWRITE the trainer's weight gradients and its kept sequence state."""
@@ -736,8 +831,7 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     if not params or any(k not in PARAM_KINDS for k in params):
         raise ValueError("params must be a non-empty selection of %s, got %r" % (", ".join(PARAM_KINDS), params))
     limits = _genome_bounds(config, bounds)
-    if step_weights is None:
-        step_weights = [0.0] * (n_repeat - 1) + [1.0] * n_ext
+    step_weights = _still_weights(step_weights, n_repeat, n_ext, flow)
     torch = trainer._torch
     C0, h, w = trainer.channels[0], trainer.h, trainer.w
     n_in = len(config.genome_config.input_keys)
@@ -783,4 +877,4 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
 
 
 __all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update", "FlowObjective",
-           "flow_direction"]
+           "PredictionFlow", "make_flow", "flow_direction"]

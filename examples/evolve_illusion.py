@@ -6,7 +6,8 @@
     python -m torch.distributed.run --nproc-per-node 8 examples/evolve_illusion.py ...   (population sharded over GPUs)
     python examples/evolve_illusion.py -g 5 --refine 4 --refine_iters 5    (Lamarckian step: after every generation the parameters of
         the 4 best genomes are replaced by those `train.refine_genomes` climbs to, before reproduction; gradient = 1 renders only;
-        --objective flow --flow-direction tangent climbs the flow objective instead of the squared error)
+        --objective flow --flow-direction tangent climbs the flow objective instead of the squared error;
+        --flow-pairing prediction pairs consecutive predictions, as the fitness that selects does)
 """
 import argparse
 import os
@@ -38,6 +39,8 @@ def main():
     ap.add_argument("--flow-radius", type=int, default=7)
     ap.add_argument("--flow-eps", type=float, default=1e-2)
     ap.add_argument("--flow-reference", default="constant", choices=["constant", "moving"], help="objective flow: moving also follows how the term moves with the still as its reference frame")
+    ap.add_argument("--flow-pairing", default="frame", choices=["frame", "prediction"],
+                    help="objective flow: frame pairs the still with the extended predictions, prediction pairs consecutive predictions as the population fitness does")
     a = ap.parse_args()
     w, h = {"small": (160, 120), "big": (640, 480)}.get(a.size) or (int(a.size), int(a.size))
     channels = [int(c) for c in a.channels.split(",")]
@@ -66,7 +69,8 @@ def main():
         flow = None
         if a.objective == "flow":
             inside = (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype("uint8")
-            flow = train.FlowObjective(a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), inside, reference=a.flow_reference)
+            flow = train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), inside,
+                                   reference=a.flow_reference)
         refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters, objective=a.objective, flow=flow)
         for g, r in zip(best, refined):
             for k, n in r.nodes.items():

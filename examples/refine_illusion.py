@@ -10,6 +10,7 @@ every image before and after.  Whether the fitness follows the stand-in is an ob
     python examples/refine_illusion.py [-m model.npz] [--size small|N] [-s 1] [-c 3] [--pop 16] [-k 4] [--iters 10] [--step 2]
     python examples/refine_illusion.py --png image.png -o refined
     python examples/refine_illusion.py --objective flow --flow-direction tangent [--flow-radius 7] [--flow-eps 1e-2] [--flow-reference constant|moving]
+        [--flow-pairing frame|prediction]   (prediction: the flow between consecutive predictions, the pairing of the fitness printed here)
         (climb the displacement a dense Lucas-Kanade solve finds between the still and the prediction, inside the structure)
 """
 import argparse
@@ -36,8 +37,8 @@ def flow_of(a, w, h, mask=None):
     """the FlowObjective of the command line (None under another objective); the term counts the pixels of `mask`"""
     if a.objective != "flow":
         return None
-    return train.FlowObjective(a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask,
-                               reference=a.flow_reference)
+    return train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask,
+                           reference=a.flow_reference)
 
 
 def main():
@@ -59,6 +60,9 @@ def main():
     ap.add_argument("--flow-eps", type=float, default=1e-2, help="objective flow: the regulariser of the 2x2 systems")
     ap.add_argument("--flow-reference", default="constant", choices=list(train.FLOW_REFERENCES),
                     help="objective flow: moving also follows how the term moves with the still as its reference frame (constant: the input path alone)")
+    ap.add_argument("--flow-pairing", default="frame", choices=list(train.FLOW_PAIRINGS),
+                    help="objective flow: frame pairs the still with the extended predictions (the single-image fitness path), prediction pairs consecutive "
+                         "predictions, as the population fitness printed here does; prediction takes --flow-reference constant only")
     ap.add_argument("--n_repeat", type=int, default=20)
     ap.add_argument("--n_ext", type=int, default=2)
     ap.add_argument("--output_dir", "-o", default=None, help="write before_<i>.png / after_<i>.png here")

@@ -463,6 +463,43 @@ int eigen_trainer_flow_term_ref(eigen_trainer* t, const float* d_pred, int64_t p
                                 double* h_value, double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride,
                                 void* stream);
 
+/* The pairing of EIGEN_OBJ_FLOW ("The prediction pairing"): which image is the reference of term s.
+ *   EIGEN_FLOW_PAIR_FRAME: frame s + 1, bytes; eigen_trainer_loss_grad_flow.  For a repeated still that is "still -> extended
+ *     prediction", the pairing of EIGEN_PAIR_SINGLE.
+ *   EIGEN_FLOW_PAIR_PREDICTION: the previous prediction P0_{s-1}, floats, itself part of the graph; for s = 0 the start state's P of
+ *     layer 0 (zeros after a reset, the kept P of a continued call), a constant of the call.  With step weights that select the term
+ *     "prediction after the last fed frame -> first extended prediction" that is what EIGEN_PAIR_POPULATION scores. */
+enum { EIGEN_FLOW_PAIR_FRAME = 0, EIGEN_FLOW_PAIR_PREDICTION = 1 };
+
+/* eigen_trainer_loss_grad_flow plus the pairing.  EIGEN_FLOW_PAIR_FRAME: the call IS eigen_trainer_loss_grad_flow, launch for launch and
+ * bit for bit.  EIGEN_FLOW_PAIR_PREDICTION (objective EIGEN_OBJ_FLOW only): term s is the value of eigen_trainer_flow_term_pair for P0_s
+ * against P0_{s-1}; loss and h_terms are those of this pairing, a term with w_s = 0 is not computed and reports 0.0.  Every computed
+ * term has two seeds, both with scale = w_s / sum w: its seed by P0_s, added in float to d loss / d P0_s ahead of the clamp's mask as
+ * under the frame pairing, and, for s >= 1, its gradient by its reference (d_prev_grad of eigen_trainer_flow_term_pair), added in float
+ * to d loss / d P0_{s-1} ahead of that step's clamp mask.  The float additions into d loss / d P0_{s-1} come in this order: what layer
+ * 0's error units of step s leave there; then the reference path of term s; then the seed of term s - 1.  Self-fed steps need nothing
+ * special: with requantised feedback the fed-back byte is a constant as before while the reference of the term stays the float
+ * P0_{s-1}.  Frames are no references: d_frame_grad holds the input path alone, which is the whole gradient.
+ * Errors: as eigen_trainer_loss_grad_flow; EIGEN_ERR_INVALID, before any launch, an unknown pairing, EIGEN_FLOW_PAIR_PREDICTION under
+ * another objective, and EIGEN_FLOW_PAIR_PREDICTION together with EIGEN_FLOW_MOVING_REFERENCE. */
+int eigen_trainer_loss_grad_flow_pair(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                      int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                      const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                      int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                      const uint8_t* d_mask, double* h_terms, int32_t pairing, void* stream);
+
+/* The flow stage alone on one pair of FLOAT images per sample, with the kernels a training call runs under
+ * EIGEN_FLOW_PAIR_PREDICTION: eigen_trainer_flow_term with I0 the gray of d_prev (floats widened to double; sample b at d_prev + b *
+ * r_bstride floats as [C][H][W]) in place of the reference bytes.  d_prev_grad (may be NULL): scale * d value / d d_prev, the gradient
+ * eigen_trainer_flow_term_ref states, float, sample b at d_prev_grad + b * pg_bstride as [C][H][W], a plain store.  With d_prev =
+ * (float)byte / 255.0f of a frame every output is eigen_trainer_flow_term_ref's on that frame, bit for bit.
+ * Errors: as eigen_trainer_flow_term (non-zero flags among them); EIGEN_ERR_INVALID a NULL d_prev, or a pg_bstride below C*H*W when
+ * d_prev_grad is given. */
+int eigen_trainer_flow_term_pair(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const float* d_prev, int64_t r_bstride,
+                                 int32_t batch, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale,
+                                 double* h_value, double* d_flow, float* d_seed, int64_t s_bstride, float* d_prev_grad, int64_t pg_bstride,
+                                 void* stream);
+
 /* One normalised ascent step on uint8 stills d_images [batch][C][H][W], in place, from a tied gradient (image b at d_grad + b *
  * g_bstride floats): per image m_b = max |g| over the pixels the mask keeps free, then x = byte / 255.0f,
  * x' = min(max(x + k * (g / m_b), 0), 1) with k = (float)(step_bytes / 255.0), byte' = (uint8_t)(int)(x' * 255.0f + 0.5f), each one

@@ -5,7 +5,7 @@ the tape-free evaluate of that call.  Prints one JSON line per side and writes p
 
     python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both] [--objective mse|l0|lall]
     python scripts/train_bench.py --frame-grads [--steps 5] [--warmup 2]
-    python scripts/train_bench.py --flow-cost [--steps 5] [--warmup 2] [--flow-reference constant|moving]
+    python scripts/train_bench.py --flow-cost [--steps 5] [--warmup 2] [--flow-reference constant|moving] [--flow-pairing frame|prediction]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
 side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
@@ -14,6 +14,8 @@ energy, the last two terms weighted); --flow-cost times one loss_grad call (no A
 weights, alternated round by round in one process, and prints the ms per call of each with the spread over the rounds.
 --flow-reference moving gives the FlowObjective the moving reference; --flow-cost then adds two legs, the "flow" call with tied frame
 gradients (left on the device) under the constant and under the moving reference: their difference is what the mode costs.
+--flow-pairing prediction makes the flow objective a PredictionFlow (term s from prediction s - 1 to prediction s); --flow-cost then adds
+one leg, "flow_prediction", beside "mse" and the frame-pairing "flow": their difference over the two computed terms is what the pairing costs.
 """
 import argparse
 import json
@@ -58,14 +60,17 @@ def frames(seed, n, T, c, h, w):
 FLOW_WEIGHTS = [0.0] * (T - 3) + [1.0, 1.0]   # two weighted terms, as a refinement call has them
 
 
-def objective_args(name, reference="constant"):
+def objective_args(name, reference="constant", pairing="frame"):
+    if name == "flow" and pairing == "prediction":
+        from evolutionary_illusion_generator_amd.train import PredictionFlow
+        return dict(objective="flow", flow=PredictionFlow(radius=7, eps=1e-2), step_weights=FLOW_WEIGHTS)
     if name == "flow":
         from evolutionary_illusion_generator_amd.train import FlowObjective
         return dict(objective="flow", flow=FlowObjective(radius=7, eps=1e-2, reference=reference), step_weights=FLOW_WEIGHTS)
     return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
 
 
-def run_flow_cost(steps, warmup, rounds=6, reference="constant"):
+def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"):
     """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round; with
     the moving reference also per "flow" call with tied frame gradients, under either reference"""
     import ctypes
@@ -77,6 +82,8 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant"):
     if reference == "moving":
         calls["flow_tied_constant"] = dict(objective_args("flow"), frame_grads="tied")
         calls["flow_tied_moving"] = dict(objective_args("flow", "moving"), frame_grads="tied")
+    if pairing == "prediction":
+        calls["flow_prediction"] = objective_args("flow", pairing="prediction")
     ms = {k: [] for k in calls}
     loss = {}
     with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
@@ -102,13 +109,13 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant"):
     return [dict(side="loss_grad_" + k, call_ms=float(np.median(v)), call_ms_min=min(v), call_ms_max=max(v), rounds=rounds, loss=loss[k]) for k, v in ms.items()]
 
 
-def run_trainer(steps, warmup, objective="mse", reference="constant"):
+def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame"):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
     d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
     tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T)
-    kw = objective_args(objective, reference)
+    kw = objective_args(objective, reference, pairing)
     for _ in range(warmup):
         tr.step(d, **kw)
     torch.cuda.synchronize()
@@ -241,10 +248,14 @@ def main():
     ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall", "flow"], help="the trainer side's objective")
     ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
     ap.add_argument("--flow-reference", default="constant", choices=["constant", "moving"], help="the flow objective's reference frame: a constant of the graph, or part of it")
+    ap.add_argument("--flow-pairing", default="frame", choices=["frame", "prediction"],
+                    help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)")
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
     a = ap.parse_args()
+    if a.flow_pairing == "prediction" and a.flow_reference == "moving":
+        ap.error("--flow-pairing prediction has no frame as a reference: it does not take --flow-reference moving")
     if a.side == "torch":
         print(json.dumps(run_torch(a.steps, a.warmup)))
         return
@@ -253,10 +264,10 @@ def main():
             print(json.dumps(r), flush=True)
         return
     if a.flow_cost:
-        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference):
+        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing):
             print(json.dumps(r), flush=True)
         return
-    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference)]
+    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing)]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
