@@ -436,30 +436,37 @@ void flow_ref_path(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, d
     ew(st, tflow_ref_fold_kernel, n, (const double*)t->f_r, n, y.H, y.W, y.C, d_refg, rg_bstride, rg_accumulate);
 }
 
-// The flow stage of one prediction / reference pair per sample (eigen_trainer_flow_term states the arithmetic): the planes, the tiled
-// solve, then what is wanted of the value (d_value, through the STEP_LOSS_BLOCKS partials at part), the flow and the seed.  d_refg
-// (may be null): the term's gradient by its reference frame (flow_ref_kernels.h), from the planes, q and u this stage leaves; u is then
-// written to the handle's workspace unless the caller wants it anyway.  fref: the reference as a float image (the prediction pairing,
-// flow_pair_kernels.h), in place of the bytes at ref.
-void flow_stage(eigen_trainer* t, hipStream_t st, int B, const float* pred, long long p_bstride, const uint8_t* ref, long long r_bstride, const FlowSpec& f,
-                double kappa, double* part, double* d_value, double* d_flow, float* d_seed, long long s_bstride, int accumulate, float* d_refg = nullptr,
-                long long rg_bstride = 0, int rg_accumulate = 0, const float* fref = nullptr)
+// One term for the flow stage and what is wanted of it; every target may be null.  Sample b of an image is at its pointer + b * its stride.
+struct FlowTerm {
+    const float* pred = nullptr; long long p_bstride = 0;
+    const uint8_t* ref = nullptr; const float* fref = nullptr; long long r_bstride = 0;  // the reference as bytes, or as floats (flow_pair_kernels.h): exactly one
+    double kappa = 0.0;                                                   // the scale of the seed and of the reference gradient
+    double *part = nullptr, *d_value = nullptr;                           // the value into d_value, through the STEP_LOSS_BLOCKS partials at part
+    double* d_flow = nullptr;                                             // the flow u [B][2][H W]
+    float* d_seed = nullptr; long long s_bstride = 0; int s_accumulate = 0;   // kappa d value / d pred, added in float or stored
+    float* d_refg = nullptr; long long rg_bstride = 0; int rg_accumulate = 0; // kappa d value / d reference (flow_ref_kernels.h), likewise
+};
+
+// The flow stage of one term (eigen_trainer_flow_term states the arithmetic): the planes, the tiled solve, then what is wanted of the
+// value, the flow and the seed.  A reference gradient is formed from the planes, q and u this stage leaves: u is then written to the
+// handle's workspace unless the caller wants it anyway.
+void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m)
 {
-    if (d_refg && !d_flow) d_flow = t->f_u;
+    double* d_flow = m.d_refg && !m.d_flow ? t->f_u : m.d_flow;
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
-    if (fref) ew(st, tflow_pair_prep_kernel, n, pred, p_bstride, fref, r_bstride, y.C, y.H, y.W, n, t->f_planes);
-    else ew(st, tflow_prep_kernel, n, pred, p_bstride, ref, r_bstride, y.C, y.H, y.W, n, t->f_planes);
+    if (m.fref) ew(st, tflow_pair_prep_kernel, n, m.pred, m.p_bstride, m.fref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
+    else ew(st, tflow_prep_kernel, n, m.pred, m.p_bstride, m.ref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
     const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
     hipLaunchKernelGGL(tflow_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, n, y.H, y.W, f.r, f.eps, f.dir, f.mask, t->f_q, t->f_mv, d_flow);
-    if (d_value) {
-        hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, part);
-        hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), d_value, 1);
+    if (m.d_value) {
+        hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
+        hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)m.part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), m.d_value, 1);
     }
-    if (d_seed)
-        hipLaunchKernelGGL(tflow_seed_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, n, y.H, y.W, y.C, f.r, kappa, d_seed,
-                           s_bstride, accumulate);
-    if (d_refg) flow_ref_path(t, st, B, f, kappa, d_flow, d_refg, rg_bstride, rg_accumulate);
+    if (m.d_seed)
+        hipLaunchKernelGGL(tflow_seed_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, n, y.H, y.W, y.C, f.r, m.kappa, m.d_seed,
+                           m.s_bstride, m.s_accumulate);
+    if (m.d_refg) flow_ref_path(t, st, B, f, m.kappa, d_flow, m.d_refg, m.rg_bstride, m.rg_accumulate);
 }
 
 // The loss of one loss_grad call: the weights of its terms and the seeds they put into the backward pass.
@@ -567,13 +574,20 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
             // frame_grad_step(s + 1) stored earlier (per frame), or to the one image of the tied mode ahead of this step's input path
             // under the prediction pairing the reference is P0_{s-1}, state slot s (for s = 0 the call's start state, a constant); the
             // flow is kept in the workspace for the reference path, which follows this step's terr_bwd
-            const double w = o.weight(s);
-            if (w != 0.0 && o.flow.pair_pred)
-                flow_stage(t, st, B, P, CHW, nullptr, CHW, o.flow, o.flow_kappa(s), t->d_spart + (long long)s * STEP_LOSS_BLOCKS, t->d_step + s,
-                           s >= 1 ? t->f_u : nullptr, y.dPn, CHW, 1, nullptr, 0, 0, y.P_at(s, B));
-            else if (w != 0.0)
-                flow_stage(t, st, B, P, CHW, xn, bstride, o.flow, o.flow_kappa(s), t->d_spart + (long long)s * STEP_LOSS_BLOCKS,
-                           t->d_step + s, nullptr, y.dPn, CHW, 1, o.flow.moving && fg.p ? fg.p + (long long)(s + 1) * fg.tstride : nullptr, fg.bstride, 1);
+            if (o.weight(s) != 0.0) {
+                FlowTerm m;
+                m.pred = P; m.p_bstride = CHW; m.kappa = o.flow_kappa(s);
+                m.part = t->d_spart + (long long)s * STEP_LOSS_BLOCKS; m.d_value = t->d_step + s;
+                m.d_seed = y.dPn; m.s_bstride = CHW; m.s_accumulate = 1;
+                if (o.flow.pair_pred) {
+                    m.fref = y.P_at(s, B); m.r_bstride = CHW;
+                    m.d_flow = s >= 1 ? t->f_u : nullptr;
+                } else {
+                    m.ref = xn; m.r_bstride = bstride;
+                    m.d_refg = o.flow.moving && fg.p ? fg.p + (long long)(s + 1) * fg.tstride : nullptr; m.rg_bstride = fg.bstride; m.rg_accumulate = 1;
+                }
+                flow_stage(t, st, B, o.flow, m);
+            }
             xn = nullptr;
         }
         const float scale = !xn ? 0.f : o.by_error ? o.err_scale(s, 0) : o.loss_scale(s);
@@ -717,6 +731,123 @@ int read_loss(eigen_trainer* t, hipStream_t st, const Objective& o, bool want_ta
     return EIGEN_OK;
 }
 
+// Everything a training call takes: the arguments of the widest exported entry, eigen_trainer_loss_grad_flow_pair.  An entry lists the
+// leading members, which every entry has, names the others it takes, and leaves the rest at these defaults, which are what it implies.
+struct LossGradCall {
+    const uint8_t* d_frames; int64_t bstride; int32_t batch, n_steps, n_fed, requant, reset; double* h_loss; float* d_pred; void* stream;
+    const double* h_step_w = nullptr;
+    int32_t objective = EIGEN_OBJ_MSE;
+    const double* h_layer_w = nullptr;
+    double* h_layer_err = nullptr;
+    FrameGrad fg;
+    const eigen_flow_settings* flow = nullptr;
+    const float* d_dir = nullptr;
+    const uint8_t* d_mask = nullptr;
+    double* h_terms = nullptr;
+    int32_t pairing = EIGEN_FLOW_PAIR_FRAME;
+};
+
+// The training call behind every exported eigen_trainer_loss_grad* entry.  The order of the checks is the order of this function: the
+// call's own arguments (check_call), the pairing, the frame gradient's strides, the objective with its weights, the flow settings; then
+// the launches.  An entry that cannot state EIGEN_OBJ_FLOW's settings refuses that objective in its own body, ahead of all of these.
+int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
+{
+    int rc = check_call(t, c.d_frames, c.bstride, c.batch, c.n_steps, c.n_fed, c.requant, c.reset, t ? t->cfg.max_steps : 0);
+    if (rc) return rc;
+    if (c.pairing != EIGEN_FLOW_PAIR_FRAME && c.pairing != EIGEN_FLOW_PAIR_PREDICTION)
+        return tfail(EIGEN_ERR_INVALID, "pairing %d is neither EIGEN_FLOW_PAIR_FRAME nor EIGEN_FLOW_PAIR_PREDICTION", c.pairing);
+    if (c.pairing != EIGEN_FLOW_PAIR_FRAME && c.objective != EIGEN_OBJ_FLOW) return tfail(EIGEN_ERR_INVALID, "EIGEN_FLOW_PAIR_PREDICTION goes with EIGEN_OBJ_FLOW only");
+    const int T = c.n_steps, B = c.batch;
+    const long long C0HW = t->ly[0].CHW();
+    const FrameGrad& fg = c.fg;
+    if (fg.p) {
+        if (fg.tstride != 0 && fg.tstride < C0HW)
+            return tfail(EIGEN_ERR_INVALID, "g_tstride %lld is neither 0 (tied) nor at least a frame (%lld floats)", fg.tstride, C0HW);
+        const long long extent = fg.tstride == 0 ? C0HW : (long long)(T - 1) * fg.tstride + C0HW;
+        if (fg.bstride < extent) return tfail(EIGEN_ERR_INVALID, "g_bstride %lld is smaller than one sample's gradient (%lld floats)", fg.bstride, extent);
+    }
+    Objective o;
+    const bool by_flow = c.objective == EIGEN_OBJ_FLOW;
+    if (!by_flow && (c.flow || c.d_dir || c.d_mask)) return tfail(EIGEN_ERR_INVALID, "flow settings, direction and mask go with EIGEN_OBJ_FLOW only");
+    // the step and layer weights follow the same rules under every objective
+    rc = make_objective(t, by_flow ? (int32_t)EIGEN_OBJ_MSE : c.objective, c.h_layer_w, c.h_step_w, T, B, o);
+    if (rc) return rc;
+    if (by_flow) {
+        rc = check_flow(t, c.flow, c.d_dir, c.d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
+        if (rc) return rc;
+        o.flow.pair_pred = c.pairing == EIGEN_FLOW_PAIR_PREDICTION;
+        // a frame is no reference under the prediction pairing: there is nothing the flag could move
+        if (o.flow.pair_pred && o.flow.moving) return tfail(EIGEN_ERR_INVALID, "EIGEN_FLOW_PAIR_PREDICTION does not take EIGEN_FLOW_MOVING_REFERENCE");
+        o.by_flow = true;
+        o.h_terms = c.h_terms;
+    }
+    hipStream_t st = (hipStream_t)c.stream;
+    rc = start_state(t, st, B, c.reset);
+    if (rc) return rc;
+    // forward with tape: step s reads state slot s, writes state slot s + 1 and tape slot s
+    for (int s = 0; s < T; ++s)
+        forward_step(t, st, B, s, s + 1, s, s < c.n_fed ? c.d_frames + s * C0HW : nullptr, c.bstride, c.requant, c.d_pred ? c.d_pred + s * C0HW : nullptr, T * C0HW);
+    const bool want_table = T >= 2 && (c.h_layer_err || (o.by_error && c.h_loss));
+    rc = reduce_losses(t, st, o, c.d_frames, c.bstride, want_table);
+    if (rc) return rc;
+    // backward through time, from zero carries
+    for (int l = 0; l < t->L; ++l)
+        for (float* a : {t->ly[l].dPn, t->ly[l].dhc, t->ly[l].dc}) TCHK(hipMemsetAsync(a, 0, B * t->ly[l].CHW() * 4, st));
+    // the tied frame gradient starts from zero; only the C0 H W floats of every sample are touched, whatever g_bstride is
+    for (int b = 0; fg.p && fg.tstride == 0 && b < B; ++b) TCHK(hipMemsetAsync(fg.p + b * fg.bstride, 0, C0HW * 4, st));
+    for (int s = T - 1; s >= 0; --s) {
+        backward_step(t, st, o, s, c.d_frames, c.bstride, fg);
+        if (fg.p) frame_grad_step(t, st, o, s, c.n_fed, c.d_frames, c.bstride, fg);
+    }
+    weight_gradients(t, st, T, B);
+    TCHK(hipGetLastError());
+    t->state_batch = B;
+    t->state_slot = T;
+    return read_loss(t, st, o, want_table, c.h_loss, c.h_layer_err);
+}
+
+// the evaluation behind eigen_trainer_evaluate and eigen_trainer_evaluate_err
+int evaluate_call(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant, int32_t reset,
+                  double* h_step_loss, double* h_layer_err, float* d_pred, void* stream)
+{
+    int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, -1);
+    if (rc) return rc;
+    const int T = n_steps, B = batch, M = t->cfg.max_steps, L = t->L;
+    const long long C0HW = t->ly[0].CHW();
+    hipStream_t st = (hipStream_t)stream;
+    rc = start_state(t, st, B, reset);
+    if (rc) return rc;
+    // state slots 0 and 1 in turn, tape slot 0; the loss of step s goes to d_step[s % max_steps], read back whenever that table is
+    // full.  Row r of the error table lives at d_err[r % max_steps]: its image-layer entry is reduced after step r, its upper entries
+    // (E_l of step r + 1) after step r + 1, and the rows are read back once the table's last row, or the call's, is complete --
+    // ahead of the image-layer entry that reuses row 0.
+    auto flush = [&](double* host, const double* dev, int r, int width) {  // rows r - r % M .. r, once r is the table's last row or the call's
+        if (r % M != M - 1 && r != T - 2) return hipSuccess;
+        return hipMemcpyAsync(host + (long long)(r - r % M) * width, dev, (long long)(r % M + 1) * width * 8, hipMemcpyDeviceToHost, st);
+    };
+    for (int s = 0; s < T; ++s) {
+        const int in = s & 1, out = in ^ 1;
+        forward_step(t, st, B, in, out, 0, s < n_fed ? d_frames + s * C0HW : nullptr, bstride, requant, d_pred ? d_pred + s * C0HW : nullptr, T * C0HW);
+        const float* P0 = t->ly[0].P_at(out, B);
+        const uint8_t* next = d_frames + (s + 1) * C0HW;  // the frame P0 predicts (read only while s < T - 1)
+        if (h_layer_err && s >= 1) {
+            upper_errors(t, st, 0, 1, B, t->d_err + (long long)((s - 1) % M) * L);
+            TCHK(flush(h_layer_err, t->d_err, s - 1, L));
+        }
+        if (h_layer_err && s < T - 1) reduce_steps(TERM_ABS, t, st, P0, next, bstride, C0HW, 1, B, (double)(B * 2 * C0HW), t->d_err + (long long)(s % M) * L, L);
+        if (s < T - 1) reduce_steps(TERM_SQ, t, st, P0, next, bstride, C0HW, 1, B, (double)(B * C0HW), t->d_step + s % M, 1);
+        if (s < T - 1 && h_step_loss) TCHK(flush(h_step_loss, t->d_step, s, 1));
+    }
+    TCHK(hipGetLastError());
+    t->state_batch = B;
+    t->state_slot = T & 1;
+    if (h_step_loss || h_layer_err) TCHK(hipStreamSynchronize(st));
+    return EIGEN_OK;
+}
+
+// EIGEN_OBJ_FLOW through an entry that has nowhere to take the flow settings from
+int refuse_flow_objective() { return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs the settings eigen_trainer_loss_grad_flow takes"); }
+
 }  // namespace
 
 extern "C" {
@@ -789,59 +920,11 @@ int eigen_trainer_loss_grad_flow_pair(eigen_trainer* t, const uint8_t* d_frames,
                                       double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride,
                                       const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double* h_terms, int32_t pairing, void* stream)
 {
-    int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, t ? t->cfg.max_steps : 0);
-    if (rc) return rc;
-    if (pairing != EIGEN_FLOW_PAIR_FRAME && pairing != EIGEN_FLOW_PAIR_PREDICTION)
-        return tfail(EIGEN_ERR_INVALID, "pairing %d is neither EIGEN_FLOW_PAIR_FRAME nor EIGEN_FLOW_PAIR_PREDICTION", pairing);
-    if (pairing != EIGEN_FLOW_PAIR_FRAME && objective != EIGEN_OBJ_FLOW) return tfail(EIGEN_ERR_INVALID, "EIGEN_FLOW_PAIR_PREDICTION goes with EIGEN_OBJ_FLOW only");
-    const int T = n_steps, B = batch;
-    const long long C0HW = t->ly[0].CHW();
-    FrameGrad fg;
-    if (d_frame_grad) {
-        fg.p = d_frame_grad; fg.bstride = g_bstride; fg.tstride = g_tstride;
-        if (g_tstride != 0 && g_tstride < C0HW)
-            return tfail(EIGEN_ERR_INVALID, "g_tstride %lld is neither 0 (tied) nor at least a frame (%lld floats)", (long long)g_tstride, C0HW);
-        const long long extent = g_tstride == 0 ? C0HW : (long long)(T - 1) * g_tstride + C0HW;
-        if (g_bstride < extent) return tfail(EIGEN_ERR_INVALID, "g_bstride %lld is smaller than one sample's gradient (%lld floats)", (long long)g_bstride, extent);
-    }
-    Objective o;
-    const bool by_flow = objective == EIGEN_OBJ_FLOW;
-    if (!by_flow && (flow || d_dir || d_mask)) return tfail(EIGEN_ERR_INVALID, "flow settings, direction and mask go with EIGEN_OBJ_FLOW only");
-    // the step and layer weights follow the same rules under every objective
-    rc = make_objective(t, by_flow ? (int32_t)EIGEN_OBJ_MSE : objective, h_layer_w, h_step_w, T, B, o);
-    if (rc) return rc;
-    if (by_flow) {
-        rc = check_flow(t, flow, d_dir, d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
-        if (rc) return rc;
-        o.flow.pair_pred = pairing == EIGEN_FLOW_PAIR_PREDICTION;
-        // a frame is no reference under the prediction pairing: there is nothing the flag could move
-        if (o.flow.pair_pred && o.flow.moving) return tfail(EIGEN_ERR_INVALID, "EIGEN_FLOW_PAIR_PREDICTION does not take EIGEN_FLOW_MOVING_REFERENCE");
-        o.by_flow = true;
-        o.h_terms = h_terms;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    rc = start_state(t, st, B, reset);
-    if (rc) return rc;
-    // forward with tape: step s reads state slot s, writes state slot s + 1 and tape slot s
-    for (int s = 0; s < T; ++s)
-        forward_step(t, st, B, s, s + 1, s, s < n_fed ? d_frames + s * C0HW : nullptr, bstride, requant, d_pred ? d_pred + s * C0HW : nullptr, T * C0HW);
-    const bool want_table = T >= 2 && (h_layer_err || (o.by_error && h_loss));
-    rc = reduce_losses(t, st, o, d_frames, bstride, want_table);
-    if (rc) return rc;
-    // backward through time, from zero carries
-    for (int l = 0; l < t->L; ++l)
-        for (float* a : {t->ly[l].dPn, t->ly[l].dhc, t->ly[l].dc}) TCHK(hipMemsetAsync(a, 0, B * t->ly[l].CHW() * 4, st));
-    // the tied frame gradient starts from zero; only the C0 H W floats of every sample are touched, whatever g_bstride is
-    for (int b = 0; fg.p && fg.tstride == 0 && b < B; ++b) TCHK(hipMemsetAsync(fg.p + b * fg.bstride, 0, C0HW * 4, st));
-    for (int s = T - 1; s >= 0; --s) {
-        backward_step(t, st, o, s, d_frames, bstride, fg);
-        if (fg.p) frame_grad_step(t, st, o, s, n_fed, d_frames, bstride, fg);
-    }
-    weight_gradients(t, st, T, B);
-    TCHK(hipGetLastError());
-    t->state_batch = B;
-    t->state_slot = T;
-    return read_loss(t, st, o, want_table, h_loss, h_layer_err);
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing;
+    return loss_grad_call(t, c);
 }
 
 int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
@@ -849,22 +932,26 @@ int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int6
                                  double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow,
                                  const float* d_dir, const uint8_t* d_mask, double* h_terms, void* stream)
 {
-    return eigen_trainer_loss_grad_flow_pair(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_w, objective, h_layer_w, h_loss, h_layer_err, d_pred,
-                                             d_frame_grad, g_bstride, g_tstride, flow, d_dir, d_mask, h_terms, EIGEN_FLOW_PAIR_FRAME, stream);
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms;
+    return loss_grad_call(t, c);
 }
 
 int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
                                    int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
                                    double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, void* stream)
 {
-    // it has nowhere to take the flow settings from: the objective is refused here, ahead of every other check of the call
-    if (objective == EIGEN_OBJ_FLOW) return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs the settings eigen_trainer_loss_grad_flow takes");
-    return eigen_trainer_loss_grad_flow(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_w, objective, h_layer_w, h_loss, h_layer_err, d_pred,
-                                        d_frame_grad, g_bstride, g_tstride, nullptr, nullptr, nullptr, nullptr, stream);
+    if (objective == EIGEN_OBJ_FLOW) return refuse_flow_objective();
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    return loss_grad_call(t, c);
 }
 
-// the three stage-alone entries: d_refg == nullptr is eigen_trainer_flow_term; d_fref, a float reference in place of d_ref, is
-// eigen_trainer_flow_term_pair
+// the three stage-alone entries share this: the checks, one FlowTerm whose seed and reference gradient are stored, not added, and the
+// value read back.  eigen_trainer_flow_term wants no reference gradient; eigen_trainer_flow_term_pair gives a float reference, d_fref
 static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
                           int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr)
@@ -880,8 +967,11 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
     const int rc = check_flow(t, flow, d_dir, d_mask, 0, f);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    flow_stage(t, st, batch, d_pred, p_bstride, d_ref, r_bstride, f, scale / (double)(batch * f.n_mask), t->d_spart, h_value ? t->d_step : nullptr, d_flow, d_seed,
-               s_bstride, 0, d_refg, rg_bstride, 0, d_fref);
+    FlowTerm m;
+    m.pred = d_pred; m.p_bstride = p_bstride; m.ref = d_ref; m.fref = d_fref; m.r_bstride = r_bstride;
+    m.kappa = scale / (double)(batch * f.n_mask); m.part = t->d_spart; m.d_value = h_value ? t->d_step : nullptr;
+    m.d_flow = d_flow; m.d_seed = d_seed; m.s_bstride = s_bstride; m.d_refg = d_refg; m.rg_bstride = rg_bstride;
+    flow_stage(t, st, batch, f, m);
     TCHK(hipGetLastError());
     if (h_value) {
         TCHK(hipMemcpyAsync(h_value, t->d_step, 8, hipMemcpyDeviceToHost, st));
@@ -918,8 +1008,10 @@ int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64
                                 int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
                                 double* h_layer_err, float* d_pred, void* stream)
 {
-    return eigen_trainer_loss_grad_frames(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_w, objective, h_layer_w, h_loss, h_layer_err, d_pred,
-                                          nullptr, 0, 0, stream);
+    if (objective == EIGEN_OBJ_FLOW) return refuse_flow_objective();
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    return loss_grad_call(t, c);
 }
 
 int eigen_trainer_still_step(eigen_trainer* t, uint8_t* d_images, const float* d_grad, int64_t g_bstride, const uint8_t* d_mask, double step_bytes,
@@ -944,57 +1036,27 @@ int eigen_trainer_still_step(eigen_trainer* t, uint8_t* d_images, const float* d
 int eigen_trainer_loss_grad_ext(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
                                 int32_t requant, int32_t reset, const double* h_step_w, double* h_loss, float* d_pred, void* stream)
 {
-    return eigen_trainer_loss_grad_obj(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_w, EIGEN_OBJ_MSE, nullptr, h_loss, nullptr, d_pred, stream);
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w;
+    return loss_grad_call(t, c);
 }
 
 int eigen_trainer_loss_grad(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
                             int32_t reset, double* h_loss, float* d_pred, void* stream)
 {
-    return eigen_trainer_loss_grad_ext(t, d_frames, bstride, batch, n_steps, n_steps, 0, reset, nullptr, h_loss, d_pred, stream);
+    return loss_grad_call(t, LossGradCall{d_frames, bstride, batch, n_steps, n_steps, 0, reset, h_loss, d_pred, stream});
 }
 
 int eigen_trainer_evaluate_err(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
                                int32_t requant, int32_t reset, double* h_step_loss, double* h_layer_err, float* d_pred, void* stream)
 {
-    int rc = check_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, -1);
-    if (rc) return rc;
-    const int T = n_steps, B = batch, M = t->cfg.max_steps, L = t->L;
-    const long long C0HW = t->ly[0].CHW();
-    hipStream_t st = (hipStream_t)stream;
-    rc = start_state(t, st, B, reset);
-    if (rc) return rc;
-    // state slots 0 and 1 in turn, tape slot 0; the loss of step s goes to d_step[s % max_steps], read back whenever that table is
-    // full.  Row r of the error table lives at d_err[r % max_steps]: its image-layer entry is reduced after step r, its upper entries
-    // (E_l of step r + 1) after step r + 1, and the rows are read back once the table's last row, or the call's, is complete --
-    // ahead of the image-layer entry that reuses row 0.
-    auto flush = [&](double* host, const double* dev, int r, int width) {  // rows r - r % M .. r, once r is the table's last row or the call's
-        if (r % M != M - 1 && r != T - 2) return hipSuccess;
-        return hipMemcpyAsync(host + (long long)(r - r % M) * width, dev, (long long)(r % M + 1) * width * 8, hipMemcpyDeviceToHost, st);
-    };
-    for (int s = 0; s < T; ++s) {
-        const int in = s & 1, out = in ^ 1;
-        forward_step(t, st, B, in, out, 0, s < n_fed ? d_frames + s * C0HW : nullptr, bstride, requant, d_pred ? d_pred + s * C0HW : nullptr, T * C0HW);
-        const float* P0 = t->ly[0].P_at(out, B);
-        const uint8_t* next = d_frames + (s + 1) * C0HW;  // the frame P0 predicts (read only while s < T - 1)
-        if (h_layer_err && s >= 1) {
-            upper_errors(t, st, 0, 1, B, t->d_err + (long long)((s - 1) % M) * L);
-            TCHK(flush(h_layer_err, t->d_err, s - 1, L));
-        }
-        if (h_layer_err && s < T - 1) reduce_steps(TERM_ABS, t, st, P0, next, bstride, C0HW, 1, B, (double)(B * 2 * C0HW), t->d_err + (long long)(s % M) * L, L);
-        if (s < T - 1) reduce_steps(TERM_SQ, t, st, P0, next, bstride, C0HW, 1, B, (double)(B * C0HW), t->d_step + s % M, 1);
-        if (s < T - 1 && h_step_loss) TCHK(flush(h_step_loss, t->d_step, s, 1));
-    }
-    TCHK(hipGetLastError());
-    t->state_batch = B;
-    t->state_slot = T & 1;
-    if (h_step_loss || h_layer_err) TCHK(hipStreamSynchronize(st));
-    return EIGEN_OK;
+    return evaluate_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_loss, h_layer_err, d_pred, stream);
 }
 
 int eigen_trainer_evaluate(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
                            int32_t requant, int32_t reset, double* h_step_loss, float* d_pred, void* stream)
 {
-    return eigen_trainer_evaluate_err(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_loss, nullptr, d_pred, stream);
+    return evaluate_call(t, d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_step_loss, nullptr, d_pred, stream);
 }
 
 // Adam moments, step count and the kept sequence state, out.  h_m / h_v: host tables in eigen_set_prednet_weights order (both or

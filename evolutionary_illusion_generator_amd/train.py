@@ -26,31 +26,37 @@ class TrainerConfig(ctypes.Structure):
                 ("channels", ctypes.c_int32 * engine.MAX_LAYERS), ("max_batch", ctypes.c_int32), ("max_steps", ctypes.c_int32)]
 
 
+# the argument groups of include/eigen_engine.h's trainer entries; every entry ends with its stream
+_I32, _I64, _P, _PD = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
+_CALL = [_P, _P, _I64, _I32, _I32, _I32, _I32, _I32]   # t, d_frames, bstride, batch, n_steps, n_fed, requant, reset
+_OBJ = [_P, _I32, _P, _PD, _P, _P]                     # h_step_w, objective, h_layer_w, h_loss, h_layer_err, d_pred
+_FRAMEGRAD = [_P, _I64, _I64]                          # d_frame_grad, g_bstride, g_tstride
+_FLOW = [_P, _P, _P, _P]                               # flow, d_dir, d_mask, h_terms
+# t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride
+_TERM = [_P, _P, _I64, _P, _I64, _I32, _P, _P, _P, ctypes.c_double, _P, _P, _P, _I64]
+# The narrowest entry that takes a training request: the entry and the argument groups that follow _CALL and _OBJ.  Keys: (False, frame
+# gradient wanted) for the mse and error objectives, (True, pairing) for the flow objective, whose entries take the frame gradient anyway.
+_ENTRIES = {(False, False): ("eigen_trainer_loss_grad_obj", ()), (False, True): ("eigen_trainer_loss_grad_frames", ("frame_grad",)),
+            (True, "frame"): ("eigen_trainer_loss_grad_flow", ("frame_grad", "flow")),
+            (True, "prediction"): ("eigen_trainer_loss_grad_flow_pair", ("frame_grad", "flow", "pairing"))}
+
+
 def _bind(lib):
     if getattr(lib, "_trainer_bound", False):
         return
-    lib.eigen_trainer_loss_grad.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p]
-    lib.eigen_trainer_loss_grad_ext.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
-                                                ctypes.c_void_p]
-    lib.eigen_trainer_evaluate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.eigen_trainer_loss_grad_obj.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                                ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.eigen_trainer_loss_grad_frames.argtypes = lib.eigen_trainer_loss_grad_obj.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
-    lib.eigen_trainer_loss_grad_flow.argtypes = lib.eigen_trainer_loss_grad_frames.argtypes[:-1] + [ctypes.c_void_p] * 5
-    lib.eigen_trainer_flow_term.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                            ctypes.c_void_p]
-    lib.eigen_trainer_flow_term_ref.argtypes = lib.eigen_trainer_flow_term.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-    lib.eigen_trainer_loss_grad_flow_pair.argtypes = lib.eigen_trainer_loss_grad_flow.argtypes[:-1] + [ctypes.c_int32, ctypes.c_void_p]
-    lib.eigen_trainer_flow_term_pair.argtypes = list(lib.eigen_trainer_flow_term_ref.argtypes)
+    lib.eigen_trainer_loss_grad.argtypes = [_P, _P, _I64, _I32, _I32, _I32, _PD, _P, _P]
+    lib.eigen_trainer_loss_grad_ext.argtypes = _CALL + [_P, _PD, _P, _P]
+    lib.eigen_trainer_evaluate.argtypes = _CALL + [_P, _P, _P]
+    lib.eigen_trainer_evaluate_err.argtypes = _CALL + [_P, _P, _P, _P]
+    lib.eigen_trainer_loss_grad_obj.argtypes = _CALL + _OBJ + [_P]
+    lib.eigen_trainer_loss_grad_frames.argtypes = _CALL + _OBJ + _FRAMEGRAD + [_P]
+    lib.eigen_trainer_loss_grad_flow.argtypes = _CALL + _OBJ + _FRAMEGRAD + _FLOW + [_P]
+    lib.eigen_trainer_loss_grad_flow_pair.argtypes = _CALL + _OBJ + _FRAMEGRAD + _FLOW + [_I32, _P]
+    lib.eigen_trainer_flow_term.argtypes = _TERM + [_P]
+    lib.eigen_trainer_flow_term_ref.argtypes = _TERM + [_P, _I64, _P]
+    lib.eigen_trainer_flow_term_pair.argtypes = _TERM + [_P, _I64, _P]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
-    lib.eigen_trainer_evaluate_err.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int32]
     lib.eigen_trainer_set_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
@@ -442,20 +448,16 @@ class PredNetTrainer:
             d_grad = torch.empty((n,) + (() if frame_grads == "tied" else (T,)) + img, dtype=torch.float32, device=d.device)
             per = int(np.prod(img))
             g_b, g_t = (per, 0) if frame_grads == "tied" else (T * per, per)
+        tails = {"frame_grad": [_ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t)]}
         if by_flow:
             terms = np.zeros(max(T - 1, 1), np.float64)
             cfg = flow.settings()
-            if flow.pairing == "frame":
-                _check(self.lib.eigen_trainer_loss_grad_flow(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask),
-                                                             _ptr(terms), _stream_arg(stream)))
-            else:
-                _check(self.lib.eigen_trainer_loss_grad_flow_pair(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), ctypes.byref(cfg), _ptr(d_dir),
-                                                                  _ptr(d_mask), _ptr(terms), ctypes.c_int32(FLOW_PAIRINGS[flow.pairing]), _stream_arg(stream)))
+            tails["flow"] = [ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask), _ptr(terms)]
+            tails["pairing"] = [ctypes.c_int32(FLOW_PAIRINGS[flow.pairing])]
+        entry, groups = _ENTRIES[by_flow, flow.pairing if by_flow else frame_grads is not None]
+        _check(getattr(self.lib, entry)(*args, *[a for g in groups for a in tails[g]], _stream_arg(stream)))
+        if by_flow:
             self.last_flow_terms = terms[:T - 1]
-        elif frame_grads is None:
-            _check(self.lib.eigen_trainer_loss_grad_obj(*args, _stream_arg(stream)))
-        else:
-            _check(self.lib.eigen_trainer_loss_grad_frames(*args, _ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t), _stream_arg(stream)))
         if table is not None:
             table = table[:T - 1]
         value = combine_terms(table, lam, w_arr if w_arr is not None and w_arr.size else None) if by_error else loss.value
@@ -511,31 +513,7 @@ class PredNetTrainer:
         (eigen_trainer_flow_term_ref) appends scale * d value / d ref, by the reference as floats (byte / 255), float32
         [n, C, H, W]: what a training call adds to the frame gradient under reference="moving".  The FlowObjective's own `reference`
         plays no part here."""
-        torch = self._torch
-        if not isinstance(flow, FlowObjective):
-            raise ValueError("flow must be a FlowObjective, got %r" % (flow,))
-        if not np.isfinite(scale):
-            raise ValueError("scale must be finite, got %r" % (scale,))
-        shp = (self.channels[0], self.h, self.w)
-        dev = "cuda:%d" % self.device
-        p = (pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32))).to(dev).contiguous()
-        r = (ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref))).to(dev).contiguous()
-        if p.dtype != torch.float32 or r.dtype != torch.uint8 or p.dim() != 4 or tuple(p.shape[1:]) != shp or tuple(r.shape) != tuple(p.shape):
-            raise ValueError("pred must be float32 and ref uint8, both [n, %d, %d, %d]; got %s %s and %s %s" % (shp + (p.dtype, tuple(p.shape), r.dtype, tuple(r.shape))))
-        n, per = int(p.shape[0]), int(np.prod(shp))
-        d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w)
-        value = ctypes.c_double(0.0)
-        u = torch.empty((n, 2, self.h, self.w), dtype=torch.float64, device=dev)
-        seed = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
-        cfg = flow.settings(stage_alone=True)
-        args = [self._h, _ptr(p), ctypes.c_int64(per), _ptr(r), ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask),
-                ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(u), _ptr(seed), ctypes.c_int64(per)]
-        if not reference_grad:
-            _check(self.lib.eigen_trainer_flow_term(*args, None))
-            return value.value, u.cpu().numpy(), seed.cpu().numpy()
-        rg = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
-        _check(self.lib.eigen_trainer_flow_term_ref(*args, _ptr(rg), ctypes.c_int64(per), None))
-        return value.value, u.cpu().numpy(), seed.cpu().numpy(), rg.cpu().numpy()
+        return self._flow_stage(pred, ref, False, flow, scale, reference_grad)
 
     def flow_term_pair(self, pred, prev, flow, scale=1.0, reference_grad=False):
         """The flow stage alone on a pair of float images (eigen_trainer_flow_term_pair), with the kernels a training call runs under a
@@ -543,6 +521,11 @@ class PredNetTrainer:
         prediction); n <= batch.  -> (value, u, seed) as ``flow_term``; reference_grad=True appends scale * d value / d prev, float32
         [n, C, H, W]: what a training call adds to d loss / d P0_{s-1}.  The radius, eps, direction and mask of `flow` are used; its
         pairing and `reference` play no part here."""
+        return self._flow_stage(pred, prev, True, flow, scale, reference_grad)
+
+    def _flow_stage(self, pred, ref, float_ref, flow, scale, reference_grad):
+        """flow_term (float_ref False: a uint8 reference) and flow_term_pair (True: a float32 one): the upload, the checks, the buffers,
+        the one call and the result tuple"""
         torch = self._torch
         if not isinstance(flow, FlowObjective):
             raise ValueError("flow must be a FlowObjective, got %r" % (flow,))
@@ -550,10 +533,11 @@ class PredNetTrainer:
             raise ValueError("scale must be finite, got %r" % (scale,))
         shp = (self.channels[0], self.h, self.w)
         dev = "cuda:%d" % self.device
-        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))).to(dev).contiguous()
-        p, r = up(pred), up(prev)
-        if p.dtype != torch.float32 or r.dtype != torch.float32 or p.dim() != 4 or tuple(p.shape[1:]) != shp or tuple(r.shape) != tuple(p.shape):
-            raise ValueError("pred and prev must be float32, both [n, %d, %d, %d]; got %s %s and %s %s" % (shp + (p.dtype, tuple(p.shape), r.dtype, tuple(r.shape))))
+        up = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=dt))).to(dev).contiguous()
+        p, r = up(pred, np.float32), up(ref, np.float32 if float_ref else None)
+        if p.dtype != torch.float32 or r.dtype != (torch.float32 if float_ref else torch.uint8) or p.dim() != 4 or tuple(p.shape[1:]) != shp or tuple(r.shape) != tuple(p.shape):
+            raise ValueError(("pred and prev must be float32, both" if float_ref else "pred must be float32 and ref uint8, both") + " [n, %d, %d, %d]; got %s %s and %s %s"
+                             % (shp + (p.dtype, tuple(p.shape), r.dtype, tuple(r.shape))))
         n, per = int(p.shape[0]), int(np.prod(shp))
         d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w)
         value = ctypes.c_double(0.0)
@@ -561,9 +545,14 @@ class PredNetTrainer:
         seed = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
         rg = torch.empty((n,) + shp, dtype=torch.float32, device=dev) if reference_grad else None
         cfg = flow.settings(stage_alone=True)
-        _check(self.lib.eigen_trainer_flow_term_pair(self._h, _ptr(p), ctypes.c_int64(per), _ptr(r), ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg),
-                                                     _ptr(d_dir), _ptr(d_mask), ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(u), _ptr(seed),
-                                                     ctypes.c_int64(per), _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None))
+        args = [self._h, _ptr(p), ctypes.c_int64(per), _ptr(r), ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask),
+                ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(u), _ptr(seed), ctypes.c_int64(per)]
+        if float_ref:
+            _check(self.lib.eigen_trainer_flow_term_pair(*args, _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None))
+        elif reference_grad:
+            _check(self.lib.eigen_trainer_flow_term_ref(*args, _ptr(rg), ctypes.c_int64(per), None))
+        else:
+            _check(self.lib.eigen_trainer_flow_term(*args, None))
         out = (value.value, u.cpu().numpy(), seed.cpu().numpy())
         return out + (rg.cpu().numpy(),) if reference_grad else out
 
@@ -656,6 +645,30 @@ class PredNetTrainer:
         self.close()
 
 
+def _still_call(trainer, n_repeat, n_ext, iters, requant, objective, layer_weights, flow):
+    """What refine_stills and refine_genomes share.  Checks the objective and the lengths at once; -> weigh(step_weights), which settles the
+    step weights (``_still_weights``, checked then) and -> loss_of(img, frame_grads): the loss of the stills img uint8 [n, C, H, W] on the
+    device, repeated n_repeat + n_ext times with the first n_repeat fed, and its frame gradient as a device tensor (None if not asked)."""
+    T = int(n_repeat) + int(n_ext)
+    _check_flow(objective, flow)
+    if n_repeat < 1 or n_ext < 1 or iters < 0:
+        raise ValueError("n_repeat >= 1, n_ext >= 1 and iters >= 0 required")
+    if T > trainer.max_steps:
+        raise ValueError("n_repeat + n_ext = %d frames exceed the trainer's max_steps %d" % (T, trainer.max_steps))
+
+    def weigh(step_weights):
+        step_weights = _still_weights(step_weights, n_repeat, n_ext, flow)
+
+        def loss_of(img, frame_grads):
+            n, per = int(img.shape[0]), int(np.prod(img.shape[1:]))
+            d = img[:, None].expand(n, T, *img.shape[1:]).contiguous()
+            value, _, _, d_grad = trainer._loss_grad(d, n, T, n_repeat, ctypes.c_int64(T * per), True, False, None, requant, step_weights, objective,
+                                                     layer_weights, False, frame_grads, flow=flow)
+            return value, d_grad
+        return loss_of
+    return weigh
+
+
 def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, requant=True, objective="mse", layer_weights=None, step_weights=None,
                   mask=None, flow=None):
     """Gradient ascent on stills: raise how far PredNet's extended prediction leaves a still, the differentiable stand-in for the
@@ -684,15 +697,10 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
 
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images.  The calls
     OVERWRITE the trainer's weight gradients and its kept sequence state."""
-    T = int(n_repeat) + int(n_ext)
-    _check_flow(objective, flow)
-    if n_repeat < 1 or n_ext < 1 or iters < 0:
-        raise ValueError("n_repeat >= 1, n_ext >= 1 and iters >= 0 required")
-    if T > trainer.max_steps:
-        raise ValueError("n_repeat + n_ext = %d frames exceed the trainer's max_steps %d" % (T, trainer.max_steps))
+    weigh = _still_call(trainer, n_repeat, n_ext, iters, requant, objective, layer_weights, flow)
     if not (np.isfinite(step) and step > 0):
         raise ValueError("step must be finite and > 0, got %r" % (step,))
-    step_weights = _still_weights(step_weights, n_repeat, n_ext, flow)
+    loss_of = weigh(step_weights)
     torch = trainer._torch
     if isinstance(images, torch.Tensor):
         img = images.detach().to("cuda:%d" % trainer.device).clone()
@@ -709,18 +717,12 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
             raise ValueError("mask must be [%d, %d], got %s" % (trainer.h, trainer.w, m.shape))
         d_mask = torch.from_numpy(m).cuda(trainer.device)
 
-    def loss_of(frame_grads):
-        d = img[:, None].expand(n, T, *img.shape[1:]).contiguous()
-        value, _, _, d_grad = trainer._loss_grad(d, n, T, n_repeat, ctypes.c_int64(T * per), True, False, None, requant, step_weights, objective,
-                                                 layer_weights, False, frame_grads, flow=flow)
-        return value, d_grad
-
     history = np.zeros(iters + 1, np.float64)
     for i in range(iters):
-        history[i], d_grad = loss_of("tied")
+        history[i], d_grad = loss_of(img, "tied")
         _check(trainer.lib.eigen_trainer_still_step(trainer._h, _ptr(img), _ptr(d_grad), ctypes.c_int64(per), _ptr(d_mask), ctypes.c_double(float(step)),
                                                     ctypes.c_int32(n), None))
-    history[iters], _ = loss_of(None)
+    history[iters], _ = loss_of(img, None)
     return img.cpu().numpy(), history
 
 
@@ -815,12 +817,7 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     import copy
     from . import fitness
     from .genome import GenomeBatch, flatten_genome_map
-    T = int(n_repeat) + int(n_ext)
-    _check_flow(objective, flow)
-    if n_repeat < 1 or n_ext < 1 or iters < 0:
-        raise ValueError("n_repeat >= 1, n_ext >= 1 and iters >= 0 required")
-    if T > trainer.max_steps:
-        raise ValueError("n_repeat + n_ext = %d frames exceed the trainer's max_steps %d" % (T, trainer.max_steps))
+    weigh = _still_call(trainer, n_repeat, n_ext, iters, requant, objective, layer_weights, flow)
     genomes = list(genomes)
     n = len(genomes)
     if not 1 <= n <= trainer.batch:
@@ -831,13 +828,12 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     if not params or any(k not in PARAM_KINDS for k in params):
         raise ValueError("params must be a non-empty selection of %s, got %r" % (", ".join(PARAM_KINDS), params))
     limits = _genome_bounds(config, bounds)
-    step_weights = _still_weights(step_weights, n_repeat, n_ext, flow)
+    loss_of = weigh(step_weights)
     torch = trainer._torch
     C0, h, w = trainer.channels[0], trainer.h, trainer.w
     n_in = len(config.genome_config.input_keys)
     out = [copy.deepcopy(g) for g in genomes]
     maps = [flatten_genome_map(g, config, n_in) for g in out]   # values change below, the structure (and so the map) does not
-    per = C0 * h * w
     with torch.cuda.device(trainer.device):
         eng = engine.Engine(w, h, [C0], n, device=trainer.device)   # weight-free: it renders and differentiates the render
         try:
@@ -849,16 +845,10 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
                 eng.render_cppn(gb, img, bg=bg, gradient=1)
                 return gb
 
-            def loss_of(frame_grads):
-                d = img[:, None].expand(n, T, C0, h, w).contiguous()
-                value, _, _, d_grad = trainer._loss_grad(d, n, T, n_repeat, ctypes.c_int64(T * per), True, False, None, requant, step_weights, objective,
-                                                         layer_weights, False, frame_grads, flow=flow)
-                return value, d_grad
-
             history = np.zeros(iters + 1, np.float64)
             for i in range(iters):
                 gb = render()
-                history[i], d_grad = loss_of("tied")
+                history[i], d_grad = loss_of(img, "tied")
                 g_bias, g_resp, g_w = eng.cppn_param_grads(gb, d_grad, bg=bg, gradient=1)
                 for j, (g, m) in enumerate(zip(out, maps)):
                     n0, n1 = int(gb.node_off[j]), int(gb.node_off[j + 1])
@@ -868,7 +858,7 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
                                                                                                               len(m["node_key"]), len(m["edge_key"])))
                     genome_update(g, m, g_bias[n0:n1], g_resp[n0:n1], g_w[e0:e1], lr, params, limits)
             render()
-            history[iters], _ = loss_of(None)
+            history[iters], _ = loss_of(img, None)
             torch.cuda.synchronize(trainer.device)
             images = img.cpu().numpy()
         finally:

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from evolutionary_illusion_generator_amd import fitness, neat_lite as neat
+from examples.flow_args import add_flow_arguments, flow_of
 
 
 def main():
@@ -35,12 +36,11 @@ def main():
     ap.add_argument("--refine", type=int, default=0, help="refine the parameters of this many of the best genomes after every generation (0: off)")
     ap.add_argument("--refine_iters", type=int, default=5, help="ascent steps of train.refine_genomes per generation")
     ap.add_argument("--objective", default="mse", choices=["mse", "error", "flow"], help="what --refine climbs")
-    ap.add_argument("--flow-direction", default=None, choices=["tangent", "radial", "horizontal", "vertical"], help="objective flow: the field (default: the mean square)")
-    ap.add_argument("--flow-radius", type=int, default=7)
-    ap.add_argument("--flow-eps", type=float, default=1e-2)
-    ap.add_argument("--flow-reference", default="constant", choices=["constant", "moving"], help="objective flow: moving also follows how the term moves with the still as its reference frame")
-    ap.add_argument("--flow-pairing", default="frame", choices=["frame", "prediction"],
-                    help="objective flow: frame pairs the still with the extended predictions, prediction pairs consecutive predictions as the population fitness does")
+    add_flow_arguments(ap, direction=dict(choices=["tangent", "radial", "horizontal", "vertical"], help="objective flow: the field (default: the mean square)"),
+                       radius=dict(help=None), eps=dict(help=None),
+                       reference=dict(choices=["constant", "moving"], help="objective flow: moving also follows how the term moves with the still as its reference frame"),
+                       pairing=dict(choices=["frame", "prediction"],
+                                    help="objective flow: frame pairs the still with the extended predictions, prediction pairs consecutive predictions as the population fitness does"))
     a = ap.parse_args()
     w, h = {"small": (160, 120), "big": (640, 480)}.get(a.size) or (int(a.size), int(a.size))
     channels = [int(c) for c in a.channels.split(",")]
@@ -66,11 +66,7 @@ def main():
         best = sorted((g for _, g in genomes), key=lambda g: -g.fitness)[:a.refine]
         if not trainer:
             trainer.append(train.PredNetTrainer(a.model, channels, w, h, a.refine, 22))
-        flow = None
-        if a.objective == "flow":
-            inside = (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype("uint8")
-            flow = train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), inside,
-                                   reference=a.flow_reference)
+        flow = flow_of(a, w, h, (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype("uint8"))
         refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters, objective=a.objective, flow=flow)
         for g, r in zip(best, refined):
             for k, n in r.nodes.items():

@@ -23,6 +23,7 @@ import torch
 
 from evolutionary_illusion_generator_amd import fitness, synth, train
 from evolutionary_illusion_generator_amd.engine import PAIR_POPULATION
+from examples.flow_args import add_flow_arguments, flow_of
 
 
 def score(images, model, structure, w, h, channels):
@@ -30,14 +31,6 @@ def score(images, model, structure, w, h, channels):
     eng = fitness.get_engine(model, w, h, channels, max_batch=len(images))
     fit, vecs = eng.eval_images(torch.from_numpy(np.ascontiguousarray(images)).cuda(), len(images), structure, pairing=PAIR_POPULATION)
     return fit, np.array([len(v) for v in vecs])
-
-
-def flow_of(a, w, h, mask=None):
-    """the FlowObjective of the command line (None under another objective); the term counts the pixels of `mask`"""
-    if a.objective != "flow":
-        return None
-    return train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask,
-                           reference=a.flow_reference)
 
 
 def main():
@@ -54,14 +47,7 @@ def main():
     ap.add_argument("--lr", type=float, default=0.02, help="largest move of a parameter per iteration")
     ap.add_argument("--params", default="weight,bias,response", help="which kinds of parameters move")
     ap.add_argument("--objective", default="mse", choices=["mse", "error", "flow"])
-    ap.add_argument("--flow-direction", default=None, choices=list(train.FLOW_DIRECTIONS), help="objective flow: climb the displacement along this field (default: its mean square)")
-    ap.add_argument("--flow-radius", type=int, default=7, help="objective flow: the window is 2 R + 1 pixels wide")
-    ap.add_argument("--flow-eps", type=float, default=1e-2, help="objective flow: the regulariser of the 2x2 systems")
-    ap.add_argument("--flow-reference", default="constant", choices=list(train.FLOW_REFERENCES),
-                    help="objective flow: moving also follows how the term moves with the still as its reference frame (constant: the input path alone)")
-    ap.add_argument("--flow-pairing", default="frame", choices=list(train.FLOW_PAIRINGS),
-                    help="objective flow: frame pairs the still with the extended predictions (the single-image fitness path), prediction pairs consecutive "
-                         "predictions, as the population fitness printed here does; prediction takes --flow-reference constant only")
+    add_flow_arguments(ap)
     ap.add_argument("--n_repeat", type=int, default=20)
     ap.add_argument("--n_ext", type=int, default=2)
     ap.add_argument("--output_dir", "-o", default=None, help="write before_<i>.png / after_<i>.png and the artefacts of the best refined genome here")

@@ -29,6 +29,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from examples.flow_args import add_flow_arguments  # noqa: E402
+
 W, H, CH, B, T = 160, 120, [3, 48, 96, 192], 16, 10
 GATES = ("i", "f", "c", "o")
 
@@ -61,12 +63,9 @@ FLOW_WEIGHTS = [0.0] * (T - 3) + [1.0, 1.0]   # two weighted terms, as a refinem
 
 
 def objective_args(name, reference="constant", pairing="frame"):
-    if name == "flow" and pairing == "prediction":
-        from evolutionary_illusion_generator_amd.train import PredictionFlow
-        return dict(objective="flow", flow=PredictionFlow(radius=7, eps=1e-2), step_weights=FLOW_WEIGHTS)
     if name == "flow":
-        from evolutionary_illusion_generator_amd.train import FlowObjective
-        return dict(objective="flow", flow=FlowObjective(radius=7, eps=1e-2, reference=reference), step_weights=FLOW_WEIGHTS)
+        from evolutionary_illusion_generator_amd.train import make_flow
+        return dict(objective="flow", flow=make_flow(pairing, radius=7, eps=1e-2, reference=reference), step_weights=FLOW_WEIGHTS)
     return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
 
 
@@ -247,9 +246,8 @@ def main():
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
     ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall", "flow"], help="the trainer side's objective")
     ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
-    ap.add_argument("--flow-reference", default="constant", choices=["constant", "moving"], help="the flow objective's reference frame: a constant of the graph, or part of it")
-    ap.add_argument("--flow-pairing", default="frame", choices=["frame", "prediction"],
-                    help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)")
+    add_flow_arguments(ap, ("reference", "pairing"), reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
+                       pairing=dict(help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)"))
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))

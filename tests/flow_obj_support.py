@@ -1,6 +1,7 @@
 """Shared by tests/test_flow_obj_host.py and tests/test_gpu_flow_obj.py ("The flow objective"):
-(a) `flow_ref`, a numpy float64 restatement of the flow stage (csrc/flow_obj_kernels.h), operation by operation in the order the
-    kernels use, window sums as loops over offsets that add shifted arrays;
+(a) `flow_stage_ref`, the numpy float64 restatement of the flow stage with its seed and its reference gradient (csrc/flow_obj_kernels.h,
+    flow_ref_kernels.h, flow_pair_kernels.h), operation by operation in the order the kernels use, window sums as loops over offsets that add
+    shifted arrays, and `flow_ref`, its adapter for a byte reference;
 (b) `run_flow`, the float64 torch-CPU autograd statement of PredNet training with the predictions in the graph and the flow term written
     in torch ops on them (the operations of oracle/prednet_train_ref.py `run`, in its order, as tests/frame_grad_support.py `run_frames`);
 (c) the case lists;
@@ -49,22 +50,50 @@ def window_sum(a, r):
     return np.swapaxes(_sum_last(np.swapaxes(_sum_last(a, r), -1, -2), r), -1, -2)
 
 
-FlowRef = namedtuple("FlowRef", "value u seed mv bound seed64")
+def _fold_last(g):
+    """[..., n + 2] padded positions -1 .. n -> [..., n]: the two ends are added onto the border, ascending, each sum from its first term"""
+    n = g.shape[-1] - 2
+    out = g[..., 1:n + 1].copy()
+    out[..., 0] = g[..., 0] + out[..., 0]
+    out[..., n - 1] = out[..., n - 1] + g[..., n + 1]
+    return out
 
 
-def flow_ref(pred, ref, r, eps, direction=None, mask=None, scale=1.0):
-    """pred float32 [B, C, H, W], ref uint8 [B, C, H, W]; direction float32 [2, H, W] or None; mask [H, W] or None.
-    -> value (exactly summed, then divided), u float64 [B, 2, H, W], seed float32 [B, C, H, W], mv = m v, the bound of a
-    double-precision sum of the N = B H W summands in any order, N 2^-53 sum |m v| / (B N_m), and the seed ahead of its rounding to float."""
+def scharr_adjoint(rx, ry):
+    """S^T(rx, ry), [B, H, W] -> [B, H, W]: the gather over the padded positions with r zero outside the image, then the padding ring
+    folded onto the border: along x first (per padded row), then along y (the order csrc/flow_ref_kernels.h states)"""
+    B, H, W = rx.shape
+    # padded position (Y, X) is index (Y + 1, X + 1) of G; r(Y + j, X + i) is index (Y + j + 2, X + i + 2) of the twice-padded r
+    px, py = np.pad(rx, ((0, 0), (2, 2), (2, 2))), np.pad(ry, ((0, 0), (2, 2), (2, 2)))
+    RX = lambda j, i: px[:, 1 + j:1 + j + H + 2, 1 + i:1 + i + W + 2]
+    RY = lambda j, i: py[:, 1 + j:1 + j + H + 2, 1 + i:1 + i + W + 2]
+    gx = ((3.0 * (RX(-1, -1) - RX(-1, 1)) + 10.0 * (RX(0, -1) - RX(0, 1))) + 3.0 * (RX(1, -1) - RX(1, 1))) / 32.0
+    gy = ((3.0 * (RY(-1, -1) - RY(1, -1)) + 10.0 * (RY(-1, 0) - RY(1, 0))) + 3.0 * (RY(-1, 1) - RY(1, 1))) / 32.0
+    G = gx + gy
+    rows = _fold_last(G)                                                  # [B, H + 2, W]
+    return np.swapaxes(_fold_last(np.swapaxes(rows, -1, -2)), -1, -2)     # [B, H, W]
+
+
+StageRef = namedtuple("StageRef", "value u seed mv bound seed64 grad grad64")
+
+
+def flow_stage_ref(pred, ref64, r, eps, direction=None, mask=None, scale=1.0):
+    """The flow stage of one prediction / reference pair, the ONE statement behind `flow_ref`, `flow_ref_support.flow_ref_grad` and
+    `flow_pair_support.pair_ref`: pred float32 [B, C, H, W]; ref64 float64 [B, C, H, W], the reference image as the prep kernel widens
+    it; direction float32 [2, H, W] or None; mask [H, W] or None.  -> value (exactly summed, then divided), u float64 [B, 2, H, W],
+    seed = scale * d value / d pred and grad = scale * d value / d reference as float32 [B, C, H, W], each also ahead of its rounding
+    to float (seed64, grad64), mv = m v, and the bound of a double-precision sum of the N = B H W summands in any order,
+    N 2^-53 sum |m v| / (B N_m)."""
     pred = np.asarray(pred, np.float32)
     B, C, H, W = pred.shape
-    x = (np.asarray(ref, np.uint8).astype(np.float32) / np.float32(255.0)).astype(np.float64)
-    I0, I1 = _gray(x), _gray(pred.astype(np.float64))
+    # tflow_prep_kernel / tflow_pair_prep_kernel
+    I0, I1 = _gray(ref64), _gray(pred.astype(np.float64))
     It = I1 - I0
     ap = np.pad(I0, ((0, 0), (1, 1), (1, 1)), mode="edge")
     a = lambda dy, dx: ap[:, 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
     Ix = ((3.0 * (a(-1, 1) - a(-1, -1)) + 10.0 * (a(0, 1) - a(0, -1))) + 3.0 * (a(1, 1) - a(1, -1))) / 32.0
     Iy = ((3.0 * (a(1, -1) - a(-1, -1)) + 10.0 * (a(1, 0) - a(-1, 0))) + 3.0 * (a(1, 1) - a(-1, 1))) / 32.0
+    # tflow_solve_kernel
     Gxx, Gxy, Gyy = window_sum(Ix * Ix, r), window_sum(Ix * Iy, r), window_sum(Iy * Iy, r)
     bx, by = window_sum(Ix * It, r), window_sum(Iy * It, r)
     aa, cc, bb = Gxx + eps, Gyy + eps, Gxy
@@ -82,16 +111,38 @@ def flow_ref(pred, ref, r, eps, direction=None, mask=None, scale=1.0):
     mv = np.where(m, v, 0.0)
     qx = np.where(m, (cc * gx - bb * gy) / det, 0.0)
     qy = np.where(m, (aa * gy - bb * gx) / det, 0.0)
+    kappa = float(scale) / float(B * n_m)
+    k = [1.0] if C == 1 else [0.299, 0.587, 0.114]
+    # tflow_seed_kernel
     Qx, Qy = window_sum(qx, r), window_sum(qy, r)
     t = Ix * Qx + Iy * Qy
-    kappa = float(scale) / float(B * n_m)
     s = -(t * kappa)
-    k = [1.0] if C == 1 else [0.299, 0.587, 0.114]
     seed64 = np.stack([kc * s for kc in k], 1)
-    seed = seed64.astype(np.float32)
+    # tflow_ref_sums_kernel
+    Mxx, Mxy, Myy = window_sum(2.0 * (qx * ux), r), window_sum(qx * uy + qy * ux, r), window_sum(2.0 * (qy * uy), r)
+    rx = -(((Qx * It + Mxx * Ix) + Mxy * Iy) * kappa)
+    ry = -(((Qy * It + Mxy * Ix) + Myy * Iy) * kappa)
+    e = t * kappa
+    # tflow_ref_fold_kernel
+    dI0 = e + scharr_adjoint(rx, ry)
+    grad64 = np.stack([kc * dI0 for kc in k], 1)
     value = math.fsum(mv.ravel().tolist()) / float(B * n_m)
     bound = mv.size * 2.0 ** -53 * math.fsum(np.abs(mv).ravel().tolist()) / float(B * n_m)
-    return FlowRef(value, np.stack([ux, uy], 1), seed, mv, bound, seed64)
+    return StageRef(value, np.stack([ux, uy], 1), seed64.astype(np.float32), mv, bound, seed64, grad64.astype(np.float32), grad64)
+
+
+def byte_reference(ref):
+    """uint8 -> the float64 image the byte prep kernel forms: (float)byte / 255.0f, widened"""
+    return (np.asarray(ref, np.uint8).astype(np.float32) / np.float32(255.0)).astype(np.float64)
+
+
+FlowRef = namedtuple("FlowRef", "value u seed mv bound seed64")
+
+
+def flow_ref(pred, ref, r, eps, direction=None, mask=None, scale=1.0):
+    """pred float32 [B, C, H, W], ref uint8 [B, C, H, W]; the settings of `flow_stage_ref`.  -> its value, u, seed, mv, bound and seed64."""
+    s = flow_stage_ref(pred, byte_reference(ref), r, eps, direction, mask, scale)
+    return FlowRef(s.value, s.u, s.seed, s.mv, s.bound, s.seed64)
 
 
 # ---- (b) the autograd statement

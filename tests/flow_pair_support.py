@@ -1,13 +1,12 @@
 """Shared by tests/test_flow_pair_host.py and tests/test_gpu_flow_pair.py ("The prediction pairing"):
-(a) `pair_ref`, the numpy float64 restatement of the flow stage on a pair of FLOAT images (csrc/flow_pair_kernels.h in front of the
-    kernels of csrc/flow_obj_kernels.h and csrc/flow_ref_kernels.h), operation by operation in the order the kernels use;
+(a) `pair_ref`, tests/flow_obj_support.py `flow_stage_ref` on a pair of FLOAT images (csrc/flow_pair_kernels.h in front of the
+    kernels of csrc/flow_obj_kernels.h and csrc/flow_ref_kernels.h);
 (b) `run_pair`, the float64 torch-CPU autograd statement: tests/flow_obj_support.py `run_flow` with a stateful `term` that remembers
     the previous P0 IN THE GRAPH and starts from the detached start-state P;
 (c) the case lists and the refinement loop on the float64 reference alone;
 (d) the name of the kernel of the new header.
 It imports tests/flow_obj_support.py and tests/flow_ref_support.py and changes neither."""
 import functools
-import math
 from collections import namedtuple
 
 import numpy as np
@@ -15,7 +14,6 @@ import torch
 
 from tests import flow_obj_support as fs
 from tests import flow_ref_support as rs
-from tests.flow_obj_support import _gray, window_sum
 from tests.train_support import _fed_from, _random_weights
 
 FLOW_PAIR_KERNELS = ["tflow_pair_prep_kernel"]
@@ -32,51 +30,11 @@ def pair_ref(pred, prev, r, eps, direction=None, mask=None, scale=1.0):
     any order, N 2^-53 sum |m v| / (B N_m)."""
     pred, prev = np.asarray(pred, np.float32), np.asarray(prev, np.float32)
     assert prev.dtype == np.float32 and prev.shape == pred.shape
-    B, C, H, W = pred.shape
-    # tflow_pair_prep_kernel
-    I0, I1 = _gray(prev.astype(np.float64)), _gray(pred.astype(np.float64))
-    It = I1 - I0
-    ap = np.pad(I0, ((0, 0), (1, 1), (1, 1)), mode="edge")
-    a = lambda dy, dx: ap[:, 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
-    Ix = ((3.0 * (a(-1, 1) - a(-1, -1)) + 10.0 * (a(0, 1) - a(0, -1))) + 3.0 * (a(1, 1) - a(1, -1))) / 32.0
-    Iy = ((3.0 * (a(1, -1) - a(-1, -1)) + 10.0 * (a(1, 0) - a(-1, 0))) + 3.0 * (a(1, 1) - a(-1, 1))) / 32.0
-    # tflow_solve_kernel
-    Gxx, Gxy, Gyy = window_sum(Ix * Ix, r), window_sum(Ix * Iy, r), window_sum(Iy * Iy, r)
-    bx, by = window_sum(Ix * It, r), window_sum(Iy * It, r)
-    aa, cc, bb = Gxx + eps, Gyy + eps, Gxy
-    det = aa * cc - bb * bb
-    ux, uy = -((cc * bx - bb * by) / det), -((aa * by - bb * bx) / det)
-    if direction is None:
-        gx, gy = 2.0 * ux, 2.0 * uy
-        v = ux * ux + uy * uy
-    else:
-        d = np.asarray(direction, np.float32).astype(np.float64)
-        gx, gy = np.broadcast_to(d[0], ux.shape), np.broadcast_to(d[1], ux.shape)
-        v = gx * ux + gy * uy
-    m = np.ones((H, W), bool) if mask is None else np.asarray(mask) != 0
-    n_m = int(m.sum())
-    mv = np.where(m, v, 0.0)
-    qx = np.where(m, (cc * gx - bb * gy) / det, 0.0)
-    qy = np.where(m, (aa * gy - bb * gx) / det, 0.0)
-    kappa = float(scale) / float(B * n_m)
-    k = [1.0] if C == 1 else [0.299, 0.587, 0.114]
-    # tflow_seed_kernel
-    Qx, Qy = window_sum(qx, r), window_sum(qy, r)
-    s = -((Ix * Qx + Iy * Qy) * kappa)
-    seed = np.stack([kc * s for kc in k], 1).astype(np.float32)
-    # tflow_ref_sums_kernel, tflow_ref_fold_kernel
-    Mxx, Mxy, Myy = window_sum(2.0 * (qx * ux), r), window_sum(qx * uy + qy * ux, r), window_sum(2.0 * (qy * uy), r)
-    rx = -(((Qx * It + Mxx * Ix) + Mxy * Iy) * kappa)
-    ry = -(((Qy * It + Mxy * Ix) + Myy * Iy) * kappa)
-    e = (Ix * Qx + Iy * Qy) * kappa
-    dI0 = e + rs.scharr_adjoint(rx, ry)
-    grad64 = np.stack([kc * dI0 for kc in k], 1)
-    value = math.fsum(mv.ravel().tolist()) / float(B * n_m)
-    bound = mv.size * 2.0 ** -53 * math.fsum(np.abs(mv).ravel().tolist()) / float(B * n_m)
-    return PairRef(value, np.stack([ux, uy], 1), seed, grad64.astype(np.float32), grad64, mv, bound)
+    s = fs.flow_stage_ref(pred, prev.astype(np.float64), r, eps, direction, mask, scale)
+    return PairRef(s.value, s.u, s.seed, s.grad, s.grad64, s.mv, s.bound)
 
 
-def field_inputs(w, h, C, kind, B=2):
+def pair_field_inputs(w, h, C, kind, B=2):
     """(pred, prev) float32 [B, C, h, w]: `flow_obj_support.field_inputs`' prediction, and a float reference that is no byte over 255:
     kind "random" floats in [0, 1] with exact 0 and 1 among them, or the "smooth" frame moved off the byte grid"""
     pred, ref = fs.field_inputs(w, h, C, kind, B)
@@ -213,22 +171,7 @@ RISING_ROWS = list(REFINE_ROWS)
 
 
 @functools.lru_cache(maxsize=None)
-def refine_reference(w, h, ch, mode):
-    """refine_stills under a PredictionFlow on the float64 reference alone: `run_pair` with the tied leaf and the weights
-    [0] * n_repeat + [1] * (n_ext - 1), then tests/frame_grad_support.py `still_step_ref`.  -> (stills uint8, history [iters + 1])"""
-    from tests.frame_grad_support import case_inputs, still_step_ref
-    frames, sets = case_inputs(w, h, tuple(ch), 2, 5)
-    stills = np.ascontiguousarray(frames[:, 0])
-    T = REFINE["n_repeat"] + REFINE["n_ext"]
-    weights = [0.0] * REFINE["n_repeat"] + [1.0] * (REFINE["n_ext"] - 1)
-    d = fs.direction_of(mode, w, h)
-    mask = rs.refine_mask(w, h)
-    hist = []
-    run = lambda st: run_pair(sets["live"], list(ch), np.ascontiguousarray(np.broadcast_to(st[:, None], (st.shape[0], T) + st.shape[1:])), radius=7, eps=1e-2,
-                              direction=d, mask=None, n_fed=REFINE["n_repeat"], requant=False, step_weights=weights, leaf="tied")
-    for _ in range(REFINE["iters"]):
-        res = run(stills)
-        hist.append(res.loss)
-        stills = still_step_ref(stills, res.frame_grad.astype(np.float32), REFINE["step"], mask)
-    hist.append(run(stills).loss)
-    return stills, np.array(hist)
+def pair_refine_reference(w, h, ch, mode):
+    """refine_stills under a PredictionFlow on the float64 reference alone: tests/flow_ref_support.py `refine_loop` with `run_pair` and the
+    weights [0] * n_repeat + [1] * (n_ext - 1).  -> (stills uint8, history [iters + 1])"""
+    return rs.refine_loop(run_pair, [0.0] * REFINE["n_repeat"] + [1.0] * (REFINE["n_ext"] - 1), w, h, ch, mode)

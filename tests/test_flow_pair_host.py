@@ -28,7 +28,7 @@ def test_the_analytic_gradients_are_autograds(w, h, C, r, masked, modes, kind):
     """`pair_ref` against torch autograd of `torch_flow_term` by both images: max |delta| <= 1e-12 max |ref| for the gradient by `prev`
     (measured 7.0e-15 at worst) and for the seed ahead of its rounding.  With prev = (float32)byte / 255 of a frame, u, seed and the
     reference gradient are those of `flow_ref_grad` on the frame to the bit."""
-    pred, prev = ps.field_inputs(w, h, C, kind)
+    pred, prev = ps.pair_field_inputs(w, h, C, kind)
     _, ref = fs.field_inputs(w, h, C, kind)
     mask = fs.field_mask(w, h) if masked else None
     assert not np.array_equal(prev, (prev * np.float32(255.0)).round() / np.float32(255.0))   # a float image, not bytes
@@ -96,7 +96,7 @@ def test_refinement_on_the_reference_alone(w, h, ch, mode):
     """`run_pair(leaf="tied")` with the population term's weights [0] * n_repeat + [1] * (n_ext - 1) and `still_step_ref`, 8 steps of 2
     bytes with the left quarter kept (REFINE of tests/flow_ref_support.py, unchanged): the term rises in all eight rows, on every single
     step (DESIGN.md has the table).  RISING_ROWS is what tests/test_gpu_flow_pair.py runs; it lists exactly the rows that rise."""
-    stills, hist = ps.refine_reference(w, h, ch, mode)
+    stills, hist = ps.pair_refine_reference(w, h, ch, mode)
     print("refine on the reference %dx%d %s: %s" % (w, h, mode, " ".join("%.4e" % v for v in hist)))
     assert hist.shape == (ps.REFINE["iters"] + 1,) and np.isfinite(hist).all()
     assert (hist[-1] > hist[0]) == ((w, h, ch, mode) in ps.RISING_ROWS), hist

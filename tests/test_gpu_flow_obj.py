@@ -13,33 +13,13 @@ from evolutionary_illusion_generator_amd import train
 from evolutionary_illusion_generator_amd.engine import EngineError
 from evolutionary_illusion_generator_amd.train import FlowObjective, FlowSettings, PredNetTrainer
 from tests import flow_obj_support as fs
+from tests.flow_gpu_support import SENT, _p, _padded, _raw_term
 from tests.frame_grad_support import case_inputs, check_frame_grads, fold_tied
 from tests.train_support import _check_grads, _grads_differ, case_weights
 
 pytestmark = pytest.mark.gpu
 
-SENT = np.float32(-12345.5)
 WORST = {"norm": 0.0, "element": 0.0, "loss": 0.0, "frames": 0.0}
-
-
-def _p(x):
-    return None if x is None else ctypes.c_void_p(x.data_ptr())
-
-
-def _raw_term(tr, d_pred, p_b, d_ref, r_b, B, radius, eps, d_dir, d_mask, scale, value, d_flow, d_seed, s_b, settings=True):
-    """eigen_trainer_flow_term called directly on device buffers"""
-    cfg = FlowSettings(radius, 0, eps)
-    return tr.lib.eigen_trainer_flow_term(tr._h, _p(d_pred), p_b, _p(d_ref), r_b, B, ctypes.byref(cfg) if settings else None, _p(d_dir), _p(d_mask), ctypes.c_double(scale),
-                                          None if value is None else ctypes.byref(value), _p(d_flow), _p(d_seed), s_b, None)
-
-
-def _padded(a, stride, fill, cuda):
-    """[B, ...] as a flat device buffer with `stride` elements between samples, `fill` in between and behind"""
-    B, per = a.shape[0], int(np.prod(a.shape[1:]))
-    buf = np.full(B * stride + 3, fill, a.dtype)
-    for b in range(B):
-        buf[b * stride:b * stride + per] = a[b].ravel()
-    return torch.from_numpy(buf).to(cuda)
 
 
 @pytest.mark.parametrize("kind", ["random", "smooth"])

@@ -10,45 +10,17 @@ import pytest
 import torch
 
 from evolutionary_illusion_generator_amd import train
-from evolutionary_illusion_generator_amd.train import FlowObjective, FlowSettings, PredictionFlow, PredNetTrainer
+from evolutionary_illusion_generator_amd.train import FlowObjective, PredictionFlow, PredNetTrainer
 from tests import flow_obj_support as fs
 from tests import flow_pair_support as ps
 from tests import flow_ref_support as rs
+from tests.flow_gpu_support import SENT, _padded, _raw_loss_grad, _raw_pair, _unpad
 from tests.frame_grad_support import case_inputs, check_frame_grads, fold_tied
 from tests.train_support import _check_grads, _grads_differ, case_weights
 
 pytestmark = pytest.mark.gpu
 
-SENT = np.float32(-12345.5)
 WORST = {"norm": 0.0, "element": 0.0, "loss": 0.0, "frames": 0.0}
-
-
-def _p(x):
-    return None if x is None else ctypes.c_void_p(x.data_ptr())
-
-
-def _padded(a, stride, fill, cuda):
-    """[B, ...] as a flat device buffer with `stride` elements between samples, `fill` in between and behind"""
-    B, per = a.shape[0], int(np.prod(a.shape[1:]))
-    buf = np.full(B * stride + 3, fill, a.dtype)
-    for b in range(B):
-        buf[b * stride:b * stride + per] = a[b].ravel()
-    return torch.from_numpy(buf).to(cuda)
-
-
-def _unpad(t, stride, B, shp):
-    """the samples of a padded buffer, and whether everything between and behind them is still SENT"""
-    buf, per = t.cpu().numpy(), int(np.prod(shp))
-    written = np.zeros(buf.shape, bool)
-    for b in range(B):
-        written[b * stride:b * stride + per] = True
-    return np.stack([buf[b * stride:b * stride + per].reshape(shp) for b in range(B)]), bool((buf[~written] == SENT).all())
-
-
-def _raw_pair(tr, d_pred, p_b, d_prev, r_b, B, radius, eps, d_dir, d_mask, scale, value, d_flow, d_seed, s_b, d_pg, pg_b, flags=0):
-    cfg = FlowSettings(radius, flags, eps)
-    return tr.lib.eigen_trainer_flow_term_pair(tr._h, _p(d_pred), p_b, _p(d_prev), r_b, B, ctypes.byref(cfg), _p(d_dir), _p(d_mask), ctypes.c_double(scale),
-                                               None if value is None else ctypes.byref(value), _p(d_flow), _p(d_seed), s_b, _p(d_pg), pg_b, None)
 
 
 @pytest.mark.parametrize("kind", ["random", "smooth"])
@@ -58,7 +30,7 @@ def test_the_stage_is_the_numpy_restatement_bit_for_bit(cuda, w, h, C, r, masked
     untouched, and the value is within N 2^-53 sum |m v| / (B N_m), N = B H W summands, of the exactly summed one (the bound of
     tests/test_gpu_flow_obj.py).  Every output is optional."""
     B = 2
-    pred, prev = ps.field_inputs(w, h, C, kind, B)
+    pred, prev = ps.pair_field_inputs(w, h, C, kind, B)
     mask = fs.field_mask(w, h) if masked else None
     per = C * h * w
     p_b, r_b, s_b, g_b = per + 5, per + 3, per + 7, per + 11
@@ -165,15 +137,6 @@ def test_a_training_call_matches_float64_autograd_with_the_previous_prediction_i
         what, norm, element, lossr, ratio, WORST["norm"], WORST["element"], WORST["loss"], WORST["frames"]))
 
 
-def _raw_loss_grad(tr, entry, d, B, T, n, flags, pairing, loss, terms, buf=None, objective=2, settings=True):
-    cfg = FlowSettings(7, flags, 1e-2)
-    args = [tr._h, _p(d), T * n, B, T, T, 0, 1, None, objective, None, ctypes.byref(loss), None, None, _p(buf), T * n if buf is not None else 0,
-            n if buf is not None else 0, ctypes.byref(cfg) if settings else None, None, None, terms]
-    if entry == "pair":
-        return tr.lib.eigen_trainer_loss_grad_flow_pair(*args, pairing, None)
-    return tr.lib.eigen_trainer_loss_grad_flow(*args, None)
-
-
 def test_the_new_entry_with_the_frame_pairing_is_the_old_one_and_calls_repeat(cuda):
     """16x12 [3, 4, 6]: `eigen_trainer_loss_grad_flow_pair(pairing=0)` equals `eigen_trainer_loss_grad_flow` bit for bit in loss, terms,
     all weight gradients and frame gradients, with the constant and with the moving reference; a second identical PredictionFlow call
@@ -246,7 +209,7 @@ def test_refinement_climbs_as_on_the_reference(cuda, w, h, ch, mode):
         out, hist = train.refine_stills(tr, stills, **kw)
         out2, hist2 = train.refine_stills(tr, torch.from_numpy(stills).to(cuda), **kw)
         explicit = train.refine_stills(tr, stills, step_weights=[0.0] * 4 + [1.0], **dict(kw, iters=1))[1]
-    _, ref_hist = ps.refine_reference(w, h, tuple(ch), mode)
+    _, ref_hist = ps.pair_refine_reference(w, h, tuple(ch), mode)
     print("refine prediction pairing %dx%d %s: %s (reference: %s)" % (w, h, mode, " ".join("%.4e" % v for v in hist), " ".join("%.4e" % v for v in ref_hist)))
     assert out.dtype == np.uint8 and out.shape == stills.shape and hist.shape == (9,) and hist.dtype == np.float64
     assert np.array_equal(out, out2) and np.array_equal(hist, hist2) and explicit[0] == hist[0] and explicit[1] == hist[1]

@@ -13,32 +13,13 @@ from evolutionary_illusion_generator_amd import train
 from evolutionary_illusion_generator_amd.train import FlowObjective, FlowSettings, PredNetTrainer
 from tests import flow_obj_support as fs
 from tests import flow_ref_support as rs
+from tests.flow_gpu_support import SENT, _p, _padded, _raw_ref
 from tests.frame_grad_support import case_inputs, check_frame_grads, zero_steps
 from tests.train_support import case_weights
 
 pytestmark = pytest.mark.gpu
 
-SENT = np.float32(-12345.5)
 WORST = {"frames": 0.0}
-
-
-def _p(x):
-    return None if x is None else ctypes.c_void_p(x.data_ptr())
-
-
-def _padded(a, stride, fill, cuda):
-    """[B, ...] as a flat device buffer with `stride` elements between samples, `fill` in between and behind"""
-    B, per = a.shape[0], int(np.prod(a.shape[1:]))
-    buf = np.full(B * stride + 3, fill, a.dtype)
-    for b in range(B):
-        buf[b * stride:b * stride + per] = a[b].ravel()
-    return torch.from_numpy(buf).to(cuda)
-
-
-def _raw_ref(tr, d_pred, p_b, d_ref, r_b, B, radius, eps, d_dir, d_mask, scale, value, d_flow, d_seed, s_b, d_rg, rg_b, flags=0):
-    cfg = FlowSettings(radius, flags, eps)
-    return tr.lib.eigen_trainer_flow_term_ref(tr._h, _p(d_pred), p_b, _p(d_ref), r_b, B, ctypes.byref(cfg), _p(d_dir), _p(d_mask), ctypes.c_double(scale),
-                                              None if value is None else ctypes.byref(value), _p(d_flow), _p(d_seed), s_b, _p(d_rg), rg_b, None)
 
 
 @pytest.mark.parametrize("kind", ["random", "smooth"])
