@@ -1,7 +1,7 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
 // the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for the flow objective
-// flow_obj_kernels.h, flow_ref_kernels.h and flow_pair_kernels.h.
+// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h and flow_score_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "flow_obj_kernels.h"
 #include "flow_ref_kernels.h"
 #include "flow_pair_kernels.h"
+#include "flow_score_kernels.h"
 
 using namespace eigt;
 
@@ -95,6 +96,8 @@ struct eigen_trainer {
     double *f_planes = nullptr, *f_q = nullptr, *f_mv = nullptr;
     // the moving reference's: the flow u [B][2][H W], which the solve writes there when that mode asks, and rx, ry, e [3][B H W]
     double *f_u = nullptr, *f_r = nullptr;
+    // the score mode's: one record per sample [B][SCORE_REC] and the partials of its reductions [B][SCORE_SLICES][SCORE_K]
+    double *f_rec = nullptr, *f_spart = nullptr;
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -243,6 +246,7 @@ int allocate(eigen_trainer* t)
     add((void**)&t->d_absmax, B * 4);
     add((void**)&t->f_planes, 3 * B * t->ly[0].HW * 8); add((void**)&t->f_q, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_mv, B * t->ly[0].HW * 8);
     add((void**)&t->f_u, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_r, 3 * B * t->ly[0].HW * 8);
+    add((void**)&t->f_rec, B * SCORE_REC * 8); add((void**)&t->f_spart, B * SCORE_SLICES * SCORE_K * 8);
     for (int l = 0; l < L; ++l) {
         TLayer& y = t->ly[l];
         const long long CHW = y.CHW();
@@ -394,7 +398,30 @@ struct FlowSpec {
     long long n_mask = 0;
     bool moving = false;  // EIGEN_FLOW_MOVING_REFERENCE: a training call adds every term's reference path to the frame gradient
     bool pair_pred = false;  // EIGEN_FLOW_PAIR_PREDICTION: the reference of term s is the float P0_{s-1}, in the graph
+    bool by_score = false;   // the score mode (flow_score_kernels.h): the value and q come from `score`, kappa loses the mask's count
+    TFlowScore score = {};
+    // what divides a term's scale in kappa: B N_m, or B in the score mode, whose value is a mean over the samples alone
+    double kappa_div(int B) const { return by_score ? (double)B : (double)(B * n_mask); }
 };
+
+// The score mode's settings, before anything is launched; a direction field does not go with them.
+int check_flow_score(const eigen_flow_score* sc, const float* d_dir, FlowSpec& f)
+{
+    if (!sc) return EIGEN_OK;
+    if (d_dir) return tfail(EIGEN_ERR_INVALID, "a flow score takes no direction field");
+    if (sc->reserved != 0) return tfail(EIGEN_ERR_INVALID, "flow score: reserved must be 0, got %d", sc->reserved);
+    if (!std::isfinite(sc->max_norm) || !(sc->max_norm > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow score max_norm %g: must be finite and > 0", sc->max_norm);
+    if (!(sc->min_norm >= 0.0) || !(sc->min_norm < sc->max_norm)) return tfail(EIGEN_ERR_INVALID, "flow score min_norm %g: must be in [0, max_norm = %g)", sc->min_norm, sc->max_norm);
+    if (!std::isfinite(sc->r_min) || !std::isfinite(sc->r_max) || !(sc->r_min >= 0.0) || !(sc->r_max >= sc->r_min))
+        return tfail(EIGEN_ERR_INVALID, "flow score limits %g .. %g: must be finite with 0 <= r_min <= r_max", sc->r_min, sc->r_max);
+    if (sc->min_count < 2) return tfail(EIGEN_ERR_INVALID, "flow score min_count %d: must be >= 2", sc->min_count);
+    for (double w : {sc->w_direction, sc->w_strength})
+        if (!std::isfinite(w) || !(w >= 0.0)) return tfail(EIGEN_ERR_INVALID, "flow score weight %g: weights must be finite and >= 0", w);
+    if (!(sc->w_direction + sc->w_strength > 0.0)) return tfail(EIGEN_ERR_INVALID, "both flow score weights are zero");
+    f.by_score = true;
+    f.score = TFlowScore{sc->max_norm, sc->min_norm, sc->r_min, sc->r_max, sc->w_direction, sc->w_strength, sc->min_count};
+    return EIGEN_OK;
+}
 
 // The settings of a flow call against the handle's image, before anything is launched.  The direction field and the mask are read back
 // to the host: every d must be finite, and kappa needs the mask's count.
@@ -452,14 +479,25 @@ struct FlowTerm {
 // handle's workspace unless the caller wants it anyway.
 void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m)
 {
-    double* d_flow = m.d_refg && !m.d_flow ? t->f_u : m.d_flow;
+    double* d_flow = (m.d_refg || f.by_score) && !m.d_flow ? t->f_u : m.d_flow;
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
     if (m.fref) ew(st, tflow_pair_prep_kernel, n, m.pred, m.p_bstride, m.fref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
     else ew(st, tflow_prep_kernel, n, m.pred, m.p_bstride, m.ref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
     const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
     hipLaunchKernelGGL(tflow_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, n, y.H, y.W, f.r, f.eps, f.dir, f.mask, t->f_q, t->f_mv, d_flow);
-    if (m.d_value) {
+    if (f.by_score) {
+        // the value and q of the score mode, from the u the solve just wrote: two passes of moments, then q over what the solve left in f_q
+        const dim3 sgrid(SCORE_SLICES, (unsigned)B);
+        const double* u = d_flow;
+        hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.score, (const double*)t->f_rec, t->f_spart);
+        hipLaunchKernelGGL(tflow_score_final_kernel<1>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, (double*)nullptr);
+        hipLaunchKernelGGL(tflow_score_moment_kernel<2>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.score, (const double*)t->f_rec, t->f_spart);
+        hipLaunchKernelGGL(tflow_score_final_kernel<2>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, m.d_value);
+        if (m.d_seed || m.d_refg)
+            hipLaunchKernelGGL(tflow_score_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, u, n, y.H, y.W, f.r, f.eps, f.mask, f.score,
+                               (const double*)t->f_rec, t->f_q);
+    } else if (m.d_value) {
         hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
         hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)m.part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), m.d_value, 1);
     }
@@ -483,8 +521,8 @@ struct Objective {
     int T = 0, B = 0;
     const TLayer* ly = nullptr;
     long long n_terms() const { return (long long)(T - 1) * B * ly[0].CHW(); }
-    // the flow objective: kappa of term s, (w_s / sum w) / (B N_m)
-    double flow_kappa(int s) const { return (weight(s) / total_weight()) / (double)(B * flow.n_mask); }
+    // the flow objective: kappa of term s, (w_s / sum w) / (B N_m); in the score mode (w_s / sum w) / B
+    double flow_kappa(int s) const { return (weight(s) / total_weight()) / flow.kappa_div(B); }
     // squared error: d loss / d P0_s = loss_scale(s) * (P0_s - x_{s+1})
     float loss_scale(int s) const
     {
@@ -731,7 +769,7 @@ int read_loss(eigen_trainer* t, hipStream_t st, const Objective& o, bool want_ta
     return EIGEN_OK;
 }
 
-// Everything a training call takes: the arguments of the widest exported entry, eigen_trainer_loss_grad_flow_pair.  An entry lists the
+// Everything a training call takes: the arguments of the widest exported entry, eigen_trainer_loss_grad_flow_score.  An entry lists the
 // leading members, which every entry has, names the others it takes, and leaves the rest at these defaults, which are what it implies.
 struct LossGradCall {
     const uint8_t* d_frames; int64_t bstride; int32_t batch, n_steps, n_fed, requant, reset; double* h_loss; float* d_pred; void* stream;
@@ -745,6 +783,7 @@ struct LossGradCall {
     const uint8_t* d_mask = nullptr;
     double* h_terms = nullptr;
     int32_t pairing = EIGEN_FLOW_PAIR_FRAME;
+    const eigen_flow_score* score = nullptr;
 };
 
 // The training call behind every exported eigen_trainer_loss_grad* entry.  The order of the checks is the order of this function: the
@@ -769,6 +808,7 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     Objective o;
     const bool by_flow = c.objective == EIGEN_OBJ_FLOW;
     if (!by_flow && (c.flow || c.d_dir || c.d_mask)) return tfail(EIGEN_ERR_INVALID, "flow settings, direction and mask go with EIGEN_OBJ_FLOW only");
+    if (!by_flow && c.score) return tfail(EIGEN_ERR_INVALID, "a flow score goes with EIGEN_OBJ_FLOW only");
     // the step and layer weights follow the same rules under every objective
     rc = make_objective(t, by_flow ? (int32_t)EIGEN_OBJ_MSE : c.objective, c.h_layer_w, c.h_step_w, T, B, o);
     if (rc) return rc;
@@ -778,6 +818,8 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
         o.flow.pair_pred = c.pairing == EIGEN_FLOW_PAIR_PREDICTION;
         // a frame is no reference under the prediction pairing: there is nothing the flag could move
         if (o.flow.pair_pred && o.flow.moving) return tfail(EIGEN_ERR_INVALID, "EIGEN_FLOW_PAIR_PREDICTION does not take EIGEN_FLOW_MOVING_REFERENCE");
+        rc = check_flow_score(c.score, c.d_dir, o.flow);
+        if (rc) return rc;
         o.by_flow = true;
         o.h_terms = c.h_terms;
     }
@@ -927,6 +969,19 @@ int eigen_trainer_loss_grad_flow_pair(eigen_trainer* t, const uint8_t* d_frames,
     return loss_grad_call(t, c);
 }
 
+int eigen_trainer_loss_grad_flow_score(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                       int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                       double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride,
+                                       const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double* h_terms, int32_t pairing,
+                                       const eigen_flow_score* score, void* stream)
+{
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score;
+    return loss_grad_call(t, c);
+}
+
 int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
                                  int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
                                  double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow,
@@ -950,11 +1005,12 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
     return loss_grad_call(t, c);
 }
 
-// the three stage-alone entries share this: the checks, one FlowTerm whose seed and reference gradient are stored, not added, and the
+// the four stage-alone entries share this (eigen_trainer_flow_term_score adds the score and the per-sample record): the checks, one FlowTerm whose seed and reference gradient are stored, not added, and the
 // value read back.  eigen_trainer_flow_term wants no reference gradient; eigen_trainer_flow_term_pair gives a float reference, d_fref
 static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
-                          int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr)
+                          int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr, const eigen_flow_score* score = nullptr,
+                          double* h_stats = nullptr)
 {
     if (!t || !d_pred || (!d_ref && !d_fref) || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
@@ -964,17 +1020,23 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
         return tfail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", C0HW);
     if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale %g is not finite", scale);
     FlowSpec f;
-    const int rc = check_flow(t, flow, d_dir, d_mask, 0, f);
+    int rc = check_flow(t, flow, d_dir, d_mask, 0, f);
+    if (rc) return rc;
+    rc = check_flow_score(score, d_dir, f);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     FlowTerm m;
     m.pred = d_pred; m.p_bstride = p_bstride; m.ref = d_ref; m.fref = d_fref; m.r_bstride = r_bstride;
-    m.kappa = scale / (double)(batch * f.n_mask); m.part = t->d_spart; m.d_value = h_value ? t->d_step : nullptr;
+    m.kappa = scale / f.kappa_div(batch); m.part = t->d_spart; m.d_value = h_value ? t->d_step : nullptr;
     m.d_flow = d_flow; m.d_seed = d_seed; m.s_bstride = s_bstride; m.d_refg = d_refg; m.rg_bstride = rg_bstride;
     flow_stage(t, st, batch, f, m);
     TCHK(hipGetLastError());
     if (h_value) {
         TCHK(hipMemcpyAsync(h_value, t->d_step, 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+    }
+    if (h_stats && f.by_score) {
+        TCHK(hipMemcpyAsync(h_stats, t->f_rec, (size_t)batch * SCORE_REC * 8, hipMemcpyDeviceToHost, st));
         TCHK(hipStreamSynchronize(st));
     }
     return EIGEN_OK;
@@ -1002,6 +1064,17 @@ int eigen_trainer_flow_term_pair(eigen_trainer* t, const float* d_pred, int64_t 
     if (!d_prev) return tfail(EIGEN_ERR_INVALID, "null argument");
     return flow_term_call(t, d_pred, p_bstride, nullptr, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_prev_grad, pg_bstride, stream,
                           d_prev);
+}
+
+int eigen_trainer_flow_term_score(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
+                                  int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask, const eigen_flow_score* score, double scale,
+                                  double* h_value, double* h_stats, double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride,
+                                  void* stream)
+{
+    if (!score) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
+    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, nullptr, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride,
+                          stream, d_fref, score, h_stats);
 }
 
 int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,

@@ -21,6 +21,12 @@ class FlowSettings(ctypes.Structure):
     _fields_ = [("radius", ctypes.c_int32), ("flags", ctypes.c_int32), ("eps", ctypes.c_double)]
 
 
+class FlowScoreSettings(ctypes.Structure):
+    """eigen_flow_score"""
+    _fields_ = [("max_norm", ctypes.c_double), ("min_norm", ctypes.c_double), ("r_min", ctypes.c_double), ("r_max", ctypes.c_double),
+                ("w_direction", ctypes.c_double), ("w_strength", ctypes.c_double), ("min_count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class TrainerConfig(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_layers", ctypes.c_int32),
                 ("channels", ctypes.c_int32 * engine.MAX_LAYERS), ("max_batch", ctypes.c_int32), ("max_steps", ctypes.c_int32)]
@@ -38,7 +44,8 @@ _TERM = [_P, _P, _I64, _P, _I64, _I32, _P, _P, _P, ctypes.c_double, _P, _P, _P, 
 # gradient wanted) for the mse and error objectives, (True, pairing) for the flow objective, whose entries take the frame gradient anyway.
 _ENTRIES = {(False, False): ("eigen_trainer_loss_grad_obj", ()), (False, True): ("eigen_trainer_loss_grad_frames", ("frame_grad",)),
             (True, "frame"): ("eigen_trainer_loss_grad_flow", ("frame_grad", "flow")),
-            (True, "prediction"): ("eigen_trainer_loss_grad_flow_pair", ("frame_grad", "flow", "pairing"))}
+            (True, "prediction"): ("eigen_trainer_loss_grad_flow_pair", ("frame_grad", "flow", "pairing")),
+            (True, "score"): ("eigen_trainer_loss_grad_flow_score", ("frame_grad", "flow", "pairing", "score"))}
 
 
 def _bind(lib):
@@ -55,6 +62,9 @@ def _bind(lib):
     lib.eigen_trainer_flow_term.argtypes = _TERM + [_P]
     lib.eigen_trainer_flow_term_ref.argtypes = _TERM + [_P, _I64, _P]
     lib.eigen_trainer_flow_term_pair.argtypes = _TERM + [_P, _I64, _P]
+    lib.eigen_trainer_loss_grad_flow_score.argtypes = _CALL + _OBJ + _FRAMEGRAD + _FLOW + [_I32, _P, _P]
+    # t, d_pred, p_bstride, d_ref, d_fref, r_bstride, batch, flow, d_mask, score, scale, h_value, h_stats, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream
+    lib.eigen_trainer_flow_term_score.argtypes = [_P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _P, ctypes.c_double, _P, _P, _P, _P, _I64, _P, _I64, _P]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
@@ -75,6 +85,46 @@ FLOW_DIRECTIONS = ("tangent", "radial", "horizontal", "vertical")
 FLOW_REFERENCES = ("constant", "moving")
 FLOW_MOVING_REFERENCE = 1  # EIGEN_FLOW_MOVING_REFERENCE
 FLOW_PAIRINGS = {"frame": 0, "prediction": 1}  # EIGEN_FLOW_PAIR_FRAME, EIGEN_FLOW_PAIR_PREDICTION
+
+
+SCORE_STATS = ("N", "mean_rho", "mean_tau", "mean_abs_dx", "mean_norm", "var_rho", "var_tau", "var_norm", "score", "spare")  # one sample's record
+
+
+class FlowScore:
+    """The score mode of ``objective="flow"`` ("The score mode"): the value of a term is the reference's own
+    ``Circles`` score on the dense field u of the stage's solve, per sample, and its mean over the samples.  A pixel is a member when
+    the objective's mask counts it, its distance from (w / 2, h / 2) is not 0 and lies in `limits`, and min_norm <= |u| <= max_norm.
+    Over the members: weights[0] times ``rotation_symmetry_score`` (the low variance of the normalised vectors' radial and tangential
+    components) plus weights[1] times ``strength_number`` (mean |dx| / max_norm times one minus the variance of the norms, capped at
+    1); a sample with fewer than min_count members scores 0 and passes no gradient.  Membership is a constant of the graph.
+
+    The defaults are the reference's constants (fitness_calculator.py:522-533): max_norm 0.3 pixels, limits (0, h / 2) (None: resolved
+    against the trainer's image), at least 25 vectors, weights (0.7, 0.3).  min_norm is this build's choice: the gradient carries
+    1 / |u|, and the floor 1e-3 caps that factor at 1000; the reference has no such floor (it divides by the norm of whatever vector
+    it was given).  ValueError: max_norm not finite or <= 0, min_norm outside [0, max_norm), limits not finite or not
+    0 <= limits[0] <= limits[1], min_count < 2, a weight that is negative or not finite, both weights zero."""
+
+    def __init__(self, max_norm=0.3, min_norm=1e-3, limits=None, min_count=25, weights=(0.7, 0.3)):
+        max_norm, min_norm = float(max_norm), float(min_norm)
+        if not (np.isfinite(max_norm) and max_norm > 0):
+            raise ValueError("max_norm must be finite and > 0, got %r" % (max_norm,))
+        if not 0 <= min_norm < max_norm:
+            raise ValueError("min_norm must be in [0, max_norm = %r), got %r" % (max_norm, min_norm))
+        if limits is not None:
+            limits = tuple(float(v) for v in limits)
+            if len(limits) != 2 or not all(np.isfinite(v) for v in limits) or not 0 <= limits[0] <= limits[1]:
+                raise ValueError("limits must be finite with 0 <= limits[0] <= limits[1], got %r" % (limits,))
+        if isinstance(min_count, bool) or int(min_count) != min_count or int(min_count) < 2:
+            raise ValueError("min_count must be an integer >= 2, got %r" % (min_count,))
+        weights = tuple(float(v) for v in weights)
+        if len(weights) != 2 or not all(np.isfinite(v) and v >= 0 for v in weights) or not sum(weights) > 0:
+            raise ValueError("weights must be two finite values >= 0, not both zero, got %r" % (weights,))
+        self.max_norm, self.min_norm, self.limits, self.min_count, self.weights = max_norm, min_norm, limits, int(min_count), weights
+
+    def settings(self, h):
+        """eigen_flow_score against an image of height h"""
+        lo, hi = self.limits if self.limits is not None else (0.0, h / 2.0)
+        return FlowScoreSettings(self.max_norm, self.min_norm, lo, hi, self.weights[0], self.weights[1], self.min_count, 0)
 
 
 def flow_direction(kind, w, h):
@@ -111,6 +161,9 @@ class FlowObjective:
     "moving", frame s + 1 is in the graph as the reference of term s, and the frame gradient of a training call (``forward_backward``,
     ``refine_stills``, ``refine_genomes``) also holds how every term moves with its reference ("The moving
     reference").  Loss, terms, weight gradients, predictions and state do not depend on it.
+    score: None, or a ``FlowScore``: the term is then the fitness's own Circles score on the solved field ("The
+    score mode"); it takes no direction (ValueError), the mask then selects the pixels that can be members.  ``scored(score)`` sets it
+    on an objective that exists, which is how a ``PredictionFlow`` takes one.
 
     The defaults are a design choice: radius 7 is a 15-pixel window, the fitness path's ``lk_win``; eps 1e-2 is in units of summed
     squared gradients of images in [0, 1] (a 15 x 15 window over an edge of contrast 0.1 sums to about 0.1), so it damps flat windows
@@ -122,7 +175,7 @@ class FlowObjective:
 
     pairing = "frame"
 
-    def __init__(self, radius=7, eps=1e-2, direction=None, mask=None, reference="constant"):
+    def __init__(self, radius=7, eps=1e-2, direction=None, mask=None, score=None, reference="constant"):
         if reference not in FLOW_REFERENCES:
             raise ValueError("reference must be one of %s, got %r" % (", ".join(FLOW_REFERENCES), reference))
         self.reference = reference
@@ -148,6 +201,18 @@ class FlowObjective:
                 raise ValueError("the mask counts no pixel")
             self.mask = m
         self._dev = {}
+        self.score = None
+        self.scored(score)
+
+    def scored(self, score):
+        """Set the score mode (a ``FlowScore``; None: the displacement modes) and return self.  ValueError: not a FlowScore, or a score on an
+        objective with a direction field."""
+        if score is not None and not isinstance(score, FlowScore):
+            raise ValueError("score must be a FlowScore or None, got %r" % (score,))
+        if score is not None and self.direction is not None:
+            raise ValueError("a score takes no direction field")
+        self.score = score
+        return self
 
     def settings(self, stage_alone=False):
         """eigen_flow_settings; the stage-alone entries take no flags (the reference gradient is asked for by the entry called)"""
@@ -172,7 +237,8 @@ class PredictionFlow(FlowObjective):
     weight on the term "prediction after the last fed frame -> first extended prediction" alone (``refine_stills``' default under this
     class) the loss is the dense stand-in for what ``get_fitnesses_neat`` / ``eval_images(pairing=PAIR_POPULATION)`` score.  Frames are no
     references here: a frame gradient is the input path alone, which is the whole gradient, and there is no `reference` argument.
-    radius, eps, direction, mask: as ``FlowObjective``."""
+    radius, eps, direction, mask: as ``FlowObjective``; the score mode is set by ``PredictionFlow(...).scored(FlowScore(...))`` or by
+    ``make_flow("prediction", score=...)``."""
 
     pairing = "prediction"
 
@@ -180,16 +246,16 @@ class PredictionFlow(FlowObjective):
         super().__init__(radius, eps, direction, mask)
 
 
-def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, reference="constant"):
+def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, reference="constant", score=None):
     """The flow objective of a command line: a ``FlowObjective`` (pairing "frame", with its `reference`) or a ``PredictionFlow``
     (pairing "prediction"; it has no frame as a reference, so reference="moving" is a ValueError)."""
     if pairing not in FLOW_PAIRINGS:
         raise ValueError("pairing must be one of %s, got %r" % (", ".join(FLOW_PAIRINGS), pairing))
     if pairing == "frame":
-        return FlowObjective(radius, eps, direction, mask, reference=reference)
+        return FlowObjective(radius, eps, direction, mask, reference=reference, score=score)
     if reference != "constant":
         raise ValueError("the prediction pairing has no frame as a reference: reference=%r does not go with it" % (reference,))
-    return PredictionFlow(radius, eps, direction, mask)
+    return PredictionFlow(radius, eps, direction, mask).scored(score)
 
 
 def _check_flow(objective, flow):
@@ -454,7 +520,10 @@ class PredNetTrainer:
             cfg = flow.settings()
             tails["flow"] = [ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask), _ptr(terms)]
             tails["pairing"] = [ctypes.c_int32(FLOW_PAIRINGS[flow.pairing])]
-        entry, groups = _ENTRIES[by_flow, flow.pairing if by_flow else frame_grads is not None]
+            if flow.score is not None:
+                sc = flow.score.settings(self.h)
+                tails["score"] = [ctypes.byref(sc)]
+        entry, groups = _ENTRIES[by_flow, ("score" if flow.score is not None else flow.pairing) if by_flow else frame_grads is not None]
         _check(getattr(self.lib, entry)(*args, *[a for g in groups for a in tails[g]], _stream_arg(stream)))
         if by_flow:
             self.last_flow_terms = terms[:T - 1]
@@ -506,24 +575,27 @@ class PredNetTrainer:
         out += (self.last_flow_terms,) if flow_terms else ()
         return out[0] if len(out) == 1 else out
 
-    def flow_term(self, pred, ref, flow, scale=1.0, reference_grad=False):
+    def flow_term(self, pred, ref, flow, scale=1.0, reference_grad=False, stats=False):
         """The flow stage alone (eigen_trainer_flow_term), with the kernels a training call runs: pred float32 [n, C, H, W], the
         prediction; ref uint8 [n, C, H, W], the reference frame; n <= batch.  -> (value, u, seed): the term, the flow float64
         [n, 2, H, W] in pixels per frame (x then y) and scale * d value / d pred as float32 [n, C, H, W].  reference_grad=True
         (eigen_trainer_flow_term_ref) appends scale * d value / d ref, by the reference as floats (byte / 255), float32
         [n, C, H, W]: what a training call adds to the frame gradient under reference="moving".  The FlowObjective's own `reference`
-        plays no part here."""
-        return self._flow_stage(pred, ref, False, flow, scale, reference_grad)
+        plays no part here.  With a ``FlowScore`` on `flow` the stage runs in the score mode (eigen_trainer_flow_term_score), and
+        stats=True (score only) appends the float64 [n, 10] record of the samples, ``SCORE_STATS``; either way a score-mode call
+        leaves it in ``self.last_flow_stats`` (None after a call without a score)."""
+        return self._flow_stage(pred, ref, False, flow, scale, reference_grad, stats)
 
     def flow_term_pair(self, pred, prev, flow, scale=1.0, reference_grad=False):
         """The flow stage alone on a pair of float images (eigen_trainer_flow_term_pair), with the kernels a training call runs under a
         ``PredictionFlow``: pred float32 [n, C, H, W], the prediction; prev float32 [n, C, H, W], the reference (the previous
         prediction); n <= batch.  -> (value, u, seed) as ``flow_term``; reference_grad=True appends scale * d value / d prev, float32
         [n, C, H, W]: what a training call adds to d loss / d P0_{s-1}.  The radius, eps, direction and mask of `flow` are used; its
-        pairing and `reference` play no part here."""
+        pairing and `reference` play no part here.  With a score on `flow` the stage runs in the score mode and leaves the float64
+        [n, 10] record of the samples in ``self.last_flow_stats``."""
         return self._flow_stage(pred, prev, True, flow, scale, reference_grad)
 
-    def _flow_stage(self, pred, ref, float_ref, flow, scale, reference_grad):
+    def _flow_stage(self, pred, ref, float_ref, flow, scale, reference_grad, stats=False):
         """flow_term (float_ref False: a uint8 reference) and flow_term_pair (True: a float32 one): the upload, the checks, the buffers,
         the one call and the result tuple"""
         torch = self._torch
@@ -531,6 +603,8 @@ class PredNetTrainer:
             raise ValueError("flow must be a FlowObjective, got %r" % (flow,))
         if not np.isfinite(scale):
             raise ValueError("scale must be finite, got %r" % (scale,))
+        if stats and flow.score is None:
+            raise ValueError("stats goes with a FlowObjective that has a score")
         shp = (self.channels[0], self.h, self.w)
         dev = "cuda:%d" % self.device
         up = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=dt))).to(dev).contiguous()
@@ -545,6 +619,17 @@ class PredNetTrainer:
         seed = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
         rg = torch.empty((n,) + shp, dtype=torch.float32, device=dev) if reference_grad else None
         cfg = flow.settings(stage_alone=True)
+        self.last_flow_stats = None
+        if flow.score is not None:
+            sc = flow.score.settings(self.h)
+            rec = np.zeros((n, len(SCORE_STATS)), np.float64)
+            _check(self.lib.eigen_trainer_flow_term_score(self._h, _ptr(p), ctypes.c_int64(per), None if float_ref else _ptr(r), _ptr(r) if float_ref else None,
+                                                          ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_mask), ctypes.byref(sc),
+                                                          ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(rec), _ptr(u), _ptr(seed), ctypes.c_int64(per),
+                                                          _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None))
+            self.last_flow_stats = rec
+            out = (value.value, u.cpu().numpy(), seed.cpu().numpy()) + ((rg.cpu().numpy(),) if reference_grad else ())
+            return out + (rec,) if stats else out
         args = [self._h, _ptr(p), ctypes.c_int64(per), _ptr(r), ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask),
                 ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(u), _ptr(seed), ctypes.c_int64(per)]
         if float_ref:
@@ -867,4 +952,4 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
 
 
 __all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update", "FlowObjective",
-           "PredictionFlow", "make_flow", "flow_direction"]
+           "PredictionFlow", "make_flow", "flow_direction", "FlowScore"]

@@ -7,7 +7,8 @@
     python examples/evolve_illusion.py -g 5 --refine 4 --refine_iters 5    (Lamarckian step: after every generation the parameters of
         the 4 best genomes are replaced by those `train.refine_genomes` climbs to, before reproduction; gradient = 1 renders only;
         --objective flow --flow-direction tangent climbs the flow objective instead of the squared error;
-        --flow-pairing prediction pairs consecutive predictions, as the fitness that selects does)
+        --flow-pairing prediction pairs consecutive predictions, as the fitness that selects does;
+        --flow-score [--flow-max-norm 0.3] climbs the fitness's own Circles score of the dense field, train.FlowScore)
 """
 import argparse
 import os

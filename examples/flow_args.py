@@ -1,5 +1,5 @@
 """The --flow-* options of examples/refine_illusion.py, refine_genomes.py, evolve_illusion.py and scripts/train_bench.py, and the flow
-objective they state (train.make_flow).  The choices are those of train.FLOW_DIRECTIONS, FLOW_REFERENCES and FLOW_PAIRINGS."""
+objective they state (train.make_flow).  The choices are those of train.FLOW_DIRECTIONS, FLOW_REFERENCES and FLOW_PAIRINGS; --flow-score and --flow-max-norm state a train.FlowScore."""
 
 FLOW_ARGUMENTS = {
     "direction": dict(default=None, choices=["tangent", "radial", "horizontal", "vertical"],
@@ -11,6 +11,9 @@ FLOW_ARGUMENTS = {
     "pairing": dict(default="frame", choices=["frame", "prediction"],
                     help="objective flow: frame pairs the still with the extended predictions (the single-image fitness path), prediction pairs consecutive "
                          "predictions, as the population fitness printed here does; prediction takes --flow-reference constant only"),
+    "score": dict(action="store_true", help="objective flow: climb the fitness's own Circles score of the dense field (train.FlowScore) in place of the "
+                                             "displacement; it takes no --flow-direction"),
+    "max-norm": dict(type=float, default=0.3, help="--flow-score: vectors longer than this many pixels are no members (the fitness's own limit is 0.3)"),
 }
 
 
@@ -25,5 +28,6 @@ def flow_of(a, w, h, mask=None):
     from evolutionary_illusion_generator_amd import train
     if a.objective != "flow":
         return None
+    score = train.FlowScore(max_norm=a.flow_max_norm) if getattr(a, "flow_score", False) else None
     return train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask,
-                           reference=a.flow_reference)
+                           reference=a.flow_reference, score=score)

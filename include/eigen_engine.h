@@ -500,6 +500,53 @@ int eigen_trainer_flow_term_pair(eigen_trainer* t, const float* d_pred, int64_t 
                                  double* h_value, double* d_flow, float* d_seed, int64_t s_bstride, float* d_prev_grad, int64_t pg_bstride,
                                  void* stream);
 
+/* The score mode of EIGEN_OBJ_FLOW ("The score mode"; csrc/flow_score_kernels.h fixes every order): the value of
+ * a term is the Circles score of the population fitness on the dense field u of eigen_trainer_flow_term's solve, which is unchanged.
+ * Float64 on the device, one IEEE operation per operation written.  Per sample b and pixel (x, y):
+ *   px = x - W / 2.0, py = y - H / 2.0, dist = sqrt(px px + py py), nrm = sqrt(ux ux + uy uy);
+ *   member: the mask counts the pixel, dist != 0, r_min <= dist <= r_max, nrm > 0, min_norm <= nrm <= max_norm; membership is a constant
+ *     of the graph;
+ *   nx = ux / nrm, ny = uy / nrm, x1 = px + nx, y1 = py + ny, rho = (x1 px + y1 py) / dist - dist, tau = (-x1 py + y1 px) / dist;
+ *   over the N members, two passes: the means m_rho, m_tau, m_a of |ux|, m_n of nrm; then V_rho, V_tau, V_n, the mean squared
+ *     deviations from them; fixed slices, fixed order;
+ *   R = ((1 - V_rho)(1 - V_rho) + (1 - V_tau)(1 - V_tau)) / 2, A = m_a / max_norm, F = 1 - min(V_n, 1),
+ *     S_b = w_direction R + w_strength (A F), or 0 with N < min_count; value f = (sum_b S_b) / batch, b ascending.
+ *   g = d S_b / d u at the members, 0 elsewhere and in a sample below min_count; q = ((c gx - b gy) / det, (a gy - b gx) / det), 0 where
+ *     the pixel is no member; seed and reference gradient are eigen_trainer_flow_term's and eigen_trainer_flow_term_ref's from this q
+ *     with kappa = scale / batch: the mask's count does not enter.
+ * reserved must be 0. */
+typedef struct {
+    double max_norm, min_norm;   /* finite max_norm > 0; 0 <= min_norm < max_norm: the gradient carries 1 / nrm */
+    double r_min, r_max;         /* finite, 0 <= r_min <= r_max: the ring of distances from (W / 2, H / 2) */
+    double w_direction, w_strength; /* finite, >= 0, not both 0 */
+    int32_t min_count, reserved; /* min_count >= 2: a sample with fewer members scores 0; reserved must be 0 */
+} eigen_flow_score;
+
+/* The flow stage alone in the score mode, with the kernels a training call runs.  Arguments as eigen_trainer_flow_term_ref /
+ * eigen_trainer_flow_term_pair, with these differences: the reference is bytes (d_ref) or floats (d_fref), exactly one of them
+ * non-NULL, sample b at + b * r_bstride; there is no direction field; score is required; h_stats (host, may be NULL) receives
+ * double[batch][10]: N, m_rho, m_tau, m_a, m_n, V_rho, V_tau, V_n, S_b and a spare 0.  d_ref_grad (may be NULL) is stored as
+ * eigen_trainer_flow_term_ref / _pair store theirs.
+ * Errors: as eigen_trainer_flow_term; EIGEN_ERR_INVALID, before any launch: a NULL score, both or neither reference, max_norm not
+ * finite or <= 0, min_norm outside [0, max_norm), r_min < 0, r_max < r_min or either not finite, min_count < 2, a weight that is
+ * negative or not finite, both weights zero, reserved != 0. */
+int eigen_trainer_flow_term_score(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref,
+                                  int64_t r_bstride, int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask,
+                                  const eigen_flow_score* score, double scale, double* h_value, double* h_stats, double* d_flow,
+                                  float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream);
+
+/* eigen_trainer_loss_grad_flow_pair plus the score.  score == NULL: the call IS eigen_trainer_loss_grad_flow_pair, launch for launch and
+ * bit for bit.  Otherwise (objective EIGEN_OBJ_FLOW only, d_dir NULL) every computed term is the value of eigen_trainer_flow_term_score
+ * under the call's pairing, its seeds carry scale = w_s / sum w with kappa = scale / batch, and everything else, the moving reference
+ * under the frame pairing included, is as without a score.
+ * Errors: as eigen_trainer_loss_grad_flow_pair and eigen_trainer_flow_term_score; EIGEN_ERR_INVALID a score under another objective or
+ * together with a direction field. */
+int eigen_trainer_loss_grad_flow_score(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                       int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                       const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                       int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                       const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score, void* stream);
+
 /* One normalised ascent step on uint8 stills d_images [batch][C][H][W], in place, from a tied gradient (image b at d_grad + b *
  * g_bstride floats): per image m_b = max |g| over the pixels the mask keeps free, then x = byte / 255.0f,
  * x' = min(max(x + k * (g / m_b), 0), 1) with k = (float)(step_bytes / 255.0), byte' = (uint8_t)(int)(x' * 255.0f + 0.5f), each one

@@ -6,6 +6,7 @@ the tape-free evaluate of that call.  Prints one JSON line per side and writes p
     python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both] [--objective mse|l0|lall]
     python scripts/train_bench.py --frame-grads [--steps 5] [--warmup 2]
     python scripts/train_bench.py --flow-cost [--steps 5] [--warmup 2] [--flow-reference constant|moving] [--flow-pairing frame|prediction]
+        [--flow-score [--flow-max-norm 0.3]]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
 side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
@@ -16,6 +17,8 @@ weights, alternated round by round in one process, and prints the ms per call of
 gradients (left on the device) under the constant and under the moving reference: their difference is what the mode costs.
 --flow-pairing prediction makes the flow objective a PredictionFlow (term s from prediction s - 1 to prediction s); --flow-cost then adds
 one leg, "flow_prediction", beside "mse" and the frame-pairing "flow": their difference over the two computed terms is what the pairing costs.
+--flow-score gives the flow objective a train.FlowScore (the Circles score of the dense field); --flow-cost then adds one leg, "flow_score",
+under the pairing and reference asked for, beside the energy-mode legs: their difference over the two computed terms is what the mode costs.
 """
 import argparse
 import json
@@ -62,14 +65,14 @@ def frames(seed, n, T, c, h, w):
 FLOW_WEIGHTS = [0.0] * (T - 3) + [1.0, 1.0]   # two weighted terms, as a refinement call has them
 
 
-def objective_args(name, reference="constant", pairing="frame"):
+def objective_args(name, reference="constant", pairing="frame", score=None):
     if name == "flow":
         from evolutionary_illusion_generator_amd.train import make_flow
-        return dict(objective="flow", flow=make_flow(pairing, radius=7, eps=1e-2, reference=reference), step_weights=FLOW_WEIGHTS)
+        return dict(objective="flow", flow=make_flow(pairing, radius=7, eps=1e-2, reference=reference, score=score), step_weights=FLOW_WEIGHTS)
     return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
 
 
-def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"):
+def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None):
     """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round; with
     the moving reference also per "flow" call with tied frame gradients, under either reference"""
     import ctypes
@@ -83,6 +86,8 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"
         calls["flow_tied_moving"] = dict(objective_args("flow", "moving"), frame_grads="tied")
     if pairing == "prediction":
         calls["flow_prediction"] = objective_args("flow", pairing="prediction")
+    if score is not None:
+        calls["flow_score"] = objective_args("flow", reference, pairing, score)
     ms = {k: [] for k in calls}
     loss = {}
     with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
@@ -108,13 +113,13 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"
     return [dict(side="loss_grad_" + k, call_ms=float(np.median(v)), call_ms_min=min(v), call_ms_max=max(v), rounds=rounds, loss=loss[k]) for k, v in ms.items()]
 
 
-def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame"):
+def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
     d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
     tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T)
-    kw = objective_args(objective, reference, pairing)
+    kw = objective_args(objective, reference, pairing, score) if objective == "flow" else objective_args(objective)
     for _ in range(warmup):
         tr.step(d, **kw)
     torch.cuda.synchronize()
@@ -246,7 +251,7 @@ def main():
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
     ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall", "flow"], help="the trainer side's objective")
     ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
-    add_flow_arguments(ap, ("reference", "pairing"), reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
+    add_flow_arguments(ap, ("reference", "pairing", "score", "max-norm"), reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
                        pairing=dict(help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)"))
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
@@ -254,6 +259,10 @@ def main():
     a = ap.parse_args()
     if a.flow_pairing == "prediction" and a.flow_reference == "moving":
         ap.error("--flow-pairing prediction has no frame as a reference: it does not take --flow-reference moving")
+    score = None
+    if a.flow_score:
+        from evolutionary_illusion_generator_amd.train import FlowScore
+        score = FlowScore(max_norm=a.flow_max_norm)
     if a.side == "torch":
         print(json.dumps(run_torch(a.steps, a.warmup)))
         return
@@ -262,10 +271,10 @@ def main():
             print(json.dumps(r), flush=True)
         return
     if a.flow_cost:
-        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing):
+        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score):
             print(json.dumps(r), flush=True)
         return
-    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing)]
+    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score)]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
