@@ -432,8 +432,13 @@ __global__ void __launch_bounds__((HALF && !NSPLIT) ? W4_THREADS / 2 : W4_THREAD
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(prs, (__attribute__((address_space(3))) void*)(Pb + po0 + ch2 * PS + part2 * 256), 16,
                                                          (int)__builtin_elementwise_add_sat(o2, pcoff + (unsigned)(ch2 - pch) * phw4), 0, 0, 0);
             }
-            if (__builtin_expect(pj + 1 == pbound, 0)) { if (pbound < nkb) plane_source(pj + 1); }   // (at the end the cursor stays on the last K-block)
-            else { ++pj; pcoff += KC * phw4; }
+            // advance first, ask afterwards: the change of source (at most twice per N-block) is laid out of line and the K-block falls through -- as
+            // if (at the boundary) switch; else advance; the compiler kept the switch in line and the hot path took a branch over it in every K-block
+            ++pj; pcoff += KC * phw4;
+            if (__builtin_expect(pj == pbound, 0)) {
+                if (pbound < nkb) plane_source(pj);
+                else { --pj; pcoff -= KC * phw4; }   // (at the end the cursor stays on the last K-block)
+            }
         };
         plane_source(3 < nkb ? 3 : nkb - 1);   // (slot 0 = 3 % 3)
         // Row XI of B^T d of the next K-block's patch in TWO phases (half the registers in flight; the same operations in the same order as w4_row):
@@ -512,11 +517,36 @@ __global__ void __launch_bounds__((HALF && !NSPLIT) ? W4_THREADS / 2 : W4_THREAD
                 for (int ni = 0; ni < NI; ++ni) dst[ni] = bsrc[ni];
             }
         };
-        // One K-block.  kind_tag: 0 full, 1 unpooled source, 2 run time; nk_tag: kind of K-block kb + 1 (whose patch rows are read now), same codes; last_tag: the last
-        // K-block (nothing to stage).  On entry v and bq hold the A operands and the first B operand of this K-block: the first instruction behind the barrier is an MFMA,
-        // and the staging work sits in slices BETWEEN the chunks -- the U fetch behind chunk 0, the plane fetch behind chunk 1, the patch rows of K-block kb + 1 and
-        // the A operands of kb + 1 behind the last chunks (see slice below).
-        auto kiter = [&](const int kb, auto kind_tag, auto nk_tag, auto last_tag, auto first_tag) __attribute__((always_inline)) {
+        // One K-block = khead + ktail.  kind_tag: 0 full, 1 unpooled source, 2 run time; nk_tag: kind of K-block kb + 1 (whose patch rows are read now), same codes;
+        // last_tag: the last K-block (nothing to stage).  On entry v and bq hold the A operands and the first B operand of this K-block: the first instruction behind
+        // the barrier is an MFMA, and the staging work sits in slices BETWEEN the chunks -- the U fetch behind chunk 0, the plane fetch behind chunk 1, the patch
+        // rows of K-block kb + 1 and the A operands of kb + 1 behind the last chunks (see slice below).
+        // All twelve waves leave the barrier together: what a wave issues between the barrier and its first MFMA is hidden behind nothing, on every SIMD, once per
+        // K-block.  So the K loops are ROTATED by chunk 0 (see run below): khead = chunk 0's MFMAs, with the B read of chunk 1 behind the first of them, stands right
+        // behind the barrier at the END of the loop body, and the back-edge, the loop counters, the m0 / offset set-up of the U fetch and the fetch itself follow in the
+        // shadow of those MFMAs.  The fences keep it so: left to itself the compiler hoists the B read and all three DMA instructions of slice 0 above chunk 0's MFMAs
+        // (some twenty instructions and the taken back-edge between the barrier and the first MFMA: DESIGN.md section 3.1).
+        float bv[2][NIW];
+        auto khead_mfma = [&]() __attribute__((always_inline)) {
+            __builtin_amdgcn_sched_barrier(0);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[0], bq[0], acc[0][0], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            read_b(uo0, 1, bv[1]);
+#pragma unroll
+            for (int ni = 1; ni < NIW; ++ni) acc[0][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[0], bq[ni], acc[0][ni], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // chunk 0 of K-block kb.  kind_tag as for ktail; an unpooled-source K-block of row xi = 2 is idle.  Run time (the first K-block behind a run, whose kind the run
+        // does not know, and the last of all): the MFMAs are issued without asking.  Where that K-block is an unpooled-source one of row xi = 2, v[0] is the exact zero
+        // the column pass made of T2 = p - p, and fma(0, u, M) = M -- what the last K-block of all has always relied on; here once more per N-block, for the first
+        // K-block of the unpooled source.  (Asking -- a wave-uniform branch around four MFMAs -- costs two VGPRs in every instantiation: the ConvLSTM at 168 with
+        // 12 bytes of scratch.  kb is not used, but without the parameter the ConvA / ConvP instantiations keep two / one more SGPRs in VGPR lanes.)
+        auto khead = [&](const int kb, auto kind_tag) __attribute__((always_inline)) {
+            constexpr int KIND = decltype(kind_tag)::value;
+            if constexpr (XI != 2 || KIND == 0) khead_mfma();
+            else if constexpr (KIND == 2) khead_mfma();
+        };
+        auto ktail = [&](const int kb, auto kind_tag, auto nk_tag, auto last_tag, auto first_tag) __attribute__((always_inline)) {
             constexpr int KIND = decltype(kind_tag)::value;
             constexpr int NK = decltype(nk_tag)::value;
             constexpr bool LAST = decltype(last_tag)::value;
@@ -524,7 +554,6 @@ __global__ void __launch_bounds__((HALF && !NSPLIT) ? W4_THREADS / 2 : W4_THREAD
             constexpr bool UP = KIND == 1;   // (run-time kind = the last K-block of all: an unpooled-source one there runs the full body on its exact-zero operands -- fma(0, u, M) = M)
             constexpr bool IDLE = UP && XI == 2;   // nothing to multiply
             constexpr int NCH = IDLE ? 0 : (UP ? 5 : 6);   // chunks: nu = 0, 1, (2,) 3, 4, 5
-            float bv[2][NIW];
             // slices of staging work behind the chunks: the U fetch behind chunk 0, the plane fetch behind chunk 1, the patch rows of K-block kb + 1 and row XI of
             // B^T d in two phases behind chunks NCH - 4 .. NCH - 2 (their registers are needed late), the column pass behind the last chunk
             auto slice = [&](int i) __attribute__((always_inline)) {
@@ -546,20 +575,25 @@ __global__ void __launch_bounds__((HALF && !NSPLIT) ? W4_THREADS / 2 : W4_THREAD
                     build_cols();
                 }
             } else {
+                slice(0);   // (khead was chunk 0)
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int i = 0; i < NCH; ++i) {
+                for (int i = 1; i < NCH; ++i) {
                     const int nu = (UP && i >= 2) ? i + 1 : i;
                     if (i + 1 < NCH) {
                         const int nu1 = (UP && i + 1 >= 2) ? i + 2 : i + 1;
                         read_b(uo0, nu1, bv[(i + 1) & 1]);
                     } else if constexpr (!LAST && !FIRST) read_b(uo1, 0, bq);
-                    const float* const b = i == 0 ? bq : bv[i & 1];
+                    const float* const b = bv[i & 1];
 #pragma unroll
                     for (int ni = 0; ni < NIW; ++ni) acc[nu][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[nu], b[ni], acc[nu][ni], 0, 0, 0);
                     slice(i);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
+            // (tall: wait_u below is a wave-uniform branch -- waves 0-3 have two plane instructions in flight -- and the compiler sinks the column pass across it to
+            // the operands' first use, behind the barrier; pinned here)
+            if constexpr (TALL && !LAST) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
             { const int t0 = uo0; uo0 = uo1; uo1 = uo2; uo2 = t0; }
             { const int t0 = po0; po0 = po1; po1 = po2; po2 = t0; }
             // the U fetch of this K-block has landed (its plane fetch may stay in flight: it is read two K-blocks from now); after the last K-block: everything
@@ -569,6 +603,7 @@ __global__ void __launch_bounds__((HALF && !NSPLIT) ? W4_THREADS / 2 : W4_THREAD
             if constexpr (FIRST) read_b(uo0, 0, bq);
         };
         const std::false_type nl{};
+        const std::integral_constant<int, 0> full{};
         const std::integral_constant<int, 2> rt{};
         int kb = 0;
         rows_begin(W4_P0, EIG4_IS_UP(0)); rows_mid(); rows_end();
@@ -576,17 +611,20 @@ __global__ void __launch_bounds__((HALF && !NSPLIT) ? W4_THREADS / 2 : W4_THREAD
         build_cols();
         EIG4_WAITCNT(0xC07F);
         EIG4_BARRIER();   // (every wave has read plane 0 out of its slot before anyone's K-block 0 fetches into it)
-        // K-blocks [kb, end) of one kind; the LAST K-block of all is left out.  A K-block reads the patch rows of the next one: same kind except at the end of a run.
+        // K-blocks [kb, end) of one kind; the LAST K-block of all is left out.  A K-block reads the patch rows of the next one: same kind except at the end of a run
+        // (there the kind is taken at run time: the same reads).  Every ktail is followed by the khead of the next K-block: the loop's body is ktail(kb),
+        // khead(kb + 1), back-edge -- the K loop rotated by chunk 0.
         auto run = [&](const int end, auto kind_tag) __attribute__((always_inline)) {
-            for (; kb + 1 < end; ++kb) kiter(kb, kind_tag, kind_tag, nl, nl);
-            if (kb + 1 == end && end < nkb) { kiter(kb, kind_tag, rt, nl, nl); ++kb; }
+            const int m = end - (end == nkb ? 1 : 0);
+            for (; kb + 1 < m; ++kb) { ktail(kb, kind_tag, kind_tag, nl, nl); khead(kb + 1, kind_tag); }
+            if (kb + 1 == m) { ktail(kb, kind_tag, rt, nl, nl); ++kb; khead(kb, rt); }
         };
-        kiter(0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, nl, std::true_type{});   // (source 0 has at least two K-blocks: Cin % 8 == 0)
+        khead(0, full); ktail(0, full, full, nl, std::true_type{}); khead(1, full);   // (source 0 has at least two K-blocks: Cin % 8 == 0)
         kb = 1;
-        run(up_lo, std::integral_constant<int, 0>{});
+        run(up_lo, full);
         run(up_hi, std::integral_constant<int, 1>{});
-        run(nkb, std::integral_constant<int, 0>{});
-        kiter(nkb - 1, rt, rt, std::true_type{}, nl);
+        run(nkb, full);
+        ktail(nkb - 1, rt, rt, std::true_type{}, nl);
     };
     switch (xi) {
         case 0: kloops(std::integral_constant<int, 0>{}); break;
