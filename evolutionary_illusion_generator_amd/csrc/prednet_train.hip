@@ -1,7 +1,7 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
 // the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for the flow objective
-// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h and flow_score_kernels.h.
+// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h, flow_score_kernels.h and flow_struct_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "flow_ref_kernels.h"
 #include "flow_pair_kernels.h"
 #include "flow_score_kernels.h"
+#include "flow_struct_kernels.h"
 
 using namespace eigt;
 
@@ -98,6 +99,11 @@ struct eigen_trainer {
     double *f_u = nullptr, *f_r = nullptr;
     // the score mode's: one record per sample [B][SCORE_REC] and the partials of its reductions [B][SCORE_SLICES][SCORE_K]
     double *f_rec = nullptr, *f_spart = nullptr;
+    // the structure scores' (flow_struct_kernels.h): g [B][2][H W], the record [B][STRUCT_REC] and the partials [B][STRUCT_SLICES][STRUCT_K];
+    // for Free theta and L [B][H W] each, rowS and colS [B][H W] each, and the member flags [B][H W]
+    double *f_g = nullptr, *f_srec = nullptr, *f_sspart = nullptr, *f_theta = nullptr, *f_L = nullptr;
+    int *f_rowS = nullptr, *f_colS = nullptr;
+    uint8_t* f_flag = nullptr;
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -259,6 +265,10 @@ int allocate(eigen_trainer* t)
         for (float** p : {&y.dhP, &y.dhc, &y.dc, &y.dPn}) add((void**)p, B * CHW * 4);
         if (l > 0) add((void**)&y.dup, B * 4 * CHW * 4);  // [B][C_l][H_{l-1}][W_{l-1}]
     }
+    // the structure scores' workspace comes last: the allocations above keep the order they had without it
+    add((void**)&t->f_g, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_srec, B * STRUCT_REC * 8); add((void**)&t->f_sspart, B * STRUCT_SLICES * STRUCT_K * 8);
+    add((void**)&t->f_theta, B * t->ly[0].HW * 8); add((void**)&t->f_L, B * t->ly[0].HW * 8);
+    add((void**)&t->f_rowS, B * t->ly[0].HW * 4); add((void**)&t->f_colS, B * t->ly[0].HW * 4); add((void**)&t->f_flag, B * t->ly[0].HW);
     for (auto& w : want) {
         const hipError_t e = hipMalloc(w.first, w.second);
         if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%zu): %s", w.second, hipGetErrorString(e));
@@ -400,9 +410,49 @@ struct FlowSpec {
     bool pair_pred = false;  // EIGEN_FLOW_PAIR_PREDICTION: the reference of term s is the float P0_{s-1}, in the graph
     bool by_score = false;   // the score mode (flow_score_kernels.h): the value and q come from `score`, kappa loses the mask's count
     TFlowScore score = {};
+    bool by_struct = false;  // a structure score (flow_struct_kernels.h): the value and q come from `sscore`, kappa as in the score mode
+    TFlowStruct sscore = {};
     // what divides a term's scale in kappa: B N_m, or B in the score mode, whose value is a mean over the samples alone
-    double kappa_div(int B) const { return by_score ? (double)B : (double)(B * n_mask); }
+    double kappa_div(int B) const { return by_score || by_struct ? (double)B : (double)(B * n_mask); }
 };
+
+// A structure score's settings, before anything is launched; a direction field does not go with them.  Every structure's rules cover
+// the fields it reads: the limits are Bands', max_distance and the weights are Free's.
+int check_flow_struct(const eigen_flow_structure_score* sc, const float* d_dir, FlowSpec& f)
+{
+    if (!sc) return EIGEN_OK;
+    if (sc->structure == 1 || sc->structure == 3)
+        return tfail(EIGEN_ERR_INVALID, "flow structure score: structure %d (Circles, CirclesFree) is the score mode's, eigen_flow_score", sc->structure);
+    if (sc->structure != STRUCT_BANDS && sc->structure != STRUCT_FREE) return tfail(EIGEN_ERR_INVALID, "flow structure score: unknown structure %d", sc->structure);
+    if (d_dir) return tfail(EIGEN_ERR_INVALID, "a flow structure score takes no direction field");
+    if (!std::isfinite(sc->max_norm) || !(sc->max_norm > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow structure score max_norm %g: must be finite and > 0", sc->max_norm);
+    if (!(sc->min_norm >= 0.0) || !(sc->min_norm < sc->max_norm))
+        return tfail(EIGEN_ERR_INVALID, "flow structure score min_norm %g: must be in [0, max_norm = %g)", sc->min_norm, sc->max_norm);
+    if (sc->min_count < 1) return tfail(EIGEN_ERR_INVALID, "flow structure score min_count %d: must be >= 1", sc->min_count);
+    TFlowStruct s = {};
+    s.structure = sc->structure; s.min_count = sc->min_count; s.max_norm = sc->max_norm; s.min_norm = sc->min_norm;
+    if (sc->structure == STRUCT_BANDS) {
+        // |lim_hi| <= 2e9: middle = (int)(lim_hi / 2) must be representable
+        if (!std::isfinite(sc->lim_lo) || !std::isfinite(sc->lim_hi) || !(sc->lim_hi >= sc->lim_lo) || std::fabs(sc->lim_hi) > 2e9)
+            return tfail(EIGEN_ERR_INVALID, "flow structure score limits %g .. %g: must be finite with lim_lo <= lim_hi and |lim_hi| <= 2e9", sc->lim_lo, sc->lim_hi);
+        s.lim_lo = sc->lim_lo; s.lim_hi = sc->lim_hi; s.middle = (int)(sc->lim_hi / 2.0);
+    } else {
+        if (!std::isfinite(sc->max_distance) || !(sc->max_distance > 0.0))
+            return tfail(EIGEN_ERR_INVALID, "flow structure score max_distance %g: must be finite and > 0", sc->max_distance);
+        double sum = 0.0;
+        for (double w : sc->w) {
+            if (!std::isfinite(w) || !(w >= 0.0)) return tfail(EIGEN_ERR_INVALID, "flow structure score weight %g: weights must be finite and >= 0", w);
+            sum += w;
+        }
+        if (!(sum > 0.0)) return tfail(EIGEN_ERR_INVALID, "all flow structure score weights are zero");
+        s.DD = sc->max_distance * sc->max_distance;
+        if (!std::isfinite(s.DD) || !(s.DD > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow structure score max_distance %g: its square must be finite and > 0", sc->max_distance);
+        s.w0 = sc->w[0]; s.w1 = sc->w[1]; s.w2 = sc->w[2];
+    }
+    f.by_struct = true;
+    f.sscore = s;
+    return EIGEN_OK;
+}
 
 // The score mode's settings, before anything is launched; a direction field does not go with them.
 int check_flow_score(const eigen_flow_score* sc, const float* d_dir, FlowSpec& f)
@@ -474,12 +524,41 @@ struct FlowTerm {
     float* d_refg = nullptr; long long rg_bstride = 0; int rg_accumulate = 0; // kappa d value / d reference (flow_ref_kernels.h), likewise
 };
 
+// The value and q of a structure score from the u the solve just wrote (flow_struct_kernels.h): two passes of moments, for Free the
+// prepare and the pair pass between them, then (want_q) the gradient g and q over what the solve left in f_q.
+template <int STRUCT>
+void struct_stage_of(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value, bool want_q)
+{
+    const TLayer& y = t->ly[0];
+    const long long n = (long long)B * y.HW;
+    const dim3 sgrid(STRUCT_SLICES, (unsigned)B);
+    const TFlowStruct& s = f.sscore;
+    if (STRUCT == STRUCT_FREE) ew(st, tflow_free_prepare_kernel, n, u, n, y.H, y.W, f.mask, s, t->f_theta, t->f_flag);
+    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 1>), sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, s, (const double*)t->f_srec, (const double*)t->f_L, t->f_sspart);
+    hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 1>), dim3(B), dim3(64), 0, st, (const double*)t->f_sspart, B, s, t->f_srec, (double*)nullptr);
+    if (STRUCT == STRUCT_FREE)
+        hipLaunchKernelGGL(tflow_free_pair_kernel, dim3((unsigned)((y.HW + PAIR_T - 1) / PAIR_T), (unsigned)B), dim3(PAIR_T), 0, st, (const double*)t->f_theta,
+                           (const uint8_t*)t->f_flag, y.H, y.W, s.DD, t->f_L, t->f_rowS, t->f_colS);
+    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 2>), sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, s, (const double*)t->f_srec, (const double*)t->f_L, t->f_sspart);
+    hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 2>), dim3(B), dim3(64), 0, st, (const double*)t->f_sspart, B, s, t->f_srec, d_value);
+    if (!want_q) return;
+    ew(st, tflow_struct_grad_kernel<STRUCT>, n, u, n, y.H, y.W, f.mask, s, (const double*)t->f_srec, (const int*)t->f_rowS, (const int*)t->f_colS, t->f_g);
+    const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
+    hipLaunchKernelGGL(tflow_struct_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_g, n, y.H, y.W, f.r, f.eps, t->f_q);
+}
+
+void struct_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value, bool want_q)
+{
+    if (f.sscore.structure == STRUCT_BANDS) struct_stage_of<STRUCT_BANDS>(t, st, B, f, u, d_value, want_q);
+    else struct_stage_of<STRUCT_FREE>(t, st, B, f, u, d_value, want_q);
+}
+
 // The flow stage of one term (eigen_trainer_flow_term states the arithmetic): the planes, the tiled solve, then what is wanted of the
 // value, the flow and the seed.  A reference gradient is formed from the planes, q and u this stage leaves: u is then written to the
 // handle's workspace unless the caller wants it anyway.
 void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m)
 {
-    double* d_flow = (m.d_refg || f.by_score) && !m.d_flow ? t->f_u : m.d_flow;
+    double* d_flow = (m.d_refg || f.by_score || f.by_struct) && !m.d_flow ? t->f_u : m.d_flow;
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
     if (m.fref) ew(st, tflow_pair_prep_kernel, n, m.pred, m.p_bstride, m.fref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
@@ -497,6 +576,8 @@ void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, cons
         if (m.d_seed || m.d_refg)
             hipLaunchKernelGGL(tflow_score_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, u, n, y.H, y.W, f.r, f.eps, f.mask, f.score,
                                (const double*)t->f_rec, t->f_q);
+    } else if (f.by_struct) {
+        struct_stage(t, st, B, f, d_flow, m.d_value, m.d_seed || m.d_refg);
     } else if (m.d_value) {
         hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
         hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)m.part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), m.d_value, 1);
@@ -784,6 +865,7 @@ struct LossGradCall {
     double* h_terms = nullptr;
     int32_t pairing = EIGEN_FLOW_PAIR_FRAME;
     const eigen_flow_score* score = nullptr;
+    const eigen_flow_structure_score* sscore = nullptr;
 };
 
 // The training call behind every exported eigen_trainer_loss_grad* entry.  The order of the checks is the order of this function: the
@@ -809,6 +891,7 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     const bool by_flow = c.objective == EIGEN_OBJ_FLOW;
     if (!by_flow && (c.flow || c.d_dir || c.d_mask)) return tfail(EIGEN_ERR_INVALID, "flow settings, direction and mask go with EIGEN_OBJ_FLOW only");
     if (!by_flow && c.score) return tfail(EIGEN_ERR_INVALID, "a flow score goes with EIGEN_OBJ_FLOW only");
+    if (!by_flow && c.sscore) return tfail(EIGEN_ERR_INVALID, "a flow structure score goes with EIGEN_OBJ_FLOW only");
     // the step and layer weights follow the same rules under every objective
     rc = make_objective(t, by_flow ? (int32_t)EIGEN_OBJ_MSE : c.objective, c.h_layer_w, c.h_step_w, T, B, o);
     if (rc) return rc;
@@ -819,6 +902,8 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
         // a frame is no reference under the prediction pairing: there is nothing the flag could move
         if (o.flow.pair_pred && o.flow.moving) return tfail(EIGEN_ERR_INVALID, "EIGEN_FLOW_PAIR_PREDICTION does not take EIGEN_FLOW_MOVING_REFERENCE");
         rc = check_flow_score(c.score, c.d_dir, o.flow);
+        if (rc) return rc;
+        rc = check_flow_struct(c.sscore, c.d_dir, o.flow);
         if (rc) return rc;
         o.by_flow = true;
         o.h_terms = c.h_terms;
@@ -1010,7 +1095,7 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
 static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
                           int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr, const eigen_flow_score* score = nullptr,
-                          double* h_stats = nullptr)
+                          double* h_stats = nullptr, const eigen_flow_structure_score* sscore = nullptr)
 {
     if (!t || !d_pred || (!d_ref && !d_fref) || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
@@ -1023,6 +1108,8 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
     int rc = check_flow(t, flow, d_dir, d_mask, 0, f);
     if (rc) return rc;
     rc = check_flow_score(score, d_dir, f);
+    if (rc) return rc;
+    rc = check_flow_struct(sscore, d_dir, f);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     FlowTerm m;
@@ -1037,6 +1124,10 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
     }
     if (h_stats && f.by_score) {
         TCHK(hipMemcpyAsync(h_stats, t->f_rec, (size_t)batch * SCORE_REC * 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+    }
+    if (h_stats && f.by_struct) {
+        TCHK(hipMemcpyAsync(h_stats, t->f_srec, (size_t)batch * STRUCT_REC * 8, hipMemcpyDeviceToHost, st));
         TCHK(hipStreamSynchronize(st));
     }
     return EIGEN_OK;
@@ -1075,6 +1166,46 @@ int eigen_trainer_flow_term_score(eigen_trainer* t, const float* d_pred, int64_t
     if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
     return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, nullptr, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride,
                           stream, d_fref, score, h_stats);
+}
+
+int eigen_trainer_flow_term_structure(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
+                                      int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask, const eigen_flow_structure_score* score, double scale,
+                                      double* h_value, double* h_stats, double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride,
+                                      void* stream)
+{
+    if (!score) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
+    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, nullptr, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride,
+                          stream, d_fref, nullptr, h_stats, score);
+}
+
+int eigen_trainer_debug_free_planes(eigen_trainer* t, int32_t batch, double* h_theta, double* h_L, int32_t* h_rowS, int32_t* h_colS, uint8_t* h_flag, void* stream)
+{
+    if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (batch < 1 || batch > t->cfg.max_batch) return tfail(EIGEN_ERR_INVALID, "batch %d outside 1 .. %d", batch, t->cfg.max_batch);
+    TCHK(hipSetDevice(t->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)batch * t->ly[0].HW;
+    if (h_theta) TCHK(hipMemcpyAsync(h_theta, t->f_theta, n * 8, hipMemcpyDeviceToHost, st));
+    if (h_L) TCHK(hipMemcpyAsync(h_L, t->f_L, n * 8, hipMemcpyDeviceToHost, st));
+    if (h_rowS) TCHK(hipMemcpyAsync(h_rowS, t->f_rowS, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_colS) TCHK(hipMemcpyAsync(h_colS, t->f_colS, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_flag) TCHK(hipMemcpyAsync(h_flag, t->f_flag, n, hipMemcpyDeviceToHost, st));
+    TCHK(hipStreamSynchronize(st));
+    return EIGEN_OK;
+}
+
+int eigen_trainer_loss_grad_flow_structure(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                           int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                           double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride,
+                                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double* h_terms, int32_t pairing,
+                                           const eigen_flow_structure_score* score, void* stream)
+{
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.sscore = score;
+    return loss_grad_call(t, c);
 }
 
 int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,

@@ -25,7 +25,8 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_trainer_get_state", "eigen_trainer_set_state", "eigen_trainer_loss_grad_obj", "eigen_trainer_evaluate_err",
            "eigen_trainer_loss_grad_frames", "eigen_trainer_still_step", "eigen_cppn_param_grads", "eigen_trainer_flow_term",
            "eigen_trainer_loss_grad_flow", "eigen_trainer_flow_term_ref", "eigen_trainer_loss_grad_flow_pair", "eigen_trainer_flow_term_pair",
-           "eigen_trainer_flow_term_score", "eigen_trainer_loss_grad_flow_score"]
+           "eigen_trainer_flow_term_score", "eigen_trainer_loss_grad_flow_score", "eigen_trainer_flow_term_structure",
+           "eigen_trainer_loss_grad_flow_structure", "eigen_trainer_debug_free_planes"]
 
 
 class EigenConfig(ctypes.Structure):

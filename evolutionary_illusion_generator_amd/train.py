@@ -27,6 +27,12 @@ class FlowScoreSettings(ctypes.Structure):
                 ("w_direction", ctypes.c_double), ("w_strength", ctypes.c_double), ("min_count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class FlowStructureSettings(ctypes.Structure):
+    """eigen_flow_structure_score"""
+    _fields_ = [("structure", ctypes.c_int32), ("min_count", ctypes.c_int32), ("max_norm", ctypes.c_double), ("min_norm", ctypes.c_double),
+                ("lim_lo", ctypes.c_double), ("lim_hi", ctypes.c_double), ("max_distance", ctypes.c_double), ("w", ctypes.c_double * 3)]
+
+
 class TrainerConfig(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_layers", ctypes.c_int32),
                 ("channels", ctypes.c_int32 * engine.MAX_LAYERS), ("max_batch", ctypes.c_int32), ("max_steps", ctypes.c_int32)]
@@ -45,7 +51,8 @@ _TERM = [_P, _P, _I64, _P, _I64, _I32, _P, _P, _P, ctypes.c_double, _P, _P, _P, 
 _ENTRIES = {(False, False): ("eigen_trainer_loss_grad_obj", ()), (False, True): ("eigen_trainer_loss_grad_frames", ("frame_grad",)),
             (True, "frame"): ("eigen_trainer_loss_grad_flow", ("frame_grad", "flow")),
             (True, "prediction"): ("eigen_trainer_loss_grad_flow_pair", ("frame_grad", "flow", "pairing")),
-            (True, "score"): ("eigen_trainer_loss_grad_flow_score", ("frame_grad", "flow", "pairing", "score"))}
+            (True, "score"): ("eigen_trainer_loss_grad_flow_score", ("frame_grad", "flow", "pairing", "score")),
+            (True, "structure"): ("eigen_trainer_loss_grad_flow_structure", ("frame_grad", "flow", "pairing", "score"))}
 
 
 def _bind(lib):
@@ -65,6 +72,9 @@ def _bind(lib):
     lib.eigen_trainer_loss_grad_flow_score.argtypes = _CALL + _OBJ + _FRAMEGRAD + _FLOW + [_I32, _P, _P]
     # t, d_pred, p_bstride, d_ref, d_fref, r_bstride, batch, flow, d_mask, score, scale, h_value, h_stats, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream
     lib.eigen_trainer_flow_term_score.argtypes = [_P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _P, ctypes.c_double, _P, _P, _P, _P, _I64, _P, _I64, _P]
+    lib.eigen_trainer_loss_grad_flow_structure.argtypes = lib.eigen_trainer_loss_grad_flow_score.argtypes
+    lib.eigen_trainer_flow_term_structure.argtypes = lib.eigen_trainer_flow_term_score.argtypes
+    lib.eigen_trainer_debug_free_planes.argtypes = [_P, _I32, _P, _P, _P, _P, _P, _P]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
@@ -125,6 +135,92 @@ class FlowScore:
         """eigen_flow_score against an image of height h"""
         lo, hi = self.limits if self.limits is not None else (0.0, h / 2.0)
         return FlowScoreSettings(self.max_norm, self.min_norm, lo, hi, self.weights[0], self.weights[1], self.min_count, 0)
+
+
+BANDS_STATS = ("N", "mean_x", "mean_y", "var_x", "spare4", "spare5", "spare6", "spare7", "score", "spare")  # one sample's record under a BandsScore
+FREE_STATS = ("N", "mean_abs_dx", "mean_norm", "var_norm", "swarm", "strength", "spare6", "spare7", "score", "spare")  # under a FreeScore
+
+
+def _check_norms_and_count(max_norm, min_norm, min_count):
+    """the rules the structure scores share -> (max_norm, min_norm, min_count)"""
+    max_norm, min_norm = float(max_norm), float(min_norm)
+    if not (np.isfinite(max_norm) and max_norm > 0):
+        raise ValueError("max_norm must be finite and > 0, got %r" % (max_norm,))
+    if not 0 <= min_norm < max_norm:
+        raise ValueError("min_norm must be in [0, max_norm = %r), got %r" % (max_norm, min_norm))
+    if isinstance(min_count, bool) or int(min_count) != min_count or int(min_count) < 1:
+        raise ValueError("min_count must be an integer >= 1, got %r" % (min_count,))
+    return max_norm, min_norm, int(min_count)
+
+
+class BandsScore:
+    """The Bands structure's score as the value of a flow term ("The structure scores"): the fitness's own
+    ``horizontal_symmetry_score`` on the dense field u of the stage's solve, per sample, and its mean over the samples.  A pixel is a
+    member when the objective's mask counts it, limits[0] <= y <= limits[1] and min_norm <= |u| <= max_norm.  With middle =
+    int(limits[1] / 2), a member above it stores (nx, nx) (the reference's quirk, kept) and one at or below it (-nx, ny), n = u / |u|;
+    the score is ((1 - var mx) + |mean mx| + (1 - |mean my|)) / 3.  A sample with fewer than min_count members scores 0 and passes no
+    gradient.  Membership is a constant of the graph.
+
+    The defaults are the reference's constants: max_norm 0.15 pixels, limits (0, (h / 4) * 2) (None: resolved against the trainer's
+    image), any vector at all (min_count 1).  min_norm is this build's floor, as ``FlowScore``'s.  ValueError: max_norm not finite or
+    <= 0, min_norm outside [0, max_norm), limits not finite, limits[1] < limits[0] or |limits[1]| > 2e9 (the middle is an int), min_count < 1."""
+
+    structure = 0
+    stats = BANDS_STATS
+
+    def __init__(self, max_norm=0.15, min_norm=1e-3, limits=None, min_count=1):
+        self.max_norm, self.min_norm, self.min_count = _check_norms_and_count(max_norm, min_norm, min_count)
+        if limits is not None:
+            limits = tuple(float(v) for v in limits)
+            if len(limits) != 2 or not all(np.isfinite(v) for v in limits) or not limits[0] <= limits[1] or abs(limits[1]) > 2e9:
+                raise ValueError("limits must be finite with limits[0] <= limits[1] and |limits[1]| <= 2e9, got %r" % (limits,))
+        self.limits = limits
+
+    def settings(self, h):
+        """eigen_flow_structure_score against an image of height h"""
+        lo, hi = self.limits if self.limits is not None else (0.0, (h / 4.0) * 2.0)
+        return FlowStructureSettings(self.structure, self.min_count, self.max_norm, self.min_norm, lo, hi, 0.0, (ctypes.c_double * 3)(0.0, 0.0, 0.0))
+
+
+class FreeScore:
+    """The Free structure's score as the value of a flow term ("The structure scores"): weights[0] times the
+    fitness's own ``swarm_score`` (its quirks kept: ``% 2 * pi`` and the arccos of the x component alone) plus weights[1] times
+    ``strength_number`` plus weights[2] times min(N, 15) / 15, on the dense field u of the stage's solve.  A pixel is a member when the
+    objective's mask counts it and min_norm <= |u| <= max_norm.  ``swarm_score`` is a sum over all ordered pairs of members nearer than
+    max_distance pixels, an N^2 pass per sample.  A sample with fewer than min_count members scores 0 and passes no gradient; the count
+    term is a constant of the graph, as membership is.
+
+    The defaults are the reference's constants: max_norm 0.4 pixels, max_distance 100, any vector at all (min_count 1), weights
+    (0.5, 0.1, 0.4).  ValueError: max_norm not finite or <= 0, min_norm outside [0, max_norm), max_distance not finite or <= 0,
+    min_count < 1, a weight that is negative or not finite, all weights zero."""
+
+    structure = 2
+    stats = FREE_STATS
+
+    def __init__(self, max_norm=0.4, min_norm=1e-3, max_distance=100.0, min_count=1, weights=(0.5, 0.1, 0.4)):
+        self.max_norm, self.min_norm, self.min_count = _check_norms_and_count(max_norm, min_norm, min_count)
+        max_distance = float(max_distance)
+        if not (np.isfinite(max_distance) and max_distance > 0 and np.isfinite(max_distance * max_distance) and max_distance * max_distance > 0):
+            raise ValueError("max_distance must be finite and > 0, got %r" % (max_distance,))
+        weights = tuple(float(v) for v in weights)
+        if len(weights) != 3 or not all(np.isfinite(v) and v >= 0 for v in weights) or not sum(weights) > 0:
+            raise ValueError("weights must be three finite values >= 0, not all zero, got %r" % (weights,))
+        self.max_distance, self.weights = max_distance, weights
+
+    def settings(self, h):
+        """eigen_flow_structure_score (the image's height plays no part)"""
+        return FlowStructureSettings(self.structure, self.min_count, self.max_norm, self.min_norm, 0.0, 0.0, self.max_distance, (ctypes.c_double * 3)(*self.weights))
+
+
+FLOW_SCORES = (FlowScore, BandsScore, FreeScore)
+
+
+def structure_score(structure, **kw):
+    """The score of a structure of the fitness (``fitness.StructureType`` or its number), with the class's defaults unless `kw` states
+    others: Bands -> ``BandsScore``, Free -> ``FreeScore``, Circles and CirclesFree -> ``FlowScore``.  ValueError: another structure."""
+    if isinstance(structure, bool) or int(structure) != structure or int(structure) not in (0, 1, 2, 3):
+        raise ValueError("structure must be 0 Bands, 1 Circles, 2 Free or 3 CirclesFree, got %r" % (structure,))
+    return {0: BandsScore, 1: FlowScore, 2: FreeScore, 3: FlowScore}[int(structure)](**kw)
 
 
 def flow_direction(kind, w, h):
@@ -205,10 +301,10 @@ class FlowObjective:
         self.scored(score)
 
     def scored(self, score):
-        """Set the score mode (a ``FlowScore``; None: the displacement modes) and return self.  ValueError: not a FlowScore, or a score on an
-        objective with a direction field."""
-        if score is not None and not isinstance(score, FlowScore):
-            raise ValueError("score must be a FlowScore or None, got %r" % (score,))
+        """Set the score mode (a ``FlowScore``, or a structure score: ``BandsScore``, ``FreeScore``; None: the displacement modes) and return
+        self.  ValueError: none of these, or a score on an objective with a direction field."""
+        if score is not None and not isinstance(score, FLOW_SCORES):
+            raise ValueError("score must be a FlowScore, a BandsScore, a FreeScore or None, got %r" % (score,))
         if score is not None and self.direction is not None:
             raise ValueError("a score takes no direction field")
         self.score = score
@@ -256,6 +352,13 @@ def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, re
     if reference != "constant":
         raise ValueError("the prediction pairing has no frame as a reference: reference=%r does not go with it" % (reference,))
     return PredictionFlow(radius, eps, direction, mask).scored(score)
+
+
+def _entry_key(flow):
+    """the key of _ENTRIES of a flow objective: its pairing, or the kind of its score"""
+    if flow.score is None:
+        return flow.pairing
+    return "score" if isinstance(flow.score, FlowScore) else "structure"
 
 
 def _check_flow(objective, flow):
@@ -523,7 +626,7 @@ class PredNetTrainer:
             if flow.score is not None:
                 sc = flow.score.settings(self.h)
                 tails["score"] = [ctypes.byref(sc)]
-        entry, groups = _ENTRIES[by_flow, ("score" if flow.score is not None else flow.pairing) if by_flow else frame_grads is not None]
+        entry, groups = _ENTRIES[by_flow, _entry_key(flow) if by_flow else frame_grads is not None]
         _check(getattr(self.lib, entry)(*args, *[a for g in groups for a in tails[g]], _stream_arg(stream)))
         if by_flow:
             self.last_flow_terms = terms[:T - 1]
@@ -623,7 +726,8 @@ class PredNetTrainer:
         if flow.score is not None:
             sc = flow.score.settings(self.h)
             rec = np.zeros((n, len(SCORE_STATS)), np.float64)
-            _check(self.lib.eigen_trainer_flow_term_score(self._h, _ptr(p), ctypes.c_int64(per), None if float_ref else _ptr(r), _ptr(r) if float_ref else None,
+            entry = self.lib.eigen_trainer_flow_term_score if isinstance(flow.score, FlowScore) else self.lib.eigen_trainer_flow_term_structure
+            _check(entry(self._h, _ptr(p), ctypes.c_int64(per), None if float_ref else _ptr(r), _ptr(r) if float_ref else None,
                                                           ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_mask), ctypes.byref(sc),
                                                           ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(rec), _ptr(u), _ptr(seed), ctypes.c_int64(per),
                                                           _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None))
@@ -640,6 +744,16 @@ class PredNetTrainer:
             _check(self.lib.eigen_trainer_flow_term(*args, None))
         out = (value.value, u.cpu().numpy(), seed.cpu().numpy())
         return out + (rg.cpu().numpy(),) if reference_grad else out
+
+    def free_planes(self, n):
+        """Debug (eigen_trainer_debug_free_planes): what the last stage under a ``FreeScore`` left of its pair pass, for the first n samples:
+        {"theta", "L": float64 [n, H, W]; "rowS", "colS": int32 [n, H, W]; "member": bool [n, H, W]}."""
+        shp = (int(n), self.h, self.w)
+        out = {"theta": np.zeros(shp, np.float64), "L": np.zeros(shp, np.float64), "rowS": np.zeros(shp, np.int32), "colS": np.zeros(shp, np.int32),
+               "member": np.zeros(shp, np.uint8)}
+        _check(self.lib.eigen_trainer_debug_free_planes(self._h, ctypes.c_int32(int(n)), *[_ptr(out[k]) for k in ("theta", "L", "rowS", "colS", "member")], None))
+        out["member"] = out["member"] != 0
+        return out
 
     def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False, layer_errors=False):
         """Forward only, no tape: the mean squared error of every step of frames uint8 [n, T, C, H, W], T of any length, as
@@ -952,4 +1066,4 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
 
 
 __all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update", "FlowObjective",
-           "PredictionFlow", "make_flow", "flow_direction", "FlowScore"]
+           "PredictionFlow", "make_flow", "flow_direction", "FlowScore", "BandsScore", "FreeScore", "structure_score"]

@@ -1,5 +1,8 @@
 """The --flow-* options of examples/refine_illusion.py, refine_genomes.py, evolve_illusion.py and scripts/train_bench.py, and the flow
-objective they state (train.make_flow).  The choices are those of train.FLOW_DIRECTIONS, FLOW_REFERENCES and FLOW_PAIRINGS; --flow-score and --flow-max-norm state a train.FlowScore."""
+objective they state (train.make_flow).  The choices are those of train.FLOW_DIRECTIONS, FLOW_REFERENCES and FLOW_PAIRINGS; --flow-score, --flow-score-structure and --flow-max-norm state a train.FlowScore, BandsScore or FreeScore."""
+
+SCORE_STRUCTURES = {"bands": 0, "circles": 1, "free": 2}   # --flow-score-structure -> the fitness's number of the structure
+
 
 FLOW_ARGUMENTS = {
     "direction": dict(default=None, choices=["tangent", "radial", "horizontal", "vertical"],
@@ -13,7 +16,11 @@ FLOW_ARGUMENTS = {
                          "predictions, as the population fitness printed here does; prediction takes --flow-reference constant only"),
     "score": dict(action="store_true", help="objective flow: climb the fitness's own Circles score of the dense field (train.FlowScore) in place of the "
                                              "displacement; it takes no --flow-direction"),
-    "max-norm": dict(type=float, default=0.3, help="--flow-score: vectors longer than this many pixels are no members (the fitness's own limit is 0.3)"),
+    "score-structure": dict(default="circles", choices=["circles", "bands", "free", "auto"],
+                            help="--flow-score: the structure whose score is climbed: circles (train.FlowScore), bands (train.BandsScore), free (train.FreeScore), "
+                                 "or auto, the script's own --structure"),
+    "max-norm": dict(type=float, default=None, help="--flow-score: vectors longer than this many pixels are no members (default: the fitness's own limit for the "
+                                                    "chosen structure, 0.3 circles, 0.15 bands, 0.4 free)"),
 }
 
 
@@ -23,11 +30,28 @@ def add_flow_arguments(ap, names=tuple(FLOW_ARGUMENTS), **own):
         ap.add_argument("--flow-" + name, **dict(FLOW_ARGUMENTS[name], **own.get(name, {})))
 
 
+def score_of(a):
+    """the score of the command line: None without --flow-score; else the class of --flow-score-structure (auto: of a.structure), with
+    --flow-max-norm where it is given"""
+    from evolutionary_illusion_generator_amd import train
+    if not getattr(a, "flow_score", False):
+        return None
+    which = getattr(a, "flow_score_structure", "circles")
+    if which == "auto":
+        if getattr(a, "structure", None) is None:
+            raise ValueError("--flow-score-structure auto needs a --structure")
+        structure = int(a.structure)
+    else:
+        structure = SCORE_STRUCTURES[which]
+    max_norm = getattr(a, "flow_max_norm", None)
+    return train.structure_score(structure, **({} if max_norm is None else {"max_norm": max_norm}))
+
+
 def flow_of(a, w, h, mask=None):
     """the FlowObjective of the command line (None under another objective); the term counts the pixels of `mask`"""
     from evolutionary_illusion_generator_amd import train
     if a.objective != "flow":
         return None
-    score = train.FlowScore(max_norm=a.flow_max_norm) if getattr(a, "flow_score", False) else None
+    score = score_of(a)
     return train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask,
                            reference=a.flow_reference, score=score)

@@ -547,6 +547,54 @@ int eigen_trainer_loss_grad_flow_score(eigen_trainer* t, const uint8_t* d_frames
                                        int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
                                        const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score, void* stream);
 
+/* The structure scores of EIGEN_OBJ_FLOW ("The structure scores"; csrc/flow_struct_kernels.h fixes every order):
+ * the value of a term is the population fitness's score of the Bands structure (0: horizontal_symmetry_score) or of the Free structure
+ * (2: 0.5 swarm_score + 0.1 strength_number + 0.4 min(n, 15) / 15), on the dense field u of eigen_trainer_flow_term's solve, which is
+ * unchanged.  Structures 1 and 3 (Circles, CirclesFree) are the score mode's, eigen_flow_score.  Float64 on the device.  Common:
+ *   nrm = sqrt(ux ux + uy uy); member: the mask counts the pixel, the structure's rule holds, nrm > 0, min_norm <= nrm <= max_norm, a
+ *   constant of the graph; nx = ux / nrm, ny = uy / nrm; a sample with N < min_count members has S_b = 0 and passes no gradient;
+ *   value f = (sum_b S_b) / batch; kappa = scale / batch; q from g = d S_b / d u as in the score mode, 0 off the members.
+ * Bands: rule lim_lo <= y <= lim_hi, middle = (int)(lim_hi / 2); y < middle: (mx, my) = (nx, nx), else (-nx, ny); two passes:
+ *   m_x, m_y, then V = mean (mx - m_x)^2; S_b = ((1 - V) + |m_x| + (1 - |m_y|)) / 3.  max_distance and w are not read.
+ * Free: no rule; theta = acos(nx); over ordered pairs of members (i, j), i = j included: f = min(d2 / (max_distance max_distance), 1),
+ *   close iff f < 1, opt = fmod(theta_i + f pi, 2) pi, L_i = sum_j close |theta_j - opt|, swarm = mean_i (pi - L_i / N) / pi;
+ *   A = mean |ux| / max_norm, F = 1 - min(var nrm, 1); S_b = (w[0] swarm + w[1] (A F)) + w[2] (min(N, 15) / 15).  The limits are not read.
+ * The record of a sample, double[10]: Bands N, m_x, m_y, V, 0, 0, 0, 0, S_b, 0; Free N, m_a, m_n, V_n, swarm, A F, 0, 0, S_b, 0. */
+typedef struct {
+    int32_t structure, min_count; /* 0 Bands, 2 Free; min_count >= 1: a sample with fewer members scores 0 */
+    double max_norm, min_norm, lim_lo, lim_hi, max_distance, w[3];
+} eigen_flow_structure_score;
+
+/* The flow stage alone under a structure score: eigen_trainer_flow_term_score's arguments with the structure score in place of the
+ * score; h_stats (host, may be NULL) receives double[batch][10], the records above.
+ * Errors: as eigen_trainer_flow_term_score; EIGEN_ERR_INVALID, before any launch: a NULL score, structure 1 or 3 (the message names
+ * eigen_flow_score) or unknown, max_norm not finite or <= 0, min_norm outside [0, max_norm), min_count < 1; Bands: limits not finite,
+ * lim_hi < lim_lo or |lim_hi| > 2e9 (middle is an int); Free: max_distance not finite or <= 0, a weight that is negative or not finite, all weights zero. */
+int eigen_trainer_flow_term_structure(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref,
+                                      int64_t r_bstride, int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask,
+                                      const eigen_flow_structure_score* score, double scale, double* h_value, double* h_stats, double* d_flow,
+                                      float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream);
+
+/* Debug: what the last Free stage of this handle (eigen_trainer_flow_term_structure, or the last computed term of a training call) left in
+ * the workspace of its pair pass, copied to the host; every target may be NULL, each is [batch][H][W]: theta = acos(nx) and the member
+ * flag of every pixel (0 off the members), L_i, and the integer sign sums rowS_i and colS_i.  No kernel is launched.  Before any Free
+ * stage the planes hold nothing defined.  Errors: EIGEN_ERR_INVALID a NULL handle or a batch outside 1 .. max_batch. */
+int eigen_trainer_debug_free_planes(eigen_trainer* t, int32_t batch, double* h_theta, double* h_L, int32_t* h_rowS, int32_t* h_colS,
+                                    uint8_t* h_flag, void* stream);
+
+/* eigen_trainer_loss_grad_flow_pair plus the structure score.  score == NULL: the call IS eigen_trainer_loss_grad_flow_pair, launch for
+ * launch and bit for bit.  Otherwise (objective EIGEN_OBJ_FLOW only, d_dir NULL) every computed term is the value of
+ * eigen_trainer_flow_term_structure under the call's pairing, with kappa = (w_s / sum w) / batch; the moving reference under the frame
+ * pairing works as without a score.
+ * Errors: as eigen_trainer_loss_grad_flow_pair and eigen_trainer_flow_term_structure; EIGEN_ERR_INVALID a structure score under another
+ * objective or together with a direction field. */
+int eigen_trainer_loss_grad_flow_structure(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                           int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                           const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                           int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                           const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_structure_score* score,
+                                           void* stream);
+
 /* One normalised ascent step on uint8 stills d_images [batch][C][H][W], in place, from a tied gradient (image b at d_grad + b *
  * g_bstride floats): per image m_b = max |g| over the pixels the mask keeps free, then x = byte / 255.0f,
  * x' = min(max(x + k * (g / m_b), 0), 1) with k = (float)(step_bytes / 255.0), byte' = (uint8_t)(int)(x' * 255.0f + 0.5f), each one

@@ -6,7 +6,7 @@ the tape-free evaluate of that call.  Prints one JSON line per side and writes p
     python scripts/train_bench.py [--steps 5] [--warmup 2] [--side trainer|torch|both] [--objective mse|l0|lall]
     python scripts/train_bench.py --frame-grads [--steps 5] [--warmup 2]
     python scripts/train_bench.py --flow-cost [--steps 5] [--warmup 2] [--flow-reference constant|moving] [--flow-pairing frame|prediction]
-        [--flow-score [--flow-max-norm 0.3]]
+        [--flow-score [--flow-score-structure circles|bands|free] [--flow-max-norm M]]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
 side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
@@ -32,7 +32,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from examples.flow_args import add_flow_arguments  # noqa: E402
+from examples.flow_args import add_flow_arguments, score_of  # noqa: E402
 
 W, H, CH, B, T = 160, 120, [3, 48, 96, 192], 16, 10
 GATES = ("i", "f", "c", "o")
@@ -251,7 +251,7 @@ def main():
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
     ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall", "flow"], help="the trainer side's objective")
     ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
-    add_flow_arguments(ap, ("reference", "pairing", "score", "max-norm"), reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
+    add_flow_arguments(ap, ("reference", "pairing", "score", "score-structure", "max-norm"), **{"score-structure": dict(choices=["circles", "bands", "free"])}, reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
                        pairing=dict(help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)"))
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
@@ -259,10 +259,7 @@ def main():
     a = ap.parse_args()
     if a.flow_pairing == "prediction" and a.flow_reference == "moving":
         ap.error("--flow-pairing prediction has no frame as a reference: it does not take --flow-reference moving")
-    score = None
-    if a.flow_score:
-        from evolutionary_illusion_generator_amd.train import FlowScore
-        score = FlowScore(max_norm=a.flow_max_norm)
+    score = score_of(a)
     if a.side == "torch":
         print(json.dumps(run_torch(a.steps, a.warmup)))
         return
