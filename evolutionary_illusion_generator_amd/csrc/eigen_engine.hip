@@ -1445,9 +1445,9 @@ int eigen_flatten_genomes(int32_t G, int32_t n_in, const int32_t* in_keys, int32
     return EIGEN_OK;
 }
 
-// Host-only: the launches of one PredNet step as prednet_run issues them, planned by the same two functions (conv_plan.h) with every switch at its default.
-int eigen_plan_text(int32_t n_layers, const int32_t* channels, int32_t width, int32_t height, int32_t batch, int32_t n_cu, int32_t wino_mask, int32_t step0,
-                    char* out, int32_t cap)
+// Host-only: the launches of one PredNet step as prednet_run issues them, planned by the same two functions (conv_plan.h) under the switches `sw` and the mask `mask`.
+static int plan_text(int32_t n_layers, const int32_t* channels, int32_t width, int32_t height, int32_t batch, int32_t n_cu, int mask, int32_t step0, const Switches& sw,
+                     char* out, int32_t cap)
 {
     const int L = n_layers;
     if (!channels || !out || cap < 1) return fail(EIGEN_ERR_INVALID, "null argument");
@@ -1456,9 +1456,8 @@ int eigen_plan_text(int32_t n_layers, const int32_t* channels, int32_t width, in
     if (batch < 1 || n_cu < 1) return fail(EIGEN_ERR_INVALID, "batch and n_cu must be >= 1");
     int C[EIGEN_MAX_LAYERS], H[EIGEN_MAX_LAYERS], W[EIGEN_MAX_LAYERS];
     for (int l = 0; l < L; ++l) { C[l] = channels[l]; H[l] = height >> l; W[l] = width >> l; if (C[l] < 1) return fail(EIGEN_ERR_INVALID, "channels[%d] < 1", l); }
-    const Switches sw;   // the default path: the environment is not read
     LayerPlan plan[EIGEN_MAX_LAYERS];
-    plan_prednet(L, C, H, W, wino_mask < 0 ? EIGEN_WINO_DEFAULT : wino_mask, sw, plan);
+    plan_prednet(L, C, H, W, mask, sw, plan);
     std::string text;
     auto line = [&](const char* name, const OpDesc& op, bool up_src, bool acc_init) {
         const LaunchPlan p = plan_launch(op, batch, n_cu, up_src, acc_init, sw);
@@ -1479,6 +1478,23 @@ int eigen_plan_text(int32_t n_layers, const int32_t* channels, int32_t width, in
     }
     snprintf(out, (size_t)cap, "%s", text.c_str());
     return (int)text.size();
+}
+
+// every switch at its default: the environment is not read
+int eigen_plan_text(int32_t n_layers, const int32_t* channels, int32_t width, int32_t height, int32_t batch, int32_t n_cu, int32_t wino_mask, int32_t step0,
+                    char* out, int32_t cap)
+{
+    return plan_text(n_layers, channels, width, height, batch, n_cu, wino_mask < 0 ? EIGEN_WINO_DEFAULT : wino_mask, step0, Switches(), out, cap);
+}
+
+// w4 = {w4_tall, w4_half, w4_pack, w4_parts} over the defaults; NULL: what THIS process launches -- switches(), and wino_mask < 0 its effective mask
+int eigen_plan_text_sw(int32_t n_layers, const int32_t* channels, int32_t width, int32_t height, int32_t batch, int32_t n_cu, int32_t wino_mask, int32_t step0,
+                       const int32_t* w4, char* out, int32_t cap)
+{
+    if (!w4) return plan_text(n_layers, channels, width, height, batch, n_cu, wino_mask < 0 ? wino_mask_env() : wino_mask, step0, switches(), out, cap);
+    Switches sw;
+    sw.w4_tall = w4[0]; sw.w4_half = w4[1]; sw.w4_pack = w4[2]; sw.w4_parts = w4[3];
+    return plan_text(n_layers, channels, width, height, batch, n_cu, wino_mask < 0 ? EIGEN_WINO_DEFAULT : wino_mask, step0, sw, out, cap);
 }
 
 int eigen_test_det_math(eigen_engine* e, const float* d_x, int32_t n, float* d_exp, float* d_sig, float* d_tanh, void* stream)

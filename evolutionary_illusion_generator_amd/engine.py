@@ -19,7 +19,7 @@ PAIR_POPULATION, PAIR_SINGLE = 0, 1
 EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eigen_last_error", "eigen_config_defaults", "eigen_create", "eigen_destroy",
            "eigen_set_prednet_weights", "eigen_set_grid", "eigen_render_cppn", "eigen_eval_cppn_nodes", "eigen_prednet_rollout", "eigen_prednet_sequence", "eigen_flow",
            "eigen_score", "eigen_eval_population", "eigen_eval_images", "eigen_test_conv", "eigen_time_conv", "eigen_test_det_math",
-           "eigen_get_timings", "eigen_conv_profile", "eigen_debug_corners", "eigen_debug_dense_flow", "eigen_debug_state", "eigen_prednet_flops_per_step", "eigen_flatten_genomes", "eigen_plan_text",
+           "eigen_get_timings", "eigen_conv_profile", "eigen_debug_corners", "eigen_debug_dense_flow", "eigen_debug_state", "eigen_prednet_flops_per_step", "eigen_flatten_genomes", "eigen_plan_text", "eigen_plan_text_sw",
            "eigen_trainer_create", "eigen_trainer_destroy", "eigen_trainer_set_weights", "eigen_trainer_get_weights", "eigen_trainer_loss_grad",
            "eigen_trainer_get_grads", "eigen_trainer_adam", "eigen_trainer_tape_bytes", "eigen_trainer_loss_grad_ext", "eigen_trainer_evaluate",
            "eigen_trainer_get_state", "eigen_trainer_set_state", "eigen_trainer_loss_grad_obj", "eigen_trainer_evaluate_err",
@@ -107,14 +107,26 @@ def _stream_arg(stream):
     return ctypes.c_void_p(int(getattr(stream, "cuda_stream", stream)))
 
 
-def plan_text(channels, width, height, batch, n_cu=256, wino_mask=-1, step0=False):
-    """The launches of one PredNet step as the library plans them (eigen_plan_text: host-only, default switches; wino_mask < 0: the built-in default):
-    one dict per launch, in launch order -- op, kernel, shape as strings, every other field an int."""
+W4_SWITCHES = ("w4_tall", "w4_half", "w4_pack", "w4_parts")   # csrc/conv_plan.h: Switches (EIGEN_W4_TALL / _HALF / _PACK / _PARTS)
+W4_DEFAULTS = {"w4_tall": -1, "w4_half": -1, "w4_pack": -1, "w4_parts": 0}
+
+
+def plan_text(channels, width, height, batch, n_cu=256, wino_mask=-1, step0=False, switches=W4_DEFAULTS):
+    """The launches of one PredNet step as the library plans them (host-only): one dict per launch, in launch order -- op, kernel, shape as strings, every
+    other field an int.  switches: the Winograd shape switches, a dict over W4_DEFAULTS (the default: eigen_plan_text, the environment is not read; wino_mask < 0:
+    the built-in default), or None: what THIS process launches -- its EIGEN_* environment, and wino_mask < 0 its effective mask (eigen_plan_text_sw)."""
     lib = load_library()
     ch = (ctypes.c_int32 * len(channels))(*channels)
     buf = ctypes.create_string_buffer(1 << 16)
-    n = lib.eigen_plan_text(ctypes.c_int32(len(channels)), ch, ctypes.c_int32(width), ctypes.c_int32(height), ctypes.c_int32(batch), ctypes.c_int32(n_cu),
-                            ctypes.c_int32(wino_mask), ctypes.c_int32(int(step0)), buf, ctypes.c_int32(len(buf)))
+    head = (ctypes.c_int32(len(channels)), ch, ctypes.c_int32(width), ctypes.c_int32(height), ctypes.c_int32(batch), ctypes.c_int32(n_cu),
+            ctypes.c_int32(wino_mask), ctypes.c_int32(int(step0)))
+    if switches is W4_DEFAULTS:
+        n = lib.eigen_plan_text(*head, buf, ctypes.c_int32(len(buf)))
+    else:
+        if switches is not None and set(switches) - set(W4_SWITCHES):
+            raise ValueError("plan_text: unknown switches %s" % sorted(set(switches) - set(W4_SWITCHES)))
+        w4 = None if switches is None else (ctypes.c_int32 * 4)(*[int(switches.get(k, W4_DEFAULTS[k])) for k in W4_SWITCHES])
+        n = lib.eigen_plan_text_sw(*head, w4, buf, ctypes.c_int32(len(buf)))
     _check(min(n, 0))
     if n >= len(buf):
         raise EngineError("eigen_plan_text: the plan has %d characters, the buffer %d" % (n, len(buf)))

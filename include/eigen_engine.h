@@ -261,6 +261,12 @@ int eigen_gate_order(void);
 int eigen_plan_text(int32_t n_layers, const int32_t* channels, int32_t width, int32_t height, int32_t batch, int32_t n_cu,
                     int32_t wino_mask, int32_t step0, char* out, int32_t cap);
 
+/* eigen_plan_text under given Winograd shape switches (same text, same return value): w4 = {EIGEN_W4_TALL, EIGEN_W4_HALF, EIGEN_W4_PACK, EIGEN_W4_PARTS} as
+ * csrc/conv_plan.h reads them (-1, -1, -1, 0: the defaults, eigen_plan_text's plan), every other switch at its default.  w4 == NULL: what THIS process will launch --
+ * every switch as the process read it from its environment, and wino_mask < 0 the mask eigen_winograd_mask reports. */
+int eigen_plan_text_sw(int32_t n_layers, const int32_t* channels, int32_t width, int32_t height, int32_t batch, int32_t n_cu,
+                       int32_t wino_mask, int32_t step0, const int32_t* w4, char* out, int32_t cap);
+
 /* The EFFECTIVE operator-form mask of this process (csrc/eigen_engine.hip: EIGEN_WINOGRAD with EIGEN_WINO_FUSEUP=0 folded in as a cleared bit 24): which 3x3
  * convolutions run in which canonical summation order.  Every rank of a multi-GPU run must report the same value -- a population scored
  * under two orders still looks valid (bench.py gathers it).  The CPU oracle's oracle.wino_mask_default() states the same rule. */

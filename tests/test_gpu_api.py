@@ -230,7 +230,9 @@ print("FRAMES", *out)
 def test_specialised_operators_equal_the_general_mfma_path(cuda):
     """Every A/B switch of the engine that must NOT change a bit (step-0 operators, single-K-block ConvA, one-block 2x2 pass, the two direct image-layer
     kernels, the eight-wave direct ConvA, the tile order, how many N-blocks of a tile a block of the F(4x4) kernel walks, its block shape) set one at a time in a fresh process: all
-    six PredNet frames of three small roll-outs are byte-identical."""
+    six PredNet frames of three small roll-outs are byte-identical.  At these shapes every F(4x4) launch is half, tall or packed by default, and such blocks do not walk
+    (csrc/conv_plan.h: plan_launch): EIGEN_W4_PARTS = 1 / 2 / 99 change no launch here -- the runs show that the switch is read without harm, no more; EIGEN_W4_HALF=0 gives wide blocks
+    of one N-block each.  The walking wide forms are tests/test_gpu_wino_wide.py's."""
     import subprocess
     script = _FRAMES_SCRIPT % {"root": ROOT}
 

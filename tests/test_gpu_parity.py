@@ -464,8 +464,9 @@ def test_winograd_operators_frames_bit_exact(cuda, oracle_lib, switch):
     source, the 20 x 15 top layer of 160 x 120 (odd height), N-blocks of 48 and 64 columns.
     None = THE DEFAULT (0x0FFFFFFE): every eligible ConvLSTM / ConvA / ConvP as Winograd F(4x4, 3x3) on the twelve-wave kernel (csrc/conv_wino4.h), the unpooled source
     inside the ConvLSTM's chains -- launches this small do not walk, and the block shape is picked per operator by map size (these roll-outs include 80 x 60 and 40 x 30
-    maps, which take the tall shape, and a 20 x 15 one, which does not); "parts=1": the same with a block of that kernel walking ALL N-blocks of its tile (EIGEN_W4_PARTS: the
-    launch geometry must not show in a single bit; test_specialised_operators... covers 2 / 99 and the forced shapes on other roll-outs); "tall=1": every F(4x4) operator on
+    maps, which take the tall shape, and a 20 x 15 one, which does not); "parts=1": EIGEN_W4_PARTS=1, which asks for one block per tile walking ALL its N-blocks -- but only
+    wide blocks walk, and every F(4x4) launch of these six roll-outs is half, tall or packed by default (csrc/conv_plan.h: plan_launch), so at these shapes the setting changes no launch:
+    it is a second run of the default (tests/test_wino_wide_host.py pins that; the walking wide forms are tests/test_gpu_wino_wide.py's); "tall=1": every F(4x4) operator on
     32 x 16-pixel blocks (EIGEN_W4_TALL); "half=1": every F(4x4) operator on 8 x 32-pixel half blocks (EIGEN_W4_HALF; the shape of launches smaller than one block per compute unit:
     twelve waves with the N-tiles split for 64-column ConvLSTMs / ConvPs, six waves otherwise); "pack=0": no packed tiles (EIGEN_W4_PACK: by default the ConvLSTM and the
     ConvP of a 20 x 15 or 16 x 16 top layer run on main + edge half blocks -- the 160 x 120 roll-out, three images = an edge block with one image missing, and the

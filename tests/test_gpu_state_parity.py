@@ -141,7 +141,8 @@ def _start_child(switch, oracle_dir):
 
 @pytest.mark.parametrize("switch", ss.SWITCHES)
 def test_state_of_every_layer_bit_exact(cuda, oracle_dir, switch):
-    """Six roll-outs x this switch setting (what each setting forces: test_winograd_operators_frames_bit_exact): the sequence of 4 fed + 2 self-fed
+    """Six roll-outs x this switch setting (what each setting forces: test_winograd_operators_frames_bit_exact; "parts=1" changes no launch at these shapes,
+    whose F(4x4) blocks are all half, tall or packed and do not walk -- test_wino_wide_host.py pins it, test_gpu_wino_wide.py runs the walking wide forms): the sequence of 4 fed + 2 self-fed
     steps runs in pieces -- reset / 1 step, then 1, 2 and the 2 self-fed steps on the kept state -- and R_l, c_l, P_l, E_l of every layer and
     image after each piece equal the oracle's state after steps 1 (the step-0 operators alone), 2, 4 (E_0 live) and 6 (E_0 exactly zero), as do
     the frames; one call over the whole sequence leaves the state of the pieces.  Dense weights under every setting; under the default also
