@@ -11,6 +11,9 @@
 // L2): corner response uses an LDS-staged derivative tile, corner selection is one workgroup per image with a
 // wavefront-reduced arg-max, the tracker is one wavefront per feature with the 15x15 window spread over lanes
 // and int64 wave reductions.
+//
+// The kernels are static: the engine unit and the trainer unit (flow_corner_kernels.h, which launches the three corner kernels) both
+// include this header, and each unit then holds kernels and host handles of its own; a kernel a unit does not launch is not emitted.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,7 +30,7 @@ __device__ __forceinline__ int reflect101(int i, int n)
 }
 
 // ---- cvtColor(BGR2GRAY), 8u, OpenCV 4.x 15-bit fixed point ----
-__global__ void gray_kernel(const uint8_t* img, long long bstride, int C, int HW, uint8_t* gray, int B)
+static __global__ void gray_kernel(const uint8_t* img, long long bstride, int C, int HW, uint8_t* gray, int B)
 {
     const int b = blockIdx.y;
     const uint8_t* src = img + (size_t)b * bstride;
@@ -40,7 +43,7 @@ __global__ void gray_kernel(const uint8_t* img, long long bstride, int C, int HW
 }
 
 // ---- pyrDown, 8u: [1 4 6 4 1]^2 / 256, (s + 128) >> 8, REFLECT_101 ----
-__global__ void pyrdown_kernel(const uint8_t* src, int H, int W, uint8_t* dst, int Hd, int Wd)
+static __global__ void pyrdown_kernel(const uint8_t* src, int H, int W, uint8_t* dst, int Hd, int Wd)
 {
     const int b = blockIdx.y;
     const uint8_t* s = src + (size_t)b * H * W;
@@ -68,7 +71,7 @@ __global__ void pyrdown_kernel(const uint8_t* src, int H, int W, uint8_t* dst, i
 // 16x16 outputs per block; Sobel derivatives of the (16+block-1)^2 neighbourhood staged in LDS as ints.
 constexpr int EIG_T = 16;
 constexpr int EIG_MAXB = 9;  // largest supported blockSize
-__global__ void __launch_bounds__(256) mineig_kernel(const uint8_t* gray, int H, int W, int block, float SC, float* eig)
+static __global__ void __launch_bounds__(256) mineig_kernel(const uint8_t* gray, int H, int W, int block, float SC, float* eig)
 {
     __shared__ int sdx[(EIG_T + EIG_MAXB - 1) * (EIG_T + EIG_MAXB - 1)];
     __shared__ int sdy[(EIG_T + EIG_MAXB - 1) * (EIG_T + EIG_MAXB - 1)];
@@ -120,7 +123,7 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     return v;
 }
 
-__global__ void __launch_bounds__(1024) corner_select_kernel(const float* eig, int H, int W, double quality, float min_dist, int max_corners,
+static __global__ void __launch_bounds__(1024) corner_select_kernel(const float* eig, int H, int W, double quality, float min_dist, int max_corners,
                                                              unsigned long long* cand /*[B][H*W]*/, float* corners /*[B][K][2]*/, int* ncorners)
 {
     __shared__ unsigned long long red[16];
@@ -202,7 +205,7 @@ __global__ void __launch_bounds__(1024) corner_select_kernel(const float* eig, i
 }
 
 // ---- calcSharrDeriv: int16 (dx, dy), REFLECT_101 ----
-__global__ void scharr_kernel(const uint8_t* gray, int H, int W, short2* deriv)
+static __global__ void scharr_kernel(const uint8_t* gray, int H, int W, short2* deriv)
 {
     const int b = blockIdx.y;
     const uint8_t* g = gray + (size_t)b * H * W;
@@ -245,7 +248,7 @@ __device__ __forceinline__ long long wave_sum_i64(long long v)
 #define EIG_DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
 
 // LKTrackerInvoker: one wavefront per feature, window positions spread over lanes (<= 4 per lane, win <= 16)
-__global__ void __launch_bounds__(64) lk_track_kernel(const LKArgs a)
+static __global__ void __launch_bounds__(64) lk_track_kernel(const LKArgs a)
 {
     const int f = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
     if (f >= a.ncorners[b]) return;
@@ -377,7 +380,7 @@ __global__ void __launch_bounds__(64) lk_track_kernel(const LKArgs a)
 }
 
 // vectors [x0, y0, x1-x0, y1-y0] for status == 1, in feature order; one 128-thread block per image (K <= 128)
-__global__ void __launch_bounds__(128) compact_vectors_kernel(const float* corners, const float* next_pts, const uint8_t* status,
+static __global__ void __launch_bounds__(128) compact_vectors_kernel(const float* corners, const float* next_pts, const uint8_t* status,
                                                               const int* ncorners, int K, float* vectors, int* counts)
 {
     __shared__ int s_pos[128];

@@ -67,9 +67,10 @@ __global__ void __launch_bounds__(EW_T) tflow_prep_kernel(const float* __restric
 //   a = Gxx + eps, c = Gyy + eps, b = Gxy, det = a c - b b, ux = -((c bx - b by) / det), uy = -((a by - b bx) / det)
 //   value v = ux ux + uy uy (dir == nullptr) or dx ux + dy uy (dir float [2][H][W]); mv = v where the mask byte is not 0 (mask nullptr: all), else 0
 //   g = (2 ux, 2 uy) or d; q = ((c gx - b gy) / det, (a gy - b gx) / det) where the mask counts, else 0
-// q [2][n], mv [n]; flow (may be null) [B][2][H][W].
+// q [2][n], mv [n]; flow (may be null) [B][2][H][W].  The mask byte of sample b, pixel p is mask[b * mask_bstride + p]: stride 0 is one plane
+// shared by the batch.
 __global__ void __launch_bounds__(FLOW_T) tflow_solve_kernel(const double* __restrict__ planes, long long n, int H, int W, int r, double eps,
-                                                             const float* __restrict__ dir, const uint8_t* __restrict__ mask, double* __restrict__ q,
+                                                             const float* __restrict__ dir, const uint8_t* __restrict__ mask, long long mask_bstride, double* __restrict__ q,
                                                              double* __restrict__ mv, double* __restrict__ flow)
 {
     __shared__ double rs[5][FLOW_ROWS][FLOW_TILE];
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__(FLOW_T) tflow_solve_kernel(const double* __res
         gx = 2.0 * ux; gy = 2.0 * uy;
         v = ux * ux + uy * uy;
     }
-    const bool counted = !mask || mask[p] != 0;
+    const bool counted = !mask || mask[(long long)blockIdx.z * mask_bstride + p] != 0;
     mv[base + p] = counted ? v : 0.0;
     q[base + p] = counted ? (c * gx - b * gy) / det : 0.0;
     q[n + base + p] = counted ? (a * gy - b * gx) / det : 0.0;

@@ -69,7 +69,7 @@ __device__ __forceinline__ TScorePoint tflow_score_point(double ux, double uy, i
 // ascending order, then a fixed LDS tree (the pattern of tloss_step_partial_kernel).  PASS 1: N, rho, tau, |ux|, nrm; PASS 2, with the
 // means of rec: (rho - m_rho)^2, (tau - m_tau)^2, (nrm - m_n)^2.  u [B][2][H][W]; consecutive lanes read consecutive doubles.
 template <int PASS>
-__global__ void __launch_bounds__(EW_T) tflow_score_moment_kernel(const double* __restrict__ u, int H, int W, const uint8_t* __restrict__ mask, TFlowScore s,
+__global__ void __launch_bounds__(EW_T) tflow_score_moment_kernel(const double* __restrict__ u, int H, int W, const uint8_t* __restrict__ mask, long long mask_bstride, TFlowScore s,
                                                                   const double* __restrict__ rec, double* __restrict__ part)
 {
     constexpr int K = PASS == 1 ? 5 : 3;
@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(EW_T) tflow_score_moment_kernel(const double* 
     for (long long p = (long long)blockIdx.x * EW_T + threadIdx.x; p < HW; p += (long long)SCORE_SLICES * EW_T) {
         const int y = (int)(p / W), x = (int)(p - (long long)y * W);
         const double vx = ux[p], vy = uy[p];
-        const TScorePoint o = tflow_score_point(vx, vy, x, y, H, W, !mask || mask[p] != 0, s);
+        const TScorePoint o = tflow_score_point(vx, vy, x, y, H, W, !mask || mask[b * mask_bstride + p] != 0, s);
         if (!o.member) continue;
         if (PASS == 1) {
             acc[0] += 1.0; acc[1] += o.rho; acc[2] += o.tau; acc[3] += fabs(vx); acc[4] += o.nrm;
@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(64) tflow_score_final_kernel(const double* __r
 // first, offsets ascending, each sum started from its first term), so a, b, c and det are the solve's bits; g is the header's gradient
 // from u and the sample's record.  q [2][n] replaces what the solve wrote there.
 __global__ void __launch_bounds__(FLOW_T) tflow_score_q_kernel(const double* __restrict__ planes, const double* __restrict__ u, long long n, int H, int W, int r,
-                                                               double eps, const uint8_t* __restrict__ mask, TFlowScore s, const double* __restrict__ rec,
+                                                               double eps, const uint8_t* __restrict__ mask, long long mask_bstride, TFlowScore s, const double* __restrict__ rec,
                                                                double* __restrict__ q)
 {
     __shared__ double rs[3][FLOW_ROWS][FLOW_TILE];
@@ -197,7 +197,7 @@ __global__ void __launch_bounds__(FLOW_T) tflow_score_q_kernel(const double* __r
     const double ux = u[2 * base + p], uy = u[2 * base + HW + p];
     const double* R = rec + (long long)blockIdx.z * SCORE_REC;
     const double N = R[0], m_rho = R[1], m_tau = R[2], m_a = R[3], m_n = R[4], Vr = R[5], Vt = R[6], Vn = R[7];
-    const TScorePoint o = tflow_score_point(ux, uy, x, y, H, W, !mask || mask[p] != 0, s);
+    const TScorePoint o = tflow_score_point(ux, uy, x, y, H, W, !mask || mask[(long long)blockIdx.z * mask_bstride + p] != 0, s);
     double qx = 0.0, qy = 0.0;
     if (o.member && !(N < (double)s.min_count)) {
         const double c_rho = -(((s.w_direction * (1.0 - Vr)) * (2.0 * (o.rho - m_rho))) / N);

@@ -72,13 +72,13 @@ __device__ __forceinline__ TStructPoint tflow_struct_point(double ux, double uy,
 __device__ __forceinline__ double tflow_sign(double v) { return v > 0.0 ? 1.0 : v < 0.0 ? -1.0 : 0.0; }
 
 // theta and the member flag of every pixel of the Free structure; n = B H W, u [B][2][H][W]
-__global__ void __launch_bounds__(EW_T) tflow_free_prepare_kernel(const double* __restrict__ u, long long n, int H, int W, const uint8_t* __restrict__ mask, TFlowStruct s,
+__global__ void __launch_bounds__(EW_T) tflow_free_prepare_kernel(const double* __restrict__ u, long long n, int H, int W, const uint8_t* __restrict__ mask, long long mask_bstride, TFlowStruct s,
                                                                   double* __restrict__ theta, uint8_t* __restrict__ flag)
 {
     const long long i = (long long)blockIdx.x * EW_T + threadIdx.x;
     if (i >= n) return;
     const long long HW = (long long)H * W, b = i / HW, p = i - b * HW;
-    const TStructPoint o = tflow_struct_point<STRUCT_FREE>(u[2 * b * HW + p], u[2 * b * HW + HW + p], 0, !mask || mask[p] != 0, s);
+    const TStructPoint o = tflow_struct_point<STRUCT_FREE>(u[2 * b * HW + p], u[2 * b * HW + HW + p], 0, !mask || mask[b * mask_bstride + p] != 0, s);
     theta[i] = o.member ? acos(o.nx) : 0.0;
     flag[i] = o.member ? 1 : 0;
 }
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(EW_T) tflow_free_prepare_kernel(const double* 
 // ascending order, then a fixed LDS tree (the pattern of tflow_score_moment_kernel).  Bands pass 1: N, mx, my; pass 2: (mx - m_x)^2.
 // Free pass 1: N, |ux|, nrm; pass 2: (nrm - m_n)^2, (pi - L / N) / pi with L [B][H W] of the pair kernel.
 template <int STRUCT, int PASS>
-__global__ void __launch_bounds__(EW_T) tflow_struct_moment_kernel(const double* __restrict__ u, int H, int W, const uint8_t* __restrict__ mask, TFlowStruct s,
+__global__ void __launch_bounds__(EW_T) tflow_struct_moment_kernel(const double* __restrict__ u, int H, int W, const uint8_t* __restrict__ mask, long long mask_bstride, TFlowStruct s,
                                                                    const double* __restrict__ rec, const double* __restrict__ L, double* __restrict__ part)
 {
     constexpr int K = PASS == 1 ? 3 : STRUCT == STRUCT_BANDS ? 1 : 2;
@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(EW_T) tflow_struct_moment_kernel(const double*
     for (long long p = (long long)blockIdx.x * EW_T + threadIdx.x; p < HW; p += (long long)STRUCT_SLICES * EW_T) {
         const int y = (int)(p / W);
         const double vx = ux[p], vy = uy[p];
-        const TStructPoint o = tflow_struct_point<STRUCT>(vx, vy, y, !mask || mask[p] != 0, s);
+        const TStructPoint o = tflow_struct_point<STRUCT>(vx, vy, y, !mask || mask[b * mask_bstride + p] != 0, s);
         if (!o.member) continue;
         if constexpr (STRUCT == STRUCT_BANDS) {
             const bool upper = y < s.middle;
@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(PAIR_T) tflow_free_pair_kernel(const double* _
 
 // g = d S_b / d u of every pixel, [B][2][H][W]; n = B H W; 0 off the members and in a sample below min_count.  rowS, colS: Free only.
 template <int STRUCT>
-__global__ void __launch_bounds__(EW_T) tflow_struct_grad_kernel(const double* __restrict__ u, long long n, int H, int W, const uint8_t* __restrict__ mask, TFlowStruct s,
+__global__ void __launch_bounds__(EW_T) tflow_struct_grad_kernel(const double* __restrict__ u, long long n, int H, int W, const uint8_t* __restrict__ mask, long long mask_bstride, TFlowStruct s,
                                                                  const double* __restrict__ rec, const int* __restrict__ rowS, const int* __restrict__ colS,
                                                                  double* __restrict__ g)
 {
@@ -244,7 +244,7 @@ __global__ void __launch_bounds__(EW_T) tflow_struct_grad_kernel(const double* _
     const long long HW = (long long)H * W, b = i / HW, p = i - b * HW;
     const int y = (int)(p / W);
     const double ux = u[2 * b * HW + p], uy = u[2 * b * HW + HW + p];
-    const TStructPoint o = tflow_struct_point<STRUCT>(ux, uy, y, !mask || mask[p] != 0, s);
+    const TStructPoint o = tflow_struct_point<STRUCT>(ux, uy, y, !mask || mask[b * mask_bstride + p] != 0, s);
     const double* R = rec + b * STRUCT_REC;
     const double N = R[0];
     double gx = 0.0, gy = 0.0;

@@ -1,7 +1,7 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
 // the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for the flow objective
-// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h, flow_score_kernels.h and flow_struct_kernels.h.
+// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h, flow_score_kernels.h, flow_struct_kernels.h and flow_corner_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "flow_pair_kernels.h"
 #include "flow_score_kernels.h"
 #include "flow_struct_kernels.h"
+#include "flow_corner_kernels.h"
 
 using namespace eigt;
 
@@ -104,6 +105,14 @@ struct eigen_trainer {
     double *f_g = nullptr, *f_srec = nullptr, *f_sspart = nullptr, *f_theta = nullptr, *f_L = nullptr;
     int *f_rowS = nullptr, *f_colS = nullptr;
     uint8_t* f_flag = nullptr;
+    // the corner members' (flow_corner_kernels.h), made by the first call that needs them (corner_workspace): the reference as bytes
+    // [B][C0 H W], its gray plane [B][H W], the eigenvalue plane and the candidate keys [B][H W] each, the corners [B][CORNER_MAX][2],
+    // their counts [B] and the member plane [B][H W]
+    uint8_t *c_bytes = nullptr, *c_gray = nullptr, *c_member = nullptr;
+    float *c_eig = nullptr, *c_corners = nullptr;
+    unsigned long long* c_cand = nullptr;
+    int* c_count = nullptr;
+    double* f_stats = nullptr;  // the records of a training call's terms [max_steps][max_batch][SCORE_REC], made by the first call that asks for them
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -405,6 +414,7 @@ struct FlowSpec {
     double eps = 0.0;
     const float* dir = nullptr;
     const uint8_t* mask = nullptr;
+    long long mask_bstride = 0;  // the mask byte of sample b, pixel p is mask[b * mask_bstride + p]; 0: one plane shared by the batch
     long long n_mask = 0;
     bool moving = false;  // EIGEN_FLOW_MOVING_REFERENCE: a training call adds every term's reference path to the frame gradient
     bool pair_pred = false;  // EIGEN_FLOW_PAIR_PREDICTION: the reference of term s is the float P0_{s-1}, in the graph
@@ -412,6 +422,10 @@ struct FlowSpec {
     TFlowScore score = {};
     bool by_struct = false;  // a structure score (flow_struct_kernels.h): the value and q come from `sscore`, kappa as in the score mode
     TFlowStruct sscore = {};
+    // EIGEN_FLOW_MEMBERS_CORNERS: every term's members are the corners of its own reference (corner_stage), under the shared `mask`
+    bool by_corners = false;
+    int max_corners = 0, block_size = 0;
+    double quality = 0.0, min_distance = 0.0;
     // what divides a term's scale in kappa: B N_m, or B in the score mode, whose value is a mean over the samples alone
     double kappa_div(int B) const { return by_score || by_struct ? (double)B : (double)(B * n_mask); }
 };
@@ -500,6 +514,99 @@ int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const fl
     return EIGEN_OK;
 }
 
+// The corner members' workspace, made by the first call that needs it and freed with the handle; the tape and every other use of the
+// handle keep the memory they had.
+int corner_workspace(eigen_trainer* t)
+{
+    if (t->c_member) return EIGEN_OK;
+    const long long B = t->cfg.max_batch, HW = t->ly[0].HW;
+    TCHK(hipSetDevice(t->cfg.device));
+    const std::pair<void**, long long> want[] = {{(void**)&t->c_bytes, B * t->ly[0].CHW()}, {(void**)&t->c_gray, B * HW}, {(void**)&t->c_eig, B * HW * 4},
+                                                 {(void**)&t->c_cand, B * HW * 8}, {(void**)&t->c_corners, B * CORNER_MAX * 2 * 4}, {(void**)&t->c_count, B * 4},
+                                                 {(void**)&t->c_member, B * HW}};
+    // all or nothing: the handle takes the buffers once every one of them exists, a failure frees what it made
+    std::vector<void*> made;
+    for (const auto& w : want) {
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, (size_t)w.second);
+        if (e != hipSuccess) {
+            for (void* q : made) (void)hipFree(q);
+            return tfail(EIGEN_ERR_HIP, "hipMalloc(%lld): %s", w.second, hipGetErrorString(e));
+        }
+        made.push_back(p);
+    }
+    for (size_t i = 0; i < made.size(); ++i) {
+        *want[i].first = made[i];
+        t->allocs.push_back(made[i]);
+    }
+    return EIGEN_OK;
+}
+
+// The records of a training call's terms, [max_steps][max_batch][SCORE_REC] doubles on the device, made by the first call that asks for
+// them (h_stats) and freed with the handle
+int stats_workspace(eigen_trainer* t)
+{
+    if (t->f_stats) return EIGEN_OK;
+    TCHK(hipSetDevice(t->cfg.device));
+    void* p = nullptr;
+    TCHK(hipMalloc(&p, (size_t)t->cfg.max_steps * t->cfg.max_batch * SCORE_REC * 8));
+    t->f_stats = (double*)p;
+    t->allocs.push_back(p);
+    return EIGEN_OK;
+}
+
+// The members of a call, before anything is launched (eigen_flow_members): f.mask, its stride and the corner settings.  check_flow has
+// seen d_mask only where it is the shared plane (per_sample_mask says when it is not).
+bool per_sample_mask(const eigen_flow_members* mem) { return mem && mem->kind == EIGEN_FLOW_MEMBERS_MASK; }
+
+int check_flow_members(eigen_trainer* t, const eigen_flow_members* mem, const uint8_t* d_mask, int B, FlowSpec& f)
+{
+    if (!mem) return EIGEN_OK;
+    if (!f.by_score && !f.by_struct) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
+    if (mem->kind != EIGEN_FLOW_MEMBERS_MASK && mem->kind != EIGEN_FLOW_MEMBERS_CORNERS) return tfail(EIGEN_ERR_INVALID, "flow members: unknown kind %d", mem->kind);
+    if (mem->reserved != 0) return tfail(EIGEN_ERR_INVALID, "flow members: reserved must be 0, got %d", mem->reserved);
+    const long long HW = t->ly[0].HW;
+    if (mem->kind == EIGEN_FLOW_MEMBERS_MASK) {
+        if (!d_mask) return tfail(EIGEN_ERR_INVALID, "flow members: EIGEN_FLOW_MEMBERS_MASK needs d_mask, one plane per sample");
+        if (mem->mask_bstride < HW) return tfail(EIGEN_ERR_INVALID, "flow members: mask_bstride %lld is smaller than one plane (%lld bytes)", (long long)mem->mask_bstride, HW);
+        // one copy of the B planes; a score does not read the count (kappa divides by the batch), so the first counted pixel settles it
+        std::vector<uint8_t> m((size_t)B * HW);
+        TCHK(hipMemcpy2D(m.data(), HW, d_mask, mem->mask_bstride, HW, B, hipMemcpyDeviceToHost));
+        if (std::find_if(m.begin(), m.end(), [](uint8_t v) { return v != 0; }) == m.end()) return tfail(EIGEN_ERR_INVALID, "the flow mask counts no pixel");
+        f.mask = d_mask; f.mask_bstride = mem->mask_bstride;
+        return EIGEN_OK;
+    }
+    if (mem->max_corners < 1 || mem->max_corners > CORNER_MAX) return tfail(EIGEN_ERR_INVALID, "flow members: max_corners %d outside 1 .. %d", mem->max_corners, CORNER_MAX);
+    if (mem->block_size < 1 || mem->block_size > eig::EIG_MAXB) return tfail(EIGEN_ERR_INVALID, "flow members: block_size %d outside 1 .. %d", mem->block_size, eig::EIG_MAXB);
+    if (!(mem->quality_level > 0.0) || !(mem->quality_level <= 1.0)) return tfail(EIGEN_ERR_INVALID, "flow members: quality_level %g: must be in (0, 1]", mem->quality_level);
+    if (!std::isfinite(mem->min_distance) || !(mem->min_distance >= 0.0)) return tfail(EIGEN_ERR_INVALID, "flow members: min_distance %g: must be finite and >= 0", mem->min_distance);
+    if (mem->mask_bstride != 0) return tfail(EIGEN_ERR_INVALID, "flow members: mask_bstride %lld: must be 0 with EIGEN_FLOW_MEMBERS_CORNERS (d_mask is the shared plane)", (long long)mem->mask_bstride);
+    f.by_corners = true;
+    f.max_corners = mem->max_corners; f.block_size = mem->block_size; f.quality = mem->quality_level; f.min_distance = mem->min_distance;
+    return corner_workspace(t);
+}
+
+// The member planes of one reference into t->c_member, the corner counts into t->c_count (flow_corner_kernels.h): the fitness path's own
+// launches of eigen_flow on the bytes the fitness would see.  f.mask is the shared plane, or null.
+void corner_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const uint8_t* ref, const float* fref, long long r_bstride)
+{
+    const TLayer& y = t->ly[0];
+    const int H = y.H, W = y.W, HW = (int)y.HW;
+    if (fref) {
+        ew(st, tcorner_quant_kernel, B * y.CHW(), fref, r_bstride, y.CHW(), B * y.CHW(), t->c_bytes);
+        ref = t->c_bytes; r_bstride = y.CHW();
+    }
+    hipLaunchKernelGGL(eig::gray_kernel, dim3((HW + 255) / 256, B), dim3(256), 0, st, ref, r_bstride, y.C, HW, t->c_gray, B);
+    const double sc = 1.0 / ((double)(1 << 2) * f.block_size * 255.0);
+    const float SC = (float)(sc * sc);
+    hipLaunchKernelGGL(eig::mineig_kernel, dim3((W + eig::EIG_T - 1) / eig::EIG_T, (H + eig::EIG_T - 1) / eig::EIG_T, B), dim3(256), 0, st, (const uint8_t*)t->c_gray, H, W,
+                       f.block_size, SC, t->c_eig);
+    hipLaunchKernelGGL(eig::corner_select_kernel, dim3(B), dim3(1024), 0, st, (const float*)t->c_eig, H, W, f.quality, (float)f.min_distance, f.max_corners, t->c_cand,
+                       t->c_corners, t->c_count);
+    hipLaunchKernelGGL(tcorner_member_kernel, dim3(B), dim3(CORNER_T), 0, st, (const float*)t->c_corners, (const int*)t->c_count, f.max_corners, H, W, f.mask,
+                       t->c_member);
+}
+
 // The gradient of the term by its reference, from the planes and q the flow stage of the same term left in the workspace and its flow
 // at d_flow: into d_refg (sample b at + b * rg_bstride), added in float or stored.  A training call under the prediction pairing runs
 // this apart from the stage, once layer 0's terr_bwd of the step has written dP0_{s-1}.
@@ -533,16 +640,16 @@ void struct_stage_of(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f,
     const long long n = (long long)B * y.HW;
     const dim3 sgrid(STRUCT_SLICES, (unsigned)B);
     const TFlowStruct& s = f.sscore;
-    if (STRUCT == STRUCT_FREE) ew(st, tflow_free_prepare_kernel, n, u, n, y.H, y.W, f.mask, s, t->f_theta, t->f_flag);
-    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 1>), sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, s, (const double*)t->f_srec, (const double*)t->f_L, t->f_sspart);
+    if (STRUCT == STRUCT_FREE) ew(st, tflow_free_prepare_kernel, n, u, n, y.H, y.W, f.mask, f.mask_bstride, s, t->f_theta, t->f_flag);
+    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 1>), sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, s, (const double*)t->f_srec, (const double*)t->f_L, t->f_sspart);
     hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 1>), dim3(B), dim3(64), 0, st, (const double*)t->f_sspart, B, s, t->f_srec, (double*)nullptr);
     if (STRUCT == STRUCT_FREE)
         hipLaunchKernelGGL(tflow_free_pair_kernel, dim3((unsigned)((y.HW + PAIR_T - 1) / PAIR_T), (unsigned)B), dim3(PAIR_T), 0, st, (const double*)t->f_theta,
                            (const uint8_t*)t->f_flag, y.H, y.W, s.DD, t->f_L, t->f_rowS, t->f_colS);
-    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 2>), sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, s, (const double*)t->f_srec, (const double*)t->f_L, t->f_sspart);
+    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 2>), sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, s, (const double*)t->f_srec, (const double*)t->f_L, t->f_sspart);
     hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 2>), dim3(B), dim3(64), 0, st, (const double*)t->f_sspart, B, s, t->f_srec, d_value);
     if (!want_q) return;
-    ew(st, tflow_struct_grad_kernel<STRUCT>, n, u, n, y.H, y.W, f.mask, s, (const double*)t->f_srec, (const int*)t->f_rowS, (const int*)t->f_colS, t->f_g);
+    ew(st, tflow_struct_grad_kernel<STRUCT>, n, u, n, y.H, y.W, f.mask, f.mask_bstride, s, (const double*)t->f_srec, (const int*)t->f_rowS, (const int*)t->f_colS, t->f_g);
     const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
     hipLaunchKernelGGL(tflow_struct_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_g, n, y.H, y.W, f.r, f.eps, t->f_q);
 }
@@ -558,23 +665,30 @@ void struct_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, co
 // handle's workspace unless the caller wants it anyway.
 void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m)
 {
+    if (f.by_corners) {
+        // the term's members from its own reference, then the stage under them as a per-sample mask
+        corner_stage(t, st, B, f, m.ref, m.fref, m.r_bstride);
+        FlowSpec g = f;
+        g.by_corners = false; g.mask = t->c_member; g.mask_bstride = t->ly[0].HW;
+        return flow_stage(t, st, B, g, m);
+    }
     double* d_flow = (m.d_refg || f.by_score || f.by_struct) && !m.d_flow ? t->f_u : m.d_flow;
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
     if (m.fref) ew(st, tflow_pair_prep_kernel, n, m.pred, m.p_bstride, m.fref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
     else ew(st, tflow_prep_kernel, n, m.pred, m.p_bstride, m.ref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
     const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-    hipLaunchKernelGGL(tflow_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, n, y.H, y.W, f.r, f.eps, f.dir, f.mask, t->f_q, t->f_mv, d_flow);
+    hipLaunchKernelGGL(tflow_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, n, y.H, y.W, f.r, f.eps, f.dir, f.mask, f.mask_bstride, t->f_q, t->f_mv, d_flow);
     if (f.by_score) {
         // the value and q of the score mode, from the u the solve just wrote: two passes of moments, then q over what the solve left in f_q
         const dim3 sgrid(SCORE_SLICES, (unsigned)B);
         const double* u = d_flow;
-        hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.score, (const double*)t->f_rec, t->f_spart);
+        hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_spart);
         hipLaunchKernelGGL(tflow_score_final_kernel<1>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, (double*)nullptr);
-        hipLaunchKernelGGL(tflow_score_moment_kernel<2>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.score, (const double*)t->f_rec, t->f_spart);
+        hipLaunchKernelGGL(tflow_score_moment_kernel<2>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_spart);
         hipLaunchKernelGGL(tflow_score_final_kernel<2>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, m.d_value);
         if (m.d_seed || m.d_refg)
-            hipLaunchKernelGGL(tflow_score_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, u, n, y.H, y.W, f.r, f.eps, f.mask, f.score,
+            hipLaunchKernelGGL(tflow_score_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, u, n, y.H, y.W, f.r, f.eps, f.mask, f.mask_bstride, f.score,
                                (const double*)t->f_rec, t->f_q);
     } else if (f.by_struct) {
         struct_stage(t, st, B, f, d_flow, m.d_value, m.d_seed || m.d_refg);
@@ -594,6 +708,7 @@ struct Objective {
     bool by_flow = false;
     FlowSpec flow;                      // by_flow
     double* h_terms = nullptr;          // by_flow: host, T - 1 terms, may be null
+    bool keep_stats = false;            // by_flow with a score: the records of every computed term are kept in f_stats [T - 1][B][10]
     double weight(int s) const { return step_w ? step_w[s] : 1.0; }
     double total_weight() const { return step_w ? sum_w : (double)(T - 1); }
     const double* step_w = nullptr;     // host, T - 1 weights; NULL: all one
@@ -676,7 +791,7 @@ struct FrameGrad {
 
 // One step of backprop through time: the cells bottom up (dP, dh, dc and dZ of step s), then the error units top down.  fg: under
 // the flow objective's moving reference, where term s adds its reference path, which belongs to frame s + 1.
-void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, const uint8_t* d_frames, long long bstride, const FrameGrad& fg)
+int backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, const uint8_t* d_frames, long long bstride, const FrameGrad& fg)
 {
     const int L = t->L, T = o.T, B = o.B;
     const float* prm = t->prm;
@@ -706,6 +821,10 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
                     m.d_refg = o.flow.moving && fg.p ? fg.p + (long long)(s + 1) * fg.tstride : nullptr; m.rg_bstride = fg.bstride; m.rg_accumulate = 1;
                 }
                 flow_stage(t, st, B, o.flow, m);
+                // the samples' records of this term, which the next term's stage overwrites: kept on the device, read once the call is done
+                if (o.keep_stats)
+                    TCHK(hipMemcpyAsync(t->f_stats + (long long)s * B * SCORE_REC, o.flow.by_score ? t->f_rec : t->f_srec, (size_t)B * SCORE_REC * 8,
+                                        hipMemcpyDeviceToDevice, st));
             }
             xn = nullptr;
         }
@@ -749,6 +868,7 @@ void backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, 
     // P0_{s-1} now, and the seed of term s - 1 follows in backward_step(s - 1), ahead of that step's clamp mask
     if (o.by_flow && o.flow.pair_pred && s >= 1 && s < T - 1 && o.weight(s) != 0.0)
         flow_ref_path(t, st, B, o.flow, o.flow_kappa(s), t->f_u, t->ly[0].dPn, t->ly[0].CHW(), 1);
+    return EIGEN_OK;
 }
 
 // g_s of backward step s, after layer 0's terr_bwd of that step (dE_0 and E_0 of step s are what that kernel read): the input path on
@@ -866,6 +986,8 @@ struct LossGradCall {
     int32_t pairing = EIGEN_FLOW_PAIR_FRAME;
     const eigen_flow_score* score = nullptr;
     const eigen_flow_structure_score* sscore = nullptr;
+    const eigen_flow_members* members = nullptr;
+    double* h_stats = nullptr;
 };
 
 // The training call behind every exported eigen_trainer_loss_grad* entry.  The order of the checks is the order of this function: the
@@ -892,11 +1014,12 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     if (!by_flow && (c.flow || c.d_dir || c.d_mask)) return tfail(EIGEN_ERR_INVALID, "flow settings, direction and mask go with EIGEN_OBJ_FLOW only");
     if (!by_flow && c.score) return tfail(EIGEN_ERR_INVALID, "a flow score goes with EIGEN_OBJ_FLOW only");
     if (!by_flow && c.sscore) return tfail(EIGEN_ERR_INVALID, "a flow structure score goes with EIGEN_OBJ_FLOW only");
+    if (!by_flow && c.members) return tfail(EIGEN_ERR_INVALID, "flow members go with EIGEN_OBJ_FLOW only");
     // the step and layer weights follow the same rules under every objective
     rc = make_objective(t, by_flow ? (int32_t)EIGEN_OBJ_MSE : c.objective, c.h_layer_w, c.h_step_w, T, B, o);
     if (rc) return rc;
     if (by_flow) {
-        rc = check_flow(t, c.flow, c.d_dir, c.d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
+        rc = check_flow(t, c.flow, c.d_dir, per_sample_mask(c.members) ? nullptr : c.d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
         if (rc) return rc;
         o.flow.pair_pred = c.pairing == EIGEN_FLOW_PAIR_PREDICTION;
         // a frame is no reference under the prediction pairing: there is nothing the flag could move
@@ -905,8 +1028,16 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
         if (rc) return rc;
         rc = check_flow_struct(c.sscore, c.d_dir, o.flow);
         if (rc) return rc;
+        if (c.score && c.sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
+        rc = check_flow_members(t, c.members, c.d_mask, B, o.flow);
+        if (rc) return rc;
         o.by_flow = true;
         o.h_terms = c.h_terms;
+        if (c.h_stats && T >= 2 && (o.flow.by_score || o.flow.by_struct)) {
+            rc = stats_workspace(t);
+            if (rc) return rc;
+            o.keep_stats = true;
+        }
     }
     hipStream_t st = (hipStream_t)c.stream;
     rc = start_state(t, st, B, c.reset);
@@ -922,14 +1053,21 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
         for (float* a : {t->ly[l].dPn, t->ly[l].dhc, t->ly[l].dc}) TCHK(hipMemsetAsync(a, 0, B * t->ly[l].CHW() * 4, st));
     // the tied frame gradient starts from zero; only the C0 H W floats of every sample are touched, whatever g_bstride is
     for (int b = 0; fg.p && fg.tstride == 0 && b < B; ++b) TCHK(hipMemsetAsync(fg.p + b * fg.bstride, 0, C0HW * 4, st));
+    // the records of the terms that are not computed read zero
+    if (o.keep_stats) TCHK(hipMemsetAsync(t->f_stats, 0, (size_t)(T - 1) * B * SCORE_REC * 8, st));
     for (int s = T - 1; s >= 0; --s) {
-        backward_step(t, st, o, s, c.d_frames, c.bstride, fg);
+        rc = backward_step(t, st, o, s, c.d_frames, c.bstride, fg);
+        if (rc) return rc;
         if (fg.p) frame_grad_step(t, st, o, s, c.n_fed, c.d_frames, c.bstride, fg);
     }
     weight_gradients(t, st, T, B);
     TCHK(hipGetLastError());
     t->state_batch = B;
     t->state_slot = T;
+    if (o.keep_stats) {
+        TCHK(hipMemcpyAsync(c.h_stats, t->f_stats, (size_t)(T - 1) * B * SCORE_REC * 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+    }
     return read_loss(t, st, o, want_table, c.h_loss, c.h_layer_err);
 }
 
@@ -1095,7 +1233,7 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
 static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
                           int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr, const eigen_flow_score* score = nullptr,
-                          double* h_stats = nullptr, const eigen_flow_structure_score* sscore = nullptr)
+                          double* h_stats = nullptr, const eigen_flow_structure_score* sscore = nullptr, const eigen_flow_members* members = nullptr)
 {
     if (!t || !d_pred || (!d_ref && !d_fref) || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
@@ -1105,11 +1243,13 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
         return tfail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", C0HW);
     if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale %g is not finite", scale);
     FlowSpec f;
-    int rc = check_flow(t, flow, d_dir, d_mask, 0, f);
+    int rc = check_flow(t, flow, d_dir, per_sample_mask(members) ? nullptr : d_mask, 0, f);
     if (rc) return rc;
     rc = check_flow_score(score, d_dir, f);
     if (rc) return rc;
     rc = check_flow_struct(sscore, d_dir, f);
+    if (rc) return rc;
+    rc = check_flow_members(t, members, d_mask, batch, f);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     FlowTerm m;
@@ -1177,6 +1317,57 @@ int eigen_trainer_flow_term_structure(eigen_trainer* t, const float* d_pred, int
     if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
     return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, nullptr, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride,
                           stream, d_fref, nullptr, h_stats, score);
+}
+
+int eigen_trainer_flow_term_members(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
+                                    int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask, const eigen_flow_score* score,
+                                    const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double scale, double* h_value, double* h_stats,
+                                    double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream)
+{
+    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
+    if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
+    if ((score != nullptr) == (sscore != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the flow score and the flow structure score must be given");
+    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, nullptr, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride,
+                          stream, d_fref, score, h_stats, sscore, members);
+}
+
+int eigen_trainer_flow_members(eigen_trainer* t, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride, int32_t batch, const eigen_flow_members* members,
+                               const uint8_t* d_mask, uint8_t* h_members, int32_t* h_counts, void* stream)
+{
+    if (!t || !members) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
+    if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
+    if (batch > t->cfg.max_batch) return tfail(EIGEN_ERR_CAPACITY, "batch %d exceeds the trainer's %d", batch, t->cfg.max_batch);
+    if (r_bstride < t->ly[0].CHW()) return tfail(EIGEN_ERR_INVALID, "r_bstride %lld is smaller than one image (%lld elements)", (long long)r_bstride, t->ly[0].CHW());
+    if (members->kind != EIGEN_FLOW_MEMBERS_CORNERS) return tfail(EIGEN_ERR_INVALID, "flow members: kind %d: this entry derives EIGEN_FLOW_MEMBERS_CORNERS", members->kind);
+    FlowSpec f;
+    f.by_score = true;  // the stage alone stands for a scored term
+    f.mask = d_mask;
+    TCHK(hipSetDevice(t->cfg.device));
+    int rc = check_flow_members(t, members, d_mask, batch, f);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    corner_stage(t, st, batch, f, d_ref, d_fref, r_bstride);
+    TCHK(hipGetLastError());
+    if (h_members) TCHK(hipMemcpyAsync(h_members, t->c_member, (size_t)batch * t->ly[0].HW, hipMemcpyDeviceToHost, st));
+    if (h_counts) TCHK(hipMemcpyAsync(h_counts, t->c_count, (size_t)batch * 4, hipMemcpyDeviceToHost, st));
+    TCHK(hipStreamSynchronize(st));
+    return EIGEN_OK;
+}
+
+int eigen_trainer_loss_grad_flow_members(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
+                                         int32_t requant, int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss,
+                                         double* h_layer_err, float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride,
+                                         const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double* h_terms, int32_t pairing,
+                                         const eigen_flow_score* score, const eigen_flow_structure_score* sscore, const eigen_flow_members* members,
+                                         double* h_stats, void* stream)
+{
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
+    c.members = members; c.h_stats = h_stats;
+    return loss_grad_call(t, c);
 }
 
 int eigen_trainer_debug_free_planes(eigen_trainer* t, int32_t batch, double* h_theta, double* h_L, int32_t* h_rowS, int32_t* h_colS, uint8_t* h_flag, void* stream)

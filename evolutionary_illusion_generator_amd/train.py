@@ -33,6 +33,12 @@ class FlowStructureSettings(ctypes.Structure):
                 ("lim_lo", ctypes.c_double), ("lim_hi", ctypes.c_double), ("max_distance", ctypes.c_double), ("w", ctypes.c_double * 3)]
 
 
+class FlowMembersSettings(ctypes.Structure):
+    """eigen_flow_members"""
+    _fields_ = [("kind", ctypes.c_int32), ("max_corners", ctypes.c_int32), ("block_size", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("quality_level", ctypes.c_double), ("min_distance", ctypes.c_double), ("mask_bstride", ctypes.c_int64)]
+
+
 class TrainerConfig(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_layers", ctypes.c_int32),
                 ("channels", ctypes.c_int32 * engine.MAX_LAYERS), ("max_batch", ctypes.c_int32), ("max_steps", ctypes.c_int32)]
@@ -52,7 +58,8 @@ _ENTRIES = {(False, False): ("eigen_trainer_loss_grad_obj", ()), (False, True): 
             (True, "frame"): ("eigen_trainer_loss_grad_flow", ("frame_grad", "flow")),
             (True, "prediction"): ("eigen_trainer_loss_grad_flow_pair", ("frame_grad", "flow", "pairing")),
             (True, "score"): ("eigen_trainer_loss_grad_flow_score", ("frame_grad", "flow", "pairing", "score")),
-            (True, "structure"): ("eigen_trainer_loss_grad_flow_structure", ("frame_grad", "flow", "pairing", "score"))}
+            (True, "structure"): ("eigen_trainer_loss_grad_flow_structure", ("frame_grad", "flow", "pairing", "score")),
+            (True, "members"): ("eigen_trainer_loss_grad_flow_members", ("frame_grad", "flow", "pairing", "members"))}
 
 
 def _bind(lib):
@@ -75,6 +82,12 @@ def _bind(lib):
     lib.eigen_trainer_loss_grad_flow_structure.argtypes = lib.eigen_trainer_loss_grad_flow_score.argtypes
     lib.eigen_trainer_flow_term_structure.argtypes = lib.eigen_trainer_flow_term_score.argtypes
     lib.eigen_trainer_debug_free_planes.argtypes = [_P, _I32, _P, _P, _P, _P, _P, _P]
+    # ... pairing, score, sscore, members, h_stats, stream
+    lib.eigen_trainer_loss_grad_flow_members.argtypes = _CALL + _OBJ + _FRAMEGRAD + _FLOW + [_I32, _P, _P, _P, _P, _P]
+    # eigen_trainer_flow_term_score's with (score, sscore, members) in place of score
+    lib.eigen_trainer_flow_term_members.argtypes = [_P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, ctypes.c_double, _P, _P, _P, _P, _I64, _P, _I64, _P]
+    # t, d_ref, d_fref, r_bstride, batch, members, d_mask, h_members, h_counts, stream
+    lib.eigen_trainer_flow_members.argtypes = [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
@@ -95,6 +108,32 @@ FLOW_DIRECTIONS = ("tangent", "radial", "horizontal", "vertical")
 FLOW_REFERENCES = ("constant", "moving")
 FLOW_MOVING_REFERENCE = 1  # EIGEN_FLOW_MOVING_REFERENCE
 FLOW_PAIRINGS = {"frame": 0, "prediction": 1}  # EIGEN_FLOW_PAIR_FRAME, EIGEN_FLOW_PAIR_PREDICTION
+FLOW_MEMBERS_MASK, FLOW_MEMBERS_CORNERS = 0, 1  # EIGEN_FLOW_MEMBERS_MASK, EIGEN_FLOW_MEMBERS_CORNERS
+CORNER_MAX, CORNER_MAX_BLOCK = 128, 9
+
+
+class CornerMembers:
+    """Membership of a score from the fitness's own corners ("The corner members"): the members of a term are the
+    at most max_corners points ``goodFeaturesToTrack(quality_level, min_distance, block_size)`` picks on the term's own reference image,
+    per sample, found on the device by the kernels of the fitness path; the score's geometric rule and its norm limits apply on top, and
+    a shared [H, W] mask on the objective removes the corners it does not count.  The defaults are ``eigen_config``'s ``lk_*`` defaults.
+    ValueError: max_corners outside 1 .. 128, block_size outside 1 .. 9, quality_level outside (0, 1], min_distance negative or not
+    finite."""
+
+    def __init__(self, max_corners=100, quality_level=0.3, min_distance=7.0, block_size=7):
+        for name, v, hi in (("max_corners", max_corners, CORNER_MAX), ("block_size", block_size, CORNER_MAX_BLOCK)):
+            if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= hi:
+                raise ValueError("%s must be an integer in 1 .. %d, got %r" % (name, hi, v))
+        quality_level, min_distance = float(quality_level), float(min_distance)
+        if not 0 < quality_level <= 1:
+            raise ValueError("quality_level must be in (0, 1], got %r" % (quality_level,))
+        if not (np.isfinite(min_distance) and min_distance >= 0):
+            raise ValueError("min_distance must be finite and >= 0, got %r" % (min_distance,))
+        self.max_corners, self.quality_level, self.min_distance, self.block_size = int(max_corners), quality_level, min_distance, int(block_size)
+
+    def settings(self):
+        """eigen_flow_members of kind CORNERS"""
+        return FlowMembersSettings(FLOW_MEMBERS_CORNERS, self.max_corners, self.block_size, 0, self.quality_level, self.min_distance, 0)
 
 
 SCORE_STATS = ("N", "mean_rho", "mean_tau", "mean_abs_dx", "mean_norm", "var_rho", "var_tau", "var_norm", "score", "spare")  # one sample's record
@@ -260,6 +299,10 @@ class FlowObjective:
     score: None, or a ``FlowScore``: the term is then the fitness's own Circles score on the solved field ("The
     score mode"); it takes no direction (ValueError), the mask then selects the pixels that can be members.  ``scored(score)`` sets it
     on an objective that exists, which is how a ``PredictionFlow`` takes one.
+    With a score the mask may also be [n, H, W], one plane per sample (n is checked against the batch of the call: ValueError), and
+    members may be a ``CornerMembers``: the members of every term are then the corners the fitness would pick on the term's own
+    reference, under the shared [H, W] mask if one is given ("The corner members"); ``with_members(m)`` sets them
+    on an objective that exists.  ValueError: a per-sample mask or members without a score, or both together.
 
     The defaults are a design choice: radius 7 is a 15-pixel window, the fitness path's ``lk_win``; eps 1e-2 is in units of summed
     squared gradients of images in [0, 1] (a 15 x 15 window over an edge of contrast 0.1 sums to about 0.1), so it damps flat windows
@@ -271,7 +314,9 @@ class FlowObjective:
 
     pairing = "frame"
 
-    def __init__(self, radius=7, eps=1e-2, direction=None, mask=None, score=None, reference="constant"):
+    def __init__(self, radius=7, eps=1e-2, direction=None, mask=None, score=None, members=None, reference="constant"):
+        if isinstance(members, str) and reference == "constant":
+            members, reference = None, members      # `reference` was the sixth positional argument before `members` existed: such a call still means it
         if reference not in FLOW_REFERENCES:
             raise ValueError("reference must be one of %s, got %r" % (", ".join(FLOW_REFERENCES), reference))
         self.reference = reference
@@ -291,14 +336,53 @@ class FlowObjective:
             self.direction = d
         if mask is not None:
             m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-            if m.ndim != 2:
-                raise ValueError("mask must be [H, W], got shape %s" % (m.shape,))
+            if m.ndim not in (2, 3):
+                raise ValueError("mask must be [H, W] or, one plane per sample, [n, H, W]; got shape %s" % (m.shape,))
             if not m.any():
                 raise ValueError("the mask counts no pixel")
             self.mask = m
         self._dev = {}
-        self.score = None
-        self.scored(score)
+        self.score = self.members = None
+        if score is not None:
+            self.scored(score)
+        self.with_members(members)
+        if self.pairing == "frame":     # a PredictionFlow takes its score after construction (``scored``): checked at its first use
+            self.check_members()
+
+    def check_members(self):
+        """ValueError: a per-sample mask without a score (``with_members`` refuses members without one)"""
+        if self.score is None and (self.members is not None or self.per_sample):
+            raise ValueError("a per-sample [n, H, W] mask and members need a score: the displacement modes divide by the shared mask's count")
+
+    @property
+    def per_sample(self):
+        """whether the mask holds one plane per sample, [n, H, W]"""
+        return self.mask is not None and self.mask.ndim == 3
+
+    def with_members(self, members):
+        """Set the membership of the score (a ``CornerMembers``; None: every pixel the mask counts) and return self.  ValueError: not a
+        ``CornerMembers``, members on an objective without a score, or together with a per-sample [n, H, W] mask (a shared [H, W] mask
+        is what combines with corners)."""
+        if members is not None:
+            if not isinstance(members, CornerMembers):
+                raise ValueError("members must be a CornerMembers or None, got %r" % (members,))
+            if self.score is None:
+                raise ValueError("members need a score: the displacement modes divide by the shared mask's count")
+            if self.per_sample:
+                raise ValueError("a per-sample [n, H, W] mask does not go with CornerMembers: a shared [H, W] mask is what combines with corners")
+        self.members = members
+        return self
+
+    def members_settings(self, n, h, w):
+        """eigen_flow_members of a call of batch n on [h, w] images, or None where the objective has neither a per-sample mask nor members.
+        ValueError: a per-sample mask that is not [n, h, w]."""
+        if self.members is not None:
+            return self.members.settings()
+        if not self.per_sample:
+            return None
+        if tuple(self.mask.shape) != (n, h, w):
+            raise ValueError("the per-sample mask is %s, the call is [%d, %d, %d]" % (self.mask.shape, n, h, w))
+        return FlowMembersSettings(FLOW_MEMBERS_MASK, 0, 0, 0, 0.0, 0.0, h * w)
 
     def scored(self, score):
         """Set the score mode (a ``FlowScore``, or a structure score: ``BandsScore``, ``FreeScore``; None: the displacement modes) and return
@@ -307,6 +391,8 @@ class FlowObjective:
             raise ValueError("score must be a FlowScore, a BandsScore, a FreeScore or None, got %r" % (score,))
         if score is not None and self.direction is not None:
             raise ValueError("a score takes no direction field")
+        if score is None and (getattr(self, "members", None) is not None or self.per_sample):
+            raise ValueError("a per-sample mask and members need a score")
         self.score = score
         return self
 
@@ -316,6 +402,7 @@ class FlowObjective:
 
     def on_device(self, torch, device, h, w):
         """(direction, mask) as device tensors (None where not set), uploaded once per device; ValueError if they are not [.., h, w]"""
+        self.check_members()
         for name, a in (("direction", self.direction), ("mask", self.mask)):
             if a is not None and tuple(a.shape[-2:]) != (h, w):
                 raise ValueError("%s is %s, the trainer's image is [%d, %d]" % (name, a.shape, h, w))
@@ -334,7 +421,8 @@ class PredictionFlow(FlowObjective):
     class) the loss is the dense stand-in for what ``get_fitnesses_neat`` / ``eval_images(pairing=PAIR_POPULATION)`` score.  Frames are no
     references here: a frame gradient is the input path alone, which is the whole gradient, and there is no `reference` argument.
     radius, eps, direction, mask: as ``FlowObjective``; the score mode is set by ``PredictionFlow(...).scored(FlowScore(...))`` or by
-    ``make_flow("prediction", score=...)``."""
+    ``make_flow("prediction", score=...)``, corner members by ``.with_members(CornerMembers(...))`` behind it or by ``make_flow``'s
+    `members`.  A per-sample [n, H, W] mask needs a score by the first call that uses the objective (ValueError there)."""
 
     pairing = "prediction"
 
@@ -342,22 +430,26 @@ class PredictionFlow(FlowObjective):
         super().__init__(radius, eps, direction, mask)
 
 
-def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, reference="constant", score=None):
+def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, reference="constant", score=None, members=None):
     """The flow objective of a command line: a ``FlowObjective`` (pairing "frame", with its `reference`) or a ``PredictionFlow``
     (pairing "prediction"; it has no frame as a reference, so reference="moving" is a ValueError)."""
     if pairing not in FLOW_PAIRINGS:
         raise ValueError("pairing must be one of %s, got %r" % (", ".join(FLOW_PAIRINGS), pairing))
     if pairing == "frame":
-        return FlowObjective(radius, eps, direction, mask, reference=reference, score=score)
+        return FlowObjective(radius, eps, direction, mask, reference=reference, score=score, members=members)
     if reference != "constant":
         raise ValueError("the prediction pairing has no frame as a reference: reference=%r does not go with it" % (reference,))
-    return PredictionFlow(radius, eps, direction, mask).scored(score)
+    flow = PredictionFlow(radius, eps, direction, mask).scored(score).with_members(members)
+    flow.check_members()
+    return flow
 
 
 def _entry_key(flow):
-    """the key of _ENTRIES of a flow objective: its pairing, or the kind of its score"""
+    """the key of _ENTRIES of a flow objective: its pairing, the kind of its score, or "members" with a per-sample mask or corner members"""
     if flow.score is None:
         return flow.pairing
+    if flow.members is not None or flow.per_sample:
+        return "members"
     return "score" if isinstance(flow.score, FlowScore) else "structure"
 
 
@@ -592,7 +684,8 @@ class PredNetTrainer:
     def _loss_grad(self, d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights, layer_errors, frame_grads, flow=None):
         """The call behind forward_backward, on frames already on the device: (loss, table or None, d_pred or None, d_grad or None), the
         last two device tensors.  Every argument is checked before anything is launched.  Under objective="flow" the float64 [T - 1]
-        terms of the call are left in ``self.last_flow_terms``."""
+        terms of the call are left in ``self.last_flow_terms``; under a per-sample mask or corner members the float64 [T - 1, n, 10] records
+        of the samples of every computed term (zeros for the others) are left in ``self.last_flow_stats``, which any other call leaves as it is."""
         torch = self._torch
         if objective not in OBJECTIVES:
             raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
@@ -623,13 +716,22 @@ class PredNetTrainer:
             cfg = flow.settings()
             tails["flow"] = [ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask), _ptr(terms)]
             tails["pairing"] = [ctypes.c_int32(FLOW_PAIRINGS[flow.pairing])]
+            stats = None
             if flow.score is not None:
                 sc = flow.score.settings(self.h)
                 tails["score"] = [ctypes.byref(sc)]
+                mem = flow.members_settings(n, self.h, self.w)
+                if mem is not None:
+                    # the widest entry: both scores (one of them NULL), the members and the records of every computed term
+                    stats = np.zeros((max(T - 1, 1), n, len(SCORE_STATS)), np.float64)
+                    by_circles = isinstance(flow.score, FlowScore)
+                    tails["members"] = [ctypes.byref(sc) if by_circles else None, None if by_circles else ctypes.byref(sc), ctypes.byref(mem), _ptr(stats)]
         entry, groups = _ENTRIES[by_flow, _entry_key(flow) if by_flow else frame_grads is not None]
         _check(getattr(self.lib, entry)(*args, *[a for g in groups for a in tails[g]], _stream_arg(stream)))
         if by_flow:
             self.last_flow_terms = terms[:T - 1]
+            if stats is not None:       # the members entry alone returns records: any other call leaves what an earlier one left
+                self.last_flow_stats = stats[:T - 1]
         if table is not None:
             table = table[:T - 1]
         value = combine_terms(table, lam, w_arr if w_arr is not None and w_arr.size else None) if by_error else loss.value
@@ -677,6 +779,33 @@ class PredNetTrainer:
         out = (value,) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table,) if layer_errors else ()) + ((d_grad.cpu().numpy(),) if frame_grads else ())
         out += (self.last_flow_terms,) if flow_terms else ()
         return out[0] if len(out) == 1 else out
+
+    def flow_members(self, ref, members, mask=None):
+        """The membership stage alone (eigen_trainer_flow_members): ref uint8 or float32 [n, C, H, W], the references (a float one is
+        clamped to [0, 1] and quantised as a self-fed step's byte is); members a ``CornerMembers``; mask [H, W], the shared plane
+        (None: every pixel counts).  -> (uint8 [n, H, W], 1 at every corner the mask counts; int32 [n], the corners picked per
+        sample, before the mask)."""
+        torch = self._torch
+        if not isinstance(members, CornerMembers):
+            raise ValueError("members must be a CornerMembers, got %r" % (members,))
+        shp = (self.channels[0], self.h, self.w)
+        dev = "cuda:%d" % self.device
+        r = (ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref))).to(dev).contiguous()
+        if r.dtype not in (torch.uint8, torch.float32) or r.dim() != 4 or tuple(r.shape[1:]) != shp or not 1 <= int(r.shape[0]) <= self.batch:
+            raise ValueError("ref must be uint8 or float32 [n, %d, %d, %d] with n <= %d; got %s %s" % (shp + (self.batch, r.dtype, tuple(r.shape))))
+        d_mask = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if m.shape != (self.h, self.w):
+                raise ValueError("mask must be [%d, %d], got %s" % (self.h, self.w, m.shape))
+            d_mask = torch.from_numpy(m).to(dev)
+        n = int(r.shape[0])
+        planes, counts = np.zeros((n, self.h, self.w), np.uint8), np.zeros(n, np.int32)
+        mem = members.settings()
+        by_float = r.dtype == torch.float32
+        _check(self.lib.eigen_trainer_flow_members(self._h, None if by_float else _ptr(r), _ptr(r) if by_float else None, ctypes.c_int64(int(np.prod(shp))),
+                                                   ctypes.c_int32(n), ctypes.byref(mem), _ptr(d_mask), _ptr(planes), _ptr(counts), None))
+        return planes, counts
 
     def flow_term(self, pred, ref, flow, scale=1.0, reference_grad=False, stats=False):
         """The flow stage alone (eigen_trainer_flow_term), with the kernels a training call runs: pred float32 [n, C, H, W], the
@@ -726,11 +855,16 @@ class PredNetTrainer:
         if flow.score is not None:
             sc = flow.score.settings(self.h)
             rec = np.zeros((n, len(SCORE_STATS)), np.float64)
-            entry = self.lib.eigen_trainer_flow_term_score if isinstance(flow.score, FlowScore) else self.lib.eigen_trainer_flow_term_structure
+            by_circles = isinstance(flow.score, FlowScore)
+            mem = flow.members_settings(n, self.h, self.w)
+            if mem is not None:
+                entry, scores = self.lib.eigen_trainer_flow_term_members, [ctypes.byref(sc) if by_circles else None, None if by_circles else ctypes.byref(sc), ctypes.byref(mem)]
+            else:
+                entry, scores = self.lib.eigen_trainer_flow_term_score if by_circles else self.lib.eigen_trainer_flow_term_structure, [ctypes.byref(sc)]
             _check(entry(self._h, _ptr(p), ctypes.c_int64(per), None if float_ref else _ptr(r), _ptr(r) if float_ref else None,
-                                                          ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_mask), ctypes.byref(sc),
-                                                          ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(rec), _ptr(u), _ptr(seed), ctypes.c_int64(per),
-                                                          _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None))
+                         ctypes.c_int64(per), ctypes.c_int32(n), ctypes.byref(cfg), _ptr(d_mask), *scores,
+                         ctypes.c_double(float(scale)), ctypes.byref(value), _ptr(rec), _ptr(u), _ptr(seed), ctypes.c_int64(per),
+                         _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None))
             self.last_flow_stats = rec
             out = (value.value, u.cpu().numpy(), seed.cpu().numpy()) + ((rg.cpu().numpy(),) if reference_grad else ())
             return out + (rec,) if stats else out
@@ -1066,4 +1200,4 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
 
 
 __all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update", "FlowObjective",
-           "PredictionFlow", "make_flow", "flow_direction", "FlowScore", "BandsScore", "FreeScore", "structure_score"]
+           "PredictionFlow", "make_flow", "flow_direction", "FlowScore", "BandsScore", "FreeScore", "structure_score", "CornerMembers"]

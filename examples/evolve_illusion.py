@@ -8,6 +8,8 @@
         the 4 best genomes are replaced by those `train.refine_genomes` climbs to, before reproduction; gradient = 1 renders only;
         --objective flow --flow-direction tangent climbs the flow objective instead of the squared error;
         --flow-pairing prediction pairs consecutive predictions, as the fitness that selects does;
+        [--flow-score --flow-members corners [--flow-corner-quality Q] [--flow-corner-distance D]]   (the members of the score are the corners the fitness itself
+        would pick on every term's reference: train.CornerMembers)
         --flow-score [--flow-score-structure circles|bands|free|auto] [--flow-max-norm M] climbs the fitness's own score of that structure on the
         dense field: train.FlowScore, BandsScore or FreeScore; auto follows --structure)
 """

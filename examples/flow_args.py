@@ -1,5 +1,6 @@
 """The --flow-* options of examples/refine_illusion.py, refine_genomes.py, evolve_illusion.py and scripts/train_bench.py, and the flow
-objective they state (train.make_flow).  The choices are those of train.FLOW_DIRECTIONS, FLOW_REFERENCES and FLOW_PAIRINGS; --flow-score, --flow-score-structure and --flow-max-norm state a train.FlowScore, BandsScore or FreeScore."""
+objective they state (train.make_flow).  The choices are those of train.FLOW_DIRECTIONS, FLOW_REFERENCES and FLOW_PAIRINGS; --flow-score, --flow-score-structure and --flow-max-norm state a train.FlowScore, BandsScore or FreeScore; --flow-members, --flow-corner-quality and
+--flow-corner-distance a train.CornerMembers."""
 
 SCORE_STRUCTURES = {"bands": 0, "circles": 1, "free": 2}   # --flow-score-structure -> the fitness's number of the structure
 
@@ -21,6 +22,11 @@ FLOW_ARGUMENTS = {
                                  "or auto, the script's own --structure"),
     "max-norm": dict(type=float, default=None, help="--flow-score: vectors longer than this many pixels are no members (default: the fitness's own limit for the "
                                                     "chosen structure, 0.3 circles, 0.15 bands, 0.4 free)"),
+    "members": dict(default="all", choices=["all", "corners"],
+                    help="--flow-score: the pixels that can be members of the score: all the mask counts, or corners, the points goodFeaturesToTrack picks on "
+                         "every term's own reference, as the fitness does (train.CornerMembers)"),
+    "corner-quality": dict(type=float, default=0.3, help="--flow-members corners: goodFeaturesToTrack's qualityLevel (the fitness's: 0.3)"),
+    "corner-distance": dict(type=float, default=7.0, help="--flow-members corners: goodFeaturesToTrack's minDistance in pixels (the fitness's: 7)"),
 }
 
 
@@ -47,6 +53,17 @@ def score_of(a):
     return train.structure_score(structure, **({} if max_norm is None else {"max_norm": max_norm}))
 
 
+def members_of(a):
+    """the members of the command line: None under --flow-members all; else a train.CornerMembers of --flow-corner-quality and
+    --flow-corner-distance.  ValueError: corners without --flow-score"""
+    from evolutionary_illusion_generator_amd import train
+    if getattr(a, "flow_members", "all") != "corners":
+        return None
+    if not getattr(a, "flow_score", False):
+        raise ValueError("--flow-members corners needs --flow-score: the displacement modes have no members")
+    return train.CornerMembers(quality_level=getattr(a, "flow_corner_quality", 0.3), min_distance=getattr(a, "flow_corner_distance", 7.0))
+
+
 def flow_of(a, w, h, mask=None):
     """the FlowObjective of the command line (None under another objective); the term counts the pixels of `mask`"""
     from evolutionary_illusion_generator_amd import train
@@ -54,4 +71,4 @@ def flow_of(a, w, h, mask=None):
         return None
     score = score_of(a)
     return train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask,
-                           reference=a.flow_reference, score=score)
+                           reference=a.flow_reference, score=score, members=members_of(a))

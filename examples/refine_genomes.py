@@ -10,6 +10,8 @@ fitness of each before and after.  Whether the fitness follows the stand-in is a
     python examples/refine_genomes.py [-m model.npz] [--size small|N] [-s 1] [-c 3] [--pop 16] [-k 4] [--iters 10] [--lr 0.02]
     python examples/refine_genomes.py --objective flow --flow-direction tangent [--flow-radius 7] [--flow-eps 1e-2] [--flow-reference constant|moving]
         [--flow-pairing frame|prediction]   (prediction: the flow between consecutive predictions, the pairing of the fitness printed here)
+        [--flow-score --flow-members corners [--flow-corner-quality Q] [--flow-corner-distance D]]   (the members of the score are the corners the fitness itself
+        would pick on every term's reference: train.CornerMembers)
         [--flow-score [--flow-score-structure circles|bands|free|auto] [--flow-max-norm M]]   (climb the fitness's own score of that structure on the
         dense field: train.FlowScore, BandsScore or FreeScore; auto follows --structure; no --flow-direction)
     python examples/refine_genomes.py -o refined      (PNGs, and best.png / enhanced.png ... of the best refined genome)

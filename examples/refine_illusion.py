@@ -11,6 +11,8 @@ every image before and after.  Whether the fitness follows the stand-in is an ob
     python examples/refine_illusion.py --png image.png -o refined
     python examples/refine_illusion.py --objective flow --flow-direction tangent [--flow-radius 7] [--flow-eps 1e-2] [--flow-reference constant|moving]
         [--flow-pairing frame|prediction]   (prediction: the flow between consecutive predictions, the pairing of the fitness printed here)
+        [--flow-score --flow-members corners [--flow-corner-quality Q] [--flow-corner-distance D]]   (the members of the score are the corners the fitness itself
+        would pick on every term's reference: train.CornerMembers)
         [--flow-score [--flow-score-structure circles|bands|free|auto] [--flow-max-norm M]]   (climb the fitness's own score of that structure on the
         dense field: train.FlowScore, BandsScore or FreeScore; auto follows --structure; no --flow-direction)
         (climb the displacement a dense Lucas-Kanade solve finds between the still and the prediction, inside the structure)

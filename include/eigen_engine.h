@@ -601,6 +601,64 @@ int eigen_trainer_loss_grad_flow_structure(eigen_trainer* t, const uint8_t* d_fr
                                            const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_structure_score* score,
                                            void* stream);
 
+/* Per-sample membership of the scores of EIGEN_OBJ_FLOW ("The corner members"; csrc/flow_corner_kernels.h).  A score's
+ * member rule reads "the mask counts the pixel"; with members that mask is one plane per sample: the mask byte of sample b, pixel p is
+ * mask[b * mask_bstride + p].  The score's geometric rule and its norm limits apply on top, and membership stays a constant of the graph.
+ *   EIGEN_FLOW_MEMBERS_MASK: d_mask holds the planes, mask_bstride >= H*W bytes apart.  A plane set that counts no pixel at all is
+ *     refused; a single sample that counts none scores 0.
+ *   EIGEN_FLOW_MEMBERS_CORNERS: the members of a term are the corners the fitness would pick on the term's own reference, derived on the
+ *     device in front of the term's stage: the reference as bytes (a byte reference as it is; a float one clamped to [0, 1], then
+ *     (uint8_t)(int)(v * 255.0f), the byte a self-fed step reads), then cvtColor / cornerMinEigenVal(block_size, 3) /
+ *     goodFeaturesToTrack(max_corners, quality_level, min_distance) with eigen_flow's own kernels.  d_mask, if given, is the shared
+ *     [H][W] plane: a corner it does not count is no member.  The workspace is allocated by the first call that needs it and freed with the
+ *     handle; eigen_trainer_tape_bytes does not count it. */
+enum { EIGEN_FLOW_MEMBERS_MASK = 0, EIGEN_FLOW_MEMBERS_CORNERS = 1 };
+typedef struct {
+    int32_t kind;            /* MASK: d_mask holds one plane per sample; CORNERS: derived from each term's reference */
+    int32_t max_corners;     /* CORNERS: 1 .. 128 */
+    int32_t block_size, reserved; /* block_size, CORNERS: 1 .. 9, what mineig_kernel's staged tile holds; reserved: 0 */
+    double quality_level;    /* CORNERS: in (0, 1] */
+    double min_distance;     /* CORNERS: finite, >= 0 */
+    int64_t mask_bstride;    /* MASK: >= H*W; CORNERS: 0 (d_mask, if given, is the shared [H][W] plane) */
+} eigen_flow_members;
+
+/* The membership stage alone (kind EIGEN_FLOW_MEMBERS_CORNERS): the corners of batch references, bytes (d_ref) or floats (d_fref), exactly
+ * one of the two non-NULL, sample b at + b * r_bstride elements.  h_members (host, may be NULL) receives uint8 [batch][H][W], 1 at every
+ * corner the shared plane d_mask (may be NULL) counts; h_counts (host, may be NULL) int32 [batch], the corners selected per sample, before
+ * the mask.  The call synchronises the stream.
+ * Errors: EIGEN_ERR_INVALID, before any launch: a NULL handle or members, both or neither reference, batch < 1, r_bstride < C*H*W, a kind
+ * other than CORNERS, reserved != 0, max_corners outside 1 .. 128, block_size outside 1 .. 9, quality_level outside (0, 1], min_distance
+ * negative or not finite, mask_bstride != 0; EIGEN_ERR_CAPACITY batch above max_batch. */
+int eigen_trainer_flow_members(eigen_trainer* t, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride, int32_t batch,
+                               const eigen_flow_members* members, const uint8_t* d_mask, uint8_t* h_members, int32_t* h_counts, void* stream);
+
+/* The flow stage alone, the widest entry: eigen_trainer_flow_term_score's arguments with exactly one of score and sscore non-NULL, plus
+ * members (NULL: the call IS eigen_trainer_flow_term_score / eigen_trainer_flow_term_structure, launch for launch and bit for bit).
+ * Under CORNERS the membership stage runs on the call's reference in front of the stage.
+ * Errors: as those two entries; EIGEN_ERR_INVALID, before any launch: members without a score (the displacement modes divide by a
+ * host-side mask count), both scores, an unknown kind, reserved != 0, a field outside the range the struct states, MASK with
+ * mask_bstride < H*W or without d_mask or with planes that count no pixel at all; the message names the field. */
+int eigen_trainer_flow_term_members(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref,
+                                    int64_t r_bstride, int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask,
+                                    const eigen_flow_score* score, const eigen_flow_structure_score* sscore, const eigen_flow_members* members,
+                                    double scale, double* h_value, double* h_stats, double* d_flow, float* d_seed, int64_t s_bstride,
+                                    float* d_ref_grad, int64_t rg_bstride, void* stream);
+
+/* The widest training entry: eigen_trainer_loss_grad_flow_score and eigen_trainer_loss_grad_flow_structure in one (at most one of score
+ * and sscore non-NULL) plus members and h_stats.  members == NULL and h_stats == NULL: the call IS the entry of its score, launch for
+ * launch and bit for bit.  Under CORNERS every term of non-zero weight runs the membership stage on its own reference in front of its
+ * stage: frame s + 1 under the frame pairing, P0_{s-1} under the prediction pairing (for s = 0 the start state's P: after a reset it is
+ * zero, there are no corners, and the term is 0 with no gradient).  h_stats (host, may be NULL; read with a score only) receives
+ * double[n_steps - 1][batch][10], the samples' records of every computed term and zeros for the others.
+ * Errors: as those entries and eigen_trainer_flow_term_members; EIGEN_ERR_INVALID members under another objective. */
+int eigen_trainer_loss_grad_flow_members(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                         int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                         const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                         int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                         const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score,
+                                         const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double* h_stats,
+                                         void* stream);
+
 /* One normalised ascent step on uint8 stills d_images [batch][C][H][W], in place, from a tied gradient (image b at d_grad + b *
  * g_bstride floats): per image m_b = max |g| over the pixels the mask keeps free, then x = byte / 255.0f,
  * x' = min(max(x + k * (g / m_b), 0), 1) with k = (float)(step_bytes / 255.0), byte' = (uint8_t)(int)(x' * 255.0f + 0.5f), each one

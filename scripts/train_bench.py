@@ -32,7 +32,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from examples.flow_args import add_flow_arguments, score_of  # noqa: E402
+from examples.flow_args import add_flow_arguments, members_of, score_of  # noqa: E402
 
 W, H, CH, B, T = 160, 120, [3, 48, 96, 192], 16, 10
 GATES = ("i", "f", "c", "o")
@@ -65,14 +65,14 @@ def frames(seed, n, T, c, h, w):
 FLOW_WEIGHTS = [0.0] * (T - 3) + [1.0, 1.0]   # two weighted terms, as a refinement call has them
 
 
-def objective_args(name, reference="constant", pairing="frame", score=None):
+def objective_args(name, reference="constant", pairing="frame", score=None, members=None):
     if name == "flow":
         from evolutionary_illusion_generator_amd.train import make_flow
-        return dict(objective="flow", flow=make_flow(pairing, radius=7, eps=1e-2, reference=reference, score=score), step_weights=FLOW_WEIGHTS)
+        return dict(objective="flow", flow=make_flow(pairing, radius=7, eps=1e-2, reference=reference, score=score, members=members), step_weights=FLOW_WEIGHTS)
     return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
 
 
-def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None):
+def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None, members=None):
     """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round; with
     the moving reference also per "flow" call with tied frame gradients, under either reference"""
     import ctypes
@@ -88,6 +88,8 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"
         calls["flow_prediction"] = objective_args("flow", pairing="prediction")
     if score is not None:
         calls["flow_score"] = objective_args("flow", reference, pairing, score)
+    if members is not None:
+        calls["flow_score_corners"] = objective_args("flow", reference, pairing, score, members)
     ms = {k: [] for k in calls}
     loss = {}
     with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
@@ -113,13 +115,13 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"
     return [dict(side="loss_grad_" + k, call_ms=float(np.median(v)), call_ms_min=min(v), call_ms_max=max(v), rounds=rounds, loss=loss[k]) for k, v in ms.items()]
 
 
-def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None):
+def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None, members=None):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
     d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
     tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T)
-    kw = objective_args(objective, reference, pairing, score) if objective == "flow" else objective_args(objective)
+    kw = objective_args(objective, reference, pairing, score, members) if objective == "flow" else objective_args(objective)
     for _ in range(warmup):
         tr.step(d, **kw)
     torch.cuda.synchronize()
@@ -251,7 +253,7 @@ def main():
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
     ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall", "flow"], help="the trainer side's objective")
     ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
-    add_flow_arguments(ap, ("reference", "pairing", "score", "score-structure", "max-norm"), **{"score-structure": dict(choices=["circles", "bands", "free"])}, reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
+    add_flow_arguments(ap, ("reference", "pairing", "score", "score-structure", "max-norm", "members", "corner-quality", "corner-distance"), **{"score-structure": dict(choices=["circles", "bands", "free"])}, reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
                        pairing=dict(help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)"))
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
@@ -260,6 +262,10 @@ def main():
     if a.flow_pairing == "prediction" and a.flow_reference == "moving":
         ap.error("--flow-pairing prediction has no frame as a reference: it does not take --flow-reference moving")
     score = score_of(a)
+    try:
+        members = members_of(a)
+    except ValueError as e:
+        ap.error(str(e))
     if a.side == "torch":
         print(json.dumps(run_torch(a.steps, a.warmup)))
         return
@@ -268,10 +274,10 @@ def main():
             print(json.dumps(r), flush=True)
         return
     if a.flow_cost:
-        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score):
+        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score, members=members):
             print(json.dumps(r), flush=True)
         return
-    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score)]
+    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members)]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
