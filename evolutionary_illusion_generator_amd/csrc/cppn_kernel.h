@@ -112,7 +112,8 @@ __global__ void __launch_bounds__(CPPN_THREADS) cppn_render_kernel(const CppnArg
                 x = (li >= a.n_planes) ? 1.0 : (li == 0 ? leaf[0] : li == 1 ? leaf[1] : li == 2 ? leaf[2] : leaf[3]);
             }
             const double term = s_ew[k] * x;
-            sum = (k == b) ? term : sum + term;   // Python sum(): 0 + t0 == t0
+            // Python sum(): 0 + t0 == t0, but for the sign of a zero: a first term of -0.0 stays -0.0 here and is +0.0 there (no byte depends on it)
+            sum = (k == b) ? term : sum + term;
         }
         const double pre = s_resp[n] * sum;
         vals[(size_t)n * CPPN_THREADS + tid] = cppn_act(s_act[n], pre + s_bias[n]);
