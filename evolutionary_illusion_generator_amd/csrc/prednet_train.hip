@@ -1,7 +1,8 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
 // the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for the flow objective
-// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h, flow_score_kernels.h, flow_struct_kernels.h and flow_corner_kernels.h.
+// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h, flow_score_kernels.h, flow_struct_kernels.h and flow_corner_kernels.h, and for
+// the optimiser controls (gradient norms, accumulation, clipping, weight decay) optim_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include "flow_score_kernels.h"
 #include "flow_struct_kernels.h"
 #include "flow_corner_kernels.h"
+#include "optim_kernels.h"
 
 using namespace eigt;
 
@@ -113,6 +115,14 @@ struct eigen_trainer {
     unsigned long long* c_cand = nullptr;
     int* c_count = nullptr;
     double* f_stats = nullptr;  // the records of a training call's terms [max_steps][max_batch][SCORE_REC], made by the first call that asks for them
+    // the optimiser controls' (optim_kernels.h): the (offset, count) of every tensor [n_tensors][2], the partials of the sums of squares
+    // [n_tensors][NORM_SLICES], the sums [n_tensors] and the global norm [1]; the gradient accumulator [n_params], made by the first
+    // call that adds to it (accumulator), and how many gradients it holds (0: empty)
+    int n_tensors = 0;
+    long long* o_tab = nullptr;
+    double *o_part = nullptr, *o_sumsq = nullptr, *o_norm = nullptr;
+    float* acc = nullptr;
+    int acc_count = 0;
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -278,6 +288,10 @@ int allocate(eigen_trainer* t)
     add((void**)&t->f_g, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_srec, B * STRUCT_REC * 8); add((void**)&t->f_sspart, B * STRUCT_SLICES * STRUCT_K * 8);
     add((void**)&t->f_theta, B * t->ly[0].HW * 8); add((void**)&t->f_L, B * t->ly[0].HW * 8);
     add((void**)&t->f_rowS, B * t->ly[0].HW * 4); add((void**)&t->f_colS, B * t->ly[0].HW * 4); add((void**)&t->f_flag, B * t->ly[0].HW);
+    // and behind it the optimiser controls' tensor table and reduction buffers
+    const Table tab = tensor_table(t);
+    const long long nt = t->n_tensors = (int)tab.size();
+    add((void**)&t->o_tab, nt * 16); add((void**)&t->o_part, nt * NORM_SLICES * 8); add((void**)&t->o_sumsq, nt * 8); add((void**)&t->o_norm, 8);
     for (auto& w : want) {
         const hipError_t e = hipMalloc(w.first, w.second);
         if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%zu): %s", w.second, hipGetErrorString(e));
@@ -285,7 +299,11 @@ int allocate(eigen_trainer* t)
     }
     hipError_t e = hipMemset(t->grd, 0, np * 4);
     if (e == hipSuccess) e = hipMemset(t->prm, 0, np * 4);
-    return e == hipSuccess ? EIGEN_OK : tfail(EIGEN_ERR_HIP, "hipMemset: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMemset: %s", hipGetErrorString(e));
+    std::vector<long long> flat;
+    for (const auto& r : tab) { flat.push_back(r.first); flat.push_back(r.second); }
+    TCHK(hipMemcpy(t->o_tab, flat.data(), flat.size() * 8, hipMemcpyHostToDevice));
+    return EIGEN_OK;
 }
 
 // Up to two host tables (eigen_set_prednet_weights order) to or from the flat device arrays d0, d1: h1 / d1 may be null.  The count and every
@@ -1110,6 +1128,38 @@ int evaluate_call(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, in
     return EIGEN_OK;
 }
 
+// what eigen_trainer_adam accepts, and its refusal
+bool adam_values_ok(double alpha, double beta1, double beta2, double eps) { return alpha > 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps > 0; }
+int refuse_adam_values() { return tfail(EIGEN_ERR_INVALID, "Adam needs alpha > 0, 0 <= beta1, beta2 < 1 and eps > 0"); }
+
+// the one launch of eigen_trainer_adam: the step count advances, tadam_kernel runs on the gradient table
+void plain_adam(eigen_trainer* t, double alpha, double beta1, double beta2, double eps, hipStream_t st)
+{
+    const int step = ++t->adam_t;
+    const double lr_t = alpha * std::sqrt(1.0 - std::pow(beta2, step)) / (1.0 - std::pow(beta1, step));
+    ew(st, tadam_kernel, t->n_params, t->prm, t->mom, t->var, (const float*)t->grd, t->n_params, (float)lr_t, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+}
+
+// the sums of squares of every tensor of the gradient table into o_sumsq and the global norm into o_norm, on the device
+void grad_norms(eigen_trainer* t, hipStream_t st)
+{
+    hipLaunchKernelGGL(tgrad_sumsq_kernel, dim3(NORM_SLICES, (unsigned)t->n_tensors), dim3(EW_T), 0, st, (const float*)t->grd, (const long long*)t->o_tab, t->o_part);
+    hipLaunchKernelGGL(tgrad_norm_final_kernel, dim3(1), dim3(NORM_FINAL_T), 0, st, (const double*)t->o_part, NORM_SLICES, t->n_tensors, t->o_sumsq, t->o_norm);
+}
+
+// The gradient accumulator, n_params floats, made by the first call that adds to it and freed with the handle; eigen_trainer_tape_bytes
+// does not count it
+int accumulator(eigen_trainer* t)
+{
+    if (t->acc) return EIGEN_OK;
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, (size_t)t->n_params * 4);
+    if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%lld): %s", t->n_params * 4, hipGetErrorString(e));
+    t->acc = (float*)p;
+    t->allocs.push_back(p);
+    return EIGEN_OK;
+}
+
 // EIGEN_OBJ_FLOW through an entry that has nowhere to take the flow settings from
 int refuse_flow_objective() { return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs the settings eigen_trainer_loss_grad_flow takes"); }
 
@@ -1165,6 +1215,7 @@ int eigen_trainer_set_weights(eigen_trainer* t, const float* const* h_tensors, i
     t->have_weights = true;
     t->adam_t = 0;
     t->state_batch = 0;
+    t->acc_count = 0;
     return EIGEN_OK;
 }
 
@@ -1507,14 +1558,94 @@ int eigen_trainer_adam(eigen_trainer* t, double alpha, double beta1, double beta
 {
     if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
-    if (!(alpha > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
-        return tfail(EIGEN_ERR_INVALID, "Adam needs alpha > 0, 0 <= beta1, beta2 < 1 and eps > 0");
+    if (!adam_values_ok(alpha, beta1, beta2, eps)) return refuse_adam_values();
     TCHK(hipSetDevice(t->cfg.device));
-    const int step = ++t->adam_t;
-    const double lr_t = alpha * std::sqrt(1.0 - std::pow(beta2, step)) / (1.0 - std::pow(beta1, step));
-    ew((hipStream_t)stream, tadam_kernel, t->n_params, t->prm, t->mom, t->var, (const float*)t->grd, t->n_params, (float)lr_t, (float)(1.0 - beta1),
-       (float)(1.0 - beta2), (float)eps);
+    plain_adam(t, alpha, beta1, beta2, eps, (hipStream_t)stream);
     TCHK(hipGetLastError());
+    return EIGEN_OK;
+}
+
+int eigen_trainer_grad_norms(eigen_trainer* t, double* h_global, double* h_per_tensor, int32_t n_tensors, void* stream)
+{
+    if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (n_tensors != t->n_tensors) return tfail(EIGEN_ERR_INVALID, "expected %d weight tensors for %d layers, got %d", t->n_tensors, t->L, n_tensors);
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    TCHK(hipSetDevice(t->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    grad_norms(t, st);
+    TCHK(hipGetLastError());
+    std::vector<double> sq(h_per_tensor ? t->n_tensors : 0);
+    if (h_per_tensor) TCHK(hipMemcpyAsync(sq.data(), t->o_sumsq, sq.size() * 8, hipMemcpyDeviceToHost, st));
+    if (h_global) TCHK(hipMemcpyAsync(h_global, t->o_norm, 8, hipMemcpyDeviceToHost, st));
+    if (h_per_tensor || h_global) TCHK(hipStreamSynchronize(st));
+    for (size_t k = 0; k < sq.size(); ++k) h_per_tensor[k] = std::sqrt(sq[k]);
+    return EIGEN_OK;
+}
+
+int eigen_trainer_adam_ex(eigen_trainer* t, const eigen_adam_settings* s, eigen_adam_report* h_report, void* stream)
+{
+    if (!t || !s) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (!adam_values_ok(s->alpha, s->beta1, s->beta2, s->eps)) return refuse_adam_values();
+    if (!(std::isfinite(s->weight_decay) && s->weight_decay >= 0) || !(std::isfinite(s->clip_norm) && s->clip_norm >= 0))
+        return tfail(EIGEN_ERR_INVALID, "weight_decay and clip_norm must be finite and >= 0 (0: off)");
+    if ((s->skip_nonfinite != 0 && s->skip_nonfinite != 1) || s->reserved != 0) return tfail(EIGEN_ERR_INVALID, "skip_nonfinite must be 0 or 1 and reserved 0");
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    TCHK(hipSetDevice(t->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (s->weight_decay == 0 && s->clip_norm == 0 && !s->skip_nonfinite && !h_report) {
+        plain_adam(t, s->alpha, s->beta1, s->beta2, s->eps, st);   // eigen_trainer_adam's launch, hence its bits
+        TCHK(hipGetLastError());
+        return EIGEN_OK;
+    }
+    grad_norms(t, st);
+    TCHK(hipGetLastError());
+    double norm = 0.0;
+    if (s->skip_nonfinite) {
+        TCHK(hipMemcpyAsync(&norm, t->o_norm, 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipStreamSynchronize(st));
+        if (!std::isfinite(norm)) {   // nothing is launched: weights, moments and the step count stay as they are
+            if (h_report) *h_report = eigen_adam_report{norm, 1.0, 0, 0};
+            return EIGEN_OK;
+        }
+    }
+    const int step = ++t->adam_t;
+    const double lr_t = s->alpha * std::sqrt(1.0 - std::pow(s->beta2, step)) / (1.0 - std::pow(s->beta1, step));
+    ew(st, tadam_ex_kernel, t->n_params, t->prm, t->mom, t->var, (const float*)t->grd, t->n_params, (float)lr_t, (float)(1.0 - s->beta1),
+       (float)(1.0 - s->beta2), (float)s->eps, (float)s->weight_decay, s->clip_norm, (const double*)t->o_norm);
+    TCHK(hipGetLastError());
+    if (h_report) {
+        if (!s->skip_nonfinite) {
+            TCHK(hipMemcpyAsync(&norm, t->o_norm, 8, hipMemcpyDeviceToHost, st));
+            TCHK(hipStreamSynchronize(st));
+        }
+        *h_report = eigen_adam_report{norm, (s->clip_norm > 0 && norm > s->clip_norm) ? s->clip_norm / norm : 1.0, 1, 0};
+    }
+    return EIGEN_OK;
+}
+
+int eigen_trainer_accumulate(eigen_trainer* t, int32_t op, double scale, void* stream)
+{
+    if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (op != EIGEN_ACC_CLEAR && op != EIGEN_ACC_ADD && op != EIGEN_ACC_LOAD) return tfail(EIGEN_ERR_INVALID, "unknown accumulator op %d", op);
+    if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale must be finite");
+    if (!t->have_weights) return tfail(EIGEN_ERR_STATE, "eigen_trainer_set_weights has not been called");
+    if (op == EIGEN_ACC_LOAD && t->acc_count == 0) return tfail(EIGEN_ERR_STATE, "EIGEN_ACC_LOAD with nothing accumulated");
+    TCHK(hipSetDevice(t->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)t->n_params * 4;
+    if (op == EIGEN_ACC_CLEAR) {
+        if (t->acc) TCHK(hipMemsetAsync(t->acc, 0, bytes, st));
+        t->acc_count = 0;
+    } else if (op == EIGEN_ACC_ADD) {
+        const int rc = accumulator(t);
+        if (rc) return rc;
+        if (t->acc_count == 0) TCHK(hipMemsetAsync(t->acc, 0, bytes, st));   // an empty accumulator starts from zero
+        ew(st, tgrad_axpy_kernel, t->n_params, t->acc, (const float*)t->grd, (float)scale, t->n_params);
+        TCHK(hipGetLastError());
+        ++t->acc_count;
+    } else {
+        TCHK(hipMemcpyAsync(t->grd, t->acc, bytes, hipMemcpyDeviceToDevice, st));
+    }
     return EIGEN_OK;
 }
 

@@ -27,7 +27,8 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_trainer_loss_grad_flow", "eigen_trainer_flow_term_ref", "eigen_trainer_loss_grad_flow_pair", "eigen_trainer_flow_term_pair",
            "eigen_trainer_flow_term_score", "eigen_trainer_loss_grad_flow_score", "eigen_trainer_flow_term_structure",
            "eigen_trainer_loss_grad_flow_structure", "eigen_trainer_debug_free_planes", "eigen_trainer_flow_members",
-           "eigen_trainer_flow_term_members", "eigen_trainer_loss_grad_flow_members"]
+           "eigen_trainer_flow_term_members", "eigen_trainer_loss_grad_flow_members", "eigen_trainer_grad_norms", "eigen_trainer_adam_ex",
+           "eigen_trainer_accumulate"]
 
 
 class EigenConfig(ctypes.Structure):

@@ -39,6 +39,17 @@ class FlowMembersSettings(ctypes.Structure):
                 ("quality_level", ctypes.c_double), ("min_distance", ctypes.c_double), ("mask_bstride", ctypes.c_int64)]
 
 
+class AdamSettings(ctypes.Structure):
+    """eigen_adam_settings"""
+    _fields_ = [("alpha", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("clip_norm", ctypes.c_double), ("skip_nonfinite", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AdamReport(ctypes.Structure):
+    """eigen_adam_report"""
+    _fields_ = [("norm", ctypes.c_double), ("rate", ctypes.c_double), ("applied", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class TrainerConfig(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_layers", ctypes.c_int32),
                 ("channels", ctypes.c_int32 * engine.MAX_LAYERS), ("max_batch", ctypes.c_int32), ("max_steps", ctypes.c_int32)]
@@ -97,9 +108,14 @@ def _bind(lib):
     lib.eigen_trainer_adam.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]
     lib.eigen_trainer_tape_bytes.restype = ctypes.c_int64
     lib.eigen_trainer_tape_bytes.argtypes = [ctypes.c_void_p]
+    lib.eigen_trainer_grad_norms.argtypes = [_P, _PD, _PD, _I32, _P]                                                       # t, h_global, h_per_tensor, n_tensors, stream
+    lib.eigen_trainer_adam_ex.argtypes = [_P, ctypes.POINTER(AdamSettings), ctypes.POINTER(AdamReport), _P]                # t, settings, h_report, stream
+    lib.eigen_trainer_accumulate.argtypes = [_P, _I32, ctypes.c_double, _P]                                                # t, op, scale, stream
     lib._trainer_bound = True
 
 HYPER = ("alpha", "beta1", "beta2", "eps")
+OPTIM = ("clip_norm", "weight_decay", "skip_nonfinite")  # the optimiser controls; neutral: (None, 0.0, False)
+ACC_CLEAR, ACC_ADD, ACC_LOAD = 0, 1, 2  # EIGEN_ACC_CLEAR, EIGEN_ACC_ADD, EIGEN_ACC_LOAD
 SEQ_PARTS = ("h", "c", "P")
 OBJECTIVES = {"mse": 0, "error": 1, "flow": 2}  # eigen_objective
 FRAME_GRADS = (None, "frames", "tied")
@@ -473,6 +489,52 @@ def check_layer_weights(layer_weights, n_layers):
     return lam
 
 
+def check_optim(clip_norm=None, weight_decay=0.0, skip_nonfinite=False):
+    """The optimiser controls of ``PredNetTrainer`` as (clip_norm: None or float > 0, weight_decay: float >= 0, skip_nonfinite: bool).
+    ValueError: a clip_norm that is not None and not finite or <= 0 (None is "no clipping"), a weight_decay that is negative or not
+    finite, a skip_nonfinite that is not a bool, a bool or a non-number where a number goes."""
+    def number(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number, got %r" % (name, v))
+        return float(v)
+    if clip_norm is not None:
+        clip_norm = number("clip_norm", clip_norm)
+        if not (np.isfinite(clip_norm) and clip_norm > 0):
+            raise ValueError("clip_norm must be None (no clipping) or finite and > 0, got %r" % (clip_norm,))
+    weight_decay = number("weight_decay", weight_decay)
+    if not (np.isfinite(weight_decay) and weight_decay >= 0):
+        raise ValueError("weight_decay must be finite and >= 0, got %r" % (weight_decay,))
+    if not isinstance(skip_nonfinite, (bool, np.bool_)):
+        raise ValueError("skip_nonfinite must be True or False, got %r" % (skip_nonfinite,))
+    return clip_norm, weight_decay, bool(skip_nonfinite)
+
+
+def optim_is_neutral(clip_norm, weight_decay, skip_nonfinite):
+    """whether the three controls leave ``adam()`` on the plain entry"""
+    return clip_norm is None and weight_decay == 0.0 and not skip_nonfinite
+
+
+def check_micro_batches(n, micro_batches, batch, reset=True, flow=None):
+    """The rules of ``PredNetTrainer.step(micro_batches=k)`` for n sequences on a handle of `batch`: -> n / k, the sequences per chunk.
+    ValueError: k not an integer >= 1; and for k > 1: n not a multiple of k, n / k above the handle's batch, reset=False (the handle
+    keeps one sequence state per batch, not one per chunk), a flow objective with a per-sample [n, H, W] mask (not sliced here)."""
+    k = micro_batches
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError("micro_batches must be an integer >= 1, got %r" % (k,))
+    k = int(k)
+    if k == 1:
+        return int(n)
+    if n % k:
+        raise ValueError("%d sequences do not divide into %d micro-batches" % (n, k))
+    if n // k > batch:
+        raise ValueError("a micro-batch of %d sequences exceeds the trainer's batch %d" % (n // k, batch))
+    if not reset:
+        raise ValueError("micro_batches > 1 needs reset=True: the handle keeps one sequence state per batch, not one per micro-batch")
+    if flow is not None and getattr(flow, "per_sample", False):
+        raise ValueError("a per-sample [n, H, W] flow mask is not sliced across micro-batches")
+    return n // k
+
+
 def combine_terms(table, layer_weights=None, step_weights=None):
     """The loss of the error-unit objective from the table err[s][l] (float64 [T - 1, L]), as the library forms it: in double,
     sum_s w_s (sum_l lambda_l err[s][l]) / sum_s w_s, added in (step, layer) order.  layer_weights None: L_0, [1, 0, ...];
@@ -516,6 +578,11 @@ def check_state(state, channels, w, h, max_batch=None):
     out = {"adam_t": int(state["adam_t"]), "hyper": {k: float(v) for k, v in dict(state.get("hyper") or {}).items()}}
     if out["adam_t"] < 0:
         raise ValueError("adam_t must be >= 0, got %d" % out["adam_t"])
+    if state.get("optim") is not None:      # the optimiser controls travel only when one of them is not neutral
+        opt = dict(state["optim"])
+        if set(opt) - set(OPTIM):
+            raise ValueError("optim holds unknown settings %s" % sorted(set(opt) - set(OPTIM)))
+        out["optim"] = dict(zip(OPTIM, check_optim(**opt)))
     for key in ("adam_m", "adam_v"):
         tab = state[key]
         if sorted(tab) != sorted(shapes):
@@ -548,8 +615,9 @@ def check_state(state, channels, w, h, max_batch=None):
 
 def write_checkpoint(path, weights, state):
     """ONE npz: the weights under the ``predictor/<name>`` keys of ``weights.save_chainer_npz`` (so ``weights.load_chainer_npz``
-    reads the file), plus ``adam/m/<name>``, ``adam/v/<name>``, ``adam/t``, ``hyper/<alpha|beta1|beta2|eps>`` and, when a sequence
-    state is kept, ``seq/<h|c|P>/<layer>``."""
+    reads the file), plus ``adam/m/<name>``, ``adam/v/<name>``, ``adam/t``, ``hyper/<alpha|beta1|beta2|eps>``, when a sequence
+    state is kept ``seq/<h|c|P>/<layer>``, and, when state["optim"] holds a control that is not neutral,
+    ``optim/<clip_norm|weight_decay|skip_nonfinite>`` (clip_norm 0: none).  A neutral trainer's file has no ``optim/*`` entry."""
     arrs = {"predictor/" + k: np.ascontiguousarray(v, dtype=np.float32) for k, v in weights.items()}
     for k, v in state["adam_m"].items():
         arrs["adam/m/" + k] = np.ascontiguousarray(v, dtype=np.float32)
@@ -558,6 +626,11 @@ def write_checkpoint(path, weights, state):
     arrs["adam/t"] = np.asarray(int(state["adam_t"]), np.int64)
     for k, v in (state.get("hyper") or {}).items():
         arrs["hyper/" + k] = np.asarray(float(v), np.float64)
+    if state.get("optim") is not None and not optim_is_neutral(*check_optim(**state["optim"])):
+        clip, wd, skip = check_optim(**state["optim"])
+        arrs["optim/clip_norm"] = np.asarray(0.0 if clip is None else clip, np.float64)     # 0: no clipping, as eigen_adam_settings spells it
+        arrs["optim/weight_decay"] = np.asarray(wd, np.float64)
+        arrs["optim/skip_nonfinite"] = np.asarray(int(skip), np.int64)
     if state.get("seq") is not None:
         for part in SEQ_PARTS:
             for l, a in enumerate(state["seq"][part]):
@@ -580,6 +653,11 @@ def read_checkpoint(path, channels, w, h):
             raise KeyError("checkpoint %s lacks adam/t" % path)
         state = {"adam_m": {n: z["adam/m/" + n] for n in wts}, "adam_v": {n: z["adam/v/" + n] for n in wts}, "adam_t": int(z["adam/t"]),
                  "hyper": {k: float(z["hyper/" + k]) for k in HYPER if "hyper/" + k in files}, "seq": None}
+        if any(("optim/" + k) in files for k in OPTIM):     # a file without them (a neutral or an earlier trainer's) loads as neutral
+            clip = float(z["optim/clip_norm"]) if "optim/clip_norm" in files else 0.0
+            state["optim"] = {"clip_norm": clip if clip != 0.0 else None,
+                              "weight_decay": float(z["optim/weight_decay"]) if "optim/weight_decay" in files else 0.0,
+                              "skip_nonfinite": bool(int(z["optim/skip_nonfinite"])) if "optim/skip_nonfinite" in files else False}
         if "seq/h/0" in files:
             try:
                 state["seq"] = {part: [z["seq/%s/%d" % (part, l)] for l in range(len(channels))] for part in SEQ_PARTS}
@@ -592,11 +670,20 @@ class PredNetTrainer:
     """One trainer handle on the current HIP device.  batch and max_steps size the tape (``tape_bytes``).
 
     model_name: anything ``fitness._resolve_weights`` takes (a weight dict, ``"synthetic[:seed]"`` or a chainer npz path): the
-    starting weights.  alpha, beta1, beta2, eps: Adam (chainer's defaults)."""
+    starting weights.  alpha, beta1, beta2, eps: Adam (chainer's defaults).
 
-    def __init__(self, model_name, channels, w, h, batch, max_steps, alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, device=None):
+    The optimiser controls ("Optimiser controls"; ``check_optim`` states their rules, ValueError): clip_norm, None
+    or the global L2 norm above which the gradient of a step is scaled down to it (chainer's GradientClipping); weight_decay, the
+    weight_decay_rate of chainer's AdamRule, p -= lr_t m / (sqrt(v) + eps) + weight_decay p; skip_nonfinite, a step whose gradient
+    norm is not finite is not taken.  They are plain attributes and may be changed between steps.  With all three neutral (the
+    defaults) ``adam()`` is the plain entry and its bits; otherwise it leaves what it did in ``last_update``."""
+
+    def __init__(self, model_name, channels, w, h, batch, max_steps, alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, device=None, clip_norm=None,
+                 weight_decay=0.0, skip_nonfinite=False):
         import torch
         from .fitness import _local_device, _resolve_weights
+        self.clip_norm, self.weight_decay, self.skip_nonfinite = check_optim(clip_norm, weight_decay, skip_nonfinite)
+        self.last_update = {"norm": None, "rate": None, "applied": None}
         self.lib = engine.load_library()
         _bind(self.lib)
         self.channels, self.w, self.h = [int(c) for c in channels], int(w), int(h)
@@ -619,7 +706,7 @@ class PredNetTrainer:
 
     # -- weights -------------------------------------------------------------------------------------
     def set_weights(self, weights):
-        """Load a weight table; clears the Adam moments and step count and any kept sequence state."""
+        """Load a weight table; clears the Adam moments and step count, any kept sequence state and what was accumulated."""
         arrs = []
         for n in self._names:
             a = np.ascontiguousarray(weights[n], dtype=np.float32)
@@ -909,21 +996,85 @@ class PredNetTrainer:
         loss = self.forward_backward(frames, reset)
         return loss, self.grads()
 
-    def adam(self, stream=None):
-        """One Adam step on the current gradients."""
-        _check(self.lib.eigen_trainer_adam(self._h, self.alpha, self.beta1, self.beta2, self.eps, _stream_arg(stream)))
+    def grad_norms(self, stream=None):
+        """The L2 norms of the current gradients, computed on the device in float64 (eigen_trainer_grad_norms): (global, {name: norm}).
+        A norm that is not finite is returned as it is."""
+        total, per = ctypes.c_double(0.0), np.zeros(len(self._names), np.float64)
+        _check(self.lib.eigen_trainer_grad_norms(self._h, ctypes.byref(total), per.ctypes.data_as(_PD), ctypes.c_int32(len(self._names)), _stream_arg(stream)))
+        return total.value, {n: float(v) for n, v in zip(self._names, per)}
 
-    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None, objective="mse", layer_weights=None, flow=None):
-        """Gradient and one Adam step; returns the loss before the step."""
-        loss = self.forward_backward(frames, reset, n_fed=n_fed, requant=requant, step_weights=step_weights, objective=objective,
-                                     layer_weights=layer_weights, flow=flow)
+    def accumulate(self, scale=1.0, stream=None):
+        """Add scale times the current gradients to the accumulator, on the device: acc = acc + float32(scale) * g, each rounded once;
+        the first addition after ``clear_accumulated`` (or ``set_weights``, or the trainer's start) starts from zero.  ValueError: a
+        scale that is not finite."""
+        scale = float(scale)
+        if not np.isfinite(scale):
+            raise ValueError("scale must be finite, got %r" % (scale,))
+        _check(self.lib.eigen_trainer_accumulate(self._h, ctypes.c_int32(ACC_ADD), ctypes.c_double(scale), _stream_arg(stream)))
+
+    def clear_accumulated(self, stream=None):
+        """Empty the accumulator."""
+        _check(self.lib.eigen_trainer_accumulate(self._h, ctypes.c_int32(ACC_CLEAR), ctypes.c_double(0.0), _stream_arg(stream)))
+
+    def load_accumulated(self, stream=None):
+        """Make the accumulated sum the current gradients (``grads()``, ``grad_norms()`` and ``adam()`` then see it); the accumulator keeps
+        its contents.  EngineError -3: nothing was accumulated."""
+        _check(self.lib.eigen_trainer_accumulate(self._h, ctypes.c_int32(ACC_LOAD), ctypes.c_double(0.0), _stream_arg(stream)))
+
+    def adam(self, stream=None):
+        """One Adam step on the current gradients.  Under neutral controls this is eigen_trainer_adam and ``last_update`` holds None
+        thrice: nothing is read back.  Otherwise eigen_trainer_adam_ex clips, decays and, under skip_nonfinite, leaves out a step whose
+        norm is not finite; ``last_update`` = {"norm": the global gradient norm, "rate": the factor the gradient was scaled by, "applied":
+        1, or 0 for a step that was left out}.  Without skip_nonfinite a gradient that is not finite is applied."""
+        clip, wd, skip = check_optim(self.clip_norm, self.weight_decay, self.skip_nonfinite)
+        if optim_is_neutral(clip, wd, skip):
+            _check(self.lib.eigen_trainer_adam(self._h, self.alpha, self.beta1, self.beta2, self.eps, _stream_arg(stream)))
+            self.last_update = {"norm": None, "rate": None, "applied": None}
+            return
+        cfg = AdamSettings(self.alpha, self.beta1, self.beta2, self.eps, wd, 0.0 if clip is None else clip, int(skip), 0)
+        rep = AdamReport()
+        _check(self.lib.eigen_trainer_adam_ex(self._h, ctypes.byref(cfg), ctypes.byref(rep), _stream_arg(stream)))
+        self.last_update = {"norm": rep.norm, "rate": rep.rate, "applied": int(rep.applied)}
+
+    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None, objective="mse", layer_weights=None, micro_batches=1, flow=None):
+        """Gradient and one Adam step; returns the loss before the step.  (`flow` stays the last argument, as in every call that takes
+        one; it was the eighth positional one before `micro_batches` existed, and such a call still means it.)
+
+        micro_batches = k > 1: the n sequences are cut into k equal chunks in order, each runs ``forward_backward`` with reset=True and is
+        added to the accumulator with scale 1 / k, the sum becomes the gradient and ONE Adam step is taken.  Every objective is a mean
+        over the samples, so in real arithmetic that is the full batch's gradient: a handle of batch n / k trains a logical batch of n.
+        The loss returned is sum_j loss_j / k, formed in double in chunk order.  ``check_micro_batches`` states the rules (ValueError)."""
+        if isinstance(micro_batches, FlowObjective) and flow is None:
+            micro_batches, flow = 1, micro_batches
+        kw = dict(n_fed=n_fed, requant=requant, step_weights=step_weights, objective=objective, layer_weights=layer_weights, flow=flow)
+        if micro_batches == 1 and not isinstance(micro_batches, bool):     # the call as it always was: the accumulator is not touched
+            loss = self.forward_backward(frames, reset, **kw)
+            self.adam()
+            return loss
+        loss = self.accumulate_micro_batches(frames, micro_batches, reset=reset, **kw)
+        self.load_accumulated()
         self.adam()
         return loss
+
+    def accumulate_micro_batches(self, frames, micro_batches, reset=True, **kw):
+        """The gradient half of ``step(micro_batches=k)``: empties the accumulator, runs the k chunks of `frames` and adds each with scale
+        1 / k; -> sum_j loss_j / k.  ``load_accumulated()`` then makes the sum the gradient.  kw: ``forward_backward``'s n_fed, requant,
+        step_weights, objective, layer_weights and flow."""
+        d = self._frames(frames)
+        m = check_micro_batches(int(d.shape[0]), micro_batches, self.batch, reset, kw.get("flow"))
+        k = int(micro_batches)
+        self.clear_accumulated()
+        total = 0.0
+        for j in range(k):
+            total += float(self.forward_backward(d[j * m:(j + 1) * m], True, **kw))
+            self.accumulate(1.0 / k)
+        return total / k
 
     # -- state in and out ------------------------------------------------------------------------------
     def state_dict(self):
         """Everything a continued run needs besides ``weights()``: {"adam_m", "adam_v": {name: float32 array}, "adam_t": int,
-        "hyper": {alpha, beta1, beta2, eps}, "seq": None or {"h", "c", "P": [one float32 [n, C_l, H_l, W_l] per layer]}}."""
+        "hyper": {alpha, beta1, beta2, eps}, "seq": None or {"h", "c", "P": [one float32 [n, C_l, H_l, W_l] per layer]}} and, when
+        one of the optimiser controls is not neutral, "optim": {clip_norm, weight_decay, skip_nonfinite}."""
         m, v = self._empty(), self._empty()
         t, nb = ctypes.c_int32(0), ctypes.c_int32(0)
         _check(self.lib.eigen_trainer_get_state(self._h, self._table([m[n] for n in self._names]), self._table([v[n] for n in self._names]),
@@ -934,11 +1085,16 @@ class PredNetTrainer:
             seq = {k: [np.empty(s, np.float32) for s in shp] for k in SEQ_PARTS}
             flat = [seq[k][l] for l in range(len(shp)) for k in SEQ_PARTS]
             _check(self.lib.eigen_trainer_get_state(self._h, None, None, ctypes.c_int32(0), None, None, self._table(flat), ctypes.c_int32(len(flat))))
-        return {"adam_m": m, "adam_v": v, "adam_t": int(t.value), "hyper": {k: float(getattr(self, k)) for k in HYPER}, "seq": seq}
+        out = {"adam_m": m, "adam_v": v, "adam_t": int(t.value), "hyper": {k: float(getattr(self, k)) for k in HYPER}, "seq": seq}
+        optim = check_optim(self.clip_norm, self.weight_decay, self.skip_nonfinite)
+        if not optim_is_neutral(*optim):    # "optim": the controls, present only when one is not neutral; the accumulator is no part of the state
+            out["optim"] = dict(zip(OPTIM, optim))
+        return out
 
     def load_state_dict(self, state):
         """Restore a ``state_dict()`` (after ``set_weights``, which clears all of it).  Shapes and dtypes are checked before
-        anything reaches the device (ValueError); the hyper-parameters, when present, replace this trainer's."""
+        anything reaches the device (ValueError); the hyper-parameters, when present, replace this trainer's, and so do the optimiser
+        controls: a state without "optim" sets them neutral."""
         st = check_state(state, self.channels, self.w, self.h, self.batch)
         tm, tv = (self._table([st[key][n] for n in self._names]) for key in ("adam_m", "adam_v"))
         flat = [] if st["seq"] is None else [st["seq"][k][l] for l in range(len(self.channels)) for k in SEQ_PARTS]
@@ -947,6 +1103,8 @@ class PredNetTrainer:
         for k, v in st["hyper"].items():
             if k in HYPER:
                 setattr(self, k, v)
+        # the optimiser controls: the state's, and neutral where it carries none (a state of a neutral or an earlier trainer)
+        self.clip_norm, self.weight_decay, self.skip_nonfinite = check_optim(**st.get("optim", {}))
 
     def save_checkpoint(self, path):
         """weights(), state_dict() and the hyper-parameters as one npz (``write_checkpoint``)."""
@@ -1200,4 +1358,5 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
 
 
 __all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update", "FlowObjective",
-           "PredictionFlow", "make_flow", "flow_direction", "FlowScore", "BandsScore", "FreeScore", "structure_score", "CornerMembers"]
+           "PredictionFlow", "make_flow", "flow_direction", "FlowScore", "BandsScore", "FreeScore", "structure_score", "CornerMembers", "check_optim",
+           "check_micro_batches"]

@@ -4,6 +4,7 @@ result in the fitness path.
 
     python examples/train_prednet.py -o trained.npz [-i frames_dir] [--size 160x120] [-c 3] [--steps 200] [--seq 10] [--batch 8]
                                      [--loss mse|l0|lall]
+                                     [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K]
                                      [--ext-steps 200 --ext-frames 4 [--requant]] [--checkpoint ckpt.npz [--every 50]] [--resume ckpt.npz]
 
 Input: the PNG files of a folder, in name order, centre-cropped to --size, cut into windows of --seq frames; without -i, seeded
@@ -16,6 +17,10 @@ mse, the squared error of the prediction; l0, the mean of the image layer's erro
 lall, L_0 plus the error units of the upper layers at weight 0.1 (L_all).  Prints the held-out per-step squared errors and the
 mean error units of every layer (tape-free `evaluate`) before and after, writes the weights as a chainer npz (-o), then evaluates one synthetic population's
 fitness with them.
+--clip-norm, --weight-decay and --skip-nonfinite are the trainer's optimiser controls (gradient clipping at a global norm, chainer's weight
+decay, leaving out a step whose gradient is not finite); --micro-batches K keeps --batch as the logical batch of a step and runs it as K
+chunks on a handle of --batch / K, so the tape is K times smaller.  At the steps whose loss is printed the global gradient norm is printed
+too, with the names of the tensors whose gradient is exactly zero.
 """
 import argparse
 import os
@@ -26,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 from evolutionary_illusion_generator_amd import fitness, grids, synth, weights
-from evolutionary_illusion_generator_amd.train import PredNetTrainer
+from evolutionary_illusion_generator_amd.train import PredNetTrainer, check_micro_batches, check_optim
 
 
 def read_windows(folder, c_dim, w, h, seq):
@@ -69,6 +74,10 @@ def main():
     ap.add_argument("--checkpoint", default=None, help="write weights + Adam state + step counter here (one npz)")
     ap.add_argument("--every", type=int, default=50, help="checkpoint period in steps")
     ap.add_argument("--resume", default=None, help="continue the run a --checkpoint file holds")
+    ap.add_argument("--clip-norm", type=float, default=None, help="scale a step's gradient down to this global L2 norm (default: no clipping)")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="chainer's AdamRule weight_decay_rate")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="leave out a step whose gradient norm is not finite")
+    ap.add_argument("--micro-batches", type=int, default=1, help="run a step's --batch sequences as K chunks on a handle of --batch / K")
     args = ap.parse_args()
     w, h = (int(v) for v in args.size.lower().split("x"))
     channels = [int(c) for c in args.channels.split(",")] if args.channels else [args.color_space, 48, 96, 192]
@@ -90,13 +99,20 @@ def main():
     fmt = lambda v: " ".join("%.5f" % x for x in v)
     obj = {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(channels) - 1))}[args.loss]
 
-    with PredNetTrainer(args.model, channels, w, h, args.batch, args.seq, alpha=args.alpha) as tr:
+    try:
+        optim = check_optim(args.clip_norm, args.weight_decay, args.skip_nonfinite)
+        chunk = check_micro_batches(args.batch, args.micro_batches, args.batch)
+    except ValueError as e:
+        ap.error(str(e))
+    obj["micro_batches"] = args.micro_batches
+
+    with PredNetTrainer(args.model, channels, w, h, chunk, args.seq, alpha=args.alpha, clip_norm=optim[0], weight_decay=optim[1], skip_nonfinite=optim[2]) as tr:
         first = 0
         if args.resume:
-            tr.load_checkpoint(args.resume)
+            tr.load_checkpoint(args.resume)    # the checkpoint's optimiser controls replace the command line's, as its hyper-parameters do
             first = tr.state_dict()["adam_t"]
-            print("resumed %s at step %d" % (args.resume, first))
-        before, err_before = tr.evaluate(held, n_fed=n_fed, requant=args.requant, layer_errors=True)
+            print("resumed %s at step %d (clip_norm %s, weight_decay %g, skip_nonfinite %s)" % (args.resume, first, tr.clip_norm, tr.weight_decay, tr.skip_nonfinite))
+        before, err_before = tr.evaluate(held[:chunk], n_fed=n_fed, requant=args.requant, layer_errors=True)
         print("held-out loss per step (%d fed, %d self-fed) before: %s" % (n_fed, args.seq - n_fed, fmt(before)))
         print("held-out error units per layer (mean over the steps; layer 0 is the L_0 error) before: %s" % fmt(err_before.mean(0)))
         for k in range(first, total):
@@ -106,9 +122,14 @@ def main():
                 loss = tr.step(batch_of(k), n_fed=n_fed, requant=args.requant, step_weights=ext_w if any(ext_w) else None, **obj)
             if k % 50 == 0 or k == total - 1 or k == args.steps:
                 print("step %4d  %s train loss (%s) %.6f" % (k, "teacher-forced" if k < args.steps else "self-fed      ", args.loss, loss))
+                # the gradient this step applied (with micro-batches: the accumulated one), before clipping
+                norm, per = tr.grad_norms()
+                dead = [n for n, v in per.items() if v == 0.0]
+                skipped = "  (step left out: the norm is not finite)" if tr.last_update["applied"] == 0 else ""
+                print("           gradient norm %.6e%s; %d of %d tensors exactly zero%s" % (norm, skipped, len(dead), len(per), ": " + " ".join(dead) if dead else ""))
             if args.checkpoint and ((k + 1) % args.every == 0 or k == total - 1):
                 tr.save_checkpoint(args.checkpoint)
-        after, err_after = tr.evaluate(held, n_fed=n_fed, requant=args.requant, layer_errors=True)
+        after, err_after = tr.evaluate(held[:chunk], n_fed=n_fed, requant=args.requant, layer_errors=True)
         trained = tr.weights()
     print("held-out loss per step after:  %s" % fmt(after))
     print("held-out error units per layer after:  %s" % fmt(err_after.mean(0)))

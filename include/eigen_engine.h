@@ -716,6 +716,62 @@ int eigen_trainer_get_grads(eigen_trainer* t, float* const* h_tensors, int32_t n
  * v += (1-beta2)(g^2-v), p -= lr_t m / (sqrt(v) + eps), lr_t = alpha sqrt(1-beta2^t) / (1-beta1^t). */
 int eigen_trainer_adam(eigen_trainer* t, double alpha, double beta1, double beta2, double eps, void* stream);
 
+/* ---- Optimiser controls ("Optimiser controls"): what a training loop puts between the gradient and the
+ * update.  All of it runs on the device, on the handle's float32 tables, with float64 reductions of a fixed partition and a fixed
+ * order (no atomics): norms, clipped steps and accumulated gradients are the same bits from run to run. */
+
+/* The settings of one eigen_trainer_adam_ex step.  alpha, beta1, beta2, eps: as eigen_trainer_adam.
+ *   weight_decay: chainer's AdamRule weight_decay_rate with eta = 1: p -= lr_t m / (sqrt(v) + eps) + weight_decay p, the two terms
+ *     added first and then subtracted.  0: off.
+ *   clip_norm: chainer's GradientClipping: with norm the global L2 norm of the gradient table, the step uses g' = rate g,
+ *     rate = (float)(clip_norm / norm) (divided in double) where norm > clip_norm, else 1.  0: off.  The gradient table itself is
+ *     not modified: eigen_trainer_get_grads still returns g.  A norm of exactly 0 gives rate 1; nothing divides by it.
+ *   skip_nonfinite: 1: a step whose norm is not finite is not taken (see the entry).  reserved: 0. */
+typedef struct {
+    double alpha, beta1, beta2, eps, weight_decay, clip_norm;
+    int32_t skip_nonfinite, reserved;
+} eigen_adam_settings;
+
+/* What a step did: the global norm it saw, the rate it applied (in double: clip_norm / norm, or 1) and whether it was applied. */
+typedef struct {
+    double norm, rate;
+    int32_t applied, reserved;
+} eigen_adam_report;
+
+/* The L2 norms of the current gradient table: *h_global that of all tensors together, h_per_tensor[k] that of tensor k in
+ * eigen_set_prednet_weights order (n_tensors of them).  Either output may be NULL.  Per tensor the squares are summed in double
+ * (a float's square is exact there): NORM_SLICES fixed strided slices, a fixed tree within each, the slices added in order; the
+ * global norm is the square root of the tensors' sums added in tensor order.  A norm that is not finite is a value to return,
+ * not an error.  The call synchronises the stream when it has an output to write.
+ * Errors: EIGEN_ERR_INVALID a NULL handle, n_tensors not the handle's count; EIGEN_ERR_STATE no weights. */
+int eigen_trainer_grad_norms(eigen_trainer* t, double* h_global, double* h_per_tensor, int32_t n_tensors, void* stream);
+
+/* One Adam step under `settings`.  With weight_decay = 0, clip_norm = 0, skip_nonfinite = 0 and h_report = NULL it launches exactly
+ * what eigen_trainer_adam launches, hence the same bits.  Otherwise it computes the norms on the device (as
+ * eigen_trainer_grad_norms) and runs the clipped, decayed update, which reads the norm from device memory: a clipped step needs no
+ * host round trip.  With skip_nonfinite the call reads the norm back first, which synchronises the stream; if it is not finite
+ * nothing is changed (weights, moments and the step count stay as they are) and the report says applied = 0.  With a report and
+ * without skip_nonfinite the norm is read back after the launch.  WITHOUT skip_nonfinite A GRADIENT THAT IS NOT FINITE IS APPLIED, as
+ * eigen_trainer_adam applies it: the weights it reaches are lost.
+ * Errors, before any launch: EIGEN_ERR_INVALID a NULL handle or settings, weight_decay or clip_norm negative or not finite,
+ * skip_nonfinite not 0 or 1, reserved not 0, and what eigen_trainer_adam refuses for alpha, beta1, beta2, eps; EIGEN_ERR_STATE no
+ * weights. */
+int eigen_trainer_adam_ex(eigen_trainer* t, const eigen_adam_settings* settings, eigen_adam_report* h_report, void* stream);
+
+/* The gradient accumulator: a second table of the gradient's size, on the device, which sums the gradients of several
+ * eigen_trainer_loss_grad* calls (each of which overwrites the gradient table) into one step: micro-batches of a logical batch the
+ * tape cannot hold, or terms under different objectives.
+ *   EIGEN_ACC_ADD: acc[i] = acc[i] + s g[i] with s = (float)scale, one rounded product and one rounded sum; on an empty
+ *     accumulator the sum starts from zero.
+ *   EIGEN_ACC_LOAD: the gradient table becomes a copy of the accumulator, which keeps its contents.
+ *   EIGEN_ACC_CLEAR: the accumulator is zeroed and empty again.  `scale` is read by ADD alone.
+ * The table is made by the first ADD; eigen_trainer_tape_bytes does not count it.  eigen_trainer_set_weights discards what was
+ * accumulated, and the accumulator is no part of eigen_trainer_get_state / _set_state: a checkpoint is taken between steps.
+ * Errors, before any launch: EIGEN_ERR_INVALID a NULL handle, an unknown op, a scale that is not finite; EIGEN_ERR_STATE no weights,
+ * EIGEN_ACC_LOAD with nothing accumulated. */
+enum { EIGEN_ACC_CLEAR = 0, EIGEN_ACC_ADD = 1, EIGEN_ACC_LOAD = 2 };
+int eigen_trainer_accumulate(eigen_trainer* t, int32_t op, double scale, void* stream);
+
 /* Device bytes of the handle's tape (activations kept for the backward pass) at max_batch x max_steps. */
 int64_t eigen_trainer_tape_bytes(const eigen_trainer* t);
 

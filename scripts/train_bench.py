@@ -7,6 +7,8 @@ the tape-free evaluate of that call.  Prints one JSON line per side and writes p
     python scripts/train_bench.py --frame-grads [--steps 5] [--warmup 2]
     python scripts/train_bench.py --flow-cost [--steps 5] [--warmup 2] [--flow-reference constant|moving] [--flow-pairing frame|prediction]
         [--flow-score [--flow-score-structure circles|bands|free] [--flow-max-norm M]]
+    python scripts/train_bench.py [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K] [--side trainer]
+    python scripts/train_bench.py --optim-cost [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
 side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
@@ -19,6 +21,10 @@ gradients (left on the device) under the constant and under the moving reference
 one leg, "flow_prediction", beside "mse" and the frame-pairing "flow": their difference over the two computed terms is what the pairing costs.
 --flow-score gives the flow objective a train.FlowScore (the Circles score of the dense field); --flow-cost then adds one leg, "flow_score",
 under the pairing and reference asked for, beside the energy-mode legs: their difference over the two computed terms is what the mode costs.
+--clip-norm, --weight-decay, --skip-nonfinite give the timed trainer those optimiser controls (DESIGN.md section 13, "Optimiser controls");
+--micro-batches K times step(micro_batches=K) of the same 16 sequences on a handle of batch 16 / K.  --optim-cost times three trainers,
+alternated round by round in one process: neutral controls, the controls given (none given: clip_norm at half the first gradient's norm
+and weight_decay 0.01) and micro-batches (K, at least 2); one JSON line each with the spread over the rounds.
 """
 import argparse
 import json
@@ -115,13 +121,52 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"
     return [dict(side="loss_grad_" + k, call_ms=float(np.median(v)), call_ms_min=min(v), call_ms_max=max(v), rounds=rounds, loss=loss[k]) for k, v in ms.items()]
 
 
-def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None, members=None):
+def run_optim_cost(steps, warmup, rounds=6, clip_norm=None, weight_decay=0.0, skip_nonfinite=False, micro_batches=2):
+    """ms per step() of three trainers on the same weights and frames, alternated round by round in one process: "plain" (neutral
+    controls: the plain Adam entry), "controls" (the controls given; none given: clip_norm = half the first gradient's norm and
+    weight_decay 0.01) and "micro" (a handle of batch B / micro_batches, step(micro_batches=...): the same logical batch)"""
+    import torch
+    from evolutionary_illusion_generator_amd import weights
+    from evolutionary_illusion_generator_amd.train import PredNetTrainer, check_optim, optim_is_neutral
+    d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
+    wts = weights.synthetic_prednet_weights(CH, W, H, seed=0)
+    optim = check_optim(clip_norm, weight_decay, skip_nonfinite)
+    legs = {"plain": (PredNetTrainer(wts, CH, W, H, B, T), {}), "controls": (PredNetTrainer(wts, CH, W, H, B, T), {}),
+            "micro": (PredNetTrainer(wts, CH, W, H, B // micro_batches, T), dict(micro_batches=micro_batches))}
+    tr = legs["controls"][0]
+    if optim_is_neutral(*optim):
+        tr.forward_backward(d)
+        optim = (0.5 * tr.grad_norms()[0], 0.01, False)
+    tr.clip_norm, tr.weight_decay, tr.skip_nonfinite = optim
+    ms, loss = {k: [] for k in legs}, {}
+    for k, (t, kw) in legs.items():
+        for _ in range(warmup):
+            t.step(d, **kw)
+    for _ in range(rounds):
+        for k, (t, kw) in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                loss[k] = t.step(d, **kw)
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3 / steps)
+    out = [dict(side="step_" + k, step_ms=float(np.median(v)), step_ms_min=min(v), step_ms_max=max(v), rounds=rounds, loss=loss[k], batch=legs[k][0].batch,
+                last_update=legs[k][0].last_update, **(dict(zip(("clip_norm", "weight_decay", "skip_nonfinite"), optim)) if k == "controls" else {})) for k, v in ms.items()]
+    for t, _ in legs.values():
+        t.close()
+    return out
+
+
+def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None, members=None, optim=(None, 0.0, False), micro_batches=1):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
     d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
-    tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T)
     kw = objective_args(objective, reference, pairing, score, members) if objective == "flow" else objective_args(objective)
+    # the logical batch stays B: with micro-batches the handle, and so the tape, is B / micro_batches
+    tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B // micro_batches, T, clip_norm=optim[0], weight_decay=optim[1],
+                        skip_nonfinite=optim[2])
+    kw = dict(kw, micro_batches=micro_batches)
     for _ in range(warmup):
         tr.step(d, **kw)
     torch.cuda.synchronize()
@@ -131,7 +176,9 @@ def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="f
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / steps
     res = dict(side="trainer", objective=objective, step_ms=ms, sample_steps_per_s=B * T / ms * 1e3, loss=loss, tape_bytes=tr.tape_bytes,
-               tape_bytes_per_sample_step=tr.tape_bytes / (B * T), conv_flops_per_step=3 * conv_flops_per_sample_step(CH, W, H) * B * T)
+               tape_bytes_per_sample_step=tr.tape_bytes / (tr.batch * T), conv_flops_per_step=3 * conv_flops_per_sample_step(CH, W, H) * B * T)
+    if optim != (None, 0.0, False) or micro_batches != 1:
+        res.update(clip_norm=optim[0], weight_decay=optim[1], skip_nonfinite=optim[2], micro_batches=micro_batches, last_update=tr.last_update)
     tr.close()
     return res
 
@@ -256,6 +303,11 @@ def main():
     add_flow_arguments(ap, ("reference", "pairing", "score", "score-structure", "max-norm", "members", "corner-quality", "corner-distance"), **{"score-structure": dict(choices=["circles", "bands", "free"])}, reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
                        pairing=dict(help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)"))
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
+    ap.add_argument("--clip-norm", type=float, default=None, help="the trainer's clip_norm (default: no clipping)")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="the trainer's weight_decay")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="the trainer's skip_nonfinite")
+    ap.add_argument("--micro-batches", type=int, default=1, help="step(micro_batches=K) on a handle of batch 16 / K")
+    ap.add_argument("--optim-cost", action="store_true", help="time step() plain, under the controls and in micro-batches, alternated, and exit")
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
     a = ap.parse_args()
@@ -277,7 +329,17 @@ def main():
         for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score, members=members):
             print(json.dumps(r), flush=True)
         return
-    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members)]
+    from evolutionary_illusion_generator_amd.train import check_micro_batches, check_optim
+    try:
+        optim = check_optim(a.clip_norm, a.weight_decay, a.skip_nonfinite)
+        check_micro_batches(B, a.micro_batches, B)
+    except ValueError as e:
+        ap.error(str(e))
+    if a.optim_cost:
+        for r in run_optim_cost(a.steps, a.warmup, clip_norm=optim[0], weight_decay=optim[1], skip_nonfinite=optim[2], micro_batches=max(a.micro_batches, 2)):
+            print(json.dumps(r), flush=True)
+        return
+    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members, optim, a.micro_batches)]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
