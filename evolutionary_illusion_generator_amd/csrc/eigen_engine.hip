@@ -24,6 +24,7 @@
 #include "farneback_kernels.h"
 #include "flow_kernels.h"
 #include "score_kernels.h"
+#include "dense_stage.h"   // the dense fitness's stage lives with the flow objective's kernels, in prednet_train.hip
 
 using namespace eig;
 
@@ -126,6 +127,8 @@ struct eigen_engine {
     int *d_ncorners = nullptr, *d_counts = nullptr;
     double* d_fitness = nullptr;
     float* d_zeros = nullptr;  // DMA source for zero fill (conv_mfma.h)
+    eigd::DenseWork dense;     // the dense fitness's workspace (eigen_dense_score): allocated by the first dense call, all of it or none
+    bool have_dense = false;
     // Farneback dense flow (cfg.flow_method == EIGEN_FLOW_FARNEBACK): allocated on first use
     float *fb_I = nullptr, *fb_R0 = nullptr, *fb_R1 = nullptr, *fb_M = nullptr, *fb_V = nullptr, *fb_flow[2] = {nullptr, nullptr};
     DevBuf<float> raw4;   // partial chains of the unpooled source, [B][4 classes][n_nblk*NB][H/2][W/2], reused by all layers
@@ -441,6 +444,8 @@ int eigen_destroy(eigen_engine* e)
                     e->d_ncorners, e->d_counts, e->d_fitness, e->d_zeros,
                     e->fb_I, e->fb_R0, e->fb_R1, e->fb_M, e->fb_V, e->fb_flow[0], e->fb_flow[1]};
     for (void* p : misc) if (p) (void)hipFree(p);
+    void* dense[] = {e->dense.planes, e->dense.u, e->dense.theta, e->dense.L, e->dense.rec, e->dense.part, e->dense.flag};
+    for (void* p : dense) if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
         for (int l = 0; l < FLOW_MAX_LEVELS; ++l) if (e->d_gray[i][l]) (void)hipFree(e->d_gray[i][l]);
     for (int l = 0; l < FLOW_MAX_LEVELS; ++l) if (e->d_deriv[l]) (void)hipFree(e->d_deriv[l]);
@@ -1034,8 +1039,74 @@ int eigen_score(eigen_engine* e, int32_t structure, int32_t width, int32_t heigh
     return EIGEN_OK;
 }
 
+// The dense fitness's workspace (dense_stage.h), made by the first call that needs it: the handle takes the buffers once every one of
+// them exists, a failure frees what it made.
+static int dense_workspace(eigen_engine* e)
+{
+    if (e->have_dense) return EIGEN_OK;
+    const size_t n = (size_t)e->B * e->H * e->W;
+    eigd::DenseWork& w = e->dense;
+    const std::pair<void**, size_t> want[] = {{(void**)&w.planes, 3 * n * 8}, {(void**)&w.u, 2 * n * 8}, {(void**)&w.theta, n * 8}, {(void**)&w.L, n * 8},
+                                              {(void**)&w.rec, (size_t)e->B * eigd::DENSE_REC * 8}, {(void**)&w.part, (size_t)e->B * eigd::DENSE_PART * 8},
+                                              {(void**)&w.flag, n}};
+    std::vector<void*> made;
+    for (const auto& x : want) {
+        void* p = nullptr;
+        const hipError_t err = hipMalloc(&p, x.second);
+        if (err != hipSuccess) {
+            for (void* q : made) (void)hipFree(q);
+            return fail(EIGEN_ERR_HIP, "hipMalloc(%zu) for the dense fitness: %s", x.second, hipGetErrorString(err));
+        }
+        made.push_back(p);
+    }
+    for (size_t i = 0; i < made.size(); ++i) *want[i].first = made[i];
+    e->have_dense = true;
+    return EIGEN_OK;
+}
+
+// What every dense entry refuses before anything is launched (the roll-out included), then the workspace
+static int dense_prepare(eigen_engine* e, const eigen_dense_settings* settings, const uint8_t* d_mask, int batch)
+{
+    if (!settings) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (batch < 1 || batch > e->B) return fail(EIGEN_ERR_INVALID, "batch %d outside 1 .. max_batch %d", batch, e->B);
+    HIPCHK(hipSetDevice(e->cfg.device));
+    const int rc = eigd::dense_check(settings, e->cfg.device, e->H, e->W, d_mask);
+    if (rc) return rc;
+    return dense_workspace(e);
+}
+
+// The stage on prepared settings, and its host outputs: S_b alone comes back where the records are not asked for
+static int dense_run(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int batch,
+                     const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, hipStream_t st, bool sync)
+{
+    eigd::dense_launch(settings, e->C0, e->H, e->W, d_img0, (long long)stride0, d_img1, (long long)stride1, batch, d_mask, e->dense, d_flow, st);
+    HIPCHK(hipGetLastError());
+    const size_t rec = eigd::DENSE_REC * sizeof(double);
+    if (h_stats) HIPCHK(hipMemcpyAsync(h_stats, e->dense.rec, rec * batch, hipMemcpyDeviceToHost, st));
+    if (h_fitness && !h_stats) HIPCHK(hipMemcpy2DAsync(h_fitness, sizeof(double), e->dense.rec + 8, rec, sizeof(double), batch, hipMemcpyDeviceToHost, st));
+    if ((h_stats || h_fitness) && sync) {
+        HIPCHK(hipStreamSynchronize(st));
+        if (h_fitness && h_stats)
+            for (int b = 0; b < batch; ++b) h_fitness[b] = h_stats[(size_t)b * eigd::DENSE_REC + 8];
+    }
+    return EIGEN_OK;
+}
+
+int eigen_dense_score(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
+                      const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, void* stream)
+{
+    if (!e || !d_img0 || !d_img1 || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
+    const int64_t per = (int64_t)e->C0 * e->H * e->W;
+    if (stride0 < per || stride1 < per) return fail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", (long long)per);
+    const int rc = dense_prepare(e, settings, d_mask, batch);
+    if (rc) return rc;
+    return dense_run(e, d_img0, stride0, d_img1, stride1, batch, settings, d_mask, h_fitness, h_stats, d_flow, (hipStream_t)stream, true);
+}
+
+// dense != nullptr: the dense stage (already prepared) in place of flow and score; h_stats is its records
 static int eval_images_impl(eigen_engine* e, const uint8_t* d_images, int batch, int structure, int pairing, double* h_fitness,
-                            float* h_vectors, int32_t* h_counts, hipStream_t st, bool rendered)
+                            float* h_vectors, int32_t* h_counts, hipStream_t st, bool rendered, const eigen_dense_settings* dense = nullptr,
+                            const uint8_t* d_mask = nullptr, double* h_stats = nullptr)
 {
     const size_t HW = (size_t)e->H * e->W, img_bytes = (size_t)e->C0 * HW;
     const int nr = e->cfg.n_repeat;
@@ -1049,6 +1120,23 @@ static int eval_images_impl(eigen_engine* e, const uint8_t* d_images, int batch,
     if (rc) return rc;
     HIPCHK(hipEventRecord(e->ev[2], st));
     const int n_out = n_steps - first;
+    if (dense) {
+        const int64_t fs = (int64_t)(n_out * img_bytes);
+        if (pairing == EIGEN_PAIR_POPULATION) rc = dense_run(e, e->d_frames, fs, e->d_frames + img_bytes, fs, batch, dense, d_mask, h_fitness, h_stats, nullptr, st, false);
+        else rc = dense_run(e, d_images, (int64_t)img_bytes, e->d_frames, fs, batch, dense, d_mask, h_fitness, h_stats, nullptr, st, false);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(e->ev[3], st));
+        HIPCHK(hipEventRecord(e->ev[4], st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h_stats)
+            for (int b = 0; b < batch; ++b) h_fitness[b] = h_stats[(size_t)b * eigd::DENSE_REC + 8];
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1])); e->ms[0] = ms;
+        HIPCHK(hipEventElapsedTime(&ms, e->ev[1], e->ev[2])); e->ms[1] = ms;
+        HIPCHK(hipEventElapsedTime(&ms, e->ev[2], e->ev[3])); e->ms[2] = ms;
+        e->ms[3] = 0;
+        return EIGEN_OK;
+    }
     if (pairing == EIGEN_PAIR_POPULATION)
         rc = eigen_flow(e, e->d_frames, (int64_t)(n_out * img_bytes), e->d_frames + img_bytes, (int64_t)(n_out * img_bytes), batch, e->d_vectors, e->d_counts, st);
     else
@@ -1092,6 +1180,46 @@ int eigen_eval_images(eigen_engine* e, const uint8_t* d_images, int32_t batch, i
     if (structure < 0 || structure > 3) return fail(EIGEN_ERR_INVALID, "unknown structure %d", structure);
     HIPCHK(hipSetDevice(e->cfg.device));
     return eval_images_impl(e, d_images, batch, structure, pairing, h_fitness, h_vectors, h_counts, (hipStream_t)stream, false);
+}
+
+// What the two population entries refuse ahead of the settings' own checks, the workspace and the render: a structure the settings'
+// score does not belong to (settings with both scores or neither pass here and are refused by dense_prepare) and a pairing the
+// handle's n_ext cannot serve (eval_images_impl's own rule and words)
+static int dense_call_check(const eigen_engine* e, int structure, int pairing, const eigen_dense_settings* s)
+{
+    if (structure < 0 || structure > 3) return fail(EIGEN_ERR_INVALID, "unknown structure %d", structure);
+    const bool circles = structure == EIGEN_CIRCLES || structure == EIGEN_CIRCLES_FREE;
+    if ((s->score != nullptr) != (s->sscore != nullptr) && (circles ? s->score == nullptr : (s->sscore == nullptr || s->sscore->structure != structure)))
+        return fail(EIGEN_ERR_INVALID, "structure %d: the dense settings carry the score of another structure", structure);
+    const int need = pairing == EIGEN_PAIR_POPULATION ? 1 : 2;
+    if (need > e->cfg.n_ext) return fail(EIGEN_ERR_INVALID, "pairing needs %d extension steps, engine has n_ext=%d", need, e->cfg.n_ext);
+    return EIGEN_OK;
+}
+
+int eigen_eval_population_dense(eigen_engine* e, const eigen_genome_batch* g, int32_t structure, int32_t bg, int32_t gradient, int32_t pairing,
+                                const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream)
+{
+    if (!e || !g || !h_fitness || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
+    int rc = dense_call_check(e, structure, pairing, settings);
+    if (rc) return rc;
+    rc = dense_prepare(e, settings, d_mask, g->n_genomes);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipEventRecord(e->ev[0], st));
+    rc = eigen_render_cppn(e, g, bg, gradient, e->d_images, st);
+    if (rc) return rc;
+    return eval_images_impl(e, e->d_images, g->n_genomes, structure, pairing, h_fitness, nullptr, nullptr, st, true, settings, d_mask, h_stats);
+}
+
+int eigen_eval_images_dense(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
+                            const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream)
+{
+    if (!e || !d_images || !h_fitness || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
+    int rc = dense_call_check(e, structure, pairing, settings);
+    if (rc) return rc;
+    rc = dense_prepare(e, settings, d_mask, batch);
+    if (rc) return rc;
+    return eval_images_impl(e, d_images, batch, structure, pairing, h_fitness, nullptr, nullptr, (hipStream_t)stream, false, settings, d_mask, h_stats);
 }
 
 int eigen_get_timings(eigen_engine* e, double* h_ms6)

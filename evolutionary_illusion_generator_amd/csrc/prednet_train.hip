@@ -22,6 +22,8 @@
 #include "flow_struct_kernels.h"
 #include "flow_corner_kernels.h"
 #include "optim_kernels.h"
+#include "dense_fitness_kernels.h"
+#include "dense_stage.h"
 
 using namespace eigt;
 
@@ -507,16 +509,16 @@ int check_flow_score(const eigen_flow_score* sc, const float* d_dir, FlowSpec& f
 
 // The settings of a flow call against the handle's image, before anything is launched.  The direction field and the mask are read back
 // to the host: every d must be finite, and kappa needs the mask's count.
-int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, int32_t allowed_flags, FlowSpec& f)
+// check_flow_on: against an image of HW pixels on `device`, which is all the rules need of a handle (eigen_dense_score has no trainer).
+int check_flow_on(int device, long long HW, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, int32_t allowed_flags, FlowSpec& f)
 {
     if (!flow) return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs its settings");
     if (flow->radius < 1 || flow->radius > FLOW_MAX_R) return tfail(EIGEN_ERR_INVALID, "flow radius %d outside 1 .. %d", flow->radius, FLOW_MAX_R);
     if (!std::isfinite(flow->eps) || !(flow->eps > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow eps %g: must be finite and > 0", flow->eps);
     if (flow->flags & ~allowed_flags) return tfail(EIGEN_ERR_INVALID, "flow flags 0x%x: this entry takes 0x%x at most", (unsigned)flow->flags, (unsigned)allowed_flags);
     f.moving = (flow->flags & EIGEN_FLOW_MOVING_REFERENCE) != 0;
-    const long long HW = t->ly[0].HW;
     f.r = flow->radius; f.eps = flow->eps; f.dir = d_dir; f.mask = d_mask; f.n_mask = HW;
-    TCHK(hipSetDevice(t->cfg.device));
+    TCHK(hipSetDevice(device));
     if (d_dir) {
         std::vector<float> d(2 * HW);
         TCHK(hipMemcpy(d.data(), d_dir, 2 * HW * 4, hipMemcpyDeviceToHost));
@@ -530,6 +532,11 @@ int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const fl
         if (f.n_mask == 0) return tfail(EIGEN_ERR_INVALID, "the flow mask counts no pixel");
     }
     return EIGEN_OK;
+}
+
+int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, int32_t allowed_flags, FlowSpec& f)
+{
+    return check_flow_on(t->cfg.device, t->ly[0].HW, flow, d_dir, d_mask, allowed_flags, f);
 }
 
 // The corner members' workspace, made by the first call that needs it and freed with the handle; the tape and every other use of the
@@ -1650,3 +1657,72 @@ int eigen_trainer_accumulate(eigen_trainer* t, int32_t op, double scale, void* s
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------- the dense fitness's stage
+// (dense_stage.h; eigen_engine.hip holds the entries and the workspace).  The score's rules are check_flow_score's and
+// check_flow_struct's, the launches are flow_stage's and struct_stage_of's with the score-only kernels of dense_fitness_kernels.h in
+// place of the prepare, solve and pair kernels.
+namespace eigd {
+
+static_assert(DENSE_REC == SCORE_REC && DENSE_REC == STRUCT_REC, "one record size for every score");
+static_assert(DENSE_PART >= SCORE_SLICES * SCORE_K && DENSE_PART >= STRUCT_SLICES * STRUCT_K, "the partials of every score fit");
+
+static int dense_spec(const eigen_dense_settings* s, int device, int H, int W, const uint8_t* d_mask, FlowSpec& f)
+{
+    if (!s) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if ((s->score != nullptr) == (s->sscore != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the flow score and the flow structure score must be given");
+    int rc = check_flow_on(device, (long long)H * W, &s->flow, nullptr, d_mask, 0, f);
+    if (rc) return rc;
+    rc = check_flow_score(s->score, nullptr, f);
+    if (rc) return rc;
+    return check_flow_struct(s->sscore, nullptr, f);
+}
+
+int dense_check(const eigen_dense_settings* s, int device, int H, int W, const uint8_t* d_mask)
+{
+    FlowSpec f;
+    return dense_spec(s, device, H, W, d_mask, f);
+}
+
+template <int STRUCT>
+static void dense_struct_passes(const TFlowStruct& s, int H, int W, int B, const uint8_t* mask, const DenseWork& w, const double* u, hipStream_t st)
+{
+    const long long HW = (long long)H * W, n = B * HW;
+    const dim3 sgrid(STRUCT_SLICES, (unsigned)B);
+    if (STRUCT == STRUCT_FREE) ew(st, tflow_free_prepare_kernel, n, u, n, H, W, mask, 0ll, s, w.theta, w.flag);
+    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 1>), sgrid, dim3(EW_T), 0, st, u, H, W, mask, 0ll, s, (const double*)w.rec, (const double*)w.L, w.part);
+    hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 1>), dim3(B), dim3(64), 0, st, (const double*)w.part, B, s, w.rec, (double*)nullptr);
+    if (STRUCT == STRUCT_FREE)
+        hipLaunchKernelGGL(tdense_free_pair_kernel, dim3((unsigned)((HW + PAIR_T - 1) / PAIR_T), (unsigned)B), dim3(PAIR_T), 0, st, (const double*)w.theta,
+                           (const uint8_t*)w.flag, H, W, s.DD, w.L);
+    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 2>), sgrid, dim3(EW_T), 0, st, u, H, W, mask, 0ll, s, (const double*)w.rec, (const double*)w.L, w.part);
+    hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 2>), dim3(B), dim3(64), 0, st, (const double*)w.part, B, s, w.rec, (double*)nullptr);
+}
+
+void dense_launch(const eigen_dense_settings* s, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1, long long stride1, int B,
+                  const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st)
+{
+    // the settings were checked by dense_check: the same fields give the same spec, without the mask's read-back
+    FlowSpec f;
+    f.r = s->flow.radius; f.eps = s->flow.eps;
+    (void)check_flow_score(s->score, nullptr, f);
+    (void)check_flow_struct(s->sscore, nullptr, f);
+    const long long n = (long long)B * H * W;
+    double* u = d_flow ? d_flow : w.u;
+    ew(st, tdense_prep_kernel, n, img0, stride0, img1, stride1, C, H, W, n, w.planes);
+    const dim3 grid((unsigned)((W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
+    hipLaunchKernelGGL(tdense_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)w.planes, n, H, W, f.r, f.eps, u);
+    if (f.by_score) {
+        const dim3 sgrid(SCORE_SLICES, (unsigned)B);
+        hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, (const double*)u, H, W, d_mask, 0ll, f.score, (const double*)w.rec, w.part);
+        hipLaunchKernelGGL(tflow_score_final_kernel<1>, dim3(B), dim3(64), 0, st, (const double*)w.part, B, f.score, w.rec, (double*)nullptr);
+        hipLaunchKernelGGL(tflow_score_moment_kernel<2>, sgrid, dim3(EW_T), 0, st, (const double*)u, H, W, d_mask, 0ll, f.score, (const double*)w.rec, w.part);
+        hipLaunchKernelGGL(tflow_score_final_kernel<2>, dim3(B), dim3(64), 0, st, (const double*)w.part, B, f.score, w.rec, (double*)nullptr);
+    } else if (f.sscore.structure == STRUCT_BANDS) {
+        dense_struct_passes<STRUCT_BANDS>(f.sscore, H, W, B, d_mask, w, u, st);
+    } else {
+        dense_struct_passes<STRUCT_FREE>(f.sscore, H, W, B, d_mask, w, u, st);
+    }
+}
+
+}  // namespace eigd

@@ -28,7 +28,7 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_trainer_flow_term_score", "eigen_trainer_loss_grad_flow_score", "eigen_trainer_flow_term_structure",
            "eigen_trainer_loss_grad_flow_structure", "eigen_trainer_debug_free_planes", "eigen_trainer_flow_members",
            "eigen_trainer_flow_term_members", "eigen_trainer_loss_grad_flow_members", "eigen_trainer_grad_norms", "eigen_trainer_adam_ex",
-           "eigen_trainer_accumulate"]
+           "eigen_trainer_accumulate", "eigen_dense_score", "eigen_eval_population_dense", "eigen_eval_images_dense"]
 
 
 class EigenConfig(ctypes.Structure):
@@ -51,7 +51,18 @@ class GenomeBatchC(ctypes.Structure):
                 ("edge_w", ctypes.c_void_p), ("out_node", ctypes.c_void_p)]
 
 
+class FlowSettingsC(ctypes.Structure):
+    """eigen_flow_settings (train.FlowSettings is the same layout)"""
+    _fields_ = [("radius", ctypes.c_int32), ("flags", ctypes.c_int32), ("eps", ctypes.c_double)]
+
+
+class DenseSettingsC(ctypes.Structure):
+    """eigen_dense_settings: the window and exactly one of the two scores"""
+    _fields_ = [("flow", FlowSettingsC), ("score", ctypes.c_void_p), ("sscore", ctypes.c_void_p)]
+
+
 FLOW_METHODS = {"lk": 0, "farneback": 1}  # eigen_flow_method
+DENSE_REC = 10  # doubles of one sample's record (train.SCORE_STATS / BANDS_STATS / FREE_STATS)
 
 
 class EngineError(RuntimeError):
@@ -165,6 +176,7 @@ class Engine:
         self.cfg = cfg
         self.width, self.height, self.channels, self.max_batch = width, height, list(channels), max_batch
         self.c_dim, self.K = channels[0], cfg.lk_max_corners
+        self.last_dense_stats = None  # float64 [n, 10]: the records of the last dense call (dense_score, eval_*(dense=...))
         self._h = ctypes.c_void_p()
         _check(self.lib.eigen_create(ctypes.byref(cfg), ctypes.byref(self._h)))
 
@@ -290,15 +302,68 @@ class Engine:
         _check(self.lib.eigen_score(self._h, ctypes.c_int32(int(structure)), ctypes.c_int32(width), ctypes.c_int32(height), _ptr(d_vectors),
                                     _ptr(d_counts), ctypes.c_int32(batch), _ptr(d_fitness), _stream_arg(stream)))
 
-    def eval_population(self, gb, structure, bg=1, gradient=1, pairing=PAIR_POPULATION, stream=None):
+    # -- the dense fitness (include/eigen_engine.h "dense fitness") --------------
+    def _dense_args(self, dense):
+        """`dense`: anything with ``dense_settings(h)`` -> (radius, eps, the ctypes settings of its score, True for a Circles score)
+        and ``mask_on(torch, device, h, w)`` -> the shared mask on the device or None (``fitness.DenseFitness``).
+        -> (DenseSettingsC, what must stay alive during the call, the mask's pointer)"""
+        radius, eps, sc, by_circles = dense.dense_settings(self.height)
+        addr = ctypes.addressof(sc)
+        cfg = DenseSettingsC(FlowSettingsC(int(radius), 0, float(eps)), addr if by_circles else None, None if by_circles else addr)
+        import torch
+        mask = dense.mask_on(torch, self.cfg.device, self.height, self.width)
+        return cfg, (sc, mask), _ptr(mask)
+
+    def dense_score(self, d_img0, stride0, d_img1, stride1, batch, dense, stats=False, flow=False, stream=None):
+        """The dense stage alone on two batches of uint8 device images (eigen_dense_score): image b of either at its pointer + b * its
+        stride (bytes).  -> the float64 [batch] fitness, S_b of every sample; stats=True appends the float64 [batch, 10] records,
+        flow=True the field u, float64 [batch, 2, H, W] (numpy).  The records are also left in ``last_dense_stats``."""
+        cfg, keep, d_mask = self._dense_args(dense)
+        batch = int(batch)
+        fit, rec = np.zeros(max(batch, 0), np.float64), np.zeros((max(batch, 0), DENSE_REC), np.float64)
+        u = None
+        if flow:
+            import torch
+            u = torch.empty((max(batch, 1), 2, self.height, self.width), dtype=torch.float64, device="cuda:%d" % self.cfg.device)
+        if 1 <= batch <= self.max_batch:   # the C side reads through raw pointers: refuse buffers smaller than what it touches
+            per = self.c_dim * self.height * self.width
+            for buf, stride, what in ((d_img0, stride0, "img0"), (d_img1, stride1, "img1")):
+                have = self._buffer_bytes(buf)
+                if have is not None and int(stride) >= per and have < (batch - 1) * int(stride) + per:
+                    raise ValueError("%s buffer holds %d bytes, %d are needed" % (what, have, (batch - 1) * int(stride) + per))
+        _check(self.lib.eigen_dense_score(self._h, _ptr(d_img0), ctypes.c_int64(int(stride0)), _ptr(d_img1), ctypes.c_int64(int(stride1)), ctypes.c_int32(batch),
+                                          ctypes.byref(cfg), d_mask, _ptr(fit), _ptr(rec), _ptr(u), _stream_arg(stream)))
+        self.last_dense_stats = rec
+        out = (fit,) + ((rec,) if stats else ()) + ((u[:batch].cpu().numpy(),) if flow else ())
+        return out[0] if len(out) == 1 else out
+
+    def eval_population(self, gb, structure, bg=1, gradient=1, pairing=PAIR_POPULATION, stream=None, dense=None):
+        """dense None: the corner fitness (eigen_eval_population).  dense: a ``fitness.DenseFitness`` resolved for `structure`: the dense
+        motion score (eigen_eval_population_dense); the records of the call are then left in ``last_dense_stats``."""
         fit = np.zeros(gb.n_genomes, dtype=np.float64)
         s = self._genome_struct(gb)
+        if dense is not None:
+            cfg, keep, d_mask = self._dense_args(dense)
+            rec = np.zeros((gb.n_genomes, DENSE_REC), np.float64)
+            _check(self.lib.eigen_eval_population_dense(self._h, ctypes.byref(s), ctypes.c_int32(int(structure)), ctypes.c_int32(bg), ctypes.c_int32(gradient),
+                                                        ctypes.c_int32(pairing), ctypes.byref(cfg), d_mask, _ptr(fit), _ptr(rec), _stream_arg(stream)))
+            self.last_dense_stats = rec
+            return fit
         _check(self.lib.eigen_eval_population(self._h, ctypes.byref(s), ctypes.c_int32(int(structure)), ctypes.c_int32(bg),
                                               ctypes.c_int32(gradient), ctypes.c_int32(pairing), _ptr(fit), _stream_arg(stream)))
         return fit
 
-    def eval_images(self, d_images, batch, structure, pairing=PAIR_SINGLE, stream=None):
+    def eval_images(self, d_images, batch, structure, pairing=PAIR_SINGLE, stream=None, dense=None):
+        """dense None: the corner fitness and its vectors (eigen_eval_images).  dense: as ``eval_population``; there are no vectors, the
+        second result is an empty list per image."""
         self._check_images(d_images, batch)
+        if dense is not None:
+            cfg, keep, d_mask = self._dense_args(dense)
+            fit, rec = np.zeros(max(int(batch), 0), np.float64), np.zeros((max(int(batch), 0), DENSE_REC), np.float64)
+            _check(self.lib.eigen_eval_images_dense(self._h, _ptr(d_images), ctypes.c_int32(batch), ctypes.c_int32(int(structure)), ctypes.c_int32(pairing),
+                                                    ctypes.byref(cfg), d_mask, _ptr(fit), _ptr(rec), _stream_arg(stream)))
+            self.last_dense_stats = rec
+            return fit, [np.zeros((0, 4), np.float32) for _ in range(int(batch))]
         fit = np.zeros(batch, dtype=np.float64)
         vec = np.zeros((batch, self.K, 4), dtype=np.float32)
         cnt = np.zeros(batch, dtype=np.int32)

@@ -302,14 +302,107 @@ FLOW_METHOD = "lk"
 GENOME_SOURCE = os.environ.get("EIGEN_GENOME_SOURCE", "rank0")
 
 
+# Which quantity the population path selects by: "corners", the reference's score of at most lk_max_corners tracked corners (what
+# generate_illusion.py computes), or "dense", the dense motion score ``objective="flow"`` climbs (``DenseFitness``, DESIGN.md section
+# 14), with the defaults of ``DenseFitness.for_structure``.  get_fitnesses_neat keeps the reference's signature, so the choice is a
+# module setting (environment EIGEN_FITNESS_SCORE); evaluate_batch, evaluate_population and population_fitness also take it as `score`.
+FITNESS_SCORES = ("corners", "dense")
+FITNESS_SCORE = os.environ.get("EIGEN_FITNESS_SCORE", "corners")
+
+
+class DenseFitness:
+    """The dense motion score as the fitness of a genome (include/eigen_engine.h eigen_dense_score): a dense,
+    regularised Lucas-Kanade solve between the two emitted frames the fitness compares (windows of Chebyshev radius `radius`, `eps` on
+    the diagonal, as ``train.FlowObjective``), then the structure's score on the solved field, per genome: what
+    ``refine_genomes(objective="flow", flow=PredictionFlow(radius, eps).scored(score))`` climbs.
+    score: a ``train.FlowScore`` (Circles, CirclesFree), ``train.BandsScore`` or ``train.FreeScore``; None: the structure's defaults,
+    resolved by ``for_structure`` when the fitness is asked for a structure.  mask: [H, W], zero = the pixel is no member (None: all).
+    ValueError: the rules of ``train.FlowObjective`` for radius, eps and the mask (a per-sample mask is refused: the population has
+    one grid), and a score that is none of the three classes."""
+
+    def __init__(self, score=None, radius=7, eps=1e-2, mask=None):
+        from . import train
+        flow = train.FlowObjective(radius, eps, mask=mask)     # its rules, its words
+        if flow.per_sample:
+            raise ValueError("mask must be [H, W], shared by the population; got shape %s" % (flow.mask.shape,))
+        if score is not None and not isinstance(score, train.FLOW_SCORES):
+            raise ValueError("score must be a FlowScore, a BandsScore, a FreeScore or None, got %r" % (score,))
+        self.score, self.radius, self.eps, self.mask = score, flow.radius, flow.eps, flow.mask
+        self._dev = {}        # the mask on every device it was asked for, uploaded once
+        self._resolved = {}   # without a score of its own: the object of every structure's class, made once
+
+    @classmethod
+    def for_structure(cls, structure, radius=7, eps=1e-2, mask=None, **kw):
+        """The dense fitness of a structure: ``train.structure_score(structure, **kw)`` as the score"""
+        from . import train
+        return cls(train.structure_score(structure, **kw), radius=radius, eps=eps, mask=mask)
+
+    def resolved(self, structure):
+        """self with a score that belongs to `structure` (the structure's defaults where it has none).  ValueError: a score of another
+        structure's class."""
+        from . import train
+        want = type(train.structure_score(structure))
+        if self.score is None:      # made once per class; it shares this one's uploaded mask
+            if want not in self._resolved:
+                d = DenseFitness(want(), self.radius, self.eps, self.mask)
+                d._dev = self._dev
+                self._resolved[want] = d
+            return self._resolved[want]
+        if type(self.score) is not want:
+            raise ValueError("structure %d is scored by a %s, the DenseFitness carries a %s" % (int(structure), want.__name__, type(self.score).__name__))
+        return self
+
+    def flow_objective(self, pairing="prediction"):
+        """The ``train.FlowObjective`` / ``PredictionFlow`` that refines by this very score (``refine_genomes(flow=...)``)"""
+        from . import train
+        if self.score is None:
+            raise ValueError("the DenseFitness has no score yet: resolved(structure) gives it the structure's")
+        return train.make_flow(pairing, self.radius, self.eps, None, self.mask, score=self.score)
+
+    # what engine.Engine asks of a `dense` argument
+    def dense_settings(self, h):
+        from . import train
+        if self.score is None:
+            raise ValueError("the DenseFitness has no score yet: resolved(structure) gives it the structure's")
+        return self.radius, self.eps, self.score.settings(h), isinstance(self.score, train.FlowScore)
+
+    def mask_on(self, torch, device, h, w):
+        if self.mask is None:
+            return None
+        if tuple(self.mask.shape) != (h, w):
+            raise ValueError("mask is %s, the image is [%d, %d]" % (self.mask.shape, h, w))
+        if device not in self._dev:
+            self._dev[device] = torch.from_numpy(self.mask).cuda(device)
+        return self._dev[device]
+
+
+_DEFAULT_DENSE = DenseFitness()   # score="dense": the defaults of every structure, resolved once each
+
+
+def resolve_score(score, structure):
+    """`score` of evaluate_batch / evaluate_population / population_fitness -> None (the corner fitness) or the ``DenseFitness`` of the
+    call.  None: the module switch FITNESS_SCORE.  ValueError: neither "corners", "dense" nor a DenseFitness."""
+    if score is None:
+        score = FITNESS_SCORE
+    if isinstance(score, DenseFitness):
+        return score.resolved(structure)
+    if score == "corners":
+        return None
+    if score == "dense":
+        return _DEFAULT_DENSE.resolved(structure)
+    raise ValueError("score must be one of %s or a DenseFitness, got %r" % (", ".join(FITNESS_SCORES), score))
+
+
 def _engine_for(model_name, w, h, channels, max_batch, flow):
     flow = flow or FLOW_METHOD
     return get_engine(model_name, w, h, channels, max_batch=max_batch, **({} if flow == "lk" else {"flow": flow}))
 
 
 def evaluate_batch(structure, gb, n_in, model_name, w, h, channels, c_dim=3, gradient=1, bg=1,
-                   pairing=PAIR_POPULATION, max_batch=None, flow=None):
-    """Fitness (float64 array) of an already flattened genome batch on the local GPU, in chunks of max_batch."""
+                   pairing=PAIR_POPULATION, max_batch=None, flow=None, score=None):
+    """Fitness (float64 array) of an already flattened genome batch on the local GPU, in chunks of max_batch.  score: "corners",
+    "dense", a ``DenseFitness``, or None: the module switch FITNESS_SCORE."""
+    dense = resolve_score(score, structure)
     channels = [int(c) for c in channels]
     if channels[0] != c_dim:
         raise ValueError("channels[0]=%d but c_dim=%d: PredNet's input channels are the image channels" % (channels[0], c_dim))
@@ -318,18 +411,18 @@ def evaluate_batch(structure, gb, n_in, model_name, w, h, channels, c_dim=3, gra
     out = np.zeros(gb.n_genomes, dtype=np.float64)
     for i in range(0, gb.n_genomes, eng.max_batch):
         j = min(gb.n_genomes, i + eng.max_batch)
-        out[i:j] = eng.eval_population(gb.slice(i, j), int(structure), bg=bg, gradient=gradient, pairing=pairing)
+        out[i:j] = eng.eval_population(gb.slice(i, j), int(structure), bg=bg, gradient=gradient, pairing=pairing, **({} if dense is None else {"dense": dense}))
     return out
 
 
 def evaluate_population(structure, genomes, model_name, config, w, h, channels, c_dim=3, gradient=1, bg=1,
-                        pairing=PAIR_POPULATION, max_batch=None, flow=None):
-    """Fitness (float64 array) of a list of genome objects on the local GPU, in chunks of max_batch."""
+                        pairing=PAIR_POPULATION, max_batch=None, flow=None, score=None):
+    """Fitness (float64 array) of a list of genome objects on the local GPU, in chunks of max_batch.  score: as evaluate_batch."""
     n_in = len(config.genome_config.input_keys)
     c_out = c_dim if gradient == 1 else 1
     gb = GenomeBatch(genomes, config, c_out, n_leaves=n_in)  # Q6: the first c_dim outputs are rendered
     return evaluate_batch(structure, gb, n_in, model_name, w, h, channels, c_dim=c_dim, gradient=gradient, bg=bg,
-                          pairing=pairing, max_batch=max_batch, flow=flow)
+                          pairing=pairing, max_batch=max_batch, flow=flow, score=score)
 
 
 _warned_diverged = [False]
@@ -349,12 +442,14 @@ def population_digest(genomes):
 
 
 def population_fitness(structure, genomes, model_name, config, w, h, channels, c_dim=3, gradient=1, max_batch=None,
-                       flow=None, source=None):
+                       flow=None, source=None, score=None):
     """Fitness of the WHOLE population list on every rank: the population is sharded over the ranks (contiguous slices in
     list order), every rank evaluates its slice on its GPU, ONE all-gather of float64 scalars returns the full vector
-    (SURVEY 8(e)).  Single process: plain evaluate_population."""
+    (SURVEY 8(e)).  Single process: plain evaluate_population.  score: as evaluate_batch; it reaches every rank's evaluator as it is
+    given and changes nothing in the exchange: one float64 per genome in the same all-gather."""
     dist = _dist()
-    kw = dict(c_dim=c_dim, gradient=gradient, max_batch=max_batch, flow=flow)
+    resolve_score(score, structure)   # a bad score raises here, on every rank alike, ahead of any collective
+    kw = dict(c_dim=c_dim, gradient=gradient, max_batch=max_batch, flow=flow, score=score)
     if dist is None:
         return evaluate_population(structure, genomes, model_name, config, w, h, channels, **kw)
     source = source or GENOME_SOURCE

@@ -12,6 +12,9 @@
         would pick on every term's reference: train.CornerMembers)
         --flow-score [--flow-score-structure circles|bands|free|auto] [--flow-max-norm M] climbs the fitness's own score of that structure on the
         dense field: train.FlowScore, BandsScore or FreeScore; auto follows --structure)
+    python examples/evolve_illusion.py -g 5 --fitness dense [--flow-radius R] [--flow-eps E] [--flow-score [--flow-max-norm M]]   (selection by the dense
+        motion score of --structure, fitness.DenseFitness, in place of the corner tracks; with --refine K --objective flow --flow-score
+        --flow-pairing prediction selection and refinement use one score with the same settings)
 """
 import argparse
 import os
@@ -22,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from evolutionary_illusion_generator_amd import fitness, neat_lite as neat
-from examples.flow_args import add_flow_arguments, flow_of
+from examples.flow_args import add_flow_arguments, dense_fitness_of, flow_of
 
 
 def main():
@@ -40,6 +43,8 @@ def main():
     ap.add_argument("--refine", type=int, default=0, help="refine the parameters of this many of the best genomes after every generation (0: off)")
     ap.add_argument("--refine_iters", type=int, default=5, help="ascent steps of train.refine_genomes per generation")
     ap.add_argument("--objective", default="mse", choices=["mse", "error", "flow"], help="what --refine climbs")
+    ap.add_argument("--fitness", default="corners", choices=["corners", "dense"],
+                    help="what selects: the reference's score of the tracked corners, or the dense motion score of --structure (fitness.DenseFitness)")
     add_flow_arguments(ap, direction=dict(choices=["tangent", "radial", "horizontal", "vertical"], help="objective flow: the field (default: the mean square)"),
                        radius=dict(help=None), eps=dict(help=None),
                        reference=dict(choices=["constant", "moving"], help="objective flow: moving also follows how the term moves with the still as its reference frame"),
@@ -52,6 +57,14 @@ def main():
         torch.cuda.set_device(int(os.environ["LOCAL_RANK"]))
         torch.distributed.init_process_group("nccl")
     config = neat.Config(neat.DefaultGenome, neat.DefaultReproduction, neat.DefaultSpeciesSet, neat.DefaultStagnation, a.config)
+
+    inside = (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype("uint8")   # the pixels of the structure's grid: the members' mask
+    try:
+        dense = dense_fitness_of(a, a.structure, inside)
+    except ValueError as e:
+        raise SystemExit("--fitness dense: %s" % e)
+    if dense is not None:
+        fitness.FITNESS_SCORE = dense    # get_fitnesses_neat keeps the reference's signature: the module switch carries the choice
 
     def eval_genomes(genomes, config):
         fitness.get_fitnesses_neat(a.structure, genomes, a.model, config, w, h, channels, c_dim=a.color_space,
@@ -70,7 +83,7 @@ def main():
         best = sorted((g for _, g in genomes), key=lambda g: -g.fitness)[:a.refine]
         if not trainer:
             trainer.append(train.PredNetTrainer(a.model, channels, w, h, a.refine, 22))
-        flow = flow_of(a, w, h, (fitness.leaf_planes(a.structure, w, h)[0] != -1).astype("uint8"))
+        flow = flow_of(a, w, h, inside)
         refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters, objective=a.objective, flow=flow)
         for g, r in zip(best, refined):
             for k, n in r.nodes.items():

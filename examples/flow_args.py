@@ -72,3 +72,14 @@ def flow_of(a, w, h, mask=None):
     score = score_of(a)
     return train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask,
                            reference=a.flow_reference, score=score, members=members_of(a))
+
+
+def dense_fitness_of(a, structure, mask=None):
+    """the fitness.DenseFitness of the command line under --fitness dense (None under corners): the window of --flow-radius and --flow-eps,
+    the score of --flow-score where it is given (it must be `structure`'s: ValueError) and the structure's defaults otherwise, the
+    pixels of `mask`.  With --refine --objective flow --flow-score --flow-pairing prediction selection and refinement then use one score
+    with the same settings."""
+    from evolutionary_illusion_generator_amd import fitness
+    if getattr(a, "fitness", "corners") != "dense":
+        return None
+    return fitness.DenseFitness(score_of(a), radius=a.flow_radius, eps=a.flow_eps, mask=mask).resolved(structure)

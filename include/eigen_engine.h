@@ -775,6 +775,56 @@ int eigen_trainer_accumulate(eigen_trainer* t, int32_t op, double scale, void* s
 /* Device bytes of the handle's tape (activations kept for the backward pass) at max_batch x max_steps. */
 int64_t eigen_trainer_tape_bytes(const eigen_trainer* t);
 
+/* ---------------------------------------------------------------------------------------------------- dense fitness
+ * The dense motion score on the population path: the score EIGEN_OBJ_FLOW climbs, as the fitness of a genome.
+ * It needs an inference handle only: no trainer, no tape.  For every sample the stage takes two emitted uint8 frames img0 (the
+ * reference) and img1 and does what eigen_trainer_flow_term_pair does on the float images (float)byte / 255.0f of the two, img1 as the
+ * prediction and img0 as d_prev: the gray planes, the normalised Scharr pair of I0, It = I1 - I0, the five truncated window sums, the
+ * 2x2 solve with eps on the diagonal, the field u in float64, and then the two moment passes of the chosen score (for Free with the
+ * prepare and pair passes between them), in the operations and orders of csrc/flow_obj_kernels.h, flow_score_kernels.h and
+ * flow_struct_kernels.h.  The fitness of a sample is S_b, entry 8 of its own record; a sample with fewer than min_count members scores
+ * exactly 0.  Float64, one IEEE operation per operation written, fixed partitions and orders, no float atomics: the result of a
+ * sample does not depend on the batch it is in.  No seed, q or gradient is formed, and no corner, Lucas-Kanade or score_kernel launch
+ * happens.
+ *   flow: radius and eps as eigen_trainer_flow_term reads them; flags must be 0.  Exactly one of score (Circles, CirclesFree) and
+ *   sscore (Bands, Free) is non-NULL.
+ * The workspace, seven float64 planes of max_batch * H * W and one byte plane, is allocated by the first dense call on the handle, all
+ * of it or none, and freed with the handle. */
+typedef struct {
+    eigen_flow_settings flow;
+    const eigen_flow_score* score;
+    const eigen_flow_structure_score* sscore;
+} eigen_dense_settings;
+
+/* The stage alone on two batches of byte images, as eigen_flow is for Lucas-Kanade: image b at d_imgX + b * strideX (bytes), planar
+ * [C][H][W]; bytes between the images are never read.  d_mask: uint8 [H][W] shared by the batch, 0 = the pixel is no member, or NULL.
+ * Outputs, each may be NULL: h_fitness host double[batch], S_b; h_stats host double[batch][10], the records (eigen_trainer_flow_term_score
+ * / eigen_trainer_flow_term_structure state their entries); d_flow device double [batch][2][H][W], the field u.  The call synchronises
+ * the stream when it has a host output to write.
+ * Errors, before any launch, all EIGEN_ERR_INVALID: a NULL handle, image or settings, batch < 1 or above max_batch, a stride below
+ * C*H*W, both scores or neither, and what eigen_trainer_flow_term_score / _structure refuse for the radius, eps, flags, the mask and the
+ * score's fields, in their words. */
+int eigen_dense_score(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
+                      const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow,
+                      void* stream);
+
+/* eigen_eval_population with the dense stage in place of flow and score: render -> roll-out -> eigen_dense_score on the two frames
+ * the pairing names (POPULATION: the prediction after step n_repeat is img0, the first extension frame img1; SINGLE: the input image
+ * is img0, the second extension frame img1).  h_fitness: host double[n_genomes], required; h_stats: host double[n_genomes][10] or NULL.
+ * structure must be the one the settings' score belongs to: EIGEN_BANDS / EIGEN_FREE the sscore of that structure, EIGEN_CIRCLES /
+ * EIGEN_CIRCLES_FREE the score.  eigen_get_timings then reports the dense stage as [2] and 0 as [3].
+ * Errors: as eigen_eval_population and eigen_dense_score (a batch above max_batch is EIGEN_ERR_INVALID here too); EIGEN_ERR_INVALID a
+ * structure the settings' score does not belong to.  The structure, the pairing (n_ext), the batch and the settings are refused before
+ * the workspace is allocated and before the render; what eigen_render_cppn and eigen_prednet_rollout themselves refuse (no grid, no
+ * weights, a malformed genome) comes from them, as in eigen_eval_population. */
+int eigen_eval_population_dense(eigen_engine* e, const eigen_genome_batch* h_genomes, int32_t structure, int32_t bg, int32_t gradient,
+                                int32_t pairing, const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness,
+                                double* h_stats, void* stream);
+
+/* eigen_eval_images likewise, for ready-made images (there are no vectors and counts to return). */
+int eigen_eval_images_dense(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
+                            const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""What the dense motion fitness costs on the population path, against the corner fitness of the same run.
+
+    python scripts/dense_fitness_bench.py [--rounds 6] [--shapes headline,ref160] [--out profiles/dense_fitness_cost.txt]
+
+Per shape of bench.py (headline: 256 x 256 colour, pop 256; ref160: 160 x 120 colour, pop 50) and per structure,
+`fitness.population_fitness` is timed under score="corners" and score="dense" in alternation, one generation each per round, after
+one warm-up generation of each: the median (min .. max) of the rounds in genome evaluations per second, the ratio of the medians, and
+the device time of the stage that follows the roll-out (Lucas-Kanade + score, or the dense stage) against the roll-out's, from the
+engine's own HIP events.  A (shape, structure) whose dense generation takes longer than --slow seconds is timed for two rounds only, and
+the line says so.  For the headline genomes the agreement of the two fitnesses is recorded: Spearman's rank correlation (ties share
+their mean rank) and the share of genomes scoring exactly 0 under each.
+
+The output file has two parts: what this script measures, which a run replaces, and everything from the line NOTES_MARK on, which a run
+keeps as it finds it: the records of other commands of the same visit (the default path against the parent commit, the example), written by
+hand."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STRUCTURES = {0: "Bands", 1: "Circles", 2: "Free"}
+NOTES_MARK = "---- records of other commands of the same visit (kept by scripts/dense_fitness_bench.py, not written by it) ----"
+
+
+def ranks(v):
+    """ranks from 1, ties share their mean rank"""
+    v = np.asarray(v, np.float64)
+    order = np.argsort(v, kind="stable")
+    r = np.empty(len(v))
+    i = 0
+    while i < len(v):
+        j = i
+        while j + 1 < len(v) and v[order[j + 1]] == v[order[i]]:
+            j += 1
+        r[order[i:j + 1]] = 0.5 * (i + j) + 1.0
+        i = j + 1
+    return r
+
+
+def spearman(a, b):
+    ra, rb = ranks(a), ranks(b)
+    if ra.std() == 0 or rb.std() == 0:
+        return float("nan")
+    return float(np.corrcoef(ra, rb)[0, 1])
+
+
+def spread(v):
+    return "%.1f (%.1f .. %.1f)" % (float(np.median(v)), min(v), max(v))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--shapes", default="headline,ref160")
+    ap.add_argument("--slow", type=float, default=4.0, help="a dense generation slower than this many seconds is timed for two rounds only")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dense_fitness_cost.txt"))
+    a = ap.parse_args()
+    import torch
+    import bench
+    from evolutionary_illusion_generator_amd import fitness
+    lines = ["dense motion fitness against the corner fitness, %s, %d rounds, corners and dense alternated per round" % (torch.cuda.get_device_name(0), a.rounds),
+             "build %s" % bench.kernel_sources_sha(), ""]
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    for shape in a.shapes.split(","):
+        W, H, CHANNELS, C_DIM, _, _, _, pop, label = bench.SHAPES[shape]
+        cfg, population, wts = bench.make_workload(shape, pop)
+        genomes = [g for _, g in population]
+        max_batch = min(pop, 256)
+        eng = fitness.get_engine(wts, W, H, CHANNELS, max_batch=max_batch)
+        say("%s: %dx%d, PredNet %s, pop %d, device batch %d" % (shape, W, H, ",".join(map(str, CHANNELS)), pop, max_batch))
+        for structure, name in STRUCTURES.items():
+            def generation(score):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fit = fitness.population_fitness(structure, genomes, wts, cfg, W, H, CHANNELS, c_dim=C_DIM, gradient=1, max_batch=max_batch, score=score)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                t = eng.timings()
+                return fit, dt, t["prednet_ms"], t["flow_ms"] + t["score_ms"]
+
+            warm = {s: generation(s) for s in ("corners", "dense")}
+            rounds = a.rounds if warm["dense"][1] <= a.slow else min(a.rounds, 2)
+            rate, stage, roll = {"corners": [], "dense": []}, {"corners": [], "dense": []}, []
+            for _ in range(rounds):
+                for s in ("corners", "dense"):
+                    fit, dt, roll_ms, stage_ms = generation(s)
+                    assert fit.tobytes() == warm[s][0].tobytes(), "the fitness of a generation changed between rounds"
+                    rate[s].append(pop / dt)
+                    stage[s].append(stage_ms)
+                    roll.append(roll_ms)
+            fc, fd = warm["corners"][0], warm["dense"][0]
+            say("  %-7s corners %s evals/s, dense %s evals/s, dense / corners %.3f%s" % (
+                name, spread(rate["corners"]), spread(rate["dense"]), np.median(rate["dense"]) / np.median(rate["corners"]),
+                "" if rounds == a.rounds else "  [%d rounds: a dense generation takes %.1f s]" % (rounds, warm["dense"][1])))
+            say("          device ms per generation: roll-out %s; flow + score %s; dense stage %s = %.1f %% of the roll-out" % (
+                spread(roll), spread(stage["corners"]), spread(stage["dense"]), 100.0 * np.median(stage["dense"]) / np.median(roll)))
+            say("          agreement over the %d genomes: Spearman %.3f; scoring 0: corners %.1f %%, dense %.1f %%" % (
+                pop, spearman(fc, fd), 100.0 * float((fc == 0).mean()), 100.0 * float((fd == 0).mean())))
+        fitness.clear_engines()
+        say("")
+    kept = ""
+    if os.path.exists(a.out):
+        old = open(a.out).read()
+        if NOTES_MARK in old:
+            kept = old[old.index(NOTES_MARK):]
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n" + kept)
+
+
+if __name__ == "__main__":
+    main()
