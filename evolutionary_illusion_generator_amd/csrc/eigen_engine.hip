@@ -21,6 +21,7 @@
 #include "conv_plan.h"     // host: which operators run (plan_prednet) and in which launch shape (plan_launch)
 #include "cppn_kernel.h"
 #include "cppn_grad_kernel.h"
+#include "cppn_motion_kernel.h"
 #include "farneback_kernels.h"
 #include "flow_kernels.h"
 #include "score_kernels.h"
@@ -112,6 +113,8 @@ struct eigen_engine {
     DevBuf<uint8_t> g_node_act;
     DevBuf<double> g_node_bias, g_node_resp, g_edge_w;
     DevBuf<double> g_grad_slabs, g_grad_sum;   // eigen_cppn_param_grads: one slab per pixel block, and their sum
+    DevBuf<double> g_affine;                   // eigen_render_moving_cppn: every affine beside its inverse
+    std::vector<double> h_affine;              // ... as packed on the host (kept: the upload is asynchronous)
     // images / frames
     uint8_t* d_images = nullptr;  // [B][C0][H][W]
     uint8_t* d_frames = nullptr;  // [B][3][C0][H][W]
@@ -637,10 +640,9 @@ int eigen_set_grid(eigen_engine* e, const double* h_planes, int32_t n_planes)
 // lds_of(max_nodes, max_edges): the caller's LDS need; above 160 KiB the batch is refused before anything is uploaded.
 struct GenomeExtent { int total_nodes = 0, total_edges = 0, max_nodes = 0, max_edges = 0; size_t lds = 0; };
 
-static int stage_genomes(eigen_engine* e, const eigen_genome_batch* g, int need_out, size_t (*lds_of)(int, int), hipStream_t st, GenomeExtent& x, CppnArgs& a)
+// the host-side checks alone, against n_planes leaf planes; fills the extents but for x.lds
+static int check_genomes(const eigen_genome_batch* g, int need_out, int n_planes, GenomeExtent& x)
 {
-    if (!e->have_grid) return fail(EIGEN_ERR_STATE, "eigen_set_grid has not been called");
-    HIPCHK(hipSetDevice(e->cfg.device));
     const int G = g->n_genomes;
     if (G < 1) return fail(EIGEN_ERR_INVALID, "n_genomes < 1");
     if (g->c_out < need_out) return fail(EIGEN_ERR_INVALID, "genome batch provides %d outputs per genome, %d needed", g->c_out, need_out);
@@ -659,8 +661,8 @@ static int stage_genomes(eigen_engine* e, const eigen_genome_batch* g, int need_
         for (int n = n0; n < n1; ++n)
             for (int k = g->edge_off[n]; k < g->edge_off[n + 1]; ++k) {
                 const int src = g->edge_src[k];
-                if (src < -(e->n_planes + 1))
-                    return fail(EIGEN_ERR_INVALID, "genome %d: edge %d references leaf %d but only %d planes are set", gi, k, -src - 1, e->n_planes);
+                if (src < -(n_planes + 1))
+                    return fail(EIGEN_ERR_INVALID, "genome %d: edge %d references leaf %d but only %d planes are set", gi, k, -src - 1, n_planes);
                 if (src >= n - n0)
                     return fail(EIGEN_ERR_INVALID, "genome %d: edge %d of node %d reads node %d (not topologically earlier)", gi, k, n - n0, src);
             }
@@ -669,8 +671,14 @@ static int stage_genomes(eigen_engine* e, const eigen_genome_batch* g, int need_
             if (o < 0 || o >= n1 - n0) return fail(EIGEN_ERR_INVALID, "genome %d: output %d names node %d of %d", gi, c, o, n1 - n0);
         }
     }
-    const size_t lds = lds_of(max_nodes, max_edges);
-    if (lds > 160 * 1024) return fail(EIGEN_ERR_CAPACITY, "genome with %d nodes / %d edges needs %zu B of LDS (> 160 KiB)", max_nodes, max_edges, lds);
+    x.total_nodes = total_nodes; x.total_edges = total_edges; x.max_nodes = max_nodes; x.max_edges = max_edges;
+    return EIGEN_OK;
+}
+
+// the checked batch on the device; GENOME_ARGS(a): the fields every CPPN kernel's arguments share, from the staging buffers
+static int upload_genomes(eigen_engine* e, const eigen_genome_batch* g, const GenomeExtent& x, hipStream_t st)
+{
+    const int G = g->n_genomes, total_nodes = x.total_nodes, total_edges = x.total_edges;
     if (e->g_node_off.ensure(G + 1) || e->g_edge_off.ensure(total_nodes + 1) || e->g_node_act.ensure(total_nodes) ||
         e->g_node_bias.ensure(total_nodes) || e->g_node_resp.ensure(total_nodes) || e->g_edge_src.ensure(std::max(total_edges, 1)) ||
         e->g_edge_w.ensure(std::max(total_edges, 1)) || e->g_out_node.ensure((size_t)G * g->c_out))
@@ -685,11 +693,27 @@ static int stage_genomes(eigen_engine* e, const eigen_genome_batch* g, int need_
         HIPCHK(hipMemcpyAsync(e->g_edge_w.p, g->edge_w, sizeof(double) * total_edges, hipMemcpyHostToDevice, st));
     }
     HIPCHK(hipMemcpyAsync(e->g_out_node.p, g->out_node, sizeof(int32_t) * G * g->c_out, hipMemcpyHostToDevice, st));
-    a.node_off = e->g_node_off.p; a.edge_off = e->g_edge_off.p; a.node_act = e->g_node_act.p;
-    a.node_bias = e->g_node_bias.p; a.node_resp = e->g_node_resp.p; a.edge_src = e->g_edge_src.p; a.edge_w = e->g_edge_w.p;
-    a.out_node = e->g_out_node.p; a.planes = e->d_planes; a.n_planes = e->n_planes; a.N = e->H * e->W;
-    a.c_out = g->c_out; a.c_dim = e->C0; a.max_nodes = max_nodes;
-    x.total_nodes = total_nodes; x.total_edges = total_edges; x.max_nodes = max_nodes; x.max_edges = max_edges; x.lds = lds;
+    return EIGEN_OK;
+}
+#define GENOME_ARGS(a)                                                                                                          \
+    do {                                                                                                                        \
+        (a).node_off = e->g_node_off.p; (a).edge_off = e->g_edge_off.p; (a).node_act = e->g_node_act.p;                         \
+        (a).node_bias = e->g_node_bias.p; (a).node_resp = e->g_node_resp.p; (a).edge_src = e->g_edge_src.p;                     \
+        (a).edge_w = e->g_edge_w.p; (a).out_node = e->g_out_node.p; (a).N = e->H * e->W; (a).c_out = g->c_out; (a).c_dim = e->C0; \
+    } while (0)
+
+static int stage_genomes(eigen_engine* e, const eigen_genome_batch* g, int need_out, size_t (*lds_of)(int, int), hipStream_t st, GenomeExtent& x, CppnArgs& a)
+{
+    if (!e->have_grid) return fail(EIGEN_ERR_STATE, "eigen_set_grid has not been called");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    int rc = check_genomes(g, need_out, e->n_planes, x);
+    if (rc != EIGEN_OK) return rc;
+    x.lds = lds_of(x.max_nodes, x.max_edges);
+    if (x.lds > 160 * 1024) return fail(EIGEN_ERR_CAPACITY, "genome with %d nodes / %d edges needs %zu B of LDS (> 160 KiB)", x.max_nodes, x.max_edges, x.lds);
+    rc = upload_genomes(e, g, x, st);
+    if (rc != EIGEN_OK) return rc;
+    GENOME_ARGS(a);
+    a.planes = e->d_planes; a.n_planes = e->n_planes; a.max_nodes = x.max_nodes;
     return EIGEN_OK;
 }
 
@@ -731,6 +755,64 @@ int eigen_eval_cppn_nodes(eigen_engine* e, const eigen_genome_batch* g, double* 
 {
     if (!e || !g || !d_nodes) return fail(EIGEN_ERR_INVALID, "null argument");
     return render_cppn_impl(e, g, 1, 3, nullptr, d_nodes, stream);
+}
+
+int eigen_render_moving_cppn(eigen_engine* e, const eigen_genome_batch* g, int32_t n, int32_t n_frames, int32_t n_layers, const double* h_affine,
+                             const double* h_affine_inv, uint8_t* d_frames, int64_t f_bstride, double* d_flow, uint8_t* d_layer, void* stream)
+{
+    if (!e || !g || !h_affine || !d_frames) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (n_layers < 1 || n_layers > 2) return fail(EIGEN_ERR_INVALID, "n_layers %d outside 1..2", n_layers);
+    if (n_frames < 1) return fail(EIGEN_ERR_INVALID, "n_frames %d < 1", n_frames);
+    if (n < 1) return fail(EIGEN_ERR_INVALID, "n %d < 1", n);
+    if (d_flow && n_frames < 2) return fail(EIGEN_ERR_INVALID, "a flow needs two frames, n_frames is %d", n_frames);
+    if (d_flow && !h_affine_inv) return fail(EIGEN_ERR_INVALID, "d_flow without h_affine_inv");
+    if (!d_flow && h_affine_inv) return fail(EIGEN_ERR_INVALID, "h_affine_inv without d_flow");
+    if (n > 65535) return fail(EIGEN_ERR_CAPACITY, "n %d exceeds the 65535 samples of one launch", n);
+    if ((long long)g->n_genomes != (long long)n * n_layers)
+        return fail(EIGEN_ERR_INVALID, "the batch holds %d genomes, n * n_layers = %lld", g->n_genomes, (long long)n * n_layers);
+    const long long seq = (long long)n_frames * e->C0 * e->H * e->W;
+    if (f_bstride < seq) return fail(EIGEN_ERR_INVALID, "f_bstride %lld < n_frames*C*H*W = %lld", (long long)f_bstride, seq);
+    if (!g->node_off || !g->edge_off || !g->node_act || !g->node_bias || !g->node_resp || !g->edge_src || !g->edge_w || !g->out_node)
+        return fail(EIGEN_ERR_INVALID, "null array in the genome batch");
+    GenomeExtent x;
+    int rc = check_genomes(g, e->C0, 2, x);   // the two leaves are u and v, whatever grid the handle has or has not
+    if (rc != EIGEN_OK) return rc;
+    // a block holds the columns of its sample's larger program beside both of its programs
+    for (int b = 0; b < n; ++b) {
+        size_t progs = 0;
+        int mn = 0;
+        for (int gi = b * n_layers; gi < (b + 1) * n_layers; ++gi) {
+            const int nn = g->node_off[gi + 1] - g->node_off[gi], ne = g->edge_off[g->node_off[gi + 1]] - g->edge_off[g->node_off[gi]];
+            progs += cppn_program_bytes(nn, ne);
+            mn = std::max(mn, nn);
+        }
+        const size_t lds = (size_t)mn * CPPN_THREADS * sizeof(double) + progs;
+        if (lds > 160 * 1024) return fail(EIGEN_ERR_CAPACITY, "sample %d: %d nodes in its larger program need %zu B of LDS (> 160 KiB)", b, mn, lds);
+        x.lds = std::max(x.lds, lds);
+    }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    CppnMotionArgs a;
+    rc = upload_genomes(e, g, x, st);
+    if (rc != EIGEN_OK) return rc;
+    GENOME_ARGS(a);
+    // one record of twelve per sample, frame and layer: the affine, then its inverse (zeros without a flow, never read)
+    const size_t n_aff = (size_t)n * n_frames * n_layers;
+    std::vector<double>& packed = e->h_affine;
+    packed.assign(n_aff * 12, 0.0);
+    for (size_t i = 0; i < n_aff; ++i) {
+        std::copy(h_affine + i * 6, h_affine + i * 6 + 6, packed.begin() + i * 12);
+        if (d_flow) std::copy(h_affine_inv + i * 6, h_affine_inv + i * 6 + 6, packed.begin() + i * 12 + 6);
+    }
+    if (e->g_affine.ensure(n_aff * 12)) return fail(EIGEN_ERR_HIP, "hipMalloc for the affines failed");
+    HIPCHK(hipMemcpyAsync(e->g_affine.p, packed.data(), sizeof(double) * n_aff * 12, hipMemcpyHostToDevice, st));
+    a.affine = e->g_affine.p;
+    a.W = e->W; a.H = e->H; a.T = n_frames; a.L = n_layers;
+    a.frames = d_frames; a.f_bstride = f_bstride; a.flow = d_flow; a.layer = d_layer;
+    (void)hipFuncSetAttribute((const void*)cppn_motion_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds);
+    hipLaunchKernelGGL(cppn_motion_kernel, dim3((a.N + CPPN_THREADS - 1) / CPPN_THREADS, n), dim3(CPPN_THREADS), x.lds, st, a);
+    HIPCHK(hipGetLastError());
+    return EIGEN_OK;
 }
 
 int eigen_cppn_param_grads(eigen_engine* e, const eigen_genome_batch* g, int32_t bg, int32_t gradient, const float* d_image_grad, int64_t g_bstride,

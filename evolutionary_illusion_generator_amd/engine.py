@@ -28,7 +28,8 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_trainer_flow_term_score", "eigen_trainer_loss_grad_flow_score", "eigen_trainer_flow_term_structure",
            "eigen_trainer_loss_grad_flow_structure", "eigen_trainer_debug_free_planes", "eigen_trainer_flow_members",
            "eigen_trainer_flow_term_members", "eigen_trainer_loss_grad_flow_members", "eigen_trainer_grad_norms", "eigen_trainer_adam_ex",
-           "eigen_trainer_accumulate", "eigen_dense_score", "eigen_eval_population_dense", "eigen_eval_images_dense"]
+           "eigen_trainer_accumulate", "eigen_dense_score", "eigen_eval_population_dense", "eigen_eval_images_dense",
+           "eigen_render_moving_cppn"]
 
 
 class EigenConfig(ctypes.Structure):
@@ -154,6 +155,27 @@ def plan_text(channels, width, height, batch, n_cu=256, wino_mask=-1, step0=Fals
     return rows
 
 
+def check_moving_affines(affine, affine_inv, n_genomes, flow):
+    """The affines of ``Engine.render_moving_cppn`` as contiguous float64 arrays (affine, affine_inv or None).  ValueError: an affine
+    that is not [n >= 1, T >= 1, L in (1, 2), 6], n * L not the batch's genome count, flow without an inverse or with fewer than two
+    frames, an inverse of another shape."""
+    a = np.ascontiguousarray(affine, dtype=np.float64)
+    if a.ndim != 4 or a.shape[0] < 1 or a.shape[1] < 1 or a.shape[2] not in (1, 2) or a.shape[3] != 6:
+        raise ValueError("affine must be float64 [n, T, L in (1, 2), 6], got shape %s" % (a.shape,))
+    if a.shape[0] * a.shape[2] != n_genomes:
+        raise ValueError("%d samples of %d layers need %d genomes, the batch has %d" % (a.shape[0], a.shape[2], a.shape[0] * a.shape[2], n_genomes))
+    if not flow:
+        return a, None
+    if affine_inv is None:
+        raise ValueError("flow=True needs affine_inv")
+    if a.shape[1] < 2:
+        raise ValueError("flow=True needs at least two frames, affine has %d" % a.shape[1])
+    i = np.ascontiguousarray(affine_inv, dtype=np.float64)
+    if i.shape != a.shape:
+        raise ValueError("affine_inv has shape %s, affine %s" % (i.shape, a.shape))
+    return a, i
+
+
 class Engine:
     """One engine handle = one GPU rank.  Sizes are fixed at creation (workspaces live in HBM)."""
 
@@ -228,6 +250,32 @@ class Engine:
         """float64 [n, c_out, H*W] raw output-node values (create_cppn node calls, generate_illusion.py:395)."""
         s = self._genome_struct(gb)
         _check(self.lib.eigen_eval_cppn_nodes(self._h, ctypes.byref(s), _ptr(d_nodes), _stream_arg(stream)))
+
+    def render_moving_cppn(self, gb, affine, affine_inv=None, flow=False, layer=False, out=None, stream=None):
+        """eigen_render_moving_cppn ("Moving textures"): n sequences of T frames of one or two CPPN layers on affine
+        coordinates.  affine: float64 [n, T, L, 6], pixel -> texture, genome b * L + l of `gb` being layer l of sample b; affine_inv: the
+        same shape, texture -> pixel, needed with flow=True.  out: a uint8 device tensor [n, T, C, H, W] to render into, contiguous but
+        for its stride between samples (default: a fresh one).
+        -> (frames uint8 [n, T, C, H, W], flow float64 [n, T - 1, 2, H, W] or None, layer uint8 [n, T, H, W] or None), device tensors."""
+        import torch
+        affine = check_moving_affines(affine, affine_inv if flow else None, gb.n_genomes, flow)
+        n, T, L = affine[0].shape[:3]
+        shape = (n, T, self.c_dim, self.height, self.width)
+        seq = int(np.prod(shape[1:]))
+        dev = torch.device("cuda", self.cfg.device)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_cuda or (n > 1 and out.stride(0) < seq) \
+                or tuple(out.stride()[1:]) != (seq // T, self.height * self.width, self.width, 1):
+            raise ValueError("out must be a uint8 device tensor %s, every sequence contiguous" % (shape,))
+        bstride = int(out.stride(0)) if n > 1 else seq
+        d_flow = torch.empty((n, T - 1, 2, self.height, self.width), dtype=torch.float64, device=dev) if flow else None
+        d_layer = torch.empty((n, T, self.height, self.width), dtype=torch.uint8, device=dev) if layer else None
+        s = self._genome_struct(gb)
+        _check(self.lib.eigen_render_moving_cppn(self._h, ctypes.byref(s), ctypes.c_int32(n), ctypes.c_int32(T), ctypes.c_int32(L), _ptr(affine[0]),
+                                                 _ptr(affine[1]) if flow else None, _ptr(out), ctypes.c_int64(bstride), _ptr(d_flow), _ptr(d_layer),
+                                                 _stream_arg(stream)))
+        return out, d_flow, d_layer
 
     def cppn_param_grads(self, gb, d_image_grad, bg=1, gradient=1, stream=None):
         """The gradient of a loss by the parameters of the genomes of `gb`, from its gradient by their gradient = 1 renders (DESIGN.md

@@ -1357,6 +1357,165 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     return out, history, images
 
 
+# ---- moving CPPN textures: a seeded, device-resident frame source with its exact flow ("Moving textures")
+def similarity_affines(c, o, m, d, n_frames):
+    """One layer's affines of a constant similarity per frame, in closed form.  Pixels and texture points are complex numbers
+    (z = px + i py about the image centre, w = u + i v): the texture sits at w = c z + o in frame 0 and every frame moves the surface
+    by g(z) = m z + d (m = zoom * exp(i turn), d the shift).  g^t(z) = m^t z + D_t with D_t = d (1 + m + ... + m^(t - 1)), so
+      A_t  = A_0 o g^-t :  w = (c / m^t) z + (o - (c / m^t) D_t)
+      A_t^-1            :  z = (m^t / c) w + (D_t - (m^t / c) o)
+    with m^t = zoom^t exp(i t turn) from pow, cos and sin, never from a product of t factors or a numerical inverse.
+    -> (affine, affine_inv), float64 [n_frames, 6]: rows (a0 .. a5) of u = a0 px + a1 py + a2, v = a3 px + a4 py + a5."""
+    c, o, m, d = complex(c), complex(o), complex(m), complex(d)
+    zoom, turn = abs(m), np.arctan2(m.imag, m.real)
+    A, Ainv = np.zeros((n_frames, 6), np.float64), np.zeros((n_frames, 6), np.float64)
+    geo = 0j   # 1 + m + ... + m^(t - 1)
+    for t in range(n_frames):
+        mt = (zoom ** t) * complex(np.cos(t * turn), np.sin(t * turn))
+        ct, it = c / mt, mt / c
+        ot, pt = o - ct * (d * geo), d * geo - it * o
+        A[t] = (ct.real, -ct.imag, ot.real, ct.imag, ct.real, ot.imag)
+        Ainv[t] = (it.real, -it.imag, pt.real, it.imag, it.real, pt.imag)
+        geo += mt
+    return A, Ainv
+
+
+def flat_genome_batch(flats, c_out):
+    """The ``GenomeBatch`` of a list of ``genome.flatten_genome`` dicts, c_out outputs of each."""
+    from .genome import GenomeBatch
+    e0 = np.cumsum([0] + [len(f["edge_w"]) for f in flats])
+    arrays = (np.cumsum([0] + [len(f["act"]) for f in flats]), np.concatenate([[0]] + [f["edge_off"][1:] + e for f, e in zip(flats, e0)]),
+              np.concatenate([f["act"] for f in flats]), np.concatenate([f["bias"] for f in flats]), np.concatenate([f["resp"] for f in flats]),
+              np.concatenate([f["edge_src"] for f in flats]), np.concatenate([f["edge_w"] for f in flats]),
+              np.concatenate([f["out_node"][:c_out] for f in flats]))
+    return GenomeBatch._from_arrays(len(flats), c_out, arrays)
+
+
+def check_moving_textures(w, h, c_dim, seq, seed=0, layers=1, max_shift=1.5, max_turn=0.02, max_zoom=0.01, texture_scale=None, num_hidden=20):
+    """The arguments of ``MovingTextures`` as (w, h, c_dim, seq, seed, layers, max_shift, max_turn, max_zoom, texture_scale,
+    num_hidden), texture_scale filled in (3 / max(w, h): the longer side spans three texture units).  ValueError: w, h, seq or
+    num_hidden not an integer >= 1, c_dim not 1 or 3, layers not 1 or 2, a seed that is not an integer >= 0, max_shift or max_turn
+    negative or not finite, max_zoom outside [0, 1), a texture_scale that is not finite and > 0, a bool or a non-number where a
+    number goes."""
+    def integer(name, v, lo):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError("%s must be an integer >= %d, got %r" % (name, lo, v))
+        return int(v)
+
+    def number(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError("%s must be a finite number, got %r" % (name, v))
+        return float(v)
+    w, h, seq, num_hidden = integer("w", w, 1), integer("h", h, 1), integer("seq", seq, 1), integer("num_hidden", num_hidden, 1)
+    seed = integer("seed", seed, 0)
+    if isinstance(c_dim, (bool, np.bool_)) or c_dim not in (1, 3):
+        raise ValueError("c_dim must be 1 or 3, got %r" % (c_dim,))
+    if isinstance(layers, (bool, np.bool_)) or layers not in (1, 2):
+        raise ValueError("layers must be 1 or 2, got %r" % (layers,))
+    max_shift, max_turn, max_zoom = number("max_shift", max_shift), number("max_turn", max_turn), number("max_zoom", max_zoom)
+    if max_shift < 0 or max_turn < 0:
+        raise ValueError("max_shift and max_turn must be >= 0, got %r and %r" % (max_shift, max_turn))
+    if not 0 <= max_zoom < 1:
+        raise ValueError("max_zoom must be in [0, 1), got %r" % (max_zoom,))
+    texture_scale = 3.0 / max(w, h) if texture_scale is None else number("texture_scale", texture_scale)
+    if not texture_scale > 0:
+        raise ValueError("texture_scale must be > 0, got %r" % (texture_scale,))
+    return w, h, int(c_dim), seq, seed, int(layers), max_shift, max_turn, max_zoom, texture_scale, num_hidden
+
+
+class MovingTextures:
+    """An unlimited, seeded stream of uint8 [n, seq, C, H, W] sequences of moving CPPN textures, rendered on the device with the
+    exact flow of every pixel (``Engine.render_moving_cppn``; DESIGN.md section 13, "Moving textures").
+
+    Batch index k holds the samples drawn from ``numpy.random.default_rng((seed, k))``: per sample and layer a ``synth.make_genome``
+    texture with num_hidden hidden nodes and a constant similarity per frame about the image centre (a shift of at most max_shift
+    pixels, a turn of at most max_turn radians, a zoom factor within 1 +- max_zoom), composed in closed form
+    (``similarity_affines``).  Layer 0 fills the image, texture_scale texture units per pixel; with layers=2 layer 1 is a disc (an
+    ellipse once it zooms) with a texture and a motion of its own in front of it: an occlusion boundary with two motions.
+    ``check_moving_textures`` states the argument rules (ValueError).  engine: an ``Engine`` of this size and c_dim to render
+    with; without one the object creates a one-layer engine of max_batch 1 (the entry does not depend on it) and closes it with
+    itself."""
+
+    def __init__(self, w, h, c_dim, seq, seed=0, layers=1, max_shift=1.5, max_turn=0.02, max_zoom=0.01, texture_scale=None, num_hidden=20, engine=None,
+                 device=None):
+        (self.w, self.h, self.c_dim, self.seq, self.seed, self.layers, self.max_shift, self.max_turn, self.max_zoom, self.texture_scale,
+         self.num_hidden) = check_moving_textures(w, h, c_dim, seq, seed, layers, max_shift, max_turn, max_zoom, texture_scale, num_hidden)
+        if engine is not None and (engine.width, engine.height, engine.c_dim) != (self.w, self.h, self.c_dim):
+            raise ValueError("the engine renders (%d, %d, %d), the textures are (%d, %d, %d) (w, h, c_dim)"
+                             % (engine.width, engine.height, engine.c_dim, self.w, self.h, self.c_dim))
+        self.engine, self._own, self.device = engine, False, device
+        from . import synth
+        self.config = synth.make_config(2, self.c_dim)
+
+    def describe(self, k, n):
+        """Host only: the n samples of batch index k as a dict -- w, h, c_dim, n, T, L; genomes (n * L ``synth`` genomes, sample-major)
+        and config; gb, their ``GenomeBatch`` (``genome.flatten_genome`` of each); affine and affine_inv, float64 [n, T, L, 6];
+        motion, float64 [n, L, 4]: the drawn (shift x, shift y, turn, zoom) of every layer."""
+        from . import synth
+        from .genome import flatten_genome
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError("the batch index must be an integer >= 0, got %r" % (k,))
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError("n must be an integer >= 1, got %r" % (n,))
+        rng = np.random.default_rng((self.seed, int(k)))
+        T, L = self.seq, self.layers
+        genomes, flats = [], []
+        affine, affine_inv, motion = np.zeros((n, T, L, 6)), np.zeros((n, T, L, 6)), np.zeros((n, L, 4))
+        for b in range(n):
+            for l in range(L):
+                g = synth.make_genome(b * L + l + 1, self.config, int(rng.integers(1 << 31)), num_hidden=self.num_hidden)
+                genomes.append(g)
+                flats.append(flatten_genome(g, self.config))
+                r, ang = rng.uniform(0.0, self.max_shift), rng.uniform(0.0, 2 * np.pi)
+                turn, zoom = rng.uniform(-self.max_turn, self.max_turn), rng.uniform(1 - self.max_zoom, 1 + self.max_zoom)
+                d, m = r * complex(np.cos(ang), np.sin(ang)), zoom * complex(np.cos(turn), np.sin(turn))
+                phi = rng.uniform(0.0, 2 * np.pi)
+                rot = complex(np.cos(phi), np.sin(phi))
+                if l == 0:   # the texture under the whole image, at a seeded offset
+                    c, o = self.texture_scale * rot, complex(rng.uniform(-1, 1), rng.uniform(-1, 1))
+                else:        # a disc of 0.2 .. 0.35 of the shorter side, its centre in the middle half of the image
+                    radius = rng.uniform(0.2, 0.35) * min(self.w, self.h)
+                    zc = complex(rng.uniform(-0.25, 0.25) * self.w, rng.uniform(-0.25, 0.25) * self.h)
+                    c = rot / radius
+                    o = -c * zc
+                affine[b, :, l], affine_inv[b, :, l] = similarity_affines(c, o, m, d, T)
+                motion[b, l] = (d.real, d.imag, turn, zoom)
+        gb = flat_genome_batch(flats, self.c_dim)
+        return dict(w=self.w, h=self.h, c_dim=self.c_dim, n=int(n), T=T, L=L, genomes=genomes, config=self.config, gb=gb, affine=affine,
+                    affine_inv=affine_inv, motion=motion)
+
+    def _engine(self):
+        if self.engine is None:
+            from .fitness import _local_device
+            self.engine = engine.Engine(self.w, self.h, [self.c_dim], 1, device=_local_device() if self.device is None else int(self.device))
+            self._own = True
+        return self.engine
+
+    def batch(self, k, n, flow=False, stream=None):
+        """The device uint8 [n, seq, C, H, W] tensor of batch index k; flow=True: (frames, flow float64 [n, seq - 1, 2, H, W], layer
+        uint8 [n, seq, H, W]).  The same (seed, k, n) always gives the same bytes."""
+        d = self.describe(k, n)
+        frames, fl, layer = self._engine().render_moving_cppn(d["gb"], d["affine"], d["affine_inv"] if flow else None, flow=flow, layer=flow, stream=stream)
+        return (frames, fl, layer) if flow else frames
+
+    def close(self):
+        if self._own and self.engine is not None:
+            self.engine.close()
+        self.engine, self._own = None, False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 __all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update", "FlowObjective",
            "PredictionFlow", "make_flow", "flow_direction", "FlowScore", "BandsScore", "FreeScore", "structure_score", "CornerMembers", "check_optim",
-           "check_micro_batches"]
+           "check_micro_batches", "MovingTextures", "check_moving_textures", "similarity_affines", "flat_genome_batch"]

@@ -3,12 +3,14 @@
 result in the fitness path.
 
     python examples/train_prednet.py -o trained.npz [-i frames_dir] [--size 160x120] [-c 3] [--steps 200] [--seq 10] [--batch 8]
-                                     [--loss mse|l0|lall]
+                                     [--data rings|textures [--texture-layers 1|2]] [--loss mse|l0|lall]
                                      [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K]
                                      [--ext-steps 200 --ext-frames 4 [--requant]] [--checkpoint ckpt.npz [--every 50]] [--resume ckpt.npz]
 
 Input: the PNG files of a folder, in name order, centre-cropped to --size, cut into windows of --seq frames; without -i, seeded
-drifting patterns (rings moving in a different direction per sequence).  The last window (or a held-out seed) is kept out of
+drifting patterns (rings moving in a different direction per sequence), or with --data textures moving CPPN textures rendered on
+the device (train.MovingTextures: a seeded texture per sequence under its own shift, turn and zoom; --texture-layers 2 puts a
+second, disc-shaped texture with a motion of its own in front).  The last window (or a held-out seed) is kept out of
 training.  Phase 1 is teacher-forced: every step reads its frame.  --ext-steps adds a second, self-fed fine-tuning phase: the last
 --ext-frames steps of every sequence read the network's own prediction (through the emitted byte with --requant), the regime the
 fitness path scores; its loss weights only the self-fed predictions.  --checkpoint writes weights, Adam state and step counter as
@@ -31,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 from evolutionary_illusion_generator_amd import fitness, grids, synth, weights
-from evolutionary_illusion_generator_amd.train import PredNetTrainer, check_micro_batches, check_optim
+from evolutionary_illusion_generator_amd.train import MovingTextures, PredNetTrainer, check_micro_batches, check_optim
 
 
 def read_windows(folder, c_dim, w, h, seq):
@@ -63,6 +65,8 @@ def main():
     ap.add_argument("--size", default="160x120", help="WxH")
     ap.add_argument("--color_space", "-c", type=int, default=3)
     ap.add_argument("--channels", "-ch", default=None, help="PredNet channels (default: c,48,96,192)")
+    ap.add_argument("--data", default="rings", choices=["rings", "textures"], help="the seeded source without -i: drifting rings (host) or moving CPPN textures (device)")
+    ap.add_argument("--texture-layers", type=int, default=1, choices=[1, 2], help="--data textures: 2 adds a disc with a motion of its own (an occlusion boundary)")
     ap.add_argument("--steps", type=int, default=200, help="Adam steps")
     ap.add_argument("--seq", type=int, default=10, help="frames per sequence")
     ap.add_argument("--batch", type=int, default=8)
@@ -82,10 +86,19 @@ def main():
     w, h = (int(v) for v in args.size.lower().split("x"))
     channels = [int(c) for c in args.channels.split(",")] if args.channels else [args.color_space, 48, 96, 192]
     c_dim = channels[0]
+    if args.input and args.data != "rings":
+        ap.error("--data %s is a source of its own: it does not go with --input" % args.data)
     if args.input:
         windows = read_windows(args.input, c_dim, w, h, args.seq)
         held, train = windows[-1:], windows[:-1]
         batch_of = lambda k: train[np.arange(k * args.batch, (k + 1) * args.batch) % len(train)]
+    elif args.data == "textures":
+        try:
+            source = MovingTextures(w, h, c_dim, args.seq, layers=args.texture_layers)
+        except ValueError as e:
+            ap.error(str(e))
+        held = source.batch(10 ** 6, args.batch)      # uint8 on the device: the trainer reads it where it is
+        batch_of = lambda k: source.batch(k, args.batch)
     else:
         held = drifting(10 ** 6, args.batch, args.seq, c_dim, w, h)
         batch_of = lambda k: drifting(k, args.batch, args.seq, c_dim, w, h)

@@ -151,6 +151,31 @@ int eigen_render_cppn(eigen_engine* e, const eigen_genome_batch* h_genomes, int3
  * d_nodes: float64 [n_genomes][c_out][H*W].  Used by the import shim pytorch_neat.pytorch_neat.cppn. */
 int eigen_eval_cppn_nodes(eigen_engine* e, const eigen_genome_batch* h_genomes, double* d_nodes, void* stream);
 
+/* Moving CPPN textures with their exact flow ("Moving textures"): n sequences of n_frames frames, each the
+ * gradient = 1 render of one or two genomes on affine coordinates.  Genome b * n_layers + l of the batch is layer l of sample b.
+ *   px = col - (W - 1) / 2, py = row - (H - 1) / 2; with A = h_affine[b][t][l] (pixel -> texture):
+ *   u = (a0 px + a1 py) + a2, v = (a3 px + a4 py) + a5, every product and sum one float64 rounding; leaves x = u, y = v, any further
+ *   leaf reads 1.0.  Layer 0 covers every pixel, layer 1 where u1 u1 + v1 v1 < 1.0 (a unit disc in its texture space); a pixel shows
+ *   the topmost layer that covers it.  byte = uint8(255 value_c) of the visible layer's output c, as eigen_render_cppn's gradient = 1
+ *   render quantises, with no background fill: a coordinate of exactly -1.0 is an ordinary coordinate.
+ *   d_frames: uint8, sample b at d_frames + b * f_bstride as [n_frames][c_dim][H][W]; f_bstride >= n_frames*C*H*W, the bytes between
+ *     two samples are not written.
+ *   d_flow (or NULL): float64 [n][n_frames - 1][2][H][W].  With I = h_affine_inv[b][t + 1][visible layer] (texture -> pixel centre)
+ *     slot t holds ((i0 u + i1 v) + i2 - px, (i3 u + i4 v) + i5 - py): where the surface visible at the pixel in frame t is in frame
+ *     t + 1, whether or not it is visible there.  The inverses are the caller's: nothing is inverted here.
+ *   d_layer (or NULL): uint8 [n][n_frames][H][W], the visible layer, 0 or 1.
+ * The entry needs neither a grid nor weights, reads no kept sequence state and uses no workspace of the handle but the genome staging
+ * buffers, which grow with the call: n is not tied to max_batch.  One sample is one row of the launch, hence n <= 65535.
+ * Errors, before anything is launched or allocated: EIGEN_ERR_INVALID a NULL handle, batch, h_affine or d_frames, n_layers outside
+ * 1 .. 2, n_frames < 1, n < 1, d_flow with n_frames < 2, d_flow without h_affine_inv or h_affine_inv without d_flow, n_genomes !=
+ * n * n_layers, c_out < c_dim, f_bstride < n_frames*C*H*W, and the genome checks of eigen_render_cppn (against two leaf planes);
+ * EIGEN_ERR_CAPACITY n > 65535, or a sample whose larger program's node values, beside both programs, need more than 160 KiB of LDS. */
+int eigen_render_moving_cppn(eigen_engine* e, const eigen_genome_batch* h_genomes, int32_t n, int32_t n_frames, int32_t n_layers,
+                             const double* h_affine,      /* [n][n_frames][n_layers][6] pixel -> texture */
+                             const double* h_affine_inv,  /* same shape, texture -> pixel; NULL iff d_flow is NULL */
+                             uint8_t* d_frames, int64_t f_bstride,
+                             double* d_flow, uint8_t* d_layer, void* stream);
+
 /* The backward pass through eigen_render_cppn's gradient = 1 render ("CPPN parameter gradients"): the gradient
  * of a loss by every bias, response and connection weight of the batch, from its gradient by the images.
  *   d_image_grad: device float, d loss / d (byte / 255) of image g at d_image_grad + g * g_bstride as [c_dim][H][W] (what

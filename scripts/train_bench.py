@@ -9,6 +9,7 @@ the tape-free evaluate of that call.  Prints one JSON line per side and writes p
         [--flow-score [--flow-score-structure circles|bands|free] [--flow-max-norm M]]
     python scripts/train_bench.py [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K] [--side trainer]
     python scripts/train_bench.py --optim-cost [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K]
+    python scripts/train_bench.py --data textures [--texture-layers 1|2] [--steps 5] [--warmup 2]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
 side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
@@ -25,6 +26,9 @@ under the pairing and reference asked for, beside the energy-mode legs: their di
 --micro-batches K times step(micro_batches=K) of the same 16 sequences on a handle of batch 16 / K.  --optim-cost times three trainers,
 alternated round by round in one process: neutral controls, the controls given (none given: clip_norm at half the first gradient's norm
 and weight_decay 0.01) and micro-batches (K, at least 2); one JSON line each with the spread over the rounds.
+--data textures (the default, rings, is every run above) times the device frame source train.MovingTextures at this shape: one
+batch(k, 16) with one and with two layers (its host part, describe, also alone), the host drifting() call of examples/train_prednet.py
+it replaces, and the trainer step fed by batch() of --texture-layers; one JSON line each.
 """
 import argparse
 import json
@@ -155,6 +159,44 @@ def run_optim_cost(steps, warmup, rounds=6, clip_norm=None, weight_decay=0.0, sk
     for t, _ in legs.values():
         t.close()
     return out
+
+
+def run_data(steps, warmup, layers=1, rounds=6):
+    """ms per MovingTextures.batch(k, B) with one and two layers, per describe(k, B) alone, per host drifting() call, and per trainer
+    step on batch() of `layers`; every leg a median over the rounds with its spread"""
+    import torch
+    from evolutionary_illusion_generator_amd import weights
+    from evolutionary_illusion_generator_amd.train import MovingTextures, PredNetTrainer
+    from examples.train_prednet import drifting
+    src = {L: MovingTextures(W, H, CH[0], T, layers=L) for L in (1, 2)}
+    tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T)
+    count = [0]
+
+    def k():
+        count[0] += 1
+        return count[0]
+    legs = {"batch_1_layer": lambda: src[1].batch(k(), B), "batch_2_layers": lambda: src[2].batch(k(), B), "describe_1_layer": lambda: src[1].describe(k(), B),
+            "describe_2_layers": lambda: src[2].describe(k(), B), "drifting_host": lambda: drifting(k(), B, T, CH[0], H, W),
+            "step_on_batch": lambda: tr.step(src[layers].batch(k(), B)), "step_alone": None}
+    still = src[layers].batch(0, B)
+    legs["step_alone"] = lambda: tr.step(still)
+    ms = {name: [] for name in legs}
+    for call in legs.values():
+        for _ in range(warmup):
+            call()
+    for _ in range(rounds):
+        for name, call in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                call()
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) * 1e3 / steps)
+    tr.close()
+    for s in src.values():
+        s.close()
+    return [dict(side=name, call_ms=float(np.median(v)), call_ms_min=min(v), call_ms_max=max(v), rounds=rounds, **(dict(layers=layers) if name.startswith("step") else {}))
+            for name, v in ms.items()]
 
 
 def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None, members=None, optim=(None, 0.0, False), micro_batches=1):
@@ -308,6 +350,8 @@ def main():
     ap.add_argument("--skip-nonfinite", action="store_true", help="the trainer's skip_nonfinite")
     ap.add_argument("--micro-batches", type=int, default=1, help="step(micro_batches=K) on a handle of batch 16 / K")
     ap.add_argument("--optim-cost", action="store_true", help="time step() plain, under the controls and in micro-batches, alternated, and exit")
+    ap.add_argument("--data", default="rings", choices=["rings", "textures"], help="textures: time the device frame source train.MovingTextures and the step it feeds, and exit")
+    ap.add_argument("--texture-layers", type=int, default=1, choices=[1, 2], help="--data textures: the layers of the batches the timed step reads")
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
     a = ap.parse_args()
@@ -320,6 +364,10 @@ def main():
         ap.error(str(e))
     if a.side == "torch":
         print(json.dumps(run_torch(a.steps, a.warmup)))
+        return
+    if a.data == "textures":
+        for r in run_data(a.steps, a.warmup, a.texture_layers):
+            print(json.dumps(r), flush=True)
         return
     if a.frame_grads:
         for r in run_frame_grads(a.steps, a.warmup):
