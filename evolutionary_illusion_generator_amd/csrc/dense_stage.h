@@ -14,16 +14,35 @@ constexpr int DENSE_PART = 16 * 5; // doubles of one sample's reduction partials
 
 // The workspace of a handle, one batch each: planes [3][B H W] (Ix, Iy, It), u [B][2][H W], for Free theta, L [B][H W] and the member
 // flags [B][H W]; the records [B][DENSE_REC] and the partials [B][DENSE_PART]
+// pyr: the pyramid of the iterated solve (eigen_dense_solve), one block of pyr_doubles(max_batch, H, W) doubles made by the first call that
+// needs it: per level l the gray planes I0_l, I1_l [B][H_l][W_l] and, for l >= 1, the level's field [B][2][H_l][W_l].
 struct DenseWork {
-    double *planes = nullptr, *u = nullptr, *theta = nullptr, *L = nullptr, *rec = nullptr, *part = nullptr;
+    double *planes = nullptr, *u = nullptr, *theta = nullptr, *L = nullptr, *rec = nullptr, *part = nullptr, *pyr = nullptr;
     uint8_t* flag = nullptr;
 };
 
-// The settings against an H x W image, before anything is launched: the trainer's own rules in the trainer's own words (eigen_last_error).
-int dense_check(const eigen_dense_settings* s, int device, int H, int W, const uint8_t* d_mask);
+constexpr int DENSE_MAX_LEVELS = 6, DENSE_MAX_ITERS = 32, DENSE_MIN_COARSE = 4;
+
+// The solve of one call.  iterated: the launches of dense_pyr_kernels.h; false (levels = iters = 1): today's prepare and solve kernels.
+struct DenseSolve {
+    int levels = 1, iters = 1;
+    bool iterated = false;
+};
+
+// doubles of the pyramid of B images of H x W at DENSE_MAX_LEVELS levels: four planes per pixel of a level
+inline long long pyr_doubles(long long B, int H, int W)
+{
+    long long total = 0;
+    for (int l = 0; l < DENSE_MAX_LEVELS; ++l, H = (H + 1) / 2, W = (W + 1) / 2) total += 4 * B * H * W;
+    return total;
+}
+
+// The settings and the solve (null: one level, one iteration) against an H x W image, before anything is launched: the trainer's own
+// rules in the trainer's own words (eigen_last_error).  force_iterated: levels = iters = 1 goes through the iteration kernel too.
+int dense_check(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int H, int W, const uint8_t* d_mask, DenseSolve& out);
 
 // The launches of the stage on checked settings: the records of the B samples into w.rec, the field into d_flow (null: w.u)
-void dense_launch(const eigen_dense_settings* s, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1, long long stride1, int B,
-                  const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st);
+void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1,
+                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st);
 
 }  // namespace eigd

@@ -132,6 +132,7 @@ struct eigen_engine {
     float* d_zeros = nullptr;  // DMA source for zero fill (conv_mfma.h)
     eigd::DenseWork dense;     // the dense fitness's workspace (eigen_dense_score): allocated by the first dense call, all of it or none
     bool have_dense = false;
+    bool dense_force_iter = false;  // eigen_debug_dense_solve: one level, one iteration goes through the iteration kernel too
     // Farneback dense flow (cfg.flow_method == EIGEN_FLOW_FARNEBACK): allocated on first use
     float *fb_I = nullptr, *fb_R0 = nullptr, *fb_R1 = nullptr, *fb_M = nullptr, *fb_V = nullptr, *fb_flow[2] = {nullptr, nullptr};
     DevBuf<float> raw4;   // partial chains of the unpooled source, [B][4 classes][n_nblk*NB][H/2][W/2], reused by all layers
@@ -447,7 +448,7 @@ int eigen_destroy(eigen_engine* e)
                     e->d_ncorners, e->d_counts, e->d_fitness, e->d_zeros,
                     e->fb_I, e->fb_R0, e->fb_R1, e->fb_M, e->fb_V, e->fb_flow[0], e->fb_flow[1]};
     for (void* p : misc) if (p) (void)hipFree(p);
-    void* dense[] = {e->dense.planes, e->dense.u, e->dense.theta, e->dense.L, e->dense.rec, e->dense.part, e->dense.flag};
+    void* dense[] = {e->dense.planes, e->dense.u, e->dense.theta, e->dense.L, e->dense.rec, e->dense.part, e->dense.flag, e->dense.pyr};
     for (void* p : dense) if (p) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
         for (int l = 0; l < FLOW_MAX_LEVELS; ++l) if (e->d_gray[i][l]) (void)hipFree(e->d_gray[i][l]);
@@ -1146,22 +1147,44 @@ static int dense_workspace(eigen_engine* e)
     return EIGEN_OK;
 }
 
+// The pyramid of the iterated solve, made by the first call that asks for one: one block, so all of it or none
+static int dense_pyramid(eigen_engine* e)
+{
+    if (e->dense.pyr) return EIGEN_OK;
+    const size_t bytes = (size_t)eigd::pyr_doubles(e->B, e->H, e->W) * 8;
+    void* p = nullptr;
+    const hipError_t err = hipMalloc(&p, bytes);
+    if (err != hipSuccess) return fail(EIGEN_ERR_HIP, "hipMalloc(%zu) for the dense fitness's pyramid: %s", bytes, hipGetErrorString(err));
+    e->dense.pyr = (double*)p;
+    return EIGEN_OK;
+}
+
+// The one record behind the plain dense entries and their _iter forms: the settings, the mask and the checked solve of a call
+struct DenseCall {
+    const eigen_dense_settings* settings = nullptr;
+    const uint8_t* d_mask = nullptr;
+    eigd::DenseSolve solve;
+};
+
 // What every dense entry refuses before anything is launched (the roll-out included), then the workspace
-static int dense_prepare(eigen_engine* e, const eigen_dense_settings* settings, const uint8_t* d_mask, int batch)
+static int dense_prepare(eigen_engine* e, DenseCall& c, const eigen_dense_settings* settings, const eigen_dense_solve* solve, const uint8_t* d_mask, int batch)
 {
     if (!settings) return fail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1 || batch > e->B) return fail(EIGEN_ERR_INVALID, "batch %d outside 1 .. max_batch %d", batch, e->B);
     HIPCHK(hipSetDevice(e->cfg.device));
-    const int rc = eigd::dense_check(settings, e->cfg.device, e->H, e->W, d_mask);
+    c.settings = settings; c.d_mask = d_mask;
+    int rc = eigd::dense_check(settings, solve, e->dense_force_iter, e->cfg.device, e->H, e->W, d_mask, c.solve);
     if (rc) return rc;
-    return dense_workspace(e);
+    rc = dense_workspace(e);
+    if (rc) return rc;
+    return c.solve.iterated ? dense_pyramid(e) : EIGEN_OK;
 }
 
-// The stage on prepared settings, and its host outputs: S_b alone comes back where the records are not asked for
-static int dense_run(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int batch,
-                     const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, hipStream_t st, bool sync)
+// The stage on a prepared call, and its host outputs: S_b alone comes back where the records are not asked for
+static int dense_run(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int batch, const DenseCall& c, double* h_fitness,
+                     double* h_stats, double* d_flow, hipStream_t st, bool sync)
 {
-    eigd::dense_launch(settings, e->C0, e->H, e->W, d_img0, (long long)stride0, d_img1, (long long)stride1, batch, d_mask, e->dense, d_flow, st);
+    eigd::dense_launch(c.settings, c.solve, e->C0, e->H, e->W, d_img0, (long long)stride0, d_img1, (long long)stride1, batch, c.d_mask, e->dense, d_flow, st);
     HIPCHK(hipGetLastError());
     const size_t rec = eigd::DENSE_REC * sizeof(double);
     if (h_stats) HIPCHK(hipMemcpyAsync(h_stats, e->dense.rec, rec * batch, hipMemcpyDeviceToHost, st));
@@ -1174,21 +1197,28 @@ static int dense_run(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, co
     return EIGEN_OK;
 }
 
-int eigen_dense_score(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
-                      const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, void* stream)
+int eigen_dense_score_iter(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
+                           const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, void* stream,
+                           const eigen_dense_solve* solve)
 {
     if (!e || !d_img0 || !d_img1 || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
     const int64_t per = (int64_t)e->C0 * e->H * e->W;
     if (stride0 < per || stride1 < per) return fail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", (long long)per);
-    const int rc = dense_prepare(e, settings, d_mask, batch);
+    DenseCall c;
+    const int rc = dense_prepare(e, c, settings, solve, d_mask, batch);
     if (rc) return rc;
-    return dense_run(e, d_img0, stride0, d_img1, stride1, batch, settings, d_mask, h_fitness, h_stats, d_flow, (hipStream_t)stream, true);
+    return dense_run(e, d_img0, stride0, d_img1, stride1, batch, c, h_fitness, h_stats, d_flow, (hipStream_t)stream, true);
+}
+
+int eigen_dense_score(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
+                      const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, void* stream)
+{
+    return eigen_dense_score_iter(e, d_img0, stride0, d_img1, stride1, batch, settings, d_mask, h_fitness, h_stats, d_flow, stream, nullptr);
 }
 
 // dense != nullptr: the dense stage (already prepared) in place of flow and score; h_stats is its records
 static int eval_images_impl(eigen_engine* e, const uint8_t* d_images, int batch, int structure, int pairing, double* h_fitness,
-                            float* h_vectors, int32_t* h_counts, hipStream_t st, bool rendered, const eigen_dense_settings* dense = nullptr,
-                            const uint8_t* d_mask = nullptr, double* h_stats = nullptr)
+                            float* h_vectors, int32_t* h_counts, hipStream_t st, bool rendered, const DenseCall* dense = nullptr, double* h_stats = nullptr)
 {
     const size_t HW = (size_t)e->H * e->W, img_bytes = (size_t)e->C0 * HW;
     const int nr = e->cfg.n_repeat;
@@ -1204,8 +1234,8 @@ static int eval_images_impl(eigen_engine* e, const uint8_t* d_images, int batch,
     const int n_out = n_steps - first;
     if (dense) {
         const int64_t fs = (int64_t)(n_out * img_bytes);
-        if (pairing == EIGEN_PAIR_POPULATION) rc = dense_run(e, e->d_frames, fs, e->d_frames + img_bytes, fs, batch, dense, d_mask, h_fitness, h_stats, nullptr, st, false);
-        else rc = dense_run(e, d_images, (int64_t)img_bytes, e->d_frames, fs, batch, dense, d_mask, h_fitness, h_stats, nullptr, st, false);
+        if (pairing == EIGEN_PAIR_POPULATION) rc = dense_run(e, e->d_frames, fs, e->d_frames + img_bytes, fs, batch, *dense, h_fitness, h_stats, nullptr, st, false);
+        else rc = dense_run(e, d_images, (int64_t)img_bytes, e->d_frames, fs, batch, *dense, h_fitness, h_stats, nullptr, st, false);
         if (rc) return rc;
         HIPCHK(hipEventRecord(e->ev[3], st));
         HIPCHK(hipEventRecord(e->ev[4], st));
@@ -1278,30 +1308,56 @@ static int dense_call_check(const eigen_engine* e, int structure, int pairing, c
     return EIGEN_OK;
 }
 
-int eigen_eval_population_dense(eigen_engine* e, const eigen_genome_batch* g, int32_t structure, int32_t bg, int32_t gradient, int32_t pairing,
-                                const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream)
+int eigen_eval_population_dense_iter(eigen_engine* e, const eigen_genome_batch* g, int32_t structure, int32_t bg, int32_t gradient, int32_t pairing,
+                                     const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
+                                     const eigen_dense_solve* solve)
 {
     if (!e || !g || !h_fitness || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
     int rc = dense_call_check(e, structure, pairing, settings);
     if (rc) return rc;
-    rc = dense_prepare(e, settings, d_mask, g->n_genomes);
+    DenseCall c;
+    rc = dense_prepare(e, c, settings, solve, d_mask, g->n_genomes);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipEventRecord(e->ev[0], st));
     rc = eigen_render_cppn(e, g, bg, gradient, e->d_images, st);
     if (rc) return rc;
-    return eval_images_impl(e, e->d_images, g->n_genomes, structure, pairing, h_fitness, nullptr, nullptr, st, true, settings, d_mask, h_stats);
+    return eval_images_impl(e, e->d_images, g->n_genomes, structure, pairing, h_fitness, nullptr, nullptr, st, true, &c, h_stats);
+}
+
+int eigen_eval_population_dense(eigen_engine* e, const eigen_genome_batch* g, int32_t structure, int32_t bg, int32_t gradient, int32_t pairing,
+                                const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream)
+{
+    return eigen_eval_population_dense_iter(e, g, structure, bg, gradient, pairing, settings, d_mask, h_fitness, h_stats, stream, nullptr);
+}
+
+int eigen_eval_images_dense_iter(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
+                                 const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
+                                 const eigen_dense_solve* solve)
+{
+    if (!e || !d_images || !h_fitness || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
+    int rc = dense_call_check(e, structure, pairing, settings);
+    if (rc) return rc;
+    DenseCall c;
+    rc = dense_prepare(e, c, settings, solve, d_mask, batch);
+    if (rc) return rc;
+    return eval_images_impl(e, d_images, batch, structure, pairing, h_fitness, nullptr, nullptr, (hipStream_t)stream, false, &c, h_stats);
 }
 
 int eigen_eval_images_dense(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
                             const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream)
 {
-    if (!e || !d_images || !h_fitness || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
-    int rc = dense_call_check(e, structure, pairing, settings);
-    if (rc) return rc;
-    rc = dense_prepare(e, settings, d_mask, batch);
-    if (rc) return rc;
-    return eval_images_impl(e, d_images, batch, structure, pairing, h_fitness, nullptr, nullptr, (hipStream_t)stream, false, settings, d_mask, h_stats);
+    return eigen_eval_images_dense_iter(e, d_images, batch, structure, pairing, settings, d_mask, h_fitness, h_stats, stream, nullptr);
+}
+
+// Test hook of the iterated solve: force >= 0 sets whether one level with one iteration goes through the iteration kernel too;
+// pyramid_bytes (may be null): the bytes of the pyramid the handle holds, 0 before the first iterated call
+int eigen_debug_dense_solve(eigen_engine* e, int32_t force, int64_t* pyramid_bytes)
+{
+    if (!e) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (force >= 0) e->dense_force_iter = force != 0;
+    if (pyramid_bytes) *pyramid_bytes = e->dense.pyr ? (int64_t)eigd::pyr_doubles(e->B, e->H, e->W) * 8 : 0;
+    return EIGEN_OK;
 }
 
 int eigen_get_timings(eigen_engine* e, double* h_ms6)

@@ -23,6 +23,7 @@
 #include "flow_corner_kernels.h"
 #include "optim_kernels.h"
 #include "dense_fitness_kernels.h"
+#include "dense_pyr_kernels.h"
 #include "dense_stage.h"
 
 using namespace eigt;
@@ -1667,6 +1668,23 @@ namespace eigd {
 static_assert(DENSE_REC == SCORE_REC && DENSE_REC == STRUCT_REC, "one record size for every score");
 static_assert(DENSE_PART >= SCORE_SLICES * SCORE_K && DENSE_PART >= STRUCT_SLICES * STRUCT_K, "the partials of every score fit");
 
+// The solve's own rules: 1 .. 6 levels, 1 .. 32 iterations, a coarsest level of at least 4 pixels on its shorter side
+static int dense_solve_check(const eigen_dense_solve* solve, bool force_iterated, int H, int W, DenseSolve& out)
+{
+    out = DenseSolve();
+    out.iterated = force_iterated;
+    if (!solve) return EIGEN_OK;
+    if (solve->levels < 1 || solve->levels > DENSE_MAX_LEVELS) return tfail(EIGEN_ERR_INVALID, "dense solve levels %d outside 1 .. %d", solve->levels, DENSE_MAX_LEVELS);
+    if (solve->iters < 1 || solve->iters > DENSE_MAX_ITERS) return tfail(EIGEN_ERR_INVALID, "dense solve iters %d outside 1 .. %d", solve->iters, DENSE_MAX_ITERS);
+    int h = H, w = W;
+    for (int l = 1; l < solve->levels; ++l) { h = (h + 1) / 2; w = (w + 1) / 2; }
+    if ((h < w ? h : w) < DENSE_MIN_COARSE)
+        return tfail(EIGEN_ERR_INVALID, "dense solve levels %d: the coarsest level of a %d x %d image is %d x %d, below %d pixels", solve->levels, W, H, w, h, DENSE_MIN_COARSE);
+    out.levels = solve->levels; out.iters = solve->iters;
+    out.iterated = force_iterated || solve->levels > 1 || solve->iters > 1;
+    return EIGEN_OK;
+}
+
 static int dense_spec(const eigen_dense_settings* s, int device, int H, int W, const uint8_t* d_mask, FlowSpec& f)
 {
     if (!s) return tfail(EIGEN_ERR_INVALID, "null argument");
@@ -1678,10 +1696,40 @@ static int dense_spec(const eigen_dense_settings* s, int device, int H, int W, c
     return check_flow_struct(s->sscore, nullptr, f);
 }
 
-int dense_check(const eigen_dense_settings* s, int device, int H, int W, const uint8_t* d_mask)
+int dense_check(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int H, int W, const uint8_t* d_mask, DenseSolve& out)
 {
     FlowSpec f;
+    const int rc = dense_solve_check(solve, force_iterated, H, W, out);   // ahead of the mask's read-back
+    if (rc) return rc;
     return dense_spec(s, device, H, W, d_mask, f);
+}
+
+// The iterated solve: the gray planes of level 0, the reduced levels, then one launch per level from the coarsest to the finest, whose
+// field goes into u.  w.pyr holds, level after level, I0_l, I1_l and (l >= 1) the level's field.
+static void dense_pyr_launch(const DenseSolve& solve, int r, double eps, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1, long long stride1,
+                             int B, const DenseWork& w, double* u, hipStream_t st)
+{
+    struct Level { int H, W; double *I0, *I1, *u; } lv[DENSE_MAX_LEVELS];
+    double* at = w.pyr;
+    for (int l = 0, h = H, ww = W; l < solve.levels; ++l, h = (h + 1) / 2, ww = (ww + 1) / 2) {
+        const long long n = (long long)B * h * ww;
+        lv[l] = Level{h, ww, at, at + n, l ? at + 2 * n : u};
+        at += 4 * n;
+    }
+    ew(st, tdense_gray_kernel, (long long)B * H * W, img0, stride0, img1, stride1, C, H, W, (long long)B * H * W, lv[0].I0, lv[0].I1);
+    for (int l = 1; l < solve.levels; ++l) {
+        const long long n = (long long)B * lv[l].H * lv[l].W;
+        ew(st, tdense_pyrdown_kernel, n, (const double*)lv[l - 1].I0, (const double*)lv[l - 1].I1, lv[l - 1].H, lv[l - 1].W, lv[l].H, lv[l].W, n, lv[l].I0, lv[l].I1);
+    }
+    const int lds = pyr_lds_doubles(r) * 8;
+    if (lds > 64 * 1024)   // radius 11 and above: more dynamic LDS than a launch gets without the attribute (set on the current device, as the CPPN launches do)
+        (void)hipFuncSetAttribute((const void*)tdense_iter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    for (int l = solve.levels - 1; l >= 0; --l) {
+        const bool top = l == solve.levels - 1;
+        const dim3 grid((unsigned)((lv[l].W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((lv[l].H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
+        hipLaunchKernelGGL(tdense_iter_kernel, grid, dim3(FLOW_T), (size_t)lds, st, (const double*)lv[l].I0, (const double*)lv[l].I1, lv[l].H, lv[l].W, r, eps,
+                           solve.iters, top ? (const double*)nullptr : (const double*)lv[l + 1].u, top ? 0 : lv[l + 1].H, top ? 0 : lv[l + 1].W, lv[l].u);
+    }
 }
 
 template <int STRUCT>
@@ -1699,8 +1747,8 @@ static void dense_struct_passes(const TFlowStruct& s, int H, int W, int B, const
     hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 2>), dim3(B), dim3(64), 0, st, (const double*)w.part, B, s, w.rec, (double*)nullptr);
 }
 
-void dense_launch(const eigen_dense_settings* s, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1, long long stride1, int B,
-                  const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st)
+void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1,
+                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st)
 {
     // the settings were checked by dense_check: the same fields give the same spec, without the mask's read-back
     FlowSpec f;
@@ -1709,9 +1757,13 @@ void dense_launch(const eigen_dense_settings* s, int C, int H, int W, const uint
     (void)check_flow_struct(s->sscore, nullptr, f);
     const long long n = (long long)B * H * W;
     double* u = d_flow ? d_flow : w.u;
-    ew(st, tdense_prep_kernel, n, img0, stride0, img1, stride1, C, H, W, n, w.planes);
-    const dim3 grid((unsigned)((W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-    hipLaunchKernelGGL(tdense_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)w.planes, n, H, W, f.r, f.eps, u);
+    if (solve.iterated) {
+        dense_pyr_launch(solve, f.r, f.eps, C, H, W, img0, stride0, img1, stride1, B, w, u, st);
+    } else {
+        ew(st, tdense_prep_kernel, n, img0, stride0, img1, stride1, C, H, W, n, w.planes);
+        const dim3 grid((unsigned)((W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
+        hipLaunchKernelGGL(tdense_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)w.planes, n, H, W, f.r, f.eps, u);
+    }
     if (f.by_score) {
         const dim3 sgrid(SCORE_SLICES, (unsigned)B);
         hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, (const double*)u, H, W, d_mask, 0ll, f.score, (const double*)w.rec, w.part);

@@ -29,7 +29,8 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_trainer_loss_grad_flow_structure", "eigen_trainer_debug_free_planes", "eigen_trainer_flow_members",
            "eigen_trainer_flow_term_members", "eigen_trainer_loss_grad_flow_members", "eigen_trainer_grad_norms", "eigen_trainer_adam_ex",
            "eigen_trainer_accumulate", "eigen_dense_score", "eigen_eval_population_dense", "eigen_eval_images_dense",
-           "eigen_render_moving_cppn"]
+           "eigen_render_moving_cppn", "eigen_dense_score_iter", "eigen_eval_population_dense_iter", "eigen_eval_images_dense_iter",
+           "eigen_debug_dense_solve"]
 
 
 class EigenConfig(ctypes.Structure):
@@ -60,6 +61,11 @@ class FlowSettingsC(ctypes.Structure):
 class DenseSettingsC(ctypes.Structure):
     """eigen_dense_settings: the window and exactly one of the two scores"""
     _fields_ = [("flow", FlowSettingsC), ("score", ctypes.c_void_p), ("sscore", ctypes.c_void_p)]
+
+
+class DenseSolveC(ctypes.Structure):
+    """eigen_dense_solve: the pyramid levels and the iterations per level of the dense stage's solve"""
+    _fields_ = [("levels", ctypes.c_int32), ("iters", ctypes.c_int32)]
 
 
 FLOW_METHODS = {"lk": 0, "farneback": 1}  # eigen_flow_method
@@ -362,11 +368,27 @@ class Engine:
         mask = dense.mask_on(torch, self.cfg.device, self.height, self.width)
         return cfg, (sc, mask), _ptr(mask)
 
+    @staticmethod
+    def _dense_solve(dense):
+        """the eigen_dense_solve of a `dense` argument (its ``levels`` and ``iters``, 1 where it has none), or None for the single step:
+        such a call goes to the plain entry, as it always did"""
+        levels, iters = int(getattr(dense, "levels", 1)), int(getattr(dense, "iters", 1))
+        return None if (levels, iters) == (1, 1) else DenseSolveC(levels, iters)
+
+    def debug_dense_solve(self, force=None):
+        """Test hook (eigen_debug_dense_solve): force True / False sets whether the single step goes through the iteration kernel too.
+        -> the bytes of the pyramid this handle holds, 0 before its first iterated call"""
+        n = ctypes.c_int64(-1)
+        _check(self.lib.eigen_debug_dense_solve(self._h, ctypes.c_int32(-1 if force is None else int(bool(force))), ctypes.byref(n)))
+        return int(n.value)
+
     def dense_score(self, d_img0, stride0, d_img1, stride1, batch, dense, stats=False, flow=False, stream=None):
         """The dense stage alone on two batches of uint8 device images (eigen_dense_score): image b of either at its pointer + b * its
         stride (bytes).  -> the float64 [batch] fitness, S_b of every sample; stats=True appends the float64 [batch, 10] records,
-        flow=True the field u, float64 [batch, 2, H, W] (numpy).  The records are also left in ``last_dense_stats``."""
+        flow=True the field u, float64 [batch, 2, H, W] (numpy).  The records are also left in ``last_dense_stats``.  A `dense` with
+        ``levels`` or ``iters`` above 1 runs the pyramidal, iterated solve (eigen_dense_score_iter)."""
         cfg, keep, d_mask = self._dense_args(dense)
+        solve = self._dense_solve(dense)
         batch = int(batch)
         fit, rec = np.zeros(max(batch, 0), np.float64), np.zeros((max(batch, 0), DENSE_REC), np.float64)
         u = None
@@ -379,8 +401,9 @@ class Engine:
                 have = self._buffer_bytes(buf)
                 if have is not None and int(stride) >= per and have < (batch - 1) * int(stride) + per:
                     raise ValueError("%s buffer holds %d bytes, %d are needed" % (what, have, (batch - 1) * int(stride) + per))
-        _check(self.lib.eigen_dense_score(self._h, _ptr(d_img0), ctypes.c_int64(int(stride0)), _ptr(d_img1), ctypes.c_int64(int(stride1)), ctypes.c_int32(batch),
-                                          ctypes.byref(cfg), d_mask, _ptr(fit), _ptr(rec), _ptr(u), _stream_arg(stream)))
+        args = (self._h, _ptr(d_img0), ctypes.c_int64(int(stride0)), _ptr(d_img1), ctypes.c_int64(int(stride1)), ctypes.c_int32(batch), ctypes.byref(cfg), d_mask,
+                _ptr(fit), _ptr(rec), _ptr(u), _stream_arg(stream))
+        _check(self.lib.eigen_dense_score(*args) if solve is None else self.lib.eigen_dense_score_iter(*args, ctypes.byref(solve)))
         self.last_dense_stats = rec
         out = (fit,) + ((rec,) if stats else ()) + ((u[:batch].cpu().numpy(),) if flow else ())
         return out[0] if len(out) == 1 else out
@@ -393,8 +416,10 @@ class Engine:
         if dense is not None:
             cfg, keep, d_mask = self._dense_args(dense)
             rec = np.zeros((gb.n_genomes, DENSE_REC), np.float64)
-            _check(self.lib.eigen_eval_population_dense(self._h, ctypes.byref(s), ctypes.c_int32(int(structure)), ctypes.c_int32(bg), ctypes.c_int32(gradient),
-                                                        ctypes.c_int32(pairing), ctypes.byref(cfg), d_mask, _ptr(fit), _ptr(rec), _stream_arg(stream)))
+            solve = self._dense_solve(dense)
+            args = (self._h, ctypes.byref(s), ctypes.c_int32(int(structure)), ctypes.c_int32(bg), ctypes.c_int32(gradient), ctypes.c_int32(pairing), ctypes.byref(cfg),
+                    d_mask, _ptr(fit), _ptr(rec), _stream_arg(stream))
+            _check(self.lib.eigen_eval_population_dense(*args) if solve is None else self.lib.eigen_eval_population_dense_iter(*args, ctypes.byref(solve)))
             self.last_dense_stats = rec
             return fit
         _check(self.lib.eigen_eval_population(self._h, ctypes.byref(s), ctypes.c_int32(int(structure)), ctypes.c_int32(bg),
@@ -408,8 +433,10 @@ class Engine:
         if dense is not None:
             cfg, keep, d_mask = self._dense_args(dense)
             fit, rec = np.zeros(max(int(batch), 0), np.float64), np.zeros((max(int(batch), 0), DENSE_REC), np.float64)
-            _check(self.lib.eigen_eval_images_dense(self._h, _ptr(d_images), ctypes.c_int32(batch), ctypes.c_int32(int(structure)), ctypes.c_int32(pairing),
-                                                    ctypes.byref(cfg), d_mask, _ptr(fit), _ptr(rec), _stream_arg(stream)))
+            solve = self._dense_solve(dense)
+            args = (self._h, _ptr(d_images), ctypes.c_int32(batch), ctypes.c_int32(int(structure)), ctypes.c_int32(pairing), ctypes.byref(cfg), d_mask, _ptr(fit),
+                    _ptr(rec), _stream_arg(stream))
+            _check(self.lib.eigen_eval_images_dense(*args) if solve is None else self.lib.eigen_eval_images_dense_iter(*args, ctypes.byref(solve)))
             self.last_dense_stats = rec
             return fit, [np.zeros((0, 4), np.float32) for _ in range(int(batch))]
         fit = np.zeros(batch, dtype=np.float64)

@@ -317,25 +317,46 @@ class DenseFitness:
     ``refine_genomes(objective="flow", flow=PredictionFlow(radius, eps).scored(score))`` climbs.
     score: a ``train.FlowScore`` (Circles, CirclesFree), ``train.BandsScore`` or ``train.FreeScore``; None: the structure's defaults,
     resolved by ``for_structure`` when the fitness is asked for a structure.  mask: [H, W], zero = the pixel is no member (None: all).
+    levels, iters: the solve (include/eigen_engine.h eigen_dense_solve).  1 and 1, the default, is the single regularised step at one
+    resolution.  Anything else is Lucas-Kanade over `levels` pyramid levels (each half the size of the one below, 5-tap reduced) with
+    `iters` iterations per level, every pixel re-sampling its whole window at its own displacement: the single step shrinks motions
+    of a pixel and more toward zero, this solve follows them.  It costs about levels-and-iters times the window per pixel and has
+    no gradient.
     ValueError: the rules of ``train.FlowObjective`` for radius, eps and the mask (a per-sample mask is refused: the population has
-    one grid), and a score that is none of the three classes."""
+    one grid), a score that is none of the three classes, levels outside 1 .. 6, iters outside 1 .. 32, and (``solve_on``, once the
+    image is known) a coarsest level below 4 pixels on its shorter side."""
 
-    def __init__(self, score=None, radius=7, eps=1e-2, mask=None):
+    MAX_LEVELS, MAX_ITERS, MIN_COARSE = 6, 32, 4
+
+    def __init__(self, score=None, radius=7, eps=1e-2, mask=None, levels=1, iters=1):
         from . import train
         flow = train.FlowObjective(radius, eps, mask=mask)     # its rules, its words
         if flow.per_sample:
             raise ValueError("mask must be [H, W], shared by the population; got shape %s" % (flow.mask.shape,))
         if score is not None and not isinstance(score, train.FLOW_SCORES):
             raise ValueError("score must be a FlowScore, a BandsScore, a FreeScore or None, got %r" % (score,))
+        for name, v, top in (("levels", levels, self.MAX_LEVELS), ("iters", iters, self.MAX_ITERS)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= top:
+                raise ValueError("%s %r outside 1 .. %d" % (name, v, top))
         self.score, self.radius, self.eps, self.mask = score, flow.radius, flow.eps, flow.mask
+        self.levels, self.iters = int(levels), int(iters)
         self._dev = {}        # the mask on every device it was asked for, uploaded once
         self._resolved = {}   # without a score of its own: the object of every structure's class, made once
 
     @classmethod
-    def for_structure(cls, structure, radius=7, eps=1e-2, mask=None, **kw):
+    def for_structure(cls, structure, radius=7, eps=1e-2, mask=None, levels=1, iters=1, **kw):
         """The dense fitness of a structure: ``train.structure_score(structure, **kw)`` as the score"""
         from . import train
-        return cls(train.structure_score(structure, **kw), radius=radius, eps=eps, mask=mask)
+        return cls(train.structure_score(structure, **kw), radius=radius, eps=eps, mask=mask, levels=levels, iters=iters)
+
+    def solve_on(self, w, h):
+        """(levels, iters) against a w x h image.  ValueError: the coarsest level would be below 4 pixels on its shorter side."""
+        cw, ch = int(w), int(h)
+        for _ in range(self.levels - 1):
+            cw, ch = (cw + 1) // 2, (ch + 1) // 2
+        if min(cw, ch) < self.MIN_COARSE:
+            raise ValueError("levels %d: the coarsest level of a %d x %d image is %d x %d, below %d pixels" % (self.levels, w, h, cw, ch, self.MIN_COARSE))
+        return self.levels, self.iters
 
     def resolved(self, structure):
         """self with a score that belongs to `structure` (the structure's defaults where it has none).  ValueError: a score of another
@@ -344,7 +365,7 @@ class DenseFitness:
         want = type(train.structure_score(structure))
         if self.score is None:      # made once per class; it shares this one's uploaded mask
             if want not in self._resolved:
-                d = DenseFitness(want(), self.radius, self.eps, self.mask)
+                d = DenseFitness(want(), self.radius, self.eps, self.mask, self.levels, self.iters)
                 d._dev = self._dev
                 self._resolved[want] = d
             return self._resolved[want]
@@ -353,7 +374,10 @@ class DenseFitness:
         return self
 
     def flow_objective(self, pairing="prediction"):
-        """The ``train.FlowObjective`` / ``PredictionFlow`` that refines by this very score (``refine_genomes(flow=...)``)"""
+        """The ``train.FlowObjective`` / ``PredictionFlow`` that refines by this score (``refine_genomes(flow=...)``).  It is always the
+        single-step objective: with levels or iters above 1 refinement climbs the first iteration at level 0 of the same solve, the
+        score of the field of one regularised step, not the iterated field the fitness scores.  A gradient through the iteration does
+        not exist."""
         from . import train
         if self.score is None:
             raise ValueError("the DenseFitness has no score yet: resolved(structure) gives it the structure's")
@@ -403,6 +427,8 @@ def evaluate_batch(structure, gb, n_in, model_name, w, h, channels, c_dim=3, gra
     """Fitness (float64 array) of an already flattened genome batch on the local GPU, in chunks of max_batch.  score: "corners",
     "dense", a ``DenseFitness``, or None: the module switch FITNESS_SCORE."""
     dense = resolve_score(score, structure)
+    if dense is not None:
+        dense.solve_on(w, h)       # ahead of the engine, as a ValueError
     channels = [int(c) for c in channels]
     if channels[0] != c_dim:
         raise ValueError("channels[0]=%d but c_dim=%d: PredNet's input channels are the image channels" % (channels[0], c_dim))

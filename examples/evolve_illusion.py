@@ -15,6 +15,8 @@
     python examples/evolve_illusion.py -g 5 --fitness dense [--flow-radius R] [--flow-eps E] [--flow-score [--flow-max-norm M]]   (selection by the dense
         motion score of --structure, fitness.DenseFitness, in place of the corner tracks; with --refine K --objective flow --flow-score
         --flow-pairing prediction selection and refinement use one score with the same settings)
+    python examples/evolve_illusion.py -g 5 --fitness dense --dense-levels 3 --dense-iters 3   (the dense score on the field of a pyramidal, iterated
+        Lucas-Kanade solve, which follows motions of a pixel and more where the single step shrinks them; refinement still climbs the single step)
 """
 import argparse
 import os
@@ -45,6 +47,8 @@ def main():
     ap.add_argument("--objective", default="mse", choices=["mse", "error", "flow"], help="what --refine climbs")
     ap.add_argument("--fitness", default="corners", choices=["corners", "dense"],
                     help="what selects: the reference's score of the tracked corners, or the dense motion score of --structure (fitness.DenseFitness)")
+    ap.add_argument("--dense-levels", type=int, default=1, help="--fitness dense: pyramid levels of the solve (1 .. 6; 1 with --dense-iters 1 is the single step)")
+    ap.add_argument("--dense-iters", type=int, default=1, help="--fitness dense: iterations per pyramid level (1 .. 32)")
     add_flow_arguments(ap, direction=dict(choices=["tangent", "radial", "horizontal", "vertical"], help="objective flow: the field (default: the mean square)"),
                        radius=dict(help=None), eps=dict(help=None),
                        reference=dict(choices=["constant", "moving"], help="objective flow: moving also follows how the term moves with the still as its reference frame"),
@@ -64,6 +68,10 @@ def main():
     except ValueError as e:
         raise SystemExit("--fitness dense: %s" % e)
     if dense is not None:
+        try:
+            dense.solve_on(w, h)
+        except ValueError as e:
+            raise SystemExit("--fitness dense: %s" % e)
         fitness.FITNESS_SCORE = dense    # get_fitnesses_neat keeps the reference's signature: the module switch carries the choice
 
     def eval_genomes(genomes, config):

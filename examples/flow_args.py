@@ -77,9 +77,10 @@ def flow_of(a, w, h, mask=None):
 def dense_fitness_of(a, structure, mask=None):
     """the fitness.DenseFitness of the command line under --fitness dense (None under corners): the window of --flow-radius and --flow-eps,
     the score of --flow-score where it is given (it must be `structure`'s: ValueError) and the structure's defaults otherwise, the
-    pixels of `mask`.  With --refine --objective flow --flow-score --flow-pairing prediction selection and refinement then use one score
+    pixels of `mask`, the solve of --dense-levels and --dense-iters.  With --refine --objective flow --flow-score --flow-pairing prediction selection and refinement then use one score
     with the same settings."""
     from evolutionary_illusion_generator_amd import fitness
     if getattr(a, "fitness", "corners") != "dense":
         return None
-    return fitness.DenseFitness(score_of(a), radius=a.flow_radius, eps=a.flow_eps, mask=mask).resolved(structure)
+    return fitness.DenseFitness(score_of(a), radius=a.flow_radius, eps=a.flow_eps, mask=mask, levels=getattr(a, "dense_levels", 1),
+                                iters=getattr(a, "dense_iters", 1)).resolved(structure)

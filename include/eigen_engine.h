@@ -850,6 +850,53 @@ int eigen_eval_population_dense(eigen_engine* e, const eigen_genome_batch* h_gen
 int eigen_eval_images_dense(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
                             const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------- dense fitness: the solve
+ * The opt-in solve of the dense stage ("The pyramidal, iterated solve"; csrc/dense_pyr_kernels.h): Lucas-Kanade
+ * over `levels` pyramid levels with `iters` iterations per level in the per-pixel window form, in place of the single regularised
+ * step.  Score only: no gradient, no trainer entry.  Float64, one IEEE operation per operation written, fixed orders.
+ *   gray planes  I0, I1 of level 0 are what the single step reads: the gray of (float)byte / 255.0f, widened.
+ *   pyramid      level l + 1 has size ((W_l + 1) / 2, (H_l + 1) / 2).  5 taps (1, 4, 6, 4, 1) / 16 centred on source index 2 i, reflect-101
+ *                borders, along x first (at every source row), then along y; one tap set is (((a + e) + 4.0 (b + d)) + 6.0 c) / 16.0.
+ *                Both images are reduced.
+ *   per level    from the coarsest to the finest: Ix, Iy the normalised Scharr pair of the level's I0, indices clamped; Gxx, Gxy, Gyy the
+ *                truncated window sums in the single step's order (rows first, then columns, offsets ascending, each sum started from
+ *                its first term); a = Gxx + eps, c = Gyy + eps, b = Gxy, det = a c - b b.  They do not change over the iterations.
+ *   start        the coarsest level starts from the zero field, held as -0.0 so that the first step added to it is the step itself bit
+ *                for bit (a step of -0.0 included); otherwise u_l(y, x) = 2.0 u_{l+1}(y >> 1, x >> 1), both components.
+ *   iteration    at pixel p with its own u = (ux, uy), for every q of the truncated window of p: d(q) = S(I1, qx + ux, qy + uy) - I0(q);
+ *                bx = sum Ix(q) d(q), by = sum Iy(q) d(q), per window row ascending in x from its first term, then the rows ascending
+ *                in y from the first row; ux += -((c bx - b by) / det), uy += -((a by - b bx) / det).
+ *   sampler S    x = x > 0 ? x : 0, then x = x < W - 1 ? x : W - 1, likewise y; x0 = floor(x), x1 = min(x0 + 1, W - 1), fx = x - x0,
+ *                likewise y; top = v00 + fx (v01 - v00), bot = v10 + fx (v11 - v10), S = top + fy (bot - top).  At integer coordinates S
+ *                is the pixel exactly, so levels = 1, iters = 1 through the iteration kernel is the single step's field bit for bit.
+ *   score        the field of level 0 after its last iteration goes into the unchanged moment, prepare, pair and final kernels: the
+ *                records and S_b keep their meaning, and a sample's result still does not depend on its batch.
+ * Accepted: levels 1 .. 6, iters 1 .. 32, and a coarsest level of at least 4 pixels on its shorter side; anything else is
+ * EIGEN_ERR_INVALID before any launch or allocation.  The pyramid (four float64 planes per pixel of every level, at max_batch) is
+ * allocated by the first iterated call on the handle, all of it or none, and freed with the handle; a handle that never asks
+ * allocates nothing more than before. */
+typedef struct {
+    int32_t levels;
+    int32_t iters;
+} eigen_dense_solve;
+
+/* The three dense entries with a solve.  solve NULL or {1, 1}: the call is the namesake's, launch for launch (the namesakes are these
+ * entries with NULL).  Errors: the namesake's, and EIGEN_ERR_INVALID for a solve outside the accepted values.  eigen_get_timings
+ * reports the stage as the namesakes do. */
+int eigen_dense_score_iter(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
+                           const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow,
+                           void* stream, const eigen_dense_solve* solve);
+int eigen_eval_population_dense_iter(eigen_engine* e, const eigen_genome_batch* h_genomes, int32_t structure, int32_t bg, int32_t gradient,
+                                     int32_t pairing, const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness,
+                                     double* h_stats, void* stream, const eigen_dense_solve* solve);
+int eigen_eval_images_dense_iter(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
+                                 const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
+                                 const eigen_dense_solve* solve);
+
+/* Test hook of the solve: force >= 0 sets whether levels = 1, iters = 1 (and a NULL solve) goes through the iteration kernel too, on
+ * this handle; pyramid_bytes (may be NULL) receives the bytes of the pyramid the handle holds, 0 before its first iterated call. */
+int eigen_debug_dense_solve(eigen_engine* e, int32_t force, int64_t* pyramid_bytes);
+
 #ifdef __cplusplus
 }
 #endif

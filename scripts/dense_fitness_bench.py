@@ -2,6 +2,7 @@
 """What the dense motion fitness costs on the population path, against the corner fitness of the same run.
 
     python scripts/dense_fitness_bench.py [--rounds 6] [--shapes headline,ref160] [--out profiles/dense_fitness_cost.txt]
+    python scripts/dense_fitness_bench.py --dense-levels 3 --dense-iters 3 --structures 0,1 --out OTHER.txt
 
 Per shape of bench.py (headline: 256 x 256 colour, pop 256; ref160: 160 x 120 colour, pop 50) and per structure,
 `fitness.population_fitness` is timed under score="corners" and score="dense" in alternation, one generation each per round, after
@@ -10,6 +11,10 @@ the device time of the stage that follows the roll-out (Lucas-Kanade + score, or
 engine's own HIP events.  A (shape, structure) whose dense generation takes longer than --slow seconds is timed for two rounds only, and
 the line says so.  For the headline genomes the agreement of the two fitnesses is recorded: Spearman's rank correlation (ties share
 their mean rank) and the share of genomes scoring exactly 0 under each.
+
+With --dense-levels or --dense-iters above 1 the comparison is another one: the dense fitness's single step ("corners" in the columns'
+place) against its pyramidal, iterated solve (fitness.DenseFitness(levels=L, iters=K), in "dense"'s place), alternated in the same
+way; the header line says so and the lines name the two.
 
 The output file has two parts: what this script measures, which a run replaces, and everything from the line NOTES_MARK on, which a run
 keeps as it finds it: the records of other commands of the same visit (the default path against the parent commit, the example), written by
@@ -59,13 +64,23 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--shapes", default="headline,ref160")
     ap.add_argument("--slow", type=float, default=4.0, help="a dense generation slower than this many seconds is timed for two rounds only")
+    ap.add_argument("--structures", default="0,1,2", help="0 Bands, 1 Circles, 2 Free")
+    ap.add_argument("--dense-levels", type=int, default=1, help="with --dense-iters: time the single step against this solve")
+    ap.add_argument("--dense-iters", type=int, default=1)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dense_fitness_cost.txt"))
     a = ap.parse_args()
     import torch
     import bench
     from evolutionary_illusion_generator_amd import fitness
-    lines = ["dense motion fitness against the corner fitness, %s, %d rounds, corners and dense alternated per round" % (torch.cuda.get_device_name(0), a.rounds),
-             "build %s" % bench.kernel_sources_sha(), ""]
+    solve = (a.dense_levels, a.dense_iters)
+    if solve == (1, 1):
+        first, second, scores = "corners", "dense", {"corners": "corners", "dense": "dense"}
+        head = "dense motion fitness against the corner fitness, %s, %d rounds, corners and dense alternated per round"
+    else:
+        first, second = "single", "%dx%d" % solve
+        scores = {"corners": fitness.DenseFitness(), "dense": fitness.DenseFitness(levels=solve[0], iters=solve[1])}
+        head = "dense motion fitness, the single step against " + "%d levels x %d iterations" % solve + ", %s, %d rounds, the two alternated per round"
+    lines = [head % (torch.cuda.get_device_name(0), a.rounds), "build %s" % bench.kernel_sources_sha(), ""]
 
     def say(s):
         print(s, flush=True)
@@ -78,11 +93,11 @@ def main():
         max_batch = min(pop, 256)
         eng = fitness.get_engine(wts, W, H, CHANNELS, max_batch=max_batch)
         say("%s: %dx%d, PredNet %s, pop %d, device batch %d" % (shape, W, H, ",".join(map(str, CHANNELS)), pop, max_batch))
-        for structure, name in STRUCTURES.items():
+        for structure, name in ((s, STRUCTURES[s]) for s in map(int, a.structures.split(","))):
             def generation(score):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                fit = fitness.population_fitness(structure, genomes, wts, cfg, W, H, CHANNELS, c_dim=C_DIM, gradient=1, max_batch=max_batch, score=score)
+                fit = fitness.population_fitness(structure, genomes, wts, cfg, W, H, CHANNELS, c_dim=C_DIM, gradient=1, max_batch=max_batch, score=scores[score])
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 t = eng.timings()
@@ -99,13 +114,14 @@ def main():
                     stage[s].append(stage_ms)
                     roll.append(roll_ms)
             fc, fd = warm["corners"][0], warm["dense"][0]
-            say("  %-7s corners %s evals/s, dense %s evals/s, dense / corners %.3f%s" % (
-                name, spread(rate["corners"]), spread(rate["dense"]), np.median(rate["dense"]) / np.median(rate["corners"]),
+            say("  %-7s %s %s evals/s, %s %s evals/s, %s / %s %.3f%s" % (
+                name, first, spread(rate["corners"]), second, spread(rate["dense"]), second, first, np.median(rate["dense"]) / np.median(rate["corners"]),
                 "" if rounds == a.rounds else "  [%d rounds: a dense generation takes %.1f s]" % (rounds, warm["dense"][1])))
-            say("          device ms per generation: roll-out %s; flow + score %s; dense stage %s = %.1f %% of the roll-out" % (
-                spread(roll), spread(stage["corners"]), spread(stage["dense"]), 100.0 * np.median(stage["dense"]) / np.median(roll)))
-            say("          agreement over the %d genomes: Spearman %.3f; scoring 0: corners %.1f %%, dense %.1f %%" % (
-                pop, spearman(fc, fd), 100.0 * float((fc == 0).mean()), 100.0 * float((fd == 0).mean())))
+            say("          device ms per generation: roll-out %s; %s %s; %s %s = %.1f %% of the roll-out" % (
+                spread(roll), "flow + score" if solve == (1, 1) else "dense stage, single step", spread(stage["corners"]),
+                "dense stage" if solve == (1, 1) else "dense stage, " + second, spread(stage["dense"]), 100.0 * np.median(stage["dense"]) / np.median(roll)))
+            say("          agreement over the %d genomes: Spearman %.3f; scoring 0: %s %.1f %%, %s %.1f %%" % (
+                pop, spearman(fc, fd), first, 100.0 * float((fc == 0).mean()), second, 100.0 * float((fd == 0).mean())))
         fitness.clear_engines()
         say("")
     kept = ""
