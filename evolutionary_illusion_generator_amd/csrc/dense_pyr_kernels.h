@@ -105,6 +105,9 @@ __device__ __forceinline__ double pyr_sample(const double* __restrict__ s1, int 
 //   truncated window, bx = sum Ix d, by = sum Iy d (per row ascending in x from its first term, then the rows ascending in y from the
 //   first row), ux += -((c bx - b by) / det), uy += -((a by - b bx) / det)
 // I0, I1 [B][H][W]; coarse [B][2][Hc][Wc] or null; flow [B][2][H][W].
+// flow_iter_kernels.h holds this kernel's twin, tfiter_fwd_kernel (the same staging and loop, statement for statement, plus the stores of
+// every iterate for the trainer's backward pass): a change here is a change there, and tests/test_gpu_flow_iter.py compares the two fields
+// bit for bit.
 __global__ void __launch_bounds__(FLOW_T) tdense_iter_kernel(const double* __restrict__ I0, const double* __restrict__ I1, int H, int W, int r, double eps, int iters,
                                                              const double* __restrict__ coarse, int Hc, int Wc, double* __restrict__ flow)
 {

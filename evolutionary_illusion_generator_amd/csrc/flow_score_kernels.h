@@ -150,6 +150,27 @@ __global__ void __launch_bounds__(64) tflow_score_final_kernel(const double* __r
     }
 }
 
+// g = d S_b / d u at a member o of a sample whose record R holds at least min_count members: the header's gradient.  tflow_score_q_kernel
+// folds it into q; the iterated solve's gradient (flow_iter_kernels.h) takes g itself.
+__device__ __forceinline__ void tflow_score_g(double ux, const TScorePoint& o, const double* __restrict__ R, const TFlowScore& s, double& gx, double& gy)
+{
+    const double N = R[0], m_rho = R[1], m_tau = R[2], m_a = R[3], m_n = R[4], Vr = R[5], Vt = R[6], Vn = R[7];
+    const double c_rho = -(((s.w_direction * (1.0 - Vr)) * (2.0 * (o.rho - m_rho))) / N);
+    const double c_tau = -(((s.w_direction * (1.0 - Vt)) * (2.0 * (o.tau - m_tau))) / N);
+    const double gmx = (c_rho * o.px) / o.dist - (c_tau * o.py) / o.dist;
+    const double gmy = (c_rho * o.py) / o.dist + (c_tau * o.px) / o.dist;
+    const double d = gmx * o.nx + gmy * o.ny;
+    gx = (gmx - d * o.nx) / o.nrm;
+    gy = (gmy - d * o.ny) / o.nrm;
+    const double A = m_a / s.max_norm;
+    const double F = 1.0 - (Vn < 1.0 ? Vn : 1.0);
+    const double sg = ux > 0.0 ? 1.0 : ux < 0.0 ? -1.0 : 0.0;
+    gx = gx + ((s.w_strength * F) * sg) / (N * s.max_norm);
+    const double c_n = Vn < 1.0 ? -(((s.w_strength * A) * (2.0 * (o.nrm - m_n))) / N) : 0.0;
+    gx = gx + c_n * o.nx;
+    gy = gy + c_n * o.ny;
+}
+
 // q of every pixel of one tile (blockIdx: tile x, tile y, sample).  Gxx, Gxy, Gyy are formed again in tflow_solve_kernel's order (rows
 // first, offsets ascending, each sum started from its first term), so a, b, c and det are the solve's bits; g is the header's gradient
 // from u and the sample's record.  q [2][n] replaces what the solve wrote there.
@@ -196,23 +217,12 @@ __global__ void __launch_bounds__(FLOW_T) tflow_score_q_kernel(const double* __r
     const long long p = (long long)y * W + x;
     const double ux = u[2 * base + p], uy = u[2 * base + HW + p];
     const double* R = rec + (long long)blockIdx.z * SCORE_REC;
-    const double N = R[0], m_rho = R[1], m_tau = R[2], m_a = R[3], m_n = R[4], Vr = R[5], Vt = R[6], Vn = R[7];
+    const double N = R[0];
     const TScorePoint o = tflow_score_point(ux, uy, x, y, H, W, !mask || mask[(long long)blockIdx.z * mask_bstride + p] != 0, s);
     double qx = 0.0, qy = 0.0;
     if (o.member && !(N < (double)s.min_count)) {
-        const double c_rho = -(((s.w_direction * (1.0 - Vr)) * (2.0 * (o.rho - m_rho))) / N);
-        const double c_tau = -(((s.w_direction * (1.0 - Vt)) * (2.0 * (o.tau - m_tau))) / N);
-        const double gmx = (c_rho * o.px) / o.dist - (c_tau * o.py) / o.dist;
-        const double gmy = (c_rho * o.py) / o.dist + (c_tau * o.px) / o.dist;
-        const double d = gmx * o.nx + gmy * o.ny;
-        double gx = (gmx - d * o.nx) / o.nrm, gy = (gmy - d * o.ny) / o.nrm;
-        const double A = m_a / s.max_norm;
-        const double F = 1.0 - (Vn < 1.0 ? Vn : 1.0);
-        const double sg = ux > 0.0 ? 1.0 : ux < 0.0 ? -1.0 : 0.0;
-        gx = gx + ((s.w_strength * F) * sg) / (N * s.max_norm);
-        const double c_n = Vn < 1.0 ? -(((s.w_strength * A) * (2.0 * (o.nrm - m_n))) / N) : 0.0;
-        gx = gx + c_n * o.nx;
-        gy = gy + c_n * o.ny;
+        double gx, gy;
+        tflow_score_g(ux, o, R, s, gx, gy);
         qx = (c * gx - b * gy) / det;
         qy = (a * gy - b * gx) / det;
     }

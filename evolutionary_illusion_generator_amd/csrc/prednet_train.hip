@@ -1,7 +1,8 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
 // the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for the flow objective
-// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h, flow_score_kernels.h, flow_struct_kernels.h and flow_corner_kernels.h, and for
+// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h, flow_score_kernels.h, flow_struct_kernels.h, flow_corner_kernels.h and (the
+// iterated solve and its gradient) flow_iter_kernels.h, and for
 // the optimiser controls (gradient norms, accumulation, clipping, weight decay) optim_kernels.h.
 #include <hip/hip_runtime.h>
 
@@ -25,10 +26,15 @@
 #include "dense_fitness_kernels.h"
 #include "dense_pyr_kernels.h"
 #include "dense_stage.h"
+#include "flow_iter_kernels.h"
 
 using namespace eigt;
 
 int eig_set_error(int code, const char* msg);  // eigen_engine.hip: eigen_last_error's text
+
+namespace eigd {
+static int dense_solve_check(const eigen_dense_solve* solve, bool force_iterated, int H, int W, DenseSolve& out);  // below, with the dense stage
+}
 
 namespace {
 
@@ -126,6 +132,12 @@ struct eigen_trainer {
     double *o_part = nullptr, *o_sumsq = nullptr, *o_norm = nullptr;
     float* acc = nullptr;
     int acc_count = 0;
+    // the iterated solve's (flow_iter_kernels.h): one block that holds the pyramid, the tape and the adjoint planes of it_levels levels at
+    // it_iters iterations (iter_plan), made by the first iterated call (iter_workspace); it_force: a {1, 1} solve takes that path too
+    double* it_ws = nullptr;
+    long long it_doubles = 0;
+    int it_levels = 0, it_iters = 0;
+    bool it_force = false;
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -445,6 +457,9 @@ struct FlowSpec {
     TFlowStruct sscore = {};
     // EIGEN_FLOW_MEMBERS_CORNERS: every term's members are the corners of its own reference (corner_stage), under the shared `mask`
     bool by_corners = false;
+    // eigen_dense_solve: the stage solves over `levels` pyramid levels with `iters` iterations each and differentiates that solve
+    bool iterated = false;
+    int levels = 1, iters = 1;
     int max_corners = 0, block_size = 0;
     double quality = 0.0, min_distance = 0.0;
     // what divides a term's scale in kappa: B N_m, or B in the score mode, whose value is a mean over the samples alone
@@ -538,6 +553,16 @@ int check_flow_on(int device, long long HW, const eigen_flow_settings* flow, con
 int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, int32_t allowed_flags, FlowSpec& f)
 {
     return check_flow_on(t->cfg.device, t->ly[0].HW, flow, d_dir, d_mask, allowed_flags, f);
+}
+
+// The solve of a flow call (null: the single step) against the handle's image, by eigen_dense_solve's own rules in their own words
+int check_solve(const eigen_trainer* t, const eigen_dense_solve* solve, FlowSpec& f)
+{
+    eigd::DenseSolve s;
+    const int rc = eigd::dense_solve_check(solve, t->it_force, t->ly[0].H, t->ly[0].W, s);
+    if (rc) return rc;
+    f.iterated = s.iterated; f.levels = s.levels; f.iters = s.iters;
+    return EIGEN_OK;
 }
 
 // The corner members' workspace, made by the first call that needs it and freed with the handle; the tape and every other use of the
@@ -659,8 +684,9 @@ struct FlowTerm {
 
 // The value and q of a structure score from the u the solve just wrote (flow_struct_kernels.h): two passes of moments, for Free the
 // prepare and the pair pass between them, then (want_q) the gradient g and q over what the solve left in f_q.
+// with_q false (the iterated solve, whose gradient takes g itself): g is left in f_g and q is not formed.
 template <int STRUCT>
-void struct_stage_of(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value, bool want_q)
+void struct_stage_of(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value, bool want_q, bool with_q)
 {
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
@@ -676,14 +702,184 @@ void struct_stage_of(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f,
     hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 2>), dim3(B), dim3(64), 0, st, (const double*)t->f_sspart, B, s, t->f_srec, d_value);
     if (!want_q) return;
     ew(st, tflow_struct_grad_kernel<STRUCT>, n, u, n, y.H, y.W, f.mask, f.mask_bstride, s, (const double*)t->f_srec, (const int*)t->f_rowS, (const int*)t->f_colS, t->f_g);
+    if (!with_q) return;
     const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
     hipLaunchKernelGGL(tflow_struct_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_g, n, y.H, y.W, f.r, f.eps, t->f_q);
 }
 
-void struct_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value, bool want_q)
+void struct_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value, bool want_q, bool with_q = true)
 {
-    if (f.sscore.structure == STRUCT_BANDS) struct_stage_of<STRUCT_BANDS>(t, st, B, f, u, d_value, want_q);
-    else struct_stage_of<STRUCT_FREE>(t, st, B, f, u, d_value, want_q);
+    if (f.sscore.structure == STRUCT_BANDS) struct_stage_of<STRUCT_BANDS>(t, st, B, f, u, d_value, want_q, with_q);
+    else struct_stage_of<STRUCT_FREE>(t, st, B, f, u, d_value, want_q, with_q);
+}
+
+// The value of the score mode from the u a solve wrote: two passes of moments into the samples' records
+void score_passes(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value)
+{
+    const TLayer& y = t->ly[0];
+    const dim3 sgrid(SCORE_SLICES, (unsigned)B);
+    hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_spart);
+    hipLaunchKernelGGL(tflow_score_final_kernel<1>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, (double*)nullptr);
+    hipLaunchKernelGGL(tflow_score_moment_kernel<2>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_spart);
+    hipLaunchKernelGGL(tflow_score_final_kernel<2>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, d_value);
+}
+
+// ---- the iterated solve and its gradient (flow_iter_kernels.h, DESIGN.md section 13, "The iterated solve's gradient")
+// One level's planes in the handle's block, each over max_batch samples: the gray images, the Scharr pair, the tape and beta
+// [iters][B][2][H W], the gradient arriving at the level's field, the level's field (levels >= 1; level 0's goes where the call wants it)
+// and the gradients by the level's images
+struct IterLevel {
+    int H, W;
+    double *I0, *I1, *gxy, *tape, *beta, *ubK, *u, *I0b, *I1b;
+};
+
+// and what the levels share, at level 0's size: ub_0 [B][2], (ab, bb, cb) [B][3], (Ixb, Iyb) [B][2], I0b's direct term [B], max |u| [B]
+struct IterPlan {
+    IterLevel lv[eigd::DENSE_MAX_LEVELS];
+    double *ub0, *abc, *rxy, *dir, *umax;
+    long long doubles;
+};
+
+// the block's layout for a solve of `levels` x `iters` (pointers relative to `at`, which may be null: the size alone)
+IterPlan iter_plan(const eigen_trainer* t, double* at, int levels, int iters)
+{
+    IterPlan pl;
+    const long long Bm = t->cfg.max_batch;
+    double* p = at;
+    auto take = [&](long long n) { double* q = p; p += n; return q; };
+    int h = t->ly[0].H, w = t->ly[0].W;
+    for (int l = 0; l < levels; ++l, h = (h + 1) / 2, w = (w + 1) / 2) {
+        const long long n = Bm * h * w;
+        IterLevel& v = pl.lv[l];
+        v.H = h; v.W = w;
+        v.I0 = take(n); v.I1 = take(n); v.gxy = take(2 * n); v.tape = take(2 * n * iters); v.beta = take(2 * n * iters);
+        v.ubK = take(2 * n); v.u = take(2 * n); v.I0b = take(n); v.I1b = take(n);
+    }
+    const long long n0 = Bm * t->ly[0].HW;
+    pl.ub0 = take(2 * n0); pl.abc = take(3 * n0); pl.rxy = take(2 * n0); pl.dir = take(n0); pl.umax = take(Bm);
+    pl.doubles = (long long)(p - at);
+    return pl;
+}
+
+// The block, made by the first iterated call and freed with the handle: one allocation, so all of it or none.  A later call with more
+// levels or iterations replaces it by one that holds both; a handle that never asks holds none.
+int iter_workspace(eigen_trainer* t, int levels, int iters)
+{
+    if (t->it_ws && levels <= t->it_levels && iters <= t->it_iters) return EIGEN_OK;
+    const int L = std::max(levels, t->it_levels), K = std::max(iters, t->it_iters);
+    const long long doubles = iter_plan(t, nullptr, L, K).doubles;
+    TCHK(hipSetDevice(t->cfg.device));
+    if (!t->it_ws) {
+        // once per handle, checked: the two tiled kernels may ask for the dynamic LDS of the largest radius (radius 11 and above is more than
+        // a launch gets without the attribute)
+        const int lds = pyr_lds_doubles(FLOW_MAX_R) * 8;
+        TCHK(hipFuncSetAttribute((const void*)tfiter_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        TCHK(hipFuncSetAttribute((const void*)tfiter_adj_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, (size_t)doubles * 8);
+    if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%lld): %s", doubles * 8, hipGetErrorString(e));
+    if (t->it_ws) {
+        TCHK(hipFree(t->it_ws));  // waits for whatever still reads it
+        t->allocs.erase(std::find(t->allocs.begin(), t->allocs.end(), (void*)t->it_ws));
+    }
+    t->allocs.push_back(p);
+    t->it_ws = (double*)p; t->it_doubles = doubles; t->it_levels = L; t->it_iters = K;
+    return EIGEN_OK;
+}
+
+// The forward: the gray planes, the pyramid, then one launch per level from the coarsest to the finest; level 0's field goes into d_flow
+void iter_forward(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const float* pred, long long p_bstride, const uint8_t* ref, const float* fref,
+                  long long r_bstride, double* d_flow)
+{
+    const TLayer& y = t->ly[0];
+    IterPlan pl = iter_plan(t, t->it_ws, f.levels, f.iters);
+    IterLevel* lv = pl.lv;
+    const long long n0 = (long long)B * y.HW;
+    if (fref) ew(st, tfiter_gray_kernel<float>, n0, pred, p_bstride, fref, r_bstride, y.C, y.H, y.W, n0, lv[0].I0, lv[0].I1);
+    else ew(st, tfiter_gray_kernel<uint8_t>, n0, pred, p_bstride, ref, r_bstride, y.C, y.H, y.W, n0, lv[0].I0, lv[0].I1);
+    for (int l = 1; l < f.levels; ++l) {
+        const long long n = (long long)B * lv[l].H * lv[l].W;
+        ew(st, tdense_pyrdown_kernel, n, (const double*)lv[l - 1].I0, (const double*)lv[l - 1].I1, lv[l - 1].H, lv[l - 1].W, lv[l].H, lv[l].W, n, lv[l].I0, lv[l].I1);
+    }
+    const int lds = pyr_lds_doubles(f.r) * 8;  // iter_workspace has set the attribute that lets a launch ask for it
+    for (int l = f.levels - 1; l >= 0; --l) {
+        const bool top = l == f.levels - 1;
+        const dim3 grid((unsigned)((lv[l].W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((lv[l].H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
+        hipLaunchKernelGGL(tfiter_fwd_kernel, grid, dim3(FLOW_T), (size_t)lds, st, (const double*)lv[l].I0, (const double*)lv[l].I1, lv[l].H, lv[l].W, f.r, f.eps, f.iters,
+                           top ? (const double*)nullptr : (const double*)lv[l + 1].u, top ? 0 : lv[l + 1].H, top ? 0 : lv[l + 1].W, l ? lv[l].u : d_flow, lv[l].tape,
+                           lv[l].gxy);
+    }
+}
+
+// The backward from g = d value / d u of level 0 [B][2][H W]: the levels from the finest to the coarsest, then the pyramid's adjoint from
+// the coarsest to the finest.  Leaves the gradients by the gray images of level 0 in the plan's lv[0].I1b (prediction) and lv[0].I0b
+// (reference), unscaled.
+void iter_backward(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* g)
+{
+    IterPlan pl = iter_plan(t, t->it_ws, f.levels, f.iters);
+    IterLevel* lv = pl.lv;
+    const int lds = pyr_lds_doubles(f.r) * 8;
+    for (int l = 0; l < f.levels; ++l) {
+        const IterLevel& v = lv[l];
+        const long long HW = (long long)v.H * v.W, n = B * HW;
+        const double* ubK = l ? (const double*)v.ubK : g;
+        const dim3 grid((unsigned)((v.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((v.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
+        hipLaunchKernelGGL(tfiter_umax_kernel, dim3(B), dim3(EW_T), 0, st, (const double*)v.tape, f.iters, HW, pl.umax);
+        hipLaunchKernelGGL(tfiter_adj_kernel, grid, dim3(FLOW_T), (size_t)lds, st, (const double*)v.I0, (const double*)v.I1, v.H, v.W, f.r, f.eps, f.iters,
+                           (const double*)v.tape, ubK, v.beta, pl.abc, pl.ub0);
+        ew(st, tfiter_i1_kernel, n, (const double*)v.tape, (const double*)v.beta, (const double*)v.gxy, (const double*)pl.umax, B, v.H, v.W, f.r, f.iters, n, v.I1b);
+        ew(st, tfiter_q_kernel, n, (const double*)v.I0, (const double*)v.I1, (const double*)v.tape, (const double*)v.beta, (const double*)pl.abc, (const double*)v.gxy, B,
+           v.H, v.W, f.r, f.iters, n, pl.rxy, pl.dir);
+        ew(st, tfiter_i0_kernel, n, (const double*)pl.rxy, (const double*)pl.dir, v.H, v.W, n, v.I0b);
+        if (l < f.levels - 1) {
+            const long long nc = (long long)B * lv[l + 1].H * lv[l + 1].W;
+            ew(st, tfiter_down_kernel, nc, (const double*)pl.ub0, v.H, v.W, lv[l + 1].H, lv[l + 1].W, nc, lv[l + 1].ubK);
+        }
+    }
+    for (int l = f.levels - 2; l >= 0; --l) {
+        const long long n = (long long)B * lv[l].H * lv[l].W;
+        ew(st, tfiter_pyr_adj_kernel, n, (const double*)lv[l + 1].I0b, (const double*)lv[l + 1].I1b, lv[l].H, lv[l].W, lv[l + 1].H, lv[l + 1].W, n, lv[l].I0b, lv[l].I1b);
+    }
+}
+
+// kappa times the gradient by the prediction (by_ref false) or by the reference (true) the last iter_backward left, as floats: stored or
+// added at out (sample b at + b * bstride).  A training call under the prediction pairing adds the reference's apart from the stage, where
+// the single step runs flow_ref_path.
+void iter_store(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, bool by_ref, double kappa, float* out, long long bstride, int accumulate)
+{
+    const TLayer& y = t->ly[0];
+    const IterPlan pl = iter_plan(t, t->it_ws, f.levels, f.iters);
+    const long long n = (long long)B * y.HW;
+    ew(st, tfiter_store_kernel, n, (const double*)(by_ref ? pl.lv[0].I0b : pl.lv[0].I1b), kappa, y.C, y.HW, n, out, bstride, accumulate);
+}
+
+// The flow stage of one term under an iterated solve: the field of level 0 from iter_forward, the unchanged value / score kernels on it,
+// which leave g = d value / d u (masked) in f_g, then iter_backward and the level-0 stores.  The field goes to the handle's workspace
+// unless the caller wants it.
+void iter_flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m)
+{
+    const TLayer& y = t->ly[0];
+    const long long n = (long long)B * y.HW;
+    double* u = m.d_flow ? m.d_flow : t->f_u;
+    iter_forward(t, st, B, f, m.pred, m.p_bstride, m.ref, m.fref, m.r_bstride, u);
+    const bool grads = m.d_seed || m.d_refg;
+    if (f.by_score) {
+        score_passes(t, st, B, f, u, m.d_value);
+        if (grads) ew(st, tfiter_score_g_kernel, n, (const double*)u, y.H, y.W, n, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_g);
+    } else if (f.by_struct) {
+        struct_stage(t, st, B, f, u, m.d_value, grads, false);
+    } else {
+        ew(st, tfiter_value_kernel, n, (const double*)u, f.dir, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
+        if (m.d_value) {
+            hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
+            hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)m.part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), m.d_value, 1);
+        }
+    }
+    if (!grads) return;
+    iter_backward(t, st, B, f, t->f_g);
+    if (m.d_seed) iter_store(t, st, B, f, false, m.kappa, m.d_seed, m.s_bstride, m.s_accumulate);
+    if (m.d_refg) iter_store(t, st, B, f, true, m.kappa, m.d_refg, m.rg_bstride, m.rg_accumulate);
 }
 
 // The flow stage of one term (eigen_trainer_flow_term states the arithmetic): the planes, the tiled solve, then what is wanted of the
@@ -698,6 +894,7 @@ void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, cons
         g.by_corners = false; g.mask = t->c_member; g.mask_bstride = t->ly[0].HW;
         return flow_stage(t, st, B, g, m);
     }
+    if (f.iterated) return iter_flow_stage(t, st, B, f, m);
     double* d_flow = (m.d_refg || f.by_score || f.by_struct) && !m.d_flow ? t->f_u : m.d_flow;
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
@@ -707,12 +904,8 @@ void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, cons
     hipLaunchKernelGGL(tflow_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, n, y.H, y.W, f.r, f.eps, f.dir, f.mask, f.mask_bstride, t->f_q, t->f_mv, d_flow);
     if (f.by_score) {
         // the value and q of the score mode, from the u the solve just wrote: two passes of moments, then q over what the solve left in f_q
-        const dim3 sgrid(SCORE_SLICES, (unsigned)B);
         const double* u = d_flow;
-        hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_spart);
-        hipLaunchKernelGGL(tflow_score_final_kernel<1>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, (double*)nullptr);
-        hipLaunchKernelGGL(tflow_score_moment_kernel<2>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_spart);
-        hipLaunchKernelGGL(tflow_score_final_kernel<2>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, m.d_value);
+        score_passes(t, st, B, f, u, m.d_value);
         if (m.d_seed || m.d_refg)
             hipLaunchKernelGGL(tflow_score_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, u, n, y.H, y.W, f.r, f.eps, f.mask, f.mask_bstride, f.score,
                                (const double*)t->f_rec, t->f_q);
@@ -892,8 +1085,10 @@ int backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, c
     }
     // the prediction pairing: dP0_{s-1} holds what layer 0's terr_bwd of this step left; term s adds its gradient by its reference
     // P0_{s-1} now, and the seed of term s - 1 follows in backward_step(s - 1), ahead of that step's clamp mask
-    if (o.by_flow && o.flow.pair_pred && s >= 1 && s < T - 1 && o.weight(s) != 0.0)
-        flow_ref_path(t, st, B, o.flow, o.flow_kappa(s), t->f_u, t->ly[0].dPn, t->ly[0].CHW(), 1);
+    if (o.by_flow && o.flow.pair_pred && s >= 1 && s < T - 1 && o.weight(s) != 0.0) {
+        if (o.flow.iterated) iter_store(t, st, B, o.flow, true, o.flow_kappa(s), t->ly[0].dPn, t->ly[0].CHW(), 1);
+        else flow_ref_path(t, st, B, o.flow, o.flow_kappa(s), t->f_u, t->ly[0].dPn, t->ly[0].CHW(), 1);
+    }
     return EIGEN_OK;
 }
 
@@ -1014,6 +1209,7 @@ struct LossGradCall {
     const eigen_flow_structure_score* sscore = nullptr;
     const eigen_flow_members* members = nullptr;
     double* h_stats = nullptr;
+    const eigen_dense_solve* solve = nullptr;
 };
 
 // The training call behind every exported eigen_trainer_loss_grad* entry.  The order of the checks is the order of this function: the
@@ -1044,7 +1240,10 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     // the step and layer weights follow the same rules under every objective
     rc = make_objective(t, by_flow ? (int32_t)EIGEN_OBJ_MSE : c.objective, c.h_layer_w, c.h_step_w, T, B, o);
     if (rc) return rc;
+    if (!by_flow && c.solve) return tfail(EIGEN_ERR_INVALID, "a dense solve goes with EIGEN_OBJ_FLOW only");
     if (by_flow) {
+        rc = check_solve(t, c.solve, o.flow);  // ahead of the mask's read-back and of every allocation
+        if (rc) return rc;
         rc = check_flow(t, c.flow, c.d_dir, per_sample_mask(c.members) ? nullptr : c.d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
         if (rc) return rc;
         o.flow.pair_pred = c.pairing == EIGEN_FLOW_PAIR_PREDICTION;
@@ -1063,6 +1262,10 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
             rc = stats_workspace(t);
             if (rc) return rc;
             o.keep_stats = true;
+        }
+        if (o.flow.iterated) {
+            rc = iter_workspace(t, o.flow.levels, o.flow.iters);
+            if (rc) return rc;
         }
     }
     hipStream_t st = (hipStream_t)c.stream;
@@ -1292,7 +1495,8 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
 static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
                           int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr, const eigen_flow_score* score = nullptr,
-                          double* h_stats = nullptr, const eigen_flow_structure_score* sscore = nullptr, const eigen_flow_members* members = nullptr)
+                          double* h_stats = nullptr, const eigen_flow_structure_score* sscore = nullptr, const eigen_flow_members* members = nullptr,
+                          const eigen_dense_solve* solve = nullptr)
 {
     if (!t || !d_pred || (!d_ref && !d_fref) || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
@@ -1302,7 +1506,9 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
         return tfail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", C0HW);
     if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale %g is not finite", scale);
     FlowSpec f;
-    int rc = check_flow(t, flow, d_dir, per_sample_mask(members) ? nullptr : d_mask, 0, f);
+    int rc = check_solve(t, solve, f);  // ahead of the mask's read-back and of every allocation
+    if (rc) return rc;
+    rc = check_flow(t, flow, d_dir, per_sample_mask(members) ? nullptr : d_mask, 0, f);
     if (rc) return rc;
     rc = check_flow_score(score, d_dir, f);
     if (rc) return rc;
@@ -1310,6 +1516,10 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
     if (rc) return rc;
     rc = check_flow_members(t, members, d_mask, batch, f);
     if (rc) return rc;
+    if (f.iterated) {
+        rc = iter_workspace(t, f.levels, f.iters);
+        if (rc) return rc;
+    }
     hipStream_t st = (hipStream_t)stream;
     FlowTerm m;
     m.pred = d_pred; m.p_bstride = p_bstride; m.ref = d_ref; m.fref = d_fref; m.r_bstride = r_bstride;
@@ -1778,3 +1988,44 @@ void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C,
 }
 
 }  // namespace eigd
+
+// ---------------------------------------------------------------------------------------------------- the flow entries with a solve
+extern "C" {
+
+int eigen_trainer_flow_term_iter(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
+                                 int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask, const eigen_flow_score* score,
+                                 const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double scale, double* h_value, double* h_stats,
+                                 double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir,
+                                 const eigen_dense_solve* solve)
+{
+    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
+    if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
+    if (score && sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
+    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream,
+                          d_fref, score, h_stats, sscore, members, solve);
+}
+
+int eigen_trainer_loss_grad_flow_iter(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant,
+                                      int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss, double* h_layer_err,
+                                      float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                      const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score,
+                                      const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double* h_stats, void* stream,
+                                      const eigen_dense_solve* solve)
+{
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
+    c.members = members; c.h_stats = h_stats; c.solve = solve;
+    return loss_grad_call(t, c);
+}
+
+int eigen_trainer_debug_flow_iter(eigen_trainer* t, int32_t force, int64_t* workspace_bytes)
+{
+    if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
+    if (force >= 0) t->it_force = force != 0;
+    if (workspace_bytes) *workspace_bytes = t->it_ws ? t->it_doubles * 8 : 0;
+    return EIGEN_OK;
+}
+
+}  // extern "C"

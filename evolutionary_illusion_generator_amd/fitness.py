@@ -383,6 +383,12 @@ class DenseFitness:
             raise ValueError("the DenseFitness has no score yet: resolved(structure) gives it the structure's")
         return train.make_flow(pairing, self.radius, self.eps, None, self.mask, score=self.score)
 
+    def solve_objective(self, pairing="prediction"):
+        """``flow_objective(pairing)`` with this fitness's own solve, ``.solved(self.levels, self.iters)``: the objective whose gradient
+        runs through every iteration and level ("The iterated solve's gradient"), so that refinement climbs the
+        score of the field the fitness scores.  At levels = iters = 1 it is ``flow_objective``'s."""
+        return self.flow_objective(pairing).solved(self.levels, self.iters)
+
     # what engine.Engine asks of a `dense` argument
     def dense_settings(self, h):
         from . import train

@@ -70,7 +70,10 @@ _ENTRIES = {(False, False): ("eigen_trainer_loss_grad_obj", ()), (False, True): 
             (True, "prediction"): ("eigen_trainer_loss_grad_flow_pair", ("frame_grad", "flow", "pairing")),
             (True, "score"): ("eigen_trainer_loss_grad_flow_score", ("frame_grad", "flow", "pairing", "score")),
             (True, "structure"): ("eigen_trainer_loss_grad_flow_structure", ("frame_grad", "flow", "pairing", "score")),
-            (True, "members"): ("eigen_trainer_loss_grad_flow_members", ("frame_grad", "flow", "pairing", "members"))}
+            (True, "members"): ("eigen_trainer_loss_grad_flow_members", ("frame_grad", "flow", "pairing", "members")),
+            # a real solve (``FlowObjective.solved``): the members entry's arguments, then, behind the stream, the solve
+            (True, "iter"): ("eigen_trainer_loss_grad_flow_iter", ("frame_grad", "flow", "pairing", "members"))}
+SOLVE_MAX_LEVELS, SOLVE_MAX_ITERS, SOLVE_MIN_COARSE = 6, 32, 4   # eigen_dense_solve's accepted values (fitness.DenseFitness states the same)
 
 
 def _bind(lib):
@@ -99,6 +102,10 @@ def _bind(lib):
     lib.eigen_trainer_flow_term_members.argtypes = [_P, _P, _I64, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, ctypes.c_double, _P, _P, _P, _P, _I64, _P, _I64, _P]
     # t, d_ref, d_fref, r_bstride, batch, members, d_mask, h_members, h_counts, stream
     lib.eigen_trainer_flow_members.argtypes = [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]
+    # the members entries' arguments, then (stage alone) d_dir and the solve, (training call) the solve
+    lib.eigen_trainer_flow_term_iter.argtypes = lib.eigen_trainer_flow_term_members.argtypes + [_P, _P]
+    lib.eigen_trainer_loss_grad_flow_iter.argtypes = lib.eigen_trainer_loss_grad_flow_members.argtypes + [_P]
+    lib.eigen_trainer_debug_flow_iter.argtypes = [_P, _I32, ctypes.POINTER(ctypes.c_int64)]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
@@ -359,6 +366,7 @@ class FlowObjective:
             self.mask = m
         self._dev = {}
         self.score = self.members = None
+        self.solve = None       # ``solved``: (levels, iters) of eigen_dense_solve; None is the single regularised step
         if score is not None:
             self.scored(score)
         self.with_members(members)
@@ -412,6 +420,36 @@ class FlowObjective:
         self.score = score
         return self
 
+    def solved(self, levels=1, iters=1):
+        """Set the solve of the stage (eigen_dense_solve; DESIGN.md section 13, "The iterated solve's gradient") and return self: the
+        term's field is then Lucas-Kanade over `levels` pyramid levels with `iters` window iterations per level, what
+        ``fitness.DenseFitness(levels=, iters=)`` scores, and the seed and the reference gradient are the exact gradient through every
+        iteration and level.  (1, 1) is the single regularised step and leaves the objective on today's entries.  ValueError: levels
+        outside 1 .. 6, iters outside 1 .. 32; a coarsest level below 4 pixels is refused by the call that knows the image
+        (``solve_on``)."""
+        for name, v, top in (("levels", levels, SOLVE_MAX_LEVELS), ("iters", iters, SOLVE_MAX_ITERS)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= top:
+                raise ValueError("%s %r outside 1 .. %d" % (name, v, top))
+        self.solve = (int(levels), int(iters))
+        return self
+
+    @property
+    def real_solve(self):
+        """whether the objective carries a solve other than the single step's (1, 1)"""
+        return self.solve is not None and self.solve != (1, 1)
+
+    def solve_on(self, w, h):
+        """eigen_dense_solve of the objective against a w x h image, or None for the single step.  ValueError: the coarsest level would
+        be below 4 pixels on its shorter side."""
+        if not self.real_solve:
+            return None
+        cw, ch = int(w), int(h)
+        for _ in range(self.solve[0] - 1):
+            cw, ch = (cw + 1) // 2, (ch + 1) // 2
+        if min(cw, ch) < SOLVE_MIN_COARSE:
+            raise ValueError("levels %d: the coarsest level of a %d x %d image is %d x %d, below %d pixels" % (self.solve[0], w, h, cw, ch, SOLVE_MIN_COARSE))
+        return engine.DenseSolveC(*self.solve)
+
     def settings(self, stage_alone=False):
         """eigen_flow_settings; the stage-alone entries take no flags (the reference gradient is asked for by the entry called)"""
         return FlowSettings(self.radius, FLOW_MOVING_REFERENCE if self.reference == "moving" and not stage_alone else 0, self.eps)
@@ -446,22 +484,27 @@ class PredictionFlow(FlowObjective):
         super().__init__(radius, eps, direction, mask)
 
 
-def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, reference="constant", score=None, members=None):
+def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, reference="constant", score=None, members=None, levels=1, iters=1):
     """The flow objective of a command line: a ``FlowObjective`` (pairing "frame", with its `reference`) or a ``PredictionFlow``
-    (pairing "prediction"; it has no frame as a reference, so reference="moving" is a ValueError)."""
+    (pairing "prediction"; it has no frame as a reference, so reference="moving" is a ValueError).  levels, iters: the solve
+    (``FlowObjective.solved``); 1 and 1, the default, is the single step and leaves the objective as it was without them."""
     if pairing not in FLOW_PAIRINGS:
         raise ValueError("pairing must be one of %s, got %r" % (", ".join(FLOW_PAIRINGS), pairing))
     if pairing == "frame":
-        return FlowObjective(radius, eps, direction, mask, reference=reference, score=score, members=members)
-    if reference != "constant":
-        raise ValueError("the prediction pairing has no frame as a reference: reference=%r does not go with it" % (reference,))
-    flow = PredictionFlow(radius, eps, direction, mask).scored(score).with_members(members)
-    flow.check_members()
-    return flow
+        flow = FlowObjective(radius, eps, direction, mask, reference=reference, score=score, members=members)
+    else:
+        if reference != "constant":
+            raise ValueError("the prediction pairing has no frame as a reference: reference=%r does not go with it" % (reference,))
+        flow = PredictionFlow(radius, eps, direction, mask).scored(score).with_members(members)
+        flow.check_members()
+    return flow if (levels, iters) == (1, 1) else flow.solved(levels, iters)
 
 
 def _entry_key(flow):
-    """the key of _ENTRIES of a flow objective: its pairing, the kind of its score, or "members" with a per-sample mask or corner members"""
+    """the key of _ENTRIES of a flow objective: "iter" under a real solve; else its pairing, the kind of its score, or "members" with a
+    per-sample mask or corner members"""
+    if flow.real_solve:
+        return "iter"
     if flow.score is None:
         return flow.pairing
     if flow.members is not None or flow.per_sample:
@@ -798,23 +841,30 @@ class PredNetTrainer:
             per = int(np.prod(img))
             g_b, g_t = (per, 0) if frame_grads == "tied" else (T * per, per)
         tails = {"frame_grad": [_ptr(d_grad), ctypes.c_int64(g_b), ctypes.c_int64(g_t)]}
+        after_stream = []   # what an entry takes behind its stream: the solve of eigen_trainer_loss_grad_flow_iter
         if by_flow:
             terms = np.zeros(max(T - 1, 1), np.float64)
             cfg = flow.settings()
             tails["flow"] = [ctypes.byref(cfg), _ptr(d_dir), _ptr(d_mask), _ptr(terms)]
             tails["pairing"] = [ctypes.c_int32(FLOW_PAIRINGS[flow.pairing])]
             stats = None
+            solve = flow.solve_on(self.w, self.h)      # the coarsest-level rule, before any call
+            if solve is not None:
+                tails["members"] = [None, None, None, None]    # the displacement modes; a score fills it in below
+                after_stream = [ctypes.byref(solve)]
             if flow.score is not None:
                 sc = flow.score.settings(self.h)
                 tails["score"] = [ctypes.byref(sc)]
                 mem = flow.members_settings(n, self.h, self.w)
+                by_circles = isinstance(flow.score, FlowScore)
                 if mem is not None:
                     # the widest entry: both scores (one of them NULL), the members and the records of every computed term
                     stats = np.zeros((max(T - 1, 1), n, len(SCORE_STATS)), np.float64)
-                    by_circles = isinstance(flow.score, FlowScore)
                     tails["members"] = [ctypes.byref(sc) if by_circles else None, None if by_circles else ctypes.byref(sc), ctypes.byref(mem), _ptr(stats)]
+                elif solve is not None:
+                    tails["members"] = [ctypes.byref(sc) if by_circles else None, None if by_circles else ctypes.byref(sc), None, None]
         entry, groups = _ENTRIES[by_flow, _entry_key(flow) if by_flow else frame_grads is not None]
-        _check(getattr(self.lib, entry)(*args, *[a for g in groups for a in tails[g]], _stream_arg(stream)))
+        _check(getattr(self.lib, entry)(*args, *[a for g in groups for a in tails[g]], _stream_arg(stream), *after_stream))
         if by_flow:
             self.last_flow_terms = terms[:T - 1]
             if stats is not None:       # the members entry alone returns records: any other call leaves what an earlier one left
@@ -939,6 +989,22 @@ class PredNetTrainer:
         rg = torch.empty((n,) + shp, dtype=torch.float32, device=dev) if reference_grad else None
         cfg = flow.settings(stage_alone=True)
         self.last_flow_stats = None
+        solve = flow.solve_on(self.w, self.h)       # the coarsest-level rule, before the call
+        if solve is not None:
+            # eigen_trainer_flow_term_iter: every mode through one entry, the solve behind the stream
+            sc = flow.score.settings(self.h) if flow.score is not None else None
+            by_circles = isinstance(flow.score, FlowScore)
+            mem = flow.members_settings(n, self.h, self.w) if flow.score is not None else None
+            rec = np.zeros((n, len(SCORE_STATS)), np.float64) if flow.score is not None else None
+            ref_of = lambda x: None if x is None else ctypes.byref(x)
+            _check(self.lib.eigen_trainer_flow_term_iter(
+                self._h, _ptr(p), ctypes.c_int64(per), None if float_ref else _ptr(r), _ptr(r) if float_ref else None, ctypes.c_int64(per), ctypes.c_int32(n),
+                ctypes.byref(cfg), _ptr(d_mask), ref_of(sc if by_circles else None), ref_of(None if by_circles else sc), ref_of(mem), ctypes.c_double(float(scale)),
+                ctypes.byref(value), _ptr(rec), _ptr(u), _ptr(seed), ctypes.c_int64(per), _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None, _ptr(d_dir),
+                ctypes.byref(solve)))
+            self.last_flow_stats = rec
+            out = (value.value, u.cpu().numpy(), seed.cpu().numpy()) + ((rg.cpu().numpy(),) if reference_grad else ())
+            return out + (rec,) if stats else out
         if flow.score is not None:
             sc = flow.score.settings(self.h)
             rec = np.zeros((n, len(SCORE_STATS)), np.float64)
@@ -975,6 +1041,14 @@ class PredNetTrainer:
         _check(self.lib.eigen_trainer_debug_free_planes(self._h, ctypes.c_int32(int(n)), *[_ptr(out[k]) for k in ("theta", "L", "rowS", "colS", "member")], None))
         out["member"] = out["member"] != 0
         return out
+
+    def debug_flow_iter(self, force=None):
+        """Test hook (eigen_trainer_debug_flow_iter): force True / False sets whether a flow call without a real solve goes through the
+        iterated stage and its backward too, on this handle.  -> the bytes of the iterated workspace the handle holds (0 before its first
+        iterated call)."""
+        n = ctypes.c_int64(0)
+        _check(self.lib.eigen_trainer_debug_flow_iter(self._h, ctypes.c_int32(-1 if force is None else int(bool(force))), ctypes.byref(n)))
+        return int(n.value)
 
     def evaluate(self, frames, reset=True, n_fed=None, requant=False, pred=False, layer_errors=False):
         """Forward only, no tape: the mean squared error of every step of frames uint8 [n, T, C, H, W], T of any length, as
@@ -1185,6 +1259,9 @@ def refine_stills(trainer, images, n_repeat=20, n_ext=2, iters=10, step=2.0, req
     With requant=True the byte a self-fed step reads is a constant of the graph, so the gradient does not hold how that byte follows the
     prediction; under a PredictionFlow every weighted term passes through such a step, and at 160 x 120 that gradient was measured
     not to predict the change of the loss, while with requant=False it does ("The prediction pairing").
+    The objective's solve is followed: with ``flow.solved(levels, iters)``, or ``DenseFitness.solve_objective()``, every term's field is
+    the pyramidal, iterated solve's and the step follows the exact gradient through it ("The iterated solve's
+    gradient"); ValueError before any call if the coarsest level of the trainer's image would be below 4 pixels.
 
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images.  The calls
     OVERWRITE the trainer's weight gradients and its kept sequence state."""
@@ -1304,7 +1381,8 @@ def refine_genomes(trainer, genomes, config, structure, n_repeat=20, n_ext=2, it
     ``eval_images(pairing=PAIR_POPULATION)``); the default step_weights and the n_ext >= 2 rule are ``refine_stills``'.
 
     history[i] is the loss of the images as they entered iteration i, history[iters] that of the returned images, which are the
-    render of genomes'.  The calls OVERWRITE the trainer's weight gradients and its kept sequence state."""
+    render of genomes'.  The objective's solve is followed as ``refine_stills`` follows it: ``DenseFitness.solve_objective()`` climbs the
+    score of the field the dense fitness itself scores.  The calls OVERWRITE the trainer's weight gradients and its kept sequence state."""
     import copy
     from . import fitness
     from .genome import GenomeBatch, flatten_genome_map

@@ -16,7 +16,8 @@
         motion score of --structure, fitness.DenseFitness, in place of the corner tracks; with --refine K --objective flow --flow-score
         --flow-pairing prediction selection and refinement use one score with the same settings)
     python examples/evolve_illusion.py -g 5 --fitness dense --dense-levels 3 --dense-iters 3   (the dense score on the field of a pyramidal, iterated
-        Lucas-Kanade solve, which follows motions of a pixel and more where the single step shrinks them; refinement still climbs the single step)
+        Lucas-Kanade solve, which follows motions of a pixel and more where the single step shrinks them; --refine-solve fitness makes --refine climb that
+        score through that solve, --flow-levels L --flow-iters K give the objective of the --flow-* options a solve of its own)
 """
 import argparse
 import os
@@ -49,6 +50,9 @@ def main():
                     help="what selects: the reference's score of the tracked corners, or the dense motion score of --structure (fitness.DenseFitness)")
     ap.add_argument("--dense-levels", type=int, default=1, help="--fitness dense: pyramid levels of the solve (1 .. 6; 1 with --dense-iters 1 is the single step)")
     ap.add_argument("--dense-iters", type=int, default=1, help="--fitness dense: iterations per pyramid level (1 .. 32)")
+    ap.add_argument("--refine-solve", default="single", choices=["single", "fitness"],
+                    help="--refine under --fitness dense: single climbs the objective of the --flow-* options (by default the single regularised step), fitness "
+                         "climbs DenseFitness.solve_objective(), the score of the field the fitness itself scores, through --dense-levels and --dense-iters")
     add_flow_arguments(ap, direction=dict(choices=["tangent", "radial", "horizontal", "vertical"], help="objective flow: the field (default: the mean square)"),
                        radius=dict(help=None), eps=dict(help=None),
                        reference=dict(choices=["constant", "moving"], help="objective flow: moving also follows how the term moves with the still as its reference frame"),
@@ -91,8 +95,13 @@ def main():
         best = sorted((g for _, g in genomes), key=lambda g: -g.fitness)[:a.refine]
         if not trainer:
             trainer.append(train.PredNetTrainer(a.model, channels, w, h, a.refine, 22))
-        flow = flow_of(a, w, h, inside)
-        refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters, objective=a.objective, flow=flow)
+        if a.refine_solve == "fitness":
+            if dense is None:
+                raise SystemExit("--refine-solve fitness needs --fitness dense: it climbs that fitness's own score through its own solve")
+            flow, objective = dense.solve_objective(), "flow"
+        else:
+            flow, objective = flow_of(a, w, h, inside), a.objective
+        refined, history, _ = train.refine_genomes(trainer[0], best, config, a.structure, iters=a.refine_iters, objective=objective, flow=flow)
         for g, r in zip(best, refined):
             for k, n in r.nodes.items():
                 g.nodes[k].bias, g.nodes[k].response = n.bias, n.response

@@ -27,6 +27,8 @@ FLOW_ARGUMENTS = {
                          "every term's own reference, as the fitness does (train.CornerMembers)"),
     "corner-quality": dict(type=float, default=0.3, help="--flow-members corners: goodFeaturesToTrack's qualityLevel (the fitness's: 0.3)"),
     "corner-distance": dict(type=float, default=7.0, help="--flow-members corners: goodFeaturesToTrack's minDistance in pixels (the fitness's: 7)"),
+    "levels": dict(type=int, default=1, help="objective flow: pyramid levels of the solve the gradient runs through (1 .. 6; 1 with --flow-iters 1 is the single step)"),
+    "iters": dict(type=int, default=1, help="objective flow: window iterations per pyramid level (1 .. 32)"),
 }
 
 
@@ -71,7 +73,7 @@ def flow_of(a, w, h, mask=None):
         return None
     score = score_of(a)
     return train.make_flow(a.flow_pairing, a.flow_radius, a.flow_eps, None if a.flow_direction is None else train.flow_direction(a.flow_direction, w, h), mask,
-                           reference=a.flow_reference, score=score, members=members_of(a))
+                           reference=a.flow_reference, score=score, members=members_of(a), levels=a.flow_levels, iters=a.flow_iters)
 
 
 def dense_fitness_of(a, structure, mask=None):

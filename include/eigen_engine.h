@@ -897,6 +897,40 @@ int eigen_eval_images_dense_iter(eigen_engine* e, const uint8_t* d_images, int32
  * this handle; pyramid_bytes (may be NULL) receives the bytes of the pyramid the handle holds, 0 before its first iterated call. */
 int eigen_debug_dense_solve(eigen_engine* e, int32_t force, int64_t* pyramid_bytes);
 
+/* ---- The flow objective through the solve ("The iterated solve's gradient").  With a solve of more than one level or
+ * iteration the flow stage of a term runs eigen_dense_solve's semantics on the trainer's float images (I0 the gray of the reference, I1 the
+ * gray of the prediction, as the single step's planes form them; on floats that are exactly (float)byte / 255.0f the field is
+ * eigen_dense_score_iter's d_flow bit for bit), the unchanged value / score / members kernels read the field of level 0, and the seed and
+ * the reference gradient are the exact derivative of the written formulas through every iteration and level, with floor,
+ * x1 = min(x0 + 1, W - 1) and the sampler's two clamps held constant (a clamped coordinate passes no gradient).  Float64, fixed orders, no
+ * atomics; cast to float once where the single step's seed and reference gradient are stored or added.
+ * The workspace (pyramid, every iterate and the adjoint planes, at max_batch) is allocated by the first iterated call on the handle, all
+ * of it or none, and freed with the handle; a handle that never asks allocates nothing more than before.
+ *
+ * eigen_trainer_flow_term_iter: eigen_trainer_flow_term_members' arguments (at most one of score and sscore; neither: the displacement
+ * modes, which take d_dir) plus d_dir and solve.  eigen_trainer_loss_grad_flow_iter: eigen_trainer_loss_grad_flow_members' arguments plus
+ * solve; both pairings and EIGEN_FLOW_MOVING_REFERENCE are accepted.  solve NULL or {1, 1}: the call is its namesake's (or, without a
+ * score, eigen_trainer_flow_term / _ref / _pair's), launch for launch and bit for bit.
+ * Errors: the namesakes'; EIGEN_ERR_INVALID before any launch or allocation for a solve outside eigen_dense_solve's accepted values
+ * (levels 1 .. 6, iters 1 .. 32, a coarsest level of at least 4 pixels), in that struct's own words. */
+int eigen_trainer_flow_term_iter(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref,
+                                 int64_t r_bstride, int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask,
+                                 const eigen_flow_score* score, const eigen_flow_structure_score* sscore, const eigen_flow_members* members,
+                                 double scale, double* h_value, double* h_stats, double* d_flow, float* d_seed, int64_t s_bstride,
+                                 float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir, const eigen_dense_solve* solve);
+int eigen_trainer_loss_grad_flow_iter(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                      int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                      const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                      int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                      const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score,
+                                      const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double* h_stats,
+                                      void* stream, const eigen_dense_solve* solve);
+
+/* Test hook of the trainer's solve: force >= 0 sets whether a {1, 1} (or NULL) solve goes through the iterated stage and its backward
+ * too, on this handle; workspace_bytes (may be NULL) receives the bytes of the iterated workspace the handle holds, 0 before its first
+ * iterated call. */
+int eigen_trainer_debug_flow_iter(eigen_trainer* t, int32_t force, int64_t* workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

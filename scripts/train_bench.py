@@ -75,16 +75,18 @@ def frames(seed, n, T, c, h, w):
 FLOW_WEIGHTS = [0.0] * (T - 3) + [1.0, 1.0]   # two weighted terms, as a refinement call has them
 
 
-def objective_args(name, reference="constant", pairing="frame", score=None, members=None):
+def objective_args(name, reference="constant", pairing="frame", score=None, members=None, levels=1, iters=1):
     if name == "flow":
         from evolutionary_illusion_generator_amd.train import make_flow
-        return dict(objective="flow", flow=make_flow(pairing, radius=7, eps=1e-2, reference=reference, score=score, members=members), step_weights=FLOW_WEIGHTS)
+        return dict(objective="flow", flow=make_flow(pairing, radius=7, eps=1e-2, reference=reference, score=score, members=members, levels=levels, iters=iters),
+                    step_weights=FLOW_WEIGHTS)
     return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
 
 
-def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None, members=None):
+def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None, members=None, levels=1, iters=1):
     """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round; with
-    the moving reference also per "flow" call with tied frame gradients, under either reference"""
+    the moving reference also per "flow" call with tied frame gradients, under either reference; with a real solve (levels, iters) also per
+    "flow" call of the same settings whose gradient runs through that solve ("flow_iter")"""
     import ctypes
     import torch
     from evolutionary_illusion_generator_amd import weights
@@ -100,6 +102,8 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"
         calls["flow_score"] = objective_args("flow", reference, pairing, score)
     if members is not None:
         calls["flow_score_corners"] = objective_args("flow", reference, pairing, score, members)
+    if (levels, iters) != (1, 1):
+        calls["flow_iter"] = objective_args("flow", reference, pairing, score, members, levels, iters)
     ms = {k: [] for k in calls}
     loss = {}
     with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
@@ -199,12 +203,13 @@ def run_data(steps, warmup, layers=1, rounds=6):
             for name, v in ms.items()]
 
 
-def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None, members=None, optim=(None, 0.0, False), micro_batches=1):
+def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None, members=None, optim=(None, 0.0, False), micro_batches=1, levels=1,
+                iters=1):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
     d = torch.from_numpy(frames(0, B, T, CH[0], H, W)).cuda()
-    kw = objective_args(objective, reference, pairing, score, members) if objective == "flow" else objective_args(objective)
+    kw = objective_args(objective, reference, pairing, score, members, levels, iters) if objective == "flow" else objective_args(objective)
     # the logical batch stays B: with micro-batches the handle, and so the tape, is B / micro_batches
     tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B // micro_batches, T, clip_norm=optim[0], weight_decay=optim[1],
                         skip_nonfinite=optim[2])
@@ -342,7 +347,7 @@ def main():
     ap.add_argument("--side", default="both", choices=["trainer", "torch", "both"])
     ap.add_argument("--objective", default="mse", choices=["mse", "l0", "lall", "flow"], help="the trainer side's objective")
     ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
-    add_flow_arguments(ap, ("reference", "pairing", "score", "score-structure", "max-norm", "members", "corner-quality", "corner-distance"), **{"score-structure": dict(choices=["circles", "bands", "free"])}, reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
+    add_flow_arguments(ap, ("reference", "pairing", "score", "score-structure", "max-norm", "members", "corner-quality", "corner-distance", "levels", "iters"), **{"score-structure": dict(choices=["circles", "bands", "free"])}, reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
                        pairing=dict(help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)"))
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--clip-norm", type=float, default=None, help="the trainer's clip_norm (default: no clipping)")
@@ -374,7 +379,7 @@ def main():
             print(json.dumps(r), flush=True)
         return
     if a.flow_cost:
-        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score, members=members):
+        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score, members=members, levels=a.flow_levels, iters=a.flow_iters):
             print(json.dumps(r), flush=True)
         return
     from evolutionary_illusion_generator_amd.train import check_micro_batches, check_optim
@@ -387,7 +392,7 @@ def main():
         for r in run_optim_cost(a.steps, a.warmup, clip_norm=optim[0], weight_decay=optim[1], skip_nonfinite=optim[2], micro_batches=max(a.micro_batches, 2)):
             print(json.dumps(r), flush=True)
         return
-    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members, optim, a.micro_batches)]
+    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members, optim, a.micro_batches, a.flow_levels, a.flow_iters)]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
