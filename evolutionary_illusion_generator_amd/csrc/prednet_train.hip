@@ -27,6 +27,7 @@
 #include "dense_pyr_kernels.h"
 #include "dense_stage.h"
 #include "flow_iter_kernels.h"
+#include "flow_target_kernels.h"
 
 using namespace eigt;
 
@@ -462,6 +463,9 @@ struct FlowSpec {
     int levels = 1, iters = 1;
     int max_corners = 0, block_size = 0;
     double quality = 0.0, min_distance = 0.0;
+    // the target field of the third displacement mode (flow_target_kernels.h; null: none), doubles: sample b of term s at
+    // + b * bstride + s * tstride as [2][H W]
+    struct Target { const double* p = nullptr; long long bstride = 0, tstride = 0; } target;
     // what divides a term's scale in kappa: B N_m, or B in the score mode, whose value is a mean over the samples alone
     double kappa_div(int B) const { return by_score || by_struct ? (double)B : (double)(B * n_mask); }
 };
@@ -680,7 +684,23 @@ struct FlowTerm {
     double* d_flow = nullptr;                                             // the flow u [B][2][H W]
     float* d_seed = nullptr; long long s_bstride = 0; int s_accumulate = 0;   // kappa d value / d pred, added in float or stored
     float* d_refg = nullptr; long long rg_bstride = 0; int rg_accumulate = 0; // kappa d value / d reference (flow_ref_kernels.h), likewise
+    const double* target = nullptr;                                           // this term's target field (null: none), sample b at + b * FlowSpec's target.bstride
 };
+
+// A target field's rules, before anything is launched or allocated (null: none, and the strides are not read): it is a displacement mode
+// of its own, so no direction, score or members go with it, and a sample's [2][H W] doubles must fit its strides.
+int check_flow_target(const eigen_trainer* t, const double* d_target, long long t_bstride, long long t_tstride, int n_terms, bool by_flow, const float* d_dir,
+                      const void* score, const void* sscore, const void* members, FlowSpec& f)
+{
+    if (!d_target) return EIGEN_OK;
+    if (!by_flow) return tfail(EIGEN_ERR_INVALID, "a flow target goes with EIGEN_OBJ_FLOW only");
+    if (d_dir || score || sscore || members) return tfail(EIGEN_ERR_INVALID, "a flow target takes no direction field, score or members");
+    const long long field = 2 * t->ly[0].HW;
+    if (t_bstride < field) return tfail(EIGEN_ERR_INVALID, "t_bstride %lld is smaller than one field (%lld doubles)", t_bstride, field);
+    if (n_terms > 1 && t_tstride < field) return tfail(EIGEN_ERR_INVALID, "t_tstride %lld is smaller than one field (%lld doubles)", t_tstride, field);
+    f.target.p = d_target; f.target.bstride = t_bstride; f.target.tstride = t_tstride;
+    return EIGEN_OK;
+}
 
 // The value and q of a structure score from the u the solve just wrote (flow_struct_kernels.h): two passes of moments, for Free the
 // prepare and the pair pass between them, then (want_q) the gradient g and q over what the solve left in f_q.
@@ -870,7 +890,8 @@ void iter_flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f,
     } else if (f.by_struct) {
         struct_stage(t, st, B, f, u, m.d_value, grads, false);
     } else {
-        ew(st, tfiter_value_kernel, n, (const double*)u, f.dir, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
+        if (m.target) ew(st, tflow_target_kernel, n, (const double*)u, m.target, f.target.bstride, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
+        else ew(st, tfiter_value_kernel, n, (const double*)u, f.dir, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
         if (m.d_value) {
             hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
             hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)m.part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), m.d_value, 1);
@@ -895,7 +916,7 @@ void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, cons
         return flow_stage(t, st, B, g, m);
     }
     if (f.iterated) return iter_flow_stage(t, st, B, f, m);
-    double* d_flow = (m.d_refg || f.by_score || f.by_struct) && !m.d_flow ? t->f_u : m.d_flow;
+    double* d_flow = (m.d_refg || f.by_score || f.by_struct || m.target) && !m.d_flow ? t->f_u : m.d_flow;
     const TLayer& y = t->ly[0];
     const long long n = (long long)B * y.HW;
     if (m.fref) ew(st, tflow_pair_prep_kernel, n, m.pred, m.p_bstride, m.fref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
@@ -911,7 +932,13 @@ void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, cons
                                (const double*)t->f_rec, t->f_q);
     } else if (f.by_struct) {
         struct_stage(t, st, B, f, d_flow, m.d_value, m.d_seed || m.d_refg);
-    } else if (m.d_value) {
+    } else if (m.target) {
+        // the target mode: mv and g from the u the solve just wrote, then q from g over the solve's own a, b, c and det
+        ew(st, tflow_target_kernel, n, (const double*)d_flow, m.target, f.target.bstride, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
+        if (m.d_seed || m.d_refg)
+            hipLaunchKernelGGL(tflow_struct_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_g, n, y.H, y.W, f.r, f.eps, t->f_q);
+    }
+    if (!f.by_score && !f.by_struct && m.d_value) {
         hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
         hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)m.part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), m.d_value, 1);
     }
@@ -1032,6 +1059,7 @@ int backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, c
                 m.pred = P; m.p_bstride = CHW; m.kappa = o.flow_kappa(s);
                 m.part = t->d_spart + (long long)s * STEP_LOSS_BLOCKS; m.d_value = t->d_step + s;
                 m.d_seed = y.dPn; m.s_bstride = CHW; m.s_accumulate = 1;
+                if (o.flow.target.p) m.target = o.flow.target.p + (long long)s * o.flow.target.tstride;
                 if (o.flow.pair_pred) {
                     m.fref = y.P_at(s, B); m.r_bstride = CHW;
                     m.d_flow = s >= 1 ? t->f_u : nullptr;
@@ -1210,6 +1238,7 @@ struct LossGradCall {
     const eigen_flow_members* members = nullptr;
     double* h_stats = nullptr;
     const eigen_dense_solve* solve = nullptr;
+    const double* d_target = nullptr; int64_t t_bstride = 0, t_tstride = 0;
 };
 
 // The training call behind every exported eigen_trainer_loss_grad* entry.  The order of the checks is the order of this function: the
@@ -1233,6 +1262,8 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     }
     Objective o;
     const bool by_flow = c.objective == EIGEN_OBJ_FLOW;
+    rc = check_flow_target(t, c.d_target, c.t_bstride, c.t_tstride, T - 1, by_flow, c.d_dir, c.score, c.sscore, c.members, o.flow);
+    if (rc) return rc;
     if (!by_flow && (c.flow || c.d_dir || c.d_mask)) return tfail(EIGEN_ERR_INVALID, "flow settings, direction and mask go with EIGEN_OBJ_FLOW only");
     if (!by_flow && c.score) return tfail(EIGEN_ERR_INVALID, "a flow score goes with EIGEN_OBJ_FLOW only");
     if (!by_flow && c.sscore) return tfail(EIGEN_ERR_INVALID, "a flow structure score goes with EIGEN_OBJ_FLOW only");
@@ -1496,7 +1527,7 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
                           int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr, const eigen_flow_score* score = nullptr,
                           double* h_stats = nullptr, const eigen_flow_structure_score* sscore = nullptr, const eigen_flow_members* members = nullptr,
-                          const eigen_dense_solve* solve = nullptr)
+                          const eigen_dense_solve* solve = nullptr, const double* d_target = nullptr, int64_t t_bstride = 0)
 {
     if (!t || !d_pred || (!d_ref && !d_fref) || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
@@ -1506,7 +1537,9 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
         return tfail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", C0HW);
     if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale %g is not finite", scale);
     FlowSpec f;
-    int rc = check_solve(t, solve, f);  // ahead of the mask's read-back and of every allocation
+    int rc = check_flow_target(t, d_target, t_bstride, 0, 1, true, d_dir, score, sscore, members, f);
+    if (rc) return rc;
+    rc = check_solve(t, solve, f);  // ahead of the mask's read-back and of every allocation
     if (rc) return rc;
     rc = check_flow(t, flow, d_dir, per_sample_mask(members) ? nullptr : d_mask, 0, f);
     if (rc) return rc;
@@ -1525,6 +1558,7 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
     m.pred = d_pred; m.p_bstride = p_bstride; m.ref = d_ref; m.fref = d_fref; m.r_bstride = r_bstride;
     m.kappa = scale / f.kappa_div(batch); m.part = t->d_spart; m.d_value = h_value ? t->d_step : nullptr;
     m.d_flow = d_flow; m.d_seed = d_seed; m.s_bstride = s_bstride; m.d_refg = d_refg; m.rg_bstride = rg_bstride;
+    m.target = f.target.p;
     flow_stage(t, st, batch, f, m);
     TCHK(hipGetLastError());
     if (h_value) {
@@ -2017,6 +2051,34 @@ int eigen_trainer_loss_grad_flow_iter(eigen_trainer* t, const uint8_t* d_frames,
     c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
     c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
     c.members = members; c.h_stats = h_stats; c.solve = solve;
+    return loss_grad_call(t, c);
+}
+
+int eigen_trainer_flow_term_target(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
+                                   int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask, const eigen_flow_score* score,
+                                   const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double scale, double* h_value, double* h_stats,
+                                   double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir,
+                                   const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride)
+{
+    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
+    if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
+    if (score && sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
+    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream,
+                          d_fref, score, h_stats, sscore, members, solve, d_target, t_bstride);
+}
+
+int eigen_trainer_loss_grad_flow_target(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant,
+                                        int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss, double* h_layer_err,
+                                        float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                        const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score,
+                                        const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double* h_stats, void* stream,
+                                        const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride, int64_t t_tstride)
+{
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
+    c.members = members; c.h_stats = h_stats; c.solve = solve; c.d_target = d_target; c.t_bstride = t_bstride; c.t_tstride = t_tstride;
     return loss_grad_call(t, c);
 }
 

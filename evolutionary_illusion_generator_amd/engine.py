@@ -30,7 +30,8 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_trainer_flow_term_members", "eigen_trainer_loss_grad_flow_members", "eigen_trainer_grad_norms", "eigen_trainer_adam_ex",
            "eigen_trainer_accumulate", "eigen_dense_score", "eigen_eval_population_dense", "eigen_eval_images_dense",
            "eigen_render_moving_cppn", "eigen_dense_score_iter", "eigen_eval_population_dense_iter", "eigen_eval_images_dense_iter",
-           "eigen_debug_dense_solve", "eigen_trainer_flow_term_iter", "eigen_trainer_loss_grad_flow_iter", "eigen_trainer_debug_flow_iter"]
+           "eigen_debug_dense_solve", "eigen_trainer_flow_term_iter", "eigen_trainer_loss_grad_flow_iter", "eigen_trainer_debug_flow_iter",
+           "eigen_trainer_flow_term_target", "eigen_trainer_loss_grad_flow_target"]
 
 
 class EigenConfig(ctypes.Structure):

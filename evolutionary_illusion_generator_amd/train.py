@@ -72,7 +72,9 @@ _ENTRIES = {(False, False): ("eigen_trainer_loss_grad_obj", ()), (False, True): 
             (True, "structure"): ("eigen_trainer_loss_grad_flow_structure", ("frame_grad", "flow", "pairing", "score")),
             (True, "members"): ("eigen_trainer_loss_grad_flow_members", ("frame_grad", "flow", "pairing", "members")),
             # a real solve (``FlowObjective.solved``): the members entry's arguments, then, behind the stream, the solve
-            (True, "iter"): ("eigen_trainer_loss_grad_flow_iter", ("frame_grad", "flow", "pairing", "members"))}
+            (True, "iter"): ("eigen_trainer_loss_grad_flow_iter", ("frame_grad", "flow", "pairing", "members")),
+            # a target field (``flow_target=``): the iter entry's arguments, then, behind the solve, the target and its two strides
+            (True, "target"): ("eigen_trainer_loss_grad_flow_target", ("frame_grad", "flow", "pairing", "members"))}
 SOLVE_MAX_LEVELS, SOLVE_MAX_ITERS, SOLVE_MIN_COARSE = 6, 32, 4   # eigen_dense_solve's accepted values (fitness.DenseFitness states the same)
 
 
@@ -106,6 +108,9 @@ def _bind(lib):
     lib.eigen_trainer_flow_term_iter.argtypes = lib.eigen_trainer_flow_term_members.argtypes + [_P, _P]
     lib.eigen_trainer_loss_grad_flow_iter.argtypes = lib.eigen_trainer_loss_grad_flow_members.argtypes + [_P]
     lib.eigen_trainer_debug_flow_iter.argtypes = [_P, _I32, ctypes.POINTER(ctypes.c_int64)]
+    # the iter entries' arguments, then d_target and t_bstride, (training call) t_tstride
+    lib.eigen_trainer_flow_term_target.argtypes = lib.eigen_trainer_flow_term_iter.argtypes + [_P, _I64]
+    lib.eigen_trainer_loss_grad_flow_target.argtypes = lib.eigen_trainer_loss_grad_flow_iter.argtypes + [_P, _I64, _I64]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
@@ -500,9 +505,11 @@ def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, re
     return flow if (levels, iters) == (1, 1) else flow.solved(levels, iters)
 
 
-def _entry_key(flow):
-    """the key of _ENTRIES of a flow objective: "iter" under a real solve; else its pairing, the kind of its score, or "members" with a
-    per-sample mask or corner members"""
+def _entry_key(flow, target=None):
+    """the key of _ENTRIES of a flow objective: "target" for a call with a target field; "iter" under a real solve; else its pairing, the
+    kind of its score, or "members" with a per-sample mask or corner members"""
+    if target is not None:
+        return "target"
     if flow.real_solve:
         return "iter"
     if flow.score is None:
@@ -519,6 +526,34 @@ def _check_flow(objective, flow):
             raise ValueError("objective='flow' needs flow=FlowObjective(...), got %r" % (flow,))
     elif flow is not None:
         raise ValueError("flow is given but the objective is %r" % (objective,))
+
+
+def check_flow_target(objective, flow, target, shape):
+    """The rules of a target field (``forward_backward(flow_target=)``, ``flow_term(target=)``) against the `shape` the call expects,
+    [n, T - 1, 2, H, W] or, for the stage alone, [n, 2, H, W]: -> None without a target, else its leading strides in doubles (one per
+    leading dimension).  The target is a float64 numpy array or torch tensor whose last three dimensions are contiguous.  ValueError: a
+    target without objective="flow"; under an objective that carries a direction, a score, members or a per-sample mask (the target is a
+    displacement mode of its own, and these modes divide by the shared mask's count); a wrong dtype or shape; last dimensions that are
+    not contiguous."""
+    if target is None:
+        return None
+    if objective != "flow" or not isinstance(flow, FlowObjective):
+        raise ValueError("flow_target goes with objective='flow' and a FlowObjective, got objective %r" % (objective,))
+    if flow.direction is not None or flow.score is not None or flow.members is not None or flow.per_sample:
+        raise ValueError("a flow target takes no direction, score, members or per-sample mask")
+    by_numpy = isinstance(target, np.ndarray)
+    if not by_numpy and not (hasattr(target, "data_ptr") and hasattr(target, "stride")):
+        raise ValueError("the flow target must be a float64 numpy array or torch tensor, got %r" % (type(target),))
+    if (target.dtype != np.float64) if by_numpy else (str(target.dtype) != "torch.float64"):
+        raise ValueError("the flow target must be float64, got %s" % (target.dtype,))
+    shape = tuple(int(v) for v in shape)
+    if tuple(target.shape) != shape:
+        raise ValueError("the flow target must be %s, got %s" % (list(shape), list(target.shape)))
+    strides = [int(v) // 8 for v in target.strides] if by_numpy else [int(v) for v in target.stride()]
+    h, w = shape[-2:]
+    if strides[-3:] != [h * w, w, 1]:
+        raise ValueError("the last three dimensions of the flow target must be contiguous, got strides %s" % (strides,))
+    return strides[:-3]
 
 
 def check_layer_weights(layer_weights, n_layers):
@@ -811,16 +846,30 @@ class PredNetTrainer:
         tab = np.zeros((max(int(d.shape[1]) - 1, 1), len(self.channels)), np.float64) if table else None
         return tab, self._torch.empty(tuple(d.shape), dtype=self._torch.float32, device=d.device) if pred else None
 
-    def _loss_grad(self, d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights, layer_errors, frame_grads, flow=None):
+    def _target(self, objective, flow, target, shape):
+        """A target field on the device and its leading strides as c_int64 (``check_flow_target`` states the rules), or (None, [])"""
+        if target is None:
+            return None, []
+        torch = self._torch
+        if isinstance(target, np.ndarray) or not target.is_cuda:
+            check_flow_target(objective, flow, target if isinstance(target, np.ndarray) else target.contiguous(), shape)
+            target = (torch.from_numpy(np.ascontiguousarray(target)) if isinstance(target, np.ndarray) else target.contiguous()).cuda(self.device)
+        return target, [ctypes.c_int64(v) for v in check_flow_target(objective, flow, target, shape)]
+
+    def _loss_grad(self, d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights, layer_errors, frame_grads,
+                   flow_target=None, flow=None):
         """The call behind forward_backward, on frames already on the device: (loss, table or None, d_pred or None, d_grad or None), the
         last two device tensors.  Every argument is checked before anything is launched.  Under objective="flow" the float64 [T - 1]
         terms of the call are left in ``self.last_flow_terms``; under a per-sample mask or corner members the float64 [T - 1, n, 10] records
         of the samples of every computed term (zeros for the others) are left in ``self.last_flow_stats``, which any other call leaves as it is."""
         torch = self._torch
+        if isinstance(flow_target, FlowObjective) and flow is None:     # `flow` was the positional argument here before `flow_target` existed
+            flow_target, flow = None, flow_target
         if objective not in OBJECTIVES:
             raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
         _check_flow(objective, flow)
         by_flow = objective == "flow"
+        d_target, t_strides = self._target(objective, flow, flow_target, (n, max(T - 1, 0), 2, self.h, self.w))
         d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w) if by_flow else (None, None)
         lam = check_layer_weights(layer_weights, len(self.channels))
         w_arr = None
@@ -863,7 +912,11 @@ class PredNetTrainer:
                     tails["members"] = [ctypes.byref(sc) if by_circles else None, None if by_circles else ctypes.byref(sc), ctypes.byref(mem), _ptr(stats)]
                 elif solve is not None:
                     tails["members"] = [ctypes.byref(sc) if by_circles else None, None if by_circles else ctypes.byref(sc), None, None]
-        entry, groups = _ENTRIES[by_flow, _entry_key(flow) if by_flow else frame_grads is not None]
+            if d_target is not None:
+                # eigen_trainer_loss_grad_flow_target: no score or members go with a target; the solve (NULL: the single step), then the target
+                tails["members"] = [None, None, None, None]
+                after_stream = [ctypes.byref(solve) if solve is not None else None, _ptr(d_target)] + t_strides
+        entry, groups = _ENTRIES[by_flow, _entry_key(flow, d_target) if by_flow else frame_grads is not None]
         _check(getattr(self.lib, entry)(*args, *[a for g in groups for a in tails[g]], _stream_arg(stream), *after_stream))
         if by_flow:
             self.last_flow_terms = terms[:T - 1]
@@ -875,7 +928,7 @@ class PredNetTrainer:
         return value, table, d_pred, d_grad
 
     def forward_backward(self, frames, reset=True, pred=False, stream=None, n_fed=None, requant=False, step_weights=None, objective="mse",
-                         layer_weights=None, layer_errors=False, frame_grads=None, flow_terms=False, flow=None):
+                         layer_weights=None, layer_errors=False, frame_grads=None, flow_terms=False, flow_target=None, flow=None):
         """Loss of frames uint8 [n, T, C, H, W] (numpy or a device tensor, n <= batch) and the gradients, kept on the device
         (``grads()``).  reset=False continues from the state the previous call left (the same n), as a constant.
         pred=True also returns the float predictions P0 [n, T, C, H, W] (numpy).
@@ -904,7 +957,18 @@ class PredNetTrainer:
         With flow=PredictionFlow(...) term s runs from the previous prediction P0_{s-1} (for s = 0 the start state's P0: zeros after a
         reset) to prediction s, both in the graph ("The prediction pairing"); loss and terms are those of that
         pairing and the frame gradient is the input path alone.
-        flow_terms=True (flow only) appends the float64 [T - 1] terms last; a term of weight zero is not computed and reads 0."""
+        flow_terms=True (flow only) appends the float64 [T - 1] terms last; a term of weight zero is not computed and reads 0.
+
+        flow_target: None, or the field every term's flow shall equal ("The target field"): float64
+        [n, T - 1, 2, H, W], numpy or a device tensor (the last three dimensions contiguous, the strides of the first two are passed
+        through), in the solve's own convention (content at x in the reference is at x + u in the prediction), which is how
+        ``MovingTextures.batch(k, n, flow=True)[1]`` states its flow.  Term s is then the mean squared endpoint error of the solved
+        field against flow_target[:, s], and takes the place of the mean squared displacement.  Under a ``FlowObjective`` term s runs
+        from frame s + 1 to P0_s.  Under ``PredictionFlow`` term s runs from P0_{s-1} to P0_s, the predictions of frames s and
+        s + 1: its truth is the motion from frame s to frame s + 1, which is flow[:, s] of a video's flow [n, T - 1, 2, H, W], so that
+        array is passed as it is.  ``check_flow_target`` states the rules (ValueError)."""
+        if isinstance(flow_target, FlowObjective) and flow is None:     # `flow` was the positional argument here before `flow_target` existed
+            flow_target, flow = None, flow_target
         if frame_grads not in FRAME_GRADS:
             raise ValueError("frame_grads must be None, 'frames' or 'tied', got %r" % (frame_grads,))
         if flow_terms and objective != "flow":
@@ -912,7 +976,7 @@ class PredNetTrainer:
         _check_flow(objective, flow)
         d, n, T, n_fed, bstride = self._call_args(frames, n_fed)
         value, table, d_pred, d_grad = self._loss_grad(d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights,
-                                                       layer_errors, frame_grads, flow=flow)
+                                                       layer_errors, frame_grads, flow=flow, flow_target=flow_target)
         out = (value,) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table,) if layer_errors else ()) + ((d_grad.cpu().numpy(),) if frame_grads else ())
         out += (self.last_flow_terms,) if flow_terms else ()
         return out[0] if len(out) == 1 else out
@@ -944,7 +1008,7 @@ class PredNetTrainer:
                                                    ctypes.c_int32(n), ctypes.byref(mem), _ptr(d_mask), _ptr(planes), _ptr(counts), None))
         return planes, counts
 
-    def flow_term(self, pred, ref, flow, scale=1.0, reference_grad=False, stats=False):
+    def flow_term(self, pred, ref, flow, scale=1.0, reference_grad=False, stats=False, target=None):
         """The flow stage alone (eigen_trainer_flow_term), with the kernels a training call runs: pred float32 [n, C, H, W], the
         prediction; ref uint8 [n, C, H, W], the reference frame; n <= batch.  -> (value, u, seed): the term, the flow float64
         [n, 2, H, W] in pixels per frame (x then y) and scale * d value / d pred as float32 [n, C, H, W].  reference_grad=True
@@ -952,8 +1016,10 @@ class PredNetTrainer:
         [n, C, H, W]: what a training call adds to the frame gradient under reference="moving".  The FlowObjective's own `reference`
         plays no part here.  With a ``FlowScore`` on `flow` the stage runs in the score mode (eigen_trainer_flow_term_score), and
         stats=True (score only) appends the float64 [n, 10] record of the samples, ``SCORE_STATS``; either way a score-mode call
-        leaves it in ``self.last_flow_stats`` (None after a call without a score)."""
-        return self._flow_stage(pred, ref, False, flow, scale, reference_grad, stats)
+        leaves it in ``self.last_flow_stats`` (None after a call without a score).
+        target: None, or float64 [n, 2, H, W] (eigen_trainer_flow_term_target): the value is then the mean squared endpoint error of u
+        against it (``check_flow_target``)."""
+        return self._flow_stage(pred, ref, False, flow, scale, reference_grad, stats, target)
 
     def flow_term_pair(self, pred, prev, flow, scale=1.0, reference_grad=False):
         """The flow stage alone on a pair of float images (eigen_trainer_flow_term_pair), with the kernels a training call runs under a
@@ -961,10 +1027,18 @@ class PredNetTrainer:
         prediction); n <= batch.  -> (value, u, seed) as ``flow_term``; reference_grad=True appends scale * d value / d prev, float32
         [n, C, H, W]: what a training call adds to d loss / d P0_{s-1}.  The radius, eps, direction and mask of `flow` are used; its
         pairing and `reference` play no part here.  With a score on `flow` the stage runs in the score mode and leaves the float64
-        [n, 10] record of the samples in ``self.last_flow_stats``."""
+        [n, 10] record of the samples in ``self.last_flow_stats``.  ``flow_term_pair_target`` is this stage against a target field."""
         return self._flow_stage(pred, prev, True, flow, scale, reference_grad)
 
-    def _flow_stage(self, pred, ref, float_ref, flow, scale, reference_grad, stats=False):
+    def flow_term_pair_target(self, pred, prev, flow, target, scale=1.0, reference_grad=False):
+        """``flow_term_pair`` against a target field (eigen_trainer_flow_term_target with a float reference), the stage a training call
+        runs under a ``PredictionFlow`` and ``flow_target=``: target float64 [n, 2, H, W] as ``flow_term``'s; the value is the mean
+        squared endpoint error of u against it.  (``flow_term_pair`` keeps its parameter list; ``flow_term`` takes `target` itself.)"""
+        if target is None:
+            raise ValueError("flow_term_pair_target needs a target field; flow_term_pair is the stage without one")
+        return self._flow_stage(pred, prev, True, flow, scale, reference_grad, target=target)
+
+    def _flow_stage(self, pred, ref, float_ref, flow, scale, reference_grad, stats=False, target=None):
         """flow_term (float_ref False: a uint8 reference) and flow_term_pair (True: a float32 one): the upload, the checks, the buffers,
         the one call and the result tuple"""
         torch = self._torch
@@ -982,6 +1056,7 @@ class PredNetTrainer:
             raise ValueError(("pred and prev must be float32, both" if float_ref else "pred must be float32 and ref uint8, both") + " [n, %d, %d, %d]; got %s %s and %s %s"
                              % (shp + (p.dtype, tuple(p.shape), r.dtype, tuple(r.shape))))
         n, per = int(p.shape[0]), int(np.prod(shp))
+        d_target, t_strides = self._target("flow", flow, target, (n, 2, self.h, self.w))
         d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w)
         value = ctypes.c_double(0.0)
         u = torch.empty((n, 2, self.h, self.w), dtype=torch.float64, device=dev)
@@ -990,6 +1065,15 @@ class PredNetTrainer:
         cfg = flow.settings(stage_alone=True)
         self.last_flow_stats = None
         solve = flow.solve_on(self.w, self.h)       # the coarsest-level rule, before the call
+        if d_target is not None:
+            # eigen_trainer_flow_term_target: the iter entry's arguments (no score or members go with a target), the solve (NULL: the single
+            # step), then the target
+            _check(self.lib.eigen_trainer_flow_term_target(
+                self._h, _ptr(p), ctypes.c_int64(per), None if float_ref else _ptr(r), _ptr(r) if float_ref else None, ctypes.c_int64(per), ctypes.c_int32(n),
+                ctypes.byref(cfg), _ptr(d_mask), None, None, None, ctypes.c_double(float(scale)), ctypes.byref(value), None, _ptr(u), _ptr(seed), ctypes.c_int64(per),
+                _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None, None, ctypes.byref(solve) if solve is not None else None, _ptr(d_target), *t_strides))
+            out = (value.value, u.cpu().numpy(), seed.cpu().numpy())
+            return out + (rg.cpu().numpy(),) if reference_grad else out
         if solve is not None:
             # eigen_trainer_flow_term_iter: every mode through one entry, the solve behind the stream
             sc = flow.score.settings(self.h) if flow.score is not None else None
@@ -1110,17 +1194,23 @@ class PredNetTrainer:
         _check(self.lib.eigen_trainer_adam_ex(self._h, ctypes.byref(cfg), ctypes.byref(rep), _stream_arg(stream)))
         self.last_update = {"norm": rep.norm, "rate": rep.rate, "applied": int(rep.applied)}
 
-    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None, objective="mse", layer_weights=None, micro_batches=1, flow=None):
+    def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None, objective="mse", layer_weights=None, micro_batches=1, flow_target=None,
+             flow=None):
         """Gradient and one Adam step; returns the loss before the step.  (`flow` stays the last argument, as in every call that takes
         one; it was the eighth positional one before `micro_batches` existed, and such a call still means it.)
 
         micro_batches = k > 1: the n sequences are cut into k equal chunks in order, each runs ``forward_backward`` with reset=True and is
         added to the accumulator with scale 1 / k, the sum becomes the gradient and ONE Adam step is taken.  Every objective is a mean
         over the samples, so in real arithmetic that is the full batch's gradient: a handle of batch n / k trains a logical batch of n.
-        The loss returned is sum_j loss_j / k, formed in double in chunk order.  ``check_micro_batches`` states the rules (ValueError)."""
+        The loss returned is sum_j loss_j / k, formed in double in chunk order.  ``check_micro_batches`` states the rules (ValueError).
+        flow_target: ``forward_backward``'s; with micro_batches = k it is sliced along n with the frames."""
         if isinstance(micro_batches, FlowObjective) and flow is None:
             micro_batches, flow = 1, micro_batches
+        if isinstance(flow_target, FlowObjective) and flow is None:
+            flow_target, flow = None, flow_target
         kw = dict(n_fed=n_fed, requant=requant, step_weights=step_weights, objective=objective, layer_weights=layer_weights, flow=flow)
+        if flow_target is not None:
+            kw["flow_target"] = flow_target
         if micro_batches == 1 and not isinstance(micro_batches, bool):     # the call as it always was: the accumulator is not touched
             loss = self.forward_backward(frames, reset, **kw)
             self.adam()
@@ -1133,14 +1223,17 @@ class PredNetTrainer:
     def accumulate_micro_batches(self, frames, micro_batches, reset=True, **kw):
         """The gradient half of ``step(micro_batches=k)``: empties the accumulator, runs the k chunks of `frames` and adds each with scale
         1 / k; -> sum_j loss_j / k.  ``load_accumulated()`` then makes the sum the gradient.  kw: ``forward_backward``'s n_fed, requant,
-        step_weights, objective, layer_weights and flow."""
+        step_weights, objective, layer_weights, flow and flow_target (sliced along n with the frames)."""
+        kw = dict(kw)
+        target = kw.pop("flow_target", None)
         d = self._frames(frames)
         m = check_micro_batches(int(d.shape[0]), micro_batches, self.batch, reset, kw.get("flow"))
         k = int(micro_batches)
         self.clear_accumulated()
         total = 0.0
         for j in range(k):
-            total += float(self.forward_backward(d[j * m:(j + 1) * m], True, **kw))
+            chunk = {} if target is None else {"flow_target": target[j * m:(j + 1) * m]}
+            total += float(self.forward_backward(d[j * m:(j + 1) * m], True, **kw, **chunk))
             self.accumulate(1.0 / k)
         return total / k
 
@@ -1208,6 +1301,19 @@ class PredNetTrainer:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def flow_epe(trainer, pred, prev_or_ref, flow, target):
+    """The mean squared endpoint error of the flow `flow` solves from prev_or_ref to pred against `target`, on the device: the value of
+    the stage alone under a target field (``PredNetTrainer.flow_term`` for a uint8 reference, ``flow_term_pair_target`` for a float32 one; float64
+    target [n, 2, H, W]), the metric form of what ``forward_backward(flow_target=)`` trains on.  The mean runs over the samples and the
+    pixels the objective's shared mask counts."""
+    if target is None:
+        raise ValueError("flow_epe needs a target field")
+    by_float = str(getattr(prev_or_ref, "dtype", "")) in ("float32", "torch.float32")
+    if by_float:
+        return trainer.flow_term_pair_target(pred, prev_or_ref, flow, target)[0]
+    return trainer.flow_term(pred, prev_or_ref, flow, target=target)[0]
 
 
 def _still_call(trainer, n_repeat, n_ext, iters, requant, objective, layer_weights, flow):

@@ -38,6 +38,20 @@ def add_flow_arguments(ap, names=tuple(FLOW_ARGUMENTS), **own):
         ap.add_argument("--flow-" + name, **dict(FLOW_ARGUMENTS[name], **own.get(name, {})))
 
 
+def add_flow_target_argument(ap):
+    """--flow-target of the scripts that train on videos with a known flow (examples/train_prednet.py, scripts/train_bench.py); a still
+    has no truth, so the refinement scripts do not take it"""
+    ap.add_argument("--flow-target", default="none", choices=["none", "truth"],
+                    help="objective flow: truth makes every term the squared endpoint error of the solved field against the exact flow of the video "
+                         "(train.MovingTextures' own, so it needs --data textures) in place of the mean squared displacement")
+
+
+def check_flow_target(ap, a):
+    """--flow-target truth without --data textures is an argparse error: no other source states its flow"""
+    if a.flow_target == "truth" and getattr(a, "data", None) != "textures":
+        ap.error("--flow-target truth needs --data textures: no other source states the flow of its frames")
+
+
 def score_of(a):
     """the score of the command line: None without --flow-score; else the class of --flow-score-structure (auto: of a.structure), with
     --flow-max-norm where it is given"""

@@ -4,6 +4,7 @@ result in the fitness path.
 
     python examples/train_prednet.py -o trained.npz [-i frames_dir] [--size 160x120] [-c 3] [--steps 200] [--seq 10] [--batch 8]
                                      [--data rings|textures [--texture-layers 1|2]] [--loss mse|l0|lall]
+                                     [--objective flow [--flow-pairing prediction] [--flow-radius 7] ... [--flow-target truth]]
                                      [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K]
                                      [--ext-steps 200 --ext-frames 4 [--requant]] [--checkpoint ckpt.npz [--every 50]] [--resume ckpt.npz]
 
@@ -19,6 +20,11 @@ mse, the squared error of the prediction; l0, the mean of the image layer's erro
 lall, L_0 plus the error units of the upper layers at weight 0.1 (L_all).  Prints the held-out per-step squared errors and the
 mean error units of every layer (tape-free `evaluate`) before and after, writes the weights as a chainer npz (-o), then evaluates one synthetic population's
 fitness with them.
+--objective flow trains on the dense motion objective of the --flow-* options in place of --loss (train.make_flow; examples/flow_args.py
+lists them).  With --data textures --flow-target truth every term is the squared endpoint error of the solved field against the exact flow
+of the video (``forward_backward(flow_target=)``): under --flow-pairing prediction "the flow between consecutive predictions shall be the
+true flow", on the self-fed steps too.  The per-term values of the printed steps are printed with the loss.  With --data textures the
+held-out mean squared endpoint error between consecutive predictions (train.flow_epe) is printed before and after, whatever the objective.
 --clip-norm, --weight-decay and --skip-nonfinite are the trainer's optimiser controls (gradient clipping at a global norm, chainer's weight
 decay, leaving out a step whose gradient is not finite); --micro-batches K keeps --batch as the logical batch of a step and runs it as K
 chunks on a handle of --batch / K, so the tape is K times smaller.  At the steps whose loss is printed the global gradient norm is printed
@@ -33,7 +39,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 from evolutionary_illusion_generator_amd import fitness, grids, synth, weights
-from evolutionary_illusion_generator_amd.train import MovingTextures, PredNetTrainer, check_micro_batches, check_optim
+from evolutionary_illusion_generator_amd.train import MovingTextures, PredictionFlow, PredNetTrainer, check_micro_batches, check_optim, flow_epe
+from examples.flow_args import add_flow_arguments, add_flow_target_argument, check_flow_target, flow_of
 
 
 def read_windows(folder, c_dim, w, h, seq):
@@ -57,6 +64,15 @@ def drifting(seed, n, seq, c_dim, w, h):
     return out
 
 
+def held_out_epe(tr, frames, truth, radius, eps, n_fed, requant):
+    """float64 [T - 2]: the mean squared endpoint error of the flow from prediction s - 1 to prediction s against the video's own flow
+    from frame s to frame s + 1, for s = 1 .. T - 2 (term 0 has no previous prediction), on the device (train.flow_epe)"""
+    import torch
+    pred = torch.from_numpy(tr.evaluate(frames, n_fed=n_fed, requant=requant, pred=True)[1])
+    flow = PredictionFlow(radius, eps)
+    return np.array([flow_epe(tr, pred[:, s], pred[:, s - 1], flow, truth[:, s]) for s in range(1, pred.shape[1] - 1)])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--input", "-i", default=None, help="folder of PNG frames (default: seeded drifting patterns)")
@@ -72,6 +88,9 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--alpha", type=float, default=1e-3)
     ap.add_argument("--loss", default="mse", choices=["mse", "l0", "lall"], help="objective: squared error, or the error units (L_0 / L_all)")
+    ap.add_argument("--objective", default="loss", choices=["loss", "flow"], help="loss: the objective of --loss; flow: the dense motion objective of the --flow-* options")
+    add_flow_arguments(ap)
+    add_flow_target_argument(ap)
     ap.add_argument("--ext-steps", type=int, default=0, help="Adam steps of a second phase whose last --ext-frames steps are self-fed")
     ap.add_argument("--ext-frames", type=int, default=4, help="self-fed steps at the end of every sequence in the second phase")
     ap.add_argument("--requant", action="store_true", help="feed predictions back through the emitted byte (cfg.requant_feedback)")
@@ -83,6 +102,9 @@ def main():
     ap.add_argument("--skip-nonfinite", action="store_true", help="leave out a step whose gradient norm is not finite")
     ap.add_argument("--micro-batches", type=int, default=1, help="run a step's --batch sequences as K chunks on a handle of --batch / K")
     args = ap.parse_args()
+    check_flow_target(ap, args)
+    if args.flow_target == "truth" and args.objective != "flow":
+        ap.error("--flow-target truth is a mode of --objective flow")
     w, h = (int(v) for v in args.size.lower().split("x"))
     channels = [int(c) for c in args.channels.split(",")] if args.channels else [args.color_space, 48, 96, 192]
     c_dim = channels[0]
@@ -111,6 +133,21 @@ def main():
     total = args.steps + args.ext_steps
     fmt = lambda v: " ".join("%.5f" % x for x in v)
     obj = {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(channels) - 1))}[args.loss]
+    try:
+        flow = flow_of(args, w, h)
+    except ValueError as e:
+        ap.error(str(e))
+    if flow is not None:
+        obj = dict(objective="flow", flow=flow)
+    name = "flow" if flow is not None else args.loss
+    truth = args.flow_target == "truth"
+
+    def step_inputs(k):
+        """the frames of step k and, under --flow-target truth, their exact flow as the step's target"""
+        if not truth:
+            return batch_of(k), {}
+        frames, fl, _ = source.batch(k, args.batch, flow=True)
+        return frames, dict(flow_target=fl)
 
     try:
         optim = check_optim(args.clip_norm, args.weight_decay, args.skip_nonfinite)
@@ -128,13 +165,21 @@ def main():
         before, err_before = tr.evaluate(held[:chunk], n_fed=n_fed, requant=args.requant, layer_errors=True)
         print("held-out loss per step (%d fed, %d self-fed) before: %s" % (n_fed, args.seq - n_fed, fmt(before)))
         print("held-out error units per layer (mean over the steps; layer 0 is the L_0 error) before: %s" % fmt(err_before.mean(0)))
+        if args.data == "textures" and not args.input:
+            held_flow = source.batch(10 ** 6, args.batch, flow=True)[1]
+            epe = lambda: held_out_epe(tr, held[:chunk], held_flow[:chunk], args.flow_radius, args.flow_eps, n_fed, args.requant)
+            epe_before = epe()
+            print("held-out squared endpoint error between consecutive predictions (terms 1 .. %d) before: %s" % (args.seq - 2, fmt(epe_before)))
         for k in range(first, total):
+            frames, extra = step_inputs(k)
             if k < args.steps:
-                loss = tr.step(batch_of(k), **obj)
+                loss = tr.step(frames, **extra, **obj)
             else:
-                loss = tr.step(batch_of(k), n_fed=n_fed, requant=args.requant, step_weights=ext_w if any(ext_w) else None, **obj)
+                loss = tr.step(frames, n_fed=n_fed, requant=args.requant, step_weights=ext_w if any(ext_w) else None, **extra, **obj)
             if k % 50 == 0 or k == total - 1 or k == args.steps:
-                print("step %4d  %s train loss (%s) %.6f" % (k, "teacher-forced" if k < args.steps else "self-fed      ", args.loss, loss))
+                print("step %4d  %s train loss (%s) %.6f" % (k, "teacher-forced" if k < args.steps else "self-fed      ", name, loss))
+                if flow is not None:     # the terms the library returned (h_terms); with micro-batches those of the step's last chunk
+                    print("           flow terms%s: %s" % (" (last micro-batch)" if args.micro_batches > 1 else "", " ".join("%.6f" % v for v in tr.last_flow_terms)))
                 # the gradient this step applied (with micro-batches: the accumulated one), before clipping
                 norm, per = tr.grad_norms()
                 dead = [n for n, v in per.items() if v == 0.0]
@@ -143,6 +188,11 @@ def main():
             if args.checkpoint and ((k + 1) % args.every == 0 or k == total - 1):
                 tr.save_checkpoint(args.checkpoint)
         after, err_after = tr.evaluate(held[:chunk], n_fed=n_fed, requant=args.requant, layer_errors=True)
+        if args.data == "textures" and not args.input:
+            epe_after = epe()
+            print("held-out squared endpoint error between consecutive predictions after:  %s" % fmt(epe_after))
+            print("held-out squared endpoint error, mean over the terms: %.6f before, %.6f after (%.1f %% lower)"
+                  % (epe_before.mean(), epe_after.mean(), 100 * (1 - epe_after.mean() / epe_before.mean())))
         trained = tr.weights()
     print("held-out loss per step after:  %s" % fmt(after))
     print("held-out error units per layer after:  %s" % fmt(err_after.mean(0)))

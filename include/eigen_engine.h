@@ -931,6 +931,36 @@ int eigen_trainer_loss_grad_flow_iter(eigen_trainer* t, const uint8_t* d_frames,
  * iterated call. */
 int eigen_trainer_debug_flow_iter(eigen_trainer* t, int32_t force, int64_t* workspace_bytes);
 
+/* ---- The flow objective against a target field ("The target field"): a third displacement mode, the squared
+ * endpoint error of the solved field u against a per-call field, in u's own sign convention (content at x in the reference is at x + u in
+ * the prediction; eigen_render_moving_cppn states its flow the same way).  Float64, one IEEE operation per operation written:
+ *   ex = ux - tx, ey = uy - ty, v = ex ex + ey ey, g = (2 ex, 2 ey); where the mask does not count the pixel v = 0 and g = 0
+ * and the term is sum(v) / (B N_m) through the displacement modes' own fixed-order reduction; kappa keeps their divisor.  q is formed from
+ * g over the solve's a, b, c and det in the solve's written formula; the seed, the reference gradient, the moving reference, both pairings
+ * and the gradient through an iterated solve are the other displacement modes'.  The target is device data and is not inspected: a
+ * non-finite element propagates.
+ *
+ * eigen_trainer_flow_term_target: eigen_trainer_flow_term_iter's arguments plus d_target, doubles [B][2][H W], sample b at
+ * d_target + b * t_bstride.  eigen_trainer_loss_grad_flow_target: eigen_trainer_loss_grad_flow_iter's arguments plus d_target, t_bstride
+ * and t_tstride: term s (prediction P0_s) reads d_target + b * t_bstride + s * t_tstride.  d_target NULL: the call is its _iter namesake,
+ * launch for launch and bit for bit, the strides are not read and nothing is allocated.
+ * Errors: the namesakes'; EIGEN_ERR_INVALID before any launch or allocation for a target together with score, sscore, members or d_dir,
+ * for t_bstride < 2 H W, for t_tstride < 2 H W when n_steps > 2, and for a target under an objective other than EIGEN_OBJ_FLOW. */
+int eigen_trainer_flow_term_target(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref,
+                                   int64_t r_bstride, int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask,
+                                   const eigen_flow_score* score, const eigen_flow_structure_score* sscore, const eigen_flow_members* members,
+                                   double scale, double* h_value, double* h_stats, double* d_flow, float* d_seed, int64_t s_bstride,
+                                   float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir, const eigen_dense_solve* solve,
+                                   const double* d_target, int64_t t_bstride);
+int eigen_trainer_loss_grad_flow_target(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                        int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                        const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                        int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                        const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score,
+                                        const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double* h_stats,
+                                        void* stream, const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride,
+                                        int64_t t_tstride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ the tape-free evaluate of that call.  Prints one JSON line per side and writes p
     python scripts/train_bench.py [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K] [--side trainer]
     python scripts/train_bench.py --optim-cost [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K]
     python scripts/train_bench.py --data textures [--texture-layers 1|2] [--steps 5] [--warmup 2]
+    python scripts/train_bench.py --flow-cost --data textures --flow-target truth [--flow-pairing prediction] [--flow-levels 3 --flow-iters 3]
 
 --objective times the trainer step under the error-unit objective instead (L_0, or L_all with the upper layers at 0.1); the torch
 side is always the squared error.  --frame-grads times that leg alone: one loss_grad call (no Adam) without frame gradients, with
@@ -29,6 +30,9 @@ and weight_decay 0.01) and micro-batches (K, at least 2); one JSON line each wit
 --data textures (the default, rings, is every run above) times the device frame source train.MovingTextures at this shape: one
 batch(k, 16) with one and with two layers (its host part, describe, also alone), the host drifting() call of examples/train_prednet.py
 it replaces, and the trainer step fed by batch() of --texture-layers; one JSON line each.
+--flow-target truth (with --data textures) reads the frames from train.MovingTextures and makes their exact flow the target of the flow objective
+(forward_backward(flow_target=)); --flow-cost then times the "flow" call of the pairing asked for without and with the target
+("flow_target"; under a real solve also "flow_iter_target"), alternated like the other legs; without --flow-cost the timed step trains on it.
 """
 import argparse
 import json
@@ -42,7 +46,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from examples.flow_args import add_flow_arguments, members_of, score_of  # noqa: E402
+from examples.flow_args import add_flow_arguments, add_flow_target_argument, check_flow_target, members_of, score_of  # noqa: E402
 
 W, H, CH, B, T = 160, 120, [3, 48, 96, 192], 16, 10
 GATES = ("i", "f", "c", "o")
@@ -83,7 +87,14 @@ def objective_args(name, reference="constant", pairing="frame", score=None, memb
     return {"mse": {}, "l0": dict(objective="error"), "lall": dict(objective="error", layer_weights=[1.0] + [0.1] * (len(CH) - 1))}[name]
 
 
-def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None, members=None, levels=1, iters=1):
+def texture_frames():
+    """(frames uint8 [B, T, C, H, W], their exact flow float64 [B, T - 1, 2, H, W]) of train.MovingTextures, on the device"""
+    from evolutionary_illusion_generator_amd.train import MovingTextures
+    with MovingTextures(W, H, CH[0], T) as src:
+        return src.batch(0, B, flow=True)[:2]
+
+
+def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None, members=None, levels=1, iters=1, target=False):
     """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round; with
     the moving reference also per "flow" call with tied frame gradients, under either reference; with a real solve (levels, iters) also per
     "flow" call of the same settings whose gradient runs through that solve ("flow_iter")"""
@@ -104,6 +115,14 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"
         calls["flow_score_corners"] = objective_args("flow", reference, pairing, score, members)
     if (levels, iters) != (1, 1):
         calls["flow_iter"] = objective_args("flow", reference, pairing, score, members, levels, iters)
+    if target:
+        # the frames of the device source and their exact flow: the call of the pairing asked for without and with the target
+        d, truth = texture_frames()
+        calls = {"mse": calls["mse"], "flow": objective_args("flow", reference, pairing)}
+        calls["flow_target"] = dict(calls["flow"], flow_target=truth)
+        if (levels, iters) != (1, 1):
+            calls["flow_iter"] = objective_args("flow", reference, pairing, levels=levels, iters=iters)
+            calls["flow_iter_target"] = dict(calls["flow_iter"], flow_target=truth)
     ms = {k: [] for k in calls}
     loss = {}
     with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
@@ -204,7 +223,7 @@ def run_data(steps, warmup, layers=1, rounds=6):
 
 
 def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None, members=None, optim=(None, 0.0, False), micro_batches=1, levels=1,
-                iters=1):
+                iters=1, target=False):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
@@ -214,6 +233,9 @@ def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="f
     tr = PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B // micro_batches, T, clip_norm=optim[0], weight_decay=optim[1],
                         skip_nonfinite=optim[2])
     kw = dict(kw, micro_batches=micro_batches)
+    if target:
+        d, truth = texture_frames()
+        kw["flow_target"] = truth
     for _ in range(warmup):
         tr.step(d, **kw)
     torch.cuda.synchronize()
@@ -349,6 +371,7 @@ def main():
     ap.add_argument("--flow-cost", action="store_true", help="time one loss_grad call under mse and under flow, alternated, and exit")
     add_flow_arguments(ap, ("reference", "pairing", "score", "score-structure", "max-norm", "members", "corner-quality", "corner-distance", "levels", "iters"), **{"score-structure": dict(choices=["circles", "bands", "free"])}, reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
                        pairing=dict(help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)"))
+    add_flow_target_argument(ap)
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--clip-norm", type=float, default=None, help="the trainer's clip_norm (default: no clipping)")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="the trainer's weight_decay")
@@ -360,6 +383,12 @@ def main():
     ap.add_argument("--torch-timeout", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_bench.json"))
     a = ap.parse_args()
+    check_flow_target(ap, a)
+    target = a.flow_target == "truth"
+    if target and not a.flow_cost and a.objective != "flow":
+        ap.error("--flow-target truth is a mode of --objective flow (or of --flow-cost)")
+    if target and (a.flow_score or a.flow_members != "all"):
+        ap.error("--flow-target truth takes no --flow-score and no --flow-members")
     if a.flow_pairing == "prediction" and a.flow_reference == "moving":
         ap.error("--flow-pairing prediction has no frame as a reference: it does not take --flow-reference moving")
     score = score_of(a)
@@ -370,7 +399,7 @@ def main():
     if a.side == "torch":
         print(json.dumps(run_torch(a.steps, a.warmup)))
         return
-    if a.data == "textures":
+    if a.data == "textures" and not target:
         for r in run_data(a.steps, a.warmup, a.texture_layers):
             print(json.dumps(r), flush=True)
         return
@@ -379,7 +408,8 @@ def main():
             print(json.dumps(r), flush=True)
         return
     if a.flow_cost:
-        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score, members=members, levels=a.flow_levels, iters=a.flow_iters):
+        for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score, members=members, levels=a.flow_levels, iters=a.flow_iters,
+                               target=target):
             print(json.dumps(r), flush=True)
         return
     from evolutionary_illusion_generator_amd.train import check_micro_batches, check_optim
@@ -392,7 +422,7 @@ def main():
         for r in run_optim_cost(a.steps, a.warmup, clip_norm=optim[0], weight_decay=optim[1], skip_nonfinite=optim[2], micro_batches=max(a.micro_batches, 2)):
             print(json.dumps(r), flush=True)
         return
-    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members, optim, a.micro_batches, a.flow_levels, a.flow_iters)]
+    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members, optim, a.micro_batches, a.flow_levels, a.flow_iters, target)]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
