@@ -22,6 +22,7 @@
 #include "cppn_kernel.h"
 #include "cppn_grad_kernel.h"
 #include "cppn_motion_kernel.h"
+#include "cppn_valid_kernel.h"
 #include "farneback_kernels.h"
 #include "flow_kernels.h"
 #include "score_kernels.h"
@@ -115,6 +116,8 @@ struct eigen_engine {
     DevBuf<double> g_grad_slabs, g_grad_sum;   // eigen_cppn_param_grads: one slab per pixel block, and their sum
     DevBuf<double> g_affine;                   // eigen_render_moving_cppn: every affine beside its inverse
     std::vector<double> h_affine;              // ... as packed on the host (kept: the upload is asynchronous)
+    DevBuf<double> g_valid_affine;             // eigen_moving_cppn_valid: the same records, in buffers of its own (a render may be in flight)
+    std::vector<double> h_valid_affine;
     // images / frames
     uint8_t* d_images = nullptr;  // [B][C0][H][W]
     uint8_t* d_frames = nullptr;  // [B][3][C0][H][W]
@@ -812,6 +815,35 @@ int eigen_render_moving_cppn(eigen_engine* e, const eigen_genome_batch* g, int32
     a.frames = d_frames; a.f_bstride = f_bstride; a.flow = d_flow; a.layer = d_layer;
     (void)hipFuncSetAttribute((const void*)cppn_motion_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds);
     hipLaunchKernelGGL(cppn_motion_kernel, dim3((a.N + CPPN_THREADS - 1) / CPPN_THREADS, n), dim3(CPPN_THREADS), x.lds, st, a);
+    HIPCHK(hipGetLastError());
+    return EIGEN_OK;
+}
+
+int eigen_moving_cppn_valid(eigen_engine* e, int32_t n, int32_t n_frames, int32_t n_layers, const double* h_affine, const double* h_affine_inv, uint8_t* d_valid,
+                            void* stream)
+{
+    if (!e || !h_affine || !h_affine_inv || !d_valid) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (n_layers < 1 || n_layers > 2) return fail(EIGEN_ERR_INVALID, "n_layers %d outside 1..2", n_layers);
+    if (n_frames < 2) return fail(EIGEN_ERR_INVALID, "a validity plane needs two frames, n_frames is %d", n_frames);
+    if (n < 1) return fail(EIGEN_ERR_INVALID, "n %d < 1", n);
+    if (n > 65535) return fail(EIGEN_ERR_CAPACITY, "n %d exceeds the 65535 samples of one launch", n);
+    HIPCHK(hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    // the packed records of eigen_render_moving_cppn: the affine, then its inverse
+    const size_t n_aff = (size_t)n * n_frames * n_layers;
+    std::vector<double>& packed = e->h_valid_affine;
+    packed.resize(n_aff * 12);
+    for (size_t i = 0; i < n_aff; ++i) {
+        std::copy(h_affine + i * 6, h_affine + i * 6 + 6, packed.begin() + i * 12);
+        std::copy(h_affine_inv + i * 6, h_affine_inv + i * 6 + 6, packed.begin() + i * 12 + 6);
+    }
+    if (e->g_valid_affine.ensure(n_aff * 12)) return fail(EIGEN_ERR_HIP, "hipMalloc for the affines failed");
+    HIPCHK(hipMemcpyAsync(e->g_valid_affine.p, packed.data(), sizeof(double) * n_aff * 12, hipMemcpyHostToDevice, st));
+    CppnValidArgs a;
+    a.affine = e->g_valid_affine.p;
+    a.W = e->W; a.H = e->H; a.N = e->H * e->W; a.T = n_frames; a.L = n_layers;
+    a.valid = d_valid;
+    hipLaunchKernelGGL(cppn_valid_kernel, dim3((a.N + CPPN_THREADS - 1) / CPPN_THREADS, n), dim3(CPPN_THREADS), 0, st, a);
     HIPCHK(hipGetLastError());
     return EIGEN_OK;
 }

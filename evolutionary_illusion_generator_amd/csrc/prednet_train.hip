@@ -28,6 +28,7 @@
 #include "dense_stage.h"
 #include "flow_iter_kernels.h"
 #include "flow_target_kernels.h"
+#include "flow_valid_kernels.h"
 
 using namespace eigt;
 
@@ -124,6 +125,8 @@ struct eigen_trainer {
     float *c_eig = nullptr, *c_corners = nullptr;
     unsigned long long* c_cand = nullptr;
     int* c_count = nullptr;
+    // the validity planes' (flow_valid_kernels.h): r_b of the current term [B]; the joint objective's: the squared error of every step [max_steps]
+    double *f_vr = nullptr, *d_jstep = nullptr;
     double* f_stats = nullptr;  // the records of a training call's terms [max_steps][max_batch][SCORE_REC], made by the first call that asks for them
     // the optimiser controls' (optim_kernels.h): the (offset, count) of every tensor [n_tensors][2], the partials of the sums of squares
     // [n_tensors][NORM_SLICES], the sums [n_tensors] and the global norm [1]; the gradient accumulator [n_params], made by the first
@@ -308,6 +311,8 @@ int allocate(eigen_trainer* t)
     const Table tab = tensor_table(t);
     const long long nt = t->n_tensors = (int)tab.size();
     add((void**)&t->o_tab, nt * 16); add((void**)&t->o_part, nt * NORM_SLICES * 8); add((void**)&t->o_sumsq, nt * 8); add((void**)&t->o_norm, 8);
+    // and last the validity planes' r_b and the joint objective's squared-error steps
+    add((void**)&t->f_vr, B * 8); add((void**)&t->d_jstep, T * 8);
     for (auto& w : want) {
         const hipError_t e = hipMalloc(w.first, w.second);
         if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%zu): %s", w.second, hipGetErrorString(e));
@@ -466,6 +471,8 @@ struct FlowSpec {
     // the target field of the third displacement mode (flow_target_kernels.h; null: none), doubles: sample b of term s at
     // + b * bstride + s * tstride as [2][H W]
     struct Target { const double* p = nullptr; long long bstride = 0, tstride = 0; } target;
+    // the validity planes under a target (flow_valid_kernels.h; null: none), bytes: sample b of term s at + b * bstride + s * tstride as [H W]
+    struct Valid { const uint8_t* p = nullptr; long long bstride = 0, tstride = 0; } valid;
     // what divides a term's scale in kappa: B N_m, or B in the score mode, whose value is a mean over the samples alone
     double kappa_div(int B) const { return by_score || by_struct ? (double)B : (double)(B * n_mask); }
 };
@@ -685,6 +692,7 @@ struct FlowTerm {
     float* d_seed = nullptr; long long s_bstride = 0; int s_accumulate = 0;   // kappa d value / d pred, added in float or stored
     float* d_refg = nullptr; long long rg_bstride = 0; int rg_accumulate = 0; // kappa d value / d reference (flow_ref_kernels.h), likewise
     const double* target = nullptr;                                           // this term's target field (null: none), sample b at + b * FlowSpec's target.bstride
+    const uint8_t* valid = nullptr;                                           // this term's validity planes (null: none), sample b at + b * FlowSpec's valid.bstride
 };
 
 // A target field's rules, before anything is launched or allocated (null: none, and the strides are not read): it is a displacement mode
@@ -699,6 +707,19 @@ int check_flow_target(const eigen_trainer* t, const double* d_target, long long 
     if (t_bstride < field) return tfail(EIGEN_ERR_INVALID, "t_bstride %lld is smaller than one field (%lld doubles)", t_bstride, field);
     if (n_terms > 1 && t_tstride < field) return tfail(EIGEN_ERR_INVALID, "t_tstride %lld is smaller than one field (%lld doubles)", t_tstride, field);
     f.target.p = d_target; f.target.bstride = t_bstride; f.target.tstride = t_tstride;
+    return EIGEN_OK;
+}
+
+// The validity planes' rules, after check_flow_target and before anything is launched or allocated (null: none, and the strides are not
+// read): they weigh a target's endpoint error, and a sample's [H W] bytes must fit their strides.
+int check_flow_valid(const eigen_trainer* t, const uint8_t* d_valid, long long v_bstride, long long v_tstride, int n_terms, FlowSpec& f)
+{
+    if (!d_valid) return EIGEN_OK;
+    if (!f.target.p) return tfail(EIGEN_ERR_INVALID, "validity planes go with a flow target only");
+    const long long HW = t->ly[0].HW;
+    if (v_bstride < HW) return tfail(EIGEN_ERR_INVALID, "v_bstride %lld is smaller than one plane (%lld bytes)", v_bstride, HW);
+    if (n_terms > 1 && v_tstride < HW) return tfail(EIGEN_ERR_INVALID, "v_tstride %lld is smaller than one plane (%lld bytes)", v_tstride, HW);
+    f.valid.p = d_valid; f.valid.bstride = v_bstride; f.valid.tstride = v_tstride;
     return EIGEN_OK;
 }
 
@@ -874,6 +895,20 @@ void iter_store(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, bool
     ew(st, tfiter_store_kernel, n, (const double*)(by_ref ? pl.lv[0].I0b : pl.lv[0].I1b), kappa, y.C, y.HW, n, out, bstride, accumulate);
 }
 
+// mv and g of the target mode from the field u, for either solve: tflow_target_kernel, or under the term's validity planes the samples'
+// counts and tflow_target_valid_kernel (flow_valid_kernels.h)
+void target_value(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m, const double* u)
+{
+    const TLayer& y = t->ly[0];
+    const long long n = (long long)B * y.HW;
+    if (!m.valid) {
+        ew(st, tflow_target_kernel, n, u, m.target, f.target.bstride, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
+        return;
+    }
+    hipLaunchKernelGGL(tflow_valid_count_kernel, dim3(B), dim3(EW_T), 0, st, m.valid, f.valid.bstride, f.mask, f.mask_bstride, y.HW, f.n_mask, t->f_vr);
+    ew(st, tflow_target_valid_kernel, n, u, m.target, f.target.bstride, f.mask, f.mask_bstride, m.valid, f.valid.bstride, (const double*)t->f_vr, y.HW, n, t->f_mv, t->f_g);
+}
+
 // The flow stage of one term under an iterated solve: the field of level 0 from iter_forward, the unchanged value / score kernels on it,
 // which leave g = d value / d u (masked) in f_g, then iter_backward and the level-0 stores.  The field goes to the handle's workspace
 // unless the caller wants it.
@@ -890,7 +925,7 @@ void iter_flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f,
     } else if (f.by_struct) {
         struct_stage(t, st, B, f, u, m.d_value, grads, false);
     } else {
-        if (m.target) ew(st, tflow_target_kernel, n, (const double*)u, m.target, f.target.bstride, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
+        if (m.target) target_value(t, st, B, f, m, u);
         else ew(st, tfiter_value_kernel, n, (const double*)u, f.dir, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
         if (m.d_value) {
             hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
@@ -934,7 +969,7 @@ void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, cons
         struct_stage(t, st, B, f, d_flow, m.d_value, m.d_seed || m.d_refg);
     } else if (m.target) {
         // the target mode: mv and g from the u the solve just wrote, then q from g over the solve's own a, b, c and det
-        ew(st, tflow_target_kernel, n, (const double*)d_flow, m.target, f.target.bstride, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
+        target_value(t, st, B, f, m, d_flow);
         if (m.d_seed || m.d_refg)
             hipLaunchKernelGGL(tflow_struct_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_g, n, y.H, y.W, f.r, f.eps, t->f_q);
     }
@@ -954,6 +989,8 @@ struct Objective {
     bool by_flow = false;
     FlowSpec flow;                      // by_flow
     double* h_terms = nullptr;          // by_flow: host, T - 1 terms, may be null
+    double mu = 0.0;                    // by_flow, the joint objective: the weight of the squared-error term beside the flow terms (0: none)
+    double* h_parts = nullptr;          // by_flow: host, (L_flow, L_mse) out, may be null
     bool keep_stats = false;            // by_flow with a score: the records of every computed term are kept in f_stats [T - 1][B][10]
     double weight(int s) const { return step_w ? step_w[s] : 1.0; }
     double total_weight() const { return step_w ? sum_w : (double)(T - 1); }
@@ -966,11 +1003,10 @@ struct Objective {
     // the flow objective: kappa of term s, (w_s / sum w) / (B N_m); in the score mode (w_s / sum w) / B
     double flow_kappa(int s) const { return (weight(s) / total_weight()) / flow.kappa_div(B); }
     // squared error: d loss / d P0_s = loss_scale(s) * (P0_s - x_{s+1})
-    float loss_scale(int s) const
-    {
-        if (T < 2) return 0.f;
-        return step_w ? (float)(2.0 * step_w[s] / (sum_w * (double)(B * ly[0].CHW()))) : (float)(2.0 / (double)n_terms());
-    }
+    double loss_scale64(int s) const { return step_w ? 2.0 * step_w[s] / (sum_w * (double)(B * ly[0].CHW())) : 2.0 / (double)n_terms(); }
+    float loss_scale(int s) const { return T < 2 ? 0.f : (float)loss_scale64(s); }
+    // the joint objective: mu times the squared error's scale, formed in double and rounded once
+    float joint_scale(int s) const { return T < 2 ? 0.f : (float)(mu * loss_scale64(s)); }
     // error units: d loss / d (one element of E_l of term s) = w_s lambda_l / (sum w * numel(E_l)), formed in double
     float err_scale(int s, int l) const
     {
@@ -1018,9 +1054,11 @@ int reduce_losses(eigen_trainer* t, hipStream_t st, const Objective& o, const ui
         reduce_steps(TERM_ABS, t, st, P0, d_frames + C0HW, bstride, C0HW, T - 1, B, (double)(B * 2 * C0HW), t->d_err, t->L);
         upper_errors(t, st, 1, T - 1, B, t->d_err);
     }
-    if (T < 2 || o.by_error || o.by_flow) return EIGEN_OK;  // the error objective's loss is formed from the table, the flow objective's from the terms the backward steps leave, on the host
+    // the error objective's loss is formed from the table, the flow objective's from the terms the backward steps leave, on the host; the
+    // joint objective adds the squared error as the "mse" call with the same step weights reduces it, its steps beside the terms' d_step
+    if (T < 2 || o.by_error || (o.by_flow && !(o.mu > 0.0))) return EIGEN_OK;
     if (o.step_w) {
-        reduce_steps(TERM_SQ, t, st, P0, d_frames + C0HW, bstride, C0HW, T - 1, B, (double)(B * C0HW), t->d_step, 1);
+        reduce_steps(TERM_SQ, t, st, P0, d_frames + C0HW, bstride, C0HW, T - 1, B, (double)(B * C0HW), o.by_flow ? t->d_jstep : t->d_step, 1);
     } else {
         hipLaunchKernelGGL(tloss_partial_kernel, dim3(LOSS_BLOCKS), dim3(EW_T), 0, st, (const float*)t->ly[0].P_at(0, B), d_frames, bstride, T - 1, B, C0HW, t->d_part);
         hipLaunchKernelGGL(tloss_final_kernel, dim3(1), dim3(64), 0, st, (const double*)t->d_part, LOSS_BLOCKS, 1.0 / (double)o.n_terms(), t->d_loss);
@@ -1060,6 +1098,7 @@ int backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, c
                 m.part = t->d_spart + (long long)s * STEP_LOSS_BLOCKS; m.d_value = t->d_step + s;
                 m.d_seed = y.dPn; m.s_bstride = CHW; m.s_accumulate = 1;
                 if (o.flow.target.p) m.target = o.flow.target.p + (long long)s * o.flow.target.tstride;
+                if (o.flow.valid.p) m.valid = o.flow.valid.p + (long long)s * o.flow.valid.tstride;
                 if (o.flow.pair_pred) {
                     m.fref = y.P_at(s, B); m.r_bstride = CHW;
                     m.d_flow = s >= 1 ? t->f_u : nullptr;
@@ -1073,9 +1112,10 @@ int backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, c
                     TCHK(hipMemcpyAsync(t->f_stats + (long long)s * B * SCORE_REC, o.flow.by_score ? t->f_rec : t->f_srec, (size_t)B * SCORE_REC * 8,
                                         hipMemcpyDeviceToDevice, st));
             }
-            xn = nullptr;
+            // the joint objective keeps the frame: the squared error's seed joins the flow term's in dP0_s
+            if (!(o.mu > 0.0)) xn = nullptr;
         }
-        const float scale = !xn ? 0.f : o.by_error ? o.err_scale(s, 0) : o.loss_scale(s);
+        const float scale = !xn ? 0.f : o.by_error ? o.err_scale(s, 0) : o.by_flow ? o.joint_scale(s) : o.loss_scale(s);
         // an error-unit term whose seed is zero is left out, not added as +0.0f (which would turn a -0 gradient into +0)
         if (o.by_error && scale == 0.f) xn = nullptr;
         if (o.by_error && xn)
@@ -1128,8 +1168,8 @@ void frame_grad_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s
     const int B = o.B;
     const long long CHW = y.CHW();
     // under the flow objective this kernel adds no target path: the frames are constants of every term, or, with the moving reference,
-    // backward_step(s - 1) adds term s - 1's reference path to what is stored here
-    const float scale = s < 1 || o.by_flow ? 0.f : o.by_error ? o.err_scale(s - 1, 0) : o.loss_scale(s - 1);
+    // backward_step(s - 1) adds term s - 1's reference path to what is stored here; the joint objective's squared error has its target path
+    const float scale = s < 1 ? 0.f : o.by_flow ? (o.mu > 0.0 ? o.joint_scale(s - 1) : 0.f) : o.by_error ? o.err_scale(s - 1, 0) : o.loss_scale(s - 1);
     const int has_input = s < n_fed, has_target = s >= 1 && scale != 0.f;
     float* out = fg.p + (long long)s * fg.tstride;
     const int acc = fg.tstride == 0;
@@ -1190,9 +1230,30 @@ int read_loss(eigen_trainer* t, hipStream_t st, const Objective& o, bool want_ta
             acc += o.weight(s) * f[s];
         }
         if (o.h_terms) memcpy(o.h_terms, f.data(), (T - 1) * 8);
-        if (h_loss) *h_loss = acc / o.total_weight();
+        const double l_flow = acc / o.total_weight();
+        double l_mse = 0.0;
+        if (o.mu > 0.0) {
+            // the squared error, combined as the "mse" call combines it below
+            if (o.step_w) {
+                std::vector<double> sl(T - 1);
+                TCHK(hipMemcpyAsync(sl.data(), t->d_jstep, (T - 1) * 8, hipMemcpyDeviceToHost, st));
+                TCHK(hipStreamSynchronize(st));
+                double sq = 0.0;
+                for (int s = 0; s < T - 1; ++s) sq += o.step_w[s] * sl[s];
+                l_mse = sq / o.sum_w;
+            } else {
+                TCHK(hipMemcpyAsync(&l_mse, t->d_loss, 8, hipMemcpyDeviceToHost, st));
+                TCHK(hipStreamSynchronize(st));
+            }
+        }
+        if (o.h_parts) { o.h_parts[0] = l_flow; o.h_parts[1] = l_mse; }
+        if (h_loss) {
+            const double weighed = o.mu * l_mse;
+            *h_loss = o.mu > 0.0 ? l_flow + weighed : l_flow;
+        }
         return EIGEN_OK;
     }
+    if (o.by_flow && o.h_parts) o.h_parts[0] = o.h_parts[1] = 0.0;  // fewer than two steps: no term
     if (!h_loss) return EIGEN_OK;
     if (o.by_error && T >= 2) {
         // sum_s w_s sum_l lambda_l err[s][l] / sum_s w_s, in (step, layer) order (train.combine_terms states the same sums)
@@ -1239,6 +1300,7 @@ struct LossGradCall {
     double* h_stats = nullptr;
     const eigen_dense_solve* solve = nullptr;
     const double* d_target = nullptr; int64_t t_bstride = 0, t_tstride = 0;
+    const eigen_flow_joint* joint = nullptr;
 };
 
 // The training call behind every exported eigen_trainer_loss_grad* entry.  The order of the checks is the order of this function: the
@@ -1264,6 +1326,14 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     const bool by_flow = c.objective == EIGEN_OBJ_FLOW;
     rc = check_flow_target(t, c.d_target, c.t_bstride, c.t_tstride, T - 1, by_flow, c.d_dir, c.score, c.sscore, c.members, o.flow);
     if (rc) return rc;
+    if (c.joint) {
+        const double mu = c.joint->frame_weight;
+        if (!std::isfinite(mu) || mu < 0.0) return tfail(EIGEN_ERR_INVALID, "frame_weight %g: must be finite and >= 0", mu);
+        if (mu > 0.0 && !by_flow) return tfail(EIGEN_ERR_INVALID, "a frame weight goes with EIGEN_OBJ_FLOW only");
+        rc = check_flow_valid(t, c.joint->d_valid, c.joint->v_bstride, c.joint->v_tstride, T - 1, o.flow);
+        if (rc) return rc;
+        o.mu = mu; o.h_parts = c.joint->h_parts;
+    }
     if (!by_flow && (c.flow || c.d_dir || c.d_mask)) return tfail(EIGEN_ERR_INVALID, "flow settings, direction and mask go with EIGEN_OBJ_FLOW only");
     if (!by_flow && c.score) return tfail(EIGEN_ERR_INVALID, "a flow score goes with EIGEN_OBJ_FLOW only");
     if (!by_flow && c.sscore) return tfail(EIGEN_ERR_INVALID, "a flow structure score goes with EIGEN_OBJ_FLOW only");
@@ -1527,7 +1597,8 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
                           const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
                           int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr, const eigen_flow_score* score = nullptr,
                           double* h_stats = nullptr, const eigen_flow_structure_score* sscore = nullptr, const eigen_flow_members* members = nullptr,
-                          const eigen_dense_solve* solve = nullptr, const double* d_target = nullptr, int64_t t_bstride = 0)
+                          const eigen_dense_solve* solve = nullptr, const double* d_target = nullptr, int64_t t_bstride = 0, const uint8_t* d_valid = nullptr,
+                          int64_t v_bstride = 0)
 {
     if (!t || !d_pred || (!d_ref && !d_fref) || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
@@ -1538,6 +1609,8 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
     if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale %g is not finite", scale);
     FlowSpec f;
     int rc = check_flow_target(t, d_target, t_bstride, 0, 1, true, d_dir, score, sscore, members, f);
+    if (rc) return rc;
+    rc = check_flow_valid(t, d_valid, v_bstride, 0, 1, f);
     if (rc) return rc;
     rc = check_solve(t, solve, f);  // ahead of the mask's read-back and of every allocation
     if (rc) return rc;
@@ -1558,7 +1631,7 @@ static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstri
     m.pred = d_pred; m.p_bstride = p_bstride; m.ref = d_ref; m.fref = d_fref; m.r_bstride = r_bstride;
     m.kappa = scale / f.kappa_div(batch); m.part = t->d_spart; m.d_value = h_value ? t->d_step : nullptr;
     m.d_flow = d_flow; m.d_seed = d_seed; m.s_bstride = s_bstride; m.d_refg = d_refg; m.rg_bstride = rg_bstride;
-    m.target = f.target.p;
+    m.target = f.target.p; m.valid = f.valid.p;
     flow_stage(t, st, batch, f, m);
     TCHK(hipGetLastError());
     if (h_value) {
@@ -2079,6 +2152,35 @@ int eigen_trainer_loss_grad_flow_target(eigen_trainer* t, const uint8_t* d_frame
     c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
     c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
     c.members = members; c.h_stats = h_stats; c.solve = solve; c.d_target = d_target; c.t_bstride = t_bstride; c.t_tstride = t_tstride;
+    return loss_grad_call(t, c);
+}
+
+int eigen_trainer_flow_term_valid(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
+                                  int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask, const eigen_flow_score* score,
+                                  const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double scale, double* h_value, double* h_stats,
+                                  double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir,
+                                  const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride, const uint8_t* d_valid, int64_t v_bstride)
+{
+    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
+    if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
+    if (score && sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
+    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream,
+                          d_fref, score, h_stats, sscore, members, solve, d_target, t_bstride, d_valid, v_bstride);
+}
+
+int eigen_trainer_loss_grad_flow_joint(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant,
+                                       int32_t reset, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_loss, double* h_layer_err,
+                                       float* d_pred, float* d_frame_grad, int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                       const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score,
+                                       const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double* h_stats, void* stream,
+                                       const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride, int64_t t_tstride, const eigen_flow_joint* joint)
+{
+    LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
+    c.members = members; c.h_stats = h_stats; c.solve = solve; c.d_target = d_target; c.t_bstride = t_bstride; c.t_tstride = t_tstride;
+    c.joint = joint;
     return loss_grad_call(t, c);
 }
 

@@ -31,7 +31,8 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_trainer_accumulate", "eigen_dense_score", "eigen_eval_population_dense", "eigen_eval_images_dense",
            "eigen_render_moving_cppn", "eigen_dense_score_iter", "eigen_eval_population_dense_iter", "eigen_eval_images_dense_iter",
            "eigen_debug_dense_solve", "eigen_trainer_flow_term_iter", "eigen_trainer_loss_grad_flow_iter", "eigen_trainer_debug_flow_iter",
-           "eigen_trainer_flow_term_target", "eigen_trainer_loss_grad_flow_target"]
+           "eigen_trainer_flow_term_target", "eigen_trainer_loss_grad_flow_target", "eigen_moving_cppn_valid", "eigen_trainer_flow_term_valid",
+           "eigen_trainer_loss_grad_flow_joint"]
 
 
 class EigenConfig(ctypes.Structure):
@@ -283,6 +284,25 @@ class Engine:
                                                  _ptr(affine[1]) if flow else None, _ptr(out), ctypes.c_int64(bstride), _ptr(d_flow), _ptr(d_layer),
                                                  _stream_arg(stream)))
         return out, d_flow, d_layer
+
+    def moving_cppn_valid(self, affine, affine_inv, stream=None):
+        """eigen_moving_cppn_valid ("The joint objective and the valid pixels"): the validity planes of the flow
+        ``render_moving_cppn`` states for the same affines, float64 [n, T >= 2, L, 6] each.  -> uint8 device tensor [n, T - 1, H, W]: 1
+        where the surface a pixel of frame t shows lies inside the image in frame t + 1 and, if it is on layer 0, is not covered there
+        by layer 1; else 0.  From the affines alone: no genome is read."""
+        import torch
+        a = np.ascontiguousarray(affine, dtype=np.float64)
+        if a.ndim != 4 or a.shape[0] < 1 or a.shape[1] < 2 or a.shape[2] not in (1, 2) or a.shape[3] != 6:
+            raise ValueError("affine must be float64 [n, T >= 2, L in (1, 2), 6], got shape %s" % (a.shape,))
+        if affine_inv is None:
+            raise ValueError("the validity planes need affine_inv")
+        i = np.ascontiguousarray(affine_inv, dtype=np.float64)
+        if i.shape != a.shape:
+            raise ValueError("affine_inv has shape %s, affine %s" % (i.shape, a.shape))
+        n, T, L = a.shape[:3]
+        d_valid = torch.empty((n, T - 1, self.height, self.width), dtype=torch.uint8, device=torch.device("cuda", self.cfg.device))
+        _check(self.lib.eigen_moving_cppn_valid(self._h, ctypes.c_int32(n), ctypes.c_int32(T), ctypes.c_int32(L), _ptr(a), _ptr(i), _ptr(d_valid), _stream_arg(stream)))
+        return d_valid
 
     def cppn_param_grads(self, gb, d_image_grad, bg=1, gradient=1, stream=None):
         """The gradient of a loss by the parameters of the genomes of `gb`, from its gradient by their gradient = 1 renders (DESIGN.md

@@ -39,6 +39,13 @@ class FlowMembersSettings(ctypes.Structure):
                 ("quality_level", ctypes.c_double), ("min_distance", ctypes.c_double), ("mask_bstride", ctypes.c_int64)]
 
 
+class FlowJointSettings(ctypes.Structure):
+    """eigen_flow_joint: the frame weight (0: no frame term), the validity planes with their strides in bytes (NULL: none) and the two
+    doubles (L_flow, L_mse) the call writes (NULL: not wanted)"""
+    _fields_ = [("frame_weight", ctypes.c_double), ("d_valid", ctypes.c_void_p), ("v_bstride", ctypes.c_int64), ("v_tstride", ctypes.c_int64),
+                ("h_parts", ctypes.c_void_p)]
+
+
 class AdamSettings(ctypes.Structure):
     """eigen_adam_settings"""
     _fields_ = [("alpha", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
@@ -74,7 +81,10 @@ _ENTRIES = {(False, False): ("eigen_trainer_loss_grad_obj", ()), (False, True): 
             # a real solve (``FlowObjective.solved``): the members entry's arguments, then, behind the stream, the solve
             (True, "iter"): ("eigen_trainer_loss_grad_flow_iter", ("frame_grad", "flow", "pairing", "members")),
             # a target field (``flow_target=``): the iter entry's arguments, then, behind the solve, the target and its two strides
-            (True, "target"): ("eigen_trainer_loss_grad_flow_target", ("frame_grad", "flow", "pairing", "members"))}
+            (True, "target"): ("eigen_trainer_loss_grad_flow_target", ("frame_grad", "flow", "pairing", "members")),
+            # a frame weight or validity planes (``frame_weight=``, ``flow_valid=``): the target entry's arguments (the target may be NULL), then
+            # the eigen_flow_joint record
+            (True, "joint"): ("eigen_trainer_loss_grad_flow_joint", ("frame_grad", "flow", "pairing", "members"))}
 SOLVE_MAX_LEVELS, SOLVE_MAX_ITERS, SOLVE_MIN_COARSE = 6, 32, 4   # eigen_dense_solve's accepted values (fitness.DenseFitness states the same)
 
 
@@ -111,6 +121,9 @@ def _bind(lib):
     # the iter entries' arguments, then d_target and t_bstride, (training call) t_tstride
     lib.eigen_trainer_flow_term_target.argtypes = lib.eigen_trainer_flow_term_iter.argtypes + [_P, _I64]
     lib.eigen_trainer_loss_grad_flow_target.argtypes = lib.eigen_trainer_loss_grad_flow_iter.argtypes + [_P, _I64, _I64]
+    # the target entries' arguments, then (stage alone) d_valid and v_bstride, (training call) the eigen_flow_joint record
+    lib.eigen_trainer_flow_term_valid.argtypes = lib.eigen_trainer_flow_term_target.argtypes + [_P, _I64]
+    lib.eigen_trainer_loss_grad_flow_joint.argtypes = lib.eigen_trainer_loss_grad_flow_target.argtypes + [_P]
     lib.eigen_trainer_still_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double, ctypes.c_int32,
                                              ctypes.c_void_p]
     lib.eigen_trainer_get_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
@@ -505,9 +518,11 @@ def make_flow(pairing="frame", radius=7, eps=1e-2, direction=None, mask=None, re
     return flow if (levels, iters) == (1, 1) else flow.solved(levels, iters)
 
 
-def _entry_key(flow, target=None):
-    """the key of _ENTRIES of a flow objective: "target" for a call with a target field; "iter" under a real solve; else its pairing, the
-    kind of its score, or "members" with a per-sample mask or corner members"""
+def _entry_key(flow, target=None, joint=False):
+    """the key of _ENTRIES of a flow objective: "joint" for a call with a frame weight or validity planes; "target" for a call with a
+    target field; "iter" under a real solve; else its pairing, the kind of its score, or "members" with a per-sample mask or corner members"""
+    if joint:
+        return "joint"
     if target is not None:
         return "target"
     if flow.real_solve:
@@ -554,6 +569,47 @@ def check_flow_target(objective, flow, target, shape):
     if strides[-3:] != [h * w, w, 1]:
         raise ValueError("the last three dimensions of the flow target must be contiguous, got strides %s" % (strides,))
     return strides[:-3]
+
+
+def check_frame_weight(objective, frame_weight):
+    """The rules of ``forward_backward(frame_weight=)``: -> None without one, else the weight as a float.  ValueError: a weight that is no
+    number, not finite or not > 0 (None is "no frame term"); a weight under an objective other than "flow" (the joint objective is the
+    flow objective plus frame_weight times the squared error; the error-unit objective as the frame term is not offered)."""
+    if frame_weight is None:
+        return None
+    if isinstance(frame_weight, (bool, np.bool_)) or not isinstance(frame_weight, (int, float, np.integer, np.floating)):
+        raise ValueError("frame_weight must be a number, got %r" % (frame_weight,))
+    mu = float(frame_weight)
+    if not (np.isfinite(mu) and mu > 0):
+        raise ValueError("frame_weight must be None (no frame term) or finite and > 0, got %r" % (frame_weight,))
+    if objective != "flow":
+        raise ValueError("frame_weight goes with objective='flow', got objective %r" % (objective,))
+    return mu
+
+
+def check_flow_valid(objective, flow, target, valid, shape):
+    """The rules of validity planes (``forward_backward(flow_valid=)``, ``flow_term_valid``) against the `shape` the call expects,
+    [n, T - 1, H, W] or, for the stage alone, [n, H, W]: -> None without planes, else their leading strides in bytes (one per leading
+    dimension).  The planes are a uint8 or bool numpy array or torch tensor whose last two dimensions are contiguous; a pixel counts
+    where its byte is not zero.  ValueError: planes without a target field (they weigh a target's endpoint error; `target` None) or
+    without objective="flow"; a wrong dtype or shape; last dimensions that are not contiguous."""
+    if valid is None:
+        return None
+    if objective != "flow" or not isinstance(flow, FlowObjective) or target is None:
+        raise ValueError("flow_valid goes with objective='flow' and a flow target, got objective %r and %s target" % (objective, "no" if target is None else "a"))
+    by_numpy = isinstance(valid, np.ndarray)
+    if not by_numpy and not (hasattr(valid, "data_ptr") and hasattr(valid, "stride")):
+        raise ValueError("the validity planes must be a uint8 or bool numpy array or torch tensor, got %r" % (type(valid),))
+    if str(valid.dtype) not in ("uint8", "bool", "torch.uint8", "torch.bool"):
+        raise ValueError("the validity planes must be uint8 or bool, got %s" % (valid.dtype,))
+    shape = tuple(int(v) for v in shape)
+    if tuple(valid.shape) != shape:
+        raise ValueError("the validity planes must be %s, got %s" % (list(shape), list(valid.shape)))
+    strides = [int(v) for v in (valid.strides if by_numpy else valid.stride())]
+    h, w = shape[-2:]
+    if strides[-2:] != [w, 1]:
+        raise ValueError("the last two dimensions of the validity planes must be contiguous, got strides %s" % (strides,))
+    return strides[:-2]
 
 
 def check_layer_weights(layer_weights, n_layers):
@@ -762,6 +818,7 @@ class PredNetTrainer:
         from .fitness import _local_device, _resolve_weights
         self.clip_norm, self.weight_decay, self.skip_nonfinite = check_optim(clip_norm, weight_decay, skip_nonfinite)
         self.last_update = {"norm": None, "rate": None, "applied": None}
+        self.last_loss_parts = None  # (L_flow, L_mse) of the last call with a frame_weight
         self.lib = engine.load_library()
         _bind(self.lib)
         self.channels, self.w, self.h = [int(c) for c in channels], int(w), int(h)
@@ -856,12 +913,23 @@ class PredNetTrainer:
             target = (torch.from_numpy(np.ascontiguousarray(target)) if isinstance(target, np.ndarray) else target.contiguous()).cuda(self.device)
         return target, [ctypes.c_int64(v) for v in check_flow_target(objective, flow, target, shape)]
 
+    def _valid(self, objective, flow, target, valid, shape):
+        """Validity planes on the device and their leading strides in bytes as c_int64 (``check_flow_valid`` states the rules), or (None, [])"""
+        if valid is None:
+            return None, []
+        torch = self._torch
+        if isinstance(valid, np.ndarray) or not valid.is_cuda:
+            check_flow_valid(objective, flow, target, valid if isinstance(valid, np.ndarray) else valid.contiguous(), shape)
+            valid = (torch.from_numpy(np.ascontiguousarray(valid)) if isinstance(valid, np.ndarray) else valid.contiguous()).cuda(self.device)
+        return valid, [ctypes.c_int64(v) for v in check_flow_valid(objective, flow, target, valid, shape)]
+
     def _loss_grad(self, d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights, layer_errors, frame_grads,
-                   flow_target=None, flow=None):
+                   flow_target=None, frame_weight=None, flow_valid=None, flow=None):
         """The call behind forward_backward, on frames already on the device: (loss, table or None, d_pred or None, d_grad or None), the
         last two device tensors.  Every argument is checked before anything is launched.  Under objective="flow" the float64 [T - 1]
         terms of the call are left in ``self.last_flow_terms``; under a per-sample mask or corner members the float64 [T - 1, n, 10] records
-        of the samples of every computed term (zeros for the others) are left in ``self.last_flow_stats``, which any other call leaves as it is."""
+        of the samples of every computed term (zeros for the others) are left in ``self.last_flow_stats``, which any other call leaves as it is.
+        A call with a frame_weight leaves (L_flow, L_mse) in ``self.last_loss_parts``, which any other call leaves as it is."""
         torch = self._torch
         if isinstance(flow_target, FlowObjective) and flow is None:     # `flow` was the positional argument here before `flow_target` existed
             flow_target, flow = None, flow_target
@@ -869,7 +937,10 @@ class PredNetTrainer:
             raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
         _check_flow(objective, flow)
         by_flow = objective == "flow"
+        mu = check_frame_weight(objective, frame_weight)
         d_target, t_strides = self._target(objective, flow, flow_target, (n, max(T - 1, 0), 2, self.h, self.w))
+        d_valid, v_strides = self._valid(objective, flow, d_target, flow_valid, (n, max(T - 1, 0), self.h, self.w))
+        joint = mu is not None or d_valid is not None
         d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w) if by_flow else (None, None)
         lam = check_layer_weights(layer_weights, len(self.channels))
         w_arr = None
@@ -916,10 +987,25 @@ class PredNetTrainer:
                 # eigen_trainer_loss_grad_flow_target: no score or members go with a target; the solve (NULL: the single step), then the target
                 tails["members"] = [None, None, None, None]
                 after_stream = [ctypes.byref(solve) if solve is not None else None, _ptr(d_target)] + t_strides
-        entry, groups = _ENTRIES[by_flow, _entry_key(flow, d_target) if by_flow else frame_grads is not None]
+            if joint:
+                # eigen_trainer_loss_grad_flow_joint: the target entry's arguments whatever the mode (a score or members fill theirs in, the
+                # direction is in the flow group, the target may be NULL), then the record
+                parts = np.zeros(2, np.float64)
+                v_b, v_t = [v.value for v in v_strides] if v_strides else (0, 0)
+                rec = FlowJointSettings(0.0 if mu is None else mu, d_valid.data_ptr() if d_valid is not None else None, v_b, v_t, parts.ctypes.data)
+                if "members" not in tails:
+                    tails["members"] = [None, None, None, None]
+                    if flow.score is not None:
+                        tails["members"] = [ctypes.byref(sc) if by_circles else None, None if by_circles else ctypes.byref(sc), None, None]
+                if d_target is None:
+                    after_stream = [ctypes.byref(solve) if solve is not None else None, None, ctypes.c_int64(0), ctypes.c_int64(0)]
+                after_stream = after_stream + [ctypes.byref(rec)]
+        entry, groups = _ENTRIES[by_flow, _entry_key(flow, d_target, joint) if by_flow else frame_grads is not None]
         _check(getattr(self.lib, entry)(*args, *[a for g in groups for a in tails[g]], _stream_arg(stream), *after_stream))
         if by_flow:
             self.last_flow_terms = terms[:T - 1]
+            if mu is not None:
+                self.last_loss_parts = (float(parts[0]), float(parts[1]))
             if stats is not None:       # the members entry alone returns records: any other call leaves what an earlier one left
                 self.last_flow_stats = stats[:T - 1]
         if table is not None:
@@ -928,7 +1014,8 @@ class PredNetTrainer:
         return value, table, d_pred, d_grad
 
     def forward_backward(self, frames, reset=True, pred=False, stream=None, n_fed=None, requant=False, step_weights=None, objective="mse",
-                         layer_weights=None, layer_errors=False, frame_grads=None, flow_terms=False, flow_target=None, flow=None):
+                         layer_weights=None, layer_errors=False, frame_grads=None, flow_terms=False, flow_target=None, frame_weight=None, flow_valid=None,
+                         flow=None):
         """Loss of frames uint8 [n, T, C, H, W] (numpy or a device tensor, n <= batch) and the gradients, kept on the device
         (``grads()``).  reset=False continues from the state the previous call left (the same n), as a constant.
         pred=True also returns the float predictions P0 [n, T, C, H, W] (numpy).
@@ -966,7 +1053,20 @@ class PredNetTrainer:
         field against flow_target[:, s], and takes the place of the mean squared displacement.  Under a ``FlowObjective`` term s runs
         from frame s + 1 to P0_s.  Under ``PredictionFlow`` term s runs from P0_{s-1} to P0_s, the predictions of frames s and
         s + 1: its truth is the motion from frame s to frame s + 1, which is flow[:, s] of a video's flow [n, T - 1, 2, H, W], so that
-        array is passed as it is.  ``check_flow_target`` states the rules (ValueError)."""
+        array is passed as it is.  ``check_flow_target`` states the rules (ValueError).
+
+        flow_valid: None, or the validity planes of the target ("The joint objective and the valid pixels"): uint8 or
+        bool [n, T - 1, H, W], numpy or a device tensor (the last two dimensions contiguous, the strides of the first two are passed
+        through), as ``MovingTextures.batch(k, n, flow=True, valid=True)[3]`` states them.  A pixel of sample b counts in term s where the
+        objective's shared mask counts it and flow_valid[b, s] is not zero; the term is the mean over the samples of each sample's mean
+        squared endpoint error over its own counted pixels, and a sample that counts none contributes 0.  Only together with
+        flow_target (``check_flow_valid``, ValueError).
+
+        frame_weight: None, or mu > 0 (objective "flow" only, with any FlowObjective): the loss is L_flow + mu L_mse, the flow
+        objective's loss plus mu times the squared error of the predictions against the next frames under the same step_weights, in
+        one backward pass.  ``self.last_loss_parts`` is then (L_flow, L_mse): the losses of the same call without frame_weight and of
+        the "mse" call with the same step_weights, to the bit.  A frame gradient holds the input path, the flow terms' reference
+        paths under reference="moving" and mu times the squared error's target path.  ``check_frame_weight`` states the rules."""
         if isinstance(flow_target, FlowObjective) and flow is None:     # `flow` was the positional argument here before `flow_target` existed
             flow_target, flow = None, flow_target
         if frame_grads not in FRAME_GRADS:
@@ -976,7 +1076,8 @@ class PredNetTrainer:
         _check_flow(objective, flow)
         d, n, T, n_fed, bstride = self._call_args(frames, n_fed)
         value, table, d_pred, d_grad = self._loss_grad(d, n, T, n_fed, bstride, reset, pred, stream, requant, step_weights, objective, layer_weights,
-                                                       layer_errors, frame_grads, flow=flow, flow_target=flow_target)
+                                                       layer_errors, frame_grads, flow=flow, flow_target=flow_target, frame_weight=frame_weight,
+                                                       flow_valid=flow_valid)
         out = (value,) + ((d_pred.cpu().numpy(),) if pred else ()) + ((table,) if layer_errors else ()) + ((d_grad.cpu().numpy(),) if frame_grads else ())
         out += (self.last_flow_terms,) if flow_terms else ()
         return out[0] if len(out) == 1 else out
@@ -1038,7 +1139,22 @@ class PredNetTrainer:
             raise ValueError("flow_term_pair_target needs a target field; flow_term_pair is the stage without one")
         return self._flow_stage(pred, prev, True, flow, scale, reference_grad, target=target)
 
-    def _flow_stage(self, pred, ref, float_ref, flow, scale, reference_grad, stats=False, target=None):
+    def flow_term_valid(self, pred, ref, flow, target, valid, scale=1.0, reference_grad=False):
+        """``flow_term(target=)`` under validity planes (eigen_trainer_flow_term_valid): valid uint8 or bool [n, H, W], numpy or a device
+        tensor; a pixel of sample b counts where the objective's shared mask counts it and valid[b] is not zero.  The value is the
+        mean over the samples of each sample's mean squared endpoint error over its own counted pixels (0 for a sample that counts
+        none); all-ones planes give the bytes of ``flow_term(target=)``.  ``check_flow_valid`` states the rules (ValueError)."""
+        if target is None or valid is None:
+            raise ValueError("flow_term_valid needs a target field and validity planes; flow_term is the stage without them")
+        return self._flow_stage(pred, ref, False, flow, scale, reference_grad, target=target, valid=valid)
+
+    def flow_term_pair_valid(self, pred, prev, flow, target, valid, scale=1.0, reference_grad=False):
+        """``flow_term_pair_target`` under validity planes (eigen_trainer_flow_term_valid with a float reference), as ``flow_term_valid``."""
+        if target is None or valid is None:
+            raise ValueError("flow_term_pair_valid needs a target field and validity planes; flow_term_pair is the stage without them")
+        return self._flow_stage(pred, prev, True, flow, scale, reference_grad, target=target, valid=valid)
+
+    def _flow_stage(self, pred, ref, float_ref, flow, scale, reference_grad, stats=False, target=None, valid=None):
         """flow_term (float_ref False: a uint8 reference) and flow_term_pair (True: a float32 one): the upload, the checks, the buffers,
         the one call and the result tuple"""
         torch = self._torch
@@ -1057,6 +1173,7 @@ class PredNetTrainer:
                              % (shp + (p.dtype, tuple(p.shape), r.dtype, tuple(r.shape))))
         n, per = int(p.shape[0]), int(np.prod(shp))
         d_target, t_strides = self._target("flow", flow, target, (n, 2, self.h, self.w))
+        d_valid, v_strides = self._valid("flow", flow, d_target, valid, (n, self.h, self.w))
         d_dir, d_mask = flow.on_device(torch, self.device, self.h, self.w)
         value = ctypes.c_double(0.0)
         u = torch.empty((n, 2, self.h, self.w), dtype=torch.float64, device=dev)
@@ -1068,10 +1185,12 @@ class PredNetTrainer:
         if d_target is not None:
             # eigen_trainer_flow_term_target: the iter entry's arguments (no score or members go with a target), the solve (NULL: the single
             # step), then the target
-            _check(self.lib.eigen_trainer_flow_term_target(
+            # under validity planes eigen_trainer_flow_term_valid: the same arguments, then the planes and their stride
+            entry, tail = (self.lib.eigen_trainer_flow_term_target, []) if d_valid is None else (self.lib.eigen_trainer_flow_term_valid, [_ptr(d_valid)] + v_strides)
+            _check(entry(
                 self._h, _ptr(p), ctypes.c_int64(per), None if float_ref else _ptr(r), _ptr(r) if float_ref else None, ctypes.c_int64(per), ctypes.c_int32(n),
                 ctypes.byref(cfg), _ptr(d_mask), None, None, None, ctypes.c_double(float(scale)), ctypes.byref(value), None, _ptr(u), _ptr(seed), ctypes.c_int64(per),
-                _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None, None, ctypes.byref(solve) if solve is not None else None, _ptr(d_target), *t_strides))
+                _ptr(rg), ctypes.c_int64(per if reference_grad else 0), None, None, ctypes.byref(solve) if solve is not None else None, _ptr(d_target), *t_strides, *tail))
             out = (value.value, u.cpu().numpy(), seed.cpu().numpy())
             return out + (rg.cpu().numpy(),) if reference_grad else out
         if solve is not None:
@@ -1195,7 +1314,7 @@ class PredNetTrainer:
         self.last_update = {"norm": rep.norm, "rate": rep.rate, "applied": int(rep.applied)}
 
     def step(self, frames, reset=True, n_fed=None, requant=False, step_weights=None, objective="mse", layer_weights=None, micro_batches=1, flow_target=None,
-             flow=None):
+             frame_weight=None, flow_valid=None, flow=None):
         """Gradient and one Adam step; returns the loss before the step.  (`flow` stays the last argument, as in every call that takes
         one; it was the eighth positional one before `micro_batches` existed, and such a call still means it.)
 
@@ -1203,14 +1322,16 @@ class PredNetTrainer:
         added to the accumulator with scale 1 / k, the sum becomes the gradient and ONE Adam step is taken.  Every objective is a mean
         over the samples, so in real arithmetic that is the full batch's gradient: a handle of batch n / k trains a logical batch of n.
         The loss returned is sum_j loss_j / k, formed in double in chunk order.  ``check_micro_batches`` states the rules (ValueError).
-        flow_target: ``forward_backward``'s; with micro_batches = k it is sliced along n with the frames."""
+        flow_target, flow_valid: ``forward_backward``'s; with micro_batches = k they are sliced along n with the frames.  frame_weight:
+        ``forward_backward``'s."""
         if isinstance(micro_batches, FlowObjective) and flow is None:
             micro_batches, flow = 1, micro_batches
         if isinstance(flow_target, FlowObjective) and flow is None:
             flow_target, flow = None, flow_target
         kw = dict(n_fed=n_fed, requant=requant, step_weights=step_weights, objective=objective, layer_weights=layer_weights, flow=flow)
-        if flow_target is not None:
-            kw["flow_target"] = flow_target
+        for key, v in (("flow_target", flow_target), ("frame_weight", frame_weight), ("flow_valid", flow_valid)):
+            if v is not None:
+                kw[key] = v
         if micro_batches == 1 and not isinstance(micro_batches, bool):     # the call as it always was: the accumulator is not touched
             loss = self.forward_backward(frames, reset, **kw)
             self.adam()
@@ -1223,9 +1344,10 @@ class PredNetTrainer:
     def accumulate_micro_batches(self, frames, micro_batches, reset=True, **kw):
         """The gradient half of ``step(micro_batches=k)``: empties the accumulator, runs the k chunks of `frames` and adds each with scale
         1 / k; -> sum_j loss_j / k.  ``load_accumulated()`` then makes the sum the gradient.  kw: ``forward_backward``'s n_fed, requant,
-        step_weights, objective, layer_weights, flow and flow_target (sliced along n with the frames)."""
+        step_weights, objective, layer_weights, flow, frame_weight, and flow_target and flow_valid (both sliced along n with the frames).
+        Under validity planes every chunk's term is the mean over ITS samples of their own means, and the chunks are averaged."""
         kw = dict(kw)
-        target = kw.pop("flow_target", None)
+        target, valid = kw.pop("flow_target", None), kw.pop("flow_valid", None)
         d = self._frames(frames)
         m = check_micro_batches(int(d.shape[0]), micro_batches, self.batch, reset, kw.get("flow"))
         k = int(micro_batches)
@@ -1233,6 +1355,8 @@ class PredNetTrainer:
         total = 0.0
         for j in range(k):
             chunk = {} if target is None else {"flow_target": target[j * m:(j + 1) * m]}
+            if valid is not None:
+                chunk["flow_valid"] = valid[j * m:(j + 1) * m]
             total += float(self.forward_backward(d[j * m:(j + 1) * m], True, **kw, **chunk))
             self.accumulate(1.0 / k)
         return total / k
@@ -1303,14 +1427,17 @@ class PredNetTrainer:
         self.close()
 
 
-def flow_epe(trainer, pred, prev_or_ref, flow, target):
+def flow_epe(trainer, pred, prev_or_ref, flow, target, valid=None):
     """The mean squared endpoint error of the flow `flow` solves from prev_or_ref to pred against `target`, on the device: the value of
     the stage alone under a target field (``PredNetTrainer.flow_term`` for a uint8 reference, ``flow_term_pair_target`` for a float32 one; float64
     target [n, 2, H, W]), the metric form of what ``forward_backward(flow_target=)`` trains on.  The mean runs over the samples and the
-    pixels the objective's shared mask counts."""
+    pixels the objective's shared mask counts.  valid: None, or validity planes [n, H, W] (``flow_term_valid``): the mean over the
+    samples of each sample's mean over its own counted pixels."""
     if target is None:
         raise ValueError("flow_epe needs a target field")
     by_float = str(getattr(prev_or_ref, "dtype", "")) in ("float32", "torch.float32")
+    if valid is not None:
+        return (trainer.flow_term_pair_valid if by_float else trainer.flow_term_valid)(pred, prev_or_ref, flow, target, valid)[0]
     if by_float:
         return trainer.flow_term_pair_target(pred, prev_or_ref, flow, target)[0]
     return trainer.flow_term(pred, prev_or_ref, flow, target=target)[0]
@@ -1675,11 +1802,17 @@ class MovingTextures:
             self._own = True
         return self.engine
 
-    def batch(self, k, n, flow=False, stream=None):
+    def batch(self, k, n, flow=False, stream=None, valid=False):
         """The device uint8 [n, seq, C, H, W] tensor of batch index k; flow=True: (frames, flow float64 [n, seq - 1, 2, H, W], layer
-        uint8 [n, seq, H, W]).  The same (seed, k, n) always gives the same bytes."""
+        uint8 [n, seq, H, W]).  The same (seed, k, n) always gives the same bytes.  valid=True (with flow=True; ValueError without)
+        appends the validity planes, uint8 [n, seq - 1, H, W] (``Engine.moving_cppn_valid``): 1 where the surface a pixel of frame t
+        shows is inside the image and uncovered in frame t + 1, so that its flow can be recovered from the two frames at all."""
+        if valid and not flow:
+            raise ValueError("valid=True states the validity of the flow: it needs flow=True")
         d = self.describe(k, n)
         frames, fl, layer = self._engine().render_moving_cppn(d["gb"], d["affine"], d["affine_inv"] if flow else None, flow=flow, layer=flow, stream=stream)
+        if valid:
+            return frames, fl, layer, self._engine().moving_cppn_valid(d["affine"], d["affine_inv"], stream=stream)
         return (frames, fl, layer) if flow else frames
 
     def close(self):
@@ -1701,5 +1834,5 @@ class MovingTextures:
 
 
 __all__ = ["PredNetTrainer", "EngineError", "check_state", "write_checkpoint", "read_checkpoint", "combine_terms", "refine_stills", "refine_genomes", "genome_update", "FlowObjective",
-           "PredictionFlow", "make_flow", "flow_direction", "FlowScore", "BandsScore", "FreeScore", "structure_score", "CornerMembers", "check_optim",
+           "check_flow_valid", "check_frame_weight", "PredictionFlow", "make_flow", "flow_direction", "FlowScore", "BandsScore", "FreeScore", "structure_score", "CornerMembers", "check_optim",
            "check_micro_batches", "MovingTextures", "check_moving_textures", "similarity_affines", "flat_genome_batch"]

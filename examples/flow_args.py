@@ -52,6 +52,30 @@ def check_flow_target(ap, a):
         ap.error("--flow-target truth needs --data textures: no other source states the flow of its frames")
 
 
+def add_flow_joint_arguments(ap):
+    """--frame-weight and --flow-valid of the scripts that train on videos (examples/train_prednet.py, scripts/train_bench.py): the joint
+    objective and the valid pixels of ``forward_backward(frame_weight=, flow_valid=)``"""
+    ap.add_argument("--frame-weight", type=float, default=None, metavar="MU",
+                    help="objective flow: the loss is the flow objective's plus MU times the squared error of the predictions, in one backward pass")
+    ap.add_argument("--flow-valid", default="none", choices=["none", "visible"],
+                    help="--flow-target truth: visible counts a pixel only where its surface can be seen in the next frame (train.MovingTextures' "
+                         "validity planes: inside the image and not covered by the second layer)")
+
+
+def check_flow_joint(ap, a):
+    """--frame-weight without --objective flow and --flow-valid visible without --data textures --flow-target truth are argparse errors"""
+    if a.frame_weight is not None and getattr(a, "objective", None) != "flow":
+        ap.error("--frame-weight is a mode of --objective flow")
+    if a.flow_valid == "visible" and (getattr(a, "data", None) != "textures" or getattr(a, "flow_target", "none") != "truth"):
+        ap.error("--flow-valid visible needs --data textures --flow-target truth: the planes state where the video's own flow can be recovered")
+    if a.frame_weight is not None:
+        from evolutionary_illusion_generator_amd.train import check_frame_weight
+        try:
+            check_frame_weight("flow", a.frame_weight)
+        except ValueError as e:
+            ap.error(str(e))
+
+
 def score_of(a):
     """the score of the command line: None without --flow-score; else the class of --flow-score-structure (auto: of a.structure), with
     --flow-max-norm where it is given"""

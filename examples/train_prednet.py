@@ -4,7 +4,8 @@ result in the fitness path.
 
     python examples/train_prednet.py -o trained.npz [-i frames_dir] [--size 160x120] [-c 3] [--steps 200] [--seq 10] [--batch 8]
                                      [--data rings|textures [--texture-layers 1|2]] [--loss mse|l0|lall]
-                                     [--objective flow [--flow-pairing prediction] [--flow-radius 7] ... [--flow-target truth]]
+                                     [--objective flow [--flow-pairing prediction] [--flow-radius 7] ... [--flow-target truth [--flow-valid visible]]
+                                      [--frame-weight MU]]
                                      [--clip-norm X] [--weight-decay X] [--skip-nonfinite] [--micro-batches K]
                                      [--ext-steps 200 --ext-frames 4 [--requant]] [--checkpoint ckpt.npz [--every 50]] [--resume ckpt.npz]
 
@@ -23,8 +24,11 @@ fitness with them.
 --objective flow trains on the dense motion objective of the --flow-* options in place of --loss (train.make_flow; examples/flow_args.py
 lists them).  With --data textures --flow-target truth every term is the squared endpoint error of the solved field against the exact flow
 of the video (``forward_backward(flow_target=)``): under --flow-pairing prediction "the flow between consecutive predictions shall be the
-true flow", on the self-fed steps too.  The per-term values of the printed steps are printed with the loss.  With --data textures the
-held-out mean squared endpoint error between consecutive predictions (train.flow_epe) is printed before and after, whatever the objective.
+true flow", on the self-fed steps too.  --flow-valid visible then counts a pixel only where its surface can be seen in the next frame
+(``flow_valid=``, the validity planes of ``MovingTextures.batch(valid=True)``), and --frame-weight MU adds MU times the squared error of the
+predictions to the flow objective's loss in the same backward pass (``frame_weight=``; the two parts are printed with the loss).  The per-term values of the printed steps are printed with the loss.  With --data textures the
+held-out mean squared endpoint error between consecutive predictions (train.flow_epe) is printed before and after, whatever the objective,
+over all pixels and over the valid ones.
 --clip-norm, --weight-decay and --skip-nonfinite are the trainer's optimiser controls (gradient clipping at a global norm, chainer's weight
 decay, leaving out a step whose gradient is not finite); --micro-batches K keeps --batch as the logical batch of a step and runs it as K
 chunks on a handle of --batch / K, so the tape is K times smaller.  At the steps whose loss is printed the global gradient norm is printed
@@ -40,7 +44,7 @@ import numpy as np
 
 from evolutionary_illusion_generator_amd import fitness, grids, synth, weights
 from evolutionary_illusion_generator_amd.train import MovingTextures, PredictionFlow, PredNetTrainer, check_micro_batches, check_optim, flow_epe
-from examples.flow_args import add_flow_arguments, add_flow_target_argument, check_flow_target, flow_of
+from examples.flow_args import add_flow_arguments, add_flow_joint_arguments, add_flow_target_argument, check_flow_joint, check_flow_target, flow_of
 
 
 def read_windows(folder, c_dim, w, h, seq):
@@ -64,13 +68,14 @@ def drifting(seed, n, seq, c_dim, w, h):
     return out
 
 
-def held_out_epe(tr, frames, truth, radius, eps, n_fed, requant):
+def held_out_epe(tr, frames, truth, radius, eps, n_fed, requant, valid=None):
     """float64 [T - 2]: the mean squared endpoint error of the flow from prediction s - 1 to prediction s against the video's own flow
-    from frame s to frame s + 1, for s = 1 .. T - 2 (term 0 has no previous prediction), on the device (train.flow_epe)"""
+    from frame s to frame s + 1, for s = 1 .. T - 2 (term 0 has no previous prediction), on the device (train.flow_epe); valid: the
+    video's validity planes [n, T - 1, H, W], the mean then runs over every sample's valid pixels"""
     import torch
     pred = torch.from_numpy(tr.evaluate(frames, n_fed=n_fed, requant=requant, pred=True)[1])
     flow = PredictionFlow(radius, eps)
-    return np.array([flow_epe(tr, pred[:, s], pred[:, s - 1], flow, truth[:, s]) for s in range(1, pred.shape[1] - 1)])
+    return np.array([flow_epe(tr, pred[:, s], pred[:, s - 1], flow, truth[:, s], None if valid is None else valid[:, s]) for s in range(1, pred.shape[1] - 1)])
 
 
 def main():
@@ -91,6 +96,7 @@ def main():
     ap.add_argument("--objective", default="loss", choices=["loss", "flow"], help="loss: the objective of --loss; flow: the dense motion objective of the --flow-* options")
     add_flow_arguments(ap)
     add_flow_target_argument(ap)
+    add_flow_joint_arguments(ap)
     ap.add_argument("--ext-steps", type=int, default=0, help="Adam steps of a second phase whose last --ext-frames steps are self-fed")
     ap.add_argument("--ext-frames", type=int, default=4, help="self-fed steps at the end of every sequence in the second phase")
     ap.add_argument("--requant", action="store_true", help="feed predictions back through the emitted byte (cfg.requant_feedback)")
@@ -105,6 +111,7 @@ def main():
     check_flow_target(ap, args)
     if args.flow_target == "truth" and args.objective != "flow":
         ap.error("--flow-target truth is a mode of --objective flow")
+    check_flow_joint(ap, args)
     w, h = (int(v) for v in args.size.lower().split("x"))
     channels = [int(c) for c in args.channels.split(",")] if args.channels else [args.color_space, 48, 96, 192]
     c_dim = channels[0]
@@ -139,6 +146,8 @@ def main():
         ap.error(str(e))
     if flow is not None:
         obj = dict(objective="flow", flow=flow)
+        if args.frame_weight is not None:
+            obj["frame_weight"] = args.frame_weight
     name = "flow" if flow is not None else args.loss
     truth = args.flow_target == "truth"
 
@@ -146,6 +155,9 @@ def main():
         """the frames of step k and, under --flow-target truth, their exact flow as the step's target"""
         if not truth:
             return batch_of(k), {}
+        if args.flow_valid == "visible":
+            frames, fl, _, visible = source.batch(k, args.batch, flow=True, valid=True)
+            return frames, dict(flow_target=fl, flow_valid=visible)
         frames, fl, _ = source.batch(k, args.batch, flow=True)
         return frames, dict(flow_target=fl)
 
@@ -170,6 +182,10 @@ def main():
             epe = lambda: held_out_epe(tr, held[:chunk], held_flow[:chunk], args.flow_radius, args.flow_eps, n_fed, args.requant)
             epe_before = epe()
             print("held-out squared endpoint error between consecutive predictions (terms 1 .. %d) before: %s" % (args.seq - 2, fmt(epe_before)))
+            held_valid = source.batch(10 ** 6, args.batch, flow=True, valid=True)[3]
+            epe_valid = lambda: held_out_epe(tr, held[:chunk], held_flow[:chunk], args.flow_radius, args.flow_eps, n_fed, args.requant, held_valid[:chunk])
+            valid_before = epe_valid()
+            print("  over the valid pixels (%.1f %% of all) before: %s" % (100 * float(held_valid[:chunk, 1:].float().mean()), fmt(valid_before)))
         for k in range(first, total):
             frames, extra = step_inputs(k)
             if k < args.steps:
@@ -178,6 +194,9 @@ def main():
                 loss = tr.step(frames, n_fed=n_fed, requant=args.requant, step_weights=ext_w if any(ext_w) else None, **extra, **obj)
             if k % 50 == 0 or k == total - 1 or k == args.steps:
                 print("step %4d  %s train loss (%s) %.6f" % (k, "teacher-forced" if k < args.steps else "self-fed      ", name, loss))
+                if flow is not None and args.frame_weight is not None:
+                    print("           flow part %.6f, squared-error part %.6f (weight %g)%s"
+                          % (tr.last_loss_parts + (args.frame_weight, " (last micro-batch)" if args.micro_batches > 1 else "")))
                 if flow is not None:     # the terms the library returned (h_terms); with micro-batches those of the step's last chunk
                     print("           flow terms%s: %s" % (" (last micro-batch)" if args.micro_batches > 1 else "", " ".join("%.6f" % v for v in tr.last_flow_terms)))
                 # the gradient this step applied (with micro-batches: the accumulated one), before clipping
@@ -193,6 +212,8 @@ def main():
             print("held-out squared endpoint error between consecutive predictions after:  %s" % fmt(epe_after))
             print("held-out squared endpoint error, mean over the terms: %.6f before, %.6f after (%.1f %% lower)"
                   % (epe_before.mean(), epe_after.mean(), 100 * (1 - epe_after.mean() / epe_before.mean())))
+            valid_after = epe_valid()
+            print("  over the valid pixels: %.6f before, %.6f after (%.1f %% lower)" % (valid_before.mean(), valid_after.mean(), 100 * (1 - valid_after.mean() / valid_before.mean())))
         trained = tr.weights()
     print("held-out loss per step after:  %s" % fmt(after))
     print("held-out error units per layer after:  %s" % fmt(err_after.mean(0)))

@@ -176,6 +176,21 @@ int eigen_render_moving_cppn(eigen_engine* e, const eigen_genome_batch* h_genome
                              uint8_t* d_frames, int64_t f_bstride,
                              double* d_flow, uint8_t* d_layer, void* stream);
 
+/* The validity planes of eigen_render_moving_cppn's flow ("The joint objective and the valid pixels"): whether
+ * the surface a pixel of frame t shows can be seen in frame t + 1.  From the affines alone, in the render's arithmetic (float64, every
+ * product and sum one rounding in the order written); no genome is read.  With (u, v) and the visible layer vis of the pixel in frame
+ * t as the render forms them and I = h_affine_inv[b][t + 1][vis]:
+ *   qx = (i0 u + i1 v) + i2, qy = (i3 u + i4 v) + i5            (the render's flow is (qx - px, qy - py))
+ *   inb = -(W - 1) / 2 <= qx <= (W - 1) / 2 && -(H - 1) / 2 <= qy <= (H - 1) / 2
+ *   occ = n_layers == 2 && vis == 0 && u1' u1' + v1' v1' < 1.0, (u1', v1') = h_affine[b][t + 1][1] applied to (qx, qy)
+ *   valid = inb && !occ, a byte 0 or 1; a NaN compares false and gives 0.
+ * h_affine, h_affine_inv: [n][n_frames][n_layers][6], as eigen_render_moving_cppn takes them.  d_valid: uint8 [n][n_frames - 1][H][W].
+ * The entry needs neither a grid nor weights and uses staging buffers of its own, which grow with the call.
+ * Errors, before anything is launched or allocated: EIGEN_ERR_INVALID a NULL handle, h_affine, h_affine_inv or d_valid, n_layers
+ * outside 1 .. 2, n_frames < 2, n < 1; EIGEN_ERR_CAPACITY n > 65535. */
+int eigen_moving_cppn_valid(eigen_engine* e, int32_t n, int32_t n_frames, int32_t n_layers, const double* h_affine,
+                            const double* h_affine_inv, uint8_t* d_valid, void* stream);
+
 /* The backward pass through eigen_render_cppn's gradient = 1 render ("CPPN parameter gradients"): the gradient
  * of a loss by every bias, response and connection weight of the batch, from its gradient by the images.
  *   d_image_grad: device float, d loss / d (byte / 255) of image g at d_image_grad + g * g_bstride as [c_dim][H][W] (what
@@ -960,6 +975,56 @@ int eigen_trainer_loss_grad_flow_target(eigen_trainer* t, const uint8_t* d_frame
                                         const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double* h_stats,
                                         void* stream, const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride,
                                         int64_t t_tstride);
+
+/* ---- The joint objective and the valid pixels ("The joint objective and the valid pixels").
+ *
+ * Validity planes under a target field: sample b of a term has a byte plane V_b [H W]; a pixel counts where the shared mask M counts it
+ * (all pixels without one; N_m is its count) and V_b is not zero.  With c_b the integer count of the counted pixels of sample b and
+ * r_b = c_b > 0 ? (double)N_m / (double)c_b : 0.0, in float64, one IEEE operation per operation written:
+ *   ex, ey, v as under the target field; mv = counted ? v r_b : 0, g = counted ? ((2 ex) r_b, (2 ey) r_b) : 0
+ * and everything behind mv and g is the target field's own (the fixed-order sum, the division by B N_m, kappa, q, the seed, the reference
+ * path, the gradient through an iterated solve).  The term is the mean over the samples of each sample's mean squared endpoint error
+ * over its own counted pixels; a sample that counts no pixel contributes exactly 0 and a zero gradient; planes that are all ones give
+ * r_b = 1.0 exactly and the bytes of the call without planes.  The counts are summed without atomics.
+ *
+ * eigen_trainer_flow_term_valid: eigen_trainer_flow_term_target's arguments plus d_valid, bytes, sample b at d_valid + b * v_bstride as
+ * [H W] (NULL: the call is its _target namesake, launch for launch).
+ *
+ * The joint objective: loss = L_flow + frame_weight * L_mse, where L_flow is the loss of the same call without a frame weight and L_mse
+ * the squared error of the image-layer predictions against the next frames under the call's own step weights, reduced as the
+ * EIGEN_OBJ_MSE call with the same step weights reduces it.  Term s seeds d loss / d P0_s with the flow term's seed plus
+ * (float)(frame_weight * the squared error's scale of step s, formed in double) * (P0_s - x_{s+1}); a frame gradient holds the input path,
+ * the flow terms' reference paths under EIGEN_FLOW_MOVING_REFERENCE and frame_weight times the squared error's target path.  The frame
+ * term goes with every mode, score, members setting, solve, pairing and reference of the flow objective.
+ *
+ * eigen_trainer_loss_grad_flow_joint: eigen_trainer_loss_grad_flow_target's arguments plus `joint` (NULL: the call is its _target
+ * namesake, launch for launch and bit for bit).  Term s (prediction P0_s) reads the plane of sample b at
+ * d_valid + b * v_bstride + s * v_tstride.
+ * Errors: the namesakes'; EIGEN_ERR_INVALID before any launch or allocation for a frame_weight that is negative or not finite, for a
+ * frame_weight > 0 under an objective other than EIGEN_OBJ_FLOW, for d_valid without d_target, for v_bstride < H W, and for
+ * v_tstride < H W when n_steps > 2.  After a refusal the outputs are untouched and the handle still works. */
+typedef struct eigen_flow_joint {
+    double frame_weight;      /* mu >= 0; 0: no frame term */
+    const uint8_t* d_valid;   /* device validity planes, or NULL */
+    int64_t v_bstride;        /* bytes between two samples' planes, >= H W */
+    int64_t v_tstride;        /* bytes between two terms' planes, >= H W when n_steps > 2 */
+    double* h_parts;          /* host, two doubles out: L_flow, L_mse; may be NULL */
+} eigen_flow_joint;
+
+int eigen_trainer_flow_term_valid(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref,
+                                  int64_t r_bstride, int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask,
+                                  const eigen_flow_score* score, const eigen_flow_structure_score* sscore, const eigen_flow_members* members,
+                                  double scale, double* h_value, double* h_stats, double* d_flow, float* d_seed, int64_t s_bstride,
+                                  float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir, const eigen_dense_solve* solve,
+                                  const double* d_target, int64_t t_bstride, const uint8_t* d_valid, int64_t v_bstride);
+int eigen_trainer_loss_grad_flow_joint(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps,
+                                       int32_t n_fed, int32_t requant, int32_t reset, const double* h_step_w, int32_t objective,
+                                       const double* h_layer_w, double* h_loss, double* h_layer_err, float* d_pred, float* d_frame_grad,
+                                       int64_t g_bstride, int64_t g_tstride, const eigen_flow_settings* flow, const float* d_dir,
+                                       const uint8_t* d_mask, double* h_terms, int32_t pairing, const eigen_flow_score* score,
+                                       const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double* h_stats,
+                                       void* stream, const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride,
+                                       int64_t t_tstride, const eigen_flow_joint* joint);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,9 @@ it replaces, and the trainer step fed by batch() of --texture-layers; one JSON l
 --flow-target truth (with --data textures) reads the frames from train.MovingTextures and makes their exact flow the target of the flow objective
 (forward_backward(flow_target=)); --flow-cost then times the "flow" call of the pairing asked for without and with the target
 ("flow_target"; under a real solve also "flow_iter_target"), alternated like the other legs; without --flow-cost the timed step trains on it.
+--frame-weight MU (with --objective flow or --flow-cost) is the joint objective, forward_backward(frame_weight=): --flow-cost then adds the
+"flow" call with the frame term ("flow_joint"; with --flow-target truth also "flow_target_joint").  --flow-valid visible (with --data textures
+--flow-target truth) passes the video's validity planes, forward_backward(flow_valid=): --flow-cost then adds "flow_target_valid".
 """
 import argparse
 import json
@@ -46,7 +49,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from examples.flow_args import add_flow_arguments, add_flow_target_argument, check_flow_target, members_of, score_of  # noqa: E402
+from examples.flow_args import add_flow_arguments, add_flow_joint_arguments, add_flow_target_argument, check_flow_joint, check_flow_target, members_of, score_of  # noqa: E402
 
 W, H, CH, B, T = 160, 120, [3, 48, 96, 192], 16, 10
 GATES = ("i", "f", "c", "o")
@@ -94,7 +97,15 @@ def texture_frames():
         return src.batch(0, B, flow=True)[:2]
 
 
-def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None, members=None, levels=1, iters=1, target=False):
+def texture_valid():
+    """the validity planes uint8 [B, T - 1, H, W] of `texture_frames`' video, on the device"""
+    from evolutionary_illusion_generator_amd.train import MovingTextures
+    with MovingTextures(W, H, CH[0], T) as src:
+        return src.batch(0, B, flow=True, valid=True)[3]
+
+
+def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame", score=None, members=None, levels=1, iters=1, target=False, frame_weight=None,
+                  valid=False):
     """ms per forward_backward call under "mse" and under "flow" (r = 7, the same two weighted terms), alternated round by round; with
     the moving reference also per "flow" call with tied frame gradients, under either reference; with a real solve (levels, iters) also per
     "flow" call of the same settings whose gradient runs through that solve ("flow_iter")"""
@@ -123,6 +134,13 @@ def run_flow_cost(steps, warmup, rounds=6, reference="constant", pairing="frame"
         if (levels, iters) != (1, 1):
             calls["flow_iter"] = objective_args("flow", reference, pairing, levels=levels, iters=iters)
             calls["flow_iter_target"] = dict(calls["flow_iter"], flow_target=truth)
+        if valid:
+            calls["flow_target_valid"] = dict(calls["flow_target"], flow_valid=texture_valid())
+    if frame_weight is not None:
+        # the joint objective: the call of the pairing asked for with the frame term beside it
+        calls["flow_joint"] = dict(calls["flow_prediction" if pairing == "prediction" and not target else "flow"], frame_weight=frame_weight)
+        if target:
+            calls["flow_target_joint"] = dict(calls["flow_target"], frame_weight=frame_weight)
     ms = {k: [] for k in calls}
     loss = {}
     with PredNetTrainer(weights.synthetic_prednet_weights(CH, W, H, seed=0), CH, W, H, B, T) as tr:
@@ -223,7 +241,7 @@ def run_data(steps, warmup, layers=1, rounds=6):
 
 
 def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="frame", score=None, members=None, optim=(None, 0.0, False), micro_batches=1, levels=1,
-                iters=1, target=False):
+                iters=1, target=False, frame_weight=None, valid=False):
     import torch
     from evolutionary_illusion_generator_amd import weights
     from evolutionary_illusion_generator_amd.train import PredNetTrainer
@@ -236,6 +254,10 @@ def run_trainer(steps, warmup, objective="mse", reference="constant", pairing="f
     if target:
         d, truth = texture_frames()
         kw["flow_target"] = truth
+        if valid:
+            kw["flow_valid"] = texture_valid()
+    if frame_weight is not None:
+        kw["frame_weight"] = frame_weight
     for _ in range(warmup):
         tr.step(d, **kw)
     torch.cuda.synchronize()
@@ -372,6 +394,7 @@ def main():
     add_flow_arguments(ap, ("reference", "pairing", "score", "score-structure", "max-norm", "members", "corner-quality", "corner-distance", "levels", "iters"), **{"score-structure": dict(choices=["circles", "bands", "free"])}, reference=dict(help="the flow objective's reference frame: a constant of the graph, or part of it"),
                        pairing=dict(help="the flow objective's pairing: prediction s against frame s + 1, or against prediction s - 1 (train.PredictionFlow)"))
     add_flow_target_argument(ap)
+    add_flow_joint_arguments(ap)
     ap.add_argument("--frame-grads", action="store_true", help="time one loss_grad call without, with per-frame and with tied frame gradients, and exit")
     ap.add_argument("--clip-norm", type=float, default=None, help="the trainer's clip_norm (default: no clipping)")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="the trainer's weight_decay")
@@ -389,6 +412,9 @@ def main():
         ap.error("--flow-target truth is a mode of --objective flow (or of --flow-cost)")
     if target and (a.flow_score or a.flow_members != "all"):
         ap.error("--flow-target truth takes no --flow-score and no --flow-members")
+    if a.flow_cost and a.frame_weight is not None:
+        a.objective = "flow"        # --flow-cost times the flow calls whatever --objective says
+    check_flow_joint(ap, a)
     if a.flow_pairing == "prediction" and a.flow_reference == "moving":
         ap.error("--flow-pairing prediction has no frame as a reference: it does not take --flow-reference moving")
     score = score_of(a)
@@ -409,7 +435,7 @@ def main():
         return
     if a.flow_cost:
         for r in run_flow_cost(a.steps, a.warmup, reference=a.flow_reference, pairing=a.flow_pairing, score=score, members=members, levels=a.flow_levels, iters=a.flow_iters,
-                               target=target):
+                               target=target, frame_weight=a.frame_weight, valid=a.flow_valid == "visible"):
             print(json.dumps(r), flush=True)
         return
     from evolutionary_illusion_generator_amd.train import check_micro_batches, check_optim
@@ -422,7 +448,8 @@ def main():
         for r in run_optim_cost(a.steps, a.warmup, clip_norm=optim[0], weight_decay=optim[1], skip_nonfinite=optim[2], micro_batches=max(a.micro_batches, 2)):
             print(json.dumps(r), flush=True)
         return
-    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members, optim, a.micro_batches, a.flow_levels, a.flow_iters, target)]
+    res = [run_trainer(a.steps, a.warmup, a.objective, a.flow_reference, a.flow_pairing, score, members, optim, a.micro_batches, a.flow_levels, a.flow_iters, target, a.frame_weight,
+                       a.flow_valid == "visible")]
     print(json.dumps(res[0]), flush=True)
     ext = run_ext(a.steps, a.warmup)
     for r in ext:
