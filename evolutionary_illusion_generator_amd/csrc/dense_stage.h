@@ -1,6 +1,5 @@
-// dense_stage.h -- what eigen_engine.hip and prednet_train.hip share of the dense motion fitness (eigen_dense_score, DESIGN.md section
-// 14).  The stage is the flow objective's, whose kernels and setting rules live in the trainer's translation unit: it is defined
-// there, over plain pointers, and the engine owns the handle, the workspace and the entries.
+// dense_stage.h -- the engine's view of the dense motion fitness's stage (eigen_dense_score).  flow_stage.hip
+// defines the stage, over plain pointers; eigen_engine.hip owns the handle, the workspace and the entries.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,8 +36,8 @@ inline long long pyr_doubles(long long B, int H, int W)
     return total;
 }
 
-// The settings and the solve (null: one level, one iteration) against an H x W image, before anything is launched: the trainer's own
-// rules in the trainer's own words (eigen_last_error).  force_iterated: levels = iters = 1 goes through the iteration kernel too.
+// The settings and the solve (null: one level, one iteration) against an H x W image, before anything is launched: the flow
+// objective's own rules in its own words (eigen_last_error).  force_iterated: levels = iters = 1 goes through the iteration kernel too.
 int dense_check(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int H, int W, const uint8_t* d_mask, DenseSolve& out);
 
 // The launches of the stage on checked settings: the records of the B samples into w.rec, the field into d_flow (null: w.u)

@@ -26,7 +26,7 @@
 #include "farneback_kernels.h"
 #include "flow_kernels.h"
 #include "score_kernels.h"
-#include "dense_stage.h"   // the dense fitness's stage lives with the flow objective's kernels, in prednet_train.hip
+#include "dense_stage.h"   // the dense fitness's stage lives with the flow objective's kernels, in flow_stage.hip
 
 using namespace eig;
 

@@ -11,7 +11,7 @@
 #include <stdint.h>
 
 #include "flow_kernels.h"
-#include "train_kernels.h"
+#include "train_common.h"
 
 namespace eigt {
 

@@ -34,12 +34,6 @@ constexpr int SCORE_SLICES = 16;  // blocks per sample of the moment reductions
 constexpr int SCORE_REC = 10;     // doubles of one sample's record: N, m_rho, m_tau, m_a, m_n, V_rho, V_tau, V_n, S_b, spare
 constexpr int SCORE_K = 5;        // partial sums per slice: pass 1 fills five, pass 2 the first three
 
-// eigen_flow_score once checked
-struct TFlowScore {
-    double max_norm, min_norm, r_min, r_max, w_direction, w_strength;
-    int min_count;
-};
-
 // what the passes and the gradient need of one pixel
 struct TScorePoint {
     double px, py, dist, nrm, nx, ny, rho, tau;

@@ -42,12 +42,6 @@ constexpr int STRUCT_K = 3;        // partial sums per slice: pass 1 fills three
 constexpr int PAIR_T = 256;        // threads of a pair block, and the pixels of one LDS tile
 constexpr double STRUCT_PI = 3.141592653589793;
 
-// eigen_flow_structure_score once checked; DD = max_distance max_distance, middle = (int)(lim_hi / 2)
-struct TFlowStruct {
-    double max_norm, min_norm, lim_lo, lim_hi, DD, w0, w1, w2;
-    int structure, min_count, middle;
-};
-
 // what the passes and the gradient need of one pixel
 struct TStructPoint {
     double nrm, nx, ny;

@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "train_kernels.h"
+#include "train_common.h"
 
 namespace eigt {
 

@@ -1,65 +1,35 @@
 // prednet_train.hip -- C ABI of PredNet training (include/eigen_engine.h, eigen_trainer_*): parameter
 // layout, tape, and the launch sequence of the training forward, backprop through time, wgrad and Adam.  All compute is in
-// the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for the flow objective
-// flow_obj_kernels.h, flow_ref_kernels.h, flow_pair_kernels.h, flow_score_kernels.h, flow_struct_kernels.h, flow_corner_kernels.h and (the
-// iterated solve and its gradient) flow_iter_kernels.h, and for
-// the optimiser controls (gradient norms, accumulation, clipping, weight decay) optim_kernels.h.
+// the kernels of train_kernels.h, for the frame gradient and the refinement of stills frame_grad_kernels.h, and for
+// the optimiser controls (gradient norms, accumulation, clipping, weight decay) optim_kernels.h.  The flow objective's stage and its
+// kernels are flow_stage.hip's: this unit holds its workspace (FlowWork) and reaches it through flow_stage.h alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "../../include/eigen_engine.h"
 #include "train_kernels.h"
 #include "frame_grad_kernels.h"
-#include "flow_obj_kernels.h"
-#include "flow_ref_kernels.h"
-#include "flow_pair_kernels.h"
-#include "flow_score_kernels.h"
-#include "flow_struct_kernels.h"
-#include "flow_corner_kernels.h"
 #include "optim_kernels.h"
-#include "dense_fitness_kernels.h"
-#include "dense_pyr_kernels.h"
-#include "dense_stage.h"
-#include "flow_iter_kernels.h"
-#include "flow_target_kernels.h"
-#include "flow_valid_kernels.h"
+#include "flow_stage.h"
 
 using namespace eigt;
+using namespace eigf;
 
-int eig_set_error(int code, const char* msg);  // eigen_engine.hip: eigen_last_error's text
-
-namespace eigd {
-static int dense_solve_check(const eigen_dense_solve* solve, bool force_iterated, int H, int W, DenseSolve& out);  // below, with the dense stage
+// flow_stage.h: the one kernel of this unit that the flow stage launches
+void eigf::flow_value_final(hipStream_t st, const double* part, double numel, double* d_value)
+{
+    hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, part, STEP_LOSS_BLOCKS, 1, numel, d_value, 1);
 }
 
 namespace {
 
-int tfail(int code, const char* fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return eig_set_error(code, buf);
-}
-
-#define TCHK(x)                                                                                                            \
-    do {                                                                                                                   \
-        hipError_t _e = (x);                                                                                               \
-        if (_e != hipSuccess) return tfail(EIGEN_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(_e)); \
-    } while (0)
-
 constexpr long long SLAB_FLOATS = 16ll << 20;  // split-K slab budget of one wgrad (floats)
 constexpr int WGRAD_WAVES = 2048;              // split-K target: waves of one wgrad launch
 constexpr int LOSS_BLOCKS = 256;
-constexpr int STEP_LOSS_BLOCKS = 64;           // blocks of one step's loss reduction
 constexpr int BIAS_SLICES = 64;                // slices of one bias-gradient reduction
 
 // offsets (floats) of one layer's parameters in the flat device table; gate tensors of one source are stacked i, f, c, o
@@ -107,27 +77,8 @@ struct eigen_trainer {
     double *d_spart = nullptr, *d_step = nullptr;  // per-step loss: partials [max_steps][STEP_LOSS_BLOCKS], losses [max_steps]
     double* d_err = nullptr;                       // error-unit means err[s][l]: [max_steps][n_layers]
     float* d_absmax = nullptr;                     // eigen_trainer_still_step: max |g| of every image, [max_batch]
-    // the flow objective's float64 planes, one batch each: Ix, Iy, It [3][B H W]; q [2][B H W]; the masked value [B H W]
-    double *f_planes = nullptr, *f_q = nullptr, *f_mv = nullptr;
-    // the moving reference's: the flow u [B][2][H W], which the solve writes there when that mode asks, and rx, ry, e [3][B H W]
-    double *f_u = nullptr, *f_r = nullptr;
-    // the score mode's: one record per sample [B][SCORE_REC] and the partials of its reductions [B][SCORE_SLICES][SCORE_K]
-    double *f_rec = nullptr, *f_spart = nullptr;
-    // the structure scores' (flow_struct_kernels.h): g [B][2][H W], the record [B][STRUCT_REC] and the partials [B][STRUCT_SLICES][STRUCT_K];
-    // for Free theta and L [B][H W] each, rowS and colS [B][H W] each, and the member flags [B][H W]
-    double *f_g = nullptr, *f_srec = nullptr, *f_sspart = nullptr, *f_theta = nullptr, *f_L = nullptr;
-    int *f_rowS = nullptr, *f_colS = nullptr;
-    uint8_t* f_flag = nullptr;
-    // the corner members' (flow_corner_kernels.h), made by the first call that needs them (corner_workspace): the reference as bytes
-    // [B][C0 H W], its gray plane [B][H W], the eigenvalue plane and the candidate keys [B][H W] each, the corners [B][CORNER_MAX][2],
-    // their counts [B] and the member plane [B][H W]
-    uint8_t *c_bytes = nullptr, *c_gray = nullptr, *c_member = nullptr;
-    float *c_eig = nullptr, *c_corners = nullptr;
-    unsigned long long* c_cand = nullptr;
-    int* c_count = nullptr;
-    // the validity planes' (flow_valid_kernels.h): r_b of the current term [B]; the joint objective's: the squared error of every step [max_steps]
-    double *f_vr = nullptr, *d_jstep = nullptr;
-    double* f_stats = nullptr;  // the records of a training call's terms [max_steps][max_batch][SCORE_REC], made by the first call that asks for them
+    FlowWork fw;                                   // the flow objective's image and buffers (flow_stage.h); allocate() makes the up-front ones
+    double* d_jstep = nullptr;                     // the joint objective's: the squared error of every step [max_steps]
     // the optimiser controls' (optim_kernels.h): the (offset, count) of every tensor [n_tensors][2], the partials of the sums of squares
     // [n_tensors][NORM_SLICES], the sums [n_tensors] and the global norm [1]; the gradient accumulator [n_params], made by the first
     // call that adds to it (accumulator), and how many gradients it holds (0: empty)
@@ -136,12 +87,6 @@ struct eigen_trainer {
     double *o_part = nullptr, *o_sumsq = nullptr, *o_norm = nullptr;
     float* acc = nullptr;
     int acc_count = 0;
-    // the iterated solve's (flow_iter_kernels.h): one block that holds the pyramid, the tape and the adjoint planes of it_levels levels at
-    // it_iters iterations (iter_plan), made by the first iterated call (iter_workspace); it_force: a {1, 1} solve takes that path too
-    double* it_ws = nullptr;
-    long long it_doubles = 0;
-    int it_levels = 0, it_iters = 0;
-    bool it_force = false;
     long long tape_bytes = 0;
     bool have_weights = false;
     int state_batch = 0, state_slot = 0;  // batch and final slot of the last loss_grad / evaluate call (0: no state kept)
@@ -177,12 +122,6 @@ Table tensor_table(const eigen_trainer* t)
     }
     return tab;
 }
-
-inline unsigned blocks(long long n) { return (unsigned)((n + EW_T - 1) / EW_T); }
-
-// launch of an element-wise kernel over n elements
-template <typename K, typename... A>
-void ew(hipStream_t st, K kernel, long long n, A... a) { hipLaunchKernelGGL(kernel, dim3(blocks(n)), dim3(EW_T), 0, st, a...); }
 
 TSrc src(const float* p, long long nstride, int cin, int up, const float* w, int wmode)
 {
@@ -274,6 +213,10 @@ void plan_layout(eigen_trainer* t)
     }
     t->slab_floats = std::max(slab, SLAB_FLOATS);
     t->n_params = off;
+    // the flow stage sees the image layer and the handle's capacity, and records its lazy workspaces in the handle's list
+    FlowWork& w = t->fw;
+    w.device = cfg.device; w.C = t->ly[0].C; w.H = t->ly[0].H; w.W = t->ly[0].W; w.HW = t->ly[0].HW;
+    w.max_batch = cfg.max_batch; w.max_steps = cfg.max_steps; w.allocs = &t->allocs;
 }
 
 // every device buffer of the handle, parameters and gradients zeroed; after a failure the caller destroys t, which frees what was made
@@ -288,9 +231,10 @@ int allocate(eigen_trainer* t)
     add((void**)&t->d_part, LOSS_BLOCKS * 8); add((void**)&t->d_loss, 8);
     add((void**)&t->d_spart, T * STEP_LOSS_BLOCKS * 8); add((void**)&t->d_step, T * 8); add((void**)&t->d_err, T * L * 8);
     add((void**)&t->d_absmax, B * 4);
-    add((void**)&t->f_planes, 3 * B * t->ly[0].HW * 8); add((void**)&t->f_q, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_mv, B * t->ly[0].HW * 8);
-    add((void**)&t->f_u, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_r, 3 * B * t->ly[0].HW * 8);
-    add((void**)&t->f_rec, B * SCORE_REC * 8); add((void**)&t->f_spart, B * SCORE_SLICES * SCORE_K * 8);
+    FlowWork& fw = t->fw;
+    add((void**)&fw.f_planes, 3 * B * fw.HW * 8); add((void**)&fw.f_q, 2 * B * fw.HW * 8); add((void**)&fw.f_mv, B * fw.HW * 8);
+    add((void**)&fw.f_u, 2 * B * fw.HW * 8); add((void**)&fw.f_r, 3 * B * fw.HW * 8);
+    add((void**)&fw.f_rec, B * FLOW_REC * 8); add((void**)&fw.f_spart, B * SCORE_PART * 8);
     for (int l = 0; l < L; ++l) {
         TLayer& y = t->ly[l];
         const long long CHW = y.CHW();
@@ -304,15 +248,15 @@ int allocate(eigen_trainer* t)
         if (l > 0) add((void**)&y.dup, B * 4 * CHW * 4);  // [B][C_l][H_{l-1}][W_{l-1}]
     }
     // the structure scores' workspace comes last: the allocations above keep the order they had without it
-    add((void**)&t->f_g, 2 * B * t->ly[0].HW * 8); add((void**)&t->f_srec, B * STRUCT_REC * 8); add((void**)&t->f_sspart, B * STRUCT_SLICES * STRUCT_K * 8);
-    add((void**)&t->f_theta, B * t->ly[0].HW * 8); add((void**)&t->f_L, B * t->ly[0].HW * 8);
-    add((void**)&t->f_rowS, B * t->ly[0].HW * 4); add((void**)&t->f_colS, B * t->ly[0].HW * 4); add((void**)&t->f_flag, B * t->ly[0].HW);
+    add((void**)&fw.f_g, 2 * B * fw.HW * 8); add((void**)&fw.f_srec, B * FLOW_REC * 8); add((void**)&fw.f_sspart, B * STRUCT_PART * 8);
+    add((void**)&fw.f_theta, B * fw.HW * 8); add((void**)&fw.f_L, B * fw.HW * 8);
+    add((void**)&fw.f_rowS, B * fw.HW * 4); add((void**)&fw.f_colS, B * fw.HW * 4); add((void**)&fw.f_flag, B * fw.HW);
     // and behind it the optimiser controls' tensor table and reduction buffers
     const Table tab = tensor_table(t);
     const long long nt = t->n_tensors = (int)tab.size();
     add((void**)&t->o_tab, nt * 16); add((void**)&t->o_part, nt * NORM_SLICES * 8); add((void**)&t->o_sumsq, nt * 8); add((void**)&t->o_norm, 8);
     // and last the validity planes' r_b and the joint objective's squared-error steps
-    add((void**)&t->f_vr, B * 8); add((void**)&t->d_jstep, T * 8);
+    add((void**)&fw.f_vr, B * 8); add((void**)&t->d_jstep, T * 8);
     for (auto& w : want) {
         const hipError_t e = hipMalloc(w.first, w.second);
         if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%zu): %s", w.second, hipGetErrorString(e));
@@ -447,542 +391,6 @@ void upper_errors(eigen_trainer* t, hipStream_t st, int slot, int n, int B, doub
         reduce_steps(TERM_SUM, t, st, t->ly[l].E_at(slot, B), nullptr, 0ll, 2 * t->ly[l].CHW(), n, B, (double)(B * 2 * t->ly[l].CHW()), err + l, t->L);
 }
 
-// The flow objective's settings once checked: the window, the direction field and the mask (device, may be null) and the mask's count
-struct FlowSpec {
-    int r = 0;
-    double eps = 0.0;
-    const float* dir = nullptr;
-    const uint8_t* mask = nullptr;
-    long long mask_bstride = 0;  // the mask byte of sample b, pixel p is mask[b * mask_bstride + p]; 0: one plane shared by the batch
-    long long n_mask = 0;
-    bool moving = false;  // EIGEN_FLOW_MOVING_REFERENCE: a training call adds every term's reference path to the frame gradient
-    bool pair_pred = false;  // EIGEN_FLOW_PAIR_PREDICTION: the reference of term s is the float P0_{s-1}, in the graph
-    bool by_score = false;   // the score mode (flow_score_kernels.h): the value and q come from `score`, kappa loses the mask's count
-    TFlowScore score = {};
-    bool by_struct = false;  // a structure score (flow_struct_kernels.h): the value and q come from `sscore`, kappa as in the score mode
-    TFlowStruct sscore = {};
-    // EIGEN_FLOW_MEMBERS_CORNERS: every term's members are the corners of its own reference (corner_stage), under the shared `mask`
-    bool by_corners = false;
-    // eigen_dense_solve: the stage solves over `levels` pyramid levels with `iters` iterations each and differentiates that solve
-    bool iterated = false;
-    int levels = 1, iters = 1;
-    int max_corners = 0, block_size = 0;
-    double quality = 0.0, min_distance = 0.0;
-    // the target field of the third displacement mode (flow_target_kernels.h; null: none), doubles: sample b of term s at
-    // + b * bstride + s * tstride as [2][H W]
-    struct Target { const double* p = nullptr; long long bstride = 0, tstride = 0; } target;
-    // the validity planes under a target (flow_valid_kernels.h; null: none), bytes: sample b of term s at + b * bstride + s * tstride as [H W]
-    struct Valid { const uint8_t* p = nullptr; long long bstride = 0, tstride = 0; } valid;
-    // what divides a term's scale in kappa: B N_m, or B in the score mode, whose value is a mean over the samples alone
-    double kappa_div(int B) const { return by_score || by_struct ? (double)B : (double)(B * n_mask); }
-};
-
-// A structure score's settings, before anything is launched; a direction field does not go with them.  Every structure's rules cover
-// the fields it reads: the limits are Bands', max_distance and the weights are Free's.
-int check_flow_struct(const eigen_flow_structure_score* sc, const float* d_dir, FlowSpec& f)
-{
-    if (!sc) return EIGEN_OK;
-    if (sc->structure == 1 || sc->structure == 3)
-        return tfail(EIGEN_ERR_INVALID, "flow structure score: structure %d (Circles, CirclesFree) is the score mode's, eigen_flow_score", sc->structure);
-    if (sc->structure != STRUCT_BANDS && sc->structure != STRUCT_FREE) return tfail(EIGEN_ERR_INVALID, "flow structure score: unknown structure %d", sc->structure);
-    if (d_dir) return tfail(EIGEN_ERR_INVALID, "a flow structure score takes no direction field");
-    if (!std::isfinite(sc->max_norm) || !(sc->max_norm > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow structure score max_norm %g: must be finite and > 0", sc->max_norm);
-    if (!(sc->min_norm >= 0.0) || !(sc->min_norm < sc->max_norm))
-        return tfail(EIGEN_ERR_INVALID, "flow structure score min_norm %g: must be in [0, max_norm = %g)", sc->min_norm, sc->max_norm);
-    if (sc->min_count < 1) return tfail(EIGEN_ERR_INVALID, "flow structure score min_count %d: must be >= 1", sc->min_count);
-    TFlowStruct s = {};
-    s.structure = sc->structure; s.min_count = sc->min_count; s.max_norm = sc->max_norm; s.min_norm = sc->min_norm;
-    if (sc->structure == STRUCT_BANDS) {
-        // |lim_hi| <= 2e9: middle = (int)(lim_hi / 2) must be representable
-        if (!std::isfinite(sc->lim_lo) || !std::isfinite(sc->lim_hi) || !(sc->lim_hi >= sc->lim_lo) || std::fabs(sc->lim_hi) > 2e9)
-            return tfail(EIGEN_ERR_INVALID, "flow structure score limits %g .. %g: must be finite with lim_lo <= lim_hi and |lim_hi| <= 2e9", sc->lim_lo, sc->lim_hi);
-        s.lim_lo = sc->lim_lo; s.lim_hi = sc->lim_hi; s.middle = (int)(sc->lim_hi / 2.0);
-    } else {
-        if (!std::isfinite(sc->max_distance) || !(sc->max_distance > 0.0))
-            return tfail(EIGEN_ERR_INVALID, "flow structure score max_distance %g: must be finite and > 0", sc->max_distance);
-        double sum = 0.0;
-        for (double w : sc->w) {
-            if (!std::isfinite(w) || !(w >= 0.0)) return tfail(EIGEN_ERR_INVALID, "flow structure score weight %g: weights must be finite and >= 0", w);
-            sum += w;
-        }
-        if (!(sum > 0.0)) return tfail(EIGEN_ERR_INVALID, "all flow structure score weights are zero");
-        s.DD = sc->max_distance * sc->max_distance;
-        if (!std::isfinite(s.DD) || !(s.DD > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow structure score max_distance %g: its square must be finite and > 0", sc->max_distance);
-        s.w0 = sc->w[0]; s.w1 = sc->w[1]; s.w2 = sc->w[2];
-    }
-    f.by_struct = true;
-    f.sscore = s;
-    return EIGEN_OK;
-}
-
-// The score mode's settings, before anything is launched; a direction field does not go with them.
-int check_flow_score(const eigen_flow_score* sc, const float* d_dir, FlowSpec& f)
-{
-    if (!sc) return EIGEN_OK;
-    if (d_dir) return tfail(EIGEN_ERR_INVALID, "a flow score takes no direction field");
-    if (sc->reserved != 0) return tfail(EIGEN_ERR_INVALID, "flow score: reserved must be 0, got %d", sc->reserved);
-    if (!std::isfinite(sc->max_norm) || !(sc->max_norm > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow score max_norm %g: must be finite and > 0", sc->max_norm);
-    if (!(sc->min_norm >= 0.0) || !(sc->min_norm < sc->max_norm)) return tfail(EIGEN_ERR_INVALID, "flow score min_norm %g: must be in [0, max_norm = %g)", sc->min_norm, sc->max_norm);
-    if (!std::isfinite(sc->r_min) || !std::isfinite(sc->r_max) || !(sc->r_min >= 0.0) || !(sc->r_max >= sc->r_min))
-        return tfail(EIGEN_ERR_INVALID, "flow score limits %g .. %g: must be finite with 0 <= r_min <= r_max", sc->r_min, sc->r_max);
-    if (sc->min_count < 2) return tfail(EIGEN_ERR_INVALID, "flow score min_count %d: must be >= 2", sc->min_count);
-    for (double w : {sc->w_direction, sc->w_strength})
-        if (!std::isfinite(w) || !(w >= 0.0)) return tfail(EIGEN_ERR_INVALID, "flow score weight %g: weights must be finite and >= 0", w);
-    if (!(sc->w_direction + sc->w_strength > 0.0)) return tfail(EIGEN_ERR_INVALID, "both flow score weights are zero");
-    f.by_score = true;
-    f.score = TFlowScore{sc->max_norm, sc->min_norm, sc->r_min, sc->r_max, sc->w_direction, sc->w_strength, sc->min_count};
-    return EIGEN_OK;
-}
-
-// The settings of a flow call against the handle's image, before anything is launched.  The direction field and the mask are read back
-// to the host: every d must be finite, and kappa needs the mask's count.
-// check_flow_on: against an image of HW pixels on `device`, which is all the rules need of a handle (eigen_dense_score has no trainer).
-int check_flow_on(int device, long long HW, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, int32_t allowed_flags, FlowSpec& f)
-{
-    if (!flow) return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs its settings");
-    if (flow->radius < 1 || flow->radius > FLOW_MAX_R) return tfail(EIGEN_ERR_INVALID, "flow radius %d outside 1 .. %d", flow->radius, FLOW_MAX_R);
-    if (!std::isfinite(flow->eps) || !(flow->eps > 0.0)) return tfail(EIGEN_ERR_INVALID, "flow eps %g: must be finite and > 0", flow->eps);
-    if (flow->flags & ~allowed_flags) return tfail(EIGEN_ERR_INVALID, "flow flags 0x%x: this entry takes 0x%x at most", (unsigned)flow->flags, (unsigned)allowed_flags);
-    f.moving = (flow->flags & EIGEN_FLOW_MOVING_REFERENCE) != 0;
-    f.r = flow->radius; f.eps = flow->eps; f.dir = d_dir; f.mask = d_mask; f.n_mask = HW;
-    TCHK(hipSetDevice(device));
-    if (d_dir) {
-        std::vector<float> d(2 * HW);
-        TCHK(hipMemcpy(d.data(), d_dir, 2 * HW * 4, hipMemcpyDeviceToHost));
-        for (long long i = 0; i < 2 * HW; ++i) if (!std::isfinite(d[i])) return tfail(EIGEN_ERR_INVALID, "flow direction element %lld is not finite", i);
-    }
-    if (d_mask) {
-        std::vector<uint8_t> m(HW);
-        TCHK(hipMemcpy(m.data(), d_mask, HW, hipMemcpyDeviceToHost));
-        f.n_mask = 0;
-        for (long long i = 0; i < HW; ++i) f.n_mask += m[i] != 0;
-        if (f.n_mask == 0) return tfail(EIGEN_ERR_INVALID, "the flow mask counts no pixel");
-    }
-    return EIGEN_OK;
-}
-
-int check_flow(const eigen_trainer* t, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, int32_t allowed_flags, FlowSpec& f)
-{
-    return check_flow_on(t->cfg.device, t->ly[0].HW, flow, d_dir, d_mask, allowed_flags, f);
-}
-
-// The solve of a flow call (null: the single step) against the handle's image, by eigen_dense_solve's own rules in their own words
-int check_solve(const eigen_trainer* t, const eigen_dense_solve* solve, FlowSpec& f)
-{
-    eigd::DenseSolve s;
-    const int rc = eigd::dense_solve_check(solve, t->it_force, t->ly[0].H, t->ly[0].W, s);
-    if (rc) return rc;
-    f.iterated = s.iterated; f.levels = s.levels; f.iters = s.iters;
-    return EIGEN_OK;
-}
-
-// The corner members' workspace, made by the first call that needs it and freed with the handle; the tape and every other use of the
-// handle keep the memory they had.
-int corner_workspace(eigen_trainer* t)
-{
-    if (t->c_member) return EIGEN_OK;
-    const long long B = t->cfg.max_batch, HW = t->ly[0].HW;
-    TCHK(hipSetDevice(t->cfg.device));
-    const std::pair<void**, long long> want[] = {{(void**)&t->c_bytes, B * t->ly[0].CHW()}, {(void**)&t->c_gray, B * HW}, {(void**)&t->c_eig, B * HW * 4},
-                                                 {(void**)&t->c_cand, B * HW * 8}, {(void**)&t->c_corners, B * CORNER_MAX * 2 * 4}, {(void**)&t->c_count, B * 4},
-                                                 {(void**)&t->c_member, B * HW}};
-    // all or nothing: the handle takes the buffers once every one of them exists, a failure frees what it made
-    std::vector<void*> made;
-    for (const auto& w : want) {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, (size_t)w.second);
-        if (e != hipSuccess) {
-            for (void* q : made) (void)hipFree(q);
-            return tfail(EIGEN_ERR_HIP, "hipMalloc(%lld): %s", w.second, hipGetErrorString(e));
-        }
-        made.push_back(p);
-    }
-    for (size_t i = 0; i < made.size(); ++i) {
-        *want[i].first = made[i];
-        t->allocs.push_back(made[i]);
-    }
-    return EIGEN_OK;
-}
-
-// The records of a training call's terms, [max_steps][max_batch][SCORE_REC] doubles on the device, made by the first call that asks for
-// them (h_stats) and freed with the handle
-int stats_workspace(eigen_trainer* t)
-{
-    if (t->f_stats) return EIGEN_OK;
-    TCHK(hipSetDevice(t->cfg.device));
-    void* p = nullptr;
-    TCHK(hipMalloc(&p, (size_t)t->cfg.max_steps * t->cfg.max_batch * SCORE_REC * 8));
-    t->f_stats = (double*)p;
-    t->allocs.push_back(p);
-    return EIGEN_OK;
-}
-
-// The members of a call, before anything is launched (eigen_flow_members): f.mask, its stride and the corner settings.  check_flow has
-// seen d_mask only where it is the shared plane (per_sample_mask says when it is not).
-bool per_sample_mask(const eigen_flow_members* mem) { return mem && mem->kind == EIGEN_FLOW_MEMBERS_MASK; }
-
-int check_flow_members(eigen_trainer* t, const eigen_flow_members* mem, const uint8_t* d_mask, int B, FlowSpec& f)
-{
-    if (!mem) return EIGEN_OK;
-    if (!f.by_score && !f.by_struct) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
-    if (mem->kind != EIGEN_FLOW_MEMBERS_MASK && mem->kind != EIGEN_FLOW_MEMBERS_CORNERS) return tfail(EIGEN_ERR_INVALID, "flow members: unknown kind %d", mem->kind);
-    if (mem->reserved != 0) return tfail(EIGEN_ERR_INVALID, "flow members: reserved must be 0, got %d", mem->reserved);
-    const long long HW = t->ly[0].HW;
-    if (mem->kind == EIGEN_FLOW_MEMBERS_MASK) {
-        if (!d_mask) return tfail(EIGEN_ERR_INVALID, "flow members: EIGEN_FLOW_MEMBERS_MASK needs d_mask, one plane per sample");
-        if (mem->mask_bstride < HW) return tfail(EIGEN_ERR_INVALID, "flow members: mask_bstride %lld is smaller than one plane (%lld bytes)", (long long)mem->mask_bstride, HW);
-        // one copy of the B planes; a score does not read the count (kappa divides by the batch), so the first counted pixel settles it
-        std::vector<uint8_t> m((size_t)B * HW);
-        TCHK(hipMemcpy2D(m.data(), HW, d_mask, mem->mask_bstride, HW, B, hipMemcpyDeviceToHost));
-        if (std::find_if(m.begin(), m.end(), [](uint8_t v) { return v != 0; }) == m.end()) return tfail(EIGEN_ERR_INVALID, "the flow mask counts no pixel");
-        f.mask = d_mask; f.mask_bstride = mem->mask_bstride;
-        return EIGEN_OK;
-    }
-    if (mem->max_corners < 1 || mem->max_corners > CORNER_MAX) return tfail(EIGEN_ERR_INVALID, "flow members: max_corners %d outside 1 .. %d", mem->max_corners, CORNER_MAX);
-    if (mem->block_size < 1 || mem->block_size > eig::EIG_MAXB) return tfail(EIGEN_ERR_INVALID, "flow members: block_size %d outside 1 .. %d", mem->block_size, eig::EIG_MAXB);
-    if (!(mem->quality_level > 0.0) || !(mem->quality_level <= 1.0)) return tfail(EIGEN_ERR_INVALID, "flow members: quality_level %g: must be in (0, 1]", mem->quality_level);
-    if (!std::isfinite(mem->min_distance) || !(mem->min_distance >= 0.0)) return tfail(EIGEN_ERR_INVALID, "flow members: min_distance %g: must be finite and >= 0", mem->min_distance);
-    if (mem->mask_bstride != 0) return tfail(EIGEN_ERR_INVALID, "flow members: mask_bstride %lld: must be 0 with EIGEN_FLOW_MEMBERS_CORNERS (d_mask is the shared plane)", (long long)mem->mask_bstride);
-    f.by_corners = true;
-    f.max_corners = mem->max_corners; f.block_size = mem->block_size; f.quality = mem->quality_level; f.min_distance = mem->min_distance;
-    return corner_workspace(t);
-}
-
-// The member planes of one reference into t->c_member, the corner counts into t->c_count (flow_corner_kernels.h): the fitness path's own
-// launches of eigen_flow on the bytes the fitness would see.  f.mask is the shared plane, or null.
-void corner_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const uint8_t* ref, const float* fref, long long r_bstride)
-{
-    const TLayer& y = t->ly[0];
-    const int H = y.H, W = y.W, HW = (int)y.HW;
-    if (fref) {
-        ew(st, tcorner_quant_kernel, B * y.CHW(), fref, r_bstride, y.CHW(), B * y.CHW(), t->c_bytes);
-        ref = t->c_bytes; r_bstride = y.CHW();
-    }
-    hipLaunchKernelGGL(eig::gray_kernel, dim3((HW + 255) / 256, B), dim3(256), 0, st, ref, r_bstride, y.C, HW, t->c_gray, B);
-    const double sc = 1.0 / ((double)(1 << 2) * f.block_size * 255.0);
-    const float SC = (float)(sc * sc);
-    hipLaunchKernelGGL(eig::mineig_kernel, dim3((W + eig::EIG_T - 1) / eig::EIG_T, (H + eig::EIG_T - 1) / eig::EIG_T, B), dim3(256), 0, st, (const uint8_t*)t->c_gray, H, W,
-                       f.block_size, SC, t->c_eig);
-    hipLaunchKernelGGL(eig::corner_select_kernel, dim3(B), dim3(1024), 0, st, (const float*)t->c_eig, H, W, f.quality, (float)f.min_distance, f.max_corners, t->c_cand,
-                       t->c_corners, t->c_count);
-    hipLaunchKernelGGL(tcorner_member_kernel, dim3(B), dim3(CORNER_T), 0, st, (const float*)t->c_corners, (const int*)t->c_count, f.max_corners, H, W, f.mask,
-                       t->c_member);
-}
-
-// The gradient of the term by its reference, from the planes and q the flow stage of the same term left in the workspace and its flow
-// at d_flow: into d_refg (sample b at + b * rg_bstride), added in float or stored.  A training call under the prediction pairing runs
-// this apart from the stage, once layer 0's terr_bwd of the step has written dP0_{s-1}.
-void flow_ref_path(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, double kappa, const double* d_flow, float* d_refg, long long rg_bstride,
-                   int rg_accumulate)
-{
-    const TLayer& y = t->ly[0];
-    const long long n = (long long)B * y.HW;
-    const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-    hipLaunchKernelGGL(tflow_ref_sums_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, d_flow, n, y.H, y.W, f.r, kappa, t->f_r);
-    ew(st, tflow_ref_fold_kernel, n, (const double*)t->f_r, n, y.H, y.W, y.C, d_refg, rg_bstride, rg_accumulate);
-}
-
-// One term for the flow stage and what is wanted of it; every target may be null.  Sample b of an image is at its pointer + b * its stride.
-struct FlowTerm {
-    const float* pred = nullptr; long long p_bstride = 0;
-    const uint8_t* ref = nullptr; const float* fref = nullptr; long long r_bstride = 0;  // the reference as bytes, or as floats (flow_pair_kernels.h): exactly one
-    double kappa = 0.0;                                                   // the scale of the seed and of the reference gradient
-    double *part = nullptr, *d_value = nullptr;                           // the value into d_value, through the STEP_LOSS_BLOCKS partials at part
-    double* d_flow = nullptr;                                             // the flow u [B][2][H W]
-    float* d_seed = nullptr; long long s_bstride = 0; int s_accumulate = 0;   // kappa d value / d pred, added in float or stored
-    float* d_refg = nullptr; long long rg_bstride = 0; int rg_accumulate = 0; // kappa d value / d reference (flow_ref_kernels.h), likewise
-    const double* target = nullptr;                                           // this term's target field (null: none), sample b at + b * FlowSpec's target.bstride
-    const uint8_t* valid = nullptr;                                           // this term's validity planes (null: none), sample b at + b * FlowSpec's valid.bstride
-};
-
-// A target field's rules, before anything is launched or allocated (null: none, and the strides are not read): it is a displacement mode
-// of its own, so no direction, score or members go with it, and a sample's [2][H W] doubles must fit its strides.
-int check_flow_target(const eigen_trainer* t, const double* d_target, long long t_bstride, long long t_tstride, int n_terms, bool by_flow, const float* d_dir,
-                      const void* score, const void* sscore, const void* members, FlowSpec& f)
-{
-    if (!d_target) return EIGEN_OK;
-    if (!by_flow) return tfail(EIGEN_ERR_INVALID, "a flow target goes with EIGEN_OBJ_FLOW only");
-    if (d_dir || score || sscore || members) return tfail(EIGEN_ERR_INVALID, "a flow target takes no direction field, score or members");
-    const long long field = 2 * t->ly[0].HW;
-    if (t_bstride < field) return tfail(EIGEN_ERR_INVALID, "t_bstride %lld is smaller than one field (%lld doubles)", t_bstride, field);
-    if (n_terms > 1 && t_tstride < field) return tfail(EIGEN_ERR_INVALID, "t_tstride %lld is smaller than one field (%lld doubles)", t_tstride, field);
-    f.target.p = d_target; f.target.bstride = t_bstride; f.target.tstride = t_tstride;
-    return EIGEN_OK;
-}
-
-// The validity planes' rules, after check_flow_target and before anything is launched or allocated (null: none, and the strides are not
-// read): they weigh a target's endpoint error, and a sample's [H W] bytes must fit their strides.
-int check_flow_valid(const eigen_trainer* t, const uint8_t* d_valid, long long v_bstride, long long v_tstride, int n_terms, FlowSpec& f)
-{
-    if (!d_valid) return EIGEN_OK;
-    if (!f.target.p) return tfail(EIGEN_ERR_INVALID, "validity planes go with a flow target only");
-    const long long HW = t->ly[0].HW;
-    if (v_bstride < HW) return tfail(EIGEN_ERR_INVALID, "v_bstride %lld is smaller than one plane (%lld bytes)", v_bstride, HW);
-    if (n_terms > 1 && v_tstride < HW) return tfail(EIGEN_ERR_INVALID, "v_tstride %lld is smaller than one plane (%lld bytes)", v_tstride, HW);
-    f.valid.p = d_valid; f.valid.bstride = v_bstride; f.valid.tstride = v_tstride;
-    return EIGEN_OK;
-}
-
-// The value and q of a structure score from the u the solve just wrote (flow_struct_kernels.h): two passes of moments, for Free the
-// prepare and the pair pass between them, then (want_q) the gradient g and q over what the solve left in f_q.
-// with_q false (the iterated solve, whose gradient takes g itself): g is left in f_g and q is not formed.
-template <int STRUCT>
-void struct_stage_of(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value, bool want_q, bool with_q)
-{
-    const TLayer& y = t->ly[0];
-    const long long n = (long long)B * y.HW;
-    const dim3 sgrid(STRUCT_SLICES, (unsigned)B);
-    const TFlowStruct& s = f.sscore;
-    if (STRUCT == STRUCT_FREE) ew(st, tflow_free_prepare_kernel, n, u, n, y.H, y.W, f.mask, f.mask_bstride, s, t->f_theta, t->f_flag);
-    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 1>), sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, s, (const double*)t->f_srec, (const double*)t->f_L, t->f_sspart);
-    hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 1>), dim3(B), dim3(64), 0, st, (const double*)t->f_sspart, B, s, t->f_srec, (double*)nullptr);
-    if (STRUCT == STRUCT_FREE)
-        hipLaunchKernelGGL(tflow_free_pair_kernel, dim3((unsigned)((y.HW + PAIR_T - 1) / PAIR_T), (unsigned)B), dim3(PAIR_T), 0, st, (const double*)t->f_theta,
-                           (const uint8_t*)t->f_flag, y.H, y.W, s.DD, t->f_L, t->f_rowS, t->f_colS);
-    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 2>), sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, s, (const double*)t->f_srec, (const double*)t->f_L, t->f_sspart);
-    hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 2>), dim3(B), dim3(64), 0, st, (const double*)t->f_sspart, B, s, t->f_srec, d_value);
-    if (!want_q) return;
-    ew(st, tflow_struct_grad_kernel<STRUCT>, n, u, n, y.H, y.W, f.mask, f.mask_bstride, s, (const double*)t->f_srec, (const int*)t->f_rowS, (const int*)t->f_colS, t->f_g);
-    if (!with_q) return;
-    const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-    hipLaunchKernelGGL(tflow_struct_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_g, n, y.H, y.W, f.r, f.eps, t->f_q);
-}
-
-void struct_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value, bool want_q, bool with_q = true)
-{
-    if (f.sscore.structure == STRUCT_BANDS) struct_stage_of<STRUCT_BANDS>(t, st, B, f, u, d_value, want_q, with_q);
-    else struct_stage_of<STRUCT_FREE>(t, st, B, f, u, d_value, want_q, with_q);
-}
-
-// The value of the score mode from the u a solve wrote: two passes of moments into the samples' records
-void score_passes(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* u, double* d_value)
-{
-    const TLayer& y = t->ly[0];
-    const dim3 sgrid(SCORE_SLICES, (unsigned)B);
-    hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_spart);
-    hipLaunchKernelGGL(tflow_score_final_kernel<1>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, (double*)nullptr);
-    hipLaunchKernelGGL(tflow_score_moment_kernel<2>, sgrid, dim3(EW_T), 0, st, u, y.H, y.W, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_spart);
-    hipLaunchKernelGGL(tflow_score_final_kernel<2>, dim3(B), dim3(64), 0, st, (const double*)t->f_spart, B, f.score, t->f_rec, d_value);
-}
-
-// ---- the iterated solve and its gradient (flow_iter_kernels.h, DESIGN.md section 13, "The iterated solve's gradient")
-// One level's planes in the handle's block, each over max_batch samples: the gray images, the Scharr pair, the tape and beta
-// [iters][B][2][H W], the gradient arriving at the level's field, the level's field (levels >= 1; level 0's goes where the call wants it)
-// and the gradients by the level's images
-struct IterLevel {
-    int H, W;
-    double *I0, *I1, *gxy, *tape, *beta, *ubK, *u, *I0b, *I1b;
-};
-
-// and what the levels share, at level 0's size: ub_0 [B][2], (ab, bb, cb) [B][3], (Ixb, Iyb) [B][2], I0b's direct term [B], max |u| [B]
-struct IterPlan {
-    IterLevel lv[eigd::DENSE_MAX_LEVELS];
-    double *ub0, *abc, *rxy, *dir, *umax;
-    long long doubles;
-};
-
-// the block's layout for a solve of `levels` x `iters` (pointers relative to `at`, which may be null: the size alone)
-IterPlan iter_plan(const eigen_trainer* t, double* at, int levels, int iters)
-{
-    IterPlan pl;
-    const long long Bm = t->cfg.max_batch;
-    double* p = at;
-    auto take = [&](long long n) { double* q = p; p += n; return q; };
-    int h = t->ly[0].H, w = t->ly[0].W;
-    for (int l = 0; l < levels; ++l, h = (h + 1) / 2, w = (w + 1) / 2) {
-        const long long n = Bm * h * w;
-        IterLevel& v = pl.lv[l];
-        v.H = h; v.W = w;
-        v.I0 = take(n); v.I1 = take(n); v.gxy = take(2 * n); v.tape = take(2 * n * iters); v.beta = take(2 * n * iters);
-        v.ubK = take(2 * n); v.u = take(2 * n); v.I0b = take(n); v.I1b = take(n);
-    }
-    const long long n0 = Bm * t->ly[0].HW;
-    pl.ub0 = take(2 * n0); pl.abc = take(3 * n0); pl.rxy = take(2 * n0); pl.dir = take(n0); pl.umax = take(Bm);
-    pl.doubles = (long long)(p - at);
-    return pl;
-}
-
-// The block, made by the first iterated call and freed with the handle: one allocation, so all of it or none.  A later call with more
-// levels or iterations replaces it by one that holds both; a handle that never asks holds none.
-int iter_workspace(eigen_trainer* t, int levels, int iters)
-{
-    if (t->it_ws && levels <= t->it_levels && iters <= t->it_iters) return EIGEN_OK;
-    const int L = std::max(levels, t->it_levels), K = std::max(iters, t->it_iters);
-    const long long doubles = iter_plan(t, nullptr, L, K).doubles;
-    TCHK(hipSetDevice(t->cfg.device));
-    if (!t->it_ws) {
-        // once per handle, checked: the two tiled kernels may ask for the dynamic LDS of the largest radius (radius 11 and above is more than
-        // a launch gets without the attribute)
-        const int lds = pyr_lds_doubles(FLOW_MAX_R) * 8;
-        TCHK(hipFuncSetAttribute((const void*)tfiter_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        TCHK(hipFuncSetAttribute((const void*)tfiter_adj_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, (size_t)doubles * 8);
-    if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%lld): %s", doubles * 8, hipGetErrorString(e));
-    if (t->it_ws) {
-        TCHK(hipFree(t->it_ws));  // waits for whatever still reads it
-        t->allocs.erase(std::find(t->allocs.begin(), t->allocs.end(), (void*)t->it_ws));
-    }
-    t->allocs.push_back(p);
-    t->it_ws = (double*)p; t->it_doubles = doubles; t->it_levels = L; t->it_iters = K;
-    return EIGEN_OK;
-}
-
-// The forward: the gray planes, the pyramid, then one launch per level from the coarsest to the finest; level 0's field goes into d_flow
-void iter_forward(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const float* pred, long long p_bstride, const uint8_t* ref, const float* fref,
-                  long long r_bstride, double* d_flow)
-{
-    const TLayer& y = t->ly[0];
-    IterPlan pl = iter_plan(t, t->it_ws, f.levels, f.iters);
-    IterLevel* lv = pl.lv;
-    const long long n0 = (long long)B * y.HW;
-    if (fref) ew(st, tfiter_gray_kernel<float>, n0, pred, p_bstride, fref, r_bstride, y.C, y.H, y.W, n0, lv[0].I0, lv[0].I1);
-    else ew(st, tfiter_gray_kernel<uint8_t>, n0, pred, p_bstride, ref, r_bstride, y.C, y.H, y.W, n0, lv[0].I0, lv[0].I1);
-    for (int l = 1; l < f.levels; ++l) {
-        const long long n = (long long)B * lv[l].H * lv[l].W;
-        ew(st, tdense_pyrdown_kernel, n, (const double*)lv[l - 1].I0, (const double*)lv[l - 1].I1, lv[l - 1].H, lv[l - 1].W, lv[l].H, lv[l].W, n, lv[l].I0, lv[l].I1);
-    }
-    const int lds = pyr_lds_doubles(f.r) * 8;  // iter_workspace has set the attribute that lets a launch ask for it
-    for (int l = f.levels - 1; l >= 0; --l) {
-        const bool top = l == f.levels - 1;
-        const dim3 grid((unsigned)((lv[l].W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((lv[l].H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-        hipLaunchKernelGGL(tfiter_fwd_kernel, grid, dim3(FLOW_T), (size_t)lds, st, (const double*)lv[l].I0, (const double*)lv[l].I1, lv[l].H, lv[l].W, f.r, f.eps, f.iters,
-                           top ? (const double*)nullptr : (const double*)lv[l + 1].u, top ? 0 : lv[l + 1].H, top ? 0 : lv[l + 1].W, l ? lv[l].u : d_flow, lv[l].tape,
-                           lv[l].gxy);
-    }
-}
-
-// The backward from g = d value / d u of level 0 [B][2][H W]: the levels from the finest to the coarsest, then the pyramid's adjoint from
-// the coarsest to the finest.  Leaves the gradients by the gray images of level 0 in the plan's lv[0].I1b (prediction) and lv[0].I0b
-// (reference), unscaled.
-void iter_backward(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const double* g)
-{
-    IterPlan pl = iter_plan(t, t->it_ws, f.levels, f.iters);
-    IterLevel* lv = pl.lv;
-    const int lds = pyr_lds_doubles(f.r) * 8;
-    for (int l = 0; l < f.levels; ++l) {
-        const IterLevel& v = lv[l];
-        const long long HW = (long long)v.H * v.W, n = B * HW;
-        const double* ubK = l ? (const double*)v.ubK : g;
-        const dim3 grid((unsigned)((v.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((v.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-        hipLaunchKernelGGL(tfiter_umax_kernel, dim3(B), dim3(EW_T), 0, st, (const double*)v.tape, f.iters, HW, pl.umax);
-        hipLaunchKernelGGL(tfiter_adj_kernel, grid, dim3(FLOW_T), (size_t)lds, st, (const double*)v.I0, (const double*)v.I1, v.H, v.W, f.r, f.eps, f.iters,
-                           (const double*)v.tape, ubK, v.beta, pl.abc, pl.ub0);
-        ew(st, tfiter_i1_kernel, n, (const double*)v.tape, (const double*)v.beta, (const double*)v.gxy, (const double*)pl.umax, B, v.H, v.W, f.r, f.iters, n, v.I1b);
-        ew(st, tfiter_q_kernel, n, (const double*)v.I0, (const double*)v.I1, (const double*)v.tape, (const double*)v.beta, (const double*)pl.abc, (const double*)v.gxy, B,
-           v.H, v.W, f.r, f.iters, n, pl.rxy, pl.dir);
-        ew(st, tfiter_i0_kernel, n, (const double*)pl.rxy, (const double*)pl.dir, v.H, v.W, n, v.I0b);
-        if (l < f.levels - 1) {
-            const long long nc = (long long)B * lv[l + 1].H * lv[l + 1].W;
-            ew(st, tfiter_down_kernel, nc, (const double*)pl.ub0, v.H, v.W, lv[l + 1].H, lv[l + 1].W, nc, lv[l + 1].ubK);
-        }
-    }
-    for (int l = f.levels - 2; l >= 0; --l) {
-        const long long n = (long long)B * lv[l].H * lv[l].W;
-        ew(st, tfiter_pyr_adj_kernel, n, (const double*)lv[l + 1].I0b, (const double*)lv[l + 1].I1b, lv[l].H, lv[l].W, lv[l + 1].H, lv[l + 1].W, n, lv[l].I0b, lv[l].I1b);
-    }
-}
-
-// kappa times the gradient by the prediction (by_ref false) or by the reference (true) the last iter_backward left, as floats: stored or
-// added at out (sample b at + b * bstride).  A training call under the prediction pairing adds the reference's apart from the stage, where
-// the single step runs flow_ref_path.
-void iter_store(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, bool by_ref, double kappa, float* out, long long bstride, int accumulate)
-{
-    const TLayer& y = t->ly[0];
-    const IterPlan pl = iter_plan(t, t->it_ws, f.levels, f.iters);
-    const long long n = (long long)B * y.HW;
-    ew(st, tfiter_store_kernel, n, (const double*)(by_ref ? pl.lv[0].I0b : pl.lv[0].I1b), kappa, y.C, y.HW, n, out, bstride, accumulate);
-}
-
-// mv and g of the target mode from the field u, for either solve: tflow_target_kernel, or under the term's validity planes the samples'
-// counts and tflow_target_valid_kernel (flow_valid_kernels.h)
-void target_value(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m, const double* u)
-{
-    const TLayer& y = t->ly[0];
-    const long long n = (long long)B * y.HW;
-    if (!m.valid) {
-        ew(st, tflow_target_kernel, n, u, m.target, f.target.bstride, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
-        return;
-    }
-    hipLaunchKernelGGL(tflow_valid_count_kernel, dim3(B), dim3(EW_T), 0, st, m.valid, f.valid.bstride, f.mask, f.mask_bstride, y.HW, f.n_mask, t->f_vr);
-    ew(st, tflow_target_valid_kernel, n, u, m.target, f.target.bstride, f.mask, f.mask_bstride, m.valid, f.valid.bstride, (const double*)t->f_vr, y.HW, n, t->f_mv, t->f_g);
-}
-
-// The flow stage of one term under an iterated solve: the field of level 0 from iter_forward, the unchanged value / score kernels on it,
-// which leave g = d value / d u (masked) in f_g, then iter_backward and the level-0 stores.  The field goes to the handle's workspace
-// unless the caller wants it.
-void iter_flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m)
-{
-    const TLayer& y = t->ly[0];
-    const long long n = (long long)B * y.HW;
-    double* u = m.d_flow ? m.d_flow : t->f_u;
-    iter_forward(t, st, B, f, m.pred, m.p_bstride, m.ref, m.fref, m.r_bstride, u);
-    const bool grads = m.d_seed || m.d_refg;
-    if (f.by_score) {
-        score_passes(t, st, B, f, u, m.d_value);
-        if (grads) ew(st, tfiter_score_g_kernel, n, (const double*)u, y.H, y.W, n, f.mask, f.mask_bstride, f.score, (const double*)t->f_rec, t->f_g);
-    } else if (f.by_struct) {
-        struct_stage(t, st, B, f, u, m.d_value, grads, false);
-    } else {
-        if (m.target) target_value(t, st, B, f, m, u);
-        else ew(st, tfiter_value_kernel, n, (const double*)u, f.dir, f.mask, f.mask_bstride, y.HW, n, t->f_mv, t->f_g);
-        if (m.d_value) {
-            hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
-            hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)m.part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), m.d_value, 1);
-        }
-    }
-    if (!grads) return;
-    iter_backward(t, st, B, f, t->f_g);
-    if (m.d_seed) iter_store(t, st, B, f, false, m.kappa, m.d_seed, m.s_bstride, m.s_accumulate);
-    if (m.d_refg) iter_store(t, st, B, f, true, m.kappa, m.d_refg, m.rg_bstride, m.rg_accumulate);
-}
-
-// The flow stage of one term (eigen_trainer_flow_term states the arithmetic): the planes, the tiled solve, then what is wanted of the
-// value, the flow and the seed.  A reference gradient is formed from the planes, q and u this stage leaves: u is then written to the
-// handle's workspace unless the caller wants it anyway.
-void flow_stage(eigen_trainer* t, hipStream_t st, int B, const FlowSpec& f, const FlowTerm& m)
-{
-    if (f.by_corners) {
-        // the term's members from its own reference, then the stage under them as a per-sample mask
-        corner_stage(t, st, B, f, m.ref, m.fref, m.r_bstride);
-        FlowSpec g = f;
-        g.by_corners = false; g.mask = t->c_member; g.mask_bstride = t->ly[0].HW;
-        return flow_stage(t, st, B, g, m);
-    }
-    if (f.iterated) return iter_flow_stage(t, st, B, f, m);
-    double* d_flow = (m.d_refg || f.by_score || f.by_struct || m.target) && !m.d_flow ? t->f_u : m.d_flow;
-    const TLayer& y = t->ly[0];
-    const long long n = (long long)B * y.HW;
-    if (m.fref) ew(st, tflow_pair_prep_kernel, n, m.pred, m.p_bstride, m.fref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
-    else ew(st, tflow_prep_kernel, n, m.pred, m.p_bstride, m.ref, m.r_bstride, y.C, y.H, y.W, n, t->f_planes);
-    const dim3 grid((unsigned)((y.W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((y.H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-    hipLaunchKernelGGL(tflow_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, n, y.H, y.W, f.r, f.eps, f.dir, f.mask, f.mask_bstride, t->f_q, t->f_mv, d_flow);
-    if (f.by_score) {
-        // the value and q of the score mode, from the u the solve just wrote: two passes of moments, then q over what the solve left in f_q
-        const double* u = d_flow;
-        score_passes(t, st, B, f, u, m.d_value);
-        if (m.d_seed || m.d_refg)
-            hipLaunchKernelGGL(tflow_score_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, u, n, y.H, y.W, f.r, f.eps, f.mask, f.mask_bstride, f.score,
-                               (const double*)t->f_rec, t->f_q);
-    } else if (f.by_struct) {
-        struct_stage(t, st, B, f, d_flow, m.d_value, m.d_seed || m.d_refg);
-    } else if (m.target) {
-        // the target mode: mv and g from the u the solve just wrote, then q from g over the solve's own a, b, c and det
-        target_value(t, st, B, f, m, d_flow);
-        if (m.d_seed || m.d_refg)
-            hipLaunchKernelGGL(tflow_struct_q_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_g, n, y.H, y.W, f.r, f.eps, t->f_q);
-    }
-    if (!f.by_score && !f.by_struct && m.d_value) {
-        hipLaunchKernelGGL(tflow_sum_kernel, dim3(STEP_LOSS_BLOCKS), dim3(EW_T), 0, st, (const double*)t->f_mv, n, m.part);
-        hipLaunchKernelGGL(tloss_step_final_kernel, dim3(1), dim3(64), 0, st, (const double*)m.part, STEP_LOSS_BLOCKS, 1, (double)(B * f.n_mask), m.d_value, 1);
-    }
-    if (m.d_seed)
-        hipLaunchKernelGGL(tflow_seed_kernel, grid, dim3(FLOW_T), 0, st, (const double*)t->f_planes, (const double*)t->f_q, n, y.H, y.W, y.C, f.r, m.kappa, m.d_seed,
-                           m.s_bstride, m.s_accumulate);
-    if (m.d_refg) flow_ref_path(t, st, B, f, m.kappa, d_flow, m.d_refg, m.rg_bstride, m.rg_accumulate);
-}
-
 // The loss of one loss_grad call: the weights of its terms and the seeds they put into the backward pass.
 struct Objective {
     bool by_error = false;
@@ -1101,15 +509,15 @@ int backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, c
                 if (o.flow.valid.p) m.valid = o.flow.valid.p + (long long)s * o.flow.valid.tstride;
                 if (o.flow.pair_pred) {
                     m.fref = y.P_at(s, B); m.r_bstride = CHW;
-                    m.d_flow = s >= 1 ? t->f_u : nullptr;
+                    m.d_flow = s >= 1 ? t->fw.f_u : nullptr;
                 } else {
                     m.ref = xn; m.r_bstride = bstride;
                     m.d_refg = o.flow.moving && fg.p ? fg.p + (long long)(s + 1) * fg.tstride : nullptr; m.rg_bstride = fg.bstride; m.rg_accumulate = 1;
                 }
-                flow_stage(t, st, B, o.flow, m);
+                flow_stage(t->fw, st, B, o.flow, m);
                 // the samples' records of this term, which the next term's stage overwrites: kept on the device, read once the call is done
                 if (o.keep_stats)
-                    TCHK(hipMemcpyAsync(t->f_stats + (long long)s * B * SCORE_REC, o.flow.by_score ? t->f_rec : t->f_srec, (size_t)B * SCORE_REC * 8,
+                    TCHK(hipMemcpyAsync(t->fw.f_stats + (long long)s * B * FLOW_REC, o.flow.by_score ? t->fw.f_rec : t->fw.f_srec, (size_t)B * FLOW_REC * 8,
                                         hipMemcpyDeviceToDevice, st));
             }
             // the joint objective keeps the frame: the squared error's seed joins the flow term's in dP0_s
@@ -1154,8 +562,8 @@ int backward_step(eigen_trainer* t, hipStream_t st, const Objective& o, int s, c
     // the prediction pairing: dP0_{s-1} holds what layer 0's terr_bwd of this step left; term s adds its gradient by its reference
     // P0_{s-1} now, and the seed of term s - 1 follows in backward_step(s - 1), ahead of that step's clamp mask
     if (o.by_flow && o.flow.pair_pred && s >= 1 && s < T - 1 && o.weight(s) != 0.0) {
-        if (o.flow.iterated) iter_store(t, st, B, o.flow, true, o.flow_kappa(s), t->ly[0].dPn, t->ly[0].CHW(), 1);
-        else flow_ref_path(t, st, B, o.flow, o.flow_kappa(s), t->f_u, t->ly[0].dPn, t->ly[0].CHW(), 1);
+        if (o.flow.iterated) iter_store(t->fw, st, B, o.flow, true, o.flow_kappa(s), t->ly[0].dPn, t->ly[0].CHW(), 1);
+        else flow_ref_path(t->fw, st, B, o.flow, o.flow_kappa(s), t->fw.f_u, t->ly[0].dPn, t->ly[0].CHW(), 1);
     }
     return EIGEN_OK;
 }
@@ -1324,13 +732,13 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     }
     Objective o;
     const bool by_flow = c.objective == EIGEN_OBJ_FLOW;
-    rc = check_flow_target(t, c.d_target, c.t_bstride, c.t_tstride, T - 1, by_flow, c.d_dir, c.score, c.sscore, c.members, o.flow);
+    rc = check_flow_target(t->fw, c.d_target, c.t_bstride, c.t_tstride, T - 1, by_flow, c.d_dir, c.score, c.sscore, c.members, o.flow);
     if (rc) return rc;
     if (c.joint) {
         const double mu = c.joint->frame_weight;
         if (!std::isfinite(mu) || mu < 0.0) return tfail(EIGEN_ERR_INVALID, "frame_weight %g: must be finite and >= 0", mu);
         if (mu > 0.0 && !by_flow) return tfail(EIGEN_ERR_INVALID, "a frame weight goes with EIGEN_OBJ_FLOW only");
-        rc = check_flow_valid(t, c.joint->d_valid, c.joint->v_bstride, c.joint->v_tstride, T - 1, o.flow);
+        rc = check_flow_valid(t->fw, c.joint->d_valid, c.joint->v_bstride, c.joint->v_tstride, T - 1, o.flow);
         if (rc) return rc;
         o.mu = mu; o.h_parts = c.joint->h_parts;
     }
@@ -1343,9 +751,12 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     if (rc) return rc;
     if (!by_flow && c.solve) return tfail(EIGEN_ERR_INVALID, "a dense solve goes with EIGEN_OBJ_FLOW only");
     if (by_flow) {
-        rc = check_solve(t, c.solve, o.flow);  // ahead of the mask's read-back and of every allocation
+        FlowWork& fw = t->fw;
+        eigd::DenseSolve solve;
+        rc = eigd::dense_solve_check(c.solve, fw.it_force, fw.H, fw.W, solve);  // ahead of the mask's read-back and of every allocation
         if (rc) return rc;
-        rc = check_flow(t, c.flow, c.d_dir, per_sample_mask(c.members) ? nullptr : c.d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
+        o.flow.set_solve(solve);
+        rc = check_flow_on(fw.device, fw.HW, c.flow, c.d_dir, per_sample_mask(c.members) ? nullptr : c.d_mask, EIGEN_FLOW_MOVING_REFERENCE, o.flow);
         if (rc) return rc;
         o.flow.pair_pred = c.pairing == EIGEN_FLOW_PAIR_PREDICTION;
         // a frame is no reference under the prediction pairing: there is nothing the flag could move
@@ -1355,17 +766,17 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
         rc = check_flow_struct(c.sscore, c.d_dir, o.flow);
         if (rc) return rc;
         if (c.score && c.sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
-        rc = check_flow_members(t, c.members, c.d_mask, B, o.flow);
+        rc = check_flow_members(fw, c.members, c.d_mask, B, o.flow);
         if (rc) return rc;
         o.by_flow = true;
         o.h_terms = c.h_terms;
         if (c.h_stats && T >= 2 && (o.flow.by_score || o.flow.by_struct)) {
-            rc = stats_workspace(t);
+            rc = stats_workspace(fw);
             if (rc) return rc;
             o.keep_stats = true;
         }
         if (o.flow.iterated) {
-            rc = iter_workspace(t, o.flow.levels, o.flow.iters);
+            rc = iter_workspace(fw, o.flow.levels, o.flow.iters);
             if (rc) return rc;
         }
     }
@@ -1384,7 +795,7 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     // the tied frame gradient starts from zero; only the C0 H W floats of every sample are touched, whatever g_bstride is
     for (int b = 0; fg.p && fg.tstride == 0 && b < B; ++b) TCHK(hipMemsetAsync(fg.p + b * fg.bstride, 0, C0HW * 4, st));
     // the records of the terms that are not computed read zero
-    if (o.keep_stats) TCHK(hipMemsetAsync(t->f_stats, 0, (size_t)(T - 1) * B * SCORE_REC * 8, st));
+    if (o.keep_stats) TCHK(hipMemsetAsync(t->fw.f_stats, 0, (size_t)(T - 1) * B * FLOW_REC * 8, st));
     for (int s = T - 1; s >= 0; --s) {
         rc = backward_step(t, st, o, s, c.d_frames, c.bstride, fg);
         if (rc) return rc;
@@ -1395,7 +806,7 @@ int loss_grad_call(eigen_trainer* t, const LossGradCall& c)
     t->state_batch = B;
     t->state_slot = T;
     if (o.keep_stats) {
-        TCHK(hipMemcpyAsync(c.h_stats, t->f_stats, (size_t)(T - 1) * B * SCORE_REC * 8, hipMemcpyDeviceToHost, st));
+        TCHK(hipMemcpyAsync(c.h_stats, t->fw.f_stats, (size_t)(T - 1) * B * FLOW_REC * 8, hipMemcpyDeviceToHost, st));
         TCHK(hipStreamSynchronize(st));
     }
     return read_loss(t, st, o, want_table, c.h_loss, c.h_layer_err);
@@ -1475,6 +886,38 @@ int accumulator(eigen_trainer* t)
 // EIGEN_OBJ_FLOW through an entry that has nowhere to take the flow settings from
 int refuse_flow_objective() { return tfail(EIGEN_ERR_INVALID, "EIGEN_OBJ_FLOW needs the settings eigen_trainer_loss_grad_flow takes"); }
 
+// What the eigen_trainer_loss_grad_* entries share beyond the leading members: the objective with its weights and where the frame gradient
+// goes (null: not wanted),
+void set_objective(LossGradCall& c, const double* h_step_w, int32_t objective, const double* h_layer_w, double* h_layer_err, float* d_frame_grad = nullptr,
+                   int64_t g_bstride = 0, int64_t g_tstride = 0)
+{
+    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+}
+
+// and the flow settings
+void set_flow(LossGradCall& c, const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double* h_terms, int32_t pairing = EIGEN_FLOW_PAIR_FRAME)
+{
+    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing;
+}
+
+// The stage-alone call on a handle's work record, through the handle's step partials and step value.  A null handle is the first of
+// flow_term_call's "null argument" refusals.
+int flow_term(eigen_trainer* t, const FlowTermCall& c)
+{
+    if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
+    return flow_term_call(t->fw, c, t->d_spart, t->d_step);
+}
+
+// what the stage-alone entries with a solve refuse ahead of the shared call
+int refuse_solve_term(const uint8_t* d_ref, const float* d_fref, const eigen_flow_score* score, const eigen_flow_structure_score* sscore, const eigen_flow_members* members)
+{
+    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
+    if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
+    if (score && sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
+    return EIGEN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1549,9 +992,8 @@ int eigen_trainer_loss_grad_flow_pair(eigen_trainer* t, const uint8_t* d_frames,
                                       const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double* h_terms, int32_t pairing, void* stream)
 {
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
-    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
+    set_flow(c, flow, d_dir, d_mask, h_terms, pairing);
     return loss_grad_call(t, c);
 }
 
@@ -1562,9 +1004,9 @@ int eigen_trainer_loss_grad_flow_score(eigen_trainer* t, const uint8_t* d_frames
                                        const eigen_flow_score* score, void* stream)
 {
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
-    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
+    set_flow(c, flow, d_dir, d_mask, h_terms, pairing);
+    c.score = score;
     return loss_grad_call(t, c);
 }
 
@@ -1574,9 +1016,8 @@ int eigen_trainer_loss_grad_flow(eigen_trainer* t, const uint8_t* d_frames, int6
                                  const float* d_dir, const uint8_t* d_mask, double* h_terms, void* stream)
 {
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
-    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
+    set_flow(c, flow, d_dir, d_mask, h_terms);
     return loss_grad_call(t, c);
 }
 
@@ -1586,74 +1027,17 @@ int eigen_trainer_loss_grad_frames(eigen_trainer* t, const uint8_t* d_frames, in
 {
     if (objective == EIGEN_OBJ_FLOW) return refuse_flow_objective();
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
     return loss_grad_call(t, c);
-}
-
-// the four stage-alone entries share this (eigen_trainer_flow_term_score adds the score and the per-sample record): the checks, one FlowTerm whose seed and reference gradient are stored, not added, and the
-// value read back.  eigen_trainer_flow_term wants no reference gradient; eigen_trainer_flow_term_pair gives a float reference, d_fref
-static int flow_term_call(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
-                          const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow, float* d_seed,
-                          int64_t s_bstride, float* d_refg, int64_t rg_bstride, void* stream, const float* d_fref = nullptr, const eigen_flow_score* score = nullptr,
-                          double* h_stats = nullptr, const eigen_flow_structure_score* sscore = nullptr, const eigen_flow_members* members = nullptr,
-                          const eigen_dense_solve* solve = nullptr, const double* d_target = nullptr, int64_t t_bstride = 0, const uint8_t* d_valid = nullptr,
-                          int64_t v_bstride = 0)
-{
-    if (!t || !d_pred || (!d_ref && !d_fref) || !flow) return tfail(EIGEN_ERR_INVALID, "null argument");
-    if (batch < 1) return tfail(EIGEN_ERR_INVALID, "batch >= 1 required");
-    if (batch > t->cfg.max_batch) return tfail(EIGEN_ERR_CAPACITY, "batch %d exceeds the trainer's %d", batch, t->cfg.max_batch);
-    const long long C0HW = t->ly[0].CHW();
-    if (p_bstride < C0HW || r_bstride < C0HW || (d_seed && s_bstride < C0HW) || (d_refg && rg_bstride < C0HW))
-        return tfail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", C0HW);
-    if (!std::isfinite(scale)) return tfail(EIGEN_ERR_INVALID, "scale %g is not finite", scale);
-    FlowSpec f;
-    int rc = check_flow_target(t, d_target, t_bstride, 0, 1, true, d_dir, score, sscore, members, f);
-    if (rc) return rc;
-    rc = check_flow_valid(t, d_valid, v_bstride, 0, 1, f);
-    if (rc) return rc;
-    rc = check_solve(t, solve, f);  // ahead of the mask's read-back and of every allocation
-    if (rc) return rc;
-    rc = check_flow(t, flow, d_dir, per_sample_mask(members) ? nullptr : d_mask, 0, f);
-    if (rc) return rc;
-    rc = check_flow_score(score, d_dir, f);
-    if (rc) return rc;
-    rc = check_flow_struct(sscore, d_dir, f);
-    if (rc) return rc;
-    rc = check_flow_members(t, members, d_mask, batch, f);
-    if (rc) return rc;
-    if (f.iterated) {
-        rc = iter_workspace(t, f.levels, f.iters);
-        if (rc) return rc;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    FlowTerm m;
-    m.pred = d_pred; m.p_bstride = p_bstride; m.ref = d_ref; m.fref = d_fref; m.r_bstride = r_bstride;
-    m.kappa = scale / f.kappa_div(batch); m.part = t->d_spart; m.d_value = h_value ? t->d_step : nullptr;
-    m.d_flow = d_flow; m.d_seed = d_seed; m.s_bstride = s_bstride; m.d_refg = d_refg; m.rg_bstride = rg_bstride;
-    m.target = f.target.p; m.valid = f.valid.p;
-    flow_stage(t, st, batch, f, m);
-    TCHK(hipGetLastError());
-    if (h_value) {
-        TCHK(hipMemcpyAsync(h_value, t->d_step, 8, hipMemcpyDeviceToHost, st));
-        TCHK(hipStreamSynchronize(st));
-    }
-    if (h_stats && f.by_score) {
-        TCHK(hipMemcpyAsync(h_stats, t->f_rec, (size_t)batch * SCORE_REC * 8, hipMemcpyDeviceToHost, st));
-        TCHK(hipStreamSynchronize(st));
-    }
-    if (h_stats && f.by_struct) {
-        TCHK(hipMemcpyAsync(h_stats, t->f_srec, (size_t)batch * STRUCT_REC * 8, hipMemcpyDeviceToHost, st));
-        TCHK(hipStreamSynchronize(st));
-    }
-    return EIGEN_OK;
 }
 
 int eigen_trainer_flow_term(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
                             const eigen_flow_settings* flow, const float* d_dir, const uint8_t* d_mask, double scale, double* h_value, double* d_flow,
                             float* d_seed, int64_t s_bstride, void* stream)
 {
-    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, nullptr, 0, stream);
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_ref = d_ref; c.d_dir = d_dir;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_flow_term_ref(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, int64_t r_bstride, int32_t batch,
@@ -1661,7 +1045,9 @@ int eigen_trainer_flow_term_ref(eigen_trainer* t, const float* d_pred, int64_t p
                                 float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream)
 {
     if (!d_ref_grad) return tfail(EIGEN_ERR_INVALID, "null argument");
-    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream);
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_ref = d_ref; c.d_dir = d_dir; c.d_refg = d_ref_grad; c.rg_bstride = rg_bstride;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_flow_term_pair(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const float* d_prev, int64_t r_bstride, int32_t batch,
@@ -1669,8 +1055,9 @@ int eigen_trainer_flow_term_pair(eigen_trainer* t, const float* d_pred, int64_t 
                                  float* d_seed, int64_t s_bstride, float* d_prev_grad, int64_t pg_bstride, void* stream)
 {
     if (!d_prev) return tfail(EIGEN_ERR_INVALID, "null argument");
-    return flow_term_call(t, d_pred, p_bstride, nullptr, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_prev_grad, pg_bstride, stream,
-                          d_prev);
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_fref = d_prev; c.d_dir = d_dir; c.d_refg = d_prev_grad; c.rg_bstride = pg_bstride;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_flow_term_score(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
@@ -1680,8 +1067,9 @@ int eigen_trainer_flow_term_score(eigen_trainer* t, const float* d_pred, int64_t
 {
     if (!score) return tfail(EIGEN_ERR_INVALID, "null argument");
     if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
-    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, nullptr, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride,
-                          stream, d_fref, score, h_stats);
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_ref = d_ref; c.d_fref = d_fref; c.d_refg = d_ref_grad; c.rg_bstride = rg_bstride; c.score = score; c.h_stats = h_stats;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_flow_term_structure(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
@@ -1691,8 +1079,9 @@ int eigen_trainer_flow_term_structure(eigen_trainer* t, const float* d_pred, int
 {
     if (!score) return tfail(EIGEN_ERR_INVALID, "null argument");
     if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
-    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, nullptr, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride,
-                          stream, d_fref, nullptr, h_stats, score);
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_ref = d_ref; c.d_fref = d_fref; c.d_refg = d_ref_grad; c.rg_bstride = rg_bstride; c.sscore = score; c.h_stats = h_stats;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_flow_term_members(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
@@ -1703,8 +1092,9 @@ int eigen_trainer_flow_term_members(eigen_trainer* t, const float* d_pred, int64
     if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
     if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
     if ((score != nullptr) == (sscore != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the flow score and the flow structure score must be given");
-    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, nullptr, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride,
-                          stream, d_fref, score, h_stats, sscore, members);
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_ref = d_ref; c.d_fref = d_fref; c.d_refg = d_ref_grad; c.rg_bstride = rg_bstride; c.score = score; c.sscore = sscore; c.members = members; c.h_stats = h_stats;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_flow_members(eigen_trainer* t, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride, int32_t batch, const eigen_flow_members* members,
@@ -1716,19 +1106,7 @@ int eigen_trainer_flow_members(eigen_trainer* t, const uint8_t* d_ref, const flo
     if (batch > t->cfg.max_batch) return tfail(EIGEN_ERR_CAPACITY, "batch %d exceeds the trainer's %d", batch, t->cfg.max_batch);
     if (r_bstride < t->ly[0].CHW()) return tfail(EIGEN_ERR_INVALID, "r_bstride %lld is smaller than one image (%lld elements)", (long long)r_bstride, t->ly[0].CHW());
     if (members->kind != EIGEN_FLOW_MEMBERS_CORNERS) return tfail(EIGEN_ERR_INVALID, "flow members: kind %d: this entry derives EIGEN_FLOW_MEMBERS_CORNERS", members->kind);
-    FlowSpec f;
-    f.by_score = true;  // the stage alone stands for a scored term
-    f.mask = d_mask;
-    TCHK(hipSetDevice(t->cfg.device));
-    int rc = check_flow_members(t, members, d_mask, batch, f);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    corner_stage(t, st, batch, f, d_ref, d_fref, r_bstride);
-    TCHK(hipGetLastError());
-    if (h_members) TCHK(hipMemcpyAsync(h_members, t->c_member, (size_t)batch * t->ly[0].HW, hipMemcpyDeviceToHost, st));
-    if (h_counts) TCHK(hipMemcpyAsync(h_counts, t->c_count, (size_t)batch * 4, hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
-    return EIGEN_OK;
+    return flow_members_call(t->fw, d_ref, d_fref, r_bstride, batch, members, d_mask, h_members, h_counts, stream);
 }
 
 int eigen_trainer_loss_grad_flow_members(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed,
@@ -1739,9 +1117,9 @@ int eigen_trainer_loss_grad_flow_members(eigen_trainer* t, const uint8_t* d_fram
                                          double* h_stats, void* stream)
 {
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
-    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
+    set_flow(c, flow, d_dir, d_mask, h_terms, pairing);
+    c.score = score; c.sscore = sscore;
     c.members = members; c.h_stats = h_stats;
     return loss_grad_call(t, c);
 }
@@ -1753,11 +1131,11 @@ int eigen_trainer_debug_free_planes(eigen_trainer* t, int32_t batch, double* h_t
     TCHK(hipSetDevice(t->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)batch * t->ly[0].HW;
-    if (h_theta) TCHK(hipMemcpyAsync(h_theta, t->f_theta, n * 8, hipMemcpyDeviceToHost, st));
-    if (h_L) TCHK(hipMemcpyAsync(h_L, t->f_L, n * 8, hipMemcpyDeviceToHost, st));
-    if (h_rowS) TCHK(hipMemcpyAsync(h_rowS, t->f_rowS, n * 4, hipMemcpyDeviceToHost, st));
-    if (h_colS) TCHK(hipMemcpyAsync(h_colS, t->f_colS, n * 4, hipMemcpyDeviceToHost, st));
-    if (h_flag) TCHK(hipMemcpyAsync(h_flag, t->f_flag, n, hipMemcpyDeviceToHost, st));
+    if (h_theta) TCHK(hipMemcpyAsync(h_theta, t->fw.f_theta, n * 8, hipMemcpyDeviceToHost, st));
+    if (h_L) TCHK(hipMemcpyAsync(h_L, t->fw.f_L, n * 8, hipMemcpyDeviceToHost, st));
+    if (h_rowS) TCHK(hipMemcpyAsync(h_rowS, t->fw.f_rowS, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_colS) TCHK(hipMemcpyAsync(h_colS, t->fw.f_colS, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_flag) TCHK(hipMemcpyAsync(h_flag, t->fw.f_flag, n, hipMemcpyDeviceToHost, st));
     TCHK(hipStreamSynchronize(st));
     return EIGEN_OK;
 }
@@ -1769,9 +1147,9 @@ int eigen_trainer_loss_grad_flow_structure(eigen_trainer* t, const uint8_t* d_fr
                                            const eigen_flow_structure_score* score, void* stream)
 {
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
-    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.sscore = score;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
+    set_flow(c, flow, d_dir, d_mask, h_terms, pairing);
+    c.sscore = score;
     return loss_grad_call(t, c);
 }
 
@@ -1781,7 +1159,7 @@ int eigen_trainer_loss_grad_obj(eigen_trainer* t, const uint8_t* d_frames, int64
 {
     if (objective == EIGEN_OBJ_FLOW) return refuse_flow_objective();
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err);
     return loss_grad_call(t, c);
 }
 
@@ -1974,142 +1352,19 @@ int eigen_trainer_accumulate(eigen_trainer* t, int32_t op, double scale, void* s
     return EIGEN_OK;
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------- the dense fitness's stage
-// (dense_stage.h; eigen_engine.hip holds the entries and the workspace).  The score's rules are check_flow_score's and
-// check_flow_struct's, the launches are flow_stage's and struct_stage_of's with the score-only kernels of dense_fitness_kernels.h in
-// place of the prepare, solve and pair kernels.
-namespace eigd {
-
-static_assert(DENSE_REC == SCORE_REC && DENSE_REC == STRUCT_REC, "one record size for every score");
-static_assert(DENSE_PART >= SCORE_SLICES * SCORE_K && DENSE_PART >= STRUCT_SLICES * STRUCT_K, "the partials of every score fit");
-
-// The solve's own rules: 1 .. 6 levels, 1 .. 32 iterations, a coarsest level of at least 4 pixels on its shorter side
-static int dense_solve_check(const eigen_dense_solve* solve, bool force_iterated, int H, int W, DenseSolve& out)
-{
-    out = DenseSolve();
-    out.iterated = force_iterated;
-    if (!solve) return EIGEN_OK;
-    if (solve->levels < 1 || solve->levels > DENSE_MAX_LEVELS) return tfail(EIGEN_ERR_INVALID, "dense solve levels %d outside 1 .. %d", solve->levels, DENSE_MAX_LEVELS);
-    if (solve->iters < 1 || solve->iters > DENSE_MAX_ITERS) return tfail(EIGEN_ERR_INVALID, "dense solve iters %d outside 1 .. %d", solve->iters, DENSE_MAX_ITERS);
-    int h = H, w = W;
-    for (int l = 1; l < solve->levels; ++l) { h = (h + 1) / 2; w = (w + 1) / 2; }
-    if ((h < w ? h : w) < DENSE_MIN_COARSE)
-        return tfail(EIGEN_ERR_INVALID, "dense solve levels %d: the coarsest level of a %d x %d image is %d x %d, below %d pixels", solve->levels, W, H, w, h, DENSE_MIN_COARSE);
-    out.levels = solve->levels; out.iters = solve->iters;
-    out.iterated = force_iterated || solve->levels > 1 || solve->iters > 1;
-    return EIGEN_OK;
-}
-
-static int dense_spec(const eigen_dense_settings* s, int device, int H, int W, const uint8_t* d_mask, FlowSpec& f)
-{
-    if (!s) return tfail(EIGEN_ERR_INVALID, "null argument");
-    if ((s->score != nullptr) == (s->sscore != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the flow score and the flow structure score must be given");
-    int rc = check_flow_on(device, (long long)H * W, &s->flow, nullptr, d_mask, 0, f);
-    if (rc) return rc;
-    rc = check_flow_score(s->score, nullptr, f);
-    if (rc) return rc;
-    return check_flow_struct(s->sscore, nullptr, f);
-}
-
-int dense_check(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int H, int W, const uint8_t* d_mask, DenseSolve& out)
-{
-    FlowSpec f;
-    const int rc = dense_solve_check(solve, force_iterated, H, W, out);   // ahead of the mask's read-back
-    if (rc) return rc;
-    return dense_spec(s, device, H, W, d_mask, f);
-}
-
-// The iterated solve: the gray planes of level 0, the reduced levels, then one launch per level from the coarsest to the finest, whose
-// field goes into u.  w.pyr holds, level after level, I0_l, I1_l and (l >= 1) the level's field.
-static void dense_pyr_launch(const DenseSolve& solve, int r, double eps, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1, long long stride1,
-                             int B, const DenseWork& w, double* u, hipStream_t st)
-{
-    struct Level { int H, W; double *I0, *I1, *u; } lv[DENSE_MAX_LEVELS];
-    double* at = w.pyr;
-    for (int l = 0, h = H, ww = W; l < solve.levels; ++l, h = (h + 1) / 2, ww = (ww + 1) / 2) {
-        const long long n = (long long)B * h * ww;
-        lv[l] = Level{h, ww, at, at + n, l ? at + 2 * n : u};
-        at += 4 * n;
-    }
-    ew(st, tdense_gray_kernel, (long long)B * H * W, img0, stride0, img1, stride1, C, H, W, (long long)B * H * W, lv[0].I0, lv[0].I1);
-    for (int l = 1; l < solve.levels; ++l) {
-        const long long n = (long long)B * lv[l].H * lv[l].W;
-        ew(st, tdense_pyrdown_kernel, n, (const double*)lv[l - 1].I0, (const double*)lv[l - 1].I1, lv[l - 1].H, lv[l - 1].W, lv[l].H, lv[l].W, n, lv[l].I0, lv[l].I1);
-    }
-    const int lds = pyr_lds_doubles(r) * 8;
-    if (lds > 64 * 1024)   // radius 11 and above: more dynamic LDS than a launch gets without the attribute (set on the current device, as the CPPN launches do)
-        (void)hipFuncSetAttribute((const void*)tdense_iter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    for (int l = solve.levels - 1; l >= 0; --l) {
-        const bool top = l == solve.levels - 1;
-        const dim3 grid((unsigned)((lv[l].W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((lv[l].H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-        hipLaunchKernelGGL(tdense_iter_kernel, grid, dim3(FLOW_T), (size_t)lds, st, (const double*)lv[l].I0, (const double*)lv[l].I1, lv[l].H, lv[l].W, r, eps,
-                           solve.iters, top ? (const double*)nullptr : (const double*)lv[l + 1].u, top ? 0 : lv[l + 1].H, top ? 0 : lv[l + 1].W, lv[l].u);
-    }
-}
-
-template <int STRUCT>
-static void dense_struct_passes(const TFlowStruct& s, int H, int W, int B, const uint8_t* mask, const DenseWork& w, const double* u, hipStream_t st)
-{
-    const long long HW = (long long)H * W, n = B * HW;
-    const dim3 sgrid(STRUCT_SLICES, (unsigned)B);
-    if (STRUCT == STRUCT_FREE) ew(st, tflow_free_prepare_kernel, n, u, n, H, W, mask, 0ll, s, w.theta, w.flag);
-    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 1>), sgrid, dim3(EW_T), 0, st, u, H, W, mask, 0ll, s, (const double*)w.rec, (const double*)w.L, w.part);
-    hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 1>), dim3(B), dim3(64), 0, st, (const double*)w.part, B, s, w.rec, (double*)nullptr);
-    if (STRUCT == STRUCT_FREE)
-        hipLaunchKernelGGL(tdense_free_pair_kernel, dim3((unsigned)((HW + PAIR_T - 1) / PAIR_T), (unsigned)B), dim3(PAIR_T), 0, st, (const double*)w.theta,
-                           (const uint8_t*)w.flag, H, W, s.DD, w.L);
-    hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 2>), sgrid, dim3(EW_T), 0, st, u, H, W, mask, 0ll, s, (const double*)w.rec, (const double*)w.L, w.part);
-    hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 2>), dim3(B), dim3(64), 0, st, (const double*)w.part, B, s, w.rec, (double*)nullptr);
-}
-
-void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1,
-                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st)
-{
-    // the settings were checked by dense_check: the same fields give the same spec, without the mask's read-back
-    FlowSpec f;
-    f.r = s->flow.radius; f.eps = s->flow.eps;
-    (void)check_flow_score(s->score, nullptr, f);
-    (void)check_flow_struct(s->sscore, nullptr, f);
-    const long long n = (long long)B * H * W;
-    double* u = d_flow ? d_flow : w.u;
-    if (solve.iterated) {
-        dense_pyr_launch(solve, f.r, f.eps, C, H, W, img0, stride0, img1, stride1, B, w, u, st);
-    } else {
-        ew(st, tdense_prep_kernel, n, img0, stride0, img1, stride1, C, H, W, n, w.planes);
-        const dim3 grid((unsigned)((W + FLOW_TILE - 1) / FLOW_TILE), (unsigned)((H + FLOW_TILE - 1) / FLOW_TILE), (unsigned)B);
-        hipLaunchKernelGGL(tdense_solve_kernel, grid, dim3(FLOW_T), 0, st, (const double*)w.planes, n, H, W, f.r, f.eps, u);
-    }
-    if (f.by_score) {
-        const dim3 sgrid(SCORE_SLICES, (unsigned)B);
-        hipLaunchKernelGGL(tflow_score_moment_kernel<1>, sgrid, dim3(EW_T), 0, st, (const double*)u, H, W, d_mask, 0ll, f.score, (const double*)w.rec, w.part);
-        hipLaunchKernelGGL(tflow_score_final_kernel<1>, dim3(B), dim3(64), 0, st, (const double*)w.part, B, f.score, w.rec, (double*)nullptr);
-        hipLaunchKernelGGL(tflow_score_moment_kernel<2>, sgrid, dim3(EW_T), 0, st, (const double*)u, H, W, d_mask, 0ll, f.score, (const double*)w.rec, w.part);
-        hipLaunchKernelGGL(tflow_score_final_kernel<2>, dim3(B), dim3(64), 0, st, (const double*)w.part, B, f.score, w.rec, (double*)nullptr);
-    } else if (f.sscore.structure == STRUCT_BANDS) {
-        dense_struct_passes<STRUCT_BANDS>(f.sscore, H, W, B, d_mask, w, u, st);
-    } else {
-        dense_struct_passes<STRUCT_FREE>(f.sscore, H, W, B, d_mask, w, u, st);
-    }
-}
-
-}  // namespace eigd
-
-// ---------------------------------------------------------------------------------------------------- the flow entries with a solve
-extern "C" {
-
+// ---- the flow entries with a solve
 int eigen_trainer_flow_term_iter(eigen_trainer* t, const float* d_pred, int64_t p_bstride, const uint8_t* d_ref, const float* d_fref, int64_t r_bstride,
                                  int32_t batch, const eigen_flow_settings* flow, const uint8_t* d_mask, const eigen_flow_score* score,
                                  const eigen_flow_structure_score* sscore, const eigen_flow_members* members, double scale, double* h_value, double* h_stats,
                                  double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir,
                                  const eigen_dense_solve* solve)
 {
-    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
-    if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
-    if (score && sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
-    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream,
-                          d_fref, score, h_stats, sscore, members, solve);
+    const int rc = refuse_solve_term(d_ref, d_fref, score, sscore, members);
+    if (rc) return rc;
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_ref = d_ref; c.d_fref = d_fref; c.d_dir = d_dir; c.d_refg = d_ref_grad; c.rg_bstride = rg_bstride;
+    c.score = score; c.sscore = sscore; c.members = members; c.h_stats = h_stats; c.solve = solve;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_loss_grad_flow_iter(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant,
@@ -2120,9 +1375,9 @@ int eigen_trainer_loss_grad_flow_iter(eigen_trainer* t, const uint8_t* d_frames,
                                       const eigen_dense_solve* solve)
 {
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
-    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
+    set_flow(c, flow, d_dir, d_mask, h_terms, pairing);
+    c.score = score; c.sscore = sscore;
     c.members = members; c.h_stats = h_stats; c.solve = solve;
     return loss_grad_call(t, c);
 }
@@ -2133,11 +1388,12 @@ int eigen_trainer_flow_term_target(eigen_trainer* t, const float* d_pred, int64_
                                    double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir,
                                    const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride)
 {
-    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
-    if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
-    if (score && sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
-    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream,
-                          d_fref, score, h_stats, sscore, members, solve, d_target, t_bstride);
+    const int rc = refuse_solve_term(d_ref, d_fref, score, sscore, members);
+    if (rc) return rc;
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_ref = d_ref; c.d_fref = d_fref; c.d_dir = d_dir; c.d_refg = d_ref_grad; c.rg_bstride = rg_bstride;
+    c.score = score; c.sscore = sscore; c.members = members; c.h_stats = h_stats; c.solve = solve; c.d_target = d_target; c.t_bstride = t_bstride;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_loss_grad_flow_target(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant,
@@ -2148,9 +1404,9 @@ int eigen_trainer_loss_grad_flow_target(eigen_trainer* t, const uint8_t* d_frame
                                         const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride, int64_t t_tstride)
 {
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
-    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
+    set_flow(c, flow, d_dir, d_mask, h_terms, pairing);
+    c.score = score; c.sscore = sscore;
     c.members = members; c.h_stats = h_stats; c.solve = solve; c.d_target = d_target; c.t_bstride = t_bstride; c.t_tstride = t_tstride;
     return loss_grad_call(t, c);
 }
@@ -2161,11 +1417,13 @@ int eigen_trainer_flow_term_valid(eigen_trainer* t, const float* d_pred, int64_t
                                   double* d_flow, float* d_seed, int64_t s_bstride, float* d_ref_grad, int64_t rg_bstride, void* stream, const float* d_dir,
                                   const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride, const uint8_t* d_valid, int64_t v_bstride)
 {
-    if ((d_ref != nullptr) == (d_fref != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the byte and the float reference must be given");
-    if (members && !score && !sscore) return tfail(EIGEN_ERR_INVALID, "flow members need a score: the displacement modes divide by the shared mask's count");
-    if (score && sscore) return tfail(EIGEN_ERR_INVALID, "a flow score and a flow structure score do not go together");
-    return flow_term_call(t, d_pred, p_bstride, d_ref, r_bstride, batch, flow, d_dir, d_mask, scale, h_value, d_flow, d_seed, s_bstride, d_ref_grad, rg_bstride, stream,
-                          d_fref, score, h_stats, sscore, members, solve, d_target, t_bstride, d_valid, v_bstride);
+    const int rc = refuse_solve_term(d_ref, d_fref, score, sscore, members);
+    if (rc) return rc;
+    FlowTermCall c{d_pred, p_bstride, r_bstride, batch, flow, d_mask, scale, h_value, d_flow, d_seed, s_bstride, stream};
+    c.d_ref = d_ref; c.d_fref = d_fref; c.d_dir = d_dir; c.d_refg = d_ref_grad; c.rg_bstride = rg_bstride;
+    c.score = score; c.sscore = sscore; c.members = members; c.h_stats = h_stats; c.solve = solve; c.d_target = d_target; c.t_bstride = t_bstride;
+    c.d_valid = d_valid; c.v_bstride = v_bstride;
+    return flow_term(t, c);
 }
 
 int eigen_trainer_loss_grad_flow_joint(eigen_trainer* t, const uint8_t* d_frames, int64_t bstride, int32_t batch, int32_t n_steps, int32_t n_fed, int32_t requant,
@@ -2176,9 +1434,9 @@ int eigen_trainer_loss_grad_flow_joint(eigen_trainer* t, const uint8_t* d_frames
                                        const eigen_dense_solve* solve, const double* d_target, int64_t t_bstride, int64_t t_tstride, const eigen_flow_joint* joint)
 {
     LossGradCall c{d_frames, bstride, batch, n_steps, n_fed, requant, reset, h_loss, d_pred, stream};
-    c.h_step_w = h_step_w; c.objective = objective; c.h_layer_w = h_layer_w; c.h_layer_err = h_layer_err;
-    c.fg.p = d_frame_grad; c.fg.bstride = g_bstride; c.fg.tstride = g_tstride;
-    c.flow = flow; c.d_dir = d_dir; c.d_mask = d_mask; c.h_terms = h_terms; c.pairing = pairing; c.score = score; c.sscore = sscore;
+    set_objective(c, h_step_w, objective, h_layer_w, h_layer_err, d_frame_grad, g_bstride, g_tstride);
+    set_flow(c, flow, d_dir, d_mask, h_terms, pairing);
+    c.score = score; c.sscore = sscore;
     c.members = members; c.h_stats = h_stats; c.solve = solve; c.d_target = d_target; c.t_bstride = t_bstride; c.t_tstride = t_tstride;
     c.joint = joint;
     return loss_grad_call(t, c);
@@ -2187,8 +1445,8 @@ int eigen_trainer_loss_grad_flow_joint(eigen_trainer* t, const uint8_t* d_frames
 int eigen_trainer_debug_flow_iter(eigen_trainer* t, int32_t force, int64_t* workspace_bytes)
 {
     if (!t) return tfail(EIGEN_ERR_INVALID, "null argument");
-    if (force >= 0) t->it_force = force != 0;
-    if (workspace_bytes) *workspace_bytes = t->it_ws ? t->it_doubles * 8 : 0;
+    if (force >= 0) t->fw.it_force = force != 0;
+    if (workspace_bytes) *workspace_bytes = t->fw.it_ws ? t->fw.it_doubles * 8 : 0;
     return EIGEN_OK;
 }
 

@@ -7,12 +7,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "train_common.h"  // WAVE, EW_T
+
 namespace eigt {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int WAVE = 64;
-constexpr int EW_T = 256;  // threads per block of the element-wise kernels
 
 // One source of a 3x3 'same' convolution.  Source sample n lives at p + n * nstride as [cin][Hs][Ws]; up = 1 reads it as the
 // nearest 2x upsample of a half-resolution map (Hs = H / 2).  Weight modes:

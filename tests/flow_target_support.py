@@ -18,7 +18,7 @@ from tests import flow_obj_support as fs
 
 FLOW_TARGET_KERNELS = ["tflow_target_kernel"]
 EPS = dp.EPS
-SUM_BLOCKS, SUM_THREADS = 64, 256      # STEP_LOSS_BLOCKS of csrc/prednet_train.hip, EW_T of csrc/train_kernels.h
+SUM_BLOCKS, SUM_THREADS = 64, 256      # STEP_LOSS_BLOCKS and EW_T of csrc/train_common.h
 
 
 # ---- (a) the numpy restatement

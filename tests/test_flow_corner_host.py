@@ -118,7 +118,7 @@ def test_the_kernels_live_in_their_own_header():
     pat = r"__global__\s+void\s+(?:__launch_bounds__\(\w+\)\s+)?(\w+)\s*\("
     text = open(os.path.join(CSRC, "flow_corner_kernels.h")).read()
     assert set(re.findall(pat, text)) == set(cs.FLOW_CORNER_KERNELS)
-    assert '#include "flow_kernels.h"' in text and '#include "flow_corner_kernels.h"' in open(os.path.join(CSRC, "prednet_train.hip")).read()
+    assert '#include "flow_kernels.h"' in text and '#include "flow_corner_kernels.h"' in open(os.path.join(CSRC, "flow_stage.hip")).read()
     # the corner kernels themselves are included, not copied: they are defined in flow_kernels.h alone
     for kernel in ("gray_kernel", "mineig_kernel", "corner_select_kernel"):
         homes = [n for n in os.listdir(CSRC) if n.endswith((".h", ".hip")) and kernel in re.findall(pat, open(os.path.join(CSRC, n)).read())]

@@ -192,7 +192,7 @@ def test_header_exports_and_abi():
 def test_the_kernels_live_in_their_own_header():
     pat = r"__global__\s+void\s+(?:__launch_bounds__\(\w+\)\s+)?(\w+)\s*\("
     assert set(re.findall(pat, open(os.path.join(CSRC, "flow_obj_kernels.h")).read())) == set(fs.FLOW_OBJ_KERNELS)
-    unit = open(os.path.join(CSRC, "prednet_train.hip")).read()
+    unit = open(os.path.join(CSRC, "flow_stage.hip")).read()
     assert '#include "flow_obj_kernels.h"' in unit
     header = open(os.path.join(CSRC, "flow_obj_kernels.h")).read()
     assert re.search(r"FLOW_TILE\s*=\s*%d\b" % fs.TILE, header) and re.search(r"FLOW_MAX_R\s*=\s*%d\b" % train.FLOW_MAX_RADIUS, header)

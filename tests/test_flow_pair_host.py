@@ -169,8 +169,8 @@ def test_the_kernels_live_in_their_own_header():
     found = lambda name: set(re.findall(pat, open(os.path.join(CSRC, name)).read()))
     assert found("flow_pair_kernels.h") == set(ps.FLOW_PAIR_KERNELS)
     assert found("flow_ref_kernels.h") == set(rs.FLOW_REF_KERNELS) and found("flow_obj_kernels.h") == set(fs.FLOW_OBJ_KERNELS)
-    unit = open(os.path.join(CSRC, "prednet_train.hip")).read()
-    assert '#include "flow_pair_kernels.h"' in unit and not re.search(pat, unit)
+    unit, trainer = (open(os.path.join(CSRC, name)).read() for name in ("flow_stage.hip", "prednet_train.hip"))
+    assert '#include "flow_pair_kernels.h"' in unit and not re.search(pat, unit) and not re.search(pat, trainer)
 
 
 @pytest.mark.parametrize("kernel", ps.FLOW_PAIR_KERNELS)

@@ -165,7 +165,7 @@ def test_the_kernels_live_in_their_own_header():
     pat = r"__global__\s+void\s+(?:__launch_bounds__\(\w+\)\s+)?(\w+)\s*\("
     assert set(re.findall(pat, open(os.path.join(CSRC, "flow_ref_kernels.h")).read())) == set(rs.FLOW_REF_KERNELS)
     assert set(re.findall(pat, open(os.path.join(CSRC, "flow_obj_kernels.h")).read())) == set(fs.FLOW_OBJ_KERNELS)
-    assert '#include "flow_ref_kernels.h"' in open(os.path.join(CSRC, "prednet_train.hip")).read()
+    assert '#include "flow_ref_kernels.h"' in open(os.path.join(CSRC, "flow_stage.hip")).read()
 
 
 @pytest.mark.parametrize("kernel", rs.FLOW_REF_KERNELS)

@@ -165,7 +165,7 @@ def test_the_kernels_live_in_their_own_header():
     pat = r"__global__\s+void\s+(?:__launch_bounds__\(\w+\)\s+)?(\w+)\s*\("
     text = open(os.path.join(CSRC, "flow_score_kernels.h")).read()
     assert set(re.findall(pat, text)) == set(ss.FLOW_SCORE_KERNELS)
-    assert '#include "flow_score_kernels.h"' in open(os.path.join(CSRC, "prednet_train.hip")).read()
+    assert '#include "flow_score_kernels.h"' in open(os.path.join(CSRC, "flow_stage.hip")).read()
     assert re.search(r"SCORE_REC\s*=\s*%d\b" % ss.REC, text) and re.search(r"SCORE_SLICES\s*=\s*%d\b" % ss.SLICES, text)
     assert "atomic" not in text.replace("no float atomics", "")
     # the q kernel's static LDS: three fields of 48 x 16 doubles, 18 KB, far under 64 KB at r = 16

@@ -229,7 +229,7 @@ def test_the_kernels_live_in_their_own_header():
     for name in os.listdir(CSRC):
         if name != "flow_struct_kernels.h" and name.endswith((".h", ".hip")):
             assert not set(re.findall(pat, open(os.path.join(CSRC, name)).read())) & set(st.FLOW_STRUCT_KERNELS), name
-    assert '#include "flow_struct_kernels.h"' in open(os.path.join(CSRC, "prednet_train.hip")).read()
+    assert '#include "flow_struct_kernels.h"' in open(os.path.join(CSRC, "flow_stage.hip")).read()
     assert re.search(r"STRUCT_REC\s*=\s*%d\b" % st.REC, text) and re.search(r"STRUCT_SLICES\s*=\s*%d\b" % st.SLICES, text)
     assert "atomic" not in text.replace("no float atomics", "")
     assert ("STRUCT_PI = %r" % st.PI) in text

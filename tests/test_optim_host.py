@@ -48,7 +48,7 @@ def test_the_kernels_live_in_their_own_header():
     assert set(re.findall(pat, text)) == set(osup.OPTIM_KERNELS)
     assert '#include "optim_kernels.h"' in open(os.path.join(CSRC, "prednet_train.hip")).read()
     assert re.search(r"NORM_SLICES\s*=\s*%d\b" % osup.NORM_SLICES, text) and re.search(r"EW_T\s*=\s*%d\b" % osup.NORM_THREADS,
-                                                                                      open(os.path.join(CSRC, "train_kernels.h")).read())
+                                                                                      open(os.path.join(CSRC, "train_common.h")).read())
     assert "atomic" not in text.replace("no atomics", "")
     osup.check_shape_properties()
 

@@ -35,7 +35,7 @@ def test_chainer_npz_round_trip_is_exact(tmp_path):
 def test_trainer_entry_points_are_declared_exported_and_listed():
     import __graft_entry__ as ge
     from evolutionary_illusion_generator_amd import engine
-    assert "prednet_train.hip" in ge.HIP_UNITS
+    assert "prednet_train.hip" in ge.HIP_UNITS and "flow_stage.hip" in ge.HIP_UNITS
     header = open(os.path.join(ROOT, "include", "eigen_engine.h")).read()
     declared = set(re.findall(r"\b(eigen_[a-z_0-9]+)\s*\(", header))
     assert "#define EIGEN_ABI_VERSION 4" in header
