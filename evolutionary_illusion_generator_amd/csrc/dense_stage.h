@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/eigen_engine.h"
 
 namespace eigd {
@@ -18,6 +20,17 @@ constexpr int DENSE_PART = 16 * 5; // doubles of one sample's reduction partials
 struct DenseWork {
     double *planes = nullptr, *u = nullptr, *theta = nullptr, *L = nullptr, *rec = nullptr, *part = nullptr, *pyr = nullptr;
     uint8_t* flag = nullptr;
+    // the members' (eigen_dense_score_members), made by the first call that needs them and recorded in member_allocs, which the handle
+    // frees.  Corner members: the gray plane, the eigenvalue plane, the candidate keys and the member plane [B][H W] each, the corners
+    // [B][128][2] and their counts [B] (flow_stage.hip, corner_workspace).  The Free structure's list (dense_member_kernels.h): one block
+    // of max_batch * list_cap slots of 12 bytes, theta then the index, and the counts [B]
+    uint8_t *c_gray = nullptr, *c_member = nullptr;
+    float *c_eig = nullptr, *c_corners = nullptr;
+    unsigned long long* c_cand = nullptr;
+    int *c_count = nullptr, *list_idx = nullptr, *list_count = nullptr;
+    double* list_th = nullptr;
+    long long list_cap = 0;
+    std::vector<void*> member_allocs;
 };
 
 constexpr int DENSE_MAX_LEVELS = 6, DENSE_MAX_ITERS = 32, DENSE_MIN_COARSE = 4;
@@ -26,6 +39,15 @@ constexpr int DENSE_MAX_LEVELS = 6, DENSE_MAX_ITERS = 32, DENSE_MIN_COARSE = 4;
 struct DenseSolve {
     int levels = 1, iters = 1;
     bool iterated = false;
+};
+
+// The members of one call once checked (null members: given is false and the call is the namesake's)
+struct DenseMembers {
+    bool given = false, by_corners = false;
+    int max_corners = 0, block_size = 0;
+    double quality = 0.0, min_distance = 0.0;
+    long long mask_bstride = 0;   // planes: sample b's plane is d_mask + b * mask_bstride
+    int list_cap = 0;             // slots per sample of the Free structure's list: max_corners under corners, H W under planes
 };
 
 // doubles of the pyramid of B images of H x W at DENSE_MAX_LEVELS levels: four planes per pixel of a level
@@ -40,8 +62,13 @@ inline long long pyr_doubles(long long B, int H, int W)
 // objective's own rules in its own words (eigen_last_error).  force_iterated: levels = iters = 1 goes through the iteration kernel too.
 int dense_check(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int H, int W, const uint8_t* d_mask, DenseSolve& out);
 
+// The same with members (null: dense_check itself): the trainer's rules for them in its words (check_flow_members), every refusal ahead of
+// any allocation; then the members' workspace on w, all of a group or none.  Under per-sample planes d_mask is not read as a shared plane.
+int dense_check_members(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int C, int H, int W, int max_batch,
+                        const uint8_t* d_mask, const eigen_flow_members* members, int B, DenseWork& w, DenseSolve& out, DenseMembers& mem);
+
 // The launches of the stage on checked settings: the records of the B samples into w.rec, the field into d_flow (null: w.u)
 void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1,
-                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st);
+                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st, const DenseMembers& mem = DenseMembers());
 
 }  // namespace eigd

@@ -453,6 +453,7 @@ int eigen_destroy(eigen_engine* e)
     for (void* p : misc) if (p) (void)hipFree(p);
     void* dense[] = {e->dense.planes, e->dense.u, e->dense.theta, e->dense.L, e->dense.rec, e->dense.part, e->dense.flag, e->dense.pyr};
     for (void* p : dense) if (p) (void)hipFree(p);
+    for (void* p : e->dense.member_allocs) (void)hipFree(p);
     for (int i = 0; i < 2; ++i)
         for (int l = 0; l < FLOW_MAX_LEVELS; ++l) if (e->d_gray[i][l]) (void)hipFree(e->d_gray[i][l]);
     for (int l = 0; l < FLOW_MAX_LEVELS; ++l) if (e->d_deriv[l]) (void)hipFree(e->d_deriv[l]);
@@ -1191,21 +1192,25 @@ static int dense_pyramid(eigen_engine* e)
     return EIGEN_OK;
 }
 
-// The one record behind the plain dense entries and their _iter forms: the settings, the mask and the checked solve of a call
+// The one record behind the plain dense entries, their _iter and their _members forms: the settings, the mask, the checked solve and the
+// checked members of a call
 struct DenseCall {
     const eigen_dense_settings* settings = nullptr;
     const uint8_t* d_mask = nullptr;
     eigd::DenseSolve solve;
+    eigd::DenseMembers mem;
 };
 
 // What every dense entry refuses before anything is launched (the roll-out included), then the workspace
-static int dense_prepare(eigen_engine* e, DenseCall& c, const eigen_dense_settings* settings, const eigen_dense_solve* solve, const uint8_t* d_mask, int batch)
+static int dense_prepare(eigen_engine* e, DenseCall& c, const eigen_dense_settings* settings, const eigen_dense_solve* solve, const uint8_t* d_mask, int batch,
+                         const eigen_flow_members* members = nullptr)
 {
     if (!settings) return fail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1 || batch > e->B) return fail(EIGEN_ERR_INVALID, "batch %d outside 1 .. max_batch %d", batch, e->B);
     HIPCHK(hipSetDevice(e->cfg.device));
     c.settings = settings; c.d_mask = d_mask;
-    int rc = eigd::dense_check(settings, solve, e->dense_force_iter, e->cfg.device, e->H, e->W, d_mask, c.solve);
+    // without members dense_check_members is dense_check; with them the members' buffers come behind every refusal
+    int rc = eigd::dense_check_members(settings, solve, e->dense_force_iter, e->cfg.device, e->C0, e->H, e->W, e->B, d_mask, members, batch, e->dense, c.solve, c.mem);
     if (rc) return rc;
     rc = dense_workspace(e);
     if (rc) return rc;
@@ -1216,7 +1221,8 @@ static int dense_prepare(eigen_engine* e, DenseCall& c, const eigen_dense_settin
 static int dense_run(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int batch, const DenseCall& c, double* h_fitness,
                      double* h_stats, double* d_flow, hipStream_t st, bool sync)
 {
-    eigd::dense_launch(c.settings, c.solve, e->C0, e->H, e->W, d_img0, (long long)stride0, d_img1, (long long)stride1, batch, c.d_mask, e->dense, d_flow, st);
+    eigd::dense_launch(c.settings, c.solve, e->C0, e->H, e->W, d_img0, (long long)stride0, d_img1, (long long)stride1, batch, c.d_mask, e->dense, d_flow, st,
+                       c.mem);
     HIPCHK(hipGetLastError());
     const size_t rec = eigd::DENSE_REC * sizeof(double);
     if (h_stats) HIPCHK(hipMemcpyAsync(h_stats, e->dense.rec, rec * batch, hipMemcpyDeviceToHost, st));
@@ -1229,17 +1235,31 @@ static int dense_run(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, co
     return EIGEN_OK;
 }
 
-int eigen_dense_score_iter(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
-                           const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, void* stream,
-                           const eigen_dense_solve* solve)
+int eigen_dense_score_members(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
+                              const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, void* stream,
+                              const eigen_dense_solve* solve, const eigen_flow_members* members, uint8_t* h_members, int32_t* h_counts)
 {
     if (!e || !d_img0 || !d_img1 || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
     const int64_t per = (int64_t)e->C0 * e->H * e->W;
     if (stride0 < per || stride1 < per) return fail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", (long long)per);
     DenseCall c;
-    const int rc = dense_prepare(e, c, settings, solve, d_mask, batch);
+    int rc = dense_prepare(e, c, settings, solve, d_mask, batch, members);
     if (rc) return rc;
-    return dense_run(e, d_img0, stride0, d_img1, stride1, batch, c, h_fitness, h_stats, d_flow, (hipStream_t)stream, true);
+    hipStream_t st = (hipStream_t)stream;
+    rc = dense_run(e, d_img0, stride0, d_img1, stride1, batch, c, h_fitness, h_stats, d_flow, st, true);
+    if (rc || !c.mem.by_corners || (!h_members && !h_counts)) return rc;
+    // the corner members' planes and the corner counts before the mask, as eigen_trainer_flow_members gives them
+    if (h_members) HIPCHK(hipMemcpyAsync(h_members, e->dense.c_member, (size_t)batch * e->H * e->W, hipMemcpyDeviceToHost, st));
+    if (h_counts) HIPCHK(hipMemcpyAsync(h_counts, e->dense.c_count, (size_t)batch * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return EIGEN_OK;
+}
+
+int eigen_dense_score_iter(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
+                           const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, void* stream,
+                           const eigen_dense_solve* solve)
+{
+    return eigen_dense_score_members(e, d_img0, stride0, d_img1, stride1, batch, settings, d_mask, h_fitness, h_stats, d_flow, stream, solve, nullptr, nullptr, nullptr);
 }
 
 int eigen_dense_score(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
@@ -1340,15 +1360,15 @@ static int dense_call_check(const eigen_engine* e, int structure, int pairing, c
     return EIGEN_OK;
 }
 
-int eigen_eval_population_dense_iter(eigen_engine* e, const eigen_genome_batch* g, int32_t structure, int32_t bg, int32_t gradient, int32_t pairing,
-                                     const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
-                                     const eigen_dense_solve* solve)
+int eigen_eval_population_dense_members(eigen_engine* e, const eigen_genome_batch* g, int32_t structure, int32_t bg, int32_t gradient, int32_t pairing,
+                                        const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
+                                        const eigen_dense_solve* solve, const eigen_flow_members* members)
 {
     if (!e || !g || !h_fitness || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
     int rc = dense_call_check(e, structure, pairing, settings);
     if (rc) return rc;
     DenseCall c;
-    rc = dense_prepare(e, c, settings, solve, d_mask, g->n_genomes);
+    rc = dense_prepare(e, c, settings, solve, d_mask, g->n_genomes, members);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipEventRecord(e->ev[0], st));
@@ -1357,23 +1377,37 @@ int eigen_eval_population_dense_iter(eigen_engine* e, const eigen_genome_batch* 
     return eval_images_impl(e, e->d_images, g->n_genomes, structure, pairing, h_fitness, nullptr, nullptr, st, true, &c, h_stats);
 }
 
+int eigen_eval_population_dense_iter(eigen_engine* e, const eigen_genome_batch* g, int32_t structure, int32_t bg, int32_t gradient, int32_t pairing,
+                                     const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
+                                     const eigen_dense_solve* solve)
+{
+    return eigen_eval_population_dense_members(e, g, structure, bg, gradient, pairing, settings, d_mask, h_fitness, h_stats, stream, solve, nullptr);
+}
+
 int eigen_eval_population_dense(eigen_engine* e, const eigen_genome_batch* g, int32_t structure, int32_t bg, int32_t gradient, int32_t pairing,
                                 const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream)
 {
     return eigen_eval_population_dense_iter(e, g, structure, bg, gradient, pairing, settings, d_mask, h_fitness, h_stats, stream, nullptr);
 }
 
-int eigen_eval_images_dense_iter(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
-                                 const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
-                                 const eigen_dense_solve* solve)
+int eigen_eval_images_dense_members(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
+                                    const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
+                                    const eigen_dense_solve* solve, const eigen_flow_members* members)
 {
     if (!e || !d_images || !h_fitness || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
     int rc = dense_call_check(e, structure, pairing, settings);
     if (rc) return rc;
     DenseCall c;
-    rc = dense_prepare(e, c, settings, solve, d_mask, batch);
+    rc = dense_prepare(e, c, settings, solve, d_mask, batch, members);
     if (rc) return rc;
     return eval_images_impl(e, d_images, batch, structure, pairing, h_fitness, nullptr, nullptr, (hipStream_t)stream, false, &c, h_stats);
+}
+
+int eigen_eval_images_dense_iter(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
+                                 const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
+                                 const eigen_dense_solve* solve)
+{
+    return eigen_eval_images_dense_members(e, d_images, batch, structure, pairing, settings, d_mask, h_fitness, h_stats, stream, solve, nullptr);
 }
 
 int eigen_eval_images_dense(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,

@@ -70,6 +70,7 @@ struct FlowWork {
     float *c_eig = nullptr, *c_corners = nullptr;
     unsigned long long* c_cand = nullptr;
     int* c_count = nullptr;
+    bool c_byte_refs = false;   // every reference of this record is bytes (the dense fitness): corner_workspace makes no c_bytes
     double* f_vr = nullptr;     // the validity planes' (flow_valid_kernels.h): r_b of the current term [B]
     double* f_stats = nullptr;  // the records of a training call's terms [max_steps][max_batch][SCORE_REC], made by the first call that asks for them
     // the iterated solve's (flow_iter_kernels.h): one block that holds the pyramid, the tape and the adjoint planes of it_levels levels at

@@ -2,8 +2,8 @@
 // rules of a flow call, the launches of one term over a FlowWork, the stage-alone call behind the eigen_trainer_flow_term* entries, and
 // the dense fitness's stage over the engine's plain pointers.  All compute is in the kernels of flow_obj_kernels.h, flow_ref_kernels.h,
 // flow_pair_kernels.h, flow_score_kernels.h, flow_struct_kernels.h, flow_corner_kernels.h, flow_iter_kernels.h (the iterated solve and
-// its gradient), flow_target_kernels.h, flow_valid_kernels.h, dense_fitness_kernels.h and dense_pyr_kernels.h, which this unit alone
-// includes.  It knows no trainer: prednet_train.hip owns the handle and the entries.
+// its gradient), flow_target_kernels.h, flow_valid_kernels.h, dense_fitness_kernels.h, dense_member_kernels.h and dense_pyr_kernels.h, which
+// this unit alone includes.  It knows no trainer: prednet_train.hip owns the handle and the entries.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "flow_struct_kernels.h"
 #include "flow_corner_kernels.h"
 #include "dense_fitness_kernels.h"
+#include "dense_member_kernels.h"
 #include "dense_pyr_kernels.h"
 #include "flow_iter_kernels.h"
 #include "flow_target_kernels.h"
@@ -118,15 +119,15 @@ int check_flow_on(int device, long long HW, const eigen_flow_settings* flow, con
 }
 
 // The corner members' workspace, made by the first call that needs it and freed with its owner; the tape and every other use of the
-// handle keep the memory they had.
+// handle keep the memory they had.  A record whose references are all bytes (the dense fitness's view) gets no byte copy of a float one.
 static int corner_workspace(FlowWork& w)
 {
     if (w.c_member) return EIGEN_OK;
     const long long B = w.max_batch, HW = w.HW;
     TCHK(hipSetDevice(w.device));
-    const std::pair<void**, long long> want[] = {{(void**)&w.c_bytes, B * w.CHW()}, {(void**)&w.c_gray, B * HW}, {(void**)&w.c_eig, B * HW * 4},
-                                                 {(void**)&w.c_cand, B * HW * 8}, {(void**)&w.c_corners, B * CORNER_MAX * 2 * 4}, {(void**)&w.c_count, B * 4},
-                                                 {(void**)&w.c_member, B * HW}};
+    std::vector<std::pair<void**, long long>> want = {{(void**)&w.c_gray, B * HW}, {(void**)&w.c_eig, B * HW * 4}, {(void**)&w.c_cand, B * HW * 8},
+                                                      {(void**)&w.c_corners, B * CORNER_MAX * 2 * 4}, {(void**)&w.c_count, B * 4}, {(void**)&w.c_member, B * HW}};
+    if (!w.c_byte_refs) want.push_back({(void**)&w.c_bytes, B * w.CHW()});
     // all or nothing: the record takes the buffers once every one of them exists, a failure frees what it made
     std::vector<void*> made;
     for (const auto& b : want) {
@@ -250,10 +251,14 @@ int check_flow_valid(const FlowWork& w, const uint8_t* d_valid, long long v_bstr
 // The two passes of moments of a structure score over the field u, for Free the prepare and the pair pass between them: the samples'
 // records into rec, the value into d_value (may be null).  This is the one statement of that launch list, over plain pointers.  rowS,
 // colS: where the pair pass leaves what the gradient needs; null (the dense fitness, which takes no gradient) runs the pair kernel
-// without them.
+// without them, or, where the call carries members (list non-null), the compacted pair pass of dense_member_kernels.h.
+struct FreeList {
+    int* idx; double* th; int* count; int cap;   // cap slots per sample
+};
+
 template <int STRUCT>
 static void struct_passes(hipStream_t st, int H, int W, int B, const uint8_t* mask, long long mask_bstride, const TFlowStruct& s, const double* u, double* theta, uint8_t* flag,
-                   double* L, int* rowS, int* colS, double* rec, double* part, double* d_value)
+                   double* L, int* rowS, int* colS, double* rec, double* part, double* d_value, const FreeList* list = nullptr)
 {
     const long long HW = (long long)H * W, n = B * HW;
     const dim3 sgrid(STRUCT_SLICES, (unsigned)B), pgrid((unsigned)((HW + PAIR_T - 1) / PAIR_T), (unsigned)B);
@@ -262,7 +267,12 @@ static void struct_passes(hipStream_t st, int H, int W, int B, const uint8_t* ma
     hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 1>), dim3(B), dim3(64), 0, st, (const double*)part, B, s, rec, (double*)nullptr);
     if (STRUCT == STRUCT_FREE && rowS)
         hipLaunchKernelGGL(tflow_free_pair_kernel, pgrid, dim3(PAIR_T), 0, st, (const double*)theta, (const uint8_t*)flag, H, W, s.DD, L, rowS, colS);
-    else if (STRUCT == STRUCT_FREE)
+    else if (STRUCT == STRUCT_FREE && list) {
+        hipLaunchKernelGGL(tdense_member_list_kernel, dim3(B), dim3(LIST_T), 0, st, (const double*)theta, (const uint8_t*)flag, (int)HW, list->cap, list->idx, list->th,
+                           list->count, L);
+        hipLaunchKernelGGL(tdense_free_pair_list_kernel, dim3((unsigned)((list->cap + PAIR_T - 1) / PAIR_T), (unsigned)B), dim3(PAIR_T), 0, st, (const int*)list->idx,
+                           (const double*)list->th, (const int*)list->count, list->cap, (int)HW, W, s.DD, L);
+    } else if (STRUCT == STRUCT_FREE)
         hipLaunchKernelGGL(tdense_free_pair_kernel, pgrid, dim3(PAIR_T), 0, st, (const double*)theta, (const uint8_t*)flag, H, W, s.DD, L);
     hipLaunchKernelGGL((tflow_struct_moment_kernel<STRUCT, 2>), sgrid, dim3(EW_T), 0, st, u, H, W, mask, mask_bstride, s, (const double*)rec, (const double*)L, part);
     hipLaunchKernelGGL((tflow_struct_final_kernel<STRUCT, 2>), dim3(B), dim3(64), 0, st, (const double*)part, B, s, rec, d_value);
@@ -632,6 +642,57 @@ int dense_check(const eigen_dense_settings* s, const eigen_dense_solve* solve, b
     return dense_spec(s, device, H, W, d_mask, f);
 }
 
+// The engine's image and the members' buffers of a DenseWork as the record the corner stage and check_flow_members work on: every
+// reference is bytes, so no byte copy of a float one is kept.  allocs: where corner_workspace records what it makes (null: a launch).
+static FlowWork members_view(int device, int C, int H, int W, int max_batch, const DenseWork& w, std::vector<void*>* allocs)
+{
+    FlowWork v;
+    v.device = device; v.C = C; v.H = H; v.W = W; v.HW = (long long)H * W; v.max_batch = max_batch; v.allocs = allocs;
+    v.c_byte_refs = true;
+    v.c_gray = w.c_gray; v.c_member = w.c_member; v.c_eig = w.c_eig; v.c_corners = w.c_corners; v.c_cand = w.c_cand; v.c_count = w.c_count;
+    return v;
+}
+
+// The Free structure's list at `cap` slots per sample, made by the first call that needs it: one block (theta, the indices, the counts),
+// so all of it or none.  A later call that needs more slots replaces it.
+static int list_workspace(int device, int max_batch, long long cap, DenseWork& w)
+{
+    if (w.list_th && cap <= w.list_cap) return EIGEN_OK;
+    TCHK(hipSetDevice(device));
+    const long long slots = (long long)max_batch * cap, bytes = slots * 12 + (long long)max_batch * 4;
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, (size_t)bytes);
+    if (e != hipSuccess) return tfail(EIGEN_ERR_HIP, "hipMalloc(%lld) for the dense fitness's member list: %s", bytes, hipGetErrorString(e));
+    if (w.list_th) {
+        TCHK(hipFree(w.list_th));  // waits for whatever still reads it
+        w.member_allocs.erase(std::find(w.member_allocs.begin(), w.member_allocs.end(), (void*)w.list_th));
+    }
+    w.member_allocs.push_back(p);
+    w.list_th = (double*)p; w.list_idx = (int*)(w.list_th + slots); w.list_count = w.list_idx + slots; w.list_cap = cap;
+    return EIGEN_OK;
+}
+
+int dense_check_members(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int C, int H, int W, int max_batch,
+                        const uint8_t* d_mask, const eigen_flow_members* members, int B, DenseWork& w, DenseSolve& out, DenseMembers& mem)
+{
+    mem = DenseMembers();
+    FlowSpec f;
+    int rc = dense_solve_check(solve, force_iterated, H, W, out);
+    if (rc) return rc;
+    rc = dense_spec(s, device, H, W, per_sample_mask(members) ? nullptr : d_mask, f);   // per-sample planes are check_flow_members' to read
+    if (rc || !members) return rc;
+    FlowWork v = members_view(device, C, H, W, max_batch, w, &w.member_allocs);
+    rc = check_flow_members(v, members, d_mask, B, f);   // every refusal of it comes ahead of its one allocation, the corner buffers
+    if (rc) return rc;
+    w.c_gray = v.c_gray; w.c_member = v.c_member; w.c_eig = v.c_eig; w.c_corners = v.c_corners; w.c_cand = v.c_cand; w.c_count = v.c_count;
+    mem.given = true; mem.by_corners = f.by_corners;
+    mem.max_corners = f.max_corners; mem.block_size = f.block_size; mem.quality = f.quality; mem.min_distance = f.min_distance;
+    mem.mask_bstride = f.mask_bstride;
+    if (!f.by_struct || f.sscore.structure != STRUCT_FREE) return EIGEN_OK;
+    mem.list_cap = f.by_corners ? f.max_corners : H * W;
+    return list_workspace(device, max_batch, f.by_corners ? (long long)CORNER_MAX : (long long)H * W, w);
+}
+
 // The iterated solve: the gray planes of level 0, the reduced levels, then one launch per level from the coarsest to the finest, whose
 // field goes into u.  w.pyr holds, level after level, I0_l, I1_l and (l >= 1) the level's field.
 static void dense_pyr_launch(const DenseSolve& solve, int r, double eps, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1, long long stride1,
@@ -660,7 +721,7 @@ static void dense_pyr_launch(const DenseSolve& solve, int r, double eps, int C, 
 }
 
 void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1,
-                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st)
+                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st, const DenseMembers& mem)
 {
     // the settings were checked by dense_check: the same fields give the same spec, without the mask's read-back
     FlowSpec f;
@@ -675,10 +736,27 @@ void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C,
         ew(st, tdense_prep_kernel, n, img0, stride0, img1, stride1, C, H, W, n, w.planes);
         hipLaunchKernelGGL(tdense_solve_kernel, flow_grid(H, W, B), dim3(FLOW_T), 0, st, (const double*)w.planes, n, H, W, f.r, f.eps, u);
     }
-    // one plane shared by the batch (mask stride 0), no value beside the records, and for Free no rowS / colS: the fitness takes no gradient
-    if (f.by_score) score_passes(st, H, W, B, d_mask, 0ll, f.score, u, w.rec, w.part, nullptr);
-    else if (f.sscore.structure == STRUCT_BANDS) struct_passes<STRUCT_BANDS>(st, H, W, B, d_mask, 0ll, f.sscore, u, w.theta, w.flag, w.L, nullptr, nullptr, w.rec, w.part, nullptr);
-    else struct_passes<STRUCT_FREE>(st, H, W, B, d_mask, 0ll, f.sscore, u, w.theta, w.flag, w.L, nullptr, nullptr, w.rec, w.part, nullptr);
+    // Who is counted.  No members: one plane shared by the batch (mask stride 0).  Corner members: the trainer's membership stage on
+    // img0, the image the solve treats as the reference, under the shared plane; its member planes then take the mask's place.
+    // Per-sample planes: d_mask holds them.  Members change nothing of the solve above.
+    const uint8_t* mask = d_mask;
+    long long mask_bstride = 0;
+    if (mem.by_corners) {
+        FlowWork v = members_view(0, C, H, W, B, w, nullptr);
+        FlowSpec g;
+        g.mask = d_mask; g.max_corners = mem.max_corners; g.block_size = mem.block_size; g.quality = mem.quality; g.min_distance = mem.min_distance;
+        corner_stage(v, st, B, g, img0, nullptr, stride0);
+        mask = w.c_member; mask_bstride = (long long)H * W;
+    } else if (mem.given) {
+        mask_bstride = mem.mask_bstride;
+    }
+    // no value beside the records, and for Free no rowS / colS: the fitness takes no gradient; under members the compacted pair pass
+    const FreeList list = {w.list_idx, w.list_th, w.list_count, mem.list_cap};
+    if (f.by_score) score_passes(st, H, W, B, mask, mask_bstride, f.score, u, w.rec, w.part, nullptr);
+    else if (f.sscore.structure == STRUCT_BANDS)
+        struct_passes<STRUCT_BANDS>(st, H, W, B, mask, mask_bstride, f.sscore, u, w.theta, w.flag, w.L, nullptr, nullptr, w.rec, w.part, nullptr);
+    else
+        struct_passes<STRUCT_FREE>(st, H, W, B, mask, mask_bstride, f.sscore, u, w.theta, w.flag, w.L, nullptr, nullptr, w.rec, w.part, nullptr, mem.given ? &list : nullptr);
 }
 
 }  // namespace eigd

@@ -32,7 +32,7 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_render_moving_cppn", "eigen_dense_score_iter", "eigen_eval_population_dense_iter", "eigen_eval_images_dense_iter",
            "eigen_debug_dense_solve", "eigen_trainer_flow_term_iter", "eigen_trainer_loss_grad_flow_iter", "eigen_trainer_debug_flow_iter",
            "eigen_trainer_flow_term_target", "eigen_trainer_loss_grad_flow_target", "eigen_moving_cppn_valid", "eigen_trainer_flow_term_valid",
-           "eigen_trainer_loss_grad_flow_joint"]
+           "eigen_trainer_loss_grad_flow_joint", "eigen_dense_score_members", "eigen_eval_population_dense_members", "eigen_eval_images_dense_members"]
 
 
 class EigenConfig(ctypes.Structure):
@@ -396,6 +396,15 @@ class Engine:
         levels, iters = int(getattr(dense, "levels", 1)), int(getattr(dense, "iters", 1))
         return None if (levels, iters) == (1, 1) else DenseSolveC(levels, iters)
 
+    def _dense_members(self, dense, batch):
+        """The members of a `dense` argument (its ``members``, None where it has none) for a call of `batch` samples -> None, or
+        (the eigen_flow_members, the per-sample planes [batch, H, W] on the device, which take d_mask's place, or None under corner
+        members, which keep the shared mask).  ``dense.members_on`` makes both (ValueError: planes of another shape)."""
+        if getattr(dense, "members", None) is None:
+            return None
+        import torch
+        return dense.members_on(torch, self.cfg.device, int(batch), self.height, self.width)
+
     def debug_dense_solve(self, force=None):
         """Test hook (eigen_debug_dense_solve): force True / False sets whether the single step goes through the iteration kernel too.
         -> the bytes of the pyramid this handle holds, 0 before its first iterated call"""
@@ -403,14 +412,19 @@ class Engine:
         _check(self.lib.eigen_debug_dense_solve(self._h, ctypes.c_int32(-1 if force is None else int(bool(force))), ctypes.byref(n)))
         return int(n.value)
 
-    def dense_score(self, d_img0, stride0, d_img1, stride1, batch, dense, stats=False, flow=False, stream=None):
+    def dense_score(self, d_img0, stride0, d_img1, stride1, batch, dense, stats=False, flow=False, stream=None, members_out=False):
         """The dense stage alone on two batches of uint8 device images (eigen_dense_score): image b of either at its pointer + b * its
         stride (bytes).  -> the float64 [batch] fitness, S_b of every sample; stats=True appends the float64 [batch, 10] records,
         flow=True the field u, float64 [batch, 2, H, W] (numpy).  The records are also left in ``last_dense_stats``.  A `dense` with
-        ``levels`` or ``iters`` above 1 runs the pyramidal, iterated solve (eigen_dense_score_iter)."""
+        ``levels`` or ``iters`` above 1 runs the pyramidal, iterated solve (eigen_dense_score_iter), one with ``members`` counts those
+        alone (eigen_dense_score_members; per-sample planes must be [batch, H, W]).  members_out=True (corner members) appends
+        (the member planes uint8 [batch, H, W], the corner counts int32 [batch], before the mask)."""
         cfg, keep, d_mask = self._dense_args(dense)
         solve = self._dense_solve(dense)
         batch = int(batch)
+        mem = self._dense_members(dense, batch)
+        if members_out and (mem is None or mem[1] is not None):
+            raise ValueError("members_out needs a dense fitness with corner members")
         fit, rec = np.zeros(max(batch, 0), np.float64), np.zeros((max(batch, 0), DENSE_REC), np.float64)
         u = None
         if flow:
@@ -424,14 +438,22 @@ class Engine:
                     raise ValueError("%s buffer holds %d bytes, %d are needed" % (what, have, (batch - 1) * int(stride) + per))
         args = (self._h, _ptr(d_img0), ctypes.c_int64(int(stride0)), _ptr(d_img1), ctypes.c_int64(int(stride1)), ctypes.c_int32(batch), ctypes.byref(cfg), d_mask,
                 _ptr(fit), _ptr(rec), _ptr(u), _stream_arg(stream))
-        _check(self.lib.eigen_dense_score(*args) if solve is None else self.lib.eigen_dense_score_iter(*args, ctypes.byref(solve)))
+        planes = counts = None
+        if mem is None:
+            _check(self.lib.eigen_dense_score(*args) if solve is None else self.lib.eigen_dense_score_iter(*args, ctypes.byref(solve)))
+        else:
+            if members_out:
+                planes, counts = np.zeros((max(batch, 0), self.height, self.width), np.uint8), np.zeros(max(batch, 0), np.int32)
+            args = args[:7] + (d_mask if mem[1] is None else _ptr(mem[1]),) + args[8:]
+            _check(self.lib.eigen_dense_score_members(*args, None if solve is None else ctypes.byref(solve), ctypes.byref(mem[0]), _ptr(planes), _ptr(counts)))
         self.last_dense_stats = rec
-        out = (fit,) + ((rec,) if stats else ()) + ((u[:batch].cpu().numpy(),) if flow else ())
+        out = (fit,) + ((rec,) if stats else ()) + ((u[:batch].cpu().numpy(),) if flow else ()) + (((planes, counts),) if members_out else ())
         return out[0] if len(out) == 1 else out
 
     def eval_population(self, gb, structure, bg=1, gradient=1, pairing=PAIR_POPULATION, stream=None, dense=None):
         """dense None: the corner fitness (eigen_eval_population).  dense: a ``fitness.DenseFitness`` resolved for `structure`: the dense
-        motion score (eigen_eval_population_dense); the records of the call are then left in ``last_dense_stats``."""
+        motion score (eigen_eval_population_dense); the records of the call are then left in ``last_dense_stats``.  A `dense` with
+        ``members`` counts those alone (eigen_eval_population_dense_members); per-sample planes must be [n_genomes, H, W]."""
         fit = np.zeros(gb.n_genomes, dtype=np.float64)
         s = self._genome_struct(gb)
         if dense is not None:
@@ -440,7 +462,12 @@ class Engine:
             solve = self._dense_solve(dense)
             args = (self._h, ctypes.byref(s), ctypes.c_int32(int(structure)), ctypes.c_int32(bg), ctypes.c_int32(gradient), ctypes.c_int32(pairing), ctypes.byref(cfg),
                     d_mask, _ptr(fit), _ptr(rec), _stream_arg(stream))
-            _check(self.lib.eigen_eval_population_dense(*args) if solve is None else self.lib.eigen_eval_population_dense_iter(*args, ctypes.byref(solve)))
+            mem = self._dense_members(dense, gb.n_genomes)
+            if mem is None:
+                _check(self.lib.eigen_eval_population_dense(*args) if solve is None else self.lib.eigen_eval_population_dense_iter(*args, ctypes.byref(solve)))
+            else:
+                args = args[:7] + (d_mask if mem[1] is None else _ptr(mem[1]),) + args[8:]
+                _check(self.lib.eigen_eval_population_dense_members(*args, None if solve is None else ctypes.byref(solve), ctypes.byref(mem[0])))
             self.last_dense_stats = rec
             return fit
         _check(self.lib.eigen_eval_population(self._h, ctypes.byref(s), ctypes.c_int32(int(structure)), ctypes.c_int32(bg),
@@ -457,7 +484,12 @@ class Engine:
             solve = self._dense_solve(dense)
             args = (self._h, _ptr(d_images), ctypes.c_int32(batch), ctypes.c_int32(int(structure)), ctypes.c_int32(pairing), ctypes.byref(cfg), d_mask, _ptr(fit),
                     _ptr(rec), _stream_arg(stream))
-            _check(self.lib.eigen_eval_images_dense(*args) if solve is None else self.lib.eigen_eval_images_dense_iter(*args, ctypes.byref(solve)))
+            mem = self._dense_members(dense, batch)
+            if mem is None:
+                _check(self.lib.eigen_eval_images_dense(*args) if solve is None else self.lib.eigen_eval_images_dense_iter(*args, ctypes.byref(solve)))
+            else:
+                args = args[:6] + (d_mask if mem[1] is None else _ptr(mem[1]),) + args[7:]
+                _check(self.lib.eigen_eval_images_dense_members(*args, None if solve is None else ctypes.byref(solve), ctypes.byref(mem[0])))
             self.last_dense_stats = rec
             return fit, [np.zeros((0, 4), np.float32) for _ in range(int(batch))]
         fit = np.zeros(batch, dtype=np.float64)

@@ -309,6 +309,12 @@ GENOME_SOURCE = os.environ.get("EIGEN_GENOME_SOURCE", "rank0")
 FITNESS_SCORES = ("corners", "dense")
 FITNESS_SCORE = os.environ.get("EIGEN_FITNESS_SCORE", "corners")
 
+# Who the dense score counts where `score` is "dense" (and in get_fitnesses_neat under FITNESS_SCORE = "dense"): "all", every pixel, or
+# "corners", the corners the sparse fitness would track, ``train.CornerMembers()`` with its defaults ("Members").
+# Environment EIGEN_DENSE_MEMBERS.  A ``DenseFitness`` given as `score` carries its own members and does not read this.
+DENSE_MEMBERS_CHOICES = ("all", "corners")
+DENSE_MEMBERS = os.environ.get("EIGEN_DENSE_MEMBERS", "all")
+
 
 class DenseFitness:
     """The dense motion score as the fitness of a genome (include/eigen_engine.h eigen_dense_score): a dense,
@@ -322,13 +328,20 @@ class DenseFitness:
     `iters` iterations per level, every pixel re-sampling its whole window at its own displacement: the single step shrinks motions
     of a pixel and more toward zero, this solve follows them.  It costs about levels-and-iters times the window per pixel and has
     no gradient.
+    members: who is counted ("Members"; None: every pixel the mask counts).  A ``train.CornerMembers``: the
+    members of a genome are the corners the sparse fitness would pick on the first image of its pair, under the shared mask if one is
+    given: the quantity ``flow_objective()`` then hands to refinement with the same members.  A uint8 / bool [n, H, W] array: one plane
+    per sample of the call, zero = no member (``Engine.dense_score``, ``eval_images`` and ``eval_population`` with a batch of n; the
+    chunking and sharding ``fitness.evaluate_*`` functions refuse planes).  Members change who is counted, never the solve.
+    ``with_members(m)`` sets them on a fitness that exists.
     ValueError: the rules of ``train.FlowObjective`` for radius, eps and the mask (a per-sample mask is refused: the population has
-    one grid), a score that is none of the three classes, levels outside 1 .. 6, iters outside 1 .. 32, and (``solve_on``, once the
-    image is known) a coarsest level below 4 pixels on its shorter side."""
+    one grid), a score that is none of the three classes, levels outside 1 .. 6, iters outside 1 .. 32, (``solve_on``, once the
+    image is known) a coarsest level below 4 pixels on its shorter side, members that are neither a ``CornerMembers`` nor a uint8 / bool
+    [n, H, W] array, and member planes together with a shared mask (the planes say it all)."""
 
     MAX_LEVELS, MAX_ITERS, MIN_COARSE = 6, 32, 4
 
-    def __init__(self, score=None, radius=7, eps=1e-2, mask=None, levels=1, iters=1):
+    def __init__(self, score=None, radius=7, eps=1e-2, mask=None, levels=1, iters=1, members=None):
         from . import train
         flow = train.FlowObjective(radius, eps, mask=mask)     # its rules, its words
         if flow.per_sample:
@@ -342,12 +355,36 @@ class DenseFitness:
         self.levels, self.iters = int(levels), int(iters)
         self._dev = {}        # the mask on every device it was asked for, uploaded once
         self._resolved = {}   # without a score of its own: the object of every structure's class, made once
+        self.members = None
+        self.with_members(members)
 
     @classmethod
-    def for_structure(cls, structure, radius=7, eps=1e-2, mask=None, levels=1, iters=1, **kw):
+    def for_structure(cls, structure, radius=7, eps=1e-2, mask=None, levels=1, iters=1, members=None, **kw):
         """The dense fitness of a structure: ``train.structure_score(structure, **kw)`` as the score"""
         from . import train
-        return cls(train.structure_score(structure, **kw), radius=radius, eps=eps, mask=mask, levels=levels, iters=iters)
+        return cls(train.structure_score(structure, **kw), radius=radius, eps=eps, mask=mask, levels=levels, iters=iters, members=members)
+
+    def with_members(self, members):
+        """Set who is counted (a ``train.CornerMembers``, a uint8 / bool [n, H, W] array of per-sample planes, or None: every pixel the
+        mask counts) and return self.  ValueError: anything else, or planes on a fitness with a shared mask."""
+        from . import train
+        if members is not None and not isinstance(members, train.CornerMembers):
+            m = np.asarray(members)
+            if m.ndim != 3 or m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+                raise ValueError("members must be a CornerMembers, a uint8 / bool [n, H, W] array or None, got %s"
+                                 % ("an array of %s %s" % (m.dtype, m.shape) if isinstance(members, np.ndarray) else repr(members)))
+            if self.mask is not None:
+                raise ValueError("per-sample member planes do not go with a shared [H, W] mask: clear in the planes what the mask would not count")
+            members = np.ascontiguousarray(m != 0, dtype=np.uint8)
+        self.members = members
+        self._resolved = {}     # the objects made for a structure's class carried the earlier members
+        self._dev_planes = {}   # the planes on every device they were asked for, uploaded once
+        return self
+
+    @property
+    def member_planes(self):
+        """True where the members are per-sample planes"""
+        return isinstance(self.members, np.ndarray)
 
     def solve_on(self, w, h):
         """(levels, iters) against a w x h image.  ValueError: the coarsest level would be below 4 pixels on its shorter side."""
@@ -365,8 +402,8 @@ class DenseFitness:
         want = type(train.structure_score(structure))
         if self.score is None:      # made once per class; it shares this one's uploaded mask
             if want not in self._resolved:
-                d = DenseFitness(want(), self.radius, self.eps, self.mask, self.levels, self.iters)
-                d._dev = self._dev
+                d = DenseFitness(want(), self.radius, self.eps, self.mask, self.levels, self.iters, self.members)
+                d._dev, d._dev_planes = self._dev, self._dev_planes
                 self._resolved[want] = d
             return self._resolved[want]
         if type(self.score) is not want:
@@ -377,11 +414,15 @@ class DenseFitness:
         """The ``train.FlowObjective`` / ``PredictionFlow`` that refines by this score (``refine_genomes(flow=...)``).  It is always the
         single-step objective: with levels or iters above 1 refinement climbs the first iteration at level 0 of the same solve, the
         score of the field of one regularised step, not the iterated field the fitness scores.  A gradient through the iteration does
-        not exist."""
+        exist: ``solve_objective`` is the objective that carries it.  Corner members go with either, so refinement climbs what was
+        selected.
+        ValueError: per-sample member planes, which belong to one call's batch and not to an objective."""
         from . import train
         if self.score is None:
             raise ValueError("the DenseFitness has no score yet: resolved(structure) gives it the structure's")
-        return train.make_flow(pairing, self.radius, self.eps, None, self.mask, score=self.score)
+        if self.member_planes:
+            raise ValueError("per-sample member planes belong to one call's batch: an objective takes CornerMembers (or a per-sample mask of its own)")
+        return train.make_flow(pairing, self.radius, self.eps, None, self.mask, score=self.score, members=self.members)
 
     def solve_objective(self, pairing="prediction"):
         """``flow_objective(pairing)`` with this fitness's own solve, ``.solved(self.levels, self.iters)``: the objective whose gradient
@@ -405,13 +446,38 @@ class DenseFitness:
             self._dev[device] = torch.from_numpy(self.mask).cuda(device)
         return self._dev[device]
 
+    def members_on(self, torch, device, n, h, w):
+        """(the eigen_flow_members of a call of n samples on [h, w] images, the per-sample planes on the device or None under corner
+        members).  ValueError: planes that are not [n, h, w]."""
+        from . import train
+        if not self.member_planes:
+            return self.members.settings(), None
+        if tuple(self.members.shape) != (n, h, w):
+            raise ValueError("the member planes are %s, the call is [%d, %d, %d]" % (self.members.shape, n, h, w))
+        if device not in self._dev_planes:
+            self._dev_planes[device] = torch.from_numpy(self.members).cuda(device)
+        return train.FlowMembersSettings(train.FLOW_MEMBERS_MASK, 0, 0, 0, 0.0, 0.0, h * w), self._dev_planes[device]
+
 
 _DEFAULT_DENSE = DenseFitness()   # score="dense": the defaults of every structure, resolved once each
+_DEFAULT_DENSE_CORNERS = []       # and under DENSE_MEMBERS = "corners", made by the first call that asks
+
+
+def _default_dense():
+    if DENSE_MEMBERS not in DENSE_MEMBERS_CHOICES:
+        raise ValueError("DENSE_MEMBERS must be one of %s, got %r" % (", ".join(DENSE_MEMBERS_CHOICES), DENSE_MEMBERS))
+    if DENSE_MEMBERS == "all":
+        return _DEFAULT_DENSE
+    if not _DEFAULT_DENSE_CORNERS:
+        from . import train
+        _DEFAULT_DENSE_CORNERS.append(DenseFitness(members=train.CornerMembers()))
+    return _DEFAULT_DENSE_CORNERS[0]
 
 
 def resolve_score(score, structure):
     """`score` of evaluate_batch / evaluate_population / population_fitness -> None (the corner fitness) or the ``DenseFitness`` of the
-    call.  None: the module switch FITNESS_SCORE.  ValueError: neither "corners", "dense" nor a DenseFitness."""
+    call.  None: the module switch FITNESS_SCORE.  "dense" counts whom DENSE_MEMBERS names.  ValueError: neither "corners", "dense" nor
+    a DenseFitness; a DENSE_MEMBERS that is neither "all" nor "corners"."""
     if score is None:
         score = FITNESS_SCORE
     if isinstance(score, DenseFitness):
@@ -419,7 +485,7 @@ def resolve_score(score, structure):
     if score == "corners":
         return None
     if score == "dense":
-        return _DEFAULT_DENSE.resolved(structure)
+        return _default_dense().resolved(structure)
     raise ValueError("score must be one of %s or a DenseFitness, got %r" % (", ".join(FITNESS_SCORES), score))
 
 
@@ -431,10 +497,13 @@ def _engine_for(model_name, w, h, channels, max_batch, flow):
 def evaluate_batch(structure, gb, n_in, model_name, w, h, channels, c_dim=3, gradient=1, bg=1,
                    pairing=PAIR_POPULATION, max_batch=None, flow=None, score=None):
     """Fitness (float64 array) of an already flattened genome batch on the local GPU, in chunks of max_batch.  score: "corners",
-    "dense", a ``DenseFitness``, or None: the module switch FITNESS_SCORE."""
+    "dense", a ``DenseFitness``, or None: the module switch FITNESS_SCORE.  ValueError: a DenseFitness with per-sample member planes,
+    which belong to one batch: this function chunks, and its callers shard."""
     dense = resolve_score(score, structure)
     if dense is not None:
         dense.solve_on(w, h)       # ahead of the engine, as a ValueError
+        if dense.member_planes:
+            raise ValueError("per-sample member planes belong to one call's batch: the population functions chunk and shard, they take CornerMembers")
     channels = [int(c) for c in channels]
     if channels[0] != c_dim:
         raise ValueError("channels[0]=%d but c_dim=%d: PredNet's input channels are the image channels" % (channels[0], c_dim))
@@ -480,7 +549,9 @@ def population_fitness(structure, genomes, model_name, config, w, h, channels, c
     (SURVEY 8(e)).  Single process: plain evaluate_population.  score: as evaluate_batch; it reaches every rank's evaluator as it is
     given and changes nothing in the exchange: one float64 per genome in the same all-gather."""
     dist = _dist()
-    resolve_score(score, structure)   # a bad score raises here, on every rank alike, ahead of any collective
+    dense = resolve_score(score, structure)   # a bad score raises here, on every rank alike, ahead of any collective
+    if dense is not None and dense.member_planes:
+        raise ValueError("per-sample member planes belong to one call's batch: the population functions chunk and shard, they take CornerMembers")
     kw = dict(c_dim=c_dim, gradient=gradient, max_batch=max_batch, flow=flow, score=score)
     if dist is None:
         return evaluate_population(structure, genomes, model_name, config, w, h, channels, **kw)

@@ -15,6 +15,8 @@
     python examples/evolve_illusion.py -g 5 --fitness dense [--flow-radius R] [--flow-eps E] [--flow-score [--flow-max-norm M]]   (selection by the dense
         motion score of --structure, fitness.DenseFitness, in place of the corner tracks; with --refine K --objective flow --flow-score
         --flow-pairing prediction selection and refinement use one score with the same settings)
+    python examples/evolve_illusion.py -g 5 --fitness dense --dense-members corners [--dense-corner-quality X --dense-corner-distance X]   (the dense score
+        over the corners the corner fitness would track, not over every pixel; --refine --refine-solve fitness then refines under the same members)
     python examples/evolve_illusion.py -g 5 --fitness dense --dense-levels 3 --dense-iters 3   (the dense score on the field of a pyramidal, iterated
         Lucas-Kanade solve, which follows motions of a pixel and more where the single step shrinks them; --refine-solve fitness makes --refine climb that
         score through that solve, --flow-levels L --flow-iters K give the objective of the --flow-* options a solve of its own)
@@ -50,6 +52,11 @@ def main():
                     help="what selects: the reference's score of the tracked corners, or the dense motion score of --structure (fitness.DenseFitness)")
     ap.add_argument("--dense-levels", type=int, default=1, help="--fitness dense: pyramid levels of the solve (1 .. 6; 1 with --dense-iters 1 is the single step)")
     ap.add_argument("--dense-iters", type=int, default=1, help="--fitness dense: iterations per pyramid level (1 .. 32)")
+    ap.add_argument("--dense-members", default="all", choices=["all", "corners"],
+                    help="--fitness dense: who is counted: every pixel, or the corners the corner fitness would track (train.CornerMembers); "
+                         "--refine-solve fitness then refines under the same members")
+    ap.add_argument("--dense-corner-quality", type=float, default=None, help="--dense-members corners: goodFeaturesToTrack's quality level, in (0, 1] (default: CornerMembers')")
+    ap.add_argument("--dense-corner-distance", type=float, default=None, help="--dense-members corners: the least distance between two corners, in pixels (default: CornerMembers')")
     ap.add_argument("--refine-solve", default="single", choices=["single", "fitness"],
                     help="--refine under --fitness dense: single climbs the objective of the --flow-* options (by default the single regularised step), fitness "
                          "climbs DenseFitness.solve_objective(), the score of the field the fitness itself scores, through --dense-levels and --dense-iters")

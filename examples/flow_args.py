@@ -117,10 +117,16 @@ def flow_of(a, w, h, mask=None):
 def dense_fitness_of(a, structure, mask=None):
     """the fitness.DenseFitness of the command line under --fitness dense (None under corners): the window of --flow-radius and --flow-eps,
     the score of --flow-score where it is given (it must be `structure`'s: ValueError) and the structure's defaults otherwise, the
-    pixels of `mask`, the solve of --dense-levels and --dense-iters.  With --refine --objective flow --flow-score --flow-pairing prediction selection and refinement then use one score
+    pixels of `mask`, the solve of --dense-levels and --dense-iters, the members of --dense-members (corners: train.CornerMembers with
+    --dense-corner-quality and --dense-corner-distance).  With --refine --objective flow --flow-score --flow-pairing prediction selection and refinement then use one score
     with the same settings."""
     from evolutionary_illusion_generator_amd import fitness
     if getattr(a, "fitness", "corners") != "dense":
         return None
+    members = None
+    if getattr(a, "dense_members", "all") == "corners":   # --dense-members corners: the sparse fitness's own corners, CornerMembers' defaults unless said otherwise
+        from evolutionary_illusion_generator_amd import train
+        kw = {k: v for k, v in (("quality_level", getattr(a, "dense_corner_quality", None)), ("min_distance", getattr(a, "dense_corner_distance", None))) if v is not None}
+        members = train.CornerMembers(**kw)
     return fitness.DenseFitness(score_of(a), radius=a.flow_radius, eps=a.flow_eps, mask=mask, levels=getattr(a, "dense_levels", 1),
-                                iters=getattr(a, "dense_iters", 1)).resolved(structure)
+                                iters=getattr(a, "dense_iters", 1), members=members).resolved(structure)

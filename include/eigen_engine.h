@@ -908,6 +908,41 @@ int eigen_eval_images_dense_iter(eigen_engine* e, const uint8_t* d_images, int32
                                  const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, void* stream,
                                  const eigen_dense_solve* solve);
 
+/* ---------------------------------------------------------------------------------------------------- dense fitness: members
+ * The three dense entries with members ("Members"; csrc/dense_member_kernels.h): each takes its _iter namesake's
+ * arguments plus an eigen_flow_members, the struct of the trainer's scores.  members NULL: the call is the namesake's, launch for launch.
+ *   EIGEN_FLOW_MEMBERS_CORNERS: the members of sample b are the corners picked on img0 of its pair, the image the solve treats as the
+ *     reference, by cvtColor / cornerMinEigenVal(block_size, 3) / goodFeaturesToTrack(max_corners, quality_level, min_distance) with
+ *     eigen_flow's own kernels, in the sequence of the trainer's membership stage; d_mask, if given, is the shared [H][W] plane and
+ *     removes the corners it does not count.  The member planes [B][H W] then take the mask's place in the unchanged moment, prepare and
+ *     final kernels.
+ *   EIGEN_FLOW_MEMBERS_MASK: d_mask holds one plane per sample, mask_bstride >= H*W bytes apart.  A plane set that counts no pixel at
+ *     all is refused; a single sample that counts none scores exactly 0.
+ * Members change who is counted, never the solve: the field is the single step's or the levels x iters solve's.  The record of a call
+ * with corner members is, bit for bit, that of eigen_trainer_flow_term_pair with the same members on the (float)byte / 255.0f images.
+ * Under members the Free structure's pair pass runs over a compacted list of the members (at most max_corners, or H*W under planes)
+ * and leaves the bytes the all-pixel pass leaves for the same members.
+ * The workspace (the corner buffers of the trainer's membership stage; for Free the list, 12 bytes per slot of max_batch times the
+ * slots of a sample) is made by the first call that needs it, all of a group or none, and freed with the handle; a handle that never
+ * passes members allocates nothing more than before.  eigen_get_timings reports the stage, the membership stage included, as [2].
+ * eigen_dense_score_members: h_members (host, may be NULL) receives uint8 [batch][H][W], the member planes, and h_counts (host, may be
+ * NULL) int32 [batch], the corners selected per sample before the mask, as eigen_trainer_flow_members gives them; both are written under
+ * CORNERS only.
+ * Errors: the namesake's; EIGEN_ERR_INVALID before any launch or allocation, with the outputs untouched, for what
+ * eigen_trainer_flow_term_members refuses of the members, in its words: an unknown kind, reserved != 0, max_corners outside 1 .. 128,
+ * block_size outside 1 .. 9, quality_level outside (0, 1], min_distance negative or not finite, mask_bstride below H*W under MASK or
+ * not 0 under CORNERS, MASK without d_mask, a plane set that counts no pixel. */
+int eigen_dense_score_members(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int32_t batch,
+                              const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow,
+                              void* stream, const eigen_dense_solve* solve, const eigen_flow_members* members, uint8_t* h_members,
+                              int32_t* h_counts);
+int eigen_eval_population_dense_members(eigen_engine* e, const eigen_genome_batch* h_genomes, int32_t structure, int32_t bg, int32_t gradient,
+                                        int32_t pairing, const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness,
+                                        double* h_stats, void* stream, const eigen_dense_solve* solve, const eigen_flow_members* members);
+int eigen_eval_images_dense_members(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
+                                    const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats,
+                                    void* stream, const eigen_dense_solve* solve, const eigen_flow_members* members);
+
 /* Test hook of the solve: force >= 0 sets whether levels = 1, iters = 1 (and a NULL solve) goes through the iteration kernel too, on
  * this handle; pyramid_bytes (may be NULL) receives the bytes of the pyramid the handle holds, 0 before its first iterated call. */
 int eigen_debug_dense_solve(eigen_engine* e, int32_t force, int64_t* pyramid_bytes);

@@ -3,6 +3,7 @@
 
     python scripts/dense_fitness_bench.py [--rounds 6] [--shapes headline,ref160] [--out profiles/dense_fitness_cost.txt]
     python scripts/dense_fitness_bench.py --dense-levels 3 --dense-iters 3 --structures 0,1 --out OTHER.txt
+    python scripts/dense_fitness_bench.py --dense-members corners [--out profiles/dense_members_cost.txt]
 
 Per shape of bench.py (headline: 256 x 256 colour, pop 256; ref160: 160 x 120 colour, pop 50) and per structure,
 `fitness.population_fitness` is timed under score="corners" and score="dense" in alternation, one generation each per round, after
@@ -15,6 +16,11 @@ their mean rank) and the share of genomes scoring exactly 0 under each.
 With --dense-levels or --dense-iters above 1 the comparison is another one: the dense fitness's single step ("corners" in the columns'
 place) against its pyramidal, iterated solve (fitness.DenseFitness(levels=L, iters=K), in "dense"'s place), alternated in the same
 way; the header line says so and the lines name the two.
+
+With --dense-members corners three fitnesses are alternated: the corner fitness, the dense fitness on every pixel ("dense all") and the
+dense fitness whose members are the corner fitness's own corners ("dense corners", fitness.DenseFitness(members=train.CornerMembers());
+DESIGN.md section 14, "Members"), one line each, the two dense ones against the corner fitness.  The output goes to
+profiles/dense_members_cost.txt unless --out says otherwise.
 
 The output file has two parts: what this script measures, which a run replaces, and everything from the line NOTES_MARK on, which a run
 keeps as it finds it: the records of other commands of the same visit (the default path against the parent commit, the example), written by
@@ -67,13 +73,24 @@ def main():
     ap.add_argument("--structures", default="0,1,2", help="0 Bands, 1 Circles, 2 Free")
     ap.add_argument("--dense-levels", type=int, default=1, help="with --dense-iters: time the single step against this solve")
     ap.add_argument("--dense-iters", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dense_fitness_cost.txt"))
+    ap.add_argument("--dense-members", default="all", choices=["all", "corners"],
+                    help="corners: also time the dense fitness under the corner fitness's own corners as members, beside the corner fitness and the all-pixel dense one")
+    ap.add_argument("--out", default=None, help="default: profiles/dense_fitness_cost.txt, or profiles/dense_members_cost.txt with --dense-members corners")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "dense_members_cost.txt" if a.dense_members == "corners" else "dense_fitness_cost.txt")
     import torch
     import bench
     from evolutionary_illusion_generator_amd import fitness
     solve = (a.dense_levels, a.dense_iters)
-    if solve == (1, 1):
+    third = None      # --dense-members corners: the label of the third fitness, scores["members"]
+    if a.dense_members == "corners":
+        from evolutionary_illusion_generator_amd import train
+        first, second, third = "corners", "dense all", "dense corners"
+        scores = {"corners": "corners", "dense": fitness.DenseFitness(levels=solve[0], iters=solve[1]),
+                  "members": fitness.DenseFitness(levels=solve[0], iters=solve[1], members=train.CornerMembers())}
+        head = ("dense motion fitness on every pixel and on the corner fitness's corners against the corner fitness" + ("" if solve == (1, 1) else ", solve %d x %d" % solve)
+                + ", %s, %d rounds, the three alternated per round")
+    elif solve == (1, 1):
         first, second, scores = "corners", "dense", {"corners": "corners", "dense": "dense"}
         head = "dense motion fitness against the corner fitness, %s, %d rounds, corners and dense alternated per round"
     else:
@@ -103,11 +120,12 @@ def main():
                 t = eng.timings()
                 return fit, dt, t["prednet_ms"], t["flow_ms"] + t["score_ms"]
 
-            warm = {s: generation(s) for s in ("corners", "dense")}
+            keys = ("corners", "dense") + (("members",) if third else ())
+            warm = {s: generation(s) for s in keys}
             rounds = a.rounds if warm["dense"][1] <= a.slow else min(a.rounds, 2)
-            rate, stage, roll = {"corners": [], "dense": []}, {"corners": [], "dense": []}, []
+            rate, stage, roll = {s: [] for s in keys}, {s: [] for s in keys}, []
             for _ in range(rounds):
-                for s in ("corners", "dense"):
+                for s in keys:
                     fit, dt, roll_ms, stage_ms = generation(s)
                     assert fit.tobytes() == warm[s][0].tobytes(), "the fitness of a generation changed between rounds"
                     rate[s].append(pop / dt)
@@ -122,6 +140,13 @@ def main():
                 "dense stage" if solve == (1, 1) else "dense stage, " + second, spread(stage["dense"]), 100.0 * np.median(stage["dense"]) / np.median(roll)))
             say("          agreement over the %d genomes: Spearman %.3f; scoring 0: %s %.1f %%, %s %.1f %%" % (
                 pop, spearman(fc, fd), first, 100.0 * float((fc == 0).mean()), second, 100.0 * float((fd == 0).mean())))
+            if third:
+                fm = warm["members"][0]
+                say("  %-7s %s %s evals/s, %s / %s %.3f, %s / %s %.3f" % ("", third, spread(rate["members"]), third, first, np.median(rate["members"]) / np.median(rate["corners"]),
+                                                                      third, second, np.median(rate["members"]) / np.median(rate["dense"])))
+                say("          device ms per generation: %s stage %s = %.1f %% of the roll-out, %.2f of flow + score" % (
+                    third, spread(stage["members"]), 100.0 * np.median(stage["members"]) / np.median(roll), np.median(stage["members"]) / np.median(stage["corners"])))
+                say("          agreement of %s with %s over the %d genomes: Spearman %.3f; scoring 0: %.1f %%" % (third, first, pop, spearman(fc, fm), 100.0 * float((fm == 0).mean())))
         fitness.clear_engines()
         say("")
     kept = ""
