@@ -30,6 +30,10 @@ struct DenseWork {
     int *c_count = nullptr, *list_idx = nullptr, *list_count = nullptr;
     double* list_th = nullptr;
     long long list_cap = 0;
+    // float frames (EIGEN_DENSE_FLOAT_FRAMES, dense_gray_workspace), in member_allocs too: the two gray planes [2][max_batch H W] of the single
+    // step (the iterated solve keeps them as level 0 of pyr), and the byte copy [max_batch][C H W] of a float img0 for the corner members
+    double* gray = nullptr;
+    uint8_t* fbytes = nullptr;
     std::vector<void*> member_allocs;
 };
 
@@ -65,10 +69,31 @@ int dense_check(const eigen_dense_settings* s, const eigen_dense_solve* solve, b
 // The same with members (null: dense_check itself): the trainer's rules for them in its words (check_flow_members), every refusal ahead of
 // any allocation; then the members' workspace on w, all of a group or none.  Under per-sample planes d_mask is not read as a shared plane.
 int dense_check_members(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int C, int H, int W, int max_batch,
-                        const uint8_t* d_mask, const eigen_flow_members* members, int B, DenseWork& w, DenseSolve& out, DenseMembers& mem);
+                        const uint8_t* d_mask, const eigen_flow_members* members, int B, DenseWork& w, DenseSolve& out, DenseMembers& mem, int32_t allowed_flags = 0);
 
 // The launches of the stage on checked settings: the records of the B samples into w.rec, the field into d_flow (null: w.u)
 void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1,
                   long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st, const DenseMembers& mem = DenseMembers());
+
+// ---- float frames ("Float frames"): the stage from the float64 gray planes I0, I1 [B][H W] of its pair
+// What a float call needs beyond the stage's workspace, made by the first call that needs it and freed with the handle: under the single step
+// the two gray planes at max_batch, and for a float img0 under corner members its byte copy.  The iterated solve needs w.pyr, which the caller
+// has made.
+int dense_gray_workspace(int device, int H, int W, int max_batch, const DenseSolve& solve, bool float_img0, bool by_corners, int C, DenseWork& w);
+
+// Where the two gray planes of a call of B samples lie: level 0 of the pyramid under the iterated solve (w.pyr, then w.pyr + B H W), else w.gray
+void dense_gray_planes(const DenseWork& w, const DenseSolve& solve, int H, int W, int B, double*& I0, double*& I1);
+
+// The gray plane of one batch of planar images (image b at img + b * stride, elements) into dst [B][H W]: one launch on st
+void dense_gray_launch(const float* img, long long stride, int C, int H, int W, int B, double* dst, hipStream_t st);
+void dense_gray_launch(const uint8_t* img, long long stride, int C, int H, int W, int B, double* dst, hipStream_t st);
+
+// The bytes (uint8)(int)(v * 255.0f) of a float batch into w.fbytes, packed: the image the corner members are picked on
+void dense_quant_launch(const float* img, long long stride, int C, int H, int W, int B, const DenseWork& w, hipStream_t st);
+
+// dense_launch from ready gray planes at dense_gray_planes(w, solve, ...).  img0, stride0: the bytes of the first image of the pair, read
+// under corner members only (else null).
+void dense_launch_gray(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, int B, const uint8_t* d_mask,
+                       const DenseWork& w, double* d_flow, hipStream_t st, const DenseMembers& mem = DenseMembers());
 
 }  // namespace eigd

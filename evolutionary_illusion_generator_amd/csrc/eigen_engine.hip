@@ -136,6 +136,9 @@ struct eigen_engine {
     eigd::DenseWork dense;     // the dense fitness's workspace (eigen_dense_score): allocated by the first dense call, all of it or none
     bool have_dense = false;
     bool dense_force_iter = false;  // eigen_debug_dense_solve: one level, one iteration goes through the iteration kernel too
+    // eigen_debug_dense_gray: where the last float dense call left its gray planes (I0, then I1 behind batch * H * W doubles); 0: none, or overwritten
+    const double* dense_gray_at = nullptr;
+    int dense_gray_batch = 0;
     // Farneback dense flow (cfg.flow_method == EIGEN_FLOW_FARNEBACK): allocated on first use
     float *fb_I = nullptr, *fb_R0 = nullptr, *fb_R1 = nullptr, *fb_M = nullptr, *fb_V = nullptr, *fb_flow[2] = {nullptr, nullptr};
     DevBuf<float> raw4;   // partial chains of the unpooled source, [B][4 classes][n_nblk*NB][H/2][W/2], reused by all layers
@@ -885,7 +888,13 @@ int eigen_cppn_param_grads(eigen_engine* e, const eigen_genome_batch* g, int32_t
 
 // What one roll-out runs (eigen_prednet_rollout, eigen_prednet_sequence).  The input of step t < n_in is the uint8 image
 // in + b * in_bstride + t * in_tstride (elements) of state slot b; every later step is fed the previous prediction (cfg.requant_feedback).
+struct RollSnap {
+    int step = -1;          // the roll-out step behind whose ConvP0 launch the gray of the float prediction P0 is taken (-1: none)
+    double* dst = nullptr;  // [batch][H][W] float64 (dense_stage.h, dense_gray_launch)
+};
+
 struct RollPlan {
+    RollSnap snap[2];  // the float frames of the dense fitness (EIGEN_DENSE_FLOAT_FRAMES); a roll-out that names none launches what it always did
     const uint8_t* in;
     long long in_bstride, in_tstride;
     int batch, n_in, n_steps, first_out;
@@ -988,6 +997,9 @@ static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
                     HIPCHK(hipEventRecord(e->ev_join[l], e->side));
                 } else
                 HIPCHK(launch_conv(e, y.convP, a, nb, s));
+                if (l == 0)  // ConvP0 never leaves the step's stream: the snapshot reads P0 behind it, before the next step overwrites it
+                    for (const RollSnap& g : p.snap)
+                        if (g.dst && g.step == t) eigd::dense_gray_launch((const float*)off(y.P, y), (long long)e->C0 * HW, e->C0, e->H, e->W, nb, g.dst + (size_t)b0 * HW, s);
             }
         }
         return EIGEN_OK;
@@ -1001,10 +1013,9 @@ static int prednet_run(eigen_engine* e, const RollPlan& p, hipStream_t st)
     return EIGEN_OK;
 }
 
-extern "C" {
-
-int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t n_steps, int32_t first_out_step,
-                          uint8_t* d_frames, void* stream)
+// eigen_prednet_rollout; snaps (may be null): the gray snapshots of a float dense call
+static int prednet_rollout_impl(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t n_steps, int32_t first_out_step, uint8_t* d_frames, void* stream,
+                                const RollSnap* snaps)
 {
     if (!e || !d_images || !d_frames) return fail(EIGEN_ERR_INVALID, "null argument");
     if (!e->have_weights) return fail(EIGEN_ERR_STATE, "eigen_set_prednet_weights has not been called");
@@ -1017,7 +1028,16 @@ int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batc
     p.in = d_images; p.in_bstride = (long long)e->C0 * e->H * e->W; p.in_tstride = 0;  // one still image per genome
     p.batch = batch; p.n_in = std::min(e->cfg.n_repeat, (int)n_steps); p.n_steps = n_steps; p.first_out = first_out_step; p.out = d_frames;
     p.reset = true; p.keep_state = false;
+    if (snaps) { p.snap[0] = snaps[0]; p.snap[1] = snaps[1]; }
     return prednet_run(e, p, (hipStream_t)stream);
+}
+
+extern "C" {
+
+int eigen_prednet_rollout(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t n_steps, int32_t first_out_step,
+                          uint8_t* d_frames, void* stream)
+{
+    return prednet_rollout_impl(e, d_images, batch, n_steps, first_out_step, d_frames, stream, nullptr);
 }
 
 int eigen_prednet_sequence(eigen_engine* e, const uint8_t* d_in, int64_t in_bstride, int32_t batch, int32_t n_in, int32_t n_ext,
@@ -1199,28 +1219,49 @@ struct DenseCall {
     const uint8_t* d_mask = nullptr;
     eigd::DenseSolve solve;
     eigd::DenseMembers mem;
+    bool float_frames = false;  // EIGEN_DENSE_FLOAT_FRAMES: the stage starts from the gray planes at dense_gray_planes
 };
 
 // What every dense entry refuses before anything is launched (the roll-out included), then the workspace
+// float_entry: 0 a byte entry, which refuses EIGEN_DENSE_FLOAT_FRAMES; 1 an eval entry, which takes the flag or 0; 2 eigen_dense_score_float, float with
+// either, 3 the same with a float img0.  A float call's own workspace comes last, behind every refusal.
 static int dense_prepare(eigen_engine* e, DenseCall& c, const eigen_dense_settings* settings, const eigen_dense_solve* solve, const uint8_t* d_mask, int batch,
-                         const eigen_flow_members* members = nullptr)
+                         const eigen_flow_members* members = nullptr, int float_entry = 0)
 {
     if (!settings) return fail(EIGEN_ERR_INVALID, "null argument");
     if (batch < 1 || batch > e->B) return fail(EIGEN_ERR_INVALID, "batch %d outside 1 .. max_batch %d", batch, e->B);
     HIPCHK(hipSetDevice(e->cfg.device));
     c.settings = settings; c.d_mask = d_mask;
     // without members dense_check_members is dense_check; with them the members' buffers come behind every refusal
-    int rc = eigd::dense_check_members(settings, solve, e->dense_force_iter, e->cfg.device, e->C0, e->H, e->W, e->B, d_mask, members, batch, e->dense, c.solve, c.mem);
+    int rc = eigd::dense_check_members(settings, solve, e->dense_force_iter, e->cfg.device, e->C0, e->H, e->W, e->B, d_mask, members, batch, e->dense, c.solve, c.mem,
+                                       float_entry ? EIGEN_DENSE_FLOAT_FRAMES : 0);
     if (rc) return rc;
+    c.float_frames = float_entry >= 2 || (settings->flow.flags & EIGEN_DENSE_FLOAT_FRAMES) != 0;
     rc = dense_workspace(e);
     if (rc) return rc;
-    return c.solve.iterated ? dense_pyramid(e) : EIGEN_OK;
+    if (c.solve.iterated) {
+        rc = dense_pyramid(e);
+        if (rc) return rc;
+    }
+    if (!c.float_frames) {
+        if (c.solve.iterated) e->dense_gray_batch = 0;  // level 0 of the pyramid is about to hold the gray of bytes
+        return EIGEN_OK;
+    }
+    rc = eigd::dense_gray_workspace(e->cfg.device, e->H, e->W, e->B, c.solve, float_entry == 3, c.mem.by_corners, e->C0, e->dense);
+    return rc;
 }
 
 // The stage on a prepared call, and its host outputs: S_b alone comes back where the records are not asked for
+// (a float call: the gray planes of the pair are in place or enqueued on st; d_img0 is the byte image the corner members are picked on, d_img1 is not read)
 static int dense_run(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, const uint8_t* d_img1, int64_t stride1, int batch, const DenseCall& c, double* h_fitness,
                      double* h_stats, double* d_flow, hipStream_t st, bool sync)
 {
+    if (c.float_frames) {
+        eigd::dense_launch_gray(c.settings, c.solve, e->C0, e->H, e->W, d_img0, (long long)stride0, batch, c.d_mask, e->dense, d_flow, st, c.mem);
+        double *I0, *I1;
+        eigd::dense_gray_planes(e->dense, c.solve, e->H, e->W, batch, I0, I1);
+        e->dense_gray_at = I0; e->dense_gray_batch = batch;
+    } else
     eigd::dense_launch(c.settings, c.solve, e->C0, e->H, e->W, d_img0, (long long)stride0, d_img1, (long long)stride1, batch, c.d_mask, e->dense, d_flow, st,
                        c.mem);
     HIPCHK(hipGetLastError());
@@ -1268,6 +1309,45 @@ int eigen_dense_score(eigen_engine* e, const uint8_t* d_img0, int64_t stride0, c
     return eigen_dense_score_iter(e, d_img0, stride0, d_img1, stride1, batch, settings, d_mask, h_fitness, h_stats, d_flow, stream, nullptr);
 }
 
+int eigen_dense_score_float(eigen_engine* e, const uint8_t* d_img0, const float* d_fimg0, int64_t stride0, const float* d_img1, int64_t stride1, int32_t batch,
+                            const eigen_dense_settings* settings, const eigen_dense_solve* solve, const eigen_flow_members* members, const uint8_t* d_mask,
+                            double* h_fitness, double* h_stats, double* d_flow, void* stream)
+{
+    if (!e || !d_img1 || !settings) return fail(EIGEN_ERR_INVALID, "null argument");
+    if ((d_img0 != nullptr) == (d_fimg0 != nullptr)) return fail(EIGEN_ERR_INVALID, "exactly one of d_img0 (bytes) and d_fimg0 (floats) must be given");
+    const int64_t per = (int64_t)e->C0 * e->H * e->W;
+    if (stride0 < per || stride1 < per) return fail(EIGEN_ERR_INVALID, "a batch stride is smaller than one image (%lld elements)", (long long)per);
+    DenseCall c;
+    int rc = dense_prepare(e, c, settings, solve, d_mask, batch, members, d_fimg0 ? 3 : 2);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double *I0, *I1;
+    eigd::dense_gray_planes(e->dense, c.solve, e->H, e->W, batch, I0, I1);
+    e->dense_gray_batch = 0;
+    if (d_fimg0) eigd::dense_gray_launch(d_fimg0, (long long)stride0, e->C0, e->H, e->W, batch, I0, st);
+    else eigd::dense_gray_launch(d_img0, (long long)stride0, e->C0, e->H, e->W, batch, I0, st);
+    eigd::dense_gray_launch(d_img1, (long long)stride1, e->C0, e->H, e->W, batch, I1, st);
+    if (d_fimg0 && c.mem.by_corners) {  // the corners are picked on the byte image of img0, as the trainer's membership stage does for a float reference
+        eigd::dense_quant_launch(d_fimg0, (long long)stride0, e->C0, e->H, e->W, batch, e->dense, st);
+        d_img0 = e->dense.fbytes; stride0 = per;
+    }
+    return dense_run(e, d_img0, stride0, nullptr, 0, batch, c, h_fitness, h_stats, d_flow, st, true);
+}
+
+int eigen_debug_dense_gray(eigen_engine* e, int32_t batch, double* h_I0, double* h_I1, void* stream)
+{
+    if (!e || !h_I0 || !h_I1) return fail(EIGEN_ERR_INVALID, "null argument");
+    if (!e->dense_gray_batch) return fail(EIGEN_ERR_STATE, "no float dense call has left its gray planes on this handle (or an iterated byte call overwrote them)");
+    if (batch != e->dense_gray_batch) return fail(EIGEN_ERR_STATE, "the last float dense call was of a batch of %d, not %d", e->dense_gray_batch, batch);
+    HIPCHK(hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)batch * e->H * e->W;
+    HIPCHK(hipMemcpyAsync(h_I0, e->dense_gray_at, n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_I1, e->dense_gray_at + n, n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return EIGEN_OK;
+}
+
 // dense != nullptr: the dense stage (already prepared) in place of flow and score; h_stats is its records
 static int eval_images_impl(eigen_engine* e, const uint8_t* d_images, int batch, int structure, int pairing, double* h_fitness,
                             float* h_vectors, int32_t* h_counts, hipStream_t st, bool rendered, const DenseCall* dense = nullptr, double* h_stats = nullptr)
@@ -1280,12 +1360,22 @@ static int eval_images_impl(eigen_engine* e, const uint8_t* d_images, int batch,
     if (n_steps > nr + e->cfg.n_ext) return fail(EIGEN_ERR_INVALID, "pairing needs %d extension steps, engine has n_ext=%d", n_steps - nr, e->cfg.n_ext);
     if (!rendered) HIPCHK(hipEventRecord(e->ev[0], st));
     HIPCHK(hipEventRecord(e->ev[1], st));
-    int rc = eigen_prednet_rollout(e, d_images, batch, n_steps, first, e->d_frames, st);
+    // float frames: the gray of P0 at the pair's steps, taken inside the roll-out (its entry of eigen_get_timings); under PAIR_SINGLE img0 is the input image
+    RollSnap snaps[2];
+    double *I0 = nullptr, *I1 = nullptr;
+    if (dense && dense->float_frames) {
+        eigd::dense_gray_planes(e->dense, dense->solve, e->H, e->W, batch, I0, I1);
+        e->dense_gray_batch = 0;
+        if (pairing == EIGEN_PAIR_POPULATION) { snaps[0].step = nr - 1; snaps[0].dst = I0; snaps[1].step = nr; snaps[1].dst = I1; }
+        else { snaps[0].step = nr + 1; snaps[0].dst = I1; }
+    }
+    int rc = prednet_rollout_impl(e, d_images, batch, n_steps, first, e->d_frames, st, snaps);
     if (rc) return rc;
     HIPCHK(hipEventRecord(e->ev[2], st));
     const int n_out = n_steps - first;
     if (dense) {
         const int64_t fs = (int64_t)(n_out * img_bytes);
+        if (dense->float_frames && pairing != EIGEN_PAIR_POPULATION) eigd::dense_gray_launch(d_images, (long long)img_bytes, e->C0, e->H, e->W, batch, I0, st);
         if (pairing == EIGEN_PAIR_POPULATION) rc = dense_run(e, e->d_frames, fs, e->d_frames + img_bytes, fs, batch, *dense, h_fitness, h_stats, nullptr, st, false);
         else rc = dense_run(e, d_images, (int64_t)img_bytes, e->d_frames, fs, batch, *dense, h_fitness, h_stats, nullptr, st, false);
         if (rc) return rc;
@@ -1368,7 +1458,7 @@ int eigen_eval_population_dense_members(eigen_engine* e, const eigen_genome_batc
     int rc = dense_call_check(e, structure, pairing, settings);
     if (rc) return rc;
     DenseCall c;
-    rc = dense_prepare(e, c, settings, solve, d_mask, g->n_genomes, members);
+    rc = dense_prepare(e, c, settings, solve, d_mask, g->n_genomes, members, 1);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipEventRecord(e->ev[0], st));
@@ -1398,7 +1488,7 @@ int eigen_eval_images_dense_members(eigen_engine* e, const uint8_t* d_images, in
     int rc = dense_call_check(e, structure, pairing, settings);
     if (rc) return rc;
     DenseCall c;
-    rc = dense_prepare(e, c, settings, solve, d_mask, batch, members);
+    rc = dense_prepare(e, c, settings, solve, d_mask, batch, members, 1);
     if (rc) return rc;
     return eval_images_impl(e, d_images, batch, structure, pairing, h_fitness, nullptr, nullptr, (hipStream_t)stream, false, &c, h_stats);
 }

@@ -20,6 +20,7 @@
 #include "dense_fitness_kernels.h"
 #include "dense_member_kernels.h"
 #include "dense_pyr_kernels.h"
+#include "dense_float_kernels.h"
 #include "flow_iter_kernels.h"
 #include "flow_target_kernels.h"
 #include "flow_valid_kernels.h"
@@ -623,11 +624,14 @@ int dense_solve_check(const eigen_dense_solve* solve, bool force_iterated, int H
     return EIGEN_OK;
 }
 
-static int dense_spec(const eigen_dense_settings* s, int device, int H, int W, const uint8_t* d_mask, FlowSpec& f)
+// allowed_flags: 0, or EIGEN_DENSE_FLOAT_FRAMES where the entry takes float frames
+static int dense_spec(const eigen_dense_settings* s, int device, int H, int W, const uint8_t* d_mask, int32_t allowed_flags, FlowSpec& f)
 {
     if (!s) return tfail(EIGEN_ERR_INVALID, "null argument");
     if ((s->score != nullptr) == (s->sscore != nullptr)) return tfail(EIGEN_ERR_INVALID, "exactly one of the flow score and the flow structure score must be given");
-    int rc = check_flow_on(device, (long long)H * W, &s->flow, nullptr, d_mask, 0, f);
+    if (!allowed_flags && s->flow.flags == EIGEN_DENSE_FLOAT_FRAMES)
+        return tfail(EIGEN_ERR_INVALID, "flow flags 0x%x: the byte stage takes no float frames, eigen_dense_score_float does", (unsigned)s->flow.flags);
+    int rc = check_flow_on(device, (long long)H * W, &s->flow, nullptr, d_mask, allowed_flags, f);
     if (rc) return rc;
     rc = check_flow_score(s->score, nullptr, f);
     if (rc) return rc;
@@ -639,7 +643,7 @@ int dense_check(const eigen_dense_settings* s, const eigen_dense_solve* solve, b
     FlowSpec f;
     const int rc = dense_solve_check(solve, force_iterated, H, W, out);   // ahead of the mask's read-back
     if (rc) return rc;
-    return dense_spec(s, device, H, W, d_mask, f);
+    return dense_spec(s, device, H, W, d_mask, 0, f);
 }
 
 // The engine's image and the members' buffers of a DenseWork as the record the corner stage and check_flow_members work on: every
@@ -673,13 +677,13 @@ static int list_workspace(int device, int max_batch, long long cap, DenseWork& w
 }
 
 int dense_check_members(const eigen_dense_settings* s, const eigen_dense_solve* solve, bool force_iterated, int device, int C, int H, int W, int max_batch,
-                        const uint8_t* d_mask, const eigen_flow_members* members, int B, DenseWork& w, DenseSolve& out, DenseMembers& mem)
+                        const uint8_t* d_mask, const eigen_flow_members* members, int B, DenseWork& w, DenseSolve& out, DenseMembers& mem, int32_t allowed_flags)
 {
     mem = DenseMembers();
     FlowSpec f;
     int rc = dense_solve_check(solve, force_iterated, H, W, out);
     if (rc) return rc;
-    rc = dense_spec(s, device, H, W, per_sample_mask(members) ? nullptr : d_mask, f);   // per-sample planes are check_flow_members' to read
+    rc = dense_spec(s, device, H, W, per_sample_mask(members) ? nullptr : d_mask, allowed_flags, f);   // per-sample planes are check_flow_members' to read
     if (rc || !members) return rc;
     FlowWork v = members_view(device, C, H, W, max_batch, w, &w.member_allocs);
     rc = check_flow_members(v, members, d_mask, B, f);   // every refusal of it comes ahead of its one allocation, the corner buffers
@@ -693,10 +697,9 @@ int dense_check_members(const eigen_dense_settings* s, const eigen_dense_solve* 
     return list_workspace(device, max_batch, f.by_corners ? (long long)CORNER_MAX : (long long)H * W, w);
 }
 
-// The iterated solve: the gray planes of level 0, the reduced levels, then one launch per level from the coarsest to the finest, whose
-// field goes into u.  w.pyr holds, level after level, I0_l, I1_l and (l >= 1) the level's field.
-static void dense_pyr_launch(const DenseSolve& solve, int r, double eps, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1, long long stride1,
-                             int B, const DenseWork& w, double* u, hipStream_t st)
+// The iterated solve from the gray planes of level 0, which the caller has launched: the reduced levels, then one launch per level from
+// the coarsest to the finest, whose field goes into u.  w.pyr holds, level after level, I0_l, I1_l and (l >= 1) the level's field.
+static void dense_pyr_levels(const DenseSolve& solve, int r, double eps, int H, int W, int B, const DenseWork& w, double* u, hipStream_t st)
 {
     struct Level { int H, W; double *I0, *I1, *u; } lv[DENSE_MAX_LEVELS];
     double* at = w.pyr;
@@ -705,7 +708,6 @@ static void dense_pyr_launch(const DenseSolve& solve, int r, double eps, int C, 
         lv[l] = Level{h, ww, at, at + n, l ? at + 2 * n : u};
         at += 4 * n;
     }
-    ew(st, tdense_gray_kernel, (long long)B * H * W, img0, stride0, img1, stride1, C, H, W, (long long)B * H * W, lv[0].I0, lv[0].I1);
     for (int l = 1; l < solve.levels; ++l) {
         const long long n = (long long)B * lv[l].H * lv[l].W;
         ew(st, tdense_pyrdown_kernel, n, (const double*)lv[l - 1].I0, (const double*)lv[l - 1].I1, lv[l - 1].H, lv[l - 1].W, lv[l].H, lv[l].W, n, lv[l].I0, lv[l].I1);
@@ -720,22 +722,21 @@ static void dense_pyr_launch(const DenseSolve& solve, int r, double eps, int C, 
     }
 }
 
-void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1,
-                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st, const DenseMembers& mem)
+// The spec of checked settings: the same fields give the same spec, without the mask's read-back
+static FlowSpec dense_checked_spec(const eigen_dense_settings* s)
 {
-    // the settings were checked by dense_check: the same fields give the same spec, without the mask's read-back
     FlowSpec f;
     f.r = s->flow.radius; f.eps = s->flow.eps;
     (void)check_flow_score(s->score, nullptr, f);
     (void)check_flow_struct(s->sscore, nullptr, f);
-    const long long n = (long long)B * H * W;
-    double* u = d_flow ? d_flow : w.u;
-    if (solve.iterated) {
-        dense_pyr_launch(solve, f.r, f.eps, C, H, W, img0, stride0, img1, stride1, B, w, u, st);
-    } else {
-        ew(st, tdense_prep_kernel, n, img0, stride0, img1, stride1, C, H, W, n, w.planes);
-        hipLaunchKernelGGL(tdense_solve_kernel, flow_grid(H, W, B), dim3(FLOW_T), 0, st, (const double*)w.planes, n, H, W, f.r, f.eps, u);
-    }
+    return f;
+}
+
+// What follows the solve, for byte and float frames alike: who is counted, then the score's passes on the field u.  img0: the bytes of the
+// image the solve treats as the reference, read under corner members only.
+static void dense_score_launch(const FlowSpec& f, int C, int H, int W, const uint8_t* img0, long long stride0, int B, const uint8_t* d_mask, const DenseWork& w,
+                               const double* u, hipStream_t st, const DenseMembers& mem)
+{
     // Who is counted.  No members: one plane shared by the batch (mask stride 0).  Corner members: the trainer's membership stage on
     // img0, the image the solve treats as the reference, under the shared plane; its member planes then take the mask's place.
     // Per-sample planes: d_mask holds them.  Members change nothing of the solve above.
@@ -757,6 +758,87 @@ void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C,
         struct_passes<STRUCT_BANDS>(st, H, W, B, mask, mask_bstride, f.sscore, u, w.theta, w.flag, w.L, nullptr, nullptr, w.rec, w.part, nullptr);
     else
         struct_passes<STRUCT_FREE>(st, H, W, B, mask, mask_bstride, f.sscore, u, w.theta, w.flag, w.L, nullptr, nullptr, w.rec, w.part, nullptr, mem.given ? &list : nullptr);
+}
+
+void dense_launch(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, const uint8_t* img1,
+                  long long stride1, int B, const uint8_t* d_mask, const DenseWork& w, double* d_flow, hipStream_t st, const DenseMembers& mem)
+{
+    const FlowSpec f = dense_checked_spec(s);
+    const long long n = (long long)B * H * W;
+    double* u = d_flow ? d_flow : w.u;
+    if (solve.iterated) {
+        ew(st, tdense_gray_kernel, n, img0, stride0, img1, stride1, C, H, W, n, w.pyr, w.pyr + n);
+        dense_pyr_levels(solve, f.r, f.eps, H, W, B, w, u, st);
+    } else {
+        ew(st, tdense_prep_kernel, n, img0, stride0, img1, stride1, C, H, W, n, w.planes);
+        hipLaunchKernelGGL(tdense_solve_kernel, flow_grid(H, W, B), dim3(FLOW_T), 0, st, (const double*)w.planes, n, H, W, f.r, f.eps, u);
+    }
+    dense_score_launch(f, C, H, W, img0, stride0, B, d_mask, w, u, st, mem);
+}
+
+// ---- float frames (dense_float_kernels.h, DESIGN.md section 14, "Float frames")
+int dense_gray_workspace(int device, int H, int W, int max_batch, const DenseSolve& solve, bool float_img0, bool by_corners, int C, DenseWork& w)
+{
+    TCHK(hipSetDevice(device));
+    const std::pair<void**, long long> want[] = {{(void**)&w.gray, solve.iterated ? 0 : 2ll * max_batch * H * W * 8},
+                                                 {(void**)&w.fbytes, float_img0 && by_corners ? (long long)max_batch * C * H * W : 0}};
+    // all or none: the record takes what this call made once every buffer it asked for exists, a failure frees what it made
+    void* made[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        if (!want[i].second || *want[i].first) continue;
+        const hipError_t e = hipMalloc(&made[i], (size_t)want[i].second);
+        if (e != hipSuccess) {
+            if (made[0]) (void)hipFree(made[0]);
+            return tfail(EIGEN_ERR_HIP, "hipMalloc(%lld) for the dense fitness's float frames: %s", want[i].second, hipGetErrorString(e));
+        }
+    }
+    for (int i = 0; i < 2; ++i) {
+        if (!made[i]) continue;
+        *want[i].first = made[i];
+        w.member_allocs.push_back(made[i]);
+    }
+    return EIGEN_OK;
+}
+
+void dense_gray_planes(const DenseWork& w, const DenseSolve& solve, int H, int W, int B, double*& I0, double*& I1)
+{
+    I0 = solve.iterated ? w.pyr : w.gray;
+    I1 = I0 + (long long)B * H * W;
+}
+
+void dense_gray_launch(const float* img, long long stride, int C, int H, int W, int B, double* dst, hipStream_t st)
+{
+    const long long HW = (long long)H * W;
+    ew(st, tdense_gray_of_kernel<float>, B * HW, img, stride, C, HW, B * HW, dst);
+}
+
+void dense_gray_launch(const uint8_t* img, long long stride, int C, int H, int W, int B, double* dst, hipStream_t st)
+{
+    const long long HW = (long long)H * W;
+    ew(st, tdense_gray_of_kernel<uint8_t>, B * HW, img, stride, C, HW, B * HW, dst);
+}
+
+void dense_quant_launch(const float* img, long long stride, int C, int H, int W, int B, const DenseWork& w, hipStream_t st)
+{
+    const long long CHW = (long long)C * H * W;
+    ew(st, tcorner_quant_kernel, B * CHW, img, stride, CHW, B * CHW, w.fbytes);
+}
+
+void dense_launch_gray(const eigen_dense_settings* s, const DenseSolve& solve, int C, int H, int W, const uint8_t* img0, long long stride0, int B, const uint8_t* d_mask,
+                       const DenseWork& w, double* d_flow, hipStream_t st, const DenseMembers& mem)
+{
+    const FlowSpec f = dense_checked_spec(s);
+    const long long n = (long long)B * H * W;
+    double* u = d_flow ? d_flow : w.u;
+    if (solve.iterated) {
+        dense_pyr_levels(solve, f.r, f.eps, H, W, B, w, u, st);   // the planes are level 0 of the pyramid: tdense_gray_kernel is not launched
+    } else {
+        double *I0, *I1;
+        dense_gray_planes(w, solve, H, W, B, I0, I1);
+        ew(st, tdense_prep_gray_kernel, n, (const double*)I0, (const double*)I1, H, W, n, w.planes);
+        hipLaunchKernelGGL(tdense_solve_kernel, flow_grid(H, W, B), dim3(FLOW_T), 0, st, (const double*)w.planes, n, H, W, f.r, f.eps, u);
+    }
+    dense_score_launch(f, C, H, W, img0, stride0, B, d_mask, w, u, st, mem);
 }
 
 }  // namespace eigd

@@ -32,7 +32,8 @@ EXPORTS = ["eigen_abi_version", "eigen_gate_order", "eigen_winograd_mask", "eige
            "eigen_render_moving_cppn", "eigen_dense_score_iter", "eigen_eval_population_dense_iter", "eigen_eval_images_dense_iter",
            "eigen_debug_dense_solve", "eigen_trainer_flow_term_iter", "eigen_trainer_loss_grad_flow_iter", "eigen_trainer_debug_flow_iter",
            "eigen_trainer_flow_term_target", "eigen_trainer_loss_grad_flow_target", "eigen_moving_cppn_valid", "eigen_trainer_flow_term_valid",
-           "eigen_trainer_loss_grad_flow_joint", "eigen_dense_score_members", "eigen_eval_population_dense_members", "eigen_eval_images_dense_members"]
+           "eigen_trainer_loss_grad_flow_joint", "eigen_dense_score_members", "eigen_eval_population_dense_members", "eigen_eval_images_dense_members",
+           "eigen_dense_score_float", "eigen_debug_dense_gray"]
 
 
 class EigenConfig(ctypes.Structure):
@@ -71,6 +72,7 @@ class DenseSolveC(ctypes.Structure):
 
 
 FLOW_METHODS = {"lk": 0, "farneback": 1}  # eigen_flow_method
+DENSE_FLOAT_FRAMES = 2  # EIGEN_DENSE_FLOAT_FRAMES: bit 1 of eigen_dense_settings.flow.flags
 DENSE_REC = 10  # doubles of one sample's record (train.SCORE_STATS / BANDS_STATS / FREE_STATS)
 
 
@@ -381,10 +383,12 @@ class Engine:
     def _dense_args(self, dense):
         """`dense`: anything with ``dense_settings(h)`` -> (radius, eps, the ctypes settings of its score, True for a Circles score)
         and ``mask_on(torch, device, h, w)`` -> the shared mask on the device or None (``fitness.DenseFitness``).
-        -> (DenseSettingsC, what must stay alive during the call, the mask's pointer)"""
+        -> (DenseSettingsC, what must stay alive during the call, the mask's pointer).  A `dense` whose ``frames`` is "float" sets
+        EIGEN_DENSE_FLOAT_FRAMES: the eval entries then score PredNet's float predictions, the byte stage refuses it."""
         radius, eps, sc, by_circles = dense.dense_settings(self.height)
         addr = ctypes.addressof(sc)
-        cfg = DenseSettingsC(FlowSettingsC(int(radius), 0, float(eps)), addr if by_circles else None, None if by_circles else addr)
+        flags = DENSE_FLOAT_FRAMES if getattr(dense, "frames", "byte") == "float" else 0
+        cfg = DenseSettingsC(FlowSettingsC(int(radius), flags, float(eps)), addr if by_circles else None, None if by_circles else addr)
         import torch
         mask = dense.mask_on(torch, self.cfg.device, self.height, self.width)
         return cfg, (sc, mask), _ptr(mask)
@@ -449,6 +453,42 @@ class Engine:
         self.last_dense_stats = rec
         out = (fit,) + ((rec,) if stats else ()) + ((u[:batch].cpu().numpy(),) if flow else ()) + (((planes, counts),) if members_out else ())
         return out[0] if len(out) == 1 else out
+
+    def dense_score_float(self, img0, stride0, img1, stride1, batch, dense, stats=False, flow=False, stream=None):
+        """The dense stage alone on float images (eigen_dense_score_float): `img0` a uint8 or float32 device tensor, `img1` a float32
+        one, image b of either at its pointer + b * its stride (elements).  Results as ``dense_score``; the two gray planes the stage
+        started from are then ``last_dense_gray()``.  `dense` may carry either ``frames``.  There is no ``members_out``: the entry
+        returns no member planes; the corners are picked on the byte image of img0, where ``dense_score(members_out=True)`` returns them."""
+        import torch
+        if not (torch.is_tensor(img0) and img0.dtype in (torch.uint8, torch.float32)) or not (torch.is_tensor(img1) and img1.dtype == torch.float32):
+            raise ValueError("img0 must be a uint8 or float32 device tensor and img1 a float32 one")
+        cfg, keep, d_mask = self._dense_args(dense)
+        solve = self._dense_solve(dense)
+        batch = int(batch)
+        mem = self._dense_members(dense, batch)
+        fit, rec = np.zeros(max(batch, 0), np.float64), np.zeros((max(batch, 0), DENSE_REC), np.float64)
+        u = torch.empty((max(batch, 1), 2, self.height, self.width), dtype=torch.float64, device="cuda:%d" % self.cfg.device) if flow else None
+        if 1 <= batch <= self.max_batch:   # the C side reads through raw pointers: refuse buffers smaller than what it touches
+            per = self.c_dim * self.height * self.width
+            for buf, stride, what in ((img0, stride0, "img0"), (img1, stride1, "img1")):
+                have = buf.numel()
+                if int(stride) >= per and have < (batch - 1) * int(stride) + per:
+                    raise ValueError("%s buffer holds %d elements, %d are needed" % (what, have, (batch - 1) * int(stride) + per))
+        as_float = img0.dtype == torch.float32
+        _check(self.lib.eigen_dense_score_float(
+            self._h, None if as_float else _ptr(img0), _ptr(img0) if as_float else None, ctypes.c_int64(int(stride0)), _ptr(img1), ctypes.c_int64(int(stride1)),
+            ctypes.c_int32(batch), ctypes.byref(cfg), None if solve is None else ctypes.byref(solve), None if mem is None else ctypes.byref(mem[0]),
+            d_mask if mem is None or mem[1] is None else _ptr(mem[1]), _ptr(fit), _ptr(rec), _ptr(u), _stream_arg(stream)))
+        self.last_dense_stats = rec
+        out = (fit,) + ((rec,) if stats else ()) + ((u[:batch].cpu().numpy(),) if flow else ())
+        return out[0] if len(out) == 1 else out
+
+    def last_dense_gray(self, batch, stream=None):
+        """(I0, I1), float64 [batch, H, W] each: the gray planes the last float dense call on this engine started from
+        (eigen_debug_dense_gray).  EngineError: there was none, or it was of another batch."""
+        I0, I1 = (np.zeros((max(int(batch), 0), self.height, self.width), np.float64) for _ in range(2))
+        _check(self.lib.eigen_debug_dense_gray(self._h, ctypes.c_int32(int(batch)), _ptr(I0), _ptr(I1), _stream_arg(stream)))
+        return I0, I1
 
     def eval_population(self, gb, structure, bg=1, gradient=1, pairing=PAIR_POPULATION, stream=None, dense=None):
         """dense None: the corner fitness (eigen_eval_population).  dense: a ``fitness.DenseFitness`` resolved for `structure`: the dense

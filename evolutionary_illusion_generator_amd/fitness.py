@@ -315,6 +315,12 @@ FITNESS_SCORE = os.environ.get("EIGEN_FITNESS_SCORE", "corners")
 DENSE_MEMBERS_CHOICES = ("all", "corners")
 DENSE_MEMBERS = os.environ.get("EIGEN_DENSE_MEMBERS", "all")
 
+# Which images the dense score reads where `score` is "dense" (and in get_fitnesses_neat under FITNESS_SCORE = "dense"): "byte", the frames
+# the roll-out emits, or "float", PredNet's float predictions before the byte, the images the flow objective itself is evaluated on
+# ("Float frames").  Environment EIGEN_DENSE_FRAMES.  A ``DenseFitness`` given as `score` carries its own.
+DENSE_FRAMES_CHOICES = ("byte", "float")
+DENSE_FRAMES = os.environ.get("EIGEN_DENSE_FRAMES", "byte")
+
 
 class DenseFitness:
     """The dense motion score as the fitness of a genome (include/eigen_engine.h eigen_dense_score): a dense,
@@ -334,14 +340,23 @@ class DenseFitness:
     per sample of the call, zero = no member (``Engine.dense_score``, ``eval_images`` and ``eval_population`` with a batch of n; the
     chunking and sharding ``fitness.evaluate_*`` functions refuse planes).  Members change who is counted, never the solve.
     ``with_members(m)`` sets them on a fitness that exists.
+    frames: which images of the pair the population path scores ("Float frames").  "byte", the default: the uint8
+    frames the roll-out emits.  "float": PredNet's float predictions P0 as the roll-out computed them, clamped to [0, 1], before the
+    byte (under ``PAIR_SINGLE`` the first image stays the input image).  The roll-out and the emitted frames do not change; corner members
+    are still picked on the bytes.  Between two consecutive predictions of a still the intensity changes are of the order of one grey
+    level, so the byte fitness sees a difference that is zero over most of the image; the float fitness is a continuous function of the
+    network's output between its norm cuts, and the same function of P0 that ``flow_objective()`` hands to refinement.
+    ``on_frames(kind)`` sets it on a fitness that exists.  ``Engine.dense_score`` is the byte stage and refuses a "float" fitness;
+    ``Engine.dense_score_float`` is the float stage.
     ValueError: the rules of ``train.FlowObjective`` for radius, eps and the mask (a per-sample mask is refused: the population has
     one grid), a score that is none of the three classes, levels outside 1 .. 6, iters outside 1 .. 32, (``solve_on``, once the
     image is known) a coarsest level below 4 pixels on its shorter side, members that are neither a ``CornerMembers`` nor a uint8 / bool
-    [n, H, W] array, and member planes together with a shared mask (the planes say it all)."""
+    [n, H, W] array, member planes together with a shared mask (the planes say it all), and frames that are neither "byte" nor
+    "float"."""
 
     MAX_LEVELS, MAX_ITERS, MIN_COARSE = 6, 32, 4
 
-    def __init__(self, score=None, radius=7, eps=1e-2, mask=None, levels=1, iters=1, members=None):
+    def __init__(self, score=None, radius=7, eps=1e-2, mask=None, levels=1, iters=1, members=None, frames="byte"):
         from . import train
         flow = train.FlowObjective(radius, eps, mask=mask)     # its rules, its words
         if flow.per_sample:
@@ -357,12 +372,21 @@ class DenseFitness:
         self._resolved = {}   # without a score of its own: the object of every structure's class, made once
         self.members = None
         self.with_members(members)
+        self.on_frames(frames)
 
     @classmethod
-    def for_structure(cls, structure, radius=7, eps=1e-2, mask=None, levels=1, iters=1, members=None, **kw):
+    def for_structure(cls, structure, radius=7, eps=1e-2, mask=None, levels=1, iters=1, members=None, frames="byte", **kw):
         """The dense fitness of a structure: ``train.structure_score(structure, **kw)`` as the score"""
         from . import train
-        return cls(train.structure_score(structure, **kw), radius=radius, eps=eps, mask=mask, levels=levels, iters=iters, members=members)
+        return cls(train.structure_score(structure, **kw), radius=radius, eps=eps, mask=mask, levels=levels, iters=iters, members=members, frames=frames)
+
+    def on_frames(self, kind):
+        """Set which images are scored ("byte" or "float") and return self.  ValueError: anything else."""
+        if not isinstance(kind, str) or kind not in DENSE_FRAMES_CHOICES:
+            raise ValueError("frames must be one of %s, got %r" % (", ".join(DENSE_FRAMES_CHOICES), kind))
+        self.frames = kind
+        self._resolved = {}     # the objects made for a structure's class carried the earlier frames
+        return self
 
     def with_members(self, members):
         """Set who is counted (a ``train.CornerMembers``, a uint8 / bool [n, H, W] array of per-sample planes, or None: every pixel the
@@ -402,7 +426,7 @@ class DenseFitness:
         want = type(train.structure_score(structure))
         if self.score is None:      # made once per class; it shares this one's uploaded mask
             if want not in self._resolved:
-                d = DenseFitness(want(), self.radius, self.eps, self.mask, self.levels, self.iters, self.members)
+                d = DenseFitness(want(), self.radius, self.eps, self.mask, self.levels, self.iters, self.members, self.frames)
                 d._dev, d._dev_planes = self._dev, self._dev_planes
                 self._resolved[want] = d
             return self._resolved[want]
@@ -415,7 +439,8 @@ class DenseFitness:
         single-step objective: with levels or iters above 1 refinement climbs the first iteration at level 0 of the same solve, the
         score of the field of one regularised step, not the iterated field the fitness scores.  A gradient through the iteration does
         exist: ``solve_objective`` is the objective that carries it.  Corner members go with either, so refinement climbs what was
-        selected.
+        selected.  The objective does not depend on ``frames``: it is evaluated on the float predictions, so under frames="float" it and
+        the fitness are the same function of P0, and under "byte" the fitness is that function of the requantised bytes.
         ValueError: per-sample member planes, which belong to one call's batch and not to an objective."""
         from . import train
         if self.score is None:
@@ -427,7 +452,8 @@ class DenseFitness:
     def solve_objective(self, pairing="prediction"):
         """``flow_objective(pairing)`` with this fitness's own solve, ``.solved(self.levels, self.iters)``: the objective whose gradient
         runs through every iteration and level ("The iterated solve's gradient"), so that refinement climbs the
-        score of the field the fitness scores.  At levels = iters = 1 it is ``flow_objective``'s."""
+        score of the field the fitness scores.  At levels = iters = 1 it is ``flow_objective``'s.  As there, ``frames`` plays no part: under
+        frames="float" this objective and the fitness are the same function of P0."""
         return self.flow_objective(pairing).solved(self.levels, self.iters)
 
     # what engine.Engine asks of a `dense` argument
@@ -461,11 +487,19 @@ class DenseFitness:
 
 _DEFAULT_DENSE = DenseFitness()   # score="dense": the defaults of every structure, resolved once each
 _DEFAULT_DENSE_CORNERS = []       # and under DENSE_MEMBERS = "corners", made by the first call that asks
+_DEFAULT_DENSE_FLOAT = {}         # and under DENSE_FRAMES = "float", per DENSE_MEMBERS, likewise
 
 
 def _default_dense():
     if DENSE_MEMBERS not in DENSE_MEMBERS_CHOICES:
         raise ValueError("DENSE_MEMBERS must be one of %s, got %r" % (", ".join(DENSE_MEMBERS_CHOICES), DENSE_MEMBERS))
+    if DENSE_FRAMES not in DENSE_FRAMES_CHOICES:
+        raise ValueError("DENSE_FRAMES must be one of %s, got %r" % (", ".join(DENSE_FRAMES_CHOICES), DENSE_FRAMES))
+    if DENSE_FRAMES == "float":
+        if DENSE_MEMBERS not in _DEFAULT_DENSE_FLOAT:
+            from . import train
+            _DEFAULT_DENSE_FLOAT[DENSE_MEMBERS] = DenseFitness(members=train.CornerMembers() if DENSE_MEMBERS == "corners" else None, frames="float")
+        return _DEFAULT_DENSE_FLOAT[DENSE_MEMBERS]
     if DENSE_MEMBERS == "all":
         return _DEFAULT_DENSE
     if not _DEFAULT_DENSE_CORNERS:
@@ -476,8 +510,9 @@ def _default_dense():
 
 def resolve_score(score, structure):
     """`score` of evaluate_batch / evaluate_population / population_fitness -> None (the corner fitness) or the ``DenseFitness`` of the
-    call.  None: the module switch FITNESS_SCORE.  "dense" counts whom DENSE_MEMBERS names.  ValueError: neither "corners", "dense" nor
-    a DenseFitness; a DENSE_MEMBERS that is neither "all" nor "corners"."""
+    call.  None: the module switch FITNESS_SCORE.  "dense" counts whom DENSE_MEMBERS names, on the images DENSE_FRAMES names.  ValueError:
+    neither "corners", "dense" nor a DenseFitness; a DENSE_MEMBERS that is neither "all" nor "corners"; a DENSE_FRAMES that is neither
+    "byte" nor "float"."""
     if score is None:
         score = FITNESS_SCORE
     if isinstance(score, DenseFitness):

@@ -17,6 +17,8 @@
         --flow-pairing prediction selection and refinement use one score with the same settings)
     python examples/evolve_illusion.py -g 5 --fitness dense --dense-members corners [--dense-corner-quality X --dense-corner-distance X]   (the dense score
         over the corners the corner fitness would track, not over every pixel; --refine --refine-solve fitness then refines under the same members)
+    python examples/evolve_illusion.py -g 5 --fitness dense --dense-frames float   (the dense score on PredNet's float predictions, not on their bytes:
+        selection then sees the sub-byte differences refinement moves)
     python examples/evolve_illusion.py -g 5 --fitness dense --dense-levels 3 --dense-iters 3   (the dense score on the field of a pyramidal, iterated
         Lucas-Kanade solve, which follows motions of a pixel and more where the single step shrinks them; --refine-solve fitness makes --refine climb that
         score through that solve, --flow-levels L --flow-iters K give the objective of the --flow-* options a solve of its own)
@@ -55,6 +57,9 @@ def main():
     ap.add_argument("--dense-members", default="all", choices=["all", "corners"],
                     help="--fitness dense: who is counted: every pixel, or the corners the corner fitness would track (train.CornerMembers); "
                          "--refine-solve fitness then refines under the same members")
+    ap.add_argument("--dense-frames", default="byte", choices=["byte", "float"],
+                    help="--fitness dense: the images the score reads: the frames the roll-out emits, or PredNet's float predictions before the byte, "
+                         "the images --objective flow itself is evaluated on (fitness.DenseFitness(frames=))")
     ap.add_argument("--dense-corner-quality", type=float, default=None, help="--dense-members corners: goodFeaturesToTrack's quality level, in (0, 1] (default: CornerMembers')")
     ap.add_argument("--dense-corner-distance", type=float, default=None, help="--dense-members corners: the least distance between two corners, in pixels (default: CornerMembers')")
     ap.add_argument("--refine-solve", default="single", choices=["single", "fitness"],

@@ -118,7 +118,7 @@ def dense_fitness_of(a, structure, mask=None):
     """the fitness.DenseFitness of the command line under --fitness dense (None under corners): the window of --flow-radius and --flow-eps,
     the score of --flow-score where it is given (it must be `structure`'s: ValueError) and the structure's defaults otherwise, the
     pixels of `mask`, the solve of --dense-levels and --dense-iters, the members of --dense-members (corners: train.CornerMembers with
-    --dense-corner-quality and --dense-corner-distance).  With --refine --objective flow --flow-score --flow-pairing prediction selection and refinement then use one score
+    --dense-corner-quality and --dense-corner-distance), the images of --dense-frames (float: PredNet's float predictions in place of the emitted bytes).  With --refine --objective flow --flow-score --flow-pairing prediction selection and refinement then use one score
     with the same settings."""
     from evolutionary_illusion_generator_amd import fitness
     if getattr(a, "fitness", "corners") != "dense":
@@ -129,4 +129,4 @@ def dense_fitness_of(a, structure, mask=None):
         kw = {k: v for k, v in (("quality_level", getattr(a, "dense_corner_quality", None)), ("min_distance", getattr(a, "dense_corner_distance", None))) if v is not None}
         members = train.CornerMembers(**kw)
     return fitness.DenseFitness(score_of(a), radius=a.flow_radius, eps=a.flow_eps, mask=mask, levels=getattr(a, "dense_levels", 1),
-                                iters=getattr(a, "dense_iters", 1), members=members).resolved(structure)
+                                iters=getattr(a, "dense_iters", 1), members=members, frames=getattr(a, "dense_frames", "byte")).resolved(structure)

@@ -318,7 +318,9 @@ int eigen_test_det_math(eigen_engine* e, const float* d_x, int32_t n, float* d_e
 
 /* Per-stage timing of the last eigen_eval_* call, milliseconds, measured with HIP events on the stream:
  * [0] render  [1] PredNet roll-out  [2] flow  [3] score  [4] PredNet conv kernels only (sum)
- * [5] number of conv kernel launches in the roll-out. */
+ * [5] number of conv kernel launches in the roll-out.
+ * A dense call reports its stage as [2] and 0 as [3]; under EIGEN_DENSE_FLOAT_FRAMES the gray snapshots taken inside the roll-out fall
+ * into [1], and the stage from the gray planes on (under EIGEN_PAIR_SINGLE with the gray of the input image) into [2]. */
 int eigen_get_timings(eigen_engine* e, double* h_ms6);
 
 /* Per-op profile of the roll-out convolutions.  enable=1 brackets every conv launch with HIP events recorded on the
@@ -826,7 +828,8 @@ int64_t eigen_trainer_tape_bytes(const eigen_trainer* t);
  * exactly 0.  Float64, one IEEE operation per operation written, fixed partitions and orders, no float atomics: the result of a
  * sample does not depend on the batch it is in.  No seed, q or gradient is formed, and no corner, Lucas-Kanade or score_kernel launch
  * happens.
- *   flow: radius and eps as eigen_trainer_flow_term reads them; flags must be 0.  Exactly one of score (Circles, CirclesFree) and
+ *   flow: radius and eps as eigen_trainer_flow_term reads them; flags must be 0 (the eval entries also take EIGEN_DENSE_FLOAT_FRAMES,
+ *   below).  Exactly one of score (Circles, CirclesFree) and
  *   sscore (Bands, Free) is non-NULL.
  * The workspace, seven float64 planes of max_batch * H * W and one byte plane, is allocated by the first dense call on the handle, all
  * of it or none, and freed with the handle. */
@@ -942,6 +945,44 @@ int eigen_eval_population_dense_members(eigen_engine* e, const eigen_genome_batc
 int eigen_eval_images_dense_members(eigen_engine* e, const uint8_t* d_images, int32_t batch, int32_t structure, int32_t pairing,
                                     const eigen_dense_settings* settings, const uint8_t* d_mask, double* h_fitness, double* h_stats,
                                     void* stream, const eigen_dense_solve* solve, const eigen_flow_members* members);
+
+/* ---------------------------------------------------------------------------------------------------- dense fitness: float frames
+ * The dense stage on PredNet's float predictions in place of the bytes the roll-out emits ("Float frames";
+ * csrc/dense_float_kernels.h): the image pair the flow objective itself is evaluated on, so that the fitness is a continuous function
+ * of the network's output between its norm cuts.  Bit 1 of eigen_dense_settings.flow.flags; the six eigen_eval_population_dense* /
+ * eigen_eval_images_dense* entries accept 0 or this bit, and refuse every other bit as before.  The three byte-stage entries
+ * eigen_dense_score* refuse it and name eigen_dense_score_float.
+ *   EIGEN_PAIR_POPULATION: img0 = P0 after step n_repeat, img1 = P0 after the first extension step, both float32 [C0][H][W] as ConvP0
+ *     wrote them: clamped to [0, 1], before the byte.
+ *   EIGEN_PAIR_SINGLE: img0 is the input image, (float)byte / 255.0f as without the flag; img1 = P0 after the second extension step.
+ * The roll-out itself does not change by a bit: extension steps are fed as cfg.requant_feedback says and the emitted frames are the
+ * bytes a call without the flag emits.  One launch behind the ConvP0 launch of a named step writes the float64 gray plane of P0
+ * (tflow_gray's operations on the widened float32 values); the stage starts from the two gray planes I0, I1 [B][H W], forms the
+ * normalised Scharr pair of I0 and It = I1 - I0 from them, and launches the single step or the levels x iters solve, the score passes
+ * and the members exactly as they are.  Hence the record of a sample is, bit for bit, the record eigen_trainer_flow_term_pair (for a
+ * byte img0: eigen_trainer_flow_term) leaves on the same float images under the same score, mask, members and solve; on float images
+ * that are exactly (float)byte / 255.0f it is the record eigen_dense_score leaves on those bytes.  Corner members are picked on the
+ * byte image of img0, (uint8)(int)(v * 255.0f): on the population path the emitted frame (or the input image), so the corners are
+ * the ones the byte fitness and the sparse fitness pick.
+ * Workspace: under the single step two float64 planes of max_batch * H * W; the iterated solve keeps the planes as level 0 of its
+ * pyramid.  The first float call on the handle allocates it, behind every refusal and before the render and the roll-out, and it is
+ * freed with the handle; a handle that never asks allocates nothing new. */
+#define EIGEN_DENSE_FLOAT_FRAMES 2
+
+/* The float stage alone.  Exactly one of d_img0 (uint8) and d_fimg0 (float32) is non-NULL, the d_ref / d_fref convention of the
+ * trainer's entries; d_img1 is float32.  Image b at its pointer + b * its stride, strides in elements, planar [C][H][W]; float values
+ * are read as they are (the corner members clamp them to [0, 1] for the byte).  settings->flow.flags is 0 or
+ * EIGEN_DENSE_FLOAT_FRAMES; solve and members may be NULL.  Outputs and synchronisation as eigen_dense_score.  With a float img0
+ * under corner members the handle keeps one byte copy of max_batch images, made by the first such call.
+ * Errors: eigen_dense_score_members' own, in its words, and EIGEN_ERR_INVALID for both or neither img0; all before any launch. */
+int eigen_dense_score_float(eigen_engine* e, const uint8_t* d_img0, const float* d_fimg0, int64_t stride0, const float* d_img1, int64_t stride1,
+                            int32_t batch, const eigen_dense_settings* settings, const eigen_dense_solve* solve, const eigen_flow_members* members,
+                            const uint8_t* d_mask, double* h_fitness, double* h_stats, double* d_flow, void* stream);
+
+/* Stage-level read-back for the tests: the two gray planes of the last float dense call on the handle, host double [batch][H][W] each.
+ * EIGEN_ERR_STATE where there was none (or an iterated byte call has since overwritten level 0 of the pyramid), or where the batch
+ * differs.  It launches no kernel. */
+int eigen_debug_dense_gray(eigen_engine* e, int32_t batch, double* h_I0, double* h_I1, void* stream);
 
 /* Test hook of the solve: force >= 0 sets whether levels = 1, iters = 1 (and a NULL solve) goes through the iteration kernel too, on
  * this handle; pyramid_bytes (may be NULL) receives the bytes of the pyramid the handle holds, 0 before its first iterated call. */

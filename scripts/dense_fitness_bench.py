@@ -22,6 +22,11 @@ dense fitness whose members are the corner fitness's own corners ("dense corners
 DESIGN.md section 14, "Members"), one line each, the two dense ones against the corner fitness.  The output goes to
 profiles/dense_members_cost.txt unless --out says otherwise.
 
+With --dense-frames float the comparison is the dense fitness on the emitted bytes ("byte") against the same fitness on PredNet's float
+predictions ("float", fitness.DenseFitness(frames="float"); DESIGN.md section 14, "Float frames"), alternated in the same way, under the
+members --dense-members names and the solve --dense-levels / --dense-iters name; the roll-out, which holds the float call's two gray
+snapshots, is reported for each of the two.  The output goes to profiles/dense_float_cost.txt unless --out says otherwise.
+
 The output file has two parts: what this script measures, which a run replaces, and everything from the line NOTES_MARK on, which a run
 keeps as it finds it: the records of other commands of the same visit (the default path against the parent commit, the example), written by
 hand."""
@@ -75,15 +80,29 @@ def main():
     ap.add_argument("--dense-iters", type=int, default=1)
     ap.add_argument("--dense-members", default="all", choices=["all", "corners"],
                     help="corners: also time the dense fitness under the corner fitness's own corners as members, beside the corner fitness and the all-pixel dense one")
-    ap.add_argument("--out", default=None, help="default: profiles/dense_fitness_cost.txt, or profiles/dense_members_cost.txt with --dense-members corners")
+    ap.add_argument("--dense-frames", default="byte", choices=["byte", "float"],
+                    help="float: time the dense fitness on the emitted bytes against the same fitness on the float predictions")
+    ap.add_argument("--append", action="store_true", help="add this run to the output file's measured part in place of replacing it")
+    ap.add_argument("--out", default=None, help="default: profiles/dense_fitness_cost.txt, dense_members_cost.txt with --dense-members corners, dense_float_cost.txt with --dense-frames float")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "dense_members_cost.txt" if a.dense_members == "corners" else "dense_fitness_cost.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "dense_float_cost.txt" if a.dense_frames == "float" else
+                                  "dense_members_cost.txt" if a.dense_members == "corners" else "dense_fitness_cost.txt")
     import torch
     import bench
     from evolutionary_illusion_generator_amd import fitness
     solve = (a.dense_levels, a.dense_iters)
-    third = None      # --dense-members corners: the label of the third fitness, scores["members"]
-    if a.dense_members == "corners":
+    third = None      # --dense-members corners (byte frames): the label of the third fitness, scores["members"]
+    # the two alternated fitnesses sit under the keys "corners" and "dense" whatever they are: first / second name them in the output
+    by_frames = a.dense_frames == "float"
+    if by_frames:
+        from evolutionary_illusion_generator_amd import train
+        members = train.CornerMembers() if a.dense_members == "corners" else None
+        first, second = "byte", "float"
+        scores = {"corners": fitness.DenseFitness(levels=solve[0], iters=solve[1], members=members),
+                  "dense": fitness.DenseFitness(levels=solve[0], iters=solve[1], members=members, frames="float")}
+        head = ("dense motion fitness on the emitted bytes against the float predictions, members %s, solve %d x %d" % ((a.dense_members,) + solve)
+                + ", %s, %d rounds, the two alternated per round")
+    elif a.dense_members == "corners":
         from evolutionary_illusion_generator_amd import train
         first, second, third = "corners", "dense all", "dense corners"
         scores = {"corners": "corners", "dense": fitness.DenseFitness(levels=solve[0], iters=solve[1]),
@@ -123,7 +142,7 @@ def main():
             keys = ("corners", "dense") + (("members",) if third else ())
             warm = {s: generation(s) for s in keys}
             rounds = a.rounds if warm["dense"][1] <= a.slow else min(a.rounds, 2)
-            rate, stage, roll = {s: [] for s in keys}, {s: [] for s in keys}, []
+            rate, stage, roll, roll_of = {s: [] for s in keys}, {s: [] for s in keys}, [], {s: [] for s in keys}
             for _ in range(rounds):
                 for s in keys:
                     fit, dt, roll_ms, stage_ms = generation(s)
@@ -131,13 +150,19 @@ def main():
                     rate[s].append(pop / dt)
                     stage[s].append(stage_ms)
                     roll.append(roll_ms)
+                    roll_of[s].append(roll_ms)
             fc, fd = warm["corners"][0], warm["dense"][0]
             say("  %-7s %s %s evals/s, %s %s evals/s, %s / %s %.3f%s" % (
                 name, first, spread(rate["corners"]), second, spread(rate["dense"]), second, first, np.median(rate["dense"]) / np.median(rate["corners"]),
                 "" if rounds == a.rounds else "  [%d rounds: a dense generation takes %.1f s]" % (rounds, warm["dense"][1])))
-            say("          device ms per generation: roll-out %s; %s %s; %s %s = %.1f %% of the roll-out" % (
-                spread(roll), "flow + score" if solve == (1, 1) else "dense stage, single step", spread(stage["corners"]),
-                "dense stage" if solve == (1, 1) else "dense stage, " + second, spread(stage["dense"]), 100.0 * np.median(stage["dense"]) / np.median(roll)))
+            if by_frames:     # the two gray snapshots of a float call run inside its roll-out: the roll-out of each of the two, to hundredths
+                fine = lambda v: "%.2f (%.2f .. %.2f)" % (float(np.median(v)), min(v), max(v))
+                say("          device ms per generation: roll-out byte %s, float %s (two gray snapshots inside), difference of the medians %.3f; dense stage byte %s, float %s" % (
+                    spread(roll_of["corners"]), spread(roll_of["dense"]), np.median(roll_of["dense"]) - np.median(roll_of["corners"]), fine(stage["corners"]), fine(stage["dense"])))
+            else:
+                say("          device ms per generation: roll-out %s; %s %s; %s %s = %.1f %% of the roll-out" % (
+                    spread(roll), "flow + score" if solve == (1, 1) else "dense stage, single step", spread(stage["corners"]),
+                    "dense stage" if solve == (1, 1) else "dense stage, " + second, spread(stage["dense"]), 100.0 * np.median(stage["dense"]) / np.median(roll)))
             say("          agreement over the %d genomes: Spearman %.3f; scoring 0: %s %.1f %%, %s %.1f %%" % (
                 pop, spearman(fc, fd), first, 100.0 * float((fc == 0).mean()), second, 100.0 * float((fd == 0).mean())))
             if third:
@@ -154,6 +179,8 @@ def main():
         old = open(a.out).read()
         if NOTES_MARK in old:
             kept = old[old.index(NOTES_MARK):]
+        if a.append:
+            lines = (old[:old.index(NOTES_MARK)] if NOTES_MARK in old else old).rstrip("\n").split("\n") + [""] + lines
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n" + kept)
 

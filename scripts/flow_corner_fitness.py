@@ -8,6 +8,11 @@ iteration at a time; before each, one forward_backward call gives the loss, its 
 members per image; the fitness is the population path's, with the number of flow vectors it tracked.
 
     python scripts/flow_corner_fitness.py [--rows score,struct] [--timing] > profiles/flow_corner_fitness.txt
+    python scripts/flow_corner_fitness.py --rows score --structures 1 --pairings prediction --dense-fitness > profiles/dense_float_refine.txt
+
+--dense-fitness appends to every line the dense fitness of the same stills under the objective's own settings (the structure's score, radius 7, eps 1e-2, the
+structure as the mask, CornerMembers()), on the emitted bytes and on the float predictions (fitness.DenseFitness(frames="float"); DESIGN.md section 14,
+"Float frames"): whether the quantity that selects follows the loss that refinement climbs.
 """
 import argparse
 import os
@@ -35,6 +40,17 @@ def score(images, structure):
     return fit, [len(v) for v in vecs]
 
 
+def dense_scores(images, structure, mask):
+    """(byte, float): the dense fitness of the stills under corner members, on the emitted bytes and on the float predictions"""
+    eng = fitness.get_engine(MODEL, W, H, CH, max_batch=len(images))
+    d = torch.from_numpy(np.ascontiguousarray(images)).cuda()
+    out = []
+    for frames in ("byte", "float"):
+        dense = fitness.DenseFitness(train.structure_score(structure), radius=7, eps=1e-2, mask=mask, members=train.CornerMembers(), frames=frames)
+        out.append(eng.eval_images(d, len(images), structure, pairing=PAIR_POPULATION, dense=dense)[0])
+    return out
+
+
 def stills_of(structure, seed):
     config = synth.make_config(2, C_DIM)
     genomes = [g for _, g in synth.make_population(POP, config, seed=seed)]
@@ -49,7 +65,7 @@ def flow_of(structure, pairing, mask, members):
                            members=members)
 
 
-def run_row(structure, seed, iters, pairing, requant):
+def run_row(structure, seed, iters, pairing, requant, dense_fitness=False):
     stills, best = stills_of(structure, seed)
     mask = (fitness.leaf_planes(structure, W, H)[0] != -1).astype(np.uint8)
     flow = flow_of(structure, pairing, mask, train.CornerMembers())
@@ -67,7 +83,8 @@ def run_row(structure, seed, iters, pairing, requant):
             fit, nvec = score(img, structure)
             print("iter %2d loss %.6e terms %s | members %s | S_b %s | fitness %s mean %.6f | flow vectors %s" % (
                 i, loss, " ".join("%.6e" % v for v in terms[N_REPEAT - 1:]), rec[:, 0].astype(int).tolist(), " ".join("%.4f" % v for v in rec[:, 8]),
-                " ".join("%.6f" % v for v in fit), float(np.mean(fit)), nvec), flush=True)
+                " ".join("%.6f" % v for v in fit), float(np.mean(fit)), nvec) + ("" if not dense_fitness else " | dense fitness byte %s mean %.6f | float %s mean %.6f" % tuple(
+                    x for f in dense_scores(img, structure, mask) for x in (" ".join("%.6f" % v for v in f), float(np.mean(f))))), flush=True)
             if i < iters:
                 img, _ = train.refine_stills(tr, img, n_repeat=N_REPEAT, n_ext=N_EXT, iters=1, step=2.0, requant=requant, objective="flow", mask=mask, flow=flow)
 
@@ -103,12 +120,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="score,struct", help="which files' rows: score, struct, both, or none")
     ap.add_argument("--timing", action="store_true")
+    ap.add_argument("--structures", default="0,1,2,3", help="the rows of these structures only")
+    ap.add_argument("--pairings", default="frame,prediction")
+    ap.add_argument("--dense-fitness", action="store_true", help="append the byte and the float dense fitness (corner members) of the stills to every line")
     a = ap.parse_args()
+    structures, pairings = [int(v) for v in a.structures.split(",")], a.pairings.split(",")
     for name in [n for n in a.rows.split(",") if n in ROWS]:
         for requant in (True, False):
             for structure, seed, iters in ROWS[name]:
                 for pairing in ("frame", "prediction"):
-                    run_row(structure, seed, iters, pairing, requant)
+                    if structure in structures and pairing in pairings:
+                        run_row(structure, seed, iters, pairing, requant, a.dense_fitness)
     if a.timing:
         timing()
 
